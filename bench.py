@@ -1,12 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- the headline metric of BASELINE.json: Mray/s at 1920x1080, 8 spp on a Sponza-scale
-(~10 M-triangle) BVH, 1/2/4/8 GPUs, with the roofline of the trace kernel and the CPU path timed beside it.
+(~10 M-triangle) BVH, 1/2/4/8 GPUs, with the roofline of the trace kernel; with --full also the CPU path timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W [--mode tiles|samples]
+    python bench.py --gpus N --steps K --warmup W [--mode tiles|samples] [--dump-outputs DIR] [--full]
         one process drives all N GPUs through the library's own multi-GPU entry (mipt_render_multi_device: scene replicas, a host
         thread and an RCCL communicator per device, ONE ncclGather / ncclReduce per frame) -- the reference's single-process host model
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
         one process per GPU, collectives through torch.distributed (backend nccl = RCCL)
+
+A plain run sets the scene up, counts the rays of one frame, warms up, times the K steps and prints the JSON line (headline,
+configuration, and the roofline figures that follow from the counts and the timed steps).  --full adds the legs that take runs
+of their own: the other sharding mode (N > 1), the parity checks (oracle sample, un-culled traversal, single-GPU frame), the
+in-library mipt_render_multi leg (N = 1) and the CPU baseline; --no-other-mode / --no-parity / --no-render-multi /
+--no-cpu-baseline leave single legs out of a --full run.
+--dump-outputs DIR writes the frame of the last timed step as a caller receives it: DIR/hdr.npy (f32 radiance, h x w x 3) and
+DIR/rgba8.npy (the RGBA8 image as float32, h x w x 4); above 64 MB together, a fixed seeded sample of pixels of both plus
+DIR/pixel_index.npy (float64 row-major pixel indices).
 
 A "step" is one full frame of the hot path (scene replicated per GPU, inputs resident in HBM):
   --mode tiles (default; BASELINE config 4's split and the metric's configuration): every rank traces its share of the
@@ -14,7 +23,7 @@ A "step" is one full frame of the hot path (scene replicated per GPU, inputs res
       frame is assembled with ONE RCCL all-gather of the rank-packed tile slices plus a de-interleave kernel.
   --mode samples (BASELINE config 5's split): every rank traces ALL pixels for its share of the samples with the
       per-sample seeds of rt_compute.wgsl:102 into un-normalised sums; ONE RCCL sum-reduce to rank 0, then / spp.
-With N > 1 the line also carries the other mode's rate ("other_mode"): the tile split is floored by the reference's
+With N > 1 a --full line also carries the other mode's rate ("other_mode"): the tile split is floored by the reference's
 sequential per-pixel RNG chain, the sample split is not.
 A "ray" is one traverse_bvh invocation (reference src/renderer/backend/cpu/ray.rs:150); ray counts come from the kernel's
 counting build on the same inputs (deterministic), run outside the timed region.  Data is synthetic (no assets ship with
@@ -139,6 +148,24 @@ def log(rank, *a):
         print("[bench]", *a, file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(out_dir, hdr, rgba8):
+    """hdr (h, w, 3) f32 and rgba8 (h, w, 4) u8 of the last timed step -> out_dir/*.npy; the whole frame, or where that exceeds
+    DUMP_BYTES the same seeded pixel sample of both, with its indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_pix = hdr.shape[0] * hdr.shape[1]
+    out = {"hdr": hdr.astype(np.float32), "rgba8": rgba8.astype(np.float32)}
+    per_pixel, slack = 3 * 4 + 4 * 4, 3 * 4096                     # bytes per pixel of the two arrays; .npy headers
+    if n_pix * per_pixel > DUMP_BYTES - slack:
+        k = (DUMP_BYTES - slack) // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, size=k, replace=False))
+        out = {"hdr": out["hdr"].reshape(-1, 3)[idx], "rgba8": out["rgba8"].reshape(-1, 4)[idx], "pixel_index": idx.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,14 +182,19 @@ def main():
     ap.add_argument("--depth", type=int, default=64)
     ap.add_argument("--tex-size", type=int, default=1024)
     ap.add_argument("--traversal", choices=["culled", "reference"], default="culled")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: other sharding mode (N > 1), parity checks, mipt_render_multi (N = 1), CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame to DIR/*.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="target CPU time of the cpu_baseline sample (both thread counts together)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-other-mode", action="store_true", help="N > 1: skip the second (other sharding mode) measurement")
-    ap.add_argument("--no-render-multi", action="store_true", help="N = 1: skip the in-library mipt_render_multi (RCCL) leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity checks")
+    ap.add_argument("--no-other-mode", action="store_true", help="--full, N > 1: skip the second (other sharding mode) measurement")
+    ap.add_argument("--no-render-multi", action="store_true", help="--full, N = 1: skip the in-library mipt_render_multi (RCCL) leg")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = rehearsal of the N>1 code path on fewer GPUs than ranks (collectives staged through host memory)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner to fd 1 when a communicator is created (seen from
     # mipt_render_multi and torch.distributed alike), so fd 1 is pointed at stderr for the whole run and the JSON line is
@@ -249,12 +281,14 @@ def main():
     if single:
         for i in range(1, world):
             replica_ms.append(round(scene.info(lib.mipt_multi_scene(multi, i))["total_ms"], 1))
-    # for the oracle legs below (outside every timed region): the tree and the triangle order BVH::build leaves in the host's Scene
-    scene._fetch_bvh(first)
+    # for the --full legs below (outside every timed region): the tree and the triangle order BVH::build leaves in the host's Scene
+    if args.full:
+        scene._fetch_bvh(first)
     t3 = time.time()
-    log(rank, f"scene: {len(scene.tris)} tris, {len(scene.bvh_nodes)} nodes; gen {t1 - t0:.1f}s, setup call {t2 - t1:.3f}s "
-              f"(upload {setup_info['upload_ms']:.0f} ms, device bvh {setup_info['build_ms']:.1f} ms, device layout {setup_info['layout_ms']:.1f} ms), "
-              f"tree read-back for the oracle {t3 - t2:.2f}s" + (f" ({world} replicas, one process: {replica_ms} ms)" if single else ""))
+    log(rank, f"scene: {setup_info['n_tris']} tris, {setup_info['n_nodes']} nodes; gen {t1 - t0:.1f}s, setup call {t2 - t1:.3f}s "
+              f"(upload {setup_info['upload_ms']:.0f} ms, device bvh {setup_info['build_ms']:.1f} ms, device layout {setup_info['layout_ms']:.1f} ms)"
+              + (f", tree read-back for the oracle {t3 - t2:.2f}s" if args.full else "")
+              + (f" ({world} replicas, one process: {replica_ms} ms)" if single else ""))
 
     trav = L.TRAVERSAL_CULLED if args.traversal == "culled" else L.TRAVERSAL_REFERENCE
     cam_ptr = L.ptr(scene.camera.uniform)
@@ -386,7 +420,10 @@ def main():
     value = tot["rays"] * args.steps / elapsed / 1e6
     frame_primary = d_frame.clone()
     import zlib
-    frame_crc = zlib.crc32(frame_primary.cpu().numpy().tobytes()) & 0xFFFFFFFF     # identifies the frame across runs / launch models
+    frame_host = frame_primary.cpu().numpy()
+    frame_crc = zlib.crc32(frame_host.tobytes()) & 0xFFFFFFFF     # identifies the frame across runs / launch models
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame_host.reshape(h, w, 3), d_rgba.cpu().numpy().reshape(h, w, 4))
 
     # roofline of the dominant kernel (pt_trace_kernel): the launches of rank 0 (one process per GPU) / device 0 (one process)
     if single:
@@ -417,7 +454,7 @@ def main():
         "value": round(value, 3), "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"atrium stand-in for Intel Sponza + curtains: {len(scene.tris)} tris, {len(scene.bvh_nodes)} BVH nodes, "
+        "config": {"workload": f"atrium stand-in for Intel Sponza + curtains: {setup_info['n_tris']} tris, {setup_info['n_nodes']} BVH nodes, "
                                f"{w}x{h}, {spp} spp, max_ray_depth {depth}, whole frame incl. the sRGB + RGBA8 epilogue (cpu.rs:60-67), traversal {args.traversal}"
                                + (f" (margin {L.CULL_MARGIN_SAFE})" if args.traversal == "culled" else "") + f", {seeds}",
                    "mode": mode, "sharding": shard, "launch": "single-process" if single else ("torch.distributed.run" if world > 1 else "single-gpu"),
@@ -461,8 +498,8 @@ def main():
             "collective_ms": round(float(np.mean([st["collective_ms"] for st in steps_st])), 3),
             "call_wall_ms": round(float(np.mean([st["wall_ms"] for st in steps_st])), 3)}
 
-    # ---- N > 1: the other sharding mode, same steps (the tile split is floored by the per-pixel RNG chain; samples are not) ----
-    if world > 1 and not args.no_other_mode:
+    # ---- --full, N > 1: the other sharding mode, same steps (the tile split is floored by the per-pixel RNG chain; samples are not) ----
+    if args.full and world > 1 and not args.no_other_mode:
         other = "samples" if mode == "tiles" else "tiles"
         e2, tot2, _, st2 = measure(other)
         k2 = [st["device_kernel_ms"][0] for st in st2] if single else [st["kernel_ms"] for st in st2]
@@ -470,8 +507,8 @@ def main():
                                 "ms_per_step": round(e2 / args.steps * 1e3, 3), "rays_per_frame": tot2["rays"],
                                 "kernel_ms_rank0": round(float(np.mean(k2)), 3)}
 
-    # ---- parity evidence at the bench size (outside the timed region) ----
-    if rank == 0 and not args.no_parity:
+    # ---- --full: parity evidence at the bench size (outside the timed region) ----
+    if args.full and rank == 0 and not args.no_parity:
         par = {"against": "oracle/pt_oracle.c = C restatement of the rayon CPU backend incl. its libm (glibc 2.35 cosf/log10f/powf restated, "
                           "== the host's libm on all 2^32 arguments: tests/test_libm_pin.py)"}
         if single:
@@ -515,8 +552,8 @@ def main():
                                      "triangles host -> device once (staged through a pinned ring), BVH::build (bvh.rs:13-161) and the whole "
                                      "device layout in HBM; tree identical to mipt_bvh_build's, layout byte-identical to the host restatement in "
                                      "libmipt_diag.so (tests/test_gpu_scene_device.py, tests/test_gpu_fullsize.py); round 3: 0.44 s + 0.89 s"}
-    # ---- N = 1: the in-library multi-GPU path (mipt_render_multi: RCCL communicator + gather / reduce behind the C ABI) ----
-    if rank == 0 and world == 1 and not single and not args.no_render_multi:
+    # ---- --full, N = 1: the in-library multi-GPU path (mipt_render_multi: RCCL communicator + gather / reduce behind the C ABI) ----
+    if args.full and rank == 0 and world == 1 and not single and not args.no_render_multi:
         try:
             r = rrt.Renderer.new(rrt.RendererOptions(samples=spp, max_ray_depth=depth, output_image_dimensions=(w, h), output_image_path="/dev/null",
                                                      traversal=trav, cull_margin=L.CULL_MARGIN_SAFE))
@@ -529,8 +566,8 @@ def main():
         except Exception as e:  # noqa: BLE001  -- the leg is evidence, not the metric
             result["render_multi"] = {"error": str(e)[:200]}
 
-    # ---- CPU baseline: the oracle (C restatement of the rayon backend) on a strided pixel sample ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # ---- --full: CPU baseline: the oracle (C restatement of the rayon backend) on a strided pixel sample ----
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import orc
         mats_arr = scene.materials_array()
         seed_mode = 0 if mode == "tiles" else 1

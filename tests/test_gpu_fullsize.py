@@ -185,7 +185,7 @@ def test_config_M_culled_traversal_renders_the_reference_traversals_frame(rrt, a
     """The metric's configuration (1920x1080, 8 spp, depth 64) on the 10 M-triangle scene: the recommended arm -- best-hit culling with
     the 2^-7 relative margin (rt_compute.wgsl:341-349 + margin) -- must produce the frame of the CPU backend's own un-culled traversal
     (reference src/renderer/backend/cpu/ray.rs:69-81, the Renderer default), all 2 073 600 pixels bit for bit, while visiting fewer
-    nodes.  (bench.py re-checks the same identity on every run; INTEGRATION.md recommends the culled arm on this evidence.)"""
+    nodes.  (bench.py --full re-checks the same identity on every run; INTEGRATION.md recommends the culled arm on this evidence.)"""
     import torch
     from rust_ray_tracing_amd import _lib as L
     sc = atrium10m

@@ -192,15 +192,12 @@ def test_jpeg_decoder_matches_libjpeg_bit_for_bit(rrt, tmp_path, size):
 
 
 def test_jpeg_real_files_when_present(rrt):
-    """Camera-made JPEGs that ship with Python packages in this image (not with the reference): same bit-for-bit check."""
+    """Camera-made JPEGs (the sample images scikit-learn and matplotlib ship, stored as tests/golden/sample_*.jpg; not from
+    the reference): same bit-for-bit check."""
     pytest.importorskip("PIL.Image")
     import glob
-    files = []
-    for pat in ("/usr/local/lib/python3*/dist-packages/sklearn/datasets/images/*.jpg",
-                "/usr/local/lib/python3*/dist-packages/matplotlib/mpl-data/sample_data/*.jpg"):
-        files += sorted(glob.glob(pat))
-    if not files:
-        pytest.skip("no sample JPEGs on this machine")
+    files = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_*.jpg")))
+    assert len(files) == 3, files
     for f in files:
         t = rrt.Texture.load(f)
         assert t is not None, f
@@ -353,14 +350,14 @@ def test_png_every_colour_type_and_depth(rrt, tmp_path, interlace):
 
 
 def test_png_decoder_on_the_reference_gallery_images(rrt):
-    """The reference ships four 1920-wide gallery PNGs (README.md) -- real encoder output (adaptive filters, big deflate
-    streams) rather than this file's own writer.  Read in place as data (skipped where /root/reference is absent), decoded
-    by Texture::load's path and compared with Pillow's decoder."""
+    """The reference ships four 1920-wide gallery PNGs (README.md) -- real encoder output (adaptive filters, multi-chunk
+    deflate streams) rather than this file's own writer.  tests/golden/gallery_*.png hold a 24-row band of each with the
+    original rows' filter bytes and ancillary chunks (tests/golden/make_gallery_bands.py), decoded by Texture::load's path
+    and compared with Pillow's decoder."""
     Image = pytest.importorskip("PIL.Image")
     import glob
-    files = sorted(glob.glob("/root/reference/*.png"))
-    if not files:
-        pytest.skip("/root/reference is not present on this machine")
+    files = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gallery_*.png")))
+    assert len(files) == 4, files
     for f in files:
         t = rrt.Texture.load(f)
         assert t is not None, f
