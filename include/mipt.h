@@ -286,6 +286,60 @@ MIPT_API int  mipt_multi_root_device(const MiptMulti *multi);
  * MiptMultiStats.total sums the counters, this is one device's share (what its one launch did). */
 MIPT_API int  mipt_multi_device_stats(const MiptMulti *multi, int index, MiptStats *out);
 
+/* ---- updating the geometry of a resident scene ------------------------------------------------------------------------
+ * The reference's realtime loop mutates its Rc<RefCell<Scene>> (src/main.rs:46) and restarts progressive accumulation
+ * (window.rs:349-389); these calls swap new triangles into an existing scene (or MiptMulti) without re-uploading its materials,
+ * texel pool or workspace.  They add nothing to the frame itself: after a successful call the scene renders exactly as a scene
+ * created from the new geometry would (see each mode).
+ *
+ * Triangle order: `tris` holds the triangles in the order of the array the scene was last built from -- for mipt_scene_create the
+ * tree order the caller passed; for mipt_scene_create_from_triangles the caller's own order (the one mipt_scene_get_bvh's
+ * tri_order_out maps); after a REBUILD the order of that call's input.  So a caller keeps writing into its own mesh array and
+ * passes it again.  The array is read during the call only; it is neither kept nor modified.
+ *
+ * Errors are status codes with a message in mipt_last_error(), and in every case the scene renders exactly as before the call
+ * (everything is validated before anything resident is overwritten): a null argument, n_tris == 0 or a bad mode:
+ * MIPT_ERR_INVALID_ARG; a REFIT whose n_tris differs from the scene's: MIPT_ERR_INVALID_ARG; material_id >= n_materials:
+ * MIPT_ERR_INVALID_ARG; a bound that comes out non-finite or beyond 2^40: MIPT_ERR_SCENE_LIMIT (mipt_scene_create's rule); more
+ * than 2^25 triangles on REBUILD: MIPT_ERR_SCENE_LIMIT. */
+enum MiptUpdateMode {
+    MIPT_UPDATE_REFIT   = 0,  /* same tree topology, bounds recomputed from the new triangles.  n_tris must equal the scene's.  The
+                               * pair-record order and the triangle slots stay; every bound becomes what Node::grow_by_tri
+                               * (bvh.rs:185-193) folds over that node's triangles; both triangle streams are rewritten (material_ids
+                               * may change).  The layout equals mipt_scene_create's from the new triangles in tree order and the old
+                               * node array with refit bounds, byte for byte (sign of a zero in a bound aside), except that the pair
+                               * records keep the order of the original tree (a fresh layout orders its lower levels by child surface
+                               * area, which the new bounds may change).  A scene that keeps its
+                               * tree (mipt_scene_get_bvh) returns the refit node array afterwards.  The first REFIT of a tree groups
+                               * its pair records by depth and keeps that plan in HBM (8 bytes per record) until the tree changes. */
+    MIPT_UPDATE_REBUILD = 1   /* BVH::build on the GPU from the new triangles (the count may change): the scene becomes what
+                               * mipt_scene_create_from_triangles would have made from them -- the same layout bytes, mipt_scene_get_bvh
+                               * and MiptSceneInfo size fields, built_on_device = 1 -- and keeps its materials, textures and
+                               * workspace.  Works for scenes made either way. */
+};
+typedef struct {
+    double   upload_ms;       /* host -> device copy of the triangles (0 for the _device entry) */
+    double   build_ms;        /* device kernels of the refit / the build, HIP events */
+    double   layout_ms;       /* rewriting pair records + both triangle streams */
+    double   total_ms;        /* whole call, host clock */
+    uint32_t n_tris, n_nodes, n_pair_records, reserved;
+} MiptUpdateInfo;
+
+/* `tris` in host memory: staged into HBM of the scene's device, then the same device path as below.  info may be NULL. */
+MIPT_API int mipt_scene_update_triangles(MiptScene *scene, const MiptTriangle *tris, uint32_t n_tris,
+                                         uint32_t mode, MiptUpdateInfo *info);
+/* `d_tris` in HBM of the scene's device (e.g. a torch tensor); the triangles never cross PCIe and REBUILD builds straight from
+ * them.  Ordered after the earlier work of `hip_stream` (hipStream_t, NULL = the null stream); blocks until done, like
+ * mipt_render_device.  info may be NULL. */
+MIPT_API int mipt_scene_update_triangles_device(MiptScene *scene, const MiptTriangle *d_tris, uint32_t n_tris,
+                                                uint32_t mode, void *hip_stream, MiptUpdateInfo *info);
+/* Updates the root replica (device_ids[0]) from host `tris`, then refreshes every other replica by device-to-device copies (the
+ * mechanism of mipt_multi_create).  Handles returned by mipt_multi_scene stay valid.  On success mipt_render_multi* in both modes
+ * equals a single-GPU render of the updated scene.  An error in a replica refresh (MIPT_ERR_HIP) leaves the root updated: destroy
+ * the MiptMulti then. */
+MIPT_API int mipt_multi_update_triangles(MiptMulti *multi, const MiptTriangle *tris, uint32_t n_tris,
+                                         uint32_t mode, MiptUpdateInfo *info);
+
 /* ---- host-side restatements of the scene model that feeds the path ------------------- */
 
 /* BVH::build (src/bvh.rs:13-161): binned SAH, 8 bins; reorders `tris` in place exactly as

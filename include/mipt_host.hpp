@@ -9,6 +9,7 @@
 #pragma once
 #include "mipt.h"
 
+#include <cmath>
 #include <cstdio>
 #include <memory>
 #include <optional>
@@ -105,9 +106,40 @@ class Scene {                                              // src/scene.rs:12-19
 
     // Device residency for Renderer::render_node: the per-device replicas, streams and RCCL communicators (MiptMulti) are
     // created on first use and kept -- like the wgpu backend's State, built once in State::new (gpu.rs:96-118) -- so a
-    // second frame costs no upload and no ncclCommInitAll.  build_bvh() invalidates it; after editing the public tris / bvh_nodes /
-    // materials / textures directly call release_device() (the camera is passed per frame and needs no re-upload).
+    // second frame costs no upload and no ncclCommInitAll.  build_bvh() invalidates it.  After editing the public tris (positions,
+    // normals, uvs, material ids -- or the count, with MIPT_UPDATE_REBUILD) call update_device(): the replicas take the new
+    // geometry in place and keep materials, textures and communicators.  After editing bvh_nodes / materials / textures directly call
+    // release_device() (the camera is passed per frame and needs no re-upload).
     void release_device() const { multi_.reset(); multi_devices_ = -1; }
+    // mipt_multi_update_triangles from `tris` (in the order the replicas were built from: the tree order with bvh_nodes, else the
+    // caller's).  REFIT keeps the tree and refits bvh_nodes here too; REBUILD builds a new tree on the GPU, after which bvh_nodes is
+    // cleared (the scene is then one made from its triangles).  Without replicas there is nothing to update: the next render_node
+    // uploads the current arrays.  Returns a MiptStatus.
+    int update_device(uint32_t mode = MIPT_UPDATE_REFIT, MiptUpdateInfo *info = nullptr) {
+        if (multi_) {
+            const int rc = mipt_multi_update_triangles(multi_.get(), tris.data(), (uint32_t)tris.size(), mode, info);
+            if (rc != MIPT_OK) { log_error(mipt_last_error()); return rc; }
+        }
+        if (mode == MIPT_UPDATE_REBUILD) bvh_nodes.clear();
+        else refit_nodes();
+        return MIPT_OK;
+    }
+    // Node::grow_by_tri (bvh.rs:185-193) over every node's triangles, children before parents (BVH::build pushes them after it)
+    void refit_nodes() {
+        for (size_t i = bvh_nodes.size(); i-- > 0;) {
+            MiptNode &n = bvh_nodes[i];
+            float lo[3] = {3.40282347e38f, 3.40282347e38f, 3.40282347e38f}, hi[3] = {-3.40282347e38f, -3.40282347e38f, -3.40282347e38f};
+            auto grow = [&](const float *a, const float *b) { for (int k = 0; k < 3; k++) { lo[k] = std::fmin(lo[k], a[k]); hi[k] = std::fmax(hi[k], b[k]); } };
+            if (n.num_tris > 0) {
+                for (uint32_t t = n.first_tri_or_child; t < n.first_tri_or_child + n.num_tris; t++)
+                    for (const MiptVertex &v : tris[t].vertices) grow(&v.position.x, &v.position.x);
+            } else {
+                for (uint32_t c = n.first_tri_or_child; c < n.first_tri_or_child + 2; c++) grow(&bvh_nodes[c].bounds_min.x, &bvh_nodes[c].bounds_max.x);
+            }
+            n.bounds_min = {lo[0], lo[1], lo[2]};
+            n.bounds_max = {hi[0], hi[1], hi[2]};
+        }
+    }
     MiptMulti *node_handle(int n_devices) const {
         if (multi_ && multi_devices_ == n_devices) return multi_.get();
         release_device();

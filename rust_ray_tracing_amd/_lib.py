@@ -36,6 +36,7 @@ CULL_MARGIN_SAFE = 0.0078125  # MIPT_CULL_MARGIN_SAFE
 
 OK, ERR_INVALID_ARG, ERR_HIP, ERR_SCENE_LIMIT, ERR_BVH, ERR_IO, ERR_STACK, ERR_RCCL = 0, -1, -2, -3, -4, -5, -6, -7
 MULTI_TILES, MULTI_SAMPLES = 0, 1
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 
 
 class MiptTexture(C.Structure):
@@ -78,6 +79,14 @@ class MiptSceneInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MiptUpdateInfo(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("build_ms", C.c_double), ("layout_ms", C.c_double), ("total_ms", C.c_double),
+                ("n_tris", C.c_uint32), ("n_nodes", C.c_uint32), ("n_pair_records", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class MiptMultiStats(C.Structure):
     _fields_ = [("total", MiptStats), ("collective_ms", C.c_double), ("wall_ms", C.c_double),
                 ("device_kernel_ms", C.c_double * 8), ("n_devices", C.c_uint32), ("reserved", C.c_uint32)]
@@ -99,6 +108,7 @@ EXPORTS = [
     "mipt_multi_create", "mipt_multi_destroy", "mipt_multi_device_count", "mipt_render_multi",
     "mipt_render_multi_device", "mipt_multi_root_device", "mipt_multi_device_stats",
     "mipt_scene_create_from_triangles", "mipt_scene_get_bvh", "mipt_scene_info", "mipt_multi_create_from_triangles", "mipt_multi_scene", "mipt_obj_load_triangles",
+    "mipt_scene_update_triangles", "mipt_scene_update_triangles_device", "mipt_multi_update_triangles",
 ]
 
 _lib = None
@@ -193,6 +203,12 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_multi_create_from_triangles.restype = C.c_int
     lib.mipt_multi_scene.argtypes = [vp, C.c_int]
     lib.mipt_multi_scene.restype = vp
+    lib.mipt_scene_update_triangles.argtypes = [vp, vp, u32, u32, C.POINTER(MiptUpdateInfo)]
+    lib.mipt_scene_update_triangles.restype = C.c_int
+    lib.mipt_scene_update_triangles_device.argtypes = [vp, vp, u32, u32, vp, C.POINTER(MiptUpdateInfo)]
+    lib.mipt_scene_update_triangles_device.restype = C.c_int
+    lib.mipt_multi_update_triangles.argtypes = [vp, vp, u32, u32, C.POINTER(MiptUpdateInfo)]
+    lib.mipt_multi_update_triangles.restype = C.c_int
     return lib
 
 

@@ -62,7 +62,7 @@ void mipt::free_scene(MiptScene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
-                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched};
+                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);

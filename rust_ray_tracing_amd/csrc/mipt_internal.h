@@ -26,6 +26,13 @@ int scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptSc
 // the same with the caller's node array (ALREADY validated: mipt_scene_create's host checks) instead of a build; triangles in the tree's order
 int scene_create_from_nodes(const MiptSceneDesc *desc, int device_id, MiptScene **out);
 
+// ---- scene_update.hip, used by mipt_multi.cpp ----
+// mipt_scene_update_triangles without the exception fence
+int scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info);
+// dst := src's geometry by device-to-device copies (mipt_multi_update_triangles: the replicas after the root changed); a failed copy
+// leaves dst as it was
+int replica_refresh(const MiptScene *src, MiptScene *dst);
+
 // ---- mipt_api.cpp, used by mipt_multi.cpp ----
 // One scene on device_ids[0] -- from the caller's nodes or, with from_triangles, built on that device -- and device-to-device
 // replicas on the others.

@@ -339,6 +339,20 @@ int mipt_multi_create_from_triangles(const MiptSceneDesc *desc, const int *devic
     catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
 }
 
+// The root replica from the host array (the one path of mipt_scene_update_triangles), then every other replica by device-to-device copies
+int mipt_multi_update_triangles(MiptMulti *m, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info) {
+    if (!m) return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_update_triangles: null argument");
+    try {
+        int rc = mipt::scene_update_host(m->scenes[0], tris, n_tris, mode, info);
+        for (int i = 1; i < m->n && rc == MIPT_OK; i++)
+            if ((rc = mipt::replica_refresh(m->scenes[0], m->scenes[(size_t)i])))
+                rc = fail(rc, "mipt_multi_update_triangles: the root is updated but the replica on device " + std::to_string(m->devices[(size_t)i]) + " is not: " + mipt_last_error());
+        return rc;
+    }
+    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
+    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+}
+
 MiptScene *mipt_multi_scene(MiptMulti *m, int index) { return (m && index >= 0 && index < m->n) ? m->scenes[(size_t)index] : nullptr; }
 
 void mipt_multi_destroy(MiptMulti *m) { destroy(m); }

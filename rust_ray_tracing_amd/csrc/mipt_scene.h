@@ -33,6 +33,11 @@ struct MiptScene {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int n_cu = 0;
     uint32_t max_leaf = 0;
+    // REFIT plan of mipt_scene_update_triangles (scene_update.hip), made on the first REFIT and kept until the tree changes: the
+    // pair records grouped by depth (record indices, level after level from the root) and, for a scene that keeps its tree
+    // (d_nodes), the reference pair index of every record
+    uint32_t *d_refit_plan = nullptr, *d_refit_pair = nullptr;
+    std::vector<uint32_t> refit_level_off;  // level d = plan[off[d], off[d+1]); empty = no plan yet
 };
 
 namespace mipt {
@@ -71,6 +76,31 @@ struct ResidentBvh {
     double build_ms = 0.0;                // HIP events around the build kernels
 };
 int bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int device_id, ResidentBvh *out);
-void bvh_builder_resolve_kernels();         // optional: what the first launch of each builder kernel would pay, up front (call with the device set)
+void bvh_builder_resolve_kernels();
+
+// The geometry half of a device-built scene (scene_device.hip): the tree and the layout kernels, from triangles already in HBM --
+// what mipt_scene_create_from_triangles / mipt_scene_create run after their upload, and what REBUILD runs on a live scene.
+struct SceneGeometry {
+    void *d_geom = nullptr, *d_tri_attr = nullptr;
+    size_t geom_alloc = 0, attr_bytes = 0, pairs_bytes = 0, pos_bytes = 0;
+    MiptNode *d_nodes = nullptr;            // the tree and the triangle permutation (BVH::build only; host nodes: null)
+    uint32_t *d_tri_order = nullptr;
+    uint32_t n_tris = 0, n_nodes = 0, n_records_padded = 0, max_leaf = 0, tiny_axes = 0, root_a = 0, root_n = 0;
+    double build_ms = 0.0, t_build = 0.0;
+};
+// `bvh` in: with host_nodes, the caller's (validated) node array already in HBM (freed here on success); else filled by the build.
+// No scene is touched; on failure everything allocated here is freed and bvh's arrays are left to the caller.
+int build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n_materials, int device_id, bool host_nodes, ResidentBvh *bvh,
+                   SceneGeometry *out);
+void free_geometry(SceneGeometry *g);
+// moves g's buffers into s (whose own geometry must be freed or moved out first) and sets dev / info geometry fields
+void attach_geometry(MiptScene *s, SceneGeometry *g);
+// the geometry, tree and refit plan of `s` (not its materials or workspace) freed; the MIPT_FLAG_TOUCHED bitmap too (sized by geometry)
+void release_geometry(MiptScene *s);
+// host -> device copy of a large pageable array through a ring of pinned buffers (scene_device.hip); blocks until it has arrived
+int upload_staged(void *d_dst, const void *h_src, size_t bytes);
+// mipt_scene_update_triangles_device without the exception fence (scene_update.hip; the host entry: mipt_internal.h)
+int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info);
+         // optional: what the first launch of each builder kernel would pay, up front (call with the device set)
 
 } // namespace mipt

@@ -375,57 +375,21 @@ class StagedUploader {
 
 } // namespace
 
-// Both ways in end here.  `host_nodes`: the caller's node array (validated by mipt_scene_create, mipt_api.cpp) is uploaded beside the
-// triangles, which are in the tree's order already; else BVH::build runs on the GPU.  The layout kernels are the same.
-static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_nodes, MiptScene **out) {
-    if (!desc || !out) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_create_from_triangles: null argument");
-    *out = nullptr;
-    if (!desc->tris || desc->n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
-    if (desc->n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(desc->n_tris) + " triangles exceed the 2^25 device-format limit");
-    if (host_nodes && (!desc->nodes || (desc->n_nodes & 1u) == 0u)) return fail(MIPT_ERR_BVH, "scene has no BVH nodes, or an even number of them");
-    const double t_begin = now_ms();
-    mipt::MaterialTables tables;
-    { const int rc = mipt::build_material_tables(desc, &tables, false); if (rc) return rc; }     // the textures are staged below, not gathered on the host
-    const uint32_t n_tris = desc->n_tris;
-
-    int ndev = 0;
-    {
-        const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("hipGetDeviceCount failed: ") + hipGetErrorString(e));
-        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device " + std::to_string(device_id) + " not available (" + std::to_string(ndev) + " visible)");
-    }
-    MiptTriangle *d_tris = nullptr;
-    mipt::ResidentBvh bvh;
+// The geometry half of both ways in (and of mipt_scene_update_triangles' REBUILD): the tree -- BVH::build in HBM, or the caller's node
+// array already uploaded to bvh->d_nodes (host_nodes) -- and the layout kernels, from triangles that are already in HBM.  Nothing of a
+// scene is touched: on success `g` owns the new geometry (and, unless host_nodes, the tree); on failure everything made here is freed.
+int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n_materials, int device_id, bool host_nodes, ResidentBvh *bvh_io,
+                         SceneGeometry *g) {
+    mipt::ResidentBvh &bvh = *bvh_io;
     char *arena = nullptr;
-    MiptScene *s = nullptr;
-    StagedUploader up_ring;
+    SceneGeometry out;
     auto cleanup = [&]() {
-        up_ring.shut();
-        if (d_tris) (void)hipFree(d_tris);
-        if (bvh.d_nodes) (void)hipFree(bvh.d_nodes);
-        if (bvh.d_tri_order) (void)hipFree(bvh.d_tri_order);
         if (arena) (void)hipFree(arena);
-        if (s) mipt::free_scene(s);
+        mipt::free_geometry(&out);
     };
-    S_HIP(hipSetDevice(device_id));
-    // ---- 1. the one host -> device copy ----
-    S_HIP(hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
-    if (host_nodes) S_HIP(hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
-    {
-        std::thread warm;
-        if (!host_nodes) warm = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
-        int rc = up_ring.copy(d_tris, desc->tris, (size_t)n_tris * sizeof(MiptTriangle));
-        if (rc == MIPT_OK && host_nodes) rc = up_ring.copy(bvh.d_nodes, desc->nodes, (size_t)desc->n_nodes * sizeof(MiptNode));
-        if (rc == MIPT_OK) rc = up_ring.finish();
-        if (warm.joinable()) warm.join();
-        up_ring.pause();                                      // back for the textures, after the build
-        if (rc) { cleanup(); return rc; }
-    }
-    const double t_up = now_ms();
     // ---- 2. BVH::build in HBM (or the caller's tree) ----
-    if (host_nodes) bvh.n_nodes = desc->n_nodes;
-    else { const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &bvh); if (rc) { cleanup(); return rc; } }
-    const double t_build = now_ms();
+    if (!host_nodes) { const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &bvh); if (rc) { cleanup(); return rc; } }
+    out.t_build = now_ms();
     const uint32_t n_nodes = bvh.n_nodes;
     if ((n_nodes & 1u) == 0u) { cleanup(); return fail(MIPT_ERR_BVH, "device builder returned an even node count"); }
     const uint32_t n_pairs = (n_nodes - 1u) / 2u;
@@ -486,18 +450,15 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     const size_t pairs_bytes = (size_t)n_records_padded * 64, pos_bytes = (size_t)n_tris * 64 + 16;
     if (pairs_bytes + pos_bytes >= 0xffffffffull) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "BVH + triangle stream exceed 4 GiB"); }
 
-    s = new (std::nothrow) MiptScene();
-    if (!s) { cleanup(); return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
-    s->device = device_id;
-    s->n_tris = n_tris;
-    s->geom_alloc = pairs_bytes + pos_bytes + 64;
-    s->attr_bytes = (size_t)n_tris * 64;
-    S_HIP(hipMalloc(&s->d_geom, s->geom_alloc));
-    S_HIP(hipMalloc(&s->d_tri_attr, s->attr_bytes));
-    float4 *d_pairs = (float4 *)s->d_geom, *d_pos = (float4 *)((char *)s->d_geom + pairs_bytes);
+    out.n_tris = n_tris;
+    out.geom_alloc = pairs_bytes + pos_bytes + 64;
+    out.attr_bytes = (size_t)n_tris * 64;
+    S_HIP(hipMalloc(&out.d_geom, out.geom_alloc));
+    S_HIP(hipMalloc(&out.d_tri_attr, out.attr_bytes));
+    float4 *d_pairs = (float4 *)out.d_geom, *d_pos = (float4 *)((char *)out.d_geom + pairs_bytes);
     if (n_records) hipLaunchKernelGGL(write_new_of, dim3(2048), dim3(kT), 0, st, order, n_records, new_of);
     if (n_records_padded) hipLaunchKernelGGL(write_pairs, dim3(2048), dim3(kT), 0, st, bvh.d_nodes, order, n_records, n_records_padded, new_of, slot, d_pairs);
-    hipLaunchKernelGGL(write_tris, dim3(4096), dim3(kT), 0, st, d_tris, bvh.d_tri_order, n_tris, desc->n_materials, slot, d_pos, (float4 *)s->d_tri_attr, ctl);
+    hipLaunchKernelGGL(write_tris, dim3(4096), dim3(kT), 0, st, d_tris, bvh.d_tri_order, n_tris, n_materials, slot, d_pos, (float4 *)out.d_tri_attr, ctl);
     S_HIP(hipGetLastError());
     MiptNode root;
     uint32_t root_slot = 0;
@@ -506,22 +467,117 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     S_HIP(hipStreamSynchronize(st));
     if (hctl.bad_tri != 0xffffffffu) {
         cleanup();
-        return fail(MIPT_ERR_INVALID_ARG, host_nodes ? "triangle " + std::to_string(hctl.bad_tri) + " has material_id >= n_materials " + std::to_string(desc->n_materials)
-                                                     : "a triangle has material_id >= n_materials " + std::to_string(desc->n_materials) + " (position " + std::to_string(hctl.bad_tri) + " of the BVH order)");
+        return fail(MIPT_ERR_INVALID_ARG, host_nodes ? "triangle " + std::to_string(hctl.bad_tri) + " has material_id >= n_materials " + std::to_string(n_materials)
+                                                     : "a triangle has material_id >= n_materials " + std::to_string(n_materials) + " (position " + std::to_string(hctl.bad_tri) + " of the BVH order)");
     }
     if (root.num_tris > 0u) S_HIP(hipMemcpy(&root_slot, slot + root.first_tri_or_child, 4, hipMemcpyDeviceToHost));
     else if (root.first_tri_or_child != 1u) { cleanup(); return fail(MIPT_ERR_BVH, "root's children must be nodes 1 and 2 (bvh.rs:121)"); }
     (void)hipFree(arena); arena = nullptr;
-    (void)hipFree(d_tris); d_tris = nullptr;
-    const double t_layout = now_ms();
 
-    s->max_leaf = hctl.max_leaf;
-    s->n_nodes = n_nodes;
+    out.max_leaf = hctl.max_leaf;
+    out.tiny_axes = hctl.tiny_axes;
+    out.n_nodes = n_nodes;
+    out.n_records_padded = n_records_padded;
+    out.pairs_bytes = pairs_bytes; out.pos_bytes = pos_bytes;
+    out.root_a = root.num_tris > 0u ? root_slot : 0u;
+    out.root_n = root.num_tris;
+    out.build_ms = host_nodes ? 0.0 : bvh.build_ms;
     if (host_nodes) { (void)hipFree(bvh.d_nodes); bvh.d_nodes = nullptr; }          // the caller has them
     else {                                                                           // kept for mipt_scene_get_bvh
-        s->d_nodes = bvh.d_nodes; bvh.d_nodes = nullptr;
-        s->d_tri_order = bvh.d_tri_order; bvh.d_tri_order = nullptr;
+        out.d_nodes = bvh.d_nodes; bvh.d_nodes = nullptr;
+        out.d_tri_order = bvh.d_tri_order; bvh.d_tri_order = nullptr;
     }
+    *g = out;
+    out = SceneGeometry();
+    return MIPT_OK;
+}
+
+void mipt::free_geometry(SceneGeometry *g) {
+    void *ptrs[] = {g->d_geom, g->d_tri_attr, g->d_nodes, g->d_tri_order};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    *g = SceneGeometry();
+}
+
+void mipt::attach_geometry(MiptScene *s, SceneGeometry *g) {
+    s->n_tris = g->n_tris;
+    s->geom_alloc = g->geom_alloc; s->attr_bytes = g->attr_bytes;
+    s->d_geom = g->d_geom; s->d_tri_attr = g->d_tri_attr;
+    s->d_nodes = g->d_nodes; s->d_tri_order = g->d_tri_order;
+    s->max_leaf = g->max_leaf;
+    s->n_nodes = g->n_nodes;
+    s->dev.pairs = (const float4 *)s->d_geom;
+    s->dev.tri_pos = (const float4 *)((const char *)s->d_geom + g->pairs_bytes);
+    s->dev.tri_off_bytes = (uint32_t)g->pairs_bytes;
+    s->dev.geom_bytes = (uint32_t)(g->pairs_bytes + g->pos_bytes);
+    s->dev.tiny_axes = g->tiny_axes;
+    s->dev.tri_attr = (const float4 *)s->d_tri_attr;
+    s->dev.n_pairs = g->n_records_padded; s->dev.n_tris = g->n_tris;
+    s->dev.root_a = g->root_a;
+    s->dev.root_n = g->root_n;
+    s->info.n_tris = g->n_tris; s->info.n_nodes = g->n_nodes; s->info.n_pair_records = g->n_records_padded; s->info.max_leaf = g->max_leaf;
+    s->info.geometry_bytes = (uint64_t)g->pairs_bytes + g->pos_bytes + g->attr_bytes;
+    *g = SceneGeometry();
+}
+
+// Both ways in end here.  `host_nodes`: the caller's node array (validated by mipt_scene_create, mipt_api.cpp) is uploaded beside the
+// triangles, which are in the tree's order already; else BVH::build runs on the GPU.  The layout kernels are the same.
+static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_nodes, MiptScene **out) {
+    if (!desc || !out) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_create_from_triangles: null argument");
+    *out = nullptr;
+    if (!desc->tris || desc->n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
+    if (desc->n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(desc->n_tris) + " triangles exceed the 2^25 device-format limit");
+    if (host_nodes && (!desc->nodes || (desc->n_nodes & 1u) == 0u)) return fail(MIPT_ERR_BVH, "scene has no BVH nodes, or an even number of them");
+    const double t_begin = now_ms();
+    mipt::MaterialTables tables;
+    { const int rc = mipt::build_material_tables(desc, &tables, false); if (rc) return rc; }     // the textures are staged below, not gathered on the host
+    const uint32_t n_tris = desc->n_tris;
+
+    int ndev = 0;
+    {
+        const hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("hipGetDeviceCount failed: ") + hipGetErrorString(e));
+        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device " + std::to_string(device_id) + " not available (" + std::to_string(ndev) + " visible)");
+    }
+    MiptTriangle *d_tris = nullptr;
+    mipt::ResidentBvh bvh;
+    mipt::SceneGeometry geo;
+    MiptScene *s = nullptr;
+    StagedUploader up_ring;
+    auto cleanup = [&]() {
+        up_ring.shut();
+        if (d_tris) (void)hipFree(d_tris);
+        if (bvh.d_nodes) (void)hipFree(bvh.d_nodes);
+        if (bvh.d_tri_order) (void)hipFree(bvh.d_tri_order);
+        mipt::free_geometry(&geo);
+        if (s) mipt::free_scene(s);
+    };
+    S_HIP(hipSetDevice(device_id));
+    // ---- 1. the one host -> device copy ----
+    S_HIP(hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
+    if (host_nodes) S_HIP(hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
+    {
+        std::thread warm;
+        if (!host_nodes) warm = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
+        int rc = up_ring.copy(d_tris, desc->tris, (size_t)n_tris * sizeof(MiptTriangle));
+        if (rc == MIPT_OK && host_nodes) rc = up_ring.copy(bvh.d_nodes, desc->nodes, (size_t)desc->n_nodes * sizeof(MiptNode));
+        if (rc == MIPT_OK) rc = up_ring.finish();
+        if (warm.joinable()) warm.join();
+        up_ring.pause();                                      // back for the textures, after the build
+        if (rc) { cleanup(); return rc; }
+    }
+    const double t_up = now_ms();
+    if (host_nodes) bvh.n_nodes = desc->n_nodes;
+    // ---- 2. + 3. the tree and the layout, from the triangles in HBM ----
+    { const int rc = mipt::build_geometry(d_tris, n_tris, desc->n_materials, device_id, host_nodes, &bvh, &geo); if (rc) { cleanup(); return rc; } }
+    (void)hipFree(d_tris); d_tris = nullptr;
+    const double t_build = geo.t_build, t_layout = now_ms();
+
+    s = new (std::nothrow) MiptScene();
+    if (!s) { cleanup(); return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
+    s->device = device_id;
+    const double build_ms = geo.build_ms;
+    mipt::attach_geometry(s, &geo);
     {   // materials + the texel pool; the textures go through the same pinned ring, straight from the caller's buffers
         int rc = mipt::upload_material_tables(s, tables);
         for (uint32_t i = 0; i < desc->n_textures && rc == MIPT_OK; i++)
@@ -531,26 +587,25 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
         if (rc) { cleanup(); return rc; }
     }
     { const int rc = mipt::scene_finish_workspace(s); if (rc) { cleanup(); return rc; } }
-    s->dev.pairs = d_pairs;
-    s->dev.tri_pos = d_pos;
-    s->dev.tri_off_bytes = (uint32_t)pairs_bytes;
-    s->dev.geom_bytes = (uint32_t)(pairs_bytes + pos_bytes);
-    s->dev.tiny_axes = hctl.tiny_axes;
-    s->dev.tri_attr = (const float4 *)s->d_tri_attr;
-    s->dev.n_pairs = n_records_padded; s->dev.n_tris = n_tris; s->dev.n_mats = desc->n_materials; s->dev.n_texs = desc->n_textures;
-    s->dev.root_a = root.num_tris > 0u ? root_slot : 0u;
-    s->dev.root_n = root.num_tris;
+    s->dev.n_mats = desc->n_materials; s->dev.n_texs = desc->n_textures;
     const double t_end = now_ms();
-    s->info.n_tris = n_tris; s->info.n_nodes = n_nodes; s->info.n_pair_records = n_records_padded; s->info.max_leaf = hctl.max_leaf;
-    s->info.geometry_bytes = (uint64_t)pairs_bytes + pos_bytes + s->attr_bytes;
     s->info.built_on_device = host_nodes ? 0u : 1u;
     s->info.upload_ms = (t_up - t_begin) + (t_end - t_layout);
-    s->info.build_ms = host_nodes ? 0.0 : bvh.build_ms;
+    s->info.build_ms = build_ms;
     s->info.layout_ms = t_layout - t_build;
     s->info.total_ms = t_end - t_begin;
     *out = s;
     s = nullptr;
     return MIPT_OK;
+}
+
+// one host -> device copy through the pinned ring (the host entry of mipt_scene_update_triangles); the current device is the target's
+int mipt::upload_staged(void *d_dst, const void *h_src, size_t bytes) {
+    StagedUploader up_ring;
+    int rc = up_ring.copy(d_dst, h_src, bytes);
+    if (rc == MIPT_OK) rc = up_ring.finish();
+    up_ring.shut();
+    return rc;
 }
 
 int mipt::scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptScene **out) { return create_on_device(desc, device_id, false, out); }

@@ -114,6 +114,7 @@ class Scene:  # scene.rs:12-19
         self.camera = Camera()
         self._handle: Optional[C.c_void_p] = None
         self._handle_device = -1
+        self._tri_order: Optional[np.ndarray] = None   # fetch_bvh: tris = (the device's input order)[_tri_order]
 
     # -- construction ------------------------------------------------------------------------
     @staticmethod
@@ -165,6 +166,7 @@ class Scene:  # scene.rs:12-19
         count = C.c_uint32(0)
         L.check(L.load().mipt_bvh_build(L.ptr(self.tris), n, L.ptr(nodes), len(nodes), C.byref(count), threads), "mipt_bvh_build")
         self.bvh_nodes = nodes[: count.value].copy()
+        self._tri_order = None
         self.release()
 
     def build_bvh_device(self, device_id: int = 0) -> float:
@@ -176,6 +178,7 @@ class Scene:  # scene.rs:12-19
         L.check(L.load().mipt_bvh_build_device(L.ptr(self.tris), n, L.ptr(nodes), len(nodes), C.byref(count), device_id, C.byref(ms)),
                 "mipt_bvh_build_device")
         self.bvh_nodes = nodes[: count.value].copy()
+        self._tri_order = None
         self.release()
         return ms.value
 
@@ -202,6 +205,7 @@ class Scene:  # scene.rs:12-19
         if self._handle is not None and self._handle_device == device_id:
             return self._handle
         self.release()
+        self._tri_order = None
         h = C.c_void_p()
         d = self.desc()
         L.check(L.load().mipt_scene_create(C.byref(d), device_id, C.byref(h)), "mipt_scene_create")
@@ -238,6 +242,7 @@ class Scene:  # scene.rs:12-19
         scene's triangles go up in their current order, the tree is built and laid out in HBM.  With ``fetch_bvh`` the Scene is
         left as BVH::build leaves the reference's (bvh.rs:13-54): ``bvh_nodes`` filled and ``tris`` reordered."""
         self.release()
+        self._tri_order = None
         h = C.c_void_p()
         d = self.desc()
         lib = L.load()
@@ -255,6 +260,46 @@ class Scene:  # scene.rs:12-19
         L.check(L.load().mipt_scene_get_bvh(handle, L.ptr(nodes), len(nodes), C.byref(count), L.ptr(order)), "mipt_scene_get_bvh")
         self.bvh_nodes = nodes[: count.value].copy()
         self.tris = self.tris[order]
+        self._tri_order = order
+
+    def update_device(self, mode: int = L.UPDATE_REFIT) -> dict:
+        """New geometry for the resident scene (mipt_scene_update_triangles) and/or its multi-GPU handle (mipt_multi_update_triangles)
+        from ``self.tris`` after the caller edited them -- materials, textures and workspace stay in HBM.  REFIT keeps the tree and
+        recomputes its bounds; REBUILD runs BVH::build on the GPU.  The device wants the order of the array it was last built from:
+        when ``fetch_bvh`` reordered ``self.tris`` into the tree's order, they are scattered back first.  Afterwards ``bvh_nodes``
+        (and, after a REBUILD of a scene that has a tree here, ``tris``) describe the scene on the device again.  Returns
+        MiptUpdateInfo as a dict (of the last handle updated)."""
+        multi = getattr(self, "_multi", None)
+        if self._handle is None and multi is None:
+            raise RuntimeError("scene is not resident on a device")
+        src = self.tris
+        if self._tri_order is not None:
+            src = np.empty_like(self.tris)
+            src[self._tri_order] = self.tris
+        src = np.ascontiguousarray(src, dtype=L.TRIANGLE)
+        lib = L.load()
+        info = L.MiptUpdateInfo()
+        if self._handle is not None:
+            L.check(lib.mipt_scene_update_triangles(self._handle, L.ptr(src), len(src), mode, C.byref(info)), "mipt_scene_update_triangles")
+        if multi is not None:
+            L.check(lib.mipt_multi_update_triangles(multi, L.ptr(src), len(src), mode, C.byref(info)), "mipt_multi_update_triangles")
+        h = self._handle if self._handle is not None else lib.mipt_multi_scene(multi, 0)
+        had_tree = len(self.bvh_nodes) > 0
+        if mode == L.UPDATE_REBUILD:
+            self.tris, self._tri_order = src, None
+            if had_tree:
+                self._fetch_bvh(h)                                     # the new tree, tris in its order
+        elif self._tri_order is not None:
+            self._fetch_nodes(h)                                       # the refit bounds
+        elif had_tree:
+            self.bvh_nodes = refit_nodes(self.bvh_nodes, self.tris)    # a host-built tree: the same fold on the host
+        return info.as_dict()
+
+    def _fetch_nodes(self, handle) -> None:
+        nodes = np.zeros(len(self.bvh_nodes), dtype=L.NODE)
+        count = C.c_uint32(0)
+        L.check(L.load().mipt_scene_get_bvh(handle, L.ptr(nodes), len(nodes), C.byref(count), None), "mipt_scene_get_bvh")
+        self.bvh_nodes = nodes[: count.value].copy()
 
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
@@ -285,6 +330,8 @@ class Scene:  # scene.rs:12-19
             self._multi = None
         h = C.c_void_p()
         d = self.desc()
+        if self._handle is None:
+            self._tri_order = None                                     # the replicas are built from tris as they are now
         ids = None if device_ids is None else (C.c_int * len(device_ids))(*device_ids)
         lib = L.load()
         if from_triangles:
@@ -301,6 +348,36 @@ class Scene:  # scene.rs:12-19
             self.release()
         except Exception:
             pass
+
+
+def refit_nodes(nodes: np.ndarray, tris: np.ndarray) -> np.ndarray:
+    """The REFIT of mipt_scene_update_triangles on the host: `nodes` with every bound re-folded by Node::grow_by_tri (bvh.rs:185-193)
+    over the node's triangles (`tris` in the tree's order) -- leaves over their range, inner nodes as the union of their children,
+    deepest level first.  f32 min/max ignore a NaN coordinate, as f32::min / f32::max do."""
+    out = nodes.copy()
+    big = np.float32(3.4028235e38)
+    pos = np.asarray(tris["vertices"]["position"], dtype=np.float32)
+    lo = np.fmin(np.fmin.reduce(pos, axis=1), big)                 # per triangle, from Node::default's +-f32::MAX
+    hi = np.fmax(np.fmax.reduce(pos, axis=1), -big)
+    leaf = np.flatnonzero(out["num_tris"] > 0)
+    if len(leaf):
+        f, n = out["first_tri_or_child"][leaf].astype(np.int64), out["num_tris"][leaf].astype(np.int64)
+        lo_s, hi_s = np.vstack([lo, np.full((1, 3), big, np.float32)]), np.vstack([hi, np.full((1, 3), -big, np.float32)])
+        idx = np.stack([f, f + n], axis=1).ravel()
+        out["bounds_min"][leaf] = np.fmin.reduceat(lo_s, idx, axis=0)[::2]
+        out["bounds_max"][leaf] = np.fmax.reduceat(hi_s, idx, axis=0)[::2]
+    levels, cur = [], np.array([0], dtype=np.int64)              # inner nodes by depth, from the root
+    while len(cur):
+        inner = cur[out["num_tris"][cur] == 0]
+        if len(inner):
+            levels.append(inner)
+        c = out["first_tri_or_child"][inner].astype(np.int64)
+        cur = np.concatenate([c, c + 1])
+    for inner in reversed(levels):
+        c = out["first_tri_or_child"][inner].astype(np.int64)
+        out["bounds_min"][inner] = np.fmin(out["bounds_min"][c], out["bounds_min"][c + 1])
+        out["bounds_max"][inner] = np.fmax(out["bounds_max"][c], out["bounds_max"][c + 1])
+    return out
 
 
 def make_options(width, height, samples, max_ray_depth, seed_mode=L.SEED_PIXEL_STREAM, traversal=L.TRAVERSAL_REFERENCE,
