@@ -216,6 +216,31 @@ MIPT_API int mipt_render(MiptScene *scene, const MiptCamera *camera, const MiptO
 MIPT_API int mipt_render_device(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
                        float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats);
 
+/* ---- many views of one scene in one launch ------------------------------------------------------------------------------
+ * Renders n_views cameras of the same scene with the same options in ONE trace launch whose work queue runs over (view, tile,
+ * pixel), so a batch of small views fills the GPU the way one large frame does.  Pixel seeds depend on the pixel position and the
+ * sample number only (cpu.rs:28-29, rt_compute.wgsl:102), never on the launch: every view comes out bit-identical to a single render.
+ *   cameras : n_views cameras in HOST memory, read during the call only.
+ *   opt     : applies to every view; the per-frame rules of mipt_render apply per view.  tile_world must be 0 or 1 and
+ *             MIPT_FLAG_PACKED is refused (a batch is not tile-sharded); MIPT_FLAG_SUM, MIPT_FLAG_ACCUM (device entry only),
+ *             sample_begin, MIPT_FLAG_COUNT and MIPT_FLAG_TOUCHED work as in the single-view calls.
+ *   output  : view-major.  View v occupies hdr[v*W*H*3 .. (v+1)*W*H*3) and rgba8[v*W*H*4 .. (v+1)*W*H*4) (W, H = opt->width,
+ *             opt->height); each slice holds exactly the bytes mipt_render / mipt_render_device writes for cameras[v] with the same
+ *             opt, in both seed modes, both traversal modes and both shading modes.  mipt_tonemap_device / mipt_postprocess_device
+ *             over n_views*W*H pixels give the per-view results of the whole batch.
+ *   limit   : n_views*W*H < MIPT_BATCH_MAX_PIXELS (2^32), else MIPT_ERR_INVALID_ARG.
+ *   stats   : the one launch: kernel_ms is its HIP-event time, the counters are summed over the views (max_stack: the maximum),
+ *             pixels = n_views*W*H.
+ * Every argument is checked before any device work; errors set mipt_last_error(), and the scene renders as before afterwards.
+ * MIPT_ERR_STACK is reported after the frame is written, as by mipt_render. */
+#define MIPT_BATCH_MAX_PIXELS 4294967296ull
+MIPT_API int mipt_render_batch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                               float *hdr_rgb, uint8_t *rgba8, MiptStats *stats);
+/* Same, into DEVICE buffers (d_hdr_rgb: n_views*W*H*3 f32, required; d_rgba8: n_views*W*H*4 bytes, may be NULL) on `hip_stream`
+ * (may be NULL); the camera table is copied on that stream.  Blocks until the kernel has finished (stats are read back). */
+MIPT_API int mipt_render_batch_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                      float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats);
+
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);
 /* d_packed_all: tile_world slices of mipt_packed_pixels()*3 floats, rank-major (the layout an

@@ -109,6 +109,7 @@ EXPORTS = [
     "mipt_render_multi_device", "mipt_multi_root_device", "mipt_multi_device_stats",
     "mipt_scene_create_from_triangles", "mipt_scene_get_bvh", "mipt_scene_info", "mipt_multi_create_from_triangles", "mipt_multi_scene", "mipt_obj_load_triangles",
     "mipt_scene_update_triangles", "mipt_scene_update_triangles_device", "mipt_multi_update_triangles",
+    "mipt_render_batch", "mipt_render_batch_device",
 ]
 
 _lib = None
@@ -143,6 +144,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_render.restype = C.c_int
     lib.mipt_render_device.argtypes = [vp, vp, C.POINTER(MiptOptions), vp, vp, vp, C.POINTER(MiptStats)]
     lib.mipt_render_device.restype = C.c_int
+    lib.mipt_render_batch.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_batch.restype = C.c_int
+    lib.mipt_render_batch_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), vp, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_batch_device.restype = C.c_int
     lib.mipt_packed_pixels.argtypes = [u32, u32, u32]
     lib.mipt_packed_pixels.restype = u64
     lib.mipt_unpack_tiles.argtypes = [vp, u32, u32, u32, vp, vp]

@@ -62,7 +62,7 @@ void mipt::free_scene(MiptScene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
-                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair};
+                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -511,24 +511,44 @@ static int validate_options(const MiptOptions *opt) {
     return MIPT_OK;
 }
 
-// `pack_single`: honour MIPT_FLAG_PACKED also at tile_world == 1 (mipt_render_multi with one device keeps the same
-// gather + unpack path as with eight); through the public entry PACKED at world 1 means full-frame, as documented.
-} // extern "C"
-int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
-                             float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats, bool pack_single) {
-    if (!scene || !camera) return fail(MIPT_ERR_INVALID_ARG, "mipt_render_device: null scene or camera");
+// A batch: n_views * width * height output pixels, below 2^32 (the kernel's 32-bit tile index and view offset).
+static int validate_batch(const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, const char *who) {
+    if (!scene || !cameras) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene or cameras", who);
+    if (n_views == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: n_views == 0", who);
     int rc = validate_options(opt);
     if (rc) return rc;
-    if (!d_hdr_rgb) return fail(MIPT_ERR_INVALID_ARG, "mipt_render_device: d_hdr_rgb == NULL");
-    HIP_TRY(hipSetDevice(scene->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
+    if (opt->tile_world > 1) return fail(MIPT_ERR_INVALID_ARG, "%s: tile_world %u: a batch is not tile-sharded (0 or 1)", who, opt->tile_world);
+    if (opt->flags & MIPT_FLAG_PACKED) return fail(MIPT_ERR_INVALID_ARG, "%s: MIPT_FLAG_PACKED: a batch is not tile-sharded", who);
+    if ((uint64_t)n_views * opt->width * opt->height >= MIPT_BATCH_MAX_PIXELS)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: %u views of %ux%u: n_views*width*height must stay below 2^32", who, n_views, opt->width, opt->height);
+    return MIPT_OK;
+}
 
+} // extern "C"
+// `pack_single`: honour MIPT_FLAG_PACKED also at tile_world == 1 (mipt_render_multi with one device keeps the same
+// gather + unpack path as with eight); through the public entry PACKED at world 1 means full-frame, as documented.
+// `batch` (mipt_render_batch*, validated by validate_batch): `cameras` holds n_views cameras and the frame is n_views views of
+// width x height, view-major, from one launch of the batch kernel; else cameras[0] is the one camera and n_views is 1.
+static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, bool batch, const MiptOptions *opt,
+                         float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats, bool pack_single) {
+    const char *who = batch ? "mipt_render_batch_device" : "mipt_render_device";
+    int rc = MIPT_OK;
+    if (batch) {
+        if ((rc = validate_batch(scene, cameras, n_views, opt, who))) return rc;
+    } else {
+        if (!scene || !cameras) return fail(MIPT_ERR_INVALID_ARG, "mipt_render_device: null scene or camera");
+        if ((rc = validate_options(opt))) return rc;
+    }
+    if (!d_hdr_rgb) return fail(MIPT_ERR_INVALID_ARG, "%s: d_hdr_rgb == NULL", who);
     const uint32_t world = opt->tile_world ? opt->tile_world : 1u;
     const bool packed = (opt->flags & MIPT_FLAG_PACKED) != 0 && (world > 1 || pack_single);
     if ((opt->flags & MIPT_FLAG_ACCUM) && !(opt->flags & MIPT_FLAG_SUM))
         return fail(MIPT_ERR_INVALID_ARG, "MIPT_FLAG_ACCUM needs MIPT_FLAG_SUM (a running sum, divided once at the end)");
     if (d_rgba8 && (packed || (opt->flags & MIPT_FLAG_SUM)))
         return fail(MIPT_ERR_INVALID_ARG, "RGBA8 output needs a full-frame mean buffer (not PACKED / SUM)");
+    HIP_TRY(hipSetDevice(scene->device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const MiptCamera *camera = cameras;
 
     mipt::DevParams pr{};
     pr.width = opt->width; pr.height = opt->height; pr.samples = opt->samples; pr.max_depth = opt->max_ray_depth;
@@ -542,7 +562,7 @@ int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const M
     const uint64_t tiles = (uint64_t)pr.tiles_x * pr.tiles_y;
     // tiles owned by this rank: t in [0, tiles) with t % world == rank
     pr.n_local_tiles = (uint32_t)((tiles + world - 1u - opt->tile_rank) / world);
-    pr.total_work = (unsigned long long)pr.n_local_tiles * 64ull;
+    pr.total_work = (unsigned long long)pr.n_local_tiles * 64ull * n_views;
     pr.aspect = (float)opt->width / (float)opt->height;       // cpu.rs:34
     pr.samples_f = (float)opt->samples;                       // cpu.rs:60
     pr.cull_scale = 1.0f + opt->cull_margin;
@@ -555,7 +575,7 @@ int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const M
 
     const bool count = (opt->flags & MIPT_FLAG_COUNT) != 0;
     const bool cull = opt->traversal == MIPT_TRAVERSAL_CULLED;
-    const int occ = mipt::trace_blocks_per_cu(count, cull, (int)opt->shading);
+    const int occ = mipt::trace_blocks_per_cu(batch, count, cull, (int)opt->shading);
     int bpc = occ;
     // Small shards (multi-GPU tile split: fewer pixels than resident lanes) are bound by the longest per-pixel chain --
     // a pixel's samples are sequential on one RNG stream -- and each chain steps faster with fewer co-resident waves:
@@ -592,15 +612,31 @@ int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const M
         HIP_TRY(hipMemsetAsync(scene->d_touched, 0, (geom_words + attr_words) * sizeof(uint32_t), stream));
         pr.touched = scene->d_touched;
     }
+    // the batch's camera table: one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream
+    mipt::DevBatch bt{};
+    if (batch) {
+        scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (uint32_t v = 0; v < n_views; v++) {
+            const MiptCamera &c = cameras[v];
+            for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
+            scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
+        }
+        const size_t bytes = scene->h_cams.size() * sizeof(float4);
+        if ((rc = ensure((void **)&scene->d_cams, &scene->cams_bytes, bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
+        bt.cams = scene->d_cams;
+        bt.view_pixels = opt->width * opt->height;
+        bt.tiles_recip = 0xffffffffu / pr.n_local_tiles;
+    }
     HIP_TRY(hipMemsetAsync(scene->d_stats, 0, sizeof(mipt::DevStats), stream));
     HIP_TRY(hipEventRecord(scene->ev0, stream));
-    HIP_TRY(mipt::launch_trace(scene->dev, pr, count, cull, (int)opt->shading, (int)grid, stream));
+    HIP_TRY(mipt::launch_trace(scene->dev, pr, batch ? &bt : nullptr, count, cull, (int)opt->shading, (int)grid, stream));
     HIP_TRY(hipEventRecord(scene->ev1, stream));
     if (touched) {
         HIP_TRY(mipt::launch_popcount(scene->d_touched, geom_words, &scene->d_stats->touched_geom, stream));
         HIP_TRY(mipt::launch_popcount(scene->d_touched + geom_words, attr_words, &scene->d_stats->touched_attr, stream));
     }
-    if (d_rgba8) HIP_TRY(mipt::launch_tonemap(d_hdr_rgb, (unsigned long long)opt->width * opt->height, 1.0f, d_rgba8, stream));
+    if (d_rgba8) HIP_TRY(mipt::launch_tonemap(d_hdr_rgb, (unsigned long long)opt->width * opt->height * n_views, 1.0f, d_rgba8, stream));
     mipt::DevStats hs;
     HIP_TRY(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -623,7 +659,41 @@ int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const M
     return MIPT_OK;
 }
 
+int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
+                             float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats, bool pack_single) {
+    return render_launch(scene, camera, 1u, false, opt, d_hdr_rgb, d_rgba8, hip_stream, stats, pack_single);
+}
+
 extern "C" {
+
+int mipt_render_batch_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                             float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats) {
+    MIPT_NO_THROW(render_launch(scene, cameras, n_views, true, opt, d_hdr_rgb, d_rgba8, hip_stream, stats, false))
+}
+
+int mipt_render_batch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                      float *hdr_rgb, uint8_t *rgba8, MiptStats *stats) {
+    int rc = validate_batch(scene, cameras, n_views, opt, "mipt_render_batch");
+    if (rc) return rc;
+    if (opt->flags & MIPT_FLAG_ACCUM) return fail(MIPT_ERR_INVALID_ARG, "MIPT_FLAG_ACCUM needs a caller-owned device buffer: use mipt_render_batch_device");
+    if (rgba8 && (opt->flags & MIPT_FLAG_SUM))
+        return fail(MIPT_ERR_INVALID_ARG, "RGBA8 output needs a full-frame mean buffer (not PACKED / SUM)");
+    HIP_TRY(hipSetDevice(scene->device));
+    const uint64_t n_pix = (uint64_t)n_views * opt->width * opt->height;
+    size_t have = scene->hdr_floats * sizeof(float);
+    if ((rc = ensure((void **)&scene->d_hdr, &have, (size_t)n_pix * 3 * sizeof(float)))) return rc;
+    scene->hdr_floats = have / sizeof(float);
+    uint8_t *d_rgba = nullptr;
+    if (rgba8) {
+        if ((rc = ensure((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        d_rgba = scene->d_rgba;
+    }
+    rc = mipt_render_batch_device(scene, cameras, n_views, opt, scene->d_hdr, d_rgba, nullptr, stats);
+    if (rc && rc != MIPT_ERR_STACK) return rc;
+    if (hdr_rgb) HIP_TRY(hipMemcpy(hdr_rgb, scene->d_hdr, (size_t)n_pix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgba8) HIP_TRY(hipMemcpy(rgba8, scene->d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
+    return rc;
+}
 
 int mipt_render_device(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
                        float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats) {

@@ -30,6 +30,9 @@ struct MiptScene {
     size_t hdr_floats = 0;
     uint8_t *d_rgba = nullptr;
     size_t rgba_bytes = 0;
+    float4 *d_cams = nullptr;               // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
+    size_t cams_bytes = 0;
+    std::vector<float4> h_cams;             // its host staging copy (outlives the stream-ordered upload)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int n_cu = 0;
     uint32_t max_leaf = 0;

@@ -81,6 +81,13 @@ struct DevParams {
     uint32_t touched_attr_base;             // first bit of the tri_attr stream in `touched`
 };
 
+// A batch of views (pt_trace_batch_kernel): a separate kernel argument, so the single-view kernels' arguments stay as they are.
+struct DevBatch {
+    const float4 *cams;                     // n_views x 64 B: {look_at column 0, column 1, column 2, position}, xyz each (w unused)
+    uint32_t view_pixels;                   // width * height: the output slots of one view
+    uint32_t tiles_recip;                   // floor((2^32 - 1) / n_local_tiles): umulhi(lt, it) is lt / n_local_tiles or up to 2 below
+};
+
 constexpr int kStackLds = 16;               // per-lane traversal-stack entries held in LDS
 constexpr int kStackOvf = 48;               // further entries spilled to HBM (rarely touched)
 constexpr int kWavesPerBlock = 4;
@@ -89,10 +96,11 @@ constexpr int kBlockThreads = 64 * kWavesPerBlock;
 constexpr uint32_t kMaxTris = 1u << 25;     // stack-entry encoding: 25-bit triangle index
 constexpr uint32_t kMaxPairs = 1u << 24;    // 24-bit pair index in the child-ref form
 
-// Launchers (stream-ordered; no allocation, no synchronisation inside).
-hipError_t launch_trace(const DevScene &sc, const DevParams &pr, bool count, bool cull, int shading,
+// Launchers (stream-ordered; no allocation, no synchronisation inside).  batch: NULL = one view (camera in pr.cam), else a
+// batch of views (pr.total_work covers all of them).
+hipError_t launch_trace(const DevScene &sc, const DevParams &pr, const DevBatch *batch, bool count, bool cull, int shading,
                         int grid_blocks, hipStream_t stream);
-int trace_blocks_per_cu(bool count, bool cull, int shading);     // occupancy query
+int trace_blocks_per_cu(bool batch, bool count, bool cull, int shading);     // occupancy query
 hipError_t launch_unpack_tiles(const float *packed_all, uint32_t width, uint32_t height,
                                uint32_t tile_world, float *hdr, hipStream_t stream);
 hipError_t launch_tonemap(const float *hdr, unsigned long long n_pixels, float divisor,

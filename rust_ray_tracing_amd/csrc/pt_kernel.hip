@@ -331,8 +331,14 @@ __device__ __forceinline__ bool shade_wgsl(const DevScene &sc, V3 &o, V3 &d, V3 
 #define MIPT_MIN_WAVES_SHADING1 4      // wgpu-shader shading, fully inlined: 127 VGPRs + 20 B scratch, 21.1 ms on config M (146 VGPRs at 3 waves: 25.2 ms; a non-inlined
                                        // shade_wgsl: 272 B of call frame, 33.3 ms -- tools/experiments/mode1_noinline_shade_result.txt)
 #endif
-template <bool COUNT, bool CULL, int SHADING>
-__global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? MIPT_MIN_WAVES_PER_SIMD : MIPT_MIN_WAVES_UNCULLED) : MIPT_MIN_WAVES_SHADING1) void pt_trace_kernel(DevScene sc, DevParams pr) {
+#define MIPT_TRACE_BOUNDS(COUNT, CULL, SHADING) \
+    __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? MIPT_MIN_WAVES_PER_SIMD : MIPT_MIN_WAVES_UNCULLED) : MIPT_MIN_WAVES_SHADING1)
+
+// The trace loop of both kernels below.  BATCH (pt_trace_batch_kernel, mipt_render_batch*): the work queue runs over
+// (view, tile, pixel) -- pr.n_local_tiles tiles per view, pr.total_work = n_views * n_local_tiles * 64 -- and a lane's camera is
+// its view's record in bt.cams; the in-view tile / pixel math, hence pix, the seed and the screen position, is the single-view one.
+template <bool COUNT, bool CULL, int SHADING, bool BATCH>
+__device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch bt) {
     __shared__ uint32_t s_stack[kWavesPerBlock][kStackLds + 1][64];   // row kStackLds: scratch target of the branch-free push
     __shared__ double s_logtab[32];                                    // __logf_data.tab (16 x {invc, logc}) for gl_log10f
     __shared__ __attribute__((aligned(16))) float s_draw[kWavesPerBlock][64 * 6];                   // scatter draws of a service pass: 3 x {u_theta, u_rho} per hit lane, compacted
@@ -352,6 +358,7 @@ __global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? M
     bool dir_safe = false;
     V3 ray_color = mk(1, 1, 1), incoming = mk(0, 0, 0), emitted = mk(0, 0, 0), final_color = mk(0, 0, 0);
     uint32_t rng = 0, pix = 0, slot = 0, sample = 0, bounces = 0;
+    uint32_t view = 0;                                     // BATCH only (its output slot is view * width * height + pix; `slot` unused)
     V3 prev_hit_point = mk(0, 0, 0);                       // SHADING == 1 only (rt_compute.wgsl:130)
     float screen_x = 0, screen_y = 0;
     // ---- per-lane traversal state ----
@@ -468,7 +475,7 @@ __global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? M
                         state = ST_G;
                     } else {
                         if (!pr.sum_only) final_color = final_color / pr.samples_f;  // cpu.rs:60
-                        float *dst = pr.hdr + (size_t)slot * 3;
+                        float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)slot) * 3;
                         if (pr.accumulate) {      // progressive rendering: add this call's samples to the running sum
                             final_color = mk(dst[0] + final_color.x, dst[1] + final_color.y, dst[2] + final_color.z);
                         }
@@ -498,14 +505,24 @@ __global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? M
                             if (COUNT && g_t_first_x == 0) g_t_first_x = clock64();
                         } else {
                             // 8x8 pixel tiles, round-robin over ranks: global tile = local*world + rank
-                            const uint32_t lt = (uint32_t)(wi >> 6), p = (uint32_t)wi & 63u;
+                            uint32_t lt = (uint32_t)(wi >> 6);
+                            const uint32_t p = (uint32_t)wi & 63u;
+                            if (BATCH) {                                      // work index -> view, tile within the view
+                                // lt / n_local_tiles by the host's reciprocal (DevBatch::tiles_recip): both operands are kernel
+                                // arguments, so no per-lane reciprocal is built and kept live through the loop
+                                const uint32_t n = pr.n_local_tiles;
+                                uint32_t q = __umulhi(lt, bt.tiles_recip), r = lt - q * n;
+                                if (r >= n) { q += 1u; r -= n; }
+                                if (r >= n) { q += 1u; r -= n; }
+                                view = q; lt = r;
+                            }
                             const uint32_t lt_o = pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt;
                             const uint32_t gt = lt_o * pr.tile_world + pr.tile_rank;
                             const uint32_t px = (gt % pr.tiles_x) * 8u + (p & 7u);
                             const uint32_t py = (gt / pr.tiles_x) * 8u + (p >> 3);
                             if (px < pr.width && py < pr.height) {            // ragged edge tiles: skip, stay ST_P
                                 pix = py * pr.width + px;
-                                slot = pr.packed ? (lt_o * 64u + p) : pix;
+                                if (!BATCH) slot = pr.packed ? (lt_o * 64u + p) : pix;
                                 rng = 987612486u * (pix + 87636354u);                 // cpu.rs:28-29
                                 const uint32_t y = pr.height - py;                    // cpu.rs:32
                                 screen_x = ((((float)px / (float)pr.width) * 2.0f) - 1.0f) * pr.aspect; // cpu.rs:33-34
@@ -528,11 +545,21 @@ __global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? M
                 const float jy = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
                 const float rx = -screen_x + jx, ry = screen_y + jy, rz = 1.0f;
                 // Mat4f * Vec3f, upper-left 3x3, data[col][row] (mat4.rs:143-152)
-                const V3 dir = mk(pr.cam[0] * rx + pr.cam[3] * ry + pr.cam[6] * rz,
-                                  pr.cam[1] * rx + pr.cam[4] * ry + pr.cam[7] * rz,
-                                  pr.cam[2] * rx + pr.cam[5] * ry + pr.cam[8] * rz);
-                d = normalized(dir);
-                o = mk(pr.cam[9], pr.cam[10], pr.cam[11]);
+                if (BATCH) {
+                    const float4 *cr = bt.cams + (size_t)view * 4;
+                    const float4 c0 = cr[0], c1 = cr[1], c2 = cr[2], c3 = cr[3];
+                    const V3 dir = mk(c0.x * rx + c1.x * ry + c2.x * rz,
+                                      c0.y * rx + c1.y * ry + c2.y * rz,
+                                      c0.z * rx + c1.z * ry + c2.z * rz);
+                    d = normalized(dir);
+                    o = mk(c3.x, c3.y, c3.z);
+                } else {
+                    const V3 dir = mk(pr.cam[0] * rx + pr.cam[3] * ry + pr.cam[6] * rz,
+                                      pr.cam[1] * rx + pr.cam[4] * ry + pr.cam[7] * rz,
+                                      pr.cam[2] * rx + pr.cam[5] * ry + pr.cam[8] * rz);
+                    d = normalized(dir);
+                    o = mk(pr.cam[9], pr.cam[10], pr.cam[11]);
+                }
                 ray_color = mk(1.0f, 1.0f, 1.0f);                                     // ray.rs:142-146
                 incoming = mk(0.0f, 0.0f, 0.0f);
                 emitted = mk(0.0f, 0.0f, 0.0f);
@@ -695,6 +722,17 @@ __global__ __launch_bounds__(kBlockThreads, SHADING == 0 ? ((CULL && !COUNT) ? M
     if (c_pixels) atomicAdd(&pr.stats->pixels, (unsigned long long)c_pixels);
 }
 
+// One frame (optionally one tile shard of it) with the camera in pr.cam.
+template <bool COUNT, bool CULL, int SHADING>
+__global__ MIPT_TRACE_BOUNDS(COUNT, CULL, SHADING) void pt_trace_kernel(DevScene sc, DevParams pr) {
+    trace_body<COUNT, CULL, SHADING, false>(sc, pr, DevBatch{});
+}
+// A batch of views of one size: view-major output (view v's pixels at slots [v * width * height, (v + 1) * width * height)).
+template <bool COUNT, bool CULL, int SHADING>
+__global__ MIPT_TRACE_BOUNDS(COUNT, CULL, SHADING) void pt_trace_batch_kernel(DevScene sc, DevParams pr, DevBatch bt) {
+    trace_body<COUNT, CULL, SHADING, true>(sc, pr, bt);
+}
+
 // ---- all-gathered rank-packed tile slices -> full frame -----------------------------------
 __global__ void unpack_tiles_kernel(const float *__restrict__ packed_all, uint32_t width, uint32_t height,
                                     uint32_t world, uint32_t tiles_x, uint32_t n_local_tiles, float *__restrict__ hdr) {
@@ -777,34 +815,43 @@ hipError_t launch_postprocess(const float *hdr, unsigned long long n_pixels, flo
     return hipGetLastError();
 }
 
-template <bool COUNT, bool CULL, int SHADING>
-static hipError_t launch_t(const DevScene &sc, const DevParams &pr, int grid, hipStream_t stream) {
-    hipLaunchKernelGGL((pt_trace_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr);
+template <bool COUNT, bool CULL, int SHADING, bool BATCH>
+static hipError_t launch_t(const DevScene &sc, const DevParams &pr, const DevBatch *bt, int grid, hipStream_t stream) {
+    if (BATCH) hipLaunchKernelGGL((pt_trace_batch_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr, *bt);
+    else hipLaunchKernelGGL((pt_trace_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr);
     return hipGetLastError();
 }
-template <bool COUNT, bool CULL, int SHADING>
+template <bool COUNT, bool CULL, int SHADING, bool BATCH>
 static int occ_t() {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pt_trace_kernel<COUNT, CULL, SHADING>, kBlockThreads, 0) != hipSuccess) n = 1;
+    hipError_t e = BATCH ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pt_trace_batch_kernel<COUNT, CULL, SHADING>, kBlockThreads, 0)
+                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pt_trace_kernel<COUNT, CULL, SHADING>, kBlockThreads, 0);
+    if (e != hipSuccess) n = 1;
     return n;
 }
-// instantiations: {CPU-backend shading, wgpu-shader shading} x {count, cull}
-#define MIPT_DISPATCH(FN, ...)                                                                                          \
+// instantiations: {single view, batch} x {CPU-backend shading, wgpu-shader shading} x {count, cull}
+#define MIPT_DISPATCH_B(FN, B, ...)                                                                                     \
     do {                                                                                                                \
         if (shading == 1) {                                                                                             \
-            if (count) return cull ? FN<true, true, 1>(__VA_ARGS__) : FN<true, false, 1>(__VA_ARGS__);                  \
-            return cull ? FN<false, true, 1>(__VA_ARGS__) : FN<false, false, 1>(__VA_ARGS__);                           \
+            if (count) return cull ? FN<true, true, 1, B>(__VA_ARGS__) : FN<true, false, 1, B>(__VA_ARGS__);            \
+            return cull ? FN<false, true, 1, B>(__VA_ARGS__) : FN<false, false, 1, B>(__VA_ARGS__);                     \
         }                                                                                                               \
-        if (count) return cull ? FN<true, true, 0>(__VA_ARGS__) : FN<true, false, 0>(__VA_ARGS__);                      \
-        return cull ? FN<false, true, 0>(__VA_ARGS__) : FN<false, false, 0>(__VA_ARGS__);                               \
+        if (count) return cull ? FN<true, true, 0, B>(__VA_ARGS__) : FN<true, false, 0, B>(__VA_ARGS__);                \
+        return cull ? FN<false, true, 0, B>(__VA_ARGS__) : FN<false, false, 0, B>(__VA_ARGS__);                         \
+    } while (0)
+#define MIPT_DISPATCH(FN, ...)                                                                                          \
+    do {                                                                                                                \
+        if (batch) MIPT_DISPATCH_B(FN, true, __VA_ARGS__);                                                              \
+        MIPT_DISPATCH_B(FN, false, __VA_ARGS__);                                                                        \
     } while (0)
 
-hipError_t launch_trace(const DevScene &sc, const DevParams &pr, bool count, bool cull, int shading, int grid, hipStream_t stream) {
-    MIPT_DISPATCH(launch_t, sc, pr, grid, stream);
+hipError_t launch_trace(const DevScene &sc, const DevParams &pr, const DevBatch *batch, bool count, bool cull, int shading, int grid,
+                        hipStream_t stream) {
+    MIPT_DISPATCH(launch_t, sc, pr, batch, grid, stream);
 }
-static int occ_dispatch(bool count, bool cull, int shading) { MIPT_DISPATCH(occ_t); }
-int trace_blocks_per_cu(bool count, bool cull, int shading) {
-    int n = occ_dispatch(count, cull, shading);
+static int occ_dispatch(bool batch, bool count, bool cull, int shading) { MIPT_DISPATCH(occ_t); }
+int trace_blocks_per_cu(bool batch, bool count, bool cull, int shading) {
+    int n = occ_dispatch(batch, count, cull, shading);
     if (n < 1) n = 1;
     if (n > 8) n = 8;
     return n;

@@ -434,6 +434,30 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = st.as_dict()
         return hdr, rgba, self.last_stats
 
+    def render_buffers_batch(self, scene: Scene, cameras, want_hdr: bool = True, want_rgba8: bool = True, flags: int = 0):
+        """Many views of one scene in one launch (mipt_render_batch): `cameras` is a sequence of Camera (or CAMERA records), all
+        rendered with this renderer's options.  View i equals render_buffers with cameras[i].  Returns (hdr float32 [n,h,w,3] |
+        None, rgba8 uint8 [n,h,w,4] | None, stats dict of the one launch)."""
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        cams = [c.uniform if isinstance(c, Camera) else c for c in cameras]
+        if not cams:
+            raise ValueError("render_buffers_batch: no cameras")
+        table = np.ascontiguousarray(np.stack([np.asarray(c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        n = len(cams)
+        w, h = o.output_image_dimensions
+        handle = scene.upload(o.device_id)
+        opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, cull_margin=o.cull_margin, shading=o.shading)
+        hdr = np.zeros((n, h, w, 3), dtype=np.float32) if want_hdr else None
+        rgba = np.zeros((n, h, w, 4), dtype=np.uint8) if want_rgba8 else None
+        st = L.MiptStats()
+        rc = L.load().mipt_render_batch(handle, L.ptr(table), n, C.byref(opt),
+                                        L.ptr(hdr) if want_hdr else None, L.ptr(rgba) if want_rgba8 else None, C.byref(st))
+        L.check(rc, "mipt_render_batch")
+        self.last_stats = st.as_dict()
+        return hdr, rgba, self.last_stats
+
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
                              want_rgba8: bool = True, flags: int = 0):
         """The same arm over all GPUs of the node in one call (mipt_render_multi): image tiles + one RCCL gather, or

@@ -1,0 +1,316 @@
+"""-m gpu: mipt_render_batch / mipt_render_batch_device -- many views of one scene in one trace launch.  Pixel seeds depend on the
+pixel position and the sample number only, never on the launch, so every view of a batch must equal the single render of its camera
+with the same options, bit for bit (u32 patterns, NaN matched to NaN), and the batch's counters must be the sums over those renders."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+COUNTERS = ("rays", "inner_steps", "tri_tests", "hits", "texel_fetches", "tex_clamped", "pixels")
+
+
+def _same(a, b):
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+
+
+@functools.lru_cache(maxsize=None)
+def _scene_cached(kind, kw_items):
+    import rust_ray_tracing_amd as rrt
+    from rust_ray_tracing_amd import synth
+    tris, mats, texs, cam = synth.make_scene(kind, **dict(kw_items))
+    sc = rrt.Scene.from_arrays(tris, mats, texs)
+    sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+    return sc, cam
+
+
+def _scene(kind, **kw):
+    return _scene_cached(kind, tuple(sorted(kw.items())))
+
+
+def _poses(rrt, cam, n, box, seed):
+    """n cameras: the scene's own, n - 2 random poses around it, and a duplicate of view 0 last."""
+    rng = np.random.default_rng(seed)
+    cams = [rrt.Camera(position=tuple(cam[0]), pitch=cam[1], yaw=cam[2])]
+    for _ in range(n - 2):
+        pos = tuple(float(x) for x in (np.array(cam[0]) + rng.uniform(-box, box, 3) * np.array([1.0, 0.25, 1.0])))
+        cams.append(rrt.Camera(position=pos, pitch=float(rng.uniform(-60, 60)), yaw=float(rng.uniform(-180, 180))))
+    cams.append(rrt.Camera(position=tuple(cam[0]), pitch=cam[1], yaw=cam[2]))
+    for c in cams:
+        c.update_view()
+    return cams
+
+
+def _table(cams):
+    from rust_ray_tracing_amd import _lib as L
+    return np.ascontiguousarray(np.stack([np.asarray(c.uniform, dtype=L.CAMERA).reshape(()) for c in cams]))
+
+
+def _singles(lib, hnd, cams, o, w, h, rgba=True):
+    from rust_ray_tracing_amd import _lib as L
+    hdrs, rgbas, stats = [], [], []
+    for c in cams:
+        hdr = np.zeros((h, w, 3), dtype=np.float32)
+        px = np.zeros((h, w, 4), dtype=np.uint8) if rgba else None
+        st = L.MiptStats()
+        L.check(lib.mipt_render(hnd, L.ptr(c.uniform), C.byref(o), L.ptr(hdr), L.ptr(px) if rgba else None, C.byref(st)), "mipt_render")
+        hdrs.append(hdr); rgbas.append(px); stats.append(st.as_dict())
+    return hdrs, rgbas, stats
+
+
+def _batch(lib, hnd, cams, o, w, h, rgba=True):
+    from rust_ray_tracing_amd import _lib as L
+    n = len(cams)
+    hdr = np.zeros((n, h, w, 3), dtype=np.float32)
+    px = np.zeros((n, h, w, 4), dtype=np.uint8) if rgba else None
+    st = L.MiptStats()
+    table = _table(cams)                                                   # kept alive through the call (L.ptr holds no reference)
+    L.check(lib.mipt_render_batch(hnd, L.ptr(table), n, C.byref(o), L.ptr(hdr), L.ptr(px) if rgba else None, C.byref(st)),
+            "mipt_render_batch")
+    return hdr, px, st.as_dict()
+
+
+def _check_equal(hdr, px, st, hdrs, rgbas, stats, counters=True):
+    for v in range(len(hdrs)):
+        assert _same(hdr[v], hdrs[v]), f"view {v}: HDR differs"
+        if rgbas[v] is not None:
+            assert np.array_equal(px[v], rgbas[v]), f"view {v}: RGBA8 differs"
+    if counters:
+        for k in COUNTERS:
+            assert st[k] == sum(s[k] for s in stats), k
+        assert st["max_stack"] == max(s["max_stack"] for s in stats)
+        assert st["stack_overflows"] == 0
+
+
+CONFIGS = {   # name -> (shading, traversal, cull_margin)
+    "cpu_culled": (0, 1, 0.0078125),
+    "cpu_reference": (0, 0, 0.0),
+    "wgpu": (1, 1, 0.0078125),
+}
+
+
+@pytest.mark.parametrize("seed_mode", [0, 1])
+@pytest.mark.parametrize("config", list(CONFIGS))
+@pytest.mark.parametrize("kind,kw,n_views,box,size,seed", [
+    ("cornell", (), 6, 0.8, (72, 40), 21),
+    ("helmet", (("n_target", 15000), ("tex_size", 64)), 7, 4.0, (61, 37), 22),
+    ("dragon", (("n_target", 200000),), 5, 6.0, (72, 40), 23),
+    ("atrium", (("n_target", 300000), ("tex_size", 128)), 9, 14.0, (61, 37), 24),
+])
+def test_batch_equals_single_renders(rrt, kind, kw, n_views, box, size, seed, config, seed_mode):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene(kind, **dict(kw))
+    hnd = sc.upload(0)
+    shading, trav, margin = CONFIGS[config]
+    w, h = size
+    o = rrt.make_options(w, h, 3, 8, seed_mode=seed_mode, traversal=trav, flags=L.FLAG_COUNT, cull_margin=margin, shading=shading)
+    cams = _poses(rrt, cam, n_views, box, seed)
+    hdrs, rgbas, stats = _singles(lib, hnd, cams, o, w, h)
+    hdr, px, st = _batch(lib, hnd, cams, o, w, h)
+    _check_equal(hdr, px, st, hdrs, rgbas, stats)
+    assert st["pixels"] == n_views * w * h and st["kernel_ms"] > 0
+    assert _same(hdr[0], hdr[-1])                                          # the duplicate of view 0
+
+
+def test_batch_view_matches_oracle(rrt, orc):
+    """One view of a batch against the CPU oracle (un-culled traversal, cpu/ray.rs:84-139) on a strided pixel sample."""
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("helmet", n_target=15000, tex_size=64)
+    hnd = sc.upload(0)
+    w, h, spp, depth, stride = 96, 54, 4, 16, 7
+    cams = _poses(rrt, cam, 4, 4.0, 31)
+    o = rrt.make_options(w, h, spp, depth, traversal=L.TRAVERSAL_REFERENCE, cull_margin=0.0)
+    hdr, _, _ = _batch(lib, hnd, cams, o, w, h, rgba=False)
+    v = 1
+    ref, _, _ = orc.render(sc.tris, sc.bvh_nodes, sc.materials_array(), sc.textures, cams[v].uniform, w, h, spp, depth, cull=0,
+                           pix_stride=stride, want_rgba8=False)
+    sel = np.arange(0, w * h, stride)
+    assert _same(hdr[v].reshape(-1, 3)[sel], ref.reshape(-1, 3)[sel])
+
+
+def test_one_view_batch_equals_render(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("dragon", n_target=200000)
+    hnd = sc.upload(0)
+    w, h = 160, 90
+    cams = _poses(rrt, cam, 2, 6.0, 41)[:1]
+    o = rrt.make_options(w, h, 2, 16, traversal=L.TRAVERSAL_CULLED, flags=L.FLAG_COUNT)
+    hdrs, rgbas, stats = _singles(lib, hnd, cams, o, w, h)
+    hdr, px, st = _batch(lib, hnd, cams, o, w, h)
+    _check_equal(hdr, px, st, hdrs, rgbas, stats)
+    for k in COUNTERS + ("max_stack",):
+        assert st[k] == stats[0][k], k
+
+
+@pytest.mark.parametrize("n_views,w,h", [(300, 8, 8), (100, 1, 1), (64, 1, 17)])
+def test_view_decode_edges(rrt, n_views, w, h):
+    """Views of one tile, of one pixel (63 of the tile's 64 work items skipped) and one pixel wide across three tiles."""
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("cornell")
+    hnd = sc.upload(0)
+    cams = _poses(rrt, cam, n_views, 0.8, 50 + n_views)
+    o = rrt.make_options(w, h, 2, 6, seed_mode=L.SEED_PER_SAMPLE, traversal=L.TRAVERSAL_CULLED, flags=L.FLAG_COUNT)
+    hdr, px, st = _batch(lib, hnd, cams, o, w, h)
+    hdrs, rgbas, stats = _singles(lib, hnd, cams, o, w, h)
+    _check_equal(hdr, px, st, hdrs, rgbas, stats)
+
+
+def test_device_entry_stream_accum_and_epilogues(rrt):
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("helmet", n_target=15000, tex_size=64)
+    hnd = sc.upload(0)
+    w, h, n = 61, 37, 5
+    cams = _poses(rrt, cam, n, 4.0, 61)
+    table = _table(cams)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(stream.cuda_stream)
+    npx = w * h
+    # plain frame + RGBA8 on a non-null stream
+    o = rrt.make_options(w, h, 3, 8, traversal=L.TRAVERSAL_CULLED)
+    bh = torch.zeros(n * npx * 3, dtype=torch.float32, device=dev)
+    bp = torch.zeros(n * npx * 4, dtype=torch.uint8, device=dev)
+    assert lib.mipt_render_batch_device(hnd, L.ptr(table), n, C.byref(o), C.c_void_p(bh.data_ptr()), C.c_void_p(bp.data_ptr()), sp,
+                                        None) == 0, lib.mipt_last_error()
+    sh = torch.zeros(n * npx * 3, dtype=torch.float32, device=dev)
+    spx = torch.zeros(n * npx * 4, dtype=torch.uint8, device=dev)
+    for v in range(n):
+        assert lib.mipt_render_device(hnd, L.ptr(cams[v].uniform), C.byref(o), C.c_void_p(sh[v * npx * 3:].data_ptr()),
+                                      C.c_void_p(spx[v * npx * 4:].data_ptr()), sp, None) == 0, lib.mipt_last_error()
+    torch.cuda.synchronize()
+    assert _same(bh.cpu().numpy(), sh.cpu().numpy()) and torch.equal(bp.cpu(), spx.cpu())
+    # mipt_tonemap_device / mipt_postprocess_device over the whole batch buffer = per view
+    t_all = torch.zeros(n * npx * 4, dtype=torch.uint8, device=dev)
+    p_all = torch.zeros(n * npx * 4, dtype=torch.int16, device=dev)
+    assert lib.mipt_tonemap_device(C.c_void_p(bh.data_ptr()), n * npx, 2.0, C.c_void_p(t_all.data_ptr()), sp) == 0
+    assert lib.mipt_postprocess_device(C.c_void_p(bh.data_ptr()), n * npx, 1.5, C.c_void_p(p_all.data_ptr()), sp) == 0
+    t_one = torch.zeros_like(t_all)
+    p_one = torch.zeros_like(p_all)
+    for v in range(n):
+        assert lib.mipt_tonemap_device(C.c_void_p(sh[v * npx * 3:].data_ptr()), npx, 2.0, C.c_void_p(t_one[v * npx * 4:].data_ptr()), sp) == 0
+        assert lib.mipt_postprocess_device(C.c_void_p(sh[v * npx * 3:].data_ptr()), npx, 1.5,
+                                           C.c_void_p(p_one[v * npx * 4:].data_ptr()), sp) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(t_all.cpu(), t_one.cpu()) and torch.equal(p_all.cpu(), p_one.cpu())
+    # progressive: three SUM | ACCUM calls with advancing sample_begin, batch against singles
+    acc_b = torch.zeros(n * npx * 3, dtype=torch.float32, device=dev)
+    acc_s = torch.zeros(n * npx * 3, dtype=torch.float32, device=dev)
+    for k in range(3):
+        oa = rrt.make_options(w, h, 2, 8, seed_mode=L.SEED_PER_SAMPLE, traversal=L.TRAVERSAL_CULLED, flags=L.FLAG_SUM | L.FLAG_ACCUM,
+                              sample_begin=1 + 2 * k)
+        assert lib.mipt_render_batch_device(hnd, L.ptr(table), n, C.byref(oa), C.c_void_p(acc_b.data_ptr()), None, sp, None) == 0
+        for v in range(n):
+            assert lib.mipt_render_device(hnd, L.ptr(cams[v].uniform), C.byref(oa), C.c_void_p(acc_s[v * npx * 3:].data_ptr()), None,
+                                          sp, None) == 0
+    torch.cuda.synchronize()
+    assert _same(acc_b.cpu().numpy(), acc_s.cpu().numpy())
+    assert acc_b.abs().sum().item() > 0
+
+
+def _chain_bvh(rrt, depth):
+    """Hand-built BVH (as in test_gpu_more.py): a chain in which every inner node has a FAR leaf child and a NEAR inner child for a
+    ray along +x, so each level pushes one stack entry: stack occupancy = depth."""
+    from rust_ray_tracing_amd import NODE, TRIANGLE
+    n = depth + 1
+    tris = np.zeros(n, dtype=TRIANGLE)
+    xs = 1000.0 - np.arange(n, dtype=np.float32) * 2.0
+    for k in range(n):
+        tris["vertices"]["position"][k] = [(xs[k], -1, -1), (xs[k], 1, -1), (xs[k], 0, 1)]
+    tris["vertices"]["normal"] = (-1, 0, 0)
+    nodes = np.zeros(2 * n - 1, dtype=NODE)
+
+    def box(lo, hi):
+        return (lo, -1.0, -1.0), (hi, 1.0, 1.0)
+    nodes[0]["bounds_min"], nodes[0]["bounds_max"] = box(xs[-1], xs[0])
+    nodes[0]["first_tri_or_child"] = 1
+    for k in range(n - 1):
+        leaf, rest = 2 * k + 1, 2 * k + 2
+        nodes[leaf]["bounds_min"], nodes[leaf]["bounds_max"] = box(xs[k], xs[k])
+        nodes[leaf]["first_tri_or_child"], nodes[leaf]["num_tris"] = k, 1
+        nodes[rest]["bounds_min"], nodes[rest]["bounds_max"] = box(xs[-1], xs[k + 1])
+        if k == n - 2:
+            nodes[rest]["first_tri_or_child"], nodes[rest]["num_tris"] = k + 1, 1
+        else:
+            nodes[rest]["first_tri_or_child"], nodes[rest]["num_tris"] = 2 * k + 3, 0
+    sc = rrt.Scene.from_arrays(tris, [rrt.material_default()], build_bvh=False)
+    sc.bvh_nodes = nodes
+    sc.set_camera(rrt.Camera(position=(0.0, 0.0, 0.0), pitch=0.0, yaw=180.0))
+    return sc
+
+
+def test_errors_leave_the_scene_rendering(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("cornell")
+    hnd = sc.upload(0)
+    w, h, n = 40, 24, 3
+    cams = _poses(rrt, cam, n, 0.8, 71)
+    table = _table(cams)
+    o = rrt.make_options(w, h, 2, 6, traversal=L.TRAVERSAL_CULLED, flags=L.FLAG_COUNT)
+    before, before_px, before_st = _batch(lib, hnd, cams, o, w, h)
+    hdr = np.zeros(n * w * h * 3, dtype=np.float32)
+    px = np.zeros(n * w * h * 4, dtype=np.uint8)
+
+    def opts(**kw):
+        x = rrt.make_options(w, h, 2, 6, traversal=L.TRAVERSAL_CULLED)
+        for k, v in kw.items():
+            setattr(x, k, v)
+        return x
+    cases = [
+        ("n_views = 0", dict(n=0)),
+        ("cameras == NULL", dict(table=None)),
+        ("tile_world = 2", dict(o=opts(tile_world=2))),
+        ("MIPT_FLAG_PACKED", dict(o=opts(flags=L.FLAG_PACKED))),
+        ("RGBA8 with SUM", dict(o=opts(flags=L.FLAG_SUM), rgba=True)),
+        ("ACCUM on the host entry", dict(o=opts(flags=L.FLAG_SUM | L.FLAG_ACCUM))),
+        ("pixel total >= 2^32", dict(o=opts(width=40000, height=40000))),      # 3 x 1.6e9 pixels: refused before any allocation
+    ]
+    for name, c in cases:
+        rc = lib.mipt_render_batch(hnd, L.ptr(table) if c.get("table", 1) is not None else None, c.get("n", n), C.byref(c.get("o", o)),
+                                   L.ptr(hdr), L.ptr(px) if c.get("rgba") else None, None)
+        assert rc == L.ERR_INVALID_ARG, name
+        assert lib.mipt_last_error(), name
+    after, after_px, after_st = _batch(lib, hnd, cams, o, w, h)
+    assert _same(after, before) and np.array_equal(after_px, before_px)
+    for k in COUNTERS + ("max_stack",):
+        assert after_st[k] == before_st[k], k
+    # a tree deeper than the kernel's stack: MIPT_ERR_STACK from a batch, as from a single render
+    deep = _chain_bvh(rrt, 120)
+    dh = deep.upload(0)
+    od = rrt.make_options(16, 16, 1, 2)
+    deep_cams = [deep.camera, deep.camera]
+    out = np.zeros(2 * 16 * 16 * 3, dtype=np.float32)
+    st = L.MiptStats()
+    deep_table = _table(deep_cams)
+    assert lib.mipt_render_batch(dh, L.ptr(deep_table), 2, C.byref(od), L.ptr(out), None, C.byref(st)) == L.ERR_STACK
+    assert st.stack_overflows > 0 and "stack" in lib.mipt_last_error().decode()
+
+
+def test_batch_after_refit(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    from rust_ray_tracing_amd import synth
+    lib = rrt.load()
+    tris, mats, texs, cam = synth.make_scene("helmet", n_target=15000, tex_size=64)
+    sc = rrt.Scene.from_arrays(tris, mats, texs)
+    sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+    hnd = sc.upload(0)
+    w, h = 72, 40
+    cams = _poses(rrt, cam, 5, 4.0, 81)
+    o = rrt.make_options(w, h, 2, 8, traversal=L.TRAVERSAL_CULLED, flags=L.FLAG_COUNT)
+    first, _, _ = _batch(lib, hnd, cams, o, w, h)
+    rng = np.random.default_rng(5)
+    sc.tris["vertices"]["position"] += rng.uniform(-0.02, 0.02, sc.tris["vertices"]["position"].shape).astype(np.float32)
+    sc.update_device(L.UPDATE_REFIT)
+    hdrs, rgbas, stats = _singles(lib, hnd, cams, o, w, h)
+    hdr, px, st = _batch(lib, hnd, cams, o, w, h)
+    _check_equal(hdr, px, st, hdrs, rgbas, stats)
+    assert not _same(hdr, first)                                           # the geometry did change
