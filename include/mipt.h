@@ -365,6 +365,88 @@ MIPT_API int mipt_scene_update_triangles_device(MiptScene *scene, const MiptTria
 MIPT_API int mipt_multi_update_triangles(MiptMulti *multi, const MiptTriangle *tris, uint32_t n_tris,
                                          uint32_t mode, MiptUpdateInfo *info);
 
+/* ---- resident indexed meshes ------------------------------------------------------------------------------------------
+ * What a caller holds before scene.rs:48-76 expands it -- vertex arrays plus index triples, cut into objects ("parts") -- kept in
+ * HBM and expanded to fat triangles ON THE GPU (csrc/scene_mesh.hip).  A scene made from a mesh is animated by one 4x4 matrix per
+ * part (64 B each over PCIe) or by new vertex arrays already in HBM; the expanded array then goes through MIPT_UPDATE_REFIT /
+ * _REBUILD above.  The trace kernels see an ordinary scene.
+ *
+ * Expansion rule (mipt_mesh_expand, the expansion kernel and tests/tools/mesh_model.py obey it bit for bit; every operator is one
+ * rounded f32 operation, nothing is fused):
+ *   - triangle t of part p, corner c: Vertex{position, tex_coord_x, normal, tex_coord_y} from the three indexed arrays (entry
+ *     3*t + c of each index stream), material_id = parts[p].material_id, _pad = 0.  Output order: part order, then triangle order
+ *     -- "the caller's order" of mipt_scene_create_from_triangles / mipt_scene_get_bvh.
+ *   - a normal / tex-coord index >= its array's count (UINT32_MAX, or any index when the array is NULL) gives zeros
+ *     (unwrap_or(&[0.0; _]), scene.rs:56-65).  A POSITION index out of range is MIPT_ERR_INVALID_ARG (the message names the first
+ *     offending index entry); on the device the expansion kernel detects it before anything resident is replaced.
+ *   - transforms == NULL: no arithmetic, attribute bits are copied (-0.0, NaN payloads and infinities survive).
+ *   - with a transform M of the part (Mat4f data[col][row], mat4.rs:6-10; columns a0,a1,a2 = data[0..2][0..2], translation
+ *     t = data[3][0..2], row 3 ignored): p' = M*p + t in the operation order of mat4.rs:146-149, x' = ((a0.x*p.x + a1.x*p.y) +
+ *     a2.x*p.z) + t.x.  Normal: c = c0*n.x + c1*n.y + c2*n.z in the same order with the cofactor columns c0 = cross(a1,a2),
+ *     c1 = cross(a2,a0), c2 = cross(a0,a1) (vec3.rs:137-143), which keeps the normal on the side of the moved triangle's winding
+ *     even under a mirror; its length is kept (the CPU shading path uses the un-normalised normal, ray.rs:179-180):
+ *     L0 = length(n), L1 = length(c) (vec3.rs:94-96); L1 > 0 and finite: n' = c * (L0 / L1), else n' = c.  Tex coords are copied.
+ *     (A NaN that this arithmetic produces is a NaN everywhere; its sign and payload are the implementation's, as in IEEE 754.)
+ *
+ * Errors: everything is validated before anything resident is overwritten, and after any error the scene renders exactly as
+ * before.  The host-visible checks (null pointers, n_indices % 3, parts not tiling the index range, reserved != 0, material_id >=
+ * n_materials, n_parts mismatch, bad mode, no triangles: MIPT_ERR_INVALID_ARG; more than 2^25 triangles: MIPT_ERR_SCENE_LIMIT) run
+ * before any device call.  A bound that comes out non-finite or beyond 2^40 after a transform: MIPT_ERR_SCENE_LIMIT from the update
+ * path.  mipt_scene_update_triangles{,_device} on a scene that owns a mesh and every mesh call on a scene without one:
+ * MIPT_ERR_INVALID_ARG.  Replicas (MiptMulti) are made from the geometry only: a replica of a mesh scene is a plain scene. */
+typedef struct {            /* one object: a run of triangles with one material and one transform (16 B) */
+    uint32_t first_tri;     /* first triangle of the part; corner c of triangle t is index entry 3*t + c */
+    uint32_t n_tris;        /* may be 0 */
+    uint32_t material_id;   /* Triangle.material_id of every triangle of the part */
+    uint32_t reserved;      /* must be 0 */
+} MiptMeshPart;
+
+typedef struct {
+    const float    *positions;   uint32_t n_positions;    /* 3 f32 each */
+    const float    *normals;     uint32_t n_normals;      /* 3 f32 each; NULL / 0 allowed */
+    const float    *tex_coords;  uint32_t n_tex_coords;   /* 2 f32 each; NULL / 0 allowed */
+    const uint32_t *indices;     uint32_t n_indices;      /* 3 per triangle: position index of each corner */
+    const uint32_t *normal_indices;                       /* n_indices entries, NULL = use `indices` */
+    const uint32_t *tex_coord_indices;                    /* n_indices entries, NULL = use `indices` */
+    const MiptMeshPart *parts;   uint32_t n_parts;        /* must tile [0, n_indices/3) in order, no gaps, no overlap */
+    const float    *transforms;                           /* n_parts x 16 f32, Mat4f data[col][row] (mat4.rs:6-10); NULL = none */
+} MiptMeshDesc;
+
+typedef struct {
+    uint32_t n_positions, n_normals, n_tex_coords, n_indices;
+    uint32_t n_tris, n_parts;
+    uint32_t has_transforms;      /* 1: the last successful create / update applied per-part matrices */
+    uint32_t index_streams;       /* index arrays held: 1 (shared) ... 3 */
+    uint64_t array_bytes;         /* HBM held for vertex arrays, index streams, part records and the transform staging buffer */
+    uint64_t expanded_bytes;      /* HBM held for the expanded triangle array (112 B per triangle), kept between updates */
+    uint64_t hbm_bytes;           /* the sum: what the mesh costs on top of MiptSceneInfo.geometry_bytes */
+} MiptMeshInfo;
+
+/* The expansion rule on the host: writes n_indices / 3 triangles to `out` (cap >= that, else MIPT_ERR_INVALID_ARG) and their count to
+ * n_out (may be NULL).  No device is touched; parts[].material_id is copied unchecked (there is no material table here). */
+MIPT_API int mipt_mesh_expand(const MiptMeshDesc *mesh, MiptTriangle *out, uint32_t cap, uint32_t *n_out);
+
+/* `desc` supplies materials and textures (tris / nodes are ignored).  The mesh arrays cross PCIe once, stay resident and are expanded
+ * by the GPU; BVH::build and the layout then run as in mipt_scene_create_from_triangles.  The result is THAT scene: the layout bytes,
+ * mipt_scene_get_bvh and the size fields of MiptSceneInfo equal those of mipt_scene_create_from_triangles(mipt_mesh_expand(mesh));
+ * upload_ms includes the mesh arrays, build_ms the expansion kernel. */
+MIPT_API int mipt_scene_create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int device_id, MiptScene **out);
+
+/* New per-part matrices from HOST memory (n_parts x 16 f32; n_parts must equal the mesh's; NULL = back to no transforms): 64 B per
+ * part are copied, the resident mesh is expanded again and the scene updated with `mode` (MiptUpdateMode).  info (may be NULL):
+ * upload_ms = the matrix copy; build_ms = the update's build_ms + the HIP-event time of the expansion kernels; layout_ms as above. */
+MIPT_API int mipt_scene_set_transforms(MiptScene *scene, const float *transforms, uint32_t n_parts, uint32_t mode, MiptUpdateInfo *info);
+
+/* A deforming mesh from HBM of the scene's device (e.g. torch tensors): each pointer may be NULL = keep what is resident; the
+ * counts are the resident mesh's (the topology is fixed; d_transforms: n_parts x 16 f32).  The arrays are read, not modified; after
+ * a successful update they replace the resident copies (device-to-device).  Ordered after the earlier work of `hip_stream`
+ * (hipStream_t, NULL = the null stream); blocks until done.  build_ms includes the expansion as above; upload_ms = 0. */
+MIPT_API int mipt_scene_update_mesh_device(MiptScene *scene, const float *d_positions, const float *d_normals, const float *d_transforms,
+                                           uint32_t mode, void *hip_stream, MiptUpdateInfo *info);
+
+/* What the scene's mesh holds.  MIPT_ERR_INVALID_ARG for a scene without a mesh. */
+MIPT_API int mipt_scene_mesh_info(const MiptScene *scene, MiptMeshInfo *out);
+
 /* ---- host-side restatements of the scene model that feeds the path ------------------- */
 
 /* BVH::build (src/bvh.rs:13-161): binned SAH, 8 bins; reorders `tris` in place exactly as

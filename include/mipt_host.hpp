@@ -61,6 +61,64 @@ struct Texture {                                           // src/texture.rs:4-1
     }
 };
 
+// An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
+// it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
+class Mesh {
+  public:
+    std::vector<float> positions, normals, tex_coords;     // 3 / 3 / 2 f32 each
+    std::vector<uint32_t> indices, normal_indices, tex_coord_indices;   // the last two empty = shared with `indices`
+    std::vector<MiptMeshPart> parts;
+    std::vector<float> transforms;                         // empty or parts.size() x 16 (Mat4f data[col][row])
+
+    MiptMeshDesc desc() const {
+        MiptMeshDesc d{};
+        d.positions = positions.data(); d.n_positions = (uint32_t)(positions.size() / 3);
+        d.normals = normals.empty() ? nullptr : normals.data(); d.n_normals = (uint32_t)(normals.size() / 3);
+        d.tex_coords = tex_coords.empty() ? nullptr : tex_coords.data(); d.n_tex_coords = (uint32_t)(tex_coords.size() / 2);
+        d.indices = indices.data(); d.n_indices = (uint32_t)indices.size();
+        d.normal_indices = normal_indices.empty() ? nullptr : normal_indices.data();
+        d.tex_coord_indices = tex_coord_indices.empty() ? nullptr : tex_coord_indices.data();
+        d.parts = parts.data(); d.n_parts = (uint32_t)parts.size();
+        d.transforms = transforms.empty() ? nullptr : transforms.data();
+        return d;
+    }
+    // mipt_mesh_expand: the fat triangles on the host (empty + a log line on error)
+    std::vector<MiptTriangle> expand() const {
+        std::vector<MiptTriangle> out(indices.size() / 3);
+        const MiptMeshDesc d = desc();
+        uint32_t n = 0;
+        if (mipt_mesh_expand(&d, out.data(), (uint32_t)out.size(), &n) != MIPT_OK) { log_error(mipt_last_error()); out.clear(); }
+        return out;
+    }
+    // mipt_scene_create_from_mesh with `materials` / `textures` of a MiptSceneDesc; the handle is owned here
+    int create(const MiptSceneDesc &materials_and_textures, int device_id = 0) {
+        const MiptMeshDesc d = desc();
+        MiptScene *s = nullptr;
+        const int rc = mipt_scene_create_from_mesh(&materials_and_textures, &d, device_id, &s);
+        if (rc != MIPT_OK) { log_error(mipt_last_error()); return rc; }
+        scene_ = std::shared_ptr<MiptScene>(s, [](MiptScene *p) { mipt_scene_destroy(p); });
+        return MIPT_OK;
+    }
+    MiptScene *handle() const { return scene_.get(); }
+    // `transforms` (empty = none) to the device, then REFIT / REBUILD
+    int set_transforms(uint32_t mode = MIPT_UPDATE_REFIT, MiptUpdateInfo *info = nullptr) {
+        const int rc = mipt_scene_set_transforms(scene_.get(), transforms.empty() ? nullptr : transforms.data(), (uint32_t)parts.size(), mode, info);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+    // arrays already in HBM of the scene's device (null = keep the resident one)
+    int update_device(const float *d_positions, const float *d_normals, const float *d_transforms, uint32_t mode = MIPT_UPDATE_REFIT,
+                      void *hip_stream = nullptr, MiptUpdateInfo *info = nullptr) {
+        const int rc = mipt_scene_update_mesh_device(scene_.get(), d_positions, d_normals, d_transforms, mode, hip_stream, info);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+    int info(MiptMeshInfo *out) const { return mipt_scene_mesh_info(scene_.get(), out); }
+
+  private:
+    std::shared_ptr<MiptScene> scene_;
+};
+
 class Scene {                                              // src/scene.rs:12-19
   public:
     Scene() = default;

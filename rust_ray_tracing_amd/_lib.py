@@ -87,6 +87,29 @@ class MiptUpdateInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
+assert MESH_PART.itemsize == 16
+
+
+class MiptMeshDesc(C.Structure):
+    _fields_ = [("positions", C.c_void_p), ("n_positions", C.c_uint32),
+                ("normals", C.c_void_p), ("n_normals", C.c_uint32),
+                ("tex_coords", C.c_void_p), ("n_tex_coords", C.c_uint32),
+                ("indices", C.c_void_p), ("n_indices", C.c_uint32),
+                ("normal_indices", C.c_void_p), ("tex_coord_indices", C.c_void_p),
+                ("parts", C.c_void_p), ("n_parts", C.c_uint32),
+                ("transforms", C.c_void_p)]
+
+
+class MiptMeshInfo(C.Structure):
+    _fields_ = [("n_positions", C.c_uint32), ("n_normals", C.c_uint32), ("n_tex_coords", C.c_uint32), ("n_indices", C.c_uint32),
+                ("n_tris", C.c_uint32), ("n_parts", C.c_uint32), ("has_transforms", C.c_uint32), ("index_streams", C.c_uint32),
+                ("array_bytes", C.c_uint64), ("expanded_bytes", C.c_uint64), ("hbm_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class MiptMultiStats(C.Structure):
     _fields_ = [("total", MiptStats), ("collective_ms", C.c_double), ("wall_ms", C.c_double),
                 ("device_kernel_ms", C.c_double * 8), ("n_devices", C.c_uint32), ("reserved", C.c_uint32)]
@@ -110,6 +133,7 @@ EXPORTS = [
     "mipt_scene_create_from_triangles", "mipt_scene_get_bvh", "mipt_scene_info", "mipt_multi_create_from_triangles", "mipt_multi_scene", "mipt_obj_load_triangles",
     "mipt_scene_update_triangles", "mipt_scene_update_triangles_device", "mipt_multi_update_triangles",
     "mipt_render_batch", "mipt_render_batch_device",
+    "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
 ]
 
 _lib = None
@@ -214,6 +238,16 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_scene_update_triangles_device.restype = C.c_int
     lib.mipt_multi_update_triangles.argtypes = [vp, vp, u32, u32, C.POINTER(MiptUpdateInfo)]
     lib.mipt_multi_update_triangles.restype = C.c_int
+    lib.mipt_mesh_expand.argtypes = [C.POINTER(MiptMeshDesc), vp, u32, C.POINTER(u32)]
+    lib.mipt_mesh_expand.restype = C.c_int
+    lib.mipt_scene_create_from_mesh.argtypes = [C.POINTER(MiptSceneDesc), C.POINTER(MiptMeshDesc), C.c_int, C.POINTER(vp)]
+    lib.mipt_scene_create_from_mesh.restype = C.c_int
+    lib.mipt_scene_set_transforms.argtypes = [vp, vp, u32, u32, C.POINTER(MiptUpdateInfo)]
+    lib.mipt_scene_set_transforms.restype = C.c_int
+    lib.mipt_scene_update_mesh_device.argtypes = [vp, vp, vp, vp, u32, vp, C.POINTER(MiptUpdateInfo)]
+    lib.mipt_scene_update_mesh_device.restype = C.c_int
+    lib.mipt_scene_mesh_info.argtypes = [vp, C.POINTER(MiptMeshInfo)]
+    lib.mipt_scene_mesh_info.restype = C.c_int
     return lib
 
 

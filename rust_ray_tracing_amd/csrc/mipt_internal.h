@@ -26,6 +26,10 @@ int scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptSc
 // the same with the caller's node array (ALREADY validated: mipt_scene_create's host checks) instead of a build; triangles in the tree's order
 int scene_create_from_nodes(const MiptSceneDesc *desc, int device_id, MiptScene **out);
 
+// mipt_scene_create_from_triangles from triangles that are in HBM of `device_id` already (scene_mesh.hip: the expanded mesh); they stay
+// the caller's.  desc supplies the materials and textures only.
+int scene_create_from_resident_triangles(const MiptSceneDesc *desc, const MiptTriangle *d_tris, uint32_t n_tris, int device_id, MiptScene **out);
+
 // ---- scene_update.hip, used by mipt_multi.cpp ----
 // mipt_scene_update_triangles without the exception fence
 int scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info);

@@ -9,6 +9,8 @@
 
 #include <vector>
 
+namespace mipt { struct SceneMesh; }
+
 struct MiptScene {
     int device = 0;
     mipt::DevScene dev{};
@@ -41,11 +43,15 @@ struct MiptScene {
     // (d_nodes), the reference pair index of every record
     uint32_t *d_refit_plan = nullptr, *d_refit_pair = nullptr;
     std::vector<uint32_t> refit_level_off;  // level d = plan[off[d], off[d+1]); empty = no plan yet
+    // the resident indexed mesh of a scene made by mipt_scene_create_from_mesh (scene_mesh.hip); null for a plain scene
+    mipt::SceneMesh *mesh = nullptr;
 };
 
 namespace mipt {
 
 void free_scene(MiptScene *s);
+// the resident mesh of `s` (if any) freed, on the current device (scene_mesh.hip); geometry, materials and workspace stay
+void free_mesh(MiptScene *s);
 // stats buffer, events, CU count: everything a scene needs besides its geometry.  On failure the scene is left for free_scene.
 int scene_finish_workspace(MiptScene *s);
 // A replica of `src` in the memory of `device` by device-to-device copies (xGMI between GPUs of a node; a plain copy on the same
@@ -103,7 +109,10 @@ void release_geometry(MiptScene *s);
 // host -> device copy of a large pageable array through a ring of pinned buffers (scene_device.hip); blocks until it has arrived
 int upload_staged(void *d_dst, const void *h_src, size_t bytes);
 // mipt_scene_update_triangles_device without the exception fence (scene_update.hip; the host entry: mipt_internal.h)
-int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info);
+// expanded_mesh: the call comes from scene_mesh.hip with the expansion of the scene's own mesh (any other caller is refused on a
+// scene that owns a mesh: its resident mesh and the triangles would disagree)
+int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info,
+                        bool expanded_mesh = false);
          // optional: what the first launch of each builder kernel would pay, up front (call with the device set)
 
 } // namespace mipt

@@ -522,16 +522,20 @@ void mipt::attach_geometry(MiptScene *s, SceneGeometry *g) {
 
 // Both ways in end here.  `host_nodes`: the caller's node array (validated by mipt_scene_create, mipt_api.cpp) is uploaded beside the
 // triangles, which are in the tree's order already; else BVH::build runs on the GPU.  The layout kernels are the same.
-static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_nodes, MiptScene **out) {
+// `d_resident` (mipt_scene_create_from_mesh, scene_mesh.hip): the n_resident triangles are in HBM of `device_id` already and stay the
+// caller's; desc->tris / n_tris are not read and nothing is uploaded but the materials and textures.
+static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_nodes, MiptScene **out, const MiptTriangle *d_resident = nullptr,
+                            uint32_t n_resident = 0) {
     if (!desc || !out) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_create_from_triangles: null argument");
     *out = nullptr;
-    if (!desc->tris || desc->n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
-    if (desc->n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(desc->n_tris) + " triangles exceed the 2^25 device-format limit");
+    if (!d_resident && (!desc->tris || desc->n_tris == 0)) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
+    const uint32_t n_tris = d_resident ? n_resident : desc->n_tris;
+    if (n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
+    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(n_tris) + " triangles exceed the 2^25 device-format limit");
     if (host_nodes && (!desc->nodes || (desc->n_nodes & 1u) == 0u)) return fail(MIPT_ERR_BVH, "scene has no BVH nodes, or an even number of them");
     const double t_begin = now_ms();
     mipt::MaterialTables tables;
     { const int rc = mipt::build_material_tables(desc, &tables, false); if (rc) return rc; }     // the textures are staged below, not gathered on the host
-    const uint32_t n_tris = desc->n_tris;
 
     int ndev = 0;
     {
@@ -554,12 +558,12 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     };
     S_HIP(hipSetDevice(device_id));
     // ---- 1. the one host -> device copy ----
-    S_HIP(hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
+    if (!d_resident) S_HIP(hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
     if (host_nodes) S_HIP(hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
     {
         std::thread warm;
         if (!host_nodes) warm = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
-        int rc = up_ring.copy(d_tris, desc->tris, (size_t)n_tris * sizeof(MiptTriangle));
+        int rc = d_resident ? MIPT_OK : up_ring.copy(d_tris, desc->tris, (size_t)n_tris * sizeof(MiptTriangle));
         if (rc == MIPT_OK && host_nodes) rc = up_ring.copy(bvh.d_nodes, desc->nodes, (size_t)desc->n_nodes * sizeof(MiptNode));
         if (rc == MIPT_OK) rc = up_ring.finish();
         if (warm.joinable()) warm.join();
@@ -569,8 +573,9 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     const double t_up = now_ms();
     if (host_nodes) bvh.n_nodes = desc->n_nodes;
     // ---- 2. + 3. the tree and the layout, from the triangles in HBM ----
-    { const int rc = mipt::build_geometry(d_tris, n_tris, desc->n_materials, device_id, host_nodes, &bvh, &geo); if (rc) { cleanup(); return rc; } }
-    (void)hipFree(d_tris); d_tris = nullptr;
+    { const int rc = mipt::build_geometry(d_resident ? d_resident : d_tris, n_tris, desc->n_materials, device_id, host_nodes, &bvh, &geo); if (rc) { cleanup(); return rc; } }
+    if (d_tris) (void)hipFree(d_tris);
+    d_tris = nullptr;
     const double t_build = geo.t_build, t_layout = now_ms();
 
     s = new (std::nothrow) MiptScene();
@@ -610,6 +615,10 @@ int mipt::upload_staged(void *d_dst, const void *h_src, size_t bytes) {
 
 int mipt::scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptScene **out) { return create_on_device(desc, device_id, false, out); }
 int mipt::scene_create_from_nodes(const MiptSceneDesc *desc, int device_id, MiptScene **out) { return create_on_device(desc, device_id, true, out); }
+int mipt::scene_create_from_resident_triangles(const MiptSceneDesc *desc, const MiptTriangle *d_tris, uint32_t n_tris, int device_id, MiptScene **out) {
+    if (!d_tris) return fail(MIPT_ERR_INVALID_ARG, "scene_create_from_resident_triangles: null argument");
+    return create_on_device(desc, device_id, false, out, d_tris, n_tris);
+}
 
 extern "C" int mipt_scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptScene **out) {
     try { return mipt::scene_create_from_triangles(desc, device_id, out); }

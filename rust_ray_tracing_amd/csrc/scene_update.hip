@@ -399,9 +399,12 @@ void mipt::release_geometry(MiptScene *s) {
     s->refit_level_off.clear();
 }
 
-int mipt::scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t st, MiptUpdateInfo *info) {
+int mipt::scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t st, MiptUpdateInfo *info,
+                              bool expanded_mesh) {
     const double t0 = now_ms();
     { const int rc = check_args("mipt_scene_update_triangles_device", s, d_tris, n_tris, mode); if (rc) return rc; }
+    if (s->mesh && !expanded_mesh)
+        return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_update_triangles_device: scene owns a mesh (use mipt_scene_set_transforms / mipt_scene_update_mesh_device)");
     MiptUpdateInfo inf{};
     hipError_t e = hipSetDevice(s->device);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                   // ordered after the caller's earlier work on `st`
@@ -416,6 +419,7 @@ int mipt::scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t
 int mipt::scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info) {
     const double t0 = now_ms();
     { const int rc = check_args("mipt_scene_update_triangles", s, tris, n_tris, mode); if (rc) return rc; }
+    if (s->mesh) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_update_triangles: scene owns a mesh (use mipt_scene_set_transforms / mipt_scene_update_mesh_device)");
     hipError_t e = hipSetDevice(s->device);
     MiptTriangle *d_tris = nullptr;
     if (e == hipSuccess) e = hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle));
@@ -423,7 +427,7 @@ int mipt::scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_t
     int rc = mipt::upload_staged(d_tris, tris, (size_t)n_tris * sizeof(MiptTriangle));
     const double t_up = now_ms();
     MiptUpdateInfo inf{};
-    if (rc == MIPT_OK) rc = mipt::scene_update_device(s, d_tris, n_tris, mode, nullptr, &inf);
+    if (rc == MIPT_OK) rc = mipt::scene_update_device(s, d_tris, n_tris, mode, nullptr, &inf, false);
     (void)hipSetDevice(s->device);
     (void)hipFree(d_tris);
     if (rc) return rc;

@@ -115,6 +115,7 @@ class Scene:  # scene.rs:12-19
         self._handle: Optional[C.c_void_p] = None
         self._handle_device = -1
         self._tri_order: Optional[np.ndarray] = None   # fetch_bvh: tris = (the device's input order)[_tri_order]
+        self.mesh: Optional[dict] = None               # from_mesh: the indexed arrays behind MiptMeshDesc
 
     # -- construction ------------------------------------------------------------------------
     @staticmethod
@@ -251,6 +252,161 @@ class Scene:  # scene.rs:12-19
         if fetch_bvh:
             self._fetch_bvh(h)
         return h
+
+    # -- resident indexed meshes (include/mipt.h "resident indexed meshes") --------------------
+    @staticmethod
+    def from_mesh(positions, normals, tex_coords, indices, parts, materials, textures=(), normal_indices=None, tex_coord_indices=None,
+                  transforms=None) -> "Scene":
+        """A scene held as an indexed mesh: ``positions`` [P,3], ``normals`` [N,3] or None, ``tex_coords`` [T,2] or None, ``indices``
+        [M,3] (position index per corner; ``normal_indices`` / ``tex_coord_indices``: the OBJ model's separate streams, None = shared),
+        ``parts`` as MESH_PART records or (first_tri, n_tris, material_id) rows, ``transforms`` [n_parts,4,4] (Mat4f data[col][row])
+        or None.  Nothing is expanded here: ``expand_mesh`` does it on the host, ``upload_from_mesh`` on the GPU."""
+        sc = Scene.from_arrays(np.zeros(0, dtype=L.TRIANGLE), materials, textures, build_bvh=False)
+
+        def f32(a, width):
+            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, width))
+
+        def u32(a):
+            return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.uint32).reshape(-1))
+
+        p = np.asarray(parts)
+        if p.dtype != L.MESH_PART:
+            rows = np.asarray(parts, dtype=np.uint32).reshape(-1, 3)
+            p = np.zeros(len(rows), dtype=L.MESH_PART)
+            p["first_tri"], p["n_tris"], p["material_id"] = rows[:, 0], rows[:, 1], rows[:, 2]
+        sc.mesh = dict(positions=f32(positions, 3), normals=f32(normals, 3), tex_coords=f32(tex_coords, 2), indices=u32(indices),
+                       normal_indices=u32(normal_indices), tex_coord_indices=u32(tex_coord_indices), parts=np.ascontiguousarray(p),
+                       transforms=None)
+        sc._set_mesh_transforms(transforms)
+        return sc
+
+    def _set_mesh_transforms(self, transforms) -> None:
+        if transforms is None:
+            self.mesh["transforms"] = None
+            return
+        t = np.ascontiguousarray(np.asarray(transforms, dtype=np.float32).reshape(-1, 16))
+        if len(t) != len(self.mesh["parts"]):
+            raise ValueError(f"{len(t)} transforms for {len(self.mesh['parts'])} parts")
+        self.mesh["transforms"] = t
+
+    def mesh_desc(self):
+        """MiptMeshDesc over this scene's mesh arrays (kept alive on the returned object)."""
+        if self.mesh is None:
+            raise RuntimeError("scene has no mesh (Scene.from_mesh)")
+        m = self.mesh
+
+        def pn(a):
+            return (None, 0) if a is None else (L.ptr(a), len(a))
+
+        d = L.MiptMeshDesc()
+        d.positions, d.n_positions = pn(m["positions"])
+        d.normals, d.n_normals = pn(m["normals"])
+        d.tex_coords, d.n_tex_coords = pn(m["tex_coords"])
+        d.indices, d.n_indices = pn(m["indices"])
+        d.normal_indices = pn(m["normal_indices"])[0]
+        d.tex_coord_indices = pn(m["tex_coord_indices"])[0]
+        d.parts, d.n_parts = pn(m["parts"])
+        d.transforms = pn(m["transforms"])[0]
+        d._keep = dict(m)
+        return d
+
+    def expand_mesh(self) -> np.ndarray:
+        """The expansion rule on the host (mipt_mesh_expand): fat triangles in the mesh's own order, also left in ``self.tris``
+        (the tree, if any, is dropped)."""
+        d = self.mesh_desc()
+        out = np.zeros(d.n_indices // 3, dtype=L.TRIANGLE)
+        n = C.c_uint32(0)
+        L.check(L.load().mipt_mesh_expand(C.byref(d), L.ptr(out), len(out), C.byref(n)), "mipt_mesh_expand")
+        self.tris = out[: n.value]
+        self.bvh_nodes = np.zeros(0, dtype=L.NODE)
+        self._tri_order = None
+        return self.tris
+
+    def upload_from_mesh(self, device_id: int = 0, fetch_bvh: bool = False) -> C.c_void_p:
+        """mipt_scene_create_from_mesh: the mesh arrays go up once and stay resident, the GPU expands them and builds the tree.  With
+        ``fetch_bvh`` the Scene is left as ``upload_from_triangles(fetch_bvh=True)`` leaves it (host expansion + the device's tree)."""
+        self.release()
+        self._tri_order = None
+        h = C.c_void_p()
+        d, md = self.desc(), self.mesh_desc()
+        L.check(L.load().mipt_scene_create_from_mesh(C.byref(d), C.byref(md), device_id, C.byref(h)), "mipt_scene_create_from_mesh")
+        self._handle, self._handle_device = h, device_id
+        if fetch_bvh:
+            self.expand_mesh()
+            self._fetch_bvh(h)
+        return h
+
+    def _mesh_mirror(self, mode: int) -> None:
+        """after an update of a mesh scene whose tree is mirrored here: tris / bvh_nodes describe the device again"""
+        if len(self.bvh_nodes) == 0:
+            return
+        order = self._tri_order
+        self.expand_mesh()
+        if mode == L.UPDATE_REBUILD or order is None:
+            self._fetch_bvh(self._handle)
+        else:
+            self.tris, self._tri_order = self.tris[order], order
+            self.bvh_nodes = np.zeros(2 * len(self.tris), dtype=L.NODE)
+            self._fetch_nodes(self._handle)
+
+    def set_transforms(self, transforms, mode: int = L.UPDATE_REFIT) -> dict:
+        """One 4x4 matrix per part from host memory (mipt_scene_set_transforms; None = back to no transforms), then REFIT / REBUILD.
+        Returns MiptUpdateInfo as a dict."""
+        if self._handle is None or self.mesh is None:
+            raise RuntimeError("scene is not resident as a mesh (upload_from_mesh)")
+        old = self.mesh["transforms"]
+        self._set_mesh_transforms(transforms)
+        t = self.mesh["transforms"]
+        info = L.MiptUpdateInfo()
+        rc = L.load().mipt_scene_set_transforms(self._handle, None if t is None else L.ptr(t), len(self.mesh["parts"]), mode, C.byref(info))
+        if rc:
+            self.mesh["transforms"] = old
+        L.check(rc, "mipt_scene_set_transforms")
+        self._mesh_mirror(mode)
+        return info.as_dict()
+
+    def update_mesh_device(self, positions=None, normals=None, transforms=None, mode: int = L.UPDATE_REFIT, stream=None) -> dict:
+        """A deforming mesh from HBM (mipt_scene_update_mesh_device): each argument is a torch tensor on the scene's device (float32,
+        contiguous; [P,3], [N,3], [n_parts,4,4]), a raw device pointer (int), or None = keep what is resident.  ``stream``: a torch
+        stream, a raw hipStream_t or None = torch's current stream (the null stream without torch).  The host mirror of the mesh
+        follows tensors (copied back); after raw pointers it is stale.  Returns MiptUpdateInfo as a dict."""
+        if self._handle is None or self.mesh is None:
+            raise RuntimeError("scene is not resident as a mesh (upload_from_mesh)")
+        m = self.mesh
+        want = {"positions": (len(m["positions"]), 3), "normals": (0 if m["normals"] is None else len(m["normals"]), 3), "transforms": (len(m["parts"]), 16)}
+        ptrs, tensors = {}, {}
+        for name, a in (("positions", positions), ("normals", normals), ("transforms", transforms)):
+            if a is None or isinstance(a, int):
+                ptrs[name] = a
+                continue
+            n, width = want[name]
+            if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.numel() != n * width or not a.is_cuda:
+                raise ValueError(f"{name}: expected a contiguous float32 device tensor of {n} x {width} values")
+            ptrs[name], tensors[name] = a.data_ptr(), a
+        if stream is None:
+            try:
+                import torch
+                stream = torch.cuda.current_stream(self._handle_device).cuda_stream
+            except Exception:
+                stream = None
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        info = L.MiptUpdateInfo()
+        L.check(L.load().mipt_scene_update_mesh_device(self._handle, ptrs["positions"], ptrs["normals"], ptrs["transforms"], mode, stream, C.byref(info)),
+                "mipt_scene_update_mesh_device")
+        for name, a in tensors.items():
+            m[name] = np.ascontiguousarray(a.detach().cpu().numpy().reshape(-1, want[name][1]))
+        if len(tensors) == sum(v is not None for v in ptrs.values()):
+            self._mesh_mirror(mode)
+        return info.as_dict()
+
+    def mesh_info(self) -> dict:
+        """MiptMeshInfo of the resident mesh: counts, parts, whether transforms are applied, HBM held."""
+        if self._handle is None:
+            raise RuntimeError("scene is not resident on a device")
+        inf = L.MiptMeshInfo()
+        L.check(L.load().mipt_scene_mesh_info(self._handle, C.byref(inf)), "mipt_scene_mesh_info")
+        return inf.as_dict()
 
     def _fetch_bvh(self, handle) -> None:
         n = len(self.tris)
