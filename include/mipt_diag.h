@@ -34,6 +34,19 @@ MIPT_DIAG_API int mipt_debug_eval(int op, const float *a, const float *b, uint64
  * (first_bits + n <= 2^32): the exhaustive sweeps of tests/test_gpu_libm.py. */
 MIPT_DIAG_API int mipt_debug_eval_range(int op, uint32_t first_bits, uint64_t n, float y, float *out);
 
+/* The building blocks of shading mode 1 (the wgpu shader's material model; rust_ray_tracing_amd/csrc/pt_device_wgsl.h, the very
+ * functions shade_wgsl inlines), element-wise: row i of `in` -> row i of `out`, host buffers, integers as float bit patterns.
+ *   op 0  sample_texture_bilinear   in: u, v                                   out: r, g, b, a
+ *         over the one texture texels[0 .. tex_w*tex_h) (packed RGBA8 words, rows of tex_w); every index it forms stays inside it
+ *   op 1  build_onb                 in: n.xyz                                  out: tangent.xyz, bitangent.xyz
+ *   op 2  to_world / op 3 to_local  in: n.xyz, l.xyz  (basis of n, and n)      out: xyz
+ *   op 4  sample_ggx_vndf           in: ve.xyz, ax, ay, bits(xorshift state)   out: Ne.xyz, bits(state after the two draws)
+ *   op 5  cosine_hemisphere_from    in: ux, uy  (the two draws)                out: xyz
+ *   op 6  Fresnel / reflect / refract step   in: d.xyz, n.xyz, eta, metallic, base.rgb
+ *                                   out: f0.rgb, fresnel.rgb, normalize(reflect).xyz, normalize(refract).xyz (NaN when k < 0), k
+ * tex_* are read by op 0 only (texels may be NULL otherwise).  n <= 2^26.  Returns as mipt_debug_eval. */
+MIPT_DIAG_API int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels, uint32_t tex_w, uint32_t tex_h, float *out);
+
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 
 /* The library-internal device-layout orders of libmipt.so (rust_ray_tracing_amd/csrc/bvh_build.cpp, hidden there), re-exported for

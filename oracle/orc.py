@@ -95,8 +95,97 @@ def load() -> C.CDLL:
     lib.orc_trace_ray.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(OrcTexture), u32, C.POINTER(f32 * 3), C.POINTER(f32 * 3),
                                   u32, C.POINTER(u32), C.c_int, C.c_int, C.POINTER(f32 * 3)]
     lib.orc_trace_ray.restype = None
+    u64 = C.c_uint64
+    lib.orc_wgsl_sample_texture.argtypes = [C.POINTER(OrcTexture), vp, vp, u64, vp, vp]
+    lib.orc_wgsl_onb.argtypes = [vp, u64, vp, vp]
+    lib.orc_wgsl_frame.argtypes = [C.c_int, vp, vp, u64, vp]
+    lib.orc_wgsl_vndf.argtypes = [vp, vp, vp, vp, u64, C.c_int, vp]
+    lib.orc_wgsl_cosine_hemisphere.argtypes = [vp, u64, C.c_int, vp]
+    lib.orc_wgsl_cosine_from.argtypes = [vp, vp, u64, C.c_int, vp]
+    lib.orc_wgsl_fresnel_step.argtypes = [vp, vp, vp, vp, vp, u64, vp]
+    lib.orc_trace_ray_wgsl.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(OrcTexture), u32, C.POINTER(f32 * 3), C.POINTER(f32 * 3),
+                                       u32, C.POINTER(u32), C.c_int, C.c_int, C.POINTER(f32 * 3), C.POINTER(u64 * 5)]
+    for name in ("orc_wgsl_sample_texture", "orc_wgsl_onb", "orc_wgsl_frame", "orc_wgsl_vndf", "orc_wgsl_cosine_hemisphere",
+                 "orc_wgsl_cosine_from", "orc_wgsl_fresnel_step", "orc_trace_ray_wgsl"):
+        getattr(lib, name).restype = None
     _lib = lib
     return lib
+
+
+# ---- the wgpu material model piece by piece (orc_wgsl_*): numpy in, numpy out ----------------------------------------------------
+def _f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a if shape is None else np.ascontiguousarray(np.broadcast_to(a, shape))
+
+
+def wgsl_sample_texture(tex, u, v):
+    """tex: (h, w, 4) uint8.  Returns (rgba [n,4] f32, texel indices [n,4] int64 into the flattened texture)."""
+    tex = np.ascontiguousarray(tex, dtype=np.uint8)
+    u, v = _f32(u).reshape(-1), _f32(v).reshape(-1)
+    t = OrcTexture(tex.shape[1], tex.shape[0], tex.ctypes.data)
+    out, idx = np.zeros((u.size, 4), np.float32), np.zeros((u.size, 4), np.int64)
+    load().orc_wgsl_sample_texture(C.byref(t), u.ctypes.data, v.ctypes.data, u.size, out.ctypes.data, idx.ctypes.data)
+    return out, idx
+
+
+def wgsl_onb(normal):
+    n = _f32(normal).reshape(-1, 3)
+    t, b = np.zeros_like(n), np.zeros_like(n)
+    load().orc_wgsl_onb(n.ctypes.data, len(n), t.ctypes.data, b.ctypes.data)
+    return t, b
+
+
+def wgsl_frame(op, normal, l):
+    n = _f32(normal).reshape(-1, 3)
+    l = _f32(l, n.shape)
+    out = np.zeros_like(n)
+    load().orc_wgsl_frame(op, n.ctypes.data, l.ctypes.data, len(n), out.ctypes.data)
+    return out
+
+
+def wgsl_vndf(ve, ax, ay, seeds, libm=LIBM_GLIBC235, return_state=False):
+    ve = _f32(ve).reshape(-1, 3)
+    ax, ay = _f32(ax, (len(ve),)), _f32(ay, (len(ve),))
+    st = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32), (len(ve),))).copy()
+    out = np.zeros_like(ve)
+    load().orc_wgsl_vndf(ve.ctypes.data, ax.ctypes.data, ay.ctypes.data, st.ctypes.data, len(ve), libm, out.ctypes.data)
+    return (out, st) if return_state else out
+
+
+def wgsl_cosine_hemisphere(seeds, libm=LIBM_GLIBC235):
+    st = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1).copy()
+    out = np.zeros((st.size, 3), np.float32)
+    load().orc_wgsl_cosine_hemisphere(st.ctypes.data, st.size, libm, out.ctypes.data)
+    return out
+
+
+def wgsl_cosine_from(ux, uy, libm=LIBM_GLIBC235):
+    ux, uy = _f32(ux).reshape(-1), _f32(uy).reshape(-1)
+    out = np.zeros((ux.size, 3), np.float32)
+    load().orc_wgsl_cosine_from(ux.ctypes.data, uy.ctypes.data, ux.size, libm, out.ctypes.data)
+    return out
+
+
+def wgsl_fresnel_step(direction, normal, ior, metallic=0.0, base=(0.5, 0.5, 0.5)):
+    """-> dict of f0 [n,3], fresnel [n,3], specular_dir [n,3], transmitted_dir [n,3], k [n]."""
+    d = _f32(direction).reshape(-1, 3)
+    nn = _f32(normal, d.shape)
+    ior, met, base = _f32(ior, (len(d),)), _f32(metallic, (len(d),)), _f32(base, d.shape)
+    out = np.zeros((len(d), 13), np.float32)
+    load().orc_wgsl_fresnel_step(d.ctypes.data, nn.ctypes.data, ior.ctypes.data, met.ctypes.data, base.ctypes.data, len(d), out.ctypes.data)
+    return dict(f0=out[:, 0:3], fresnel=out[:, 3:6], specular_dir=out[:, 6:9], transmitted_dir=out[:, 9:12], k=out[:, 12], raw=out)
+
+
+def trace_ray_wgsl(tris, nodes, materials, textures, origin, direction, max_depth, seed, cull=0, libm=LIBM_GLIBC235):
+    """trace_wgsl on one ray -> (radiance [3] f32, counters dict, final rng state)."""
+    tris, nodes, materials = np.ascontiguousarray(tris), np.ascontiguousarray(nodes), np.ascontiguousarray(materials)
+    textures = [np.ascontiguousarray(t) for t in textures]
+    o, d, out = (C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in direction]), (C.c_float * 3)()
+    st, cnt = C.c_uint32(int(seed)), (C.c_uint64 * 5)()
+    load().orc_trace_ray_wgsl(tris.ctypes.data, tris.nbytes // 112, nodes.ctypes.data, nodes.nbytes // 32, materials.ctypes.data,
+                              materials.nbytes // 80, _tex_array(textures), len(textures), C.byref(o), C.byref(d), max_depth,
+                              C.byref(st), cull, libm, C.byref(out), C.byref(cnt))
+    return np.array(list(out), np.float32), dict(zip(("rays", "inner_steps", "tri_tests", "hits", "texel_fetches"), list(cnt))), st.value
 
 
 def eval_array(op, a, b=None, libm=LIBM_GLIBC235, threads=1):

@@ -389,13 +389,17 @@ static v3 trace(Ray *ray, uint32_t max_bounces, const SceneView *sc, uint32_t *r
 /* pow/exp/sin/cos/inverseSqrt, the bilinear filter's weights): this is ONE    */
 /* deterministic reading -- one rounded f32 op per operator, the glibc restatement for the  */
 /* transcendentals, exact f32 bilinear weights -- shared with the kernel.      */
-/* "parity unpinned" against a real GPU run.                                   */
+/* "parity unpinned" against a real GPU run.  A second, independent reading of */
+/* the same shader text exists (oracle/pt_oracle_py.py render_wgsl) and must   */
+/* agree with this one bit for bit (tests/test_wgsl_second_reading.py); the    */
+/* pieces have known-answer / float64 tests (tests/test_wgsl_kat.py) through   */
+/* the orc_wgsl_* entry points below.                                          */
 /* ------------------------------------------------------------------------- */
 typedef struct { float x, y, z, w; } v4;
 static inline v3 w_normalize(v3 a) { return v_divs(a, v_length(a)); }          /* normalize(): v / length(v) */
 static inline float w_clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
-static v4 sample_texture(const OrcTexture *t, float u, float v, Ctx *cx) { /* rt_compute.wgsl:499-501; sampler gpu.rs:393-401: linear, repeat */
+static v4 sample_texture_idx(const OrcTexture *t, float u, float v, Ctx *cx, int64_t idx[4]) { /* rt_compute.wgsl:499-501; sampler gpu.rs:393-401: linear, repeat */
     const int64_t W = t->width, H = t->height;
     float uu = u * (float)W - 0.5f, vv = v * (float)H - 0.5f;
     float fu = floorf(uu), fv = floorf(vv);
@@ -414,10 +418,12 @@ static v4 sample_texture(const OrcTexture *t, float u, float v, Ctx *cx) { /* rt
         float bot = t01 * (1.0f - a) + t11 * a;
         out[c] = top * (1.0f - b) + bot * b;
     }
-    cx->s.texel_fetches++;
+    if (cx) cx->s.texel_fetches++;
+    if (idx) { idx[0] = i0 + j0 * W; idx[1] = i1 + j0 * W; idx[2] = i0 + j1 * W; idx[3] = i1 + j1 * W; }
     v4 r = {out[0], out[1], out[2], out[3]};
     return r;
 }
+static v4 sample_texture(const OrcTexture *t, float u, float v, Ctx *cx) { return sample_texture_idx(t, u, v, cx, NULL); }
 
 static void build_orthonormal_basis(v3 n, v3 *tangent, v3 *bitangent) {       /* rt_compute.wgsl:565-569 */
     v3 up = (fabsf(n.z) < 0.9999999f) ? V3(0.0f, 0.0f, 1.0f) : V3(1.0f, 0.0f, 0.0f);
@@ -446,8 +452,7 @@ static v3 sample_ggx_vndf(v3 ve, float ax, float ay, uint32_t *rng, int libm) { 
     v3 Nh = v_add(v_add(v_muls(T1, t1), v_muls(T2, t2)), v_muls(Vh, k));
     return w_normalize(V3(ax * Nh.x, ay * Nh.y, fmaxf(0.0f, Nh.z)));
 }
-static v3 cosine_sample_hemisphere(uint32_t *rng, int libm) {                    /* rt_compute.wgsl:527-551 */
-    float ux = orc_rand_f32(rng), uy = orc_rand_f32(rng);
+static v3 cosine_hemisphere_from(float ux, float uy, int libm) {                 /* rt_compute.wgsl:527-551 after the two draws */
     float ox = 2.0f * ux - 1.0f, oy = 2.0f * uy - 1.0f;
     float dx, dy;
     if (ox == 0.0f && oy == 0.0f) { dx = 0.0f; dy = 0.0f; }
@@ -459,6 +464,37 @@ static v3 cosine_sample_hemisphere(uint32_t *rng, int libm) {                   
     }
     float z = sqrtf(fmaxf(0.0f, 1.0f - dx * dx - dy * dy));
     return V3(dx, dy, z);
+}
+static v3 cosine_sample_hemisphere(uint32_t *rng, int libm) {
+    float ux = orc_rand_f32(rng), uy = orc_rand_f32(rng);
+    return cosine_hemisphere_from(ux, uy, libm);
+}
+
+/* :158-163 -- f0, Schlick Fresnel, reflect and refract for one (direction, sampled normal, eta, metallic, base colour) */
+typedef struct { v3 f0, fresnel, specular_dir, transmitted_dir; float k; } FresnelStep;
+static FresnelStep fresnel_step(v3 dir, v3 sampled_normal, float ior, float metallic, v3 base_color) {
+    FresnelStep o;
+    v3 neg_dir = V3(-dir.x, -dir.y, -dir.z);
+    /* pow(x, 2) and pow(x, 5) have integer literal exponents: read as repeated multiplication (what shader compilers emit;
+     * exp2(y*log2(x)) would be NaN for the negative base 1 - ior on back faces, which no render of the reference shows) */
+    float f0s = ((1.0f - ior) * (1.0f - ior)) / ((1.0f + ior) * (1.0f + ior));
+    o.f0 = V3(f0s * (1.0f - metallic) + base_color.x * metallic, f0s * (1.0f - metallic) + base_color.y * metallic,
+              f0s * (1.0f - metallic) + base_color.z * metallic);                              /* mix(f0, base_color, metallic) */
+    float p1 = 1.0f - v_dot(sampled_normal, neg_dir), p2 = p1 * p1;
+    float p5 = (p2 * p2) * p1;                                                             /* schlick_fresnel, :553-555 */
+    o.fresnel = V3(o.f0.x + (1.0f - o.f0.x) * p5, o.f0.y + (1.0f - o.f0.y) * p5, o.f0.z + (1.0f - o.f0.z) * p5);
+    float two_ndi = 2.0f * v_dot(sampled_normal, dir);                                     /* reflect(I, N) = I - 2 dot(N, I) N */
+    o.specular_dir = w_normalize(v_sub(dir, v_muls(sampled_normal, two_ndi)));
+    {                                                                                      /* refract(I, N, eta); k < 0 (total internal
+                                                                                            * reflection) -> normalize(0) = NaN */
+        float ndi = v_dot(sampled_normal, dir);
+        float k = 1.0f - ior * ior * (1.0f - ndi * ndi);
+        v3 r = (k < 0.0f) ? V3(0.0f, 0.0f, 0.0f)
+                          : v_sub(v_muls(dir, ior), v_muls(sampled_normal, ior * ndi + sqrtf(k)));
+        o.transmitted_dir = w_normalize(r);
+        o.k = k;
+    }
+    return o;
 }
 
 static v3 trace_wgsl(Ray *ray, uint32_t max_depth, const SceneView *sc, uint32_t *rng, Ctx *cx) { /* rt_compute.wgsl:126-229 */
@@ -515,24 +551,8 @@ static v3 trace_wgsl(Ray *ray, uint32_t max_depth, const SceneView *sc, uint32_t
         float alpha = w_clamp(m.roughness * m.roughness, EPSILON, 1.0f);
         v3 neg_dir = V3(-ray->direction.x, -ray->direction.y, -ray->direction.z);
         v3 sampled_normal = to_world(tangent, bitangent, tbn_n, sample_ggx_vndf(to_local(tangent, bitangent, tbn_n, neg_dir), alpha, alpha, rng, libm));
-        /* pow(x, 2) and pow(x, 5) have integer literal exponents: read as repeated multiplication (what shader compilers emit;
-         * exp2(y*log2(x)) would be NaN for the negative base 1 - ior on back faces, which no render of the reference shows) */
-        float f0s = ((1.0f - m.ior) * (1.0f - m.ior)) / ((1.0f + m.ior) * (1.0f + m.ior));
-        v3 f0 = V3(f0s * (1.0f - m.metallic) + m.base_color.x * m.metallic, f0s * (1.0f - m.metallic) + m.base_color.y * m.metallic,
-                   f0s * (1.0f - m.metallic) + m.base_color.z * m.metallic);                   /* mix(f0, base_color, metallic) */
-        float p1 = 1.0f - v_dot(sampled_normal, neg_dir), p2 = p1 * p1;
-        float p5 = (p2 * p2) * p1;                                                             /* schlick_fresnel, :553-555 */
-        v3 fresnel = V3(f0.x + (1.0f - f0.x) * p5, f0.y + (1.0f - f0.y) * p5, f0.z + (1.0f - f0.z) * p5);
-        float two_ndi = 2.0f * v_dot(sampled_normal, ray->direction);                          /* reflect(I, N) = I - 2 dot(N, I) N */
-        v3 specular_dir = w_normalize(v_sub(ray->direction, v_muls(sampled_normal, two_ndi)));
-        v3 transmitted_dir;                                                                    /* refract(I, N, eta) */
-        {
-            float ndi = v_dot(sampled_normal, ray->direction);
-            float k = 1.0f - m.ior * m.ior * (1.0f - ndi * ndi);
-            v3 r = (k < 0.0f) ? V3(0.0f, 0.0f, 0.0f)
-                              : v_sub(v_muls(ray->direction, m.ior), v_muls(sampled_normal, m.ior * ndi + sqrtf(k)));
-            transmitted_dir = w_normalize(r);
-        }
+        const FresnelStep fs = fresnel_step(ray->direction, sampled_normal, m.ior, m.metallic, m.base_color);
+        const v3 fresnel = fs.fresnel, specular_dir = fs.specular_dir, transmitted_dir = fs.transmitted_dir;
         v3 diffuse_dir = w_normalize(to_world(tangent, bitangent, tbn_n, cosine_sample_hemisphere(rng, libm)));
         /* select_bsdf, :231-248 */
         int specular = 0, transmitted = 0;
@@ -598,6 +618,77 @@ void orc_trace_ray(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *node
     Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
     v3 c = trace(&r, max_depth, &sc, rng, &cx);
     out[0] = c.x; out[1] = c.y; out[2] = c.z;
+}
+
+/* Element-wise entry points for the pieces of the wgpu material model (tests/test_wgsl_kat.py, tests/test_gpu_wgsl.py). */
+void orc_wgsl_sample_texture(const OrcTexture *t, const float *u, const float *v, uint64_t n, float *out_rgba, int64_t *out_idx) {
+    for (uint64_t i = 0; i < n; i++) {                                 /* out_idx (may be NULL): the four texel indices read */
+        v4 r = sample_texture_idx(t, u[i], v[i], NULL, out_idx ? out_idx + 4 * i : NULL);
+        out_rgba[4 * i] = r.x; out_rgba[4 * i + 1] = r.y; out_rgba[4 * i + 2] = r.z; out_rgba[4 * i + 3] = r.w;
+    }
+}
+void orc_wgsl_onb(const float *normal, uint64_t n, float *tangent, float *bitangent) {
+    for (uint64_t i = 0; i < n; i++) {
+        v3 t, b;
+        build_orthonormal_basis(V3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]), &t, &b);
+        tangent[3 * i] = t.x; tangent[3 * i + 1] = t.y; tangent[3 * i + 2] = t.z;
+        bitangent[3 * i] = b.x; bitangent[3 * i + 1] = b.y; bitangent[3 * i + 2] = b.z;
+    }
+}
+/* op 0: to_world(tbn, l), 1: to_local(tbn, l) with tbn = the basis of `normal` and the normal itself */
+void orc_wgsl_frame(int op, const float *normal, const float *l, uint64_t n, float *out) {
+    for (uint64_t i = 0; i < n; i++) {
+        v3 nn = V3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]), t, b, x = V3(l[3 * i], l[3 * i + 1], l[3 * i + 2]);
+        build_orthonormal_basis(nn, &t, &b);
+        v3 r = op == 0 ? to_world(t, b, nn, x) : to_local(t, b, nn, x);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+void orc_wgsl_vndf(const float *ve, const float *ax, const float *ay, uint32_t *rng, uint64_t n, int libm, float *out) {
+    for (uint64_t i = 0; i < n; i++) {                                 /* rng[i]: the element's xorshift state, advanced by two draws */
+        v3 r = sample_ggx_vndf(V3(ve[3 * i], ve[3 * i + 1], ve[3 * i + 2]), ax[i], ay[i], &rng[i], libm);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+void orc_wgsl_cosine_hemisphere(uint32_t *rng, uint64_t n, int libm, float *out) {
+    for (uint64_t i = 0; i < n; i++) {
+        v3 r = cosine_sample_hemisphere(&rng[i], libm);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+void orc_wgsl_cosine_from(const float *ux, const float *uy, uint64_t n, int libm, float *out) {
+    for (uint64_t i = 0; i < n; i++) {
+        v3 r = cosine_hemisphere_from(ux[i], uy[i], libm);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+/* out: 13 floats per element = f0.xyz, fresnel.xyz, specular_dir.xyz, transmitted_dir.xyz, refract's k */
+void orc_wgsl_fresnel_step(const float *dir, const float *normal, const float *ior, const float *metallic, const float *base, uint64_t n, float *out) {
+    for (uint64_t i = 0; i < n; i++) {
+        FresnelStep f = fresnel_step(V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), V3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]),
+                                     ior[i], metallic[i], V3(base[3 * i], base[3 * i + 1], base[3 * i + 2]));
+        float *o = out + 13 * i;
+        o[0] = f.f0.x; o[1] = f.f0.y; o[2] = f.f0.z; o[3] = f.fresnel.x; o[4] = f.fresnel.y; o[5] = f.fresnel.z;
+        o[6] = f.specular_dir.x; o[7] = f.specular_dir.y; o[8] = f.specular_dir.z;
+        o[9] = f.transmitted_dir.x; o[10] = f.transmitted_dir.y; o[11] = f.transmitted_dir.z; o[12] = f.k;
+    }
+}
+/* trace_wgsl on one ray; counters_out (may be NULL) = rays, inner_steps, tri_tests, hits, texel_fetches */
+void orc_trace_ray_wgsl(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                        const OrcMaterial *materials, uint32_t n_materials,
+                        const OrcTexture *textures, uint32_t n_textures,
+                        const float o[3], const float d[3], uint32_t max_depth,
+                        uint32_t *rng, int cull, int libm, float out[3], uint64_t counters_out[5]) {
+    SceneView sc = {tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures};
+    Ctx cx; memset(&cx, 0, sizeof cx);
+    cx.stack_cap = 64; cx.cull = cull; cx.cull_scale = 1.0f; cx.libm = libm;
+    Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
+    v3 c = trace_wgsl(&r, max_depth, &sc, rng, &cx);
+    out[0] = c.x; out[1] = c.y; out[2] = c.z;
+    if (counters_out) {
+        counters_out[0] = cx.s.rays; counters_out[1] = cx.s.inner_steps; counters_out[2] = cx.s.tri_tests;
+        counters_out[3] = cx.s.hits; counters_out[4] = cx.s.texel_fetches;
+    }
 }
 
 /* ------------------------------------------------------------------------- */

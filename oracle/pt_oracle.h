@@ -165,6 +165,23 @@ void     orc_trace_ray(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *
                        const float o[3], const float d[3], uint32_t max_depth,
                        uint32_t *rng, int cull, int libm, float out[3]);
 
+/* ---- the wgpu material model (rt_compute.wgsl, shading mode 1) piece by piece, element-wise over n inputs ---- */
+/* linear / repeat sampler (:500-502): out_rgba 4 floats per element; out_idx (may be NULL) the 4 texel indices read: (i0,j0) (i1,j0) (i0,j1) (i1,j1) */
+void     orc_wgsl_sample_texture(const OrcTexture *t, const float *u, const float *v, uint64_t n, float *out_rgba, int64_t *out_idx);
+void     orc_wgsl_onb(const float *normal, uint64_t n, float *tangent, float *bitangent);                  /* :565-569 */
+void     orc_wgsl_frame(int op, const float *normal, const float *l, uint64_t n, float *out);              /* 0 to_world, 1 to_local on the basis of `normal` */
+void     orc_wgsl_vndf(const float *ve, const float *ax, const float *ay, uint32_t *rng, uint64_t n, int libm, float *out);   /* :504-525; rng[i] advances */
+void     orc_wgsl_cosine_hemisphere(uint32_t *rng, uint64_t n, int libm, float *out);                       /* :546-551; rng[i] advances */
+void     orc_wgsl_cosine_from(const float *ux, const float *uy, uint64_t n, int libm, float *out);          /* the same after its two draws */
+/* :158-163: out = 13 floats per element: f0.xyz, fresnel.xyz, normalize(reflect).xyz, normalize(refract).xyz (NaN when k < 0), k */
+void     orc_wgsl_fresnel_step(const float *dir, const float *normal, const float *ior, const float *metallic, const float *base, uint64_t n, float *out);
+/* trace (:126-229) on one explicit ray; counters_out (may be NULL) = rays, inner_steps, tri_tests, hits, texel_fetches */
+void     orc_trace_ray_wgsl(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                            const OrcMaterial *materials, uint32_t n_materials,
+                            const OrcTexture *textures, uint32_t n_textures,
+                            const float o[3], const float d[3], uint32_t max_depth,
+                            uint32_t *rng, int cull, int libm, float out[3], uint64_t counters_out[5]);
+
 #ifdef __cplusplus
 }
 #endif

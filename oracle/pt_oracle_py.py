@@ -491,3 +491,416 @@ def camera_from_pose(position, pitch_deg, yaw_deg):
         m[i][i] = 1
     m[0][:3], m[1][:3], m[2][:3], m[3][:3] = r, u, f, pos
     return m, np.array(pos, np.float32)
+
+
+# ======================================================================================================================
+# Second reading of the wgpu backend's shaders (shading mode 1): src/renderer/backend/gpu/rt_compute.wgsl:100-569 and
+# pp_compute.wgsl:7-34, written from the WGSL text and the WGSL specification's definitions of its builtins -- NOT from
+# pt_oracle.c's trace_wgsl.  tests/test_wgsl_second_reading.py requires the two to agree bit for bit.
+#
+# WGSL leaves several things to the implementation; this project fixes them once and both readings follow:
+#   * every operator is one rounded binary32 operation, nothing is contracted except the explicit fma() at :319;
+#   * sin / cos / exp / pow with a float exponent are the platform libm's (called here through ctypes, like cosf / log10f
+#     above, so agreement also checks the glibc restatement on the arguments mode 1 produces);
+#   * pow(x, 2) and pow(x, 5) -- integer literal exponents -- are products: x*x and ((x*x)*(x*x))*x;
+#   * inverseSqrt(x) is 1 / sqrt(x);  min / max drop a NaN operand;  normalize(v) is v / length(v);
+#   * textureSampleLevel with the linear / repeat sampler (gpu.rs:393-401) is the textbook bilinear filter with weights
+#     in binary32; a texel coordinate that is NaN or whose floor is 1e9 or more in magnitude reads texel column / row 0,
+#     and a NaN weight counts as 0 (the shader leaves non-finite coordinates undefined).
+# The reading also reports which of the shader's rarely taken branches a render went through (WGSL_BRANCHES).
+# ======================================================================================================================
+for _n in ("sinf", "expf"):
+    getattr(_libm, _n).restype = _C.c_float
+    getattr(_libm, _n).argtypes = [_C.c_float]
+_libm.powf.restype = _C.c_float
+_libm.powf.argtypes = [_C.c_float, _C.c_float]
+_libm.fmaf.restype = _C.c_float
+_libm.fmaf.argtypes = [_C.c_float, _C.c_float, _C.c_float]
+
+
+def libm_sinf(x): return F(_libm.sinf(float(F(x))))
+def libm_expf(x): return F(_libm.expf(float(F(x))))
+def libm_powf(x, y): return F(_libm.powf(float(F(x)), float(F(y))))
+def libm_fmaf(a, b, c): return F(_libm.fmaf(float(F(a)), float(F(b)), float(F(c))))
+
+
+W_PI = F(3.1415926535)
+W_PI_OVER_2 = F(1.5707963268)
+W_PI_OVER_4 = F(0.7853981634)
+W_EPSILON = F(0.0001)
+
+WGSL_BRANCHES = ("cutout_continue", "normal_map", "onb_alternate_axis", "lensq_zero", "u_offset_zero", "disk_arm_x", "disk_arm_y",
+                 "lobe_specular", "lobe_transmitted", "lobe_diffuse", "refract_k_negative", "transmitted_break", "specular_break",
+                 "beer_absorption", "roulette_entered", "roulette_break")
+WGSL_COUNTERS = ("rays", "inner_steps", "tri_tests", "hits", "texel_fetches")
+
+
+def wgsl_counters():
+    return {k: 0 for k in WGSL_COUNTERS + WGSL_BRANCHES}
+
+
+def w_neg(a): return (-a[0], -a[1], -a[2])
+def w_normalize(a): return v_div(a, length(a))
+def w_mix(a, b, t): return a * (F(1.0) - t) + b * t                                        # mix(e1, e2, e3) = e1*(1-e3) + e2*e3
+
+
+def w_reflect(i, n):                                        # WGSL reflect(e1, e2) = e1 - 2 * dot(e2, e1) * e2
+    k = F(2.0) * dot(n, i)
+    return v_sub(i, v_scale(n, k))
+
+
+def w_refract(i, n, eta, c=None):                           # WGSL refract: k = 1 - eta^2 (1 - dot(n, i)^2); k < 0 -> 0
+    ndi = dot(n, i)
+    k = F(1.0) - eta * eta * (F(1.0) - ndi * ndi)
+    if k < 0:
+        if c is not None:
+            c["refract_k_negative"] += 1
+        return (F(0), F(0), F(0))
+    return v_sub(v_scale(i, eta), v_scale(n, eta * ndi + np.sqrt(k)))
+
+
+def w_schlick_fresnel(n_dot_v, f0):                         # :553-555
+    p = F(1.0) - n_dot_v
+    p2 = p * p
+    p5 = (p2 * p2) * p
+    return tuple(f + (F(1.0) - f) * p5 for f in f0)
+
+
+def w_build_orthonormal_basis(n, c=None):                   # :565-569 -> (tangent, bitangent)
+    if abs(n[2]) < F(0.9999999):
+        up = (F(0), F(0), F(1))
+    else:
+        up = (F(1), F(0), F(0))
+        if c is not None:
+            c["onb_alternate_axis"] += 1
+    t = w_normalize(cross(up, n))
+    return t, cross(n, t)
+
+
+def w_to_world(tbn, l):                                     # :561-563, column-major mat3x3 times vector
+    t, b, n = tbn
+    return tuple((t[k] * l[0] + b[k] * l[1]) + n[k] * l[2] for k in range(3))
+
+
+def w_to_local(tbn, w):                                     # :557-559, transpose(tbn) * world: one dot product per column
+    t, b, n = tbn
+    return (dot(t, w), dot(b, w), dot(n, w))
+
+
+def w_concentric_sample_disk(u, c=None):                    # :528-543
+    ox, oy = F(2.0) * u[0] - F(1.0), F(2.0) * u[1] - F(1.0)
+    if ox == 0 and oy == 0:
+        if c is not None:
+            c["u_offset_zero"] += 1
+        return (F(0), F(0))
+    if abs(ox) > abs(oy):
+        if c is not None:
+            c["disk_arm_x"] += 1
+        r, theta = ox, W_PI_OVER_4 * (oy / ox)
+    else:
+        if c is not None:
+            c["disk_arm_y"] += 1
+        r, theta = oy, W_PI_OVER_2 - W_PI_OVER_4 * (ox / oy)
+    return (r * libm_cosf(theta), r * libm_sinf(theta))
+
+
+def w_cosine_sample_hemisphere(rng, c=None):                # :546-551
+    ux = rand_f32(rng)
+    uy = rand_f32(rng)
+    d = w_concentric_sample_disk((ux, uy), c)
+    z = np.sqrt(fmax(F(0), F(1.0) - d[0] * d[0] - d[1] * d[1]))
+    return (d[0], d[1], F(z))
+
+
+def w_sample_ggx_vndf(ve, ax, ay, rng, c=None):             # :504-525
+    u1 = rand_f32(rng)
+    u2 = rand_f32(rng)
+    vh = w_normalize((ax * ve[0], ay * ve[1], ve[2]))
+    lensq = vh[0] * vh[0] + vh[1] * vh[1]
+    if lensq > 0:
+        inv = F(1.0) / np.sqrt(lensq)
+        t1v = (-vh[1] * inv, vh[0] * inv, F(0) * inv)
+    else:
+        if c is not None:
+            c["lensq_zero"] += 1
+        t1v = (F(1), F(0), F(0))
+    t2v = cross(vh, t1v)
+    r = np.sqrt(u1)
+    phi = F(2.0) * W_PI * u2
+    t1 = r * libm_cosf(phi)
+    t2 = r * libm_sinf(phi)
+    s = F(0.5) * (F(1.0) + vh[2])
+    t2 = (F(1.0) - s) * np.sqrt(F(1.0) - t1 * t1) + s * t2
+    k = np.sqrt(fmax(F(0), F(1.0) - t1 * t1 - t2 * t2))
+    nh = v_add(v_add(v_scale(t1v, t1), v_scale(t2v, t2)), v_scale(vh, k))
+    return w_normalize((ax * nh[0], ay * nh[1], fmax(F(0), nh[2])))
+
+
+def w_texel_pair(x, size):
+    """One axis of the linear / repeat sampler: (index of the lower texel, index of the upper texel, weight of the upper)."""
+    s = x * F(size) - F(0.5)
+    fl = np.floor(s)
+    frac = s - fl
+    i0 = int(fl) if abs(fl) < F(1e9) else 0                 # NaN compares false: texel 0
+    if frac != frac:
+        frac = F(0)
+    return i0 % size, (i0 + 1) % size, F(frac)              # Python's % is the floor modulus: repeat addressing
+
+
+def w_sample_texture(tex, uv, c=None):                      # :500-502; tex: (h, w, 4) u8 -> 4 floats
+    h, w = tex.shape[:2]
+    i0, i1, a = w_texel_pair(uv[0], w)
+    j0, j1, b = w_texel_pair(uv[1], h)
+    if c is not None:
+        c["texel_fetches"] += 1
+    out = []
+    for ch in range(4):
+        t00, t10 = F(tex[j0, i0, ch]) / F(255.0), F(tex[j0, i1, ch]) / F(255.0)
+        t01, t11 = F(tex[j1, i0, ch]) / F(255.0), F(tex[j1, i1, ch]) / F(255.0)
+        top = w_mix(t00, t10, a)
+        bot = w_mix(t01, t11, a)
+        out.append(w_mix(top, bot, b))
+    return tuple(out)
+
+
+def w_intersect_tri(o, d, tri, best):                       # :296-339; None unless it is a hit closer than `best`
+    v1, v2, v3 = (vec(tri["vertices"][k]["position"]) for k in range(3))
+    e1, e2 = v_sub(v2, v1), v_sub(v3, v1)
+    rce2 = cross(d, e2)
+    det = dot(e1, rce2)
+    inv = F(1.0) / det
+    s = v_sub(o, v1)
+    u = inv * dot(s, rce2)
+    sce1 = cross(s, e1)
+    v = inv * dot(d, sce1)
+    t = inv * dot(e2, sce1)
+    has_hit = bool(t > 0) and not (det < 0 and det > F(-0.0)) and not (u < 0 or u > 1) and not (v < 0 or u + v > 1)
+    if not (has_hit and t < best):
+        return None
+    point = tuple(libm_fmaf(d[k], t, o[k]) for k in range(3))                               # fma(direction, t, origin)
+    front = bool(det > 0)
+    n0, n1, n2 = (vec(tri["vertices"][k]["normal"]) for k in range(3))
+    w = F(1.0) - u - v
+    normal = v_add(v_add(v_scale(n0, w), v_scale(n1, u)), v_scale(n2, v))
+    normal = w_normalize(normal if front else w_neg(normal))
+    t0, t1, t2 = ((F(tri["vertices"][k]["tex_coord_x"]), F(tri["vertices"][k]["tex_coord_y"])) for k in range(3))
+    uv = ((t0[0] * w + t1[0] * u) + t2[0] * v, (t0[1] * w + t1[1] * u) + t2[1] * v)
+    return dict(has_hit=True, point=point, normal=normal, distance=t, uv=uv, material_id=int(tri["material_id"]), front_face=front)
+
+
+def w_intersect_node(o, d, node, max_distance):             # :341-349
+    lo, hi = vec(node["bounds_min"]), vec(node["bounds_max"])
+    tmin = tuple((lo[k] - o[k]) / d[k] for k in range(3))
+    tmax = tuple((hi[k] - o[k]) / d[k] for k in range(3))
+    t1 = tuple(fmin(tmin[k], tmax[k]) for k in range(3))
+    t2 = tuple(fmax(tmin[k], tmax[k]) for k in range(3))
+    t_near = fmax(fmax(t1[0], t1[1]), t1[2])
+    t_far = fmin(fmin(t2[0], t2[1]), t2[2])
+    return t_near if (t_near <= t_far and t_near < max_distance and t_far > 0) else MISS
+
+
+def w_traverse_bvh(o, d, nodes, tris, c):                   # :351-408 (the shader's stack holds 16 nodes; deeper is not followed here)
+    hit = dict(has_hit=False, distance=MISS)
+    stack = []
+    node = nodes[0]
+    c["rays"] += 1
+    while True:
+        if node["num_tris"] > 0:
+            first = int(node["first_tri_or_child"])
+            for i in range(int(node["num_tris"])):
+                c["tri_tests"] += 1
+                h = w_intersect_tri(o, d, tris[first + i], hit["distance"])
+                if h is not None:
+                    hit = h
+            if not stack:
+                break
+            node = stack.pop()
+            continue
+        c["inner_steps"] += 1
+        c1 = nodes[int(node["first_tri_or_child"])]
+        c2 = nodes[int(node["first_tri_or_child"]) + 1]
+        d1, d2 = w_intersect_node(o, d, c1, hit["distance"]), w_intersect_node(o, d, c2, hit["distance"])
+        if d1 > d2:
+            d1, d2 = d2, d1
+            c1, c2 = c2, c1
+        if d1 == MISS:
+            if not stack:
+                break
+            node = stack.pop()
+        else:
+            node = c1
+            if d2 < MISS:
+                stack.append(c2)
+    return hit
+
+
+def w_select_bsdf(m, rng, c):                               # :231-248 -> "specular" | "transmitted" | "diffuse"
+    r = rand_f32(rng)
+    if m["metallic"] > r:
+        c["lobe_specular"] += 1
+        return "specular"
+    if m["metallic"] + m["transmission"] > r:
+        c["lobe_transmitted"] += 1
+        return "transmitted"
+    c["lobe_diffuse"] += 1
+    return "diffuse"
+
+
+def w_set_surface_properties(hit, m, textures, c):          # :251-294; m is a mutable copy of the material
+    if hit["front_face"]:
+        m["ior"] = F(1.0) / m["ior"]
+    NONE = U32
+    if m["base_color_tex_id"] != NONE:
+        t = w_sample_texture(textures[m["base_color_tex_id"]], hit["uv"], c)
+        m["base_color"] = tuple(libm_powf(t[k], F(2.2)) for k in range(3))
+    if m["transparency_tex_id"] != NONE:
+        m["transparency"] = w_sample_texture(textures[m["transparency_tex_id"]], hit["uv"], c)[3]
+    if m["roughness_tex_id"] != NONE:
+        m["roughness"] = w_sample_texture(textures[m["roughness_tex_id"]], hit["uv"], c)[1]
+    if m["metallic_tex_id"] != NONE:
+        m["metallic"] = w_sample_texture(textures[m["metallic_tex_id"]], hit["uv"], c)[2]
+    if m["emission_tex_id"] != NONE:
+        t = w_sample_texture(textures[m["emission_tex_id"]], hit["uv"], c)
+        m["emission"] = tuple(libm_powf(t[k], F(2.2)) for k in range(3))
+    tangent, bitangent = w_build_orthonormal_basis(hit["normal"], c)
+    hit["tbn"] = (tangent, bitangent, hit["normal"])
+    if m["normal_tex_id"] != NONE:
+        c["normal_map"] += 1
+        t = w_sample_texture(textures[m["normal_tex_id"]], hit["uv"], c)
+        hit["normal"] = w_normalize(w_to_world(hit["tbn"], tuple(t[k] * F(2.0) - F(1.0) for k in range(3))))
+        tangent, bitangent = w_build_orthonormal_basis(hit["normal"], c)
+        hit["tbn"] = (tangent, bitangent, hit["normal"])
+
+
+def _w_material(rec):
+    m = {k: F(rec[k]) for k in ("transmission", "ior", "roughness", "metallic", "transparency")}
+    for k in ("base_color", "emission"):
+        m[k] = vec(rec[k])
+    for k in ("base_color_tex_id", "transparency_tex_id", "roughness_tex_id", "metallic_tex_id", "emission_tex_id", "normal_tex_id"):
+        m[k] = int(rec[k])
+    return m
+
+
+def w_trace(o, d, max_ray_depth, nodes, tris, materials, textures, rng, c):   # :126-229
+    one = F(1.0)
+    ray_color, incoming = (one, one, one), (F(0), F(0), F(0))
+    prev_hit_point = o
+    depth = 0
+    while depth < max_ray_depth:
+        hit = w_traverse_bvh(o, d, nodes, tris, c)
+        if not hit["has_hit"]:
+            ray_color = v_mul(ray_color, (one, one, one))                                   # sky colour, then sky strength
+            incoming = v_add(incoming, v_mul((one, one, one), ray_color))
+            break
+        c["hits"] += 1
+        depth += 1
+        m = _w_material(materials[hit["material_id"]])
+        w_set_surface_properties(hit, m, textures, c)
+        transmitted_distance = hit["distance"]
+        if hit["front_face"]:
+            prev_hit_point = hit["point"]
+        else:
+            transmitted_distance = length(v_sub(hit["point"], prev_hit_point))              # distance(a, b) = length(a - b)
+        if m["transparency"] < rand_f32(rng):
+            c["cutout_continue"] += 1
+            o = v_add(hit["point"], v_scale(d, W_EPSILON))
+            continue
+        alpha = fmin(fmax(m["roughness"] * m["roughness"], W_EPSILON), one)                 # clamp(x, lo, hi) = min(max(x, lo), hi)
+        sampled_normal = w_to_world(hit["tbn"], w_sample_ggx_vndf(w_to_local(hit["tbn"], w_neg(d)), alpha, alpha, rng, c))
+        a, b = one - m["ior"], one + m["ior"]
+        f0s = (a * a) / (b * b)
+        f0 = tuple(w_mix(f0s, m["base_color"][k], m["metallic"]) for k in range(3))
+        fresnel = w_schlick_fresnel(dot(sampled_normal, w_neg(d)), f0)
+        specular_dir = w_normalize(w_reflect(d, sampled_normal))
+        transmitted_dir = w_normalize(w_refract(d, sampled_normal, m["ior"], c))
+        diffuse_dir = w_normalize(w_to_world(hit["tbn"], w_cosine_sample_hemisphere(rng, c)))
+        lobe = w_select_bsdf(m, rng, c)
+        if length(fresnel) < rand_f32(rng) and lobe != "specular":
+            ray_color = v_mul(ray_color, m["base_color"])
+            if lobe == "transmitted":
+                new_dir = transmitted_dir
+                if dot(new_dir, hit["normal"]) > 0:
+                    c["transmitted_break"] += 1
+                    break
+                absorption = (one, one, one)
+                if not hit["front_face"]:
+                    c["beer_absorption"] += 1
+                    absorption = tuple(libm_expf(-(one - m["base_color"][k]) * transmitted_distance) for k in range(3))
+                ray_color = v_mul(ray_color, absorption)
+            else:
+                new_dir = diffuse_dir
+        else:
+            if lobe == "specular":
+                ray_color = v_mul(ray_color, fresnel)
+            new_dir = specular_dir
+            if dot(new_dir, hit["normal"]) < 0:
+                c["specular_break"] += 1
+                break
+        rr = one
+        if depth >= 4:
+            c["roulette_entered"] += 1
+            rr = fmax(ray_color[0], fmax(ray_color[2], ray_color[1]))
+            if rr < rand_f32(rng):
+                c["roulette_break"] += 1
+                break
+        ray_color = v_div(ray_color, rr)
+        incoming = v_add(incoming, v_mul(m["emission"], ray_color))
+        o = v_add(hit["point"], v_scale(new_dir, W_EPSILON))
+        d = new_dir
+    return incoming if depth == 0 else v_div(incoming, F(depth))
+
+
+def w_camera_ray(look, x, y, width, height, rng):           # main, :105-115 -> normalised direction
+    dims = (F(width), F(height))
+    aspect = dims[0] / dims[1]
+    sx = ((F(x) / dims[0]) * F(2.0) - F(1.0)) * aspect
+    sy = (F((int(dims[1]) - y) & U32) / dims[1]) * F(2.0) - F(1.0)
+    jx = (rand_f32(rng) * F(2.0) - F(1.0)) * F(0.0005)
+    jy = (rand_f32(rng) * F(2.0) - F(1.0)) * F(0.0005)
+    v4 = (-sx + jx, sy + jy, F(1.0), F(0.0))
+    r = tuple(((look[0][k] * v4[0] + look[1][k] * v4[1]) + look[2][k] * v4[2]) + look[3][k] * v4[3] for k in range(4))   # mat4x4 * vec4
+    n = np.sqrt(((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]) + r[3] * r[3])                  # normalize() of the vec4, then .xyz
+    return (r[0] / n, r[1] / n, r[2] / n)
+
+
+def render_wgsl(tris, nodes, materials, textures, camera, width, height, samples, max_ray_depth, pixels=None, sample_begin=1):
+    """rt_compute.wgsl main + trace for the pixel indices in `pixels` (default: all), samples sample_begin .. sample_begin +
+    samples - 1 (`current_sample`, which the host counts from 1).  The shader blends each sample into an rgba16unorm
+    accumulator; like the C oracle this returns the plain f32 mean of the samples instead, summed in order.
+    Returns ({index: (r, g, b)}, counters) with the traversal counters and the WGSL_BRANCHES tallies."""
+    look = np.asarray(camera["look_at"], dtype=np.float32).reshape(4, 4)
+    pos = vec(np.asarray(camera["position"], dtype=np.float32).reshape(-1)[:3])
+    out, c = {}, wgsl_counters()
+    with np.errstate(all="ignore"):
+        for index in (range(width * height) if pixels is None else pixels):
+            x, y = index % width, index // width                                            # global_id.x, global_id.y
+            final = (F(0), F(0), F(0))
+            for s in range(sample_begin, sample_begin + samples):
+                rng = [(s * 6023 + (757283 * x + 872653746 * y)) & U32]                     # :102
+                d = w_camera_ray(look, x, y, width, height, rng)
+                final = v_add(final, w_trace(pos, d, max_ray_depth, nodes, tris, materials, textures, rng, c))
+            out[index] = v_div(final, F(samples))
+    return out, c
+
+
+def postprocess_wgsl(hdr, divisor=1.0):
+    """pp_compute.wgsl:7-34 on an array of f32 radiance values (any shape) -> uint16 unorm codes of the same shape: the
+    value is divided by `divisor` when that is not 1 (the mean of an accumulated sum), clamped to [0, 1] as the rgba16unorm
+    accumulator stores it, then linear_to_srgb, aces_filmic and the unorm16 store floor(x * 65535 + 0.5)."""
+    flat = np.asarray(hdr, dtype=np.float32).reshape(-1)
+    out = np.zeros(flat.shape, dtype=np.uint16)
+    exponent = F(1.0 / 2.4)                                                                 # an abstract-float constant expression
+    with np.errstate(all="ignore"):
+        for i, v in enumerate(flat):
+            if F(divisor) != 1:
+                v = v / F(divisor)
+            v = fmin(fmax(v, F(0)), F(1))
+            cutoff = F(1.0) if v < F(0.0031308) else F(0.0)
+            higher = F(1.055) * libm_powf(v, exponent) - F(0.055)
+            lower = v * F(12.92)
+            x = w_mix(higher, lower, cutoff)
+            a, b, cc, dd, e = F(2.51), F(0.03), F(2.43), F(0.59), F(0.14)
+            y = (x * (a * x + b)) / (x * (cc * x + dd) + e)
+            y = fmin(fmax(y, F(0)), F(1))
+            out[i] = int(np.floor(y * F(65535.0) + F(0.5)))
+    return out.reshape(np.shape(hdr))

@@ -415,6 +415,9 @@ static int scene_create_many(const MiptSceneDesc *desc, const int *device_ids, i
     // records, both triangle streams -- is produced there by the kernels mipt_scene_create_from_triangles uses after its build
     // (scene_device.hip); further replicas are device-to-device copies.  (Rounds 1-3 laid the scene out on host threads: 0.55 s for
     // 10 M triangles; that code now lives in libmipt_diag.so as the byte-for-byte reference of the kernels, tests/cpp/host_layout.cpp.)
+    // A material's texture id is UINT32_MAX or names a texture with texels (the kernel reads "has a texture" from the width it copies
+    // into its tables): anything else is refused here, with the other host checks, before the first device call.
+    { mipt::MaterialTables checked; const int bad = mipt::build_material_tables(desc, &checked, false); if (bad) return bad; }
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     for (int i = 0; i < n_dev; i++)

@@ -2,9 +2,11 @@
 //
 // NOT part of the product library: libmipt.so exports nothing from this file.  The probe evaluates the kernel's own
 // arithmetic building blocks (pt_device_math.h: the glibc 2.35 restatement, the exact per-ray division, RNG, sRGB
-// quantisation) element-wise, so tests can compare them bit for bit with the CPU oracle on millions of arguments.
+// quantisation; pt_device_wgsl.h: the sampler, basis, VNDF, hemisphere and Fresnel / reflect / refract of shading mode 1)
+// element-wise, so tests can compare them bit for bit with the CPU oracle on millions of arguments.
 #include "../../include/mipt_diag.h"
 #include "pt_device_math.h"
+#include "pt_device_wgsl.h"
 
 #include <stdio.h>
 
@@ -70,6 +72,47 @@ __global__ void debug_eval_range_kernel(int op, uint32_t first_bits, float y, un
     }
 }
 
+// shading mode 1's building blocks (pt_device_wgsl.h), one element per row of `in` (kWgslIn[op] floats) -> one row of `out`
+// (kWgslOut[op] floats); integers travel as float bit patterns.  The texture of op 0 is texels[0 .. W*H) (checked by the host entry).
+constexpr uint32_t kWgslOps = 7;
+constexpr uint32_t kWgslIn[kWgslOps] = {2, 3, 6, 6, 6, 2, 11};
+constexpr uint32_t kWgslOut[kWgslOps] = {4, 6, 3, 3, 4, 3, 13};
+__global__ void debug_wgsl_kernel(int op, const float *__restrict__ in, unsigned long long n, const uint32_t *__restrict__ texels,
+                                  uint32_t tex_w, uint32_t tex_h, float *__restrict__ out, uint32_t ni, uint32_t no) {
+    using namespace mipt;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const float *a = in + i * ni;
+        float *o = out + i * no;
+        switch (op) {
+        case 0: { const V4 r = sample_texture_bilinear(texels, 0u, tex_w, tex_h, a[0], a[1]); o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w; } break;
+        case 1: { V3 t, b; build_onb(mk(a[0], a[1], a[2]), t, b); o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = b.x; o[4] = b.y; o[5] = b.z; } break;
+        case 2:
+        case 3: {
+            const V3 nn = mk(a[0], a[1], a[2]), l = mk(a[3], a[4], a[5]);
+            V3 t, b; build_onb(nn, t, b);
+            const V3 r = (op == 2) ? to_world(t, b, nn, l) : to_local(t, b, nn, l);
+            o[0] = r.x; o[1] = r.y; o[2] = r.z;
+        } break;
+        case 4: {
+            uint32_t rng = __float_as_uint(a[5]);
+            const V3 r = sample_ggx_vndf(mk(a[0], a[1], a[2]), a[3], a[4], rng);
+            o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = __uint_as_float(rng);
+        } break;
+        case 5: { const V3 r = cosine_hemisphere_from(a[0], a[1]); o[0] = r.x; o[1] = r.y; o[2] = r.z; } break;
+        case 6: {
+            const V3 d = mk(a[0], a[1], a[2]), nn = mk(a[3], a[4], a[5]);
+            const V3 f0 = wgsl_f0(a[6], a[7], mk(a[8], a[9], a[10]));
+            const V3 fr = wgsl_schlick_fresnel(dot(nn, mk(-d.x, -d.y, -d.z)), f0);
+            const V3 sp = wgsl_reflect_dir(d, nn), tr = wgsl_refract_dir(d, nn, a[6]);
+            o[0] = f0.x; o[1] = f0.y; o[2] = f0.z; o[3] = fr.x; o[4] = fr.y; o[5] = fr.z; o[6] = sp.x; o[7] = sp.y; o[8] = sp.z;
+            o[9] = tr.x; o[10] = tr.y; o[11] = tr.z; o[12] = wgsl_refract_k(d, nn, a[6]);
+        } break;
+        default: break;
+        }
+    }
+}
+
 struct DevBuf {                       // frees on every exit path
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -110,6 +153,30 @@ int mipt_debug_eval_range(int op, uint32_t first_bits, uint64_t n, float y, floa
     hipLaunchKernelGGL(debug_eval_range_kernel, dim3(2048), dim3(256), 0, nullptr, op, first_bits, y, (unsigned long long)n, (float *)dout.p);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
     if ((e = hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels, uint32_t tex_w, uint32_t tex_h, float *out) {
+    if (op < 0 || op >= (int)kWgslOps || !in || !out || n == 0 || n > (1ull << 26) ||
+        (op == 0 && (!texels || tex_w == 0 || tex_h == 0 || (uint64_t)tex_w * tex_h > (1ull << 24)))) {
+        snprintf(g_err, sizeof g_err, "mipt_debug_wgsl: bad argument");
+        return -1;
+    }
+    const uint64_t in_bytes = n * kWgslIn[op] * 4, out_bytes = n * kWgslOut[op] * 4;
+    DevBuf din, dtex, dout;
+    hipError_t e;
+    if ((e = hipMalloc(&din.p, in_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMalloc(&dout.p, out_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if (op == 0) {
+        const uint64_t tex_bytes = (uint64_t)tex_w * tex_h * 4;
+        if ((e = hipMalloc(&dtex.p, tex_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+        if ((e = hipMemcpy(dtex.p, texels, tex_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    }
+    hipLaunchKernelGGL(debug_wgsl_kernel, dim3(1024), dim3(256), 0, nullptr, op, (const float *)din.p, (unsigned long long)n,
+                       (const uint32_t *)dtex.p, tex_w, tex_h, (float *)dout.p, kWgslIn[op], kWgslOut[op]);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+    if ((e = hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
 }
 

@@ -511,36 +511,18 @@ def test_fuzz_random_scenes_match_oracle(rrt, orc, seed):
 
 
 def _pbr_scene(rrt, n_target=40000, tex_size=32):
-    """Atrium with materials that exercise every branch of the wgpu shader: mirrors, rough metals, glass, alpha cut-out,
-    emitters, and textures in all six slots (base, transparency, roughness, metallic, emission, normal)."""
-    from rust_ray_tracing_amd import synth
-    tris, mats, texs, cam = synth.make_scene("atrium", n_target=n_target, tex_size=tex_size)
-    rng = np.random.default_rng(77)
-    texs = list(texs) + [rng.integers(0, 256, (16, 16, 4), dtype=np.uint8) for _ in range(3)]
-    nt = len(texs)
-    names = list(mats.keys())
-    for i, k in enumerate(names):
-        m = mats[k]
-        m["roughness"] = [1.0, 0.05, 0.3, 0.6][i % 4]
-        m["metallic"] = [0.0, 1.0, 0.5, 0.0, 0.0][i % 5]
-        m["transmission"] = [0.0, 0.0, 0.0, 1.0, 0.6][i % 5]
-        m["transparency"] = 1.0 if i % 6 else 0.5
-        m["ior"] = [1.45, 1.33, 2.4][i % 3]
-        if i % 7 == 3: m["roughness_tex_id"] = nt - 1
-        if i % 7 == 4: m["metallic_tex_id"] = nt - 2
-        if i % 7 == 5: m["normal_tex_id"] = nt - 3
-        if i % 7 == 6: m["transparency_tex_id"] = nt - 1
-        if i % 9 == 2: m["emission_tex_id"] = nt - 2
-    sc = rrt.Scene.from_arrays(tris, mats, texs)
-    sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
-    return sc
+    sys.path.insert(0, os.path.join(HERE, "tools"))
+    from wgsl_scenes import pbr_scene                       # shared with tests/test_wgsl_second_reading.py and tests/test_gpu_wgsl.py
+    return pbr_scene(rrt, n_target=n_target, tex_size=tex_size)
 
 
 @pytest.mark.parametrize("traversal,margin", [(0, 0.0), (1, 0.0), (1, 0.0078125)])
 def test_wgpu_material_model_matches_its_oracle(rrt, orc, traversal, margin):
     """the wgpu shader's material model (rt_compute.wgsl) as shading mode 1 -- kernel vs the oracle's
-    restatement of the same shader, bit for bit (radiance, RGBA8, counters).  Pinned only against that restatement: the
-    reference has no CPU implementation of this model and WGSL leaves the transcendental / filtering precision open."""
+    restatement of the same shader, bit for bit (radiance, RGBA8, counters).  The reference has no CPU implementation of this
+    model and WGSL leaves the transcendental / filtering precision open, so the oracle's restatement is itself held by a second,
+    independent reading of the shader (oracle/pt_oracle_py.py render_wgsl, tests/test_wgsl_second_reading.py) and by known-answer
+    and float64 property tests (tests/test_wgsl_kat.py); more scenes, the fuzz and the device probes are in tests/test_gpu_wgsl.py."""
     sc = _pbr_scene(rrt)
     w, h, spp, depth = 128, 72, 4, 24
     hdr, rgba, st = _render(rrt, sc, w, h, spp, depth, traversal=traversal, cull_margin=margin, shading=rrt.SHADING_WGPU)
