@@ -47,6 +47,15 @@ MIPT_DIAG_API int mipt_debug_eval_range(int op, uint32_t first_bits, uint64_t n,
  * tex_* are read by op 0 only (texels may be NULL otherwise).  n <= 2^26.  Returns as mipt_debug_eval. */
 MIPT_DIAG_API int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels, uint32_t tex_w, uint32_t tex_h, float *out);
 
+/* The two kernels of the frame epilogue that include/mipt.h reaches only through mipt_render_multi and MIPT_FLAG_TOUCHED, launched by the
+ * product's own launchers (pt_kernel.hip launch_divide / launch_popcount, linked into this library unchanged) on the CALLER'S DEVICE
+ * buffers, stream-ordered on `stream` (a hipStream_t, NULL = the null stream) without synchronising:
+ *   divide    d_buf[i] = d_buf[i] / divisor in place, i < n_floats  (cpu.rs:60 on a reduced sum buffer)
+ *   popcount  *d_out += number of set bits in d_bitmap[0 .. n_words)   (it adds: the caller presets *d_out)
+ * Returns 0, -1 (null pointer or a count of zero; nothing is launched) or -2 (HIP error). */
+MIPT_DIAG_API int mipt_debug_divide(float *d_buf, uint64_t n_floats, float divisor, void *stream);
+MIPT_DIAG_API int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words, uint64_t *d_out, void *stream);
+
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 
 /* The library-internal device-layout orders of libmipt.so (rust_ray_tracing_amd/csrc/bvh_build.cpp, hidden there), re-exported for

@@ -7,6 +7,7 @@
 #include "../../include/mipt_diag.h"
 #include "pt_device_math.h"
 #include "pt_device_wgsl.h"
+#include "pt_kernel.h"
 
 #include <stdio.h>
 
@@ -178,6 +179,20 @@ int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels,
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
     if ((e = hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
+}
+
+// the frame epilogue's two helpers that have no entry point of their own in include/mipt.h: the product's launchers (pt_kernel.hip,
+// linked into this library unchanged) on the caller's device buffers, stream-ordered, no synchronisation
+int mipt_debug_divide(float *d_buf, uint64_t n_floats, float divisor, void *stream) {
+    if (!d_buf || n_floats == 0) { snprintf(g_err, sizeof g_err, "mipt_debug_divide: bad argument"); return -1; }
+    const hipError_t e = mipt::launch_divide(d_buf, (unsigned long long)n_floats, divisor, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail(e, "launch_divide");
+}
+
+int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words, uint64_t *d_out, void *stream) {
+    if (!d_bitmap || !d_out || n_words == 0) { snprintf(g_err, sizeof g_err, "mipt_debug_popcount: bad argument"); return -1; }
+    const hipError_t e = mipt::launch_popcount(d_bitmap, (unsigned long long)n_words, (unsigned long long *)d_out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail(e, "launch_popcount");
 }
 
 const char *mipt_diag_last_error(void) { return g_err; }

@@ -253,7 +253,16 @@ def test_tonemap_device_matches_render_path(rrt):
     L.check(rrt.load().mipt_tonemap_device(C.c_void_p(d.data_ptr()), 96 * 54, 4.0, C.c_void_p(out.data_ptr()), None), "tonemap")
     torch.cuda.synchronize()
     got = out.cpu().numpy().reshape(54, 96, 4)
-    assert np.mean(got != rgba) < 0.01            # (x*4)/4 == x except at f32 overflow/denormal edges
+    sys.path.insert(0, os.path.join(HERE, "tools"))
+    from epilogue_model import rgba8_model
+    x4 = hdr * np.float32(4)
+    assert np.array_equal(got, rgba8_model(x4, 4.0))                       # the kernel is the model, byte for byte
+    # against the render path: (x*4)/4 == x except where x*4 overflows or x/4's denormal rounds -- only those pixels may differ
+    with np.errstate(all="ignore"):
+        back = x4 / np.float32(4)
+    moved = np.any((back.view(np.uint32) != hdr.view(np.uint32)) & ~(np.isnan(back) & np.isnan(hdr)), axis=-1)
+    print(f"pixels whose radiance does not survive x * 4 / 4: {int(moved.sum())} of {moved.size}")
+    assert np.array_equal(got[~moved], rgba[~moved]) and moved.mean() < 0.01
     assert np.array_equal(got[..., 3], rgba[..., 3])
 
 
