@@ -241,6 +241,60 @@ MIPT_API int mipt_render_batch(MiptScene *scene, const MiptCamera *cameras, uint
 MIPT_API int mipt_render_batch_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
                                       float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats);
 
+/* ---- ray queries: closest hit and occlusion for the caller's rays -----------------------------------------------------------
+ * The traversal of the trace kernel, Ray::traverse_bvh (cpu/ray.rs:84-139), run over rays the caller supplies instead of camera
+ * and scatter rays (csrc/ray_query.hip).  Nothing is generated or shaded: rays in, hits out.
+ *
+ * Closest hit.  hits[i] is exactly what traverse_bvh leaves in hit_info for ray i when hit_info.distance starts at rays[i].t_max
+ * (t_max = 1e30f: the reference call itself): the reference's visit order (nearer child first, the other pushed; the root is not
+ * slab-tested); a triangle replaces the hit iff has_hit && t < distance -- strict, so among equal t the first in visit order stays
+ * (SURVEY T6); has_hit in the negated-OR form of ray.rs:56-59 (a NaN u or v passes, a NaN t fails); one rounded f32 operation per
+ * operator, nothing fused.  t, u, v are the bits intersect_tri computed for the winning triangle (a NaN that this arithmetic
+ * produces -- u or v of a degenerate winner -- is a NaN everywhere; its sign and payload are the implementation's, as in IEEE 754:
+ * gfx950 and an x86 host differ there).  The direction is used as given
+ * (not normalised: t is in units of its length).  Zero, denormal, huge, infinite or NaN components neither trap nor hang: such a
+ * ray takes IEEE divisions in the slab test instead of the exact reciprocal path and returns what the reference arithmetic returns.
+ *
+ * prim.  The index of the triangle in the array the scene was last built from -- "the caller's order" of the update section below:
+ * the tree order passed to mipt_scene_create; for scenes built on the device (mipt_scene_create_from_triangles / _from_mesh, or
+ * after a REBUILD) the caller's own order, i.e. tri_order_out[tree index] of mipt_scene_get_bvh.
+ *
+ * Occlusion.  occluded[i] = 1 iff some triangle the traversal tests has has_hit && t < t_max, else 0; a ray stops at its first
+ * such triangle.  MIPT_TRAVERSAL_REFERENCE tests every triangle whose leaf the un-culled slab tests reach, whatever the order.
+ * With MIPT_TRAVERSAL_CULLED a child is skipped iff !(t_near < t_max * (1 + cull_margin)): the bound stays at t_max, so the answer
+ * does not depend on the order either.
+ *
+ * Options (NULL = all zero): traversal / cull_margin as in MiptOptions (closest hit culls against the shrinking
+ * best * (1 + cull_margin), as the trace kernel does); flags: MIPT_FLAG_COUNT only.  stats (may be NULL): kernel_ms and
+ * stack_overflows always; with MIPT_FLAG_COUNT also rays, inner_steps, tri_tests, hits (rays that hit / are occluded) and
+ * max_stack; every other field 0.
+ *
+ * Errors.  Checked before any device work, MIPT_ERR_INVALID_ARG with a message in mipt_last_error(): a null scene, rays or output;
+ * n_rays >= MIPT_QUERY_MAX_RAYS; an unknown traversal or flag; a negative or non-finite cull_margin; non-zero reserved option
+ * fields; for the _device entries rays / hits not 16-byte aligned, or a pointer that is not device memory of the scene's device.
+ * n_rays == 0 is MIPT_OK without a launch.  A traversal-stack overflow (more than 64 entries) is MIPT_ERR_STACK after the results
+ * are written, as in mipt_render.  After any error the scene renders and queries as before.
+ *
+ * The _device entries take buffers in HBM of the scene's device (e.g. torch tensors), are ordered after the earlier work of
+ * `hip_stream` (hipStream_t, NULL = the null stream) and block until done, like mipt_render_device.  Queries see the geometry of
+ * the last successful update (REFIT, REBUILD, mipt_scene_set_transforms, mipt_scene_update_mesh_device) and work on a replica
+ * handle from mipt_multi_scene. */
+typedef struct { float origin[3]; float t_max; float direction[3]; uint32_t reserved; } MiptRay;   /* 32 B; reserved is ignored */
+typedef struct { float t, u, v; uint32_t prim; } MiptHit;                                          /* 16 B */
+#define MIPT_HIT_NONE        0xffffffffu   /* prim of a miss; then t = 1e30f (HitInfo::default, ray.rs:214-226), u = v = 0 */
+#define MIPT_HIT_FRONT_FACE  0x80000000u   /* bit 31 of prim: det > 0 (ray.rs:39); triangle = prim & 0x01ffffff */
+typedef struct { uint32_t traversal; float cull_margin; uint32_t flags; uint32_t reserved[5]; } MiptQueryOptions;  /* NULL = all zero */
+#define MIPT_QUERY_MAX_RAYS 2147483648ull
+
+MIPT_API int mipt_query_closest(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt,
+                                MiptHit *hits, MiptStats *stats);
+MIPT_API int mipt_query_closest_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt,
+                                       MiptHit *d_hits, void *hip_stream, MiptStats *stats);
+MIPT_API int mipt_query_occluded(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt,
+                                 uint8_t *occluded, MiptStats *stats);
+MIPT_API int mipt_query_occluded_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt,
+                                        uint8_t *d_occluded, void *hip_stream, MiptStats *stats);
+
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);
 /* d_packed_all: tile_world slices of mipt_packed_pixels()*3 floats, rank-major (the layout an

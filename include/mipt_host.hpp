@@ -61,6 +61,26 @@ struct Texture {                                           // src/texture.rs:4-1
     }
 };
 
+// mipt_query_closest / mipt_query_occluded on any resident scene handle, vectors in and out (MIPT_ERR_STACK leaves the results written)
+inline int query_closest_on(MiptScene *scene, const std::vector<MiptRay> &rays, std::vector<MiptHit> &hits, const MiptQueryOptions *opt = nullptr,
+                            MiptStats *stats = nullptr) {
+    hits.resize(rays.size());
+    static const MiptRay no_ray{};
+    static MiptHit no_hit{};
+    const int rc = mipt_query_closest(scene, rays.empty() ? &no_ray : rays.data(), rays.size(), opt, hits.empty() ? &no_hit : hits.data(), stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+inline int query_occluded_on(MiptScene *scene, const std::vector<MiptRay> &rays, std::vector<uint8_t> &occluded, const MiptQueryOptions *opt = nullptr,
+                             MiptStats *stats = nullptr) {
+    occluded.resize(rays.size());
+    static const MiptRay no_ray{};
+    static uint8_t no_byte = 0;
+    const int rc = mipt_query_occluded(scene, rays.empty() ? &no_ray : rays.data(), rays.size(), opt, occluded.empty() ? &no_byte : occluded.data(), stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -114,6 +134,13 @@ class Mesh {
         return rc;
     }
     int info(MiptMeshInfo *out) const { return mipt_scene_mesh_info(scene_.get(), out); }
+    // ray queries on the resident mesh scene (mipt_query_closest / mipt_query_occluded): hits[i] / occluded[i] for rays[i]
+    int query_closest(const std::vector<MiptRay> &rays, std::vector<MiptHit> &hits, const MiptQueryOptions *opt = nullptr, MiptStats *stats = nullptr) {
+        return query_closest_on(scene_.get(), rays, hits, opt, stats);
+    }
+    int query_occluded(const std::vector<MiptRay> &rays, std::vector<uint8_t> &occluded, const MiptQueryOptions *opt = nullptr, MiptStats *stats = nullptr) {
+        return query_occluded_on(scene_.get(), rays, occluded, opt, stats);
+    }
 
   private:
     std::shared_ptr<MiptScene> scene_;
@@ -212,6 +239,16 @@ class Scene {                                              // src/scene.rs:12-19
         multi_ = std::shared_ptr<MiptMulti>(m, [](MiptMulti *p) { mipt_multi_destroy(p); });
         multi_devices_ = n_devices;
         return m;
+    }
+
+    // ray queries on the root replica of the scene's device residency (created on first use, like render_node's)
+    int query_closest(const std::vector<MiptRay> &rays, std::vector<MiptHit> &hits, const MiptQueryOptions *opt = nullptr, MiptStats *stats = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? query_closest_on(mipt_multi_scene(m, 0), rays, hits, opt, stats) : MIPT_ERR_HIP;
+    }
+    int query_occluded(const std::vector<MiptRay> &rays, std::vector<uint8_t> &occluded, const MiptQueryOptions *opt = nullptr, MiptStats *stats = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? query_occluded_on(mipt_multi_scene(m, 0), rays, occluded, opt, stats) : MIPT_ERR_HIP;
     }
 
   private:

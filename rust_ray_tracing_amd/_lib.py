@@ -87,6 +87,18 @@ class MiptUpdateInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+# ---- ray queries (include/mipt.h "ray queries") ----
+RAY = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])   # MiptRay
+HIT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])                               # MiptHit
+assert RAY.itemsize == 32 and HIT.itemsize == 16
+HIT_NONE, HIT_FRONT_FACE, HIT_TRI_MASK = 0xFFFFFFFF, 0x80000000, 0x01FFFFFF
+QUERY_MAX_RAYS = 1 << 31
+
+
+class MiptQueryOptions(C.Structure):
+    _fields_ = [("traversal", C.c_uint32), ("cull_margin", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -133,6 +145,7 @@ EXPORTS = [
     "mipt_scene_create_from_triangles", "mipt_scene_get_bvh", "mipt_scene_info", "mipt_multi_create_from_triangles", "mipt_multi_scene", "mipt_obj_load_triangles",
     "mipt_scene_update_triangles", "mipt_scene_update_triangles_device", "mipt_multi_update_triangles",
     "mipt_render_batch", "mipt_render_batch_device",
+    "mipt_query_closest", "mipt_query_closest_device", "mipt_query_occluded", "mipt_query_occluded_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
 ]
 
@@ -248,6 +261,15 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_scene_update_mesh_device.restype = C.c_int
     lib.mipt_scene_mesh_info.argtypes = [vp, C.POINTER(MiptMeshInfo)]
     lib.mipt_scene_mesh_info.restype = C.c_int
+    qo = C.POINTER(MiptQueryOptions)
+    lib.mipt_query_closest.argtypes = [vp, vp, u64, qo, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_closest.restype = C.c_int
+    lib.mipt_query_closest_device.argtypes = [vp, vp, u64, qo, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_closest_device.restype = C.c_int
+    lib.mipt_query_occluded.argtypes = [vp, vp, u64, qo, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_occluded.restype = C.c_int
+    lib.mipt_query_occluded_device.argtypes = [vp, vp, u64, qo, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_occluded_device.restype = C.c_int
     return lib
 
 

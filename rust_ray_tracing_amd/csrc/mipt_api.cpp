@@ -63,7 +63,7 @@ void mipt::free_scene(MiptScene *s) {
     (void)hipSetDevice(s->device);
     mipt::free_mesh(s);
     void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
-                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams};
+                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams, s->d_qrays, s->d_qout};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);

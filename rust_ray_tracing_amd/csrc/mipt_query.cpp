@@ -1,0 +1,173 @@
+// mipt_query.cpp -- the ray-query entry points of include/mipt.h (mipt_query_closest*, mipt_query_occluded*): argument checks,
+// staging for the host entries and the launch of ray_query.hip's kernel.  Host C++ only; every device operation is stream-ordered HIP.
+#include "../../include/mipt.h"
+#include "pt_kernel.h"
+#include "mipt_internal.h"
+#include "mipt_scene.h"
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <exception>
+#include <new>
+
+static_assert(sizeof(MiptRay) == 32 && sizeof(MiptHit) == 16 && sizeof(MiptQueryOptions) == 32, "ABI struct sizes (tests/test_query_abi.py)");
+
+namespace {
+
+int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    mipt_internal_set_error(buf);
+    return code;
+}
+#define Q_HIP(expr)                                                                             \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess)                                                                  \
+            return fail(MIPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));          \
+    } while (0)
+
+int ensure(void **p, size_t *have, size_t want_bytes) {
+    if (*have >= want_bytes && *p) return MIPT_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
+    Q_HIP(hipMalloc(p, want_bytes));
+    *have = want_bytes;
+    return MIPT_OK;
+}
+
+// everything that needs neither the scene's contents nor a device
+int validate(const char *who, const MiptScene *scene, const void *rays, const void *out, uint64_t n_rays, const MiptQueryOptions *opt) {
+    if (!scene || !rays || !out) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, rays or output", who);
+    if (n_rays >= MIPT_QUERY_MAX_RAYS) return fail(MIPT_ERR_INVALID_ARG, "%s: n_rays %llu: must stay below 2^31", who, (unsigned long long)n_rays);
+    if (opt) {
+        if (opt->traversal > MIPT_TRAVERSAL_CULLED) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown traversal %u", who, opt->traversal);
+        if (opt->flags & ~(uint32_t)MIPT_FLAG_COUNT) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_FLAG_COUNT is accepted", who, opt->flags);
+        if (!(opt->cull_margin >= 0.0f) || !std::isfinite(opt->cull_margin))
+            return fail(MIPT_ERR_INVALID_ARG, "%s: cull_margin must be finite and >= 0", who);
+        for (uint32_t r : opt->reserved)
+            if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
+    }
+    return MIPT_OK;
+}
+
+int device_buffer_check(const char *who, const void *p, int device, const char *name) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) (void)hipGetLastError();         // an unregistered host pointer is reported as an error: clear it
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: %s is not device memory of the scene's device %d", who, name, device);
+    return MIPT_OK;
+}
+
+// the launch, with every argument already checked; d_rays / d_out in HBM of the scene's device
+int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, void *d_out, bool anyhit,
+                 hipStream_t stream, MiptStats *stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_rays == 0) return MIPT_OK;
+    const bool count = opt && (opt->flags & MIPT_FLAG_COUNT) != 0;
+    const bool cull = opt && opt->traversal == MIPT_TRAVERSAL_CULLED;
+    Q_HIP(hipSetDevice(scene->device));
+
+    mipt::DevQuery q{};
+    q.rays = reinterpret_cast<const float4 *>(d_rays);
+    q.out = d_out;
+    q.tri_order = scene->d_tri_order;
+    q.n_rays = n_rays;
+    q.cull_scale = 1.0f + (opt ? opt->cull_margin : 0.0f);
+    q.stats = scene->d_stats;
+
+    long long grid = (long long)scene->n_cu * mipt::query_blocks_per_cu(count, cull, anyhit);
+    const long long need_blocks = (long long)((n_rays + mipt::kBlockThreads - 1) / mipt::kBlockThreads);
+    if (grid > need_blocks) grid = need_blocks;
+    if (grid < 1) grid = 1;
+    const size_t waves = (size_t)grid * mipt::kWavesPerBlock;
+    if (waves > scene->ovf_waves) {
+        if (scene->d_ovf) { (void)hipFree(scene->d_ovf); scene->d_ovf = nullptr; scene->ovf_waves = 0; }
+        Q_HIP(hipMalloc((void **)&scene->d_ovf, waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t)));
+        scene->ovf_waves = waves;
+    }
+    q.ovf = scene->d_ovf;
+
+    Q_HIP(hipMemsetAsync(scene->d_stats, 0, sizeof(mipt::DevStats), stream));
+    Q_HIP(hipEventRecord(scene->ev0, stream));
+    Q_HIP(mipt::launch_ray_query(scene->dev, q, count, cull, anyhit, (int)grid, stream));
+    Q_HIP(hipEventRecord(scene->ev1, stream));
+    mipt::DevStats hs;
+    Q_HIP(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
+    Q_HIP(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    Q_HIP(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
+    if (stats) {
+        stats->kernel_ms = ms;
+        stats->stack_overflows = hs.stack_overflows;
+        if (count) {
+            stats->rays = hs.rays; stats->inner_steps = hs.inner_steps; stats->tri_tests = hs.tri_tests;
+            stats->hits = hs.hits; stats->max_stack = hs.max_stack;
+        }
+    }
+    if (hs.stack_overflows)
+        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
+                    hs.stack_overflows, mipt::kStackLds + mipt::kStackOvf);
+    return MIPT_OK;
+}
+
+int query_device(const char *who, MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, void *d_out,
+                 bool anyhit, void *hip_stream, MiptStats *stats) {
+    int rc = validate(who, scene, d_rays, d_out, n_rays, opt);
+    if (rc) return rc;
+    if (((uintptr_t)d_rays & 15u) || (!anyhit && ((uintptr_t)d_out & 15u)))
+        return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", who, ((uintptr_t)d_rays & 15u) ? "d_rays" : "d_hits");
+    if (n_rays == 0) return query_launch(scene, nullptr, 0, opt, nullptr, anyhit, nullptr, stats);       // MIPT_OK, no device work
+    if ((rc = device_buffer_check(who, d_rays, scene->device, "d_rays"))) return rc;
+    if ((rc = device_buffer_check(who, d_out, scene->device, anyhit ? "d_occluded" : "d_hits"))) return rc;
+    return query_launch(scene, d_rays, n_rays, opt, d_out, anyhit, (hipStream_t)hip_stream, stats);
+}
+
+int query_host(const char *who, MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, void *out, bool anyhit,
+               MiptStats *stats) {
+    int rc = validate(who, scene, rays, out, n_rays, opt);
+    if (rc) return rc;
+    if (n_rays == 0) return query_launch(scene, nullptr, 0, opt, nullptr, anyhit, nullptr, stats);
+    Q_HIP(hipSetDevice(scene->device));
+    const size_t out_bytes = (size_t)n_rays * (anyhit ? 1u : sizeof(MiptHit));
+    if ((rc = ensure(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
+    if ((rc = ensure(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
+    Q_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
+    rc = query_launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, scene->d_qout, anyhit, nullptr, stats);
+    if (rc && rc != MIPT_ERR_STACK) return rc;
+    Q_HIP(hipMemcpy(out, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+} // namespace
+
+// No C++ exception may cross the C ABI: allocation failures become status codes.
+#define Q_NO_THROW(call)                                                                                                \
+    try { return call; }                                                                                               \
+    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }                        \
+    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, "internal error: %s", e.what()); }
+
+extern "C" {
+
+int mipt_query_closest(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, MiptHit *hits, MiptStats *stats) {
+    Q_NO_THROW(query_host("mipt_query_closest", scene, rays, n_rays, opt, hits, false, stats))
+}
+int mipt_query_closest_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, MiptHit *d_hits,
+                              void *hip_stream, MiptStats *stats) {
+    Q_NO_THROW(query_device("mipt_query_closest_device", scene, d_rays, n_rays, opt, d_hits, false, hip_stream, stats))
+}
+int mipt_query_occluded(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, uint8_t *occluded, MiptStats *stats) {
+    Q_NO_THROW(query_host("mipt_query_occluded", scene, rays, n_rays, opt, occluded, true, stats))
+}
+int mipt_query_occluded_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, uint8_t *d_occluded,
+                               void *hip_stream, MiptStats *stats) {
+    Q_NO_THROW(query_device("mipt_query_occluded_device", scene, d_rays, n_rays, opt, d_occluded, true, hip_stream, stats))
+}
+
+} // extern "C"

@@ -35,6 +35,8 @@ struct MiptScene {
     float4 *d_cams = nullptr;               // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
     size_t cams_bytes = 0;
     std::vector<float4> h_cams;             // its host staging copy (outlives the stream-ordered upload)
+    void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
+    size_t qrays_bytes = 0, qout_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int n_cu = 0;
     uint32_t max_leaf = 0;

@@ -106,6 +106,19 @@ hipError_t launch_unpack_tiles(const float *packed_all, uint32_t width, uint32_t
 hipError_t launch_tonemap(const float *hdr, unsigned long long n_pixels, float divisor,
                           uint8_t *rgba8, hipStream_t stream);
 
+// ---- ray queries (ray_query.hip; mipt_query_closest* / mipt_query_occluded*) ----
+struct DevQuery {
+    const float4 *rays;                     // n_rays x 32 B (MiptRay): {origin.xyz, t_max}, {direction.xyz, reserved}
+    void *out;                              // closest hit: n_rays x 16 B (MiptHit); occlusion: n_rays bytes
+    const uint32_t *tri_order;              // tree order -> the caller's order (the scene's d_tri_order); NULL = they are the same
+    unsigned long long n_rays;
+    float cull_scale;                       // 1 + cull_margin
+    uint32_t *ovf;                          // traversal-stack overflow area [wave][entry][lane]
+    DevStats *stats;                        // zeroed before the launch; `queue` hands out the ray indices
+};
+hipError_t launch_ray_query(const DevScene &sc, const DevQuery &q, bool count, bool cull, bool anyhit, int grid_blocks, hipStream_t stream);
+int query_blocks_per_cu(bool count, bool cull, bool anyhit);                 // occupancy query
+
 // number of set bits in words [0, n_words) of `bitmap`, added to *out (a device counter)
 hipError_t launch_popcount(const uint32_t *bitmap, unsigned long long n_words, unsigned long long *out, hipStream_t stream);
 hipError_t launch_divide(float *hdr, unsigned long long n_floats, float divisor, hipStream_t stream);

@@ -457,6 +457,110 @@ class Scene:  # scene.rs:12-19
         L.check(L.load().mipt_scene_get_bvh(handle, L.ptr(nodes), len(nodes), C.byref(count), None), "mipt_scene_get_bvh")
         self.bvh_nodes = nodes[: count.value].copy()
 
+    # -- ray queries (include/mipt.h "ray queries") ---------------------------------------------
+    @staticmethod
+    def _is_torch(a) -> bool:
+        return type(a).__module__.split(".")[0] == "torch"
+
+    @staticmethod
+    def _query_rays(rays, t_max):
+        """-> ("host", RAY array [n]) or ("device", float32 cuda tensor [n, 8]); ValueError for anything else."""
+        if isinstance(rays, (tuple, list)) and len(rays) == 2:
+            o, d = rays
+            if Scene._is_torch(o) != Scene._is_torch(d):
+                raise ValueError("rays: origins and directions must both be numpy arrays or both torch tensors")
+            if Scene._is_torch(o):
+                import torch
+                if o.dtype != torch.float32 or d.dtype != torch.float32 or o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
+                    raise ValueError("rays: (origins, directions) must be float32 device tensors of shape (n, 3) on one device")
+                n = o.shape[0]
+                t = torch.full((n,), 1e30, dtype=torch.float32, device=o.device) if t_max is None else torch.as_tensor(t_max, dtype=torch.float32, device=o.device)
+                if t.dim() == 0:
+                    t = t.expand(n)
+                if t.shape != (n,):
+                    raise ValueError(f"t_max: expected a scalar or {n} values")
+                return "device", torch.cat([o, t.reshape(n, 1), d, torch.zeros((n, 1), dtype=torch.float32, device=o.device)], dim=1).contiguous()
+            o, d = np.asarray(o), np.asarray(d)
+            if o.dtype != np.float32 or d.dtype != np.float32 or o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+                raise ValueError("rays: (origins, directions) must be float32 arrays of shape (n, 3)")
+            t = np.float32(1e30) if t_max is None else np.asarray(t_max, dtype=np.float32)
+            if t.ndim > 1 or (t.ndim == 1 and t.shape != (len(o),)):
+                raise ValueError(f"t_max: expected a scalar or {len(o)} values")
+            out = np.zeros(len(o), dtype=L.RAY)
+            out["origin"], out["direction"], out["t_max"] = o, d, t
+            return "host", out
+        if t_max is not None:
+            raise ValueError("t_max is given only with (origins, directions); an n x 8 array carries its own")
+        if Scene._is_torch(rays):
+            import torch
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_cuda or not rays.is_contiguous():
+                raise ValueError("rays: expected a contiguous float32 device tensor of shape (n, 8)")
+            return "device", rays
+        a = np.asarray(rays)
+        if a.dtype == L.RAY and a.ndim == 1:
+            return "host", np.ascontiguousarray(a)
+        if a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 8:
+            return "host", np.ascontiguousarray(a).view(L.RAY).reshape(-1)
+        raise ValueError("rays: expected an (n, 8) float32 array, a RAY record array, a float32 device tensor of shape (n, 8) or (origins, directions)")
+
+    def _query(self, anyhit: bool, rays, t_max, traversal, cull_margin, count, handle, stream):
+        """-> (raw result, stats dict).  Host rays: a HIT record array / uint8 array; device rays: an int32 tensor [n, 4] (the MiptHit
+        words) / a uint8 tensor, on the rays' device."""
+        where, r = self._query_rays(rays, t_max)
+        h = handle if handle is not None else self._handle
+        if h is None:
+            raise RuntimeError("scene is not resident on a device")
+        opt = L.MiptQueryOptions()
+        opt.traversal, opt.cull_margin, opt.flags = traversal, cull_margin, (L.FLAG_COUNT if count else 0)
+        st = L.MiptStats()
+        lib = L.load()
+        n = len(r)
+        if where == "host":
+            out = np.zeros(n, dtype=np.uint8 if anyhit else L.HIT)
+            # n == 0: the library returns before it reads either buffer, but refuses null pointers
+            f = lib.mipt_query_occluded if anyhit else lib.mipt_query_closest
+            rc = f(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out) if n else C.c_void_p(16), C.byref(st))
+        else:
+            import torch
+            out = torch.empty((n,), dtype=torch.uint8, device=r.device) if anyhit else torch.empty((n, 4), dtype=torch.int32, device=r.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(r.device).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            f = lib.mipt_query_occluded_device if anyhit else lib.mipt_query_closest_device
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, stream, C.byref(st))
+        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
+            L.check(rc, f.__name__)
+        return out, st.as_dict()
+
+    def query_closest(self, rays, t_max=None, traversal: int = L.TRAVERSAL_REFERENCE, cull_margin: float = L.CULL_MARGIN_SAFE,
+                      count: bool = False, handle=None, stream=None):
+        """Closest hit of every ray on the resident scene (mipt_query_closest / _device): what Ray::traverse_bvh finds with
+        hit_info.distance starting at t_max.  ``rays``: an (n, 8) float32 array {origin, t_max, direction, 0} or RAY records (host
+        entry); a contiguous float32 device tensor of shape (n, 8) (device entry on ``stream`` -- a torch stream, a raw hipStream_t or
+        None = torch's current stream -- returning torch tensors); or ``(origins, directions)`` of shape (n, 3) with ``t_max`` a
+        scalar or n values (None = 1e30).  Returns ({"t", "u", "v", "prim", "front_face", "hit"}, stats): prim is the triangle's
+        index in the caller's order as int64, -1 for a miss (then t = 1e30, u = v = 0)."""
+        raw, stats = self._query(False, rays, t_max, traversal, cull_margin, count, handle, stream)
+        if isinstance(raw, np.ndarray):
+            p = raw["prim"].astype(np.int64)
+            hit = p != L.HIT_NONE
+            return dict(t=raw["t"].copy(), u=raw["u"].copy(), v=raw["v"].copy(), prim=np.where(hit, p & L.HIT_TRI_MASK, -1),
+                        front_face=hit & ((p & L.HIT_FRONT_FACE) != 0), hit=hit), stats
+        import torch
+        f = raw.view(torch.float32)
+        p = raw[:, 3].to(torch.int64) & 0xFFFFFFFF
+        hit = p != L.HIT_NONE
+        return dict(t=f[:, 0].clone(), u=f[:, 1].clone(), v=f[:, 2].clone(), prim=torch.where(hit, p & L.HIT_TRI_MASK, torch.full_like(p, -1)),
+                    front_face=hit & ((p & L.HIT_FRONT_FACE) != 0), hit=hit), stats
+
+    def query_occluded(self, rays, t_max=None, traversal: int = L.TRAVERSAL_REFERENCE, cull_margin: float = L.CULL_MARGIN_SAFE,
+                       count: bool = False, handle=None, stream=None):
+        """Is anything in front of t_max on every ray (mipt_query_occluded / _device)?  Arguments as ``query_closest``.  Returns
+        (bool array or tensor [n], stats)."""
+        raw, stats = self._query(True, rays, t_max, traversal, cull_margin, count, handle, stream)
+        return raw != 0, stats
+
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
         h = handle if handle is not None else self._handle
