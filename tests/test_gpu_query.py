@@ -1,6 +1,7 @@
 """GPU: mipt_query_closest / mipt_query_occluded (csrc/ray_query.hip) against the model of tests/tools/query_model.py, which is held
 to the oracle by tests/test_query_model.py.  Every comparison is bit for bit on the MiptHit words (and, with MIPT_FLAG_COUNT, on the
-five counters); the rays are few enough for the Python model."""
+five counters); the distinct rays are few enough for the Python model, and batches larger than one launch holds in flight
+repeat a modelled pool."""
 import ctypes as C
 import os
 import sys
@@ -146,6 +147,153 @@ def test_ray_counts_and_sentinel(rrt, orc, n):
     h_out, h_occ = d_out.cpu().numpy(), d_occ.cpu().numpy()
     assert Q.same_bits(h_out[:n].view(Q.HIT).reshape(-1), want) and np.all(h_out[n:] == 0x25A5A5A5)
     assert np.array_equal(h_occ[:n], want_occ) and np.all(h_occ[n:] == 0x5A)
+
+
+# ---- batches larger than one launch holds in flight: the refill into a partly busy wave -----------------------------------------------
+# query_launch sizes the grid as min(n_cu * blocks_per_cu, ceil(n / 256)) blocks of 256 lanes, so up to grid * 256 rays every wave
+# takes its rays in its first fetch and every later refill only retires lanes.  blocks_per_cu is what the occupancy query returns,
+# clamped to 8 by query_blocks_per_cu (ray_query.hip): more than n_cu * 8 * 256 rays exceed the launch whatever that query says.
+# The model cannot trace a million rays and need not: a ray's answer and counts do not depend on scheduling, so the batch is a pool
+# of a few hundred modelled rays gathered through Q.tiled (48 short and 16 long rays in any 64 consecutive positions), which
+# tests/test_query_model.py shows to refill waves whose other lanes are mid-traversal.
+BLOCKS_PER_CU_CAP, BLOCK_LANES = 8, 256
+BIG = [(2, 77), (1, 1)]                        # n = k * n_cu * 8 * 256 + extra: several refills per wave and a ragged tail; the queue
+                                               # runs out inside a refill (one lane gets a ray, its neighbours retire)
+
+
+def _launch_capacity():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count * BLOCKS_PER_CU_CAP * BLOCK_LANES
+
+
+_pools = {}
+
+
+def _pool(rrt, orc, which):
+    """(resident Scene, {(arm, anyhit): (rays, model hits, model occ, per-ray counters, classes)}, filled on demand and left unchanged)"""
+    if which not in _pools:
+        if which == "helmet":                                                  # host-built: the scene of _case
+            sc = _case(rrt, orc, "helmet")[0]
+            pool = Q.refill_pool(orc, sc)
+        elif which == "helmet-device":                                         # built on the device: prim goes through tri_order
+            tris, mats, texs, cam = _make(rrt, "helmet")
+            sc = rrt.Scene.from_arrays(tris, mats, texs, build_bvh=False)
+            sc.upload_from_triangles(0, fetch_bvh=True)
+            sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+            pool = Q.refill_pool(orc, sc)
+        else:
+            from test_gpu_batch import _chain_bvh
+            sc = _chain_bvh(rrt, 40)                                           # stack occupancy 40: 16 in LDS, the rest spilled
+            sc.upload(0)
+            pool = Q.chain_rays()
+        _pools[which] = (sc, pool, {})
+    return _pools[which]
+
+
+def _pool_model(rrt, orc, which, arm, anyhit):
+    sc, pool, models = _pool(rrt, orc, which)
+    if (arm, anyhit) not in models:
+        kw = dict(cull=arm[0] == CULL, margin=arm[1], tri_order=sc._tri_order)
+        rays = pool
+        if anyhit:
+            rays = Q.occlusion_t_max(pool, _pool_model(rrt, orc, which, ARMS[0], False)[2])
+        hits, occ, per = Q.per_ray(orc.load(), sc.tris, sc.bvh_nodes, rays, anyhit=anyhit, **kw)
+        n_steps = Q.steps(per)
+        classes = Q.classify(n_steps)
+        if which == "helmet-device":                                           # this tree exists only here: the other pools are
+            Q.refill_conditions(n_steps, classes)                              # held to the conditions by tests/test_query_model.py
+        models[arm, anyhit] = (sc, rays, hits, occ, per, classes)
+    return models[arm, anyhit]
+
+
+def _big_query(rrt, sc, rays, d_rays, n, arm, anyhit, count, device):
+    """One call of the C entry with a sentinel behind the output -> (HIT records or occlusion bytes [n], stats dict)"""
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    opt = L.MiptQueryOptions()
+    opt.traversal, opt.cull_margin, opt.flags = arm[0], arm[1], (L.FLAG_COUNT if count else 0)
+    st = L.MiptStats()
+    if device:                                                                 # one extra MiptHit / 16 extra bytes keep their pattern
+        if anyhit:
+            d_out = torch.full((n + 16,), 0x5A, dtype=torch.uint8, device="cuda")
+            rc = lib.mipt_query_occluded_device(sc._handle, d_rays.data_ptr(), n, C.byref(opt), d_out.data_ptr(), None, C.byref(st))
+        else:
+            d_out = torch.full((n + 1, 4), 0x25A5A5A5, dtype=torch.int32, device="cuda")
+            rc = lib.mipt_query_closest_device(sc._handle, d_rays.data_ptr(), n, C.byref(opt), d_out.data_ptr(), None, C.byref(st))
+        out = d_out.cpu().numpy()
+        assert rc == 0 and np.all(out[n:] == (0x5A if anyhit else 0x25A5A5A5)), (rc, arm, anyhit, count)
+        return (out[:n] if anyhit else out[:n].view(Q.HIT).reshape(-1)), st.as_dict()
+    if anyhit:                                                                 # the caller's buffer is longer than n and stays so
+        out = np.full(n + 16, 0x5A, dtype=np.uint8)
+        rc = lib.mipt_query_occluded(sc._handle, L.ptr(rays), n, C.byref(opt), L.ptr(out), C.byref(st))
+        assert rc == 0 and np.all(out[n:] == 0x5A), (rc, arm, count)
+    else:
+        out = np.full(4 * (n + 1), 0xA5A5A5A5, dtype=np.uint32).view(Q.HIT)
+        rc = lib.mipt_query_closest(sc._handle, L.ptr(rays), n, C.byref(opt), L.ptr(out), C.byref(st))
+        assert rc == 0 and np.all(out[n:].view(np.uint32) == 0xA5A5A5A5), (rc, arm, count)
+    return out[:n], st.as_dict()
+
+
+def _mismatch(got, want, idx):
+    """for the message of a failed comparison: the first differing rays, their pool members and what was written"""
+    g, w = np.ascontiguousarray(got).view(np.uint32).reshape(len(idx), -1), np.ascontiguousarray(want).view(np.uint32).reshape(len(idx), -1)
+    bad = np.flatnonzero((g != w).any(axis=1))
+    return [(int(i), int(idx[i]), g[i].tolist(), w[i].tolist()) for i in bad[:4]], len(bad)
+
+
+def _check_big(rrt, orc, which, n, arm, anyhit, entries=(False, True)):
+    sc, pool_rays, hits, occ, per, classes = _pool_model(rrt, orc, which, arm, anyhit)
+    assert n > _launch_capacity()                                              # some wave gets a second block of real rays
+    idx = Q.tiled(len(pool_rays), classes, n)
+    rays = np.ascontiguousarray(pool_rays[idx])
+    want = occ[idx] if anyhit else hits[idx]
+    sums = {k: int(per[k][idx].sum()) for k in ("inner_steps", "tri_tests", "hits")}
+    sums.update(rays=n, max_stack=int(per["max_stack"][idx].max()))
+    assert np.all(per["stack_overflows"] == 0) and 0 < sums["hits"] < n
+    d_rays = _dev(rays) if True in entries else None
+    for device in entries:
+        for count in (True, False):                                            # the counting twin, then the production instantiation
+            got, st = _big_query(rrt, sc, rays, d_rays, n, arm, anyhit, count, device)
+            same = np.array_equal(got, want) if anyhit else Q.same_bits(got, want)
+            assert same, (which, n, arm, anyhit, device, count, _mismatch(got, want, idx))
+            assert st["stack_overflows"] == 0 and st["kernel_ms"] > 0
+            if count:
+                assert {k: st[k] for k in Q.COUNTERS} == sums, (which, n, arm, anyhit, device, st, sums)
+            else:
+                assert st["rays"] == 0 and st["tri_tests"] == 0
+    return sums
+
+
+@pytest.mark.parametrize("size", BIG, ids=lambda s: "%dx+%d" % s)
+@pytest.mark.parametrize("arm", ARMS)
+def test_closest_hit_on_batches_larger_than_the_launch(rrt, orc, arm, size):
+    _check_big(rrt, orc, "helmet", size[0] * _launch_capacity() + size[1], arm, False)
+
+
+@pytest.mark.parametrize("size", BIG, ids=lambda s: "%dx+%d" % s)
+@pytest.mark.parametrize("arm", [ARMS[0], ARMS[2]])
+def test_occlusion_on_batches_larger_than_the_launch(rrt, orc, arm, size):
+    _check_big(rrt, orc, "helmet", size[0] * _launch_capacity() + size[1], arm, True)
+
+
+@pytest.mark.parametrize("anyhit", [False, True], ids=["closest", "occluded"])
+def test_spilled_stacks_across_refills(rrt, orc, anyhit):
+    """The chain tree: a long ray holds 40 stack entries, 24 of them in the lane's HBM spill slots, and an occluded one stops
+    with them still stacked.  The lane's next ray, short or spilled, must not read its predecessor's entries."""
+    sums = _check_big(rrt, orc, "chain", _launch_capacity() + 4099, ARMS[0], anyhit)
+    assert sums["max_stack"] > 16
+
+
+def test_prim_through_tri_order_on_a_batch_larger_than_the_launch(rrt, orc):
+    """A device-built scene: the hit's triangle goes through q.tri_order when the refill writes it, after neighbours were refilled"""
+    sc, _, hits, _, _, classes = _pool_model(rrt, orc, "helmet-device", ARMS[2], False)
+    order = sc._tri_order
+    assert order is not None and not np.array_equal(order, np.arange(len(order)))
+    hit = (hits["prim"] != Q.NONE) & (classes != Q.UNUSED)
+    tree = Q.per_ray(orc.load(), sc.tris, sc.bvh_nodes, _pools["helmet-device"][1][hit], cull=True, margin=SAFE)[0]
+    assert hit.sum() >= 16 and np.any(tree["prim"] != hits["prim"][hit])       # the permutation shows in the expected records
+    _check_big(rrt, orc, "helmet-device", BIG[0][0] * _launch_capacity() + BIG[0][1], ARMS[2], False, entries=(True,))
 
 
 # ---- degenerate scenes -----------------------------------------------------------------------------------------------------------

@@ -66,3 +66,81 @@ def test_model_t_max_and_occlusion(rrt, orc):
         assert c2["tri_tests"] <= c["tri_tests"] and c2["inner_steps"] <= c["inner_steps"]
         if expect:
             assert Q.same_bits(hits["t"], rec_t)
+
+
+# ---- the pools of the large-batch GPU tests (tests/test_gpu_query.py) -------------------------------------------------------------
+SAFE = 0.0078125
+ARMS = [(False, 0.0), (True, 0.0), (True, SAFE)]                         # (cull, margin): reference, culled, culled with the safe margin
+
+
+def test_tiling_and_the_restated_wave():
+    """`tiled` and `wave_refills` on hand-made classes and step counts"""
+    classes = np.array([Q.SHORT] * 5 + [Q.UNUSED] * 3 + [Q.LONG] * 7 + [Q.SHORT] * 6, dtype=np.uint8)
+    idx = Q.tiled(len(classes), classes, 1000)
+    long_at = classes[idx] == Q.LONG
+    assert not np.any(classes[idx] == Q.UNUSED)
+    assert np.array_equal(long_at, np.arange(1000) % 8 >= 6)
+    window = np.convolve(long_at.astype(np.int64), np.ones(64, dtype=np.int64), mode="valid")
+    assert np.all(window == 16)                                           # 48 short and 16 long at every alignment
+    assert set(idx.tolist()) == set(np.flatnonzero(classes != Q.UNUSED).tolist())   # every member of both classes is used
+    assert len({tuple(idx[k:k + 64]) for k in range(0, 960, 64)}) == 15   # neighbouring windows differ
+    # a batch one fetch holds never refills a busy wave, whatever its rays cost: the queue is empty by then
+    assert Q.wave_refills(np.full(64, 5)) == 0 and Q.wave_refills(np.arange(1, 41)) == 0
+    # 128 rays, the first 64 with 48 short: the second fetch finds 16 lanes at their second step of 20
+    two = np.concatenate([np.where(np.arange(64) % 8 < 6, 1, 20), np.full(64, 3)])
+    assert Q.wave_refills(two) == 2                                       # 48 rays into 48 idle lanes, then 16 once those are over
+    assert Q.wave_refills(two, refill_den=1) == 0                         # "refill only when nothing traverses" never does it
+    assert Q.wave_refills(two, [0, 100]) == 1                             # the queue runs out inside the second block: 28 rays, 20 retire
+    assert Q.wave_refills(two, [0]) == 0                                  # ... or before it
+
+
+def _pool_models(lib, tris, nodes, pool, arms_closest, arms_occluded):
+    """{(arm, anyhit): (rays, hits, occ, per-ray counters)}; the occlusion rays carry a t_max around the reference arm's closest t"""
+    out = {}
+    for arm in arms_closest:
+        out[arm, False] = (pool,) + Q.per_ray(lib, tris, nodes, pool, cull=arm[0], margin=arm[1])
+    occ_rays = Q.occlusion_t_max(pool, out[ARMS[0], False][1])
+    for arm in arms_occluded:
+        out[arm, True] = (occ_rays,) + Q.per_ray(lib, tris, nodes, occ_rays, cull=arm[0], margin=arm[1], anyhit=True)
+    return out
+
+
+def test_large_batch_pools_reach_the_partial_refill(rrt, orc):
+    """The pools of the large-batch GPU tests, per traversal arm: short rays are over in at most 2 steps, long rays take at least
+    16, both exist, and the restated scheduling rule refills a wave while other lanes traverse.  With that and more rays than
+    one launch holds in flight the device test reaches the partial refill.  (The Cornell box cannot serve: its tree has 5 inner
+    nodes and 6 two-triangle leaves of which no line meets more than five, so no ray takes more than 15 steps there.)"""
+    from test_gpu_batch import _chain_bvh
+    lib = orc.load()
+    sc = _scene(rrt, "helmet")
+    pool = Q.refill_pool(orc, sc)
+    assert 200 <= len(pool) <= 800
+    models = _pool_models(lib, sc.tris, sc.bvh_nodes, pool, ARMS, [ARMS[0], ARMS[2]])
+    chain = _chain_bvh(rrt, 40)
+    chain_pool = Q.chain_rays()
+    chain_models = _pool_models(lib, chain.tris, chain.bvh_nodes, chain_pool, ARMS[:1], ARMS[:1])
+    for name, group in (("helmet", models), ("chain", chain_models)):
+        for (arm, anyhit), (rays, hits, occ, per) in group.items():
+            n_steps = Q.steps(per)
+            classes = Q.classify(n_steps)
+            alone, scattered = Q.refill_conditions(n_steps, classes)
+            assert alone > 0 and scattered > 0, (name, arm, anyhit)
+            used = classes != Q.UNUSED
+            assert np.all(per["stack_overflows"] == 0)
+            if anyhit:                                                    # about half of the rays that hit anything are occluded
+                assert 0 < occ[used].sum() < (group[ARMS[0], False][2][used] != 0).sum(), (name, arm)
+                assert np.any(occ[classes == Q.LONG] != 0) and np.any(occ[classes == Q.LONG] == 0), (name, arm)
+            else:
+                assert np.any(occ[classes == Q.LONG] != 0), (name, arm)
+            # per_ray is `query` ray by ray
+            q_hits, q_occ, q_c = Q.query(lib, np.ascontiguousarray(sc.tris if name == "helmet" else chain.tris),
+                                         sc.bvh_nodes if name == "helmet" else chain.bvh_nodes, rays, cull=arm[0], margin=arm[1], anyhit=anyhit)
+            assert Q.same_bits(hits, q_hits) and np.array_equal(occ, q_occ)
+            assert all(int(per[k].sum()) == q_c[k] for k in ("inner_steps", "tri_tests", "hits")) and int(per["max_stack"].max()) == q_c["max_stack"]
+    # the chain's long rays go through the spill region (16 entries in LDS), its short rays leave at the root
+    per = chain_models[ARMS[0], False][3]
+    assert per["max_stack"][:70].min() > 16 and np.all(Q.steps(per)[70:] == 1)
+    # the rule the kernel would follow with kRefillDen = 1 never refills a busy wave: the conditions above would fail
+    n_steps = Q.steps(models[ARMS[2], False][3])
+    with pytest.raises(AssertionError, match="partly busy"):
+        Q.refill_conditions(n_steps, Q.classify(n_steps), refill_den=1)
