@@ -34,6 +34,8 @@
 
 #include "mipt_internal.h"
 #include "mipt_scene.h"
+#define MIPT_HIP_FAIL_FMT "mipt_bvh_build_device: %s: %s"        // this file's HIP errors name the entry, not "... failed"
+#include "mipt_host_util.h"
 
 namespace {
 
@@ -1335,14 +1337,6 @@ __global__ void gather_tris(const MiptTriangle *src, const uint32_t *order, uint
     }
 }
 
-int fail(int code, const char *what, hipError_t e) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "mipt_bvh_build_device: %s: %s", what, hipGetErrorString(e));
-    mipt_internal_set_error(buf);
-    return code;
-}
-#define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(MIPT_ERR_HIP, #x, e_); } } while (0)
-
 } // namespace
 
 // The build proper: triangles already in HBM (`d_tris`, original order), results stay in HBM -- the node array in the reference's
@@ -1363,7 +1357,7 @@ void mipt::bvh_builder_resolve_kernels() {
 }
 
 int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int device_id, ResidentBvh *res) {
-    if (!d_tris || !res || n_tris == 0) { mipt_internal_set_error("mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); return MIPT_ERR_INVALID_ARG; }
+    if (!d_tris || !res || n_tris == 0) { return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); }
     *res = ResidentBvh{};
     Proxy *d_px[2] = {nullptr, nullptr};
     BNode *d_bn = nullptr;
@@ -1390,23 +1384,23 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     };
-    HIP_TRY(hipSetDevice(device_id));
+    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
     const uint32_t max_nodes = 2u * n_tris;
-    HIP_TRY(hipMalloc((void **)&d_px[0], (size_t)n_tris * sizeof(Proxy)));
-    HIP_TRY(hipMalloc((void **)&d_px[1], (size_t)n_tris * sizeof(Proxy)));
-    HIP_TRY(hipMalloc((void **)&d_bn, (size_t)max_nodes * sizeof(BNode)));
-    HIP_TRY(hipMalloc((void **)&d_nodes, (size_t)max_nodes * sizeof(MiptNode)));
-    HIP_TRY(hipMalloc((void **)&d_order, (size_t)n_tris * 4));
-    HIP_TRY(hipMalloc((void **)&d_pool, (size_t)max_nodes * sizeof(PoolNode)));
-    HIP_TRY(hipMalloc((void **)&d_hp, (size_t)n_tris * 4));
-    HIP_TRY(hipMalloc((void **)&d_tp, (size_t)n_tris * 4));
-    HIP_TRY(hipMalloc((void **)&d_ctrl, sizeof(Ctrl)));
-    HIP_TRY(hipHostMalloc((void **)&h_snap, 2 * sizeof(LevelSnap), hipHostMallocDefault));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_px[0], (size_t)n_tris * sizeof(Proxy)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_px[1], (size_t)n_tris * sizeof(Proxy)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_bn, (size_t)max_nodes * sizeof(BNode)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_nodes, (size_t)max_nodes * sizeof(MiptNode)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_order, (size_t)n_tris * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_pool, (size_t)max_nodes * sizeof(PoolNode)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_hp, (size_t)n_tris * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tp, (size_t)n_tris * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_ctrl, sizeof(Ctrl)));
+    MIPT_HIP_OR(cleanup(), hipHostMalloc((void **)&h_snap, 2 * sizeof(LevelSnap), hipHostMallocDefault));
     memset(h_snap, 0, 2 * sizeof(LevelSnap));
     // work lists: a level has at most min(2^level, n_tris) nodes; a class list never holds more nodes than triangles / its
     // smallest node... sized by the simple bound n_tris + 1 per (parity, class)
     const size_t list_cap = (size_t)n_tris + 1u;
-    HIP_TRY(hipMalloc((void **)&d_lists, (2 * (size_t)(kClasses - 1) * list_cap + 2 * (size_t)big_cap) * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_lists, (2 * (size_t)(kClasses - 1) * list_cap + 2 * (size_t)big_cap) * 4));
     Lists ls;
     for (int pa = 0; pa < 2; pa++) {
         int slot = 0;
@@ -1416,28 +1410,28 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         }
         ls.l[pa][CLS_BIG] = d_lists + 2 * (size_t)(kClasses - 1) * list_cap + (size_t)pa * big_cap;
     }
-    HIP_TRY(hipMalloc((void **)&d_root, 48));
-    HIP_TRY(hipMalloc((void **)&d_cbins, (size_t)chunk_cap * sizeof(ChunkBins)));
-    HIP_TRY(hipMalloc((void **)&d_crange, 2 * (size_t)big_cap * 6 * 4));
-    HIP_TRY(hipMalloc((void **)&d_cbeg, (size_t)(big_cap + 1) * 4));
-    HIP_TRY(hipMalloc((void **)&d_big, (size_t)big_cap * sizeof(BigState)));
-    HIP_TRY(hipMalloc((void **)&d_chunks, (size_t)chunk_cap * sizeof(ChunkInfo)));
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_root, 48));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_cbins, (size_t)chunk_cap * sizeof(ChunkBins)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_crange, 2 * (size_t)big_cap * 6 * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_cbeg, (size_t)(big_cap + 1) * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_big, (size_t)big_cap * sizeof(BigState)));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_chunks, (size_t)chunk_cap * sizeof(ChunkInfo)));
+    MIPT_HIP_OR(cleanup(), hipEventCreate(&e0));
+    MIPT_HIP_OR(cleanup(), hipEventCreate(&e1));
     {   // blocking streams: ordered against the null stream's copies / launches.  The chunked path is a chain of eight dependent launches:
         // its stream gets the higher priority, so that a link of the chain is not left waiting for a CU under the wave kernels' workgroups
         // (-0.5 ms).  The others stay at the default priority: a stream at a priority the process has not used yet costs a new hardware
         // queue, 6-7 ms each the first time in a process (tools/setup_trace_first.py); creating them on a helper thread during the upload does
         // not hide that -- the runtime serialises queue creation with the copies (tried: the upload grew by what the creation took).
         int prio_lo = 0, prio_hi = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        HIP_TRY(hipStreamCreateWithPriority(&sg, hipStreamDefault, prio_hi));
-        HIP_TRY(hipStreamCreate(&sw));
-        HIP_TRY(hipStreamCreate(&sw2));
-        HIP_TRY(hipStreamCreate(&ss));
+        MIPT_HIP_OR(cleanup(), hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+        MIPT_HIP_OR(cleanup(), hipStreamCreateWithPriority(&sg, hipStreamDefault, prio_hi));
+        MIPT_HIP_OR(cleanup(), hipStreamCreate(&sw));
+        MIPT_HIP_OR(cleanup(), hipStreamCreate(&sw2));
+        MIPT_HIP_OR(cleanup(), hipStreamCreate(&ss));
     }
     const uint32_t root_init[12] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    HIP_TRY(hipMemcpy(d_root, root_init, 48, hipMemcpyHostToDevice));
+    MIPT_HIP_OR(cleanup(), hipMemcpy(d_root, root_init, 48, hipMemcpyHostToDevice));
     Ctrl hc;
     memset(&hc, 0, sizeof hc);
     hc.n_nodes.v = 1u;
@@ -1445,10 +1439,10 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         const int cls = (int)node_class(n_tris);
         hc.cnt[0][cls].v = 1u;
         const uint32_t zero = 0u;
-        HIP_TRY(hipMemcpy(ls.l[0][cls], &zero, 4, hipMemcpyHostToDevice));
+        MIPT_HIP_OR(cleanup(), hipMemcpy(ls.l[0][cls], &zero, 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMemcpy(d_ctrl, &hc, sizeof hc, hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(e0, nullptr));
+    MIPT_HIP_OR(cleanup(), hipMemcpy(d_ctrl, &hc, sizeof hc, hipMemcpyHostToDevice));
+    MIPT_HIP_OR(cleanup(), hipEventRecord(e0, nullptr));
     hipLaunchKernelGGL(make_proxies, dim3(2048), dim3(256), 0, nullptr, d_tris, n_tris, d_px[0], d_root);
     hipLaunchKernelGGL(init_root, dim3(1), dim3(1), 0, nullptr, d_bn, d_root, n_tris);
     std::vector<uint32_t> lvl_begin;
@@ -1463,9 +1457,9 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         if (nb) {                                       // top of the tree: nodes too large for one workgroup (chunks of kChunk);
                                                         // its own stream: these 8 launches overlap the level's wave / group / thread kernels
             const uint32_t nc = n_tris / kChunk + nb;   // bound on sum(ceil(n_j / kChunk)); the real count lives in ctrl->n_chunks
-            if (nb > big_cap || nc > chunk_cap) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: internal capacity"); return MIPT_ERR_BVH; }
+            if (nb > big_cap || nc > chunk_cap) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity"); }
             const dim3 gb((nb + 63) / 64), tb(64);
-            if (hc.cnt[row][kClasses].v > big_cap) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: internal capacity"); return MIPT_ERR_BVH; }
+            if (hc.cnt[row][kClasses].v > big_cap) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity"); }
             hipLaunchKernelGGL(big_setup, dim3(1), dim3(kSetupT), 0, sg, d_big, d_bn, ls.l[parity][CLS_BIG], nb, d_chunks, d_cbeg, d_ctrl, d_root, d_crange + (size_t)parity * big_cap * 6);
             hipLaunchKernelGGL(big_bin, dim3(nc), dim3(kT), 0, sg, d_big, d_chunks, d_cbins, d_px[cur], d_ctrl);
             hipLaunchKernelGGL(big_choose, dim3(nb), dim3(64), 0, sg, d_big, nb, d_px[cur]);
@@ -1487,7 +1481,7 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         if (ng16) hipLaunchKernelGGL((build_level_group<16, kTiny, 16u>), dim3((ng16 + 31u) / 32u), dim3(512), 0, sw2, d_bn, ls.l[parity][CLS_G16], ng16, d_px[cur], d_px[cur ^ 1], d_ctrl, ls, next);
         if (ntin) hipLaunchKernelGGL(build_level_tiny, dim3((ntin + 63u) / 64u), dim3(64), 0, st, d_bn, ls.l[parity][CLS_TINY], ntin, d_px[cur], d_px[cur ^ 1], d_ctrl, ls, next);
         if (nsub) hipLaunchKernelGGL(build_subtree_tiny, dim3((nsub + 63u) / 64u), dim3(64), 0, ss, d_bn, ls.l[parity][CLS_SUB], nsub, d_px[cur], d_px[0], d_px[1], d_pool, d_ctrl);
-        HIP_TRY(hipGetLastError());
+        MIPT_HIP_OR(cleanup(), hipGetLastError());
         {   // the level's barrier and the next level's counts: level_mark on every stream that got work, then poll its flag
             hipStream_t used[4];
             uint32_t n_used = 0;
@@ -1500,7 +1494,7 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
                 const size_t lvl = lvl_begin.size();                    // level + 1: never 0
                 LevelSnap *snap = h_snap + (lvl & 1u);
                 for (uint32_t i = 0; i < n_used; i++) hipLaunchKernelGGL(level_mark, dim3(1), dim3(64), 0, used[i], d_ctrl, n_used, row_next, row, snap, (uint32_t)lvl);
-                HIP_TRY(hipGetLastError());
+                MIPT_HIP_OR(cleanup(), hipGetLastError());
                 const auto t_spin = std::chrono::steady_clock::now();
                 for (uint32_t spins = 0; snap->flag != (uint32_t)lvl; spins++) {
                     if ((spins & 0xfffffu) == 0xfffffu && std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(20)) {
@@ -1516,14 +1510,14 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
             }
         }
         const uint32_t total = hc.n_nodes.v;
-        if (total > max_nodes) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: node overflow"); return MIPT_ERR_BVH; }
+        if (total > max_nodes) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow"); }
         begin = end; end = total; cur ^= 1; parity ^= 1u; row = row_next;
-        if (lvl_begin.size() > 4096) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: tree deeper than 4096 levels"); return MIPT_ERR_BVH; }
+        if (lvl_begin.size() > 4096) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: tree deeper than 4096 levels"); }
     }
     const uint32_t n_bn = end;                                  // nodes built level by level; the finished subtrees' nodes live in the pool
     const uint32_t n_nodes = n_bn + hc.sub_nodes.v;
     lvl_begin.push_back(n_bn);
-    if (n_nodes > max_nodes) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: node overflow"); return MIPT_ERR_BVH; }
+    if (n_nodes > max_nodes) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow"); }
     hipLaunchKernelGGL(extract_order, dim3(2048), dim3(256), 0, sw, d_px[cur], n_tris, d_order);      // beside the two tree passes below (every stream is idle here: the last level's barrier has been seen)
     {   // subtree sizes bottom-up, then depth-first bases top-down (which also writes the nodes): runs of small levels in one launch each, wide levels one by one
         const int n_lvl = (int)lvl_begin.size() - 1;
@@ -1559,10 +1553,10 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
             l = hi + 1;
         }
     }
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
+    MIPT_HIP_OR(cleanup(), hipEventRecord(e1, nullptr));
+    MIPT_HIP_OR(cleanup(), hipDeviceSynchronize());
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    MIPT_HIP_OR(cleanup(), hipEventElapsedTime(&ms, e0, e1));
     res->d_nodes = d_nodes; res->n_nodes = n_nodes; res->d_tri_order = d_order; res->build_ms = ms;
     res->levels = (uint32_t)lvl_begin.size();
     d_nodes = nullptr; d_order = nullptr;                   // the caller's now
@@ -1573,7 +1567,7 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
 // The C ABI entry: host arrays in, host arrays out (reorders `tris` in place like bvh.rs:105).
 extern "C" int mipt_bvh_build_device(MiptTriangle *tris, uint32_t n_tris, MiptNode *nodes_out, uint32_t nodes_cap,
                                      uint32_t *n_nodes_out, int device_id, double *build_ms_out) {
-    if (!tris || !nodes_out || n_tris == 0 || nodes_cap == 0) { mipt_internal_set_error("mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); return MIPT_ERR_INVALID_ARG; }
+    if (!tris || !nodes_out || n_tris == 0 || nodes_cap == 0) { return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); }
     MiptTriangle *d_tris = nullptr, *d_out = nullptr;
     mipt::ResidentBvh r;
     auto cleanup = [&]() {
@@ -1582,17 +1576,17 @@ extern "C" int mipt_bvh_build_device(MiptTriangle *tris, uint32_t n_tris, MiptNo
         if (r.d_nodes) (void)hipFree(r.d_nodes);
         if (r.d_tri_order) (void)hipFree(r.d_tri_order);
     };
-    HIP_TRY(hipSetDevice(device_id));
+    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
     const size_t nb = (size_t)n_tris * sizeof(MiptTriangle);
-    HIP_TRY(hipMalloc((void **)&d_tris, nb));
-    HIP_TRY(hipMalloc((void **)&d_out, nb));
-    HIP_TRY(hipMemcpy(d_tris, tris, nb, hipMemcpyHostToDevice));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tris, nb));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_out, nb));
+    MIPT_HIP_OR(cleanup(), hipMemcpy(d_tris, tris, nb, hipMemcpyHostToDevice));
     const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &r);
     if (rc != MIPT_OK) { cleanup(); return rc; }
-    if (r.n_nodes > nodes_cap) { cleanup(); mipt_internal_set_error("mipt_bvh_build_device: nodes_cap too small"); return MIPT_ERR_INVALID_ARG; }
+    if (r.n_nodes > nodes_cap) { cleanup(); return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: nodes_cap too small"); }
     hipEvent_t g0 = nullptr, g1 = nullptr;                  // the 112-byte gather belongs to the build (bvh.rs:105 swaps the triangles themselves)
-    HIP_TRY(hipEventCreate(&g0));
-    if (hipEventCreate(&g1) != hipSuccess) { (void)hipEventDestroy(g0); cleanup(); mipt_internal_set_error("mipt_bvh_build_device: hipEventCreate failed"); return MIPT_ERR_HIP; }
+    MIPT_HIP_OR(cleanup(), hipEventCreate(&g0));
+    if (hipEventCreate(&g1) != hipSuccess) { (void)hipEventDestroy(g0); cleanup(); return mipt::fail(MIPT_ERR_HIP, "mipt_bvh_build_device: hipEventCreate failed"); }
     (void)hipEventRecord(g0, nullptr);
     hipLaunchKernelGGL(gather_tris, dim3(4096), dim3(256), 0, nullptr, d_tris, r.d_tri_order, n_tris, d_out);
     (void)hipEventRecord(g1, nullptr);
@@ -1600,9 +1594,9 @@ extern "C" int mipt_bvh_build_device(MiptTriangle *tris, uint32_t n_tris, MiptNo
     float gms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&gms, g0, g1);
     (void)hipEventDestroy(g0); (void)hipEventDestroy(g1);
-    HIP_TRY(e);
-    HIP_TRY(hipMemcpy(tris, d_out, nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(nodes_out, r.d_nodes, (size_t)r.n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
+    MIPT_HIP_OR(cleanup(), e);
+    MIPT_HIP_OR(cleanup(), hipMemcpy(tris, d_out, nb, hipMemcpyDeviceToHost));
+    MIPT_HIP_OR(cleanup(), hipMemcpy(nodes_out, r.d_nodes, (size_t)r.n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
     if (n_nodes_out) *n_nodes_out = r.n_nodes;
     if (build_ms_out) *build_ms_out = r.build_ms + gms;
     cleanup();

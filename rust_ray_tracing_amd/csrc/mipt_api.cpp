@@ -6,6 +6,7 @@
 #include "pt_kernel.h"
 #include "mipt_internal.h"
 #include "mipt_scene.h"
+#include "mipt_host_util.h"
 
 #include <atomic>
 #include <chrono>
@@ -38,22 +39,6 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return fail(MIPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));          \
-    } while (0)
-
 } // namespace
 
 void mipt_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
@@ -73,6 +58,7 @@ void mipt::free_scene(MiptScene *s) {
 
 namespace {
 
+using mipt::fail;
 using mipt::free_scene;
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -81,20 +67,12 @@ template <class T>
 int upload(void **dst, const T *src, size_t count, size_t min_bytes = 16) {
     size_t bytes = count * sizeof(T);
     size_t alloc = bytes < min_bytes ? min_bytes : bytes;
-    HIP_TRY(hipMalloc(dst, alloc));
-    if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    MIPT_HIP(hipMalloc(dst, alloc));
+    if (bytes) MIPT_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     return MIPT_OK;
 }
 template <class T>
 int upload(void **dst, const std::vector<T> &src, size_t min_bytes = 16) { return upload(dst, src.data(), src.size(), min_bytes); }
-
-int ensure(void **p, size_t *have, size_t want_bytes) {
-    if (*have >= want_bytes && *p) return MIPT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    HIP_TRY(hipMalloc(p, want_bytes));
-    *have = want_bytes;
-    return MIPT_OK;
-}
 
 // host loops over the caller's arrays (the material-id check) on up to 16 threads
 template <class F> void parallel_for(size_t n, F body) {                 // body(begin, end) on disjoint ranges; results must not depend on the split
@@ -176,7 +154,7 @@ int mipt::upload_material_tables(MiptScene *s, const MaterialTables &t) {
     int rc;
     if ((rc = upload(&s->d_mats, t.mats, 64)) || (rc = upload(&s->d_mats_full, t.mats_full, 128))) return rc;
     if (!t.texels.empty() || t.n_texels == 0) { if ((rc = upload(&s->d_texels, t.texels, 16))) return rc; }
-    else HIP_TRY(hipMalloc(&s->d_texels, (size_t)t.n_texels * 4));              // filled by the caller (scene_device.hip stages the textures itself)
+    else MIPT_HIP(hipMalloc(&s->d_texels, (size_t)t.n_texels * 4));              // filled by the caller (scene_device.hip stages the textures itself)
     s->mats_bytes = t.mats.size() * sizeof(mipt::DevMaterial) < 64 ? 64 : t.mats.size() * sizeof(mipt::DevMaterial);
     s->mats_full_bytes = t.mats_full.size() * sizeof(mipt::DevMaterialFull) < 128 ? 128 : t.mats_full.size() * sizeof(mipt::DevMaterialFull);
     s->texel_bytes = (size_t)t.n_texels * 4 < 16 ? 16 : (size_t)t.n_texels * 4;
@@ -203,7 +181,7 @@ int mipt::scene_finish_workspace(MiptScene *s) {
 // queues the copies on ITS null stream, `clone_finish` waits for them.  Seven pulls from device 0 use seven different xGMI links.
 static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
     *out = nullptr;
-    HIP_TRY(hipSetDevice(device));
+    MIPT_HIP(hipSetDevice(device));
     if (device != src->device) {
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) {
@@ -237,7 +215,7 @@ static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
 }
 static int clone_finish(const MiptScene *src, MiptScene *s, double t0) {
     const int device = s->device;
-    HIP_TRY(hipSetDevice(device));
+    MIPT_HIP(hipSetDevice(device));
     {
         const hipError_t e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) return fail(MIPT_ERR_HIP, "replica copy %d -> %d: %s", src->device, device, hipGetErrorString(e));
@@ -419,7 +397,7 @@ static int scene_create_many(const MiptSceneDesc *desc, const int *device_ids, i
     // into its tables): anything else is refused here, with the other host checks, before the first device call.
     { mipt::MaterialTables checked; const int bad = mipt::build_material_tables(desc, &checked, false); if (bad) return bad; }
     int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
+    MIPT_HIP(hipGetDeviceCount(&ndev));
     for (int i = 0; i < n_dev; i++)
         if (device_ids[i] < 0 || device_ids[i] >= ndev) return fail(MIPT_ERR_HIP, "HIP device %d not available (%d visible)", device_ids[i], ndev);
     MiptScene *s = nullptr;
@@ -442,11 +420,6 @@ static int scene_create_impl(const MiptSceneDesc *desc, int device_id, MiptScene
     return scene_create_many(desc, &device_id, 1, out);
 }
 
-// No C++ exception may cross the C ABI (the caller may be Rust or C): allocation failures become status codes.
-#define MIPT_NO_THROW(call)                                                                                             \
-    try { return call; }                                                                                               \
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }                        \
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, "internal error: %s", e.what()); }
 int mipt_scene_create(const MiptSceneDesc *desc, int device_id, MiptScene **out) { MIPT_NO_THROW(scene_create_impl(desc, device_id, out)) }
 } // extern "C"
 // internal (mipt_multi.cpp): one scene on device_ids[0], device-to-device replicas on the others
@@ -480,9 +453,9 @@ int mipt_scene_get_bvh(MiptScene *scene, MiptNode *nodes_out, uint32_t nodes_cap
     if (!scene->d_nodes || !scene->d_tri_order)
         return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_get_bvh: this scene was created from host-built nodes (the caller already has them)");
     if (nodes_cap < scene->n_nodes) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_get_bvh: nodes_cap %u < %u nodes", nodes_cap, scene->n_nodes);
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipMemcpy(nodes_out, scene->d_nodes, (size_t)scene->n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
-    if (tri_order_out) HIP_TRY(hipMemcpy(tri_order_out, scene->d_tri_order, scene->n_tris * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    MIPT_HIP(hipSetDevice(scene->device));
+    MIPT_HIP(hipMemcpy(nodes_out, scene->d_nodes, (size_t)scene->n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
+    if (tri_order_out) MIPT_HIP(hipMemcpy(tri_order_out, scene->d_tri_order, scene->n_tris * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (n_nodes_out) *n_nodes_out = scene->n_nodes;
     return MIPT_OK;
 }
@@ -550,7 +523,7 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         return fail(MIPT_ERR_INVALID_ARG, "MIPT_FLAG_ACCUM needs MIPT_FLAG_SUM (a running sum, divided once at the end)");
     if (d_rgba8 && (packed || (opt->flags & MIPT_FLAG_SUM)))
         return fail(MIPT_ERR_INVALID_ARG, "RGBA8 output needs a full-frame mean buffer (not PACKED / SUM)");
-    HIP_TRY(hipSetDevice(scene->device));
+    MIPT_HIP(hipSetDevice(scene->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     const MiptCamera *camera = cameras;
 
@@ -594,16 +567,8 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     // (world 2 / 4 / 8) spends most of its time in the latency-bound tail and is 2 - 8 % slower with it: period 1 there
     pr.leaf_period = (pr.total_work >= 4ull * (unsigned long long)scene->n_cu * (unsigned long long)occ * mipt::kBlockThreads) ? 4u : 1u;
     pr.leaf_den = 4u;
-    long long grid = (long long)scene->n_cu * bpc;
-    const long long need_blocks = (long long)((pr.total_work + mipt::kBlockThreads - 1) / mipt::kBlockThreads);
-    if (grid > need_blocks) grid = need_blocks;
-    if (grid < 1) grid = 1;
-    const size_t waves = (size_t)grid * mipt::kWavesPerBlock;
-    if (waves > scene->ovf_waves) {
-        if (scene->d_ovf) { (void)hipFree(scene->d_ovf); scene->d_ovf = nullptr; scene->ovf_waves = 0; }
-        HIP_TRY(hipMalloc((void **)&scene->d_ovf, waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t)));
-        scene->ovf_waves = waves;
-    }
+    int grid = 0;
+    if ((rc = mipt::traversal_grid(scene, bpc, pr.total_work, &grid))) return rc;
     pr.ovf = scene->d_ovf;
 
     // MIPT_FLAG_TOUCHED (diagnostic, counting build only): one bit per 128-B line of [pairs | tri_pos] and of tri_attr
@@ -612,8 +577,8 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     const size_t geom_words = (geom_lines + 31) / 32, attr_words = (attr_lines + 31) / 32;
     pr.touched = nullptr; pr.touched_attr_base = (uint32_t)(geom_words * 32);
     if (touched) {
-        if (!scene->d_touched) HIP_TRY(hipMalloc((void **)&scene->d_touched, (geom_words + attr_words) * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(scene->d_touched, 0, (geom_words + attr_words) * sizeof(uint32_t), stream));
+        if (!scene->d_touched) MIPT_HIP(hipMalloc((void **)&scene->d_touched, (geom_words + attr_words) * sizeof(uint32_t)));
+        MIPT_HIP(hipMemsetAsync(scene->d_touched, 0, (geom_words + attr_words) * sizeof(uint32_t), stream));
         pr.touched = scene->d_touched;
     }
     // the batch's camera table: one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream
@@ -626,26 +591,30 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
             scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
         }
         const size_t bytes = scene->h_cams.size() * sizeof(float4);
-        if ((rc = ensure((void **)&scene->d_cams, &scene->cams_bytes, bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, bytes))) return rc;
+        MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
         bt.cams = scene->d_cams;
         bt.view_pixels = opt->width * opt->height;
         bt.tiles_recip = 0xffffffffu / pr.n_local_tiles;
     }
-    HIP_TRY(hipMemsetAsync(scene->d_stats, 0, sizeof(mipt::DevStats), stream));
-    HIP_TRY(hipEventRecord(scene->ev0, stream));
-    HIP_TRY(mipt::launch_trace(scene->dev, pr, batch ? &bt : nullptr, count, cull, (int)opt->shading, (int)grid, stream));
-    HIP_TRY(hipEventRecord(scene->ev1, stream));
-    if (touched) {
-        HIP_TRY(mipt::launch_popcount(scene->d_touched, geom_words, &scene->d_stats->touched_geom, stream));
-        HIP_TRY(mipt::launch_popcount(scene->d_touched + geom_words, attr_words, &scene->d_stats->touched_attr, stream));
-    }
-    if (d_rgba8) HIP_TRY(mipt::launch_tonemap(d_hdr_rgb, (unsigned long long)opt->width * opt->height * n_views, 1.0f, d_rgba8, stream));
     mipt::DevStats hs;
-    HIP_TRY(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
+    rc = mipt::traversal_launch(
+        scene, stream,
+        [&]() -> int {
+            MIPT_HIP(mipt::launch_trace(scene->dev, pr, batch ? &bt : nullptr, count, cull, (int)opt->shading, (int)grid, stream));
+            return MIPT_OK;
+        },
+        [&]() -> int {
+            if (touched) {
+                MIPT_HIP(mipt::launch_popcount(scene->d_touched, geom_words, &scene->d_stats->touched_geom, stream));
+                MIPT_HIP(mipt::launch_popcount(scene->d_touched + geom_words, attr_words, &scene->d_stats->touched_attr, stream));
+            }
+            if (d_rgba8) MIPT_HIP(mipt::launch_tonemap(d_hdr_rgb, (unsigned long long)opt->width * opt->height * n_views, 1.0f, d_rgba8, stream));
+            return MIPT_OK;
+        },
+        hs, ms);
+    if (rc && rc != MIPT_ERR_STACK) return rc;
     if (stats) {
         memset(stats, 0, sizeof *stats);
         stats->kernel_ms = ms;
@@ -657,10 +626,7 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
         stats->touched_lines[0] = hs.touched_geom; stats->touched_lines[1] = hs.touched_attr;
     }
-    if (hs.stack_overflows)
-        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
-                    hs.stack_overflows, mipt::kStackLds + mipt::kStackOvf);
-    return MIPT_OK;
+    return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the frame and the stats delivered
 }
 
 int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
@@ -682,20 +648,18 @@ int mipt_render_batch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_vi
     if (opt->flags & MIPT_FLAG_ACCUM) return fail(MIPT_ERR_INVALID_ARG, "MIPT_FLAG_ACCUM needs a caller-owned device buffer: use mipt_render_batch_device");
     if (rgba8 && (opt->flags & MIPT_FLAG_SUM))
         return fail(MIPT_ERR_INVALID_ARG, "RGBA8 output needs a full-frame mean buffer (not PACKED / SUM)");
-    HIP_TRY(hipSetDevice(scene->device));
+    MIPT_HIP(hipSetDevice(scene->device));
     const uint64_t n_pix = (uint64_t)n_views * opt->width * opt->height;
-    size_t have = scene->hdr_floats * sizeof(float);
-    if ((rc = ensure((void **)&scene->d_hdr, &have, (size_t)n_pix * 3 * sizeof(float)))) return rc;
-    scene->hdr_floats = have / sizeof(float);
+    if ((rc = mipt::grow_device_buffer((void **)&scene->d_hdr, &scene->hdr_bytes, (size_t)n_pix * 3 * sizeof(float)))) return rc;
     uint8_t *d_rgba = nullptr;
     if (rgba8) {
-        if ((rc = ensure((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
         d_rgba = scene->d_rgba;
     }
     rc = mipt_render_batch_device(scene, cameras, n_views, opt, scene->d_hdr, d_rgba, nullptr, stats);
     if (rc && rc != MIPT_ERR_STACK) return rc;
-    if (hdr_rgb) HIP_TRY(hipMemcpy(hdr_rgb, scene->d_hdr, (size_t)n_pix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rgba8) HIP_TRY(hipMemcpy(rgba8, scene->d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
+    if (hdr_rgb) MIPT_HIP(hipMemcpy(hdr_rgb, scene->d_hdr, (size_t)n_pix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgba8) MIPT_HIP(hipMemcpy(rgba8, scene->d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -710,24 +674,22 @@ int mipt_render(MiptScene *scene, const MiptCamera *camera, const MiptOptions *o
     int rc = validate_options(opt);
     if (rc) return rc;
     if (opt->flags & MIPT_FLAG_ACCUM) return fail(MIPT_ERR_INVALID_ARG, "MIPT_FLAG_ACCUM needs a caller-owned device buffer: use mipt_render_device");
-    HIP_TRY(hipSetDevice(scene->device));
+    MIPT_HIP(hipSetDevice(scene->device));
     const uint32_t world = opt->tile_world ? opt->tile_world : 1u;
     const bool packed = (opt->flags & MIPT_FLAG_PACKED) != 0 && world > 1;
     const uint64_t n_pix = (uint64_t)opt->width * opt->height;
     const uint64_t n_out = packed ? mipt_packed_pixels(opt->width, opt->height, world) : n_pix;
-    size_t have = scene->hdr_floats * sizeof(float);
-    if ((rc = ensure((void **)&scene->d_hdr, &have, (size_t)n_out * 3 * sizeof(float)))) return rc;
-    scene->hdr_floats = have / sizeof(float);
-    if (world > 1 && !packed) HIP_TRY(hipMemsetAsync(scene->d_hdr, 0, (size_t)n_out * 3 * sizeof(float), nullptr));
+    if ((rc = mipt::grow_device_buffer((void **)&scene->d_hdr, &scene->hdr_bytes, (size_t)n_out * 3 * sizeof(float)))) return rc;
+    if (world > 1 && !packed) MIPT_HIP(hipMemsetAsync(scene->d_hdr, 0, (size_t)n_out * 3 * sizeof(float), nullptr));
     uint8_t *d_rgba = nullptr;
     if (rgba8) {
-        if ((rc = ensure((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
         d_rgba = scene->d_rgba;
     }
     rc = mipt_render_device(scene, camera, opt, scene->d_hdr, d_rgba, nullptr, stats);
     if (rc && rc != MIPT_ERR_STACK) return rc;
-    if (hdr_rgb) HIP_TRY(hipMemcpy(hdr_rgb, scene->d_hdr, (size_t)n_out * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (rgba8) HIP_TRY(hipMemcpy(rgba8, scene->d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
+    if (hdr_rgb) MIPT_HIP(hipMemcpy(hdr_rgb, scene->d_hdr, (size_t)n_out * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgba8) MIPT_HIP(hipMemcpy(rgba8, scene->d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -735,19 +697,19 @@ int mipt_unpack_tiles(const float *d_packed_all, uint32_t width, uint32_t height
                       float *d_hdr_rgb, void *hip_stream) {
     if (!d_packed_all || !d_hdr_rgb || width == 0 || height == 0 || tile_world == 0)
         return fail(MIPT_ERR_INVALID_ARG, "mipt_unpack_tiles: bad argument");
-    HIP_TRY(mipt::launch_unpack_tiles(d_packed_all, width, height, tile_world, d_hdr_rgb, (hipStream_t)hip_stream));
+    MIPT_HIP(mipt::launch_unpack_tiles(d_packed_all, width, height, tile_world, d_hdr_rgb, (hipStream_t)hip_stream));
     return MIPT_OK;
 }
 
 int mipt_tonemap_device(const float *d_hdr_rgb, uint64_t n_pixels, float divisor, uint8_t *d_rgba8, void *hip_stream) {
     if (!d_hdr_rgb || !d_rgba8 || n_pixels == 0) return fail(MIPT_ERR_INVALID_ARG, "mipt_tonemap_device: bad argument");
-    HIP_TRY(mipt::launch_tonemap(d_hdr_rgb, n_pixels, divisor, d_rgba8, (hipStream_t)hip_stream));
+    MIPT_HIP(mipt::launch_tonemap(d_hdr_rgb, n_pixels, divisor, d_rgba8, (hipStream_t)hip_stream));
     return MIPT_OK;
 }
 
 int mipt_postprocess_device(const float *d_hdr_rgb, uint64_t n_pixels, float divisor, uint16_t *d_rgba16, void *hip_stream) {
     if (!d_hdr_rgb || !d_rgba16 || n_pixels == 0) return fail(MIPT_ERR_INVALID_ARG, "mipt_postprocess_device: bad argument");
-    HIP_TRY(mipt::launch_postprocess(d_hdr_rgb, n_pixels, divisor, d_rgba16, (hipStream_t)hip_stream));
+    MIPT_HIP(mipt::launch_postprocess(d_hdr_rgb, n_pixels, divisor, d_rgba16, (hipStream_t)hip_stream));
     return MIPT_OK;
 }
 

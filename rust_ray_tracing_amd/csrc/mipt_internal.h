@@ -1,10 +1,51 @@
 // mipt_internal.h -- functions shared between the translation units of libmipt.so.  None of them is exported: the library is built
 // with -fvisibility=hidden and only the MIPT_API declarations of include/mipt.h leave it.  (Host C++ only: no HIP types here, so the
 // CPU sanitizer builds of tests/cpp/ can include it.)
+// The error plumbing that needs no HIP type lives here: mipt::fail (defined below) and the MIPT_NO_THROW fence.  The HIP-call
+// macros and the grow-on-demand device buffer are in mipt_host_util.h.
 #pragma once
 #include "../../include/mipt.h"
 
+#include <cstdarg>
+#include <cstdio>
+#include <exception>
+#include <new>
+#include <string>
+
 void mipt_internal_set_error(const char *msg);          // sets the calling thread's mipt_last_error() text (mipt_api.cpp)
+
+namespace mipt {
+
+// Sets the calling thread's mipt_last_error() text (printf-style, any length) and returns `code`.  Defined here, over
+// mipt_internal_set_error, and not beside the text in mipt_api.cpp: obj_loader.cpp reports through it, and the CPU sanitizer build
+// of tests/cpp/sanitize_host.cpp links the loader without mipt_api.cpp, with its own mipt_internal_set_error.
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+inline int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap, ap2;
+    va_start(ap, fmt);
+    va_copy(ap2, ap);
+    const int n = vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (n >= (int)sizeof buf) {                          // a long path or a nested message: format again into a buffer that fits
+        std::string big((size_t)n + 1, '\0');
+        vsnprintf(&big[0], big.size(), fmt, ap2);
+        mipt_internal_set_error(big.c_str());
+    } else
+        mipt_internal_set_error(n < 0 ? "" : buf);
+    va_end(ap2);
+    return code;
+}
+
+} // namespace mipt
+
+// No C++ exception may cross the C ABI (the caller may be Rust or C): allocation failures become status codes.  The body of an
+// extern "C" entry is `MIPT_NO_THROW(impl(args))`; MIPT_NO_THROW_AS names the status code (the loaders report MIPT_ERR_IO).
+#define MIPT_NO_THROW_AS(code, call)                                                                                    \
+    try { return call; }                                                                                               \
+    catch (const std::bad_alloc &) { return mipt::fail(code, "out of host memory"); }                                  \
+    catch (const std::exception &e) { return mipt::fail(code, "internal error: %s", e.what()); }
+#define MIPT_NO_THROW(call) MIPT_NO_THROW_AS(MIPT_ERR_INVALID_ARG, call)
 
 namespace mipt {
 

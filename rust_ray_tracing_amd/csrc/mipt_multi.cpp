@@ -14,6 +14,7 @@
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
 #include "mipt_internal.h"
+#include "mipt_host_util.h"
 
 #include <rccl/rccl.h>
 
@@ -32,11 +33,11 @@ struct MiptMulti {
     std::vector<ncclComm_t> comms;
     std::vector<hipStream_t> streams;
     std::vector<float *> d_part;          // per device: packed tile slice / full-frame partial sum
-    std::vector<size_t> part_floats;
+    std::vector<size_t> part_bytes;
     float *d_all = nullptr;               // root: gathered slices
-    size_t all_floats = 0;
+    size_t all_bytes = 0;
     float *d_frame = nullptr;             // root: assembled frame
-    size_t frame_floats = 0;
+    size_t frame_bytes = 0;
     uint8_t *d_rgba = nullptr;
     size_t rgba_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -54,28 +55,13 @@ constexpr bool kLogicalRanks = true;
 constexpr bool kLogicalRanks = false;
 #endif
 
-int fail(int code, const std::string &msg) {
-    mipt_internal_set_error(msg.c_str());
-    return code;
-}
-#define M_HIP(expr)                                                                                                    \
-    do {                                                                                                               \
-        hipError_t e__ = (expr);                                                                                       \
-        if (e__ != hipSuccess) return fail(MIPT_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e__));     \
-    } while (0)
+using mipt::fail;
+
 #define M_NCCL(expr)                                                                                                   \
     do {                                                                                                               \
         ncclResult_t r__ = (expr);                                                                                     \
-        if (r__ != ncclSuccess) return fail(MIPT_ERR_RCCL, std::string(#expr " failed: ") + ncclGetErrorString(r__)); \
+        if (r__ != ncclSuccess) return fail(MIPT_ERR_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r__));           \
     } while (0)
-
-int grow(void **p, size_t *have, size_t want_bytes) {
-    if (*p && *have >= want_bytes) return MIPT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    M_HIP(hipMalloc(p, want_bytes));
-    *have = want_bytes;
-    return MIPT_OK;
-}
 
 int root_buffer_check(const void *p, int root_device, const char *name) {
     hipPointerAttribute_t a;
@@ -83,7 +69,7 @@ int root_buffer_check(const void *p, int root_device, const char *name) {
     const hipError_t e = hipPointerGetAttributes(&a, p);
     if (e != hipSuccess) (void)hipGetLastError();         // an unregistered host pointer is reported as an error: clear it
     if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != root_device)
-        return fail(MIPT_ERR_INVALID_ARG, std::string("mipt_render_multi_device: ") + name + " is not device memory of the root device " + std::to_string(root_device));
+        return fail(MIPT_ERR_INVALID_ARG, "mipt_render_multi_device: %s is not device memory of the root device %d", name, root_device);
     return MIPT_OK;
 }
 
@@ -114,12 +100,12 @@ int create_impl(const MiptSceneDesc *desc, const int *device_ids, int n_devices,
     if (visible < 0) return visible;
     if (n_devices == 0) n_devices = visible;                     // 0 = every visible device
     if (n_devices < 1 || (!kLogicalRanks && n_devices > visible) || n_devices > 64)
-        return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_create: n_devices " + std::to_string(n_devices) + " but " + std::to_string(visible) + " HIP device(s) visible");
+        return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_create: n_devices %d but %d HIP device(s) visible", n_devices, visible);
     MiptMulti *m = new MiptMulti();
     m->n = n_devices;
     for (int i = 0; i < n_devices; i++) {
         const int d = device_ids ? device_ids[i] : i;
-        if (d < 0 || d >= visible) { destroy(m); return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_create: bad device id " + std::to_string(d)); }
+        if (d < 0 || d >= visible) { destroy(m); return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_create: bad device id %d", d); }
         for (int j = 0; j < i && !kLogicalRanks; j++)
             if (m->devices[j] == d) { destroy(m); return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_create: device listed twice"); }
         m->devices.push_back(d);
@@ -127,24 +113,24 @@ int create_impl(const MiptSceneDesc *desc, const int *device_ids, int n_devices,
     m->scenes.assign(n_devices, nullptr);
     m->streams.assign(n_devices, nullptr);
     m->d_part.assign(n_devices, nullptr);
-    m->part_floats.assign(n_devices, 0);
+    m->part_bytes.assign(n_devices, 0);
     m->last.assign(n_devices, MiptStats{});
     // scene replicas: the scene reaches device 0 once (host layout + upload, or built there from the triangles); the others are
     // device-to-device copies
     {
         const int rc = mipt::scene_create_replicas(desc, m->devices.data(), n_devices, m->scenes.data(), from_triangles);
-        if (rc) { const std::string e = mipt_last_error(); destroy(m); return fail(rc, e); }
+        if (rc) { const std::string e = mipt_last_error(); destroy(m); return fail(rc, "%s", e.c_str()); }
     }
     for (int i = 0; i < n_devices; i++) {
         hipError_t e = hipSetDevice(m->devices[i]);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->streams[i], hipStreamNonBlocking);
-        if (e != hipSuccess) { destroy(m); return fail(MIPT_ERR_HIP, std::string("stream creation failed: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { destroy(m); return fail(MIPT_ERR_HIP, "stream creation failed: %s", hipGetErrorString(e)); }
     }
     (void)hipSetDevice(m->devices[0]);
     if (hipEventCreate(&m->ev0) != hipSuccess || hipEventCreate(&m->ev1) != hipSuccess) { destroy(m); return fail(MIPT_ERR_HIP, "event creation failed"); }
     m->comms.assign(n_devices, nullptr);
     ncclResult_t r = ncclCommInitAll(m->comms.data(), n_devices, m->devices.data());
-    if (r != ncclSuccess) { destroy(m); return fail(MIPT_ERR_RCCL, std::string("ncclCommInitAll failed: ") + ncclGetErrorString(r)); }
+    if (r != ncclSuccess) { destroy(m); return fail(MIPT_ERR_RCCL, "ncclCommInitAll failed: %s", ncclGetErrorString(r)); }
     *out = m;
     return MIPT_OK;
 }
@@ -182,23 +168,17 @@ int render_impl(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, 
     const size_t part_floats = (size_t)(mode == MIPT_MULTI_TILES ? slots : n_pix) * 3;
 
     for (int i = 0; i < n; i++) {
-        M_HIP(hipSetDevice(m->devices[i]));
-        size_t have = m->part_floats[i] * sizeof(float);
-        int rc = grow((void **)&m->d_part[i], &have, part_floats * sizeof(float));
+        MIPT_HIP(hipSetDevice(m->devices[i]));
+        const int rc = mipt::grow_device_buffer((void **)&m->d_part[i], &m->part_bytes[i], part_floats * sizeof(float));
         if (rc) return rc;
-        m->part_floats[i] = have / sizeof(float);
     }
-    M_HIP(hipSetDevice(m->devices[0]));
+    MIPT_HIP(hipSetDevice(m->devices[0]));
     {
-        size_t have = m->all_floats * sizeof(float);
-        int rc = grow((void **)&m->d_all, &have, (mode == MIPT_MULTI_TILES ? (size_t)n * part_floats : 4) * sizeof(float));
+        int rc = mipt::grow_device_buffer((void **)&m->d_all, &m->all_bytes, (mode == MIPT_MULTI_TILES ? (size_t)n * part_floats : 4) * sizeof(float));
         if (rc) return rc;
-        m->all_floats = have / sizeof(float);
         if (!device_out) {
-            have = m->frame_floats * sizeof(float);
-            if ((rc = grow((void **)&m->d_frame, &have, (size_t)n_pix * 3 * sizeof(float)))) return rc;
-            m->frame_floats = have / sizeof(float);
-            if (rgba8 && (rc = grow((void **)&m->d_rgba, &m->rgba_bytes, (size_t)n_pix * 4))) return rc;
+            if ((rc = mipt::grow_device_buffer((void **)&m->d_frame, &m->frame_bytes, (size_t)n_pix * 3 * sizeof(float)))) return rc;
+            if (rgba8 && (rc = mipt::grow_device_buffer((void **)&m->d_rgba, &m->rgba_bytes, (size_t)n_pix * 4))) return rc;
         }
     }
     float *const d_frame = device_out ? hdr_rgb : m->d_frame;       // where the assembled frame is built (device 0)
@@ -259,18 +239,13 @@ int render_impl(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, 
     int soft = MIPT_OK;                                                   // MIPT_ERR_STACK: frame incomplete but delivered, like mipt_render
     for (int i = 0; i < n; i++) {
         if (rcs[i] == MIPT_ERR_STACK) { soft = MIPT_ERR_STACK; continue; }
-        if (rcs[i]) return fail(rcs[i], "device " + std::to_string(i) + ": " + errs[i]);
+        if (rcs[i]) return fail(rcs[i], "device %d: %s", i, errs[i].c_str());
     }
 
     // ---- the one collective, then assemble on device 0 ----
     // From here on every rank's stream may hold work that touches d_part / d_all: any failure drains all streams before returning.
-#define M_HIP_D(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e__ = (expr);                                                                                       \
-        if (e__ != hipSuccess) { drain(m); return fail(MIPT_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e__)); } \
-    } while (0)
-    M_HIP(hipSetDevice(m->devices[0]));
-    M_HIP(hipEventRecord(m->ev0, m->streams[0]));
+    MIPT_HIP(hipSetDevice(m->devices[0]));
+    MIPT_HIP(hipEventRecord(m->ev0, m->streams[0]));
     {
         ncclResult_t r = ncclGroupStart();
         for (int i = 0; i < n && r == ncclSuccess; i++) {
@@ -281,34 +256,33 @@ int render_impl(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, 
         }
         const ncclResult_t r_end = ncclGroupEnd();
         if (r == ncclSuccess) r = r_end;
-        if (r != ncclSuccess) { drain(m); return fail(MIPT_ERR_RCCL, std::string("RCCL collective failed: ") + ncclGetErrorString(r)); }
+        if (r != ncclSuccess) { drain(m); return fail(MIPT_ERR_RCCL, "RCCL collective failed: %s", ncclGetErrorString(r)); }
     }
-    M_HIP_D(hipSetDevice(m->devices[0]));
+    MIPT_HIP_OR(drain(m), hipSetDevice(m->devices[0]));
     if (mode == MIPT_MULTI_TILES)
-        M_HIP_D(mipt::launch_unpack_tiles(m->d_all, opt->width, opt->height, (uint32_t)n, d_frame, m->streams[0]));
+        MIPT_HIP_OR(drain(m), mipt::launch_unpack_tiles(m->d_all, opt->width, opt->height, (uint32_t)n, d_frame, m->streams[0]));
     else
-        M_HIP_D(mipt::launch_divide(d_frame, (unsigned long long)n_pix * 3, (float)opt->samples, m->streams[0]));   // cpu.rs:60
-    if (rgba8) M_HIP_D(mipt::launch_tonemap(d_frame, (unsigned long long)n_pix, 1.0f, d_rgba, m->streams[0]));
-    M_HIP_D(hipEventRecord(m->ev1, m->streams[0]));
+        MIPT_HIP_OR(drain(m), mipt::launch_divide(d_frame, (unsigned long long)n_pix * 3, (float)opt->samples, m->streams[0]));   // cpu.rs:60
+    if (rgba8) MIPT_HIP_OR(drain(m), mipt::launch_tonemap(d_frame, (unsigned long long)n_pix, 1.0f, d_rgba, m->streams[0]));
+    MIPT_HIP_OR(drain(m), hipEventRecord(m->ev1, m->streams[0]));
     if (!device_out) {
-        if (hdr_rgb) M_HIP_D(hipMemcpyAsync(hdr_rgb, d_frame, (size_t)n_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, m->streams[0]));
-        if (rgba8) M_HIP_D(hipMemcpyAsync(rgba8, d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost, m->streams[0]));
+        if (hdr_rgb) MIPT_HIP_OR(drain(m), hipMemcpyAsync(hdr_rgb, d_frame, (size_t)n_pix * 3 * sizeof(float), hipMemcpyDeviceToHost, m->streams[0]));
+        if (rgba8) MIPT_HIP_OR(drain(m), hipMemcpyAsync(rgba8, d_rgba, (size_t)n_pix * 4, hipMemcpyDeviceToHost, m->streams[0]));
     }
     for (int i = n - 1; i >= 0; i--) {                                    // every rank's part of the collective has drained
-        M_HIP_D(hipSetDevice(m->devices[i]));
-        M_HIP_D(hipStreamSynchronize(m->streams[i]));
+        MIPT_HIP_OR(drain(m), hipSetDevice(m->devices[i]));
+        MIPT_HIP_OR(drain(m), hipStreamSynchronize(m->streams[i]));
     }
-#undef M_HIP_D
     for (int i = 0; i < n; i++) {
         ncclResult_t async_err = ncclSuccess;
         M_NCCL(ncclCommGetAsyncError(m->comms[i], &async_err));
-        if (async_err != ncclSuccess) return fail(MIPT_ERR_RCCL, std::string("RCCL asynchronous error: ") + ncclGetErrorString(async_err));
+        if (async_err != ncclSuccess) return fail(MIPT_ERR_RCCL, "RCCL asynchronous error: %s", ncclGetErrorString(async_err));
     }
     if (stats) {
         memset(stats, 0, sizeof *stats);
         stats->n_devices = (uint32_t)n;
         float ms = 0.0f;
-        M_HIP(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+        MIPT_HIP(hipEventElapsedTime(&ms, m->ev0, m->ev1));
         stats->collective_ms = ms;
         MiptStats &t = stats->total;
         for (int i = 0; i < n; i++) {
@@ -330,27 +304,24 @@ int render_impl(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, 
 extern "C" {
 
 int mipt_multi_create(const MiptSceneDesc *desc, const int *device_ids, int n_devices, MiptMulti **out) {
-    try { return create_impl(desc, device_ids, n_devices, out, false); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(create_impl(desc, device_ids, n_devices, out, false))
 }
 
 int mipt_multi_create_from_triangles(const MiptSceneDesc *desc, const int *device_ids, int n_devices, MiptMulti **out) {
-    try { return create_impl(desc, device_ids, n_devices, out, true); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(create_impl(desc, device_ids, n_devices, out, true))
 }
 
 // The root replica from the host array (the one path of mipt_scene_update_triangles), then every other replica by device-to-device copies
+static int update_impl(MiptMulti *m, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info) {
+    int rc = mipt::scene_update_host(m->scenes[0], tris, n_tris, mode, info);
+    for (int i = 1; i < m->n && rc == MIPT_OK; i++)
+        if ((rc = mipt::replica_refresh(m->scenes[0], m->scenes[(size_t)i])))
+            rc = fail(rc, "mipt_multi_update_triangles: the root is updated but the replica on device %d is not: %s", m->devices[(size_t)i], mipt_last_error());
+    return rc;
+}
 int mipt_multi_update_triangles(MiptMulti *m, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info) {
     if (!m) return fail(MIPT_ERR_INVALID_ARG, "mipt_multi_update_triangles: null argument");
-    try {
-        int rc = mipt::scene_update_host(m->scenes[0], tris, n_tris, mode, info);
-        for (int i = 1; i < m->n && rc == MIPT_OK; i++)
-            if ((rc = mipt::replica_refresh(m->scenes[0], m->scenes[(size_t)i])))
-                rc = fail(rc, "mipt_multi_update_triangles: the root is updated but the replica on device " + std::to_string(m->devices[(size_t)i]) + " is not: " + mipt_last_error());
-        return rc;
-    }
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(update_impl(m, tris, n_tris, mode, info))
 }
 
 MiptScene *mipt_multi_scene(MiptMulti *m, int index) { return (m && index >= 0 && index < m->n) ? m->scenes[(size_t)index] : nullptr; }
@@ -361,14 +332,12 @@ int mipt_multi_device_count(const MiptMulti *m) { return m ? m->n : 0; }
 
 int mipt_render_multi(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, uint32_t mode,
                       float *hdr_rgb, uint8_t *rgba8, MiptMultiStats *stats) {
-    try { return render_impl(m, camera, opt, mode, hdr_rgb, rgba8, stats, false); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(render_impl(m, camera, opt, mode, hdr_rgb, rgba8, stats, false))
 }
 
 int mipt_render_multi_device(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, uint32_t mode,
                              float *d_hdr_rgb, uint8_t *d_rgba8, MiptMultiStats *stats) {
-    try { return render_impl(m, camera, opt, mode, d_hdr_rgb, d_rgba8, stats, true); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(render_impl(m, camera, opt, mode, d_hdr_rgb, d_rgba8, stats, true))
 }
 
 int mipt_multi_device_stats(const MiptMulti *m, int index, MiptStats *out) {

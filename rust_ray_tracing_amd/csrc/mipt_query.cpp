@@ -4,41 +4,16 @@
 #include "pt_kernel.h"
 #include "mipt_internal.h"
 #include "mipt_scene.h"
+#include "mipt_host_util.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <exception>
-#include <new>
 
 static_assert(sizeof(MiptRay) == 32 && sizeof(MiptHit) == 16 && sizeof(MiptQueryOptions) == 32, "ABI struct sizes (tests/test_query_abi.py)");
 
 namespace {
 
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    mipt_internal_set_error(buf);
-    return code;
-}
-#define Q_HIP(expr)                                                                             \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return fail(MIPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));          \
-    } while (0)
-
-int ensure(void **p, size_t *have, size_t want_bytes) {
-    if (*have >= want_bytes && *p) return MIPT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    Q_HIP(hipMalloc(p, want_bytes));
-    *have = want_bytes;
-    return MIPT_OK;
-}
+using mipt::fail;
 
 // everything that needs neither the scene's contents nor a device
 int validate(const char *who, const MiptScene *scene, const void *rays, const void *out, uint64_t n_rays, const MiptQueryOptions *opt) {
@@ -72,7 +47,7 @@ int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const
     if (n_rays == 0) return MIPT_OK;
     const bool count = opt && (opt->flags & MIPT_FLAG_COUNT) != 0;
     const bool cull = opt && opt->traversal == MIPT_TRAVERSAL_CULLED;
-    Q_HIP(hipSetDevice(scene->device));
+    MIPT_HIP(hipSetDevice(scene->device));
 
     mipt::DevQuery q{};
     q.rays = reinterpret_cast<const float4 *>(d_rays);
@@ -82,27 +57,20 @@ int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const
     q.cull_scale = 1.0f + (opt ? opt->cull_margin : 0.0f);
     q.stats = scene->d_stats;
 
-    long long grid = (long long)scene->n_cu * mipt::query_blocks_per_cu(count, cull, anyhit);
-    const long long need_blocks = (long long)((n_rays + mipt::kBlockThreads - 1) / mipt::kBlockThreads);
-    if (grid > need_blocks) grid = need_blocks;
-    if (grid < 1) grid = 1;
-    const size_t waves = (size_t)grid * mipt::kWavesPerBlock;
-    if (waves > scene->ovf_waves) {
-        if (scene->d_ovf) { (void)hipFree(scene->d_ovf); scene->d_ovf = nullptr; scene->ovf_waves = 0; }
-        Q_HIP(hipMalloc((void **)&scene->d_ovf, waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t)));
-        scene->ovf_waves = waves;
-    }
+    int grid = 0, rc = mipt::traversal_grid(scene, mipt::query_blocks_per_cu(count, cull, anyhit), n_rays, &grid);
+    if (rc) return rc;
     q.ovf = scene->d_ovf;
 
-    Q_HIP(hipMemsetAsync(scene->d_stats, 0, sizeof(mipt::DevStats), stream));
-    Q_HIP(hipEventRecord(scene->ev0, stream));
-    Q_HIP(mipt::launch_ray_query(scene->dev, q, count, cull, anyhit, (int)grid, stream));
-    Q_HIP(hipEventRecord(scene->ev1, stream));
     mipt::DevStats hs;
-    Q_HIP(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
-    Q_HIP(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    Q_HIP(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
+    rc = mipt::traversal_launch(
+        scene, stream,
+        [&]() -> int {
+            MIPT_HIP(mipt::launch_ray_query(scene->dev, q, count, cull, anyhit, (int)grid, stream));
+            return MIPT_OK;
+        },
+        []() -> int { return MIPT_OK; }, hs, ms);
+    if (rc && rc != MIPT_ERR_STACK) return rc;
     if (stats) {
         stats->kernel_ms = ms;
         stats->stack_overflows = hs.stack_overflows;
@@ -111,10 +79,7 @@ int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const
             stats->hits = hs.hits; stats->max_stack = hs.max_stack;
         }
     }
-    if (hs.stack_overflows)
-        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
-                    hs.stack_overflows, mipt::kStackLds + mipt::kStackOvf);
-    return MIPT_OK;
+    return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the results and the stats delivered
 }
 
 int query_device(const char *who, MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, void *d_out,
@@ -134,40 +99,34 @@ int query_host(const char *who, MiptScene *scene, const MiptRay *rays, uint64_t 
     int rc = validate(who, scene, rays, out, n_rays, opt);
     if (rc) return rc;
     if (n_rays == 0) return query_launch(scene, nullptr, 0, opt, nullptr, anyhit, nullptr, stats);
-    Q_HIP(hipSetDevice(scene->device));
+    MIPT_HIP(hipSetDevice(scene->device));
     const size_t out_bytes = (size_t)n_rays * (anyhit ? 1u : sizeof(MiptHit));
-    if ((rc = ensure(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
-    if ((rc = ensure(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
-    Q_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
+    if ((rc = mipt::grow_device_buffer(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
+    if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
+    MIPT_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
     rc = query_launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, scene->d_qout, anyhit, nullptr, stats);
     if (rc && rc != MIPT_ERR_STACK) return rc;
-    Q_HIP(hipMemcpy(out, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
+    MIPT_HIP(hipMemcpy(out, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
     return rc;
 }
 
 } // namespace
 
-// No C++ exception may cross the C ABI: allocation failures become status codes.
-#define Q_NO_THROW(call)                                                                                                \
-    try { return call; }                                                                                               \
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }                        \
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, "internal error: %s", e.what()); }
-
 extern "C" {
 
 int mipt_query_closest(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, MiptHit *hits, MiptStats *stats) {
-    Q_NO_THROW(query_host("mipt_query_closest", scene, rays, n_rays, opt, hits, false, stats))
+    MIPT_NO_THROW(query_host("mipt_query_closest", scene, rays, n_rays, opt, hits, false, stats))
 }
 int mipt_query_closest_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, MiptHit *d_hits,
                               void *hip_stream, MiptStats *stats) {
-    Q_NO_THROW(query_device("mipt_query_closest_device", scene, d_rays, n_rays, opt, d_hits, false, hip_stream, stats))
+    MIPT_NO_THROW(query_device("mipt_query_closest_device", scene, d_rays, n_rays, opt, d_hits, false, hip_stream, stats))
 }
 int mipt_query_occluded(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, uint8_t *occluded, MiptStats *stats) {
-    Q_NO_THROW(query_host("mipt_query_occluded", scene, rays, n_rays, opt, occluded, true, stats))
+    MIPT_NO_THROW(query_host("mipt_query_occluded", scene, rays, n_rays, opt, occluded, true, stats))
 }
 int mipt_query_occluded_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, uint8_t *d_occluded,
                                void *hip_stream, MiptStats *stats) {
-    Q_NO_THROW(query_device("mipt_query_occluded_device", scene, d_rays, n_rays, opt, d_occluded, true, hip_stream, stats))
+    MIPT_NO_THROW(query_device("mipt_query_occluded_device", scene, d_rays, n_rays, opt, d_occluded, true, hip_stream, stats))
 }
 
 } // extern "C"

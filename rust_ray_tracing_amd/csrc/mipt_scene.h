@@ -1,6 +1,8 @@
-// mipt_scene.h -- the device-resident scene behind the opaque MiptScene handle, shared by the translation units that build it
-// (mipt_api.cpp: host layout + upload; scene_device.hip: layout built on the GPU; both: replicas by peer copy) and by the test
-// library's checksum hook (tests/cpp/scene_hooks.hip, libmipt_diag.so).  Internal: HIP types, not part of include/mipt.h.
+// mipt_scene.h -- the device-resident scene behind the opaque MiptScene handle, shared by the translation units that build, change
+// and use it -- mipt_api.cpp (host checks, materials, replicas, renders), scene_device.hip (tree and layout built on the GPU),
+// bvh_build_device.hip (the builder), scene_update.hip (refit / rebuild), scene_mesh.hip (the resident mesh), mipt_query.cpp (ray
+// queries), mipt_multi.cpp (one replica per GPU) -- and by the test library's checksum hook (tests/cpp/scene_hooks.hip,
+// libmipt_diag.so).  Internal: HIP types, not part of include/mipt.h.
 #pragma once
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
@@ -24,12 +26,12 @@ struct MiptScene {
     MiptSceneInfo info{};
     // workspace
     mipt::DevStats *d_stats = nullptr;
-    uint32_t *d_ovf = nullptr;
-    size_t ovf_waves = 0;
+    uint32_t *d_ovf = nullptr;              // spill slots of the traversal stack, one set per wave of the largest grid launched so far:
+    size_t ovf_waves = 0;                   // sized and grown by mipt::traversal_grid (mipt_host_util.h) and by nothing else
     uint32_t *d_touched = nullptr;          // MIPT_FLAG_TOUCHED: line bitmap, allocated on first use
     size_t n_tris = 0;
     float *d_hdr = nullptr;
-    size_t hdr_floats = 0;
+    size_t hdr_bytes = 0;
     uint8_t *d_rgba = nullptr;
     size_t rgba_bytes = 0;
     float4 *d_cams = nullptr;               // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
@@ -87,6 +89,7 @@ struct ResidentBvh {
     double build_ms = 0.0;                // HIP events around the build kernels
 };
 int bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int device_id, ResidentBvh *out);
+// optional: what the first launch of each builder kernel would pay, up front (call with the device set)
 void bvh_builder_resolve_kernels();
 
 // The geometry half of a device-built scene (scene_device.hip): the tree and the layout kernels, from triangles already in HBM --
@@ -115,6 +118,5 @@ int upload_staged(void *d_dst, const void *h_src, size_t bytes);
 // scene that owns a mesh: its resident mesh and the triangles would disagree)
 int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info,
                         bool expanded_mesh = false);
-         // optional: what the first launch of each builder kernel would pay, up front (call with the device set)
 
 } // namespace mipt

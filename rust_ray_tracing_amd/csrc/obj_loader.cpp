@@ -112,8 +112,6 @@ std::string resource_path(const std::string &file_path, const std::string &res) 
 
 bool starts_with(const std::string &s, const char *p) { return s.compare(0, strlen(p), p) == 0; }
 
-int fail(const std::string &m) { mipt_internal_set_error(m.c_str()); return MIPT_ERR_IO; }
-
 // texture.rs:40-48: djb2 over every 4th pixel, pixel read as a native-endian u32
 uint32_t djb2(const std::vector<uint8_t> &rgba) {
     uint32_t hash = 5381;
@@ -210,7 +208,7 @@ void load_texture(const std::string &path, MiptObj *obj, uint32_t *slot) {
 
 int load_mtl(MiptObj *obj, const std::string &path) {               // obj.rs:131-265
     std::vector<std::string> lines;
-    if (!read_lines(path, &lines)) return fail("could not read .mtl file '" + path + "'");
+    if (!read_lines(path, &lines)) return mipt::fail(MIPT_ERR_IO, "could not read .mtl file '%s'", path.c_str());
     size_t li = 0;
     while (li < lines.size()) {
         const std::string &line = lines[li++];
@@ -244,7 +242,7 @@ int load_mtl(MiptObj *obj, const std::string &path) {               // obj.rs:13
             else if (p == "map_Pm" && tok.size() >= 2) load_texture(resource_path(path, tok[1]), obj, &m.metallic_tex_id);
             else if (p == "map_Ke" && tok.size() >= 2) load_texture(resource_path(path, tok[1]), obj, &m.emission_tex_id);
             else if (p == "map_Bump" && tok.size() >= 2) load_texture(resource_path(path, tok.back()), obj, &m.normal_tex_id);
-            if (!ok) return fail("malformed '" + p + "' line in '" + path + "': " + l2);
+            if (!ok) return mipt::fail(MIPT_ERR_IO, "malformed '%s' line in '%s': %s", p.c_str(), path.c_str(), l2.c_str());
         }
         bool replaced = false;                                       // HashMap::insert replaces an existing key
         for (size_t i = 0; i < obj->material_names.size(); i++)
@@ -504,18 +502,18 @@ template <class F> void run_parallel(size_t n_items, unsigned threads, F body) {
 extern "C" {
 
 static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
-    if (!path_c || !out) return fail("mipt_obj_load: null argument");
+    if (!path_c || !out) return mipt::fail(MIPT_ERR_IO, "mipt_obj_load: null argument");
     *out = nullptr;
     const std::string path = path_c;
     {   // Scene::load (scene.rs:22-36)
         std::ifstream probe(path);
-        if (!probe) return fail("Could not find scene at path: '" + path + "'");
+        if (!probe) return mipt::fail(MIPT_ERR_IO, "Could not find scene at path: '%s'", path.c_str());
         size_t dot = path.find_last_of('.');
         std::string fmt = dot == std::string::npos ? path : path.substr(dot + 1);
-        if (fmt != "obj") return fail("Unsupported scene format '" + fmt + "' at path '" + path + "'");
+        if (fmt != "obj") return mipt::fail(MIPT_ERR_IO, "Unsupported scene format '%s' at path '%s'", fmt.c_str(), path.c_str());
     }
     Mapped file;
-    if (!file.open(path)) return fail("could not read '" + path + "'");
+    if (!file.open(path)) return mipt::fail(MIPT_ERR_IO, "could not read '%s'", path.c_str());
     const char *const fb = file.data, *const fe = file.data + file.size;
     std::unique_ptr<MiptObj> obj(new MiptObj);
     bool has_mtl = false;
@@ -533,7 +531,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
             if (!le) le = fe;
             if (le > lb && le[-1] == '\r') le--;
             const std::string l(lb, le);
-            if (!starts_with(l, "mtllib ")) return fail("malformed mtllib line: " + l);
+            if (!starts_with(l, "mtllib ")) return mipt::fail(MIPT_ERR_IO, "malformed mtllib line: %s", l.c_str());
             int rc = load_mtl(obj.get(), resource_path(path, l.substr(7)));
             if (rc) return rc;
             has_mtl = true;
@@ -567,7 +565,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
     run_parallel(chunks.size(), threads, [&](size_t i) { parse_chunk(&chunks[i], has_mtl, obj->material_names); });
     for (const Chunk &c : chunks) {                                      // the first error in file order, as a line-by-line reader meets it
         for (const std::string &name : c.unknown) fprintf(stderr, "[mipt] material '%s' doesn't exist; keeping the active one\n", name.c_str());
-        if (c.failed) return fail(c.err);
+        if (c.failed) return mipt::fail(MIPT_ERR_IO, "%s", c.err.c_str());
     }
     // ---- concatenate in file order; resolve the active material across chunks (obj.rs:76-92) ----
     std::vector<size_t> o_pos(chunks.size() + 1, 0), o_nrm(chunks.size() + 1, 0), o_tex(chunks.size() + 1, 0), o_tri(chunks.size() + 1, 0);
@@ -581,7 +579,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
             for (int64_t &ev : chunks[i].events) { if (ev >= 0) active = (uint32_t)ev; ev = (int64_t)active; }   // event -> the material active after it
         }
     }
-    if (o_tri.back() > 0xffffffffull) return fail("'" + path + "' holds more than 2^32 triangles");
+    if (o_tri.back() > 0xffffffffull) return mipt::fail(MIPT_ERR_IO, "'%s' holds more than 2^32 triangles", path.c_str());
     std::vector<std::array<float, 3>> positions(o_pos.back()), normals(o_nrm.back());
     std::vector<std::array<float, 2>> tex_coords(o_tex.back());
     std::vector<ObjTri> otris(o_tri.back());
@@ -602,7 +600,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
     auto slice = [&](size_t i, size_t *b2, size_t *e2) { *b2 = otris.size() * i / n_slices; *e2 = otris.size() * (i + 1) / n_slices; };
     if (normals.empty()) {                                           // flat normals, obj.rs:106-120: triangle i gets normal i
         for (const ObjTri &t : otris)
-            for (int k = 0; k < 3; k++) if (t.pos[k] >= positions.size()) return fail("face references a missing vertex");
+            for (int k = 0; k < 3; k++) if (t.pos[k] >= positions.size()) return mipt::fail(MIPT_ERR_IO, "face references a missing vertex");
         normals.resize(otris.size());
         run_parallel(n_slices, threads, [&](size_t si) {
             size_t b2, e2;
@@ -619,7 +617,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
             }
         });
     }
-    if (otris.empty()) return fail("'" + path + "' contains no faces (the reference panics in BVH::build)");
+    if (otris.empty()) return mipt::fail(MIPT_ERR_IO, "'%s' contains no faces (the reference panics in BVH::build)", path.c_str());
     // impl From<OBJ> for Scene (scene.rs:44-85): missing indices read as zeros
     obj->tris.resize(otris.size());
     run_parallel(n_slices, threads, [&](size_t si) {
@@ -645,7 +643,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
         obj->nodes.resize(2 * obj->tris.size());
         uint32_t n_nodes = 0;
         int rc = mipt_bvh_build(obj->tris.data(), (uint32_t)obj->tris.size(), obj->nodes.data(), (uint32_t)obj->nodes.size(), &n_nodes, 0);
-        if (rc) return fail("BVH::build failed");
+        if (rc) return mipt::fail(MIPT_ERR_IO, "BVH::build failed");
         obj->nodes.resize(n_nodes);
     }
     for (const Tex &t : obj->textures) obj->tex_desc.push_back({t.w, t.h, t.rgba.data()});
@@ -655,7 +653,7 @@ static int obj_load_impl(const char *path_c, MiptObj **out, bool build_bvh) {
 }
 
 int mipt_obj_get(MiptObj *obj, MiptSceneDesc *desc, const char ***material_names) {
-    if (!obj || !desc) return fail("mipt_obj_get: null argument");
+    if (!obj || !desc) return mipt::fail(MIPT_ERR_IO, "mipt_obj_get: null argument");
     desc->tris = obj->tris.data(); desc->n_tris = (uint32_t)obj->tris.size();
     desc->nodes = obj->nodes.empty() ? nullptr : obj->nodes.data(); desc->n_nodes = (uint32_t)obj->nodes.size();   // empty: mipt_obj_load_triangles
     desc->materials = obj->materials.data(); desc->n_materials = (uint32_t)obj->materials.size();
@@ -669,14 +667,14 @@ void mipt_obj_free(MiptObj *obj) { delete obj; }
 struct MiptImage { Tex t; };
 
 static int texture_load_impl(const char *path, MiptImage **out, MiptTexture *desc_out, uint32_t *hash_out) {
-    if (!path || !out || !desc_out) return fail("mipt_texture_load: null argument");
+    if (!path || !out || !desc_out) return mipt::fail(MIPT_ERR_IO, "mipt_texture_load: null argument");
     *out = nullptr;
     FILE *f = fopen(path, "rb");
-    if (!f) return fail(std::string("Could not find texture at path: '") + path + "'");          // texture.rs:14-17
+    if (!f) return mipt::fail(MIPT_ERR_IO, "Could not find texture at path: '%s'", path);          // texture.rs:14-17
     fclose(f);
     MiptImage *img = new MiptImage();
     std::string err;
-    if (!load_any_texture(path, &img->t, &err)) { delete img; return fail(std::string("texture '") + path + "': " + err); }
+    if (!load_any_texture(path, &img->t, &err)) { delete img; return mipt::fail(MIPT_ERR_IO, "texture '%s': %s", path, err.c_str()); }
     desc_out->width = img->t.w; desc_out->height = img->t.h; desc_out->rgba8 = img->t.rgba.data();
     if (hash_out) *hash_out = img->t.hash;
     *out = img;
@@ -685,23 +683,18 @@ static int texture_load_impl(const char *path, MiptImage **out, MiptTexture *des
 void mipt_texture_free(MiptImage *img) { delete img; }
 
 static int image_save_png_impl(const char *path, uint32_t width, uint32_t height, uint32_t bits_per_sample, const void *rgba) {
-    if (!path || !rgba) return fail("mipt_image_save_png: null argument");
+    if (!path || !rgba) return mipt::fail(MIPT_ERR_IO, "mipt_image_save_png: null argument");
     std::string err;
-    if (!mipt_png::write_rgba(path, width, height, (int)bits_per_sample, rgba, &err)) return fail("Failed to write image data: " + err);   // renderer.rs:79-82
+    if (!mipt_png::write_rgba(path, width, height, (int)bits_per_sample, rgba, &err)) return mipt::fail(MIPT_ERR_IO, "Failed to write image data: %s", err.c_str());   // renderer.rs:79-82
     return MIPT_OK;
 }
 
-
-// No C++ exception may cross the C ABI: allocation failures and parser surprises become status codes.
-#define MIPT_NO_THROW(call)                                                                \
-    try { return call; }                                                                  \
-    catch (const std::bad_alloc &) { return fail("out of host memory"); }                 \
-    catch (const std::exception &e) { return fail(std::string("internal error: ") + e.what()); }
-int mipt_obj_load(const char *path, MiptObj **out) { MIPT_NO_THROW(obj_load_impl(path, out, true)) }
-int mipt_obj_load_triangles(const char *path, MiptObj **out) { MIPT_NO_THROW(obj_load_impl(path, out, false)) }
-int mipt_texture_load(const char *path, MiptImage **out, MiptTexture *desc_out, uint32_t *hash_out) { MIPT_NO_THROW(texture_load_impl(path, out, desc_out, hash_out)) }
+// No C++ exception may cross the C ABI: allocation failures and parser surprises become MIPT_ERR_IO.
+int mipt_obj_load(const char *path, MiptObj **out) { MIPT_NO_THROW_AS(MIPT_ERR_IO, obj_load_impl(path, out, true)) }
+int mipt_obj_load_triangles(const char *path, MiptObj **out) { MIPT_NO_THROW_AS(MIPT_ERR_IO, obj_load_impl(path, out, false)) }
+int mipt_texture_load(const char *path, MiptImage **out, MiptTexture *desc_out, uint32_t *hash_out) { MIPT_NO_THROW_AS(MIPT_ERR_IO, texture_load_impl(path, out, desc_out, hash_out)) }
 int mipt_image_save_png(const char *path, uint32_t width, uint32_t height, uint32_t bits_per_sample, const void *rgba) {
-    MIPT_NO_THROW(image_save_png_impl(path, width, height, bits_per_sample, rgba))
+    MIPT_NO_THROW_AS(MIPT_ERR_IO, image_save_png_impl(path, width, height, bits_per_sample, rgba))
 }
 
 } // extern "C"

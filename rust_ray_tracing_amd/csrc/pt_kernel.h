@@ -39,7 +39,7 @@ struct DevScene {
     const float4 *pairs;          // = geom: [pairs | tri_pos] live in ONE allocation so the traversal step can address either
     const float4 *tri_pos;        //   through one buffer descriptor with a 32-bit byte offset (tri_off_bytes = n_pairs * 64)
     uint32_t tri_off_bytes, geom_bytes;
-    uint32_t tiny_axes;           // bit c: some bounding plane has a coordinate 0 < |p_c| < 2^-76 on axis c (see ray_safe, pt_kernel.hip)
+    uint32_t tiny_axes;           // bit c: some bounding plane has a coordinate 0 < |p_c| < 2^-76 on axis c (see ray_safe, pt_traverse.h)
     const float4 *tri_attr;
     const DevMaterial *mats;
     const DevMaterialFull *mats_full;   // shading mode 1 (rt_compute.wgsl material model)

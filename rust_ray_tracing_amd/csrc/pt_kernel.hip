@@ -27,8 +27,6 @@ namespace {
 #define MIPT_DIAG_STAMPS 0
 #endif
 constexpr bool DIAG_STAMPS = MIPT_DIAG_STAMPS != 0;   // counting build only: in-iteration s_memtime stamps
-constexpr uint32_t kNoTri = 0xffffffffu;
-constexpr uint32_t kFrontBit = 0x80000000u;
 
 enum : uint32_t {
     ST_T = 0,   // traversing
@@ -594,7 +592,7 @@ __global__ void unpack_tiles_kernel(const float *__restrict__ packed_all, uint32
     }
 }
 
-// ---- cpu.rs:60 on a reduced sum buffer: final_color /= samples (sample-sharded renders divide once, after the reduce) ----
+// ---- MIPT_FLAG_TOUCHED: the set bits of the line bitmap, added to *out ----
 __global__ void popcount_kernel(const uint32_t *__restrict__ bitmap, unsigned long long n_words, unsigned long long *out) {
     unsigned long long c = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_words;
@@ -608,6 +606,7 @@ hipError_t launch_popcount(const uint32_t *bitmap, unsigned long long n_words, u
     return hipGetLastError();
 }
 
+// ---- cpu.rs:60 on a reduced sum buffer: final_color /= samples (sample-sharded renders divide once, after the reduce) ----
 __global__ void divide_kernel(float *__restrict__ hdr, unsigned long long n_floats, float divisor) {
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_floats;
          i += (unsigned long long)gridDim.x * blockDim.x)

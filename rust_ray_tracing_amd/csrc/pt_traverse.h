@@ -10,6 +10,8 @@ namespace mipt {
 namespace {
 
 constexpr float kMiss = 1e30f;                     // ray.rs:79,217
+constexpr uint32_t kNoTri = 0xffffffffu;           // best_tri of a miss; MIPT_HIT_NONE
+constexpr uint32_t kFrontBit = 0x80000000u;        // bit 31 of best_tri: the hit is on the front face; MIPT_HIT_FRONT_FACE
 
 // stack entry: inner -> pair index (bit31 = 0);
 // leaf -> bit31 | n << 25 | first_tri  (1 <= n <= 63);

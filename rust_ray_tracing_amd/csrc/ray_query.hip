@@ -16,9 +16,6 @@ namespace mipt {
 
 namespace {
 
-constexpr uint32_t kNoTri = 0xffffffffu;             // MIPT_HIT_NONE
-constexpr uint32_t kFrontBit = 0x80000000u;          // MIPT_HIT_FRONT_FACE
-
 // refill when idle lanes / live lanes >= kRefillNum / kRefillDen: the refill pass is two 16-B loads, three divisions and one store
 // per lane, far lighter than the trace kernel's service pass (3/8 there)
 constexpr uint32_t kRefillNum = 1, kRefillDen = 4;

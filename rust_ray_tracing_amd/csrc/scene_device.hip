@@ -21,6 +21,7 @@
 #include "mipt_internal.h"
 #include "mipt_scene.h"
 #include "copy_crew.h"
+#include "mipt_host_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -29,9 +30,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <exception>
 #include <new>
-#include <string>
 #include <thread>
 #include <vector>
 
@@ -41,10 +40,7 @@ constexpr int kT = 256;
 constexpr int kScanGrid = 512;                  // workgroups of a scan pass (fixed: the element count lives on the device)
 constexpr uint32_t kPad = 0xffffffffu;
 
-int fail(int code, const std::string &msg) {
-    mipt_internal_set_error(msg.c_str());
-    return code;
-}
+using mipt::fail;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- device-side state of the layout pass ------------------------------------------------------------------------------------
@@ -327,12 +323,12 @@ class StagedUploader {
             e = hipMemcpyAsync((char *)d_dst + off, pin_[slot], len, hipMemcpyHostToDevice, stream_);
             if (e == hipSuccess) e = hipEventRecord(ev_[slot], stream_);
         }
-        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, std::string("staged upload: ") + hipGetErrorString(e));
+        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, "staged upload: %s", hipGetErrorString(e));
     }
     int finish() {                                             // everything queued so far has arrived
         if (!ready_) return MIPT_OK;
         const hipError_t e = hipStreamSynchronize(stream_);
-        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, std::string("staged upload: ") + hipGetErrorString(e));
+        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, "staged upload: %s", hipGetErrorString(e));
     }
     void pause() { crew_.stop(); }                            // the ring stays; the helpers stop spinning until the next copy
     void shut() {
@@ -346,7 +342,7 @@ class StagedUploader {
   private:
     int direct(void *d_dst, const void *h_src, size_t bytes) {
         const hipError_t e = hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice);
-        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+        return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, "upload: %s", hipGetErrorString(e));
     }
     int init() {                                               // 0 ok, 1 = no pinned memory / stream: fall back to hipMemcpy, < 0 error
         hipError_t e = hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
@@ -366,12 +362,6 @@ class StagedUploader {
     size_t seq_ = 0;
     bool ready_ = false;
 };
-
-#define S_HIP(expr)                                                                                                    \
-    do {                                                                                                               \
-        hipError_t e__ = (expr);                                                                                       \
-        if (e__ != hipSuccess) { cleanup(); return fail(MIPT_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e__)); } \
-    } while (0)
 
 } // namespace
 
@@ -393,7 +383,7 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
     const uint32_t n_nodes = bvh.n_nodes;
     if ((n_nodes & 1u) == 0u) { cleanup(); return fail(MIPT_ERR_BVH, "device builder returned an even node count"); }
     const uint32_t n_pairs = (n_nodes - 1u) / 2u;
-    if (n_pairs > mipt::kMaxPairs) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(n_pairs) + " node pairs exceed the 2^24 device-format limit"); }
+    if (n_pairs > mipt::kMaxPairs) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "%u node pairs exceed the 2^24 device-format limit", n_pairs); }
 
     // ---- 3. layout kernels.  One arena for the temporaries ----
     const size_t np = n_pairs ? n_pairs : 1, order_cap = 2 * (size_t)n_pairs + 4;
@@ -401,7 +391,7 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
     const size_t o_ctl = 0, o_sums = up(sizeof(Ctl)), o_slot = o_sums + up(sizeof(U4) * kScanGrid), o_placed = o_slot + up((size_t)n_tris * 4),
                  o_lvl0 = o_placed + up(n_tris), o_lvl1 = o_lvl0 + up(np * 4), o_lone = o_lvl1 + up(np * 4), o_taken = o_lone + up(np * 4),
                  o_order = o_taken + up(np), o_newof = o_order + up(order_cap * 4), arena_bytes = o_newof + up(np * 4);
-    S_HIP(hipMalloc((void **)&arena, arena_bytes));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&arena, arena_bytes));
     Ctl *ctl = (Ctl *)(arena + o_ctl);
     U4 *sums = (U4 *)(arena + o_sums);
     uint32_t *slot = (uint32_t *)(arena + o_slot), *lvl[2] = {(uint32_t *)(arena + o_lvl0), (uint32_t *)(arena + o_lvl1)},
@@ -413,11 +403,11 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
         memset(&h, 0, sizeof h);
         h.lv[0].cnt = n_pairs ? 1u : 0u;                           // level 0 = { pair 0 } (the root's children)
         h.bad_tri = 0xffffffffu;
-        S_HIP(hipMemcpy(ctl, &h, sizeof h, hipMemcpyHostToDevice));
-        S_HIP(hipMemsetAsync(placed, 0, n_tris, st));
-        S_HIP(hipMemsetAsync(taken, 0, np, st));
-        S_HIP(hipMemsetAsync(order, 0xff, order_cap * 4, st));     // every entry a pad until a pair is written there
-        S_HIP(hipMemsetAsync(lvl[0], 0, 4, st));
+        MIPT_HIP_OR(cleanup(), hipMemcpy(ctl, &h, sizeof h, hipMemcpyHostToDevice));
+        MIPT_HIP_OR(cleanup(), hipMemsetAsync(placed, 0, n_tris, st));
+        MIPT_HIP_OR(cleanup(), hipMemsetAsync(taken, 0, np, st));
+        MIPT_HIP_OR(cleanup(), hipMemsetAsync(order, 0xff, order_cap * 4, st));     // every entry a pad until a pair is written there
+        MIPT_HIP_OR(cleanup(), hipMemsetAsync(lvl[0], 0, 4, st));
     }
     hipLaunchKernelGGL(check_nodes, dim3(1024), dim3(kT), 0, st, bvh.d_nodes, n_nodes, ctl);
     if (n_pairs) run_scan(DoublesOp{bvh.d_nodes, n_pairs, slot, placed, ctl}, sums, st);
@@ -431,15 +421,15 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
         for (;;) {
             for (int b = 0; b < 16; b++, depth++)
                 run_scan(LevelOp{bvh.d_nodes, lvl[depth & 1u], lvl[(depth & 1u) ^ 1u], taken, order, lone, ctl, depth & 1u, depth >= top ? 1u : 0u}, sums, st);
-            S_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-            S_HIP(hipStreamSynchronize(st));
+            MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+            MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
             if (hctl.lv[depth & 1u].cnt == 0u) break;
             if (depth > 8192u) { cleanup(); return fail(MIPT_ERR_BVH, "BVH deeper than 8192 levels"); }
         }
         hipLaunchKernelGGL(append_lone, dim3(1024), dim3(kT), 0, st, lone, order, ctl, depth & 1u);
     } else {
-        S_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-        S_HIP(hipStreamSynchronize(st));
+        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     }
     if (hctl.bad_bound) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40"); }
     const LevelState fin = hctl.lv[depth & 1u];
@@ -453,24 +443,24 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
     out.n_tris = n_tris;
     out.geom_alloc = pairs_bytes + pos_bytes + 64;
     out.attr_bytes = (size_t)n_tris * 64;
-    S_HIP(hipMalloc(&out.d_geom, out.geom_alloc));
-    S_HIP(hipMalloc(&out.d_tri_attr, out.attr_bytes));
+    MIPT_HIP_OR(cleanup(), hipMalloc(&out.d_geom, out.geom_alloc));
+    MIPT_HIP_OR(cleanup(), hipMalloc(&out.d_tri_attr, out.attr_bytes));
     float4 *d_pairs = (float4 *)out.d_geom, *d_pos = (float4 *)((char *)out.d_geom + pairs_bytes);
     if (n_records) hipLaunchKernelGGL(write_new_of, dim3(2048), dim3(kT), 0, st, order, n_records, new_of);
     if (n_records_padded) hipLaunchKernelGGL(write_pairs, dim3(2048), dim3(kT), 0, st, bvh.d_nodes, order, n_records, n_records_padded, new_of, slot, d_pairs);
     hipLaunchKernelGGL(write_tris, dim3(4096), dim3(kT), 0, st, d_tris, bvh.d_tri_order, n_tris, n_materials, slot, d_pos, (float4 *)out.d_tri_attr, ctl);
-    S_HIP(hipGetLastError());
+    MIPT_HIP_OR(cleanup(), hipGetLastError());
     MiptNode root;
     uint32_t root_slot = 0;
-    S_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-    S_HIP(hipMemcpyAsync(&root, bvh.d_nodes, sizeof root, hipMemcpyDeviceToHost, st));
-    S_HIP(hipStreamSynchronize(st));
+    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&root, bvh.d_nodes, sizeof root, hipMemcpyDeviceToHost, st));
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     if (hctl.bad_tri != 0xffffffffu) {
         cleanup();
-        return fail(MIPT_ERR_INVALID_ARG, host_nodes ? "triangle " + std::to_string(hctl.bad_tri) + " has material_id >= n_materials " + std::to_string(n_materials)
-                                                     : "a triangle has material_id >= n_materials " + std::to_string(n_materials) + " (position " + std::to_string(hctl.bad_tri) + " of the BVH order)");
+        return host_nodes ? fail(MIPT_ERR_INVALID_ARG, "triangle %u has material_id >= n_materials %u", hctl.bad_tri, n_materials)
+                          : fail(MIPT_ERR_INVALID_ARG, "a triangle has material_id >= n_materials %u (position %u of the BVH order)", n_materials, hctl.bad_tri);
     }
-    if (root.num_tris > 0u) S_HIP(hipMemcpy(&root_slot, slot + root.first_tri_or_child, 4, hipMemcpyDeviceToHost));
+    if (root.num_tris > 0u) MIPT_HIP_OR(cleanup(), hipMemcpy(&root_slot, slot + root.first_tri_or_child, 4, hipMemcpyDeviceToHost));
     else if (root.first_tri_or_child != 1u) { cleanup(); return fail(MIPT_ERR_BVH, "root's children must be nodes 1 and 2 (bvh.rs:121)"); }
     (void)hipFree(arena); arena = nullptr;
 
@@ -531,7 +521,7 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     if (!d_resident && (!desc->tris || desc->n_tris == 0)) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
     const uint32_t n_tris = d_resident ? n_resident : desc->n_tris;
     if (n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "scene has no triangles (the reference panics in BVH::build)");
-    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(n_tris) + " triangles exceed the 2^25 device-format limit");
+    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, "%u triangles exceed the 2^25 device-format limit", n_tris);
     if (host_nodes && (!desc->nodes || (desc->n_nodes & 1u) == 0u)) return fail(MIPT_ERR_BVH, "scene has no BVH nodes, or an even number of them");
     const double t_begin = now_ms();
     mipt::MaterialTables tables;
@@ -540,8 +530,8 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     int ndev = 0;
     {
         const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("hipGetDeviceCount failed: ") + hipGetErrorString(e));
-        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device " + std::to_string(device_id) + " not available (" + std::to_string(ndev) + " visible)");
+        if (e != hipSuccess) return fail(MIPT_ERR_HIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
+        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device %d not available (%d visible)", device_id, ndev);
     }
     MiptTriangle *d_tris = nullptr;
     mipt::ResidentBvh bvh;
@@ -556,10 +546,10 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
         mipt::free_geometry(&geo);
         if (s) mipt::free_scene(s);
     };
-    S_HIP(hipSetDevice(device_id));
+    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
     // ---- 1. the one host -> device copy ----
-    if (!d_resident) S_HIP(hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
-    if (host_nodes) S_HIP(hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
+    if (!d_resident) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
+    if (host_nodes) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
     {
         std::thread warm;
         if (!host_nodes) warm = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
@@ -621,7 +611,5 @@ int mipt::scene_create_from_resident_triangles(const MiptSceneDesc *desc, const 
 }
 
 extern "C" int mipt_scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptScene **out) {
-    try { return mipt::scene_create_from_triangles(desc, device_id, out); }
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(mipt::scene_create_from_triangles(desc, device_id, out))
 }

@@ -20,15 +20,14 @@
 #include "../../include/mipt.h"
 #include "mipt_internal.h"
 #include "mipt_scene.h"
+#include "mipt_host_util.h"
 
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <exception>
 #include <new>
-#include <string>
 
 static_assert(sizeof(MiptMeshPart) == 16 && sizeof(MiptMeshInfo) == 56 && sizeof(MiptMeshDesc) == 104, "mesh ABI structs (rust_ray_tracing_amd/_lib.py)");
 static_assert(sizeof(MiptTriangle) == 112, "Triangle");
@@ -65,17 +64,8 @@ using mipt::SceneMesh;
 constexpr int kT = 256;                                   // lanes = triangles of a workgroup of mesh_expand
 constexpr uint32_t kNoIndex = 0xffffffffu;
 
-int fail(int code, const std::string &msg) {
-    mipt_internal_set_error(msg.c_str());
-    return code;
-}
+using mipt::fail;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-#define M_HIP(expr)                                                                                        \
-    do {                                                                                                   \
-        const hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess) { cleanup(); return fail(MIPT_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e__)); } \
-    } while (0)
 
 // ---- the expansion rule: one function for the host and the device -------------------------------------------------------------
 __host__ __device__ inline void cross3(const float *a, const float *b, float *o) {      // vec3.rs:137-143
@@ -174,41 +164,36 @@ __global__ __launch_bounds__(kT) void mesh_expand(MeshView m, const PartRec *par
 // ---- host-visible checks (before any device call) -------------------------------------------------------------------------------
 // n_materials < 0: not checked (mipt_mesh_expand has no material table)
 int check_mesh(const char *who, const MiptMeshDesc *m, int64_t n_materials) {
-    const std::string w = std::string(who) + ": ";
-    if (!m->positions || !m->indices || !m->parts) return fail(MIPT_ERR_INVALID_ARG, w + "null positions, indices or parts");
-    if (m->n_indices % 3u) return fail(MIPT_ERR_INVALID_ARG, w + "n_indices " + std::to_string(m->n_indices) + " is not a multiple of 3");
+    if (!m->positions || !m->indices || !m->parts) return fail(MIPT_ERR_INVALID_ARG, "%s: null positions, indices or parts", who);
+    if (m->n_indices % 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: n_indices %u is not a multiple of 3", who, m->n_indices);
     const uint32_t n_tris = m->n_indices / 3u;
-    if (n_tris == 0u) return fail(MIPT_ERR_INVALID_ARG, w + "no triangles (the reference panics in BVH::build)");
-    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(n_tris) + " triangles exceed the 2^25 device-format limit");
+    if (n_tris == 0u) return fail(MIPT_ERR_INVALID_ARG, "%s: no triangles (the reference panics in BVH::build)", who);
+    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, "%u triangles exceed the 2^25 device-format limit", n_tris);
     uint64_t next = 0;
     for (uint32_t p = 0; p < m->n_parts; p++) {
         const MiptMeshPart &q = m->parts[p];
-        if (q.reserved != 0u) return fail(MIPT_ERR_INVALID_ARG, w + "part " + std::to_string(p) + ": reserved must be 0");
+        if (q.reserved != 0u) return fail(MIPT_ERR_INVALID_ARG, "%s: part %u: reserved must be 0", who, p);
         if (q.first_tri != next)
-            return fail(MIPT_ERR_INVALID_ARG, w + "parts must tile the triangles in order: part " + std::to_string(p) + " starts at " + std::to_string(q.first_tri) +
-                                                  ", expected " + std::to_string(next));
+            return fail(MIPT_ERR_INVALID_ARG, "%s: parts must tile the triangles in order: part %u starts at %u, expected %llu", who, p, q.first_tri, (unsigned long long)next);
         next += q.n_tris;
         if (next > n_tris)
-            return fail(MIPT_ERR_INVALID_ARG, w + "parts must tile the triangles in order: part " + std::to_string(p) + " ends at " + std::to_string(next) + " of " +
-                                                  std::to_string(n_tris) + " triangles");
+            return fail(MIPT_ERR_INVALID_ARG, "%s: parts must tile the triangles in order: part %u ends at %llu of %u triangles", who, p, (unsigned long long)next, n_tris);
         if (n_materials >= 0 && (int64_t)q.material_id >= n_materials)
-            return fail(MIPT_ERR_INVALID_ARG, w + "part " + std::to_string(p) + " has material_id " + std::to_string(q.material_id) + " >= n_materials " + std::to_string(n_materials));
+            return fail(MIPT_ERR_INVALID_ARG, "%s: part %u has material_id %u >= n_materials %lld", who, p, q.material_id, (long long)n_materials);
     }
     if (next != n_tris)
-        return fail(MIPT_ERR_INVALID_ARG, w + "parts must tile the triangles in order: " + std::to_string(m->n_parts) + " parts cover " + std::to_string(next) + " of " +
-                                              std::to_string(n_tris) + " triangles");
+        return fail(MIPT_ERR_INVALID_ARG, "%s: parts must tile the triangles in order: %u parts cover %llu of %u triangles", who, m->n_parts, (unsigned long long)next, n_tris);
     return MIPT_OK;
 }
 
 int check_mode(const char *who, uint32_t mode) {
     if (mode != MIPT_UPDATE_REFIT && mode != MIPT_UPDATE_REBUILD)
-        return fail(MIPT_ERR_INVALID_ARG, std::string(who) + ": mode " + std::to_string(mode) + " is neither MIPT_UPDATE_REFIT nor MIPT_UPDATE_REBUILD");
+        return fail(MIPT_ERR_INVALID_ARG, "%s: mode %u is neither MIPT_UPDATE_REFIT nor MIPT_UPDATE_REBUILD", who, mode);
     return MIPT_OK;
 }
 
 int bad_position_index(uint32_t entry, uint32_t value, uint32_t n_pos) {
-    return fail(MIPT_ERR_INVALID_ARG, "position index " + std::to_string(value) + " at index entry " + std::to_string(entry) + " (triangle " + std::to_string(entry / 3u) +
-                                          ", corner " + std::to_string(entry % 3u) + ") is out of range: " + std::to_string(n_pos) + " positions");
+    return fail(MIPT_ERR_INVALID_ARG, "position index %u at index entry %u (triangle %u, corner %u) is out of range: %u positions", value, entry, entry / 3u, entry % 3u, n_pos);
 }
 
 int mesh_expand_host(const MiptMeshDesc *m, MiptTriangle *out, uint32_t cap, uint32_t *n_out) {
@@ -216,7 +201,7 @@ int mesh_expand_host(const MiptMeshDesc *m, MiptTriangle *out, uint32_t cap, uin
     { const int rc = check_mesh("mipt_mesh_expand", m, -1); if (rc) return rc; }
     const uint32_t n_tris = m->n_indices / 3u;
     if (n_out) *n_out = n_tris;
-    if (!out || cap < n_tris) return fail(MIPT_ERR_INVALID_ARG, "mipt_mesh_expand: room for " + std::to_string(out ? cap : 0u) + " triangles, the mesh has " + std::to_string(n_tris));
+    if (!out || cap < n_tris) return fail(MIPT_ERR_INVALID_ARG, "mipt_mesh_expand: room for %u triangles, the mesh has %u", out ? cap : 0u, n_tris);
     const MeshView v{m->positions, m->normals, m->tex_coords, m->indices, m->normal_indices ? m->normal_indices : m->indices,
                      m->tex_coord_indices ? m->tex_coord_indices : m->indices, m->n_positions, m->normals ? m->n_normals : 0u,
                      m->tex_coords ? m->n_tex_coords : 0u, n_tris};
@@ -279,8 +264,8 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
     int ndev = 0;
     {
         const hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("hipGetDeviceCount failed: ") + hipGetErrorString(e));
-        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device " + std::to_string(device_id) + " not available (" + std::to_string(ndev) + " visible)");
+        if (e != hipSuccess) return fail(MIPT_ERR_HIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
+        if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device %d not available (%d visible)", device_id, ndev);
     }
     SceneMesh *m = new (std::nothrow) SceneMesh();
     if (!m) return fail(MIPT_ERR_INVALID_ARG, "out of host memory");
@@ -290,7 +275,7 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
         if (s) { s->mesh = nullptr; mipt::free_scene(s); s = nullptr; }
         free_mesh_buffers(m); m = nullptr;
     };
-    M_HIP(hipSetDevice(device_id));
+    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
     m->n_pos = mesh->n_positions;
     m->n_nrm = mesh->normals ? mesh->n_normals : 0u;
     m->n_tex = mesh->tex_coords ? mesh->n_tex_coords : 0u;
@@ -309,31 +294,31 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
     for (const Up &u : ups) {
         const bool stage = u.dst == (void **)&m->d_xf_stage;              // allocated even without transforms: mipt_scene_set_transforms fills it
         if (!u.bytes || (!u.src && !stage)) continue;
-        M_HIP(hipMalloc(u.dst, u.bytes));
+        MIPT_HIP_OR(cleanup(), hipMalloc(u.dst, u.bytes));
         m->array_bytes += u.bytes;
         if (u.src) { const int rc = mipt::upload_staged(*u.dst, u.src, u.bytes); if (rc) { cleanup(); return rc; } }
     }
     m->streams = 1u + (m->d_idx[1] ? 1u : 0u) + (m->d_idx[2] ? 1u : 0u);
     if (!m->d_idx[1]) m->d_idx[1] = m->d_idx[0];
     if (!m->d_idx[2]) m->d_idx[2] = m->d_idx[0];
-    M_HIP(hipMalloc((void **)&m->d_rec[0], rec_b));
-    M_HIP(hipMalloc((void **)&m->d_rec[1], rec_b));
-    M_HIP(hipMalloc((void **)&m->d_flag, 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_rec[0], rec_b));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_rec[1], rec_b));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_flag, 4));
     m->array_bytes += 2 * rec_b + 4;
-    M_HIP(hipMalloc((void **)&m->d_expanded, exp_b));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_expanded, exp_b));
     const double t_up = now_ms();
     // ---- expansion; a position index out of range ends the call here ----
-    M_HIP(hipMemset(m->d_flag, 0xff, 4));
+    MIPT_HIP_OR(cleanup(), hipMemset(m->d_flag, 0xff, 4));
     float expand_ms = 0.0f;
     {
         ExpandTimer tm;
-        M_HIP(queue_expand(m, nullptr, nullptr, mesh->transforms ? m->d_xf_stage : nullptr, true, 0, nullptr, &tm));
+        MIPT_HIP_OR(cleanup(), queue_expand(m, nullptr, nullptr, mesh->transforms ? m->d_xf_stage : nullptr, true, 0, nullptr, &tm));
         uint32_t bad = kNoIndex;
-        M_HIP(hipMemcpy(&bad, m->d_flag, 4, hipMemcpyDeviceToHost));      // null stream: after the kernels
+        MIPT_HIP_OR(cleanup(), hipMemcpy(&bad, m->d_flag, 4, hipMemcpyDeviceToHost));      // null stream: after the kernels
         (void)hipEventElapsedTime(&expand_ms, tm.e0, tm.e1);
         if (bad != kNoIndex) {
             uint32_t value = 0;
-            M_HIP(hipMemcpy(&value, m->d_idx[0] + bad, 4, hipMemcpyDeviceToHost));
+            MIPT_HIP_OR(cleanup(), hipMemcpy(&value, m->d_idx[0] + bad, 4, hipMemcpyDeviceToHost));
             cleanup();
             return bad_position_index(bad, value, mesh->n_positions);
         }
@@ -353,20 +338,20 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
 int apply(MiptScene *s, const float *d_pos, const float *d_nrm, const float *d_xf, int xf_change, uint32_t mode, hipStream_t st, MiptUpdateInfo *inf) {
     SceneMesh *m = s->mesh;
     auto cleanup = [&]() { (void)hipStreamSynchronize(st); };
-    M_HIP(hipStreamSynchronize(st));                                      // ordered after the caller's earlier work on `st`
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));                                      // ordered after the caller's earlier work on `st`
     const int rec = xf_change ? m->cur ^ 1 : m->cur;
     float expand_ms = 0.0f;
     {
         ExpandTimer tm;
-        M_HIP(queue_expand(m, d_pos, d_nrm, xf_change == 1 ? d_xf : nullptr, xf_change != 0, rec, st, &tm));
-        M_HIP(hipStreamSynchronize(st));
+        MIPT_HIP_OR(cleanup(), queue_expand(m, d_pos, d_nrm, xf_change == 1 ? d_xf : nullptr, xf_change != 0, rec, st, &tm));
+        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
         (void)hipEventElapsedTime(&expand_ms, tm.e0, tm.e1);
     }
     { const int rc = mipt::scene_update_device(s, m->d_expanded, m->n_tris, mode, st, inf, true); if (rc) return rc; }
     // ---- commit ----
-    if (d_pos) M_HIP(hipMemcpyAsync(m->d_pos, d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
-    if (d_nrm) M_HIP(hipMemcpyAsync(m->d_nrm, d_nrm, (size_t)m->n_nrm * 12, hipMemcpyDeviceToDevice, st));
-    M_HIP(hipStreamSynchronize(st));
+    if (d_pos) MIPT_HIP_OR(cleanup(), hipMemcpyAsync(m->d_pos, d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
+    if (d_nrm) MIPT_HIP_OR(cleanup(), hipMemcpyAsync(m->d_nrm, d_nrm, (size_t)m->n_nrm * 12, hipMemcpyDeviceToDevice, st));
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     m->cur = rec;
     if (xf_change) m->has_xf = xf_change == 1 ? 1u : 0u;
     inf->build_ms += expand_ms;
@@ -380,10 +365,9 @@ int set_transforms(MiptScene *s, const float *xf, uint32_t n_parts, uint32_t mod
     if (!s->mesh) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_set_transforms: the scene has no mesh (it was not made by mipt_scene_create_from_mesh)");
     SceneMesh *m = s->mesh;
     if (n_parts != m->n_parts)
-        return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_set_transforms: " + std::to_string(n_parts) + " transforms given, the mesh has " + std::to_string(m->n_parts) + " parts");
-    auto cleanup = []() {};
-    M_HIP(hipSetDevice(s->device));
-    if (xf) M_HIP(hipMemcpy(m->d_xf_stage, xf, (size_t)n_parts * 64, hipMemcpyHostToDevice));
+        return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_set_transforms: %u transforms given, the mesh has %u parts", n_parts, m->n_parts);
+    MIPT_HIP(hipSetDevice(s->device));
+    if (xf) MIPT_HIP(hipMemcpy(m->d_xf_stage, xf, (size_t)n_parts * 64, hipMemcpyHostToDevice));
     const double t_up = now_ms();
     MiptUpdateInfo inf{};
     { const int rc = apply(s, nullptr, nullptr, m->d_xf_stage, xf ? 1 : 2, mode, nullptr, &inf); if (rc) return rc; }
@@ -399,8 +383,7 @@ int update_mesh_device(MiptScene *s, const float *d_pos, const float *d_nrm, con
     { const int rc = check_mode("mipt_scene_update_mesh_device", mode); if (rc) return rc; }
     if (!s->mesh) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_update_mesh_device: the scene has no mesh (it was not made by mipt_scene_create_from_mesh)");
     if (d_nrm && s->mesh->n_nrm == 0u) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_update_mesh_device: the mesh has no normals to replace");
-    auto cleanup = []() {};
-    M_HIP(hipSetDevice(s->device));
+    MIPT_HIP(hipSetDevice(s->device));
     MiptUpdateInfo inf{};
     { const int rc = apply(s, d_pos, d_nrm, d_xf, d_xf ? 1 : 0, mode, st, &inf); if (rc) return rc; }
     inf.upload_ms = 0.0;
@@ -431,28 +414,23 @@ void mipt::free_mesh(MiptScene *s) {
     s->mesh = nullptr;
 }
 
-#define MESH_FENCE(call)                                                                                             \
-    try { return call; }                                                                                             \
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }                      \
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
-
 extern "C" {
 
-int mipt_mesh_expand(const MiptMeshDesc *mesh, MiptTriangle *out, uint32_t cap, uint32_t *n_out) { MESH_FENCE(mesh_expand_host(mesh, out, cap, n_out)) }
+int mipt_mesh_expand(const MiptMeshDesc *mesh, MiptTriangle *out, uint32_t cap, uint32_t *n_out) { MIPT_NO_THROW(mesh_expand_host(mesh, out, cap, n_out)) }
 
 int mipt_scene_create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int device_id, MiptScene **out) {
-    MESH_FENCE(create_from_mesh(desc, mesh, device_id, out))
+    MIPT_NO_THROW(create_from_mesh(desc, mesh, device_id, out))
 }
 
 int mipt_scene_set_transforms(MiptScene *scene, const float *transforms, uint32_t n_parts, uint32_t mode, MiptUpdateInfo *info) {
-    MESH_FENCE(set_transforms(scene, transforms, n_parts, mode, info))
+    MIPT_NO_THROW(set_transforms(scene, transforms, n_parts, mode, info))
 }
 
 int mipt_scene_update_mesh_device(MiptScene *scene, const float *d_positions, const float *d_normals, const float *d_transforms, uint32_t mode,
                                   void *hip_stream, MiptUpdateInfo *info) {
-    MESH_FENCE(update_mesh_device(scene, d_positions, d_normals, d_transforms, mode, (hipStream_t)hip_stream, info))
+    MIPT_NO_THROW(update_mesh_device(scene, d_positions, d_normals, d_transforms, mode, (hipStream_t)hip_stream, info))
 }
 
-int mipt_scene_mesh_info(const MiptScene *scene, MiptMeshInfo *out) { MESH_FENCE(mesh_info(scene, out)) }
+int mipt_scene_mesh_info(const MiptScene *scene, MiptMeshInfo *out) { MIPT_NO_THROW(mesh_info(scene, out)) }
 
 } // extern "C"

@@ -15,15 +15,13 @@
 #include "../../include/mipt.h"
 #include "mipt_internal.h"
 #include "mipt_scene.h"
+#include "mipt_host_util.h"
 
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cmath>
 #include <cstring>
-#include <exception>
-#include <new>
-#include <string>
 #include <vector>
 
 namespace {
@@ -32,10 +30,7 @@ constexpr int kT = 256;
 constexpr uint32_t kSerialLeaf = 16;            // a leaf child with more triangles goes to the workgroup-per-leaf pass
 constexpr uint32_t kMaxLevels = 8192 + 64;      // mipt_scene_create refuses trees deeper than 8192 (+ one batch) levels
 
-int fail(int code, const std::string &msg) {
-    mipt_internal_set_error(msg.c_str());
-    return code;
-}
+using mipt::fail;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Box { float lo[3], hi[3]; };
@@ -228,12 +223,6 @@ uint32_t grid_for(size_t n, uint32_t cap) {
     return g < 1 ? 1u : (g > cap ? cap : (uint32_t)g);
 }
 
-#define U_HIP(expr)                                                                                                    \
-    do {                                                                                                               \
-        hipError_t e__ = (expr);                                                                                       \
-        if (e__ != hipSuccess) { cleanup(); return fail(MIPT_ERR_HIP, std::string(#expr " failed: ") + hipGetErrorString(e__)); } \
-    } while (0)
-
 // the REFIT plan of `s`, made once per tree (see MiptScene::refit_level_off)
 int ensure_plan(MiptScene *s, hipStream_t st) {
     if (!s->refit_level_off.empty() || s->dev.n_pairs == 0) return MIPT_OK;
@@ -244,32 +233,32 @@ int ensure_plan(MiptScene *s, hipStream_t st) {
         (void)hipStreamSynchronize(st);
         for (void *p : {(void *)plan, (void *)pair_of, (void *)lv, (void *)ctl}) if (p) (void)hipFree(p);
     };
-    U_HIP(hipMalloc((void **)&plan, (size_t)cap * 4));
-    if (s->d_nodes) U_HIP(hipMalloc((void **)&pair_of, (size_t)cap * 4));
-    U_HIP(hipMalloc((void **)&lv, (size_t)(2 * kMaxLevels + 1) * 4));
-    U_HIP(hipMalloc((void **)&ctl, sizeof(Ctl)));
-    U_HIP(hipMemsetAsync(lv, 0, (size_t)(2 * kMaxLevels + 1) * 4, st));
-    U_HIP(hipMemsetAsync(ctl, 0, sizeof(Ctl), st));
-    U_HIP(hipMemsetAsync(plan, 0, 4, st));                             // level 0 = { record 0 } (pair 0)
-    if (pair_of) U_HIP(hipMemsetAsync(pair_of, 0, 4, st));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&plan, (size_t)cap * 4));
+    if (s->d_nodes) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&pair_of, (size_t)cap * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&lv, (size_t)(2 * kMaxLevels + 1) * 4));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&ctl, sizeof(Ctl)));
+    MIPT_HIP_OR(cleanup(), hipMemsetAsync(lv, 0, (size_t)(2 * kMaxLevels + 1) * 4, st));
+    MIPT_HIP_OR(cleanup(), hipMemsetAsync(ctl, 0, sizeof(Ctl), st));
+    MIPT_HIP_OR(cleanup(), hipMemsetAsync(plan, 0, 4, st));                             // level 0 = { record 0 } (pair 0)
+    if (pair_of) MIPT_HIP_OR(cleanup(), hipMemsetAsync(pair_of, 0, 4, st));
     {
         const uint32_t one = 1;
-        U_HIP(hipMemcpyAsync(lv, &one, 4, hipMemcpyHostToDevice, st));
-        U_HIP(hipStreamSynchronize(st));
+        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(lv, &one, 4, hipMemcpyHostToDevice, st));
+        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     }
     std::vector<uint32_t> h_lv(2 * kMaxLevels + 1);
     uint32_t depth = 0;
     for (;;) {                                                          // batches of levels, then one look at the next level's size
         for (int b = 0; b < 16 && depth + 1 < kMaxLevels; b++, depth++)
             hipLaunchKernelGGL(plan_level, dim3(1024), dim3(kT), 0, st, (const float4 *)s->dev.pairs, s->d_nodes, plan, pair_of, cap, lv, depth, ctl);
-        U_HIP(hipGetLastError());
-        U_HIP(hipMemcpyAsync(h_lv.data(), lv, h_lv.size() * 4, hipMemcpyDeviceToHost, st));
-        U_HIP(hipStreamSynchronize(st));
+        MIPT_HIP_OR(cleanup(), hipGetLastError());
+        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(h_lv.data(), lv, h_lv.size() * 4, hipMemcpyDeviceToHost, st));
+        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
         if (h_lv[depth] == 0u) break;
-        if (depth + 1 >= kMaxLevels) { cleanup(); return fail(MIPT_ERR_BVH, "refit plan: tree deeper than " + std::to_string(kMaxLevels) + " levels"); }
+        if (depth + 1 >= kMaxLevels) { cleanup(); return fail(MIPT_ERR_BVH, "refit plan: tree deeper than %u levels", kMaxLevels); }
     }
     Ctl hc;
-    U_HIP(hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
+    MIPT_HIP_OR(cleanup(), hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
     if (hc.overflow) { cleanup(); return fail(MIPT_ERR_BVH, "refit plan: more records reached than the scene holds (internal)"); }
     (void)hipFree(lv); lv = nullptr;
     (void)hipFree(ctl); ctl = nullptr;
@@ -294,25 +283,25 @@ int refit(MiptScene *s, const MiptTriangle *d_tris, hipStream_t st, MiptUpdateIn
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     };
-    U_HIP(hipEventCreate(&e0));
-    U_HIP(hipEventCreate(&e1));
-    U_HIP(hipMalloc((void **)&ctl, sizeof(Ctl)));
+    MIPT_HIP_OR(cleanup(), hipEventCreate(&e0));
+    MIPT_HIP_OR(cleanup(), hipEventCreate(&e1));
+    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&ctl, sizeof(Ctl)));
     if (n_records) {
-        U_HIP(hipMalloc((void **)&scratch, (size_t)n_records * 64));
-        U_HIP(hipMalloc((void **)&big, (size_t)n_records * 2 * 4));
+        MIPT_HIP_OR(cleanup(), hipMalloc((void **)&scratch, (size_t)n_records * 64));
+        MIPT_HIP_OR(cleanup(), hipMalloc((void **)&big, (size_t)n_records * 2 * 4));
     }
     {
         Ctl h;
         memset(&h, 0, sizeof h);
         h.bad_tri = 0xffffffffu;
-        U_HIP(hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
+        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
     }
     const float4 *pairs = s->dev.pairs, *tri_pos = s->dev.tri_pos;
     const uint32_t *order = s->d_tri_order;
-    U_HIP(hipEventRecord(e0, st));
+    MIPT_HIP_OR(cleanup(), hipEventRecord(e0, st));
     hipLaunchKernelGGL(check_materials, dim3(grid_for(n_tris, 4096)), dim3(kT), 0, st, d_tris, n_tris, s->dev.n_mats, ctl);
     if (n_records) {
-        U_HIP(hipMemcpyAsync(scratch, pairs, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
+        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(scratch, pairs, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(refit_leaves, dim3(grid_for(n_records, 4096)), dim3(kT), 0, st, pairs, scratch, n_records, tri_pos, d_tris, order, big, ctl);
         hipLaunchKernelGGL(refit_big_leaves, dim3(1024), dim3(kT), 0, st, pairs, scratch, tri_pos, d_tris, order, big, ctl);
         const std::vector<uint32_t> &off = s->refit_level_off;
@@ -323,11 +312,11 @@ int refit(MiptScene *s, const MiptTriangle *d_tris, hipStream_t st, MiptUpdateIn
     }
     hipLaunchKernelGGL(refit_root, dim3(1), dim3(kT), 0, st, scratch, n_records ? 1u : 0u, s->dev.root_a, s->dev.root_n, tri_pos, d_tris, order, ctl);
     hipLaunchKernelGGL(check_bounds, dim3(grid_for(2 * (size_t)n_records + 1, 2048)), dim3(kT), 0, st, scratch, n_records, ctl);
-    U_HIP(hipGetLastError());
-    U_HIP(hipEventRecord(e1, st));
+    MIPT_HIP_OR(cleanup(), hipGetLastError());
+    MIPT_HIP_OR(cleanup(), hipEventRecord(e1, st));
     Ctl hc;
-    U_HIP(hipMemcpyAsync(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost, st));
-    U_HIP(hipStreamSynchronize(st));
+    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost, st));
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     float build_ms = 0.0f;
     (void)hipEventElapsedTime(&build_ms, e0, e1);
     if (hc.bad_bound) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40"); }
@@ -335,20 +324,19 @@ int refit(MiptScene *s, const MiptTriangle *d_tris, hipStream_t st, MiptUpdateIn
         MiptTriangle t;
         const hipError_t e = hipMemcpy(&t, d_tris + hc.bad_tri, sizeof t, hipMemcpyDeviceToHost);
         cleanup();
-        if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("reading a triangle back: ") + hipGetErrorString(e));
-        return fail(MIPT_ERR_INVALID_ARG, "triangle " + std::to_string(hc.bad_tri) + " has material_id " + std::to_string(t.material_id) +
-                                              " >= n_materials " + std::to_string(s->dev.n_mats));
+        if (e != hipSuccess) return fail(MIPT_ERR_HIP, "reading a triangle back: %s", hipGetErrorString(e));
+        return fail(MIPT_ERR_INVALID_ARG, "triangle %u has material_id %u >= n_materials %u", hc.bad_tri, t.material_id, s->dev.n_mats);
     }
     // ---- commit: nothing below can fail on the data, only on the runtime ----
     const double t_commit = now_ms();
-    if (n_records) U_HIP(hipMemcpyAsync((void *)pairs, scratch, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
+    if (n_records) MIPT_HIP_OR(cleanup(), hipMemcpyAsync((void *)pairs, scratch, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(rewrite_tris, dim3(grid_for(n_tris, 4096)), dim3(kT), 0, st, d_tris, order, n_tris, (float4 *)tri_pos, (float4 *)s->dev.tri_attr);
     if (s->d_nodes) {
         const uint32_t n_plan = s->refit_level_off.empty() ? 0u : s->refit_level_off.back();
         hipLaunchKernelGGL(refit_nodes, dim3(grid_for(n_plan, 2048)), dim3(kT), 0, st, scratch, s->d_refit_plan, n_plan, s->d_refit_pair, s->d_nodes, ctl);
     }
-    U_HIP(hipGetLastError());
-    U_HIP(hipStreamSynchronize(st));
+    MIPT_HIP_OR(cleanup(), hipGetLastError());
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
     s->dev.tiny_axes = hc.tiny_axes;
     inf->build_ms = build_ms;
     inf->layout_ms = now_ms() - t_commit;
@@ -373,12 +361,12 @@ int rebuild(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, MiptUpdat
 }
 
 int check_args(const char *who, const MiptScene *s, const void *tris, uint32_t n_tris, uint32_t mode) {
-    if (!s || !tris) return fail(MIPT_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    if (mode != MIPT_UPDATE_REFIT && mode != MIPT_UPDATE_REBUILD) return fail(MIPT_ERR_INVALID_ARG, std::string(who) + ": mode " + std::to_string(mode) + " is neither MIPT_UPDATE_REFIT nor MIPT_UPDATE_REBUILD");
-    if (n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, std::string(who) + ": no triangles (the reference panics in BVH::build)");
+    if (!s || !tris) return fail(MIPT_ERR_INVALID_ARG, "%s: null argument", who);
+    if (mode != MIPT_UPDATE_REFIT && mode != MIPT_UPDATE_REBUILD) return fail(MIPT_ERR_INVALID_ARG, "%s: mode %u is neither MIPT_UPDATE_REFIT nor MIPT_UPDATE_REBUILD", who, mode);
+    if (n_tris == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: no triangles (the reference panics in BVH::build)", who);
     if (mode == MIPT_UPDATE_REFIT && n_tris != s->n_tris)
-        return fail(MIPT_ERR_INVALID_ARG, std::string(who) + ": REFIT keeps the tree: " + std::to_string(n_tris) + " triangles given, the scene has " + std::to_string(s->n_tris));
-    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, std::to_string(n_tris) + " triangles exceed the 2^25 device-format limit");
+        return fail(MIPT_ERR_INVALID_ARG, "%s: REFIT keeps the tree: %u triangles given, the scene has %zu", who, n_tris, s->n_tris);
+    if (n_tris > mipt::kMaxTris) return fail(MIPT_ERR_SCENE_LIMIT, "%u triangles exceed the 2^25 device-format limit", n_tris);
     return MIPT_OK;
 }
 
@@ -408,7 +396,7 @@ int mipt::scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t
     MiptUpdateInfo inf{};
     hipError_t e = hipSetDevice(s->device);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                   // ordered after the caller's earlier work on `st`
-    if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("mipt_scene_update_triangles_device: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MIPT_ERR_HIP, "mipt_scene_update_triangles_device: %s", hipGetErrorString(e));
     const int rc = mode == MIPT_UPDATE_REFIT ? refit(s, d_tris, st, &inf) : rebuild(s, d_tris, n_tris, &inf);
     if (rc) return rc;
     finish_info(s, &inf, t0);
@@ -423,7 +411,7 @@ int mipt::scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_t
     hipError_t e = hipSetDevice(s->device);
     MiptTriangle *d_tris = nullptr;
     if (e == hipSuccess) e = hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle));
-    if (e != hipSuccess) return fail(MIPT_ERR_HIP, std::string("mipt_scene_update_triangles: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MIPT_ERR_HIP, "mipt_scene_update_triangles: %s", hipGetErrorString(e));
     int rc = mipt::upload_staged(d_tris, tris, (size_t)n_tris * sizeof(MiptTriangle));
     const double t_up = now_ms();
     MiptUpdateInfo inf{};
@@ -443,7 +431,7 @@ int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
     const int device = dst->device;
     SceneGeometry g;
     auto cleanup = [&]() { (void)hipSetDevice(device); (void)hipStreamSynchronize(nullptr); free_geometry(&g); };
-    U_HIP(hipSetDevice(device));
+    MIPT_HIP_OR(cleanup(), hipSetDevice(device));
     if (device != src->device) {
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) {
@@ -458,10 +446,10 @@ int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
                           {(void **)&g.d_tri_order, src->d_tri_order, src->n_tris * 4, src->n_tris * 4}};
     for (const Part &p : parts) {
         if (!p.from) continue;
-        U_HIP(hipMalloc(p.dst, p.alloc ? p.alloc : 16));
-        if (p.copy) U_HIP(hipMemcpyPeerAsync(*p.dst, device, p.from, src->device, p.copy, nullptr));
+        MIPT_HIP_OR(cleanup(), hipMalloc(p.dst, p.alloc ? p.alloc : 16));
+        if (p.copy) MIPT_HIP_OR(cleanup(), hipMemcpyPeerAsync(*p.dst, device, p.from, src->device, p.copy, nullptr));
     }
-    U_HIP(hipStreamSynchronize(nullptr));
+    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(nullptr));
     release_geometry(dst);
     dst->n_tris = src->n_tris; dst->n_nodes = src->n_nodes; dst->max_leaf = src->max_leaf;
     dst->geom_alloc = src->geom_alloc; dst->attr_bytes = src->attr_bytes;
@@ -481,16 +469,12 @@ int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
 extern "C" {
 
 int mipt_scene_update_triangles(MiptScene *scene, const MiptTriangle *tris, uint32_t n_tris, uint32_t mode, MiptUpdateInfo *info) {
-    try { return mipt::scene_update_host(scene, tris, n_tris, mode, info); }
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(mipt::scene_update_host(scene, tris, n_tris, mode, info))
 }
 
 int mipt_scene_update_triangles_device(MiptScene *scene, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, void *hip_stream,
                                        MiptUpdateInfo *info) {
-    try { return mipt::scene_update_device(scene, d_tris, n_tris, mode, (hipStream_t)hip_stream, info); }
-    catch (const std::bad_alloc &) { return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
-    catch (const std::exception &e) { return fail(MIPT_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); }
+    MIPT_NO_THROW(mipt::scene_update_device(scene, d_tris, n_tris, mode, (hipStream_t)hip_stream, info))
 }
 
 } // extern "C"

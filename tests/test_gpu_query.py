@@ -285,6 +285,39 @@ def test_spilled_stacks_across_refills(rrt, orc, anyhit):
     assert sums["max_stack"] > 16
 
 
+def test_renders_and_queries_share_one_spill_buffer(rrt):
+    """Renders and queries of one scene spill into the same per-wave HBM stack slots, which grow with the launch's grid: a one-block
+    render, a five-block query (the slots must grow), the render again, a one-block query.  Each call's result and counters are bit for
+    bit those of the same call as the first on a fresh scene."""
+    from test_gpu_batch import _chain_bvh
+    from rust_ray_tracing_amd import _lib as L
+    spilled = Q.chain_rays()[:70]                                              # the rays along +x: 40 stack entries each
+    big, small = np.resize(spilled, 4 * 256 + 1), np.resize(spilled, 65)
+
+    def render(sc):
+        r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=3, output_image_dimensions=(8, 8), output_image_path="/dev/null"))
+        hdr, _, st = r.render_buffers(sc, want_rgba8=False, flags=L.FLAG_COUNT)
+        return hdr.view(np.uint32).copy(), st
+
+    calls = [render, lambda sc: _closest(sc, big), render, lambda sc: _closest(sc, small)]
+
+    def scene():
+        sc = _chain_bvh(rrt, 40)
+        sc.upload(0)
+        return sc
+
+    def counters(st):                                                          # all but the clock readings: kernel_ms and diag[7 .. 10]
+        return dict({k: v for k, v in st.items() if k != "kernel_ms"}, diag=st["diag"][:7])
+
+    shared = scene()
+    for i, call in enumerate(calls):
+        want, want_st = call(scene())
+        got, got_st = call(shared)
+        assert want_st["max_stack"] > 16 and want_st["stack_overflows"] == 0, (i, want_st)   # the call spills
+        assert np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), i
+        assert counters(got_st) == counters(want_st), (i, got_st, want_st)
+
+
 def test_prim_through_tri_order_on_a_batch_larger_than_the_launch(rrt, orc):
     """A device-built scene: the hit's triangle goes through q.tri_order when the refill writes it, after neighbours were refilled"""
     sc, _, hits, _, _, classes = _pool_model(rrt, orc, "helmet-device", ARMS[2], False)
