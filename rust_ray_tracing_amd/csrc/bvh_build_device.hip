@@ -32,10 +32,8 @@
 #include <cstring>
 #include <vector>
 
-#include "mipt_internal.h"
-#include "mipt_scene.h"
-#define MIPT_HIP_FAIL_FMT "mipt_bvh_build_device: %s: %s"        // this file's HIP errors name the entry, not "... failed"
-#include "mipt_host_util.h"
+#define MIPT_HIP_FAIL_FMT "mipt_bvh_build_device: %s: %s"        // this file's HIP errors name the entry, not "... failed" (before mipt_host_util.h)
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
 namespace {
 
@@ -1359,48 +1357,39 @@ void mipt::bvh_builder_resolve_kernels() {
 int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int device_id, ResidentBvh *res) {
     if (!d_tris || !res || n_tris == 0) { return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); }
     *res = ResidentBvh{};
-    Proxy *d_px[2] = {nullptr, nullptr};
-    BNode *d_bn = nullptr;
-    MiptNode *d_nodes = nullptr;
-    uint32_t *d_order = nullptr;
-    PoolNode *d_pool = nullptr;
-    uint32_t *d_hp = nullptr, *d_tp = nullptr, *d_root = nullptr, *d_cbeg = nullptr, *d_lists = nullptr, *d_crange = nullptr;
-    Ctrl *d_ctrl = nullptr;
-    LevelSnap *h_snap = nullptr;                            // pinned, written by level_mark
-    BigState *d_big = nullptr;
-    ChunkInfo *d_chunks = nullptr;
-    ChunkBins *d_cbins = nullptr;
+    // released in reverse order of declaration: the streams first, then the buffers, the pinned block, the events
+    mipt::Event e0, e1;
+    mipt::PinnedPtr<LevelSnap> h_snap;                      // written by level_mark
+    mipt::DevPtr<Proxy> d_px[2];
+    mipt::DevPtr<BNode> d_bn;
+    mipt::DevPtr<MiptNode> d_nodes;
+    mipt::DevPtr<PoolNode> d_pool;
+    mipt::DevPtr<uint32_t> d_order, d_hp, d_tp, d_root, d_cbeg, d_lists, d_crange;
+    mipt::DevPtr<Ctrl> d_ctrl;
+    mipt::DevPtr<BigState> d_big;
+    mipt::DevPtr<ChunkInfo> d_chunks;
+    mipt::DevPtr<ChunkBins> d_cbins;
     const uint32_t big_cap = n_tris / kBig + 2u, chunk_cap = n_tris / kChunk + big_cap + 2u;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     // The per-level kernels touch disjoint nodes and overlap on four streams: the chunked path; the 65..512 wave kernel (the longest of
     // a deep level); the other wave and group kernels; the two thread kernels.  (A stream costs ~6 ms to create the first time in a process.)
-    hipStream_t sw = nullptr, sw2 = nullptr, sg = nullptr, ss = nullptr;
-    auto cleanup = [&]() {
-        hipStream_t all[] = {sw, sw2, sg, ss};
-        for (hipStream_t x : all) if (x) (void)hipStreamDestroy(x);
-        void *p[] = {d_px[0], d_px[1], d_bn, d_nodes, d_order, d_pool, d_hp, d_tp, d_ctrl, d_root, d_cbeg, d_big, d_chunks, d_cbins, d_crange, d_lists};
-        for (void *q : p) if (q) (void)hipFree(q);
-        if (h_snap) (void)hipHostFree(h_snap);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
+    mipt::Stream sw, sw2, sg, ss;
+    MIPT_HIP(hipSetDevice(device_id));
     const uint32_t max_nodes = 2u * n_tris;
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_px[0], (size_t)n_tris * sizeof(Proxy)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_px[1], (size_t)n_tris * sizeof(Proxy)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_bn, (size_t)max_nodes * sizeof(BNode)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_nodes, (size_t)max_nodes * sizeof(MiptNode)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_order, (size_t)n_tris * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_pool, (size_t)max_nodes * sizeof(PoolNode)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_hp, (size_t)n_tris * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tp, (size_t)n_tris * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_ctrl, sizeof(Ctrl)));
-    MIPT_HIP_OR(cleanup(), hipHostMalloc((void **)&h_snap, 2 * sizeof(LevelSnap), hipHostMallocDefault));
+    MIPT_HIP(d_px[0].alloc(n_tris));
+    MIPT_HIP(d_px[1].alloc(n_tris));
+    MIPT_HIP(d_bn.alloc(max_nodes));
+    MIPT_HIP(d_nodes.alloc(max_nodes));
+    MIPT_HIP(d_order.alloc(n_tris));
+    MIPT_HIP(d_pool.alloc(max_nodes));
+    MIPT_HIP(d_hp.alloc(n_tris));
+    MIPT_HIP(d_tp.alloc(n_tris));
+    MIPT_HIP(d_ctrl.alloc(1));
+    MIPT_HIP(h_snap.alloc(2));
     memset(h_snap, 0, 2 * sizeof(LevelSnap));
     // work lists: a level has at most min(2^level, n_tris) nodes; a class list never holds more nodes than triangles / its
     // smallest node... sized by the simple bound n_tris + 1 per (parity, class)
     const size_t list_cap = (size_t)n_tris + 1u;
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_lists, (2 * (size_t)(kClasses - 1) * list_cap + 2 * (size_t)big_cap) * 4));
+    MIPT_HIP(d_lists.alloc(2 * (size_t)(kClasses - 1) * list_cap + 2 * (size_t)big_cap));
     Lists ls;
     for (int pa = 0; pa < 2; pa++) {
         int slot = 0;
@@ -1410,28 +1399,28 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         }
         ls.l[pa][CLS_BIG] = d_lists + 2 * (size_t)(kClasses - 1) * list_cap + (size_t)pa * big_cap;
     }
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_root, 48));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_cbins, (size_t)chunk_cap * sizeof(ChunkBins)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_crange, 2 * (size_t)big_cap * 6 * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_cbeg, (size_t)(big_cap + 1) * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_big, (size_t)big_cap * sizeof(BigState)));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_chunks, (size_t)chunk_cap * sizeof(ChunkInfo)));
-    MIPT_HIP_OR(cleanup(), hipEventCreate(&e0));
-    MIPT_HIP_OR(cleanup(), hipEventCreate(&e1));
+    MIPT_HIP(d_root.alloc(12));
+    MIPT_HIP(d_cbins.alloc(chunk_cap));
+    MIPT_HIP(d_crange.alloc(2 * (size_t)big_cap * 6));
+    MIPT_HIP(d_cbeg.alloc((size_t)big_cap + 1));
+    MIPT_HIP(d_big.alloc(big_cap));
+    MIPT_HIP(d_chunks.alloc(chunk_cap));
+    MIPT_HIP(hipEventCreate(e0.put()));
+    MIPT_HIP(hipEventCreate(e1.put()));
     {   // blocking streams: ordered against the null stream's copies / launches.  The chunked path is a chain of eight dependent launches:
         // its stream gets the higher priority, so that a link of the chain is not left waiting for a CU under the wave kernels' workgroups
         // (-0.5 ms).  The others stay at the default priority: a stream at a priority the process has not used yet costs a new hardware
         // queue, 6-7 ms each the first time in a process (tools/setup_trace_first.py); creating them on a helper thread during the upload does
         // not hide that -- the runtime serialises queue creation with the copies (tried: the upload grew by what the creation took).
         int prio_lo = 0, prio_hi = 0;
-        MIPT_HIP_OR(cleanup(), hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        MIPT_HIP_OR(cleanup(), hipStreamCreateWithPriority(&sg, hipStreamDefault, prio_hi));
-        MIPT_HIP_OR(cleanup(), hipStreamCreate(&sw));
-        MIPT_HIP_OR(cleanup(), hipStreamCreate(&sw2));
-        MIPT_HIP_OR(cleanup(), hipStreamCreate(&ss));
+        MIPT_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+        MIPT_HIP(hipStreamCreateWithPriority(sg.put(), hipStreamDefault, prio_hi));
+        MIPT_HIP(hipStreamCreate(sw.put()));
+        MIPT_HIP(hipStreamCreate(sw2.put()));
+        MIPT_HIP(hipStreamCreate(ss.put()));
     }
     const uint32_t root_init[12] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    MIPT_HIP_OR(cleanup(), hipMemcpy(d_root, root_init, 48, hipMemcpyHostToDevice));
+    MIPT_HIP(hipMemcpy(d_root, root_init, 48, hipMemcpyHostToDevice));
     Ctrl hc;
     memset(&hc, 0, sizeof hc);
     hc.n_nodes.v = 1u;
@@ -1439,10 +1428,10 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         const int cls = (int)node_class(n_tris);
         hc.cnt[0][cls].v = 1u;
         const uint32_t zero = 0u;
-        MIPT_HIP_OR(cleanup(), hipMemcpy(ls.l[0][cls], &zero, 4, hipMemcpyHostToDevice));
+        MIPT_HIP(hipMemcpy(ls.l[0][cls], &zero, 4, hipMemcpyHostToDevice));
     }
-    MIPT_HIP_OR(cleanup(), hipMemcpy(d_ctrl, &hc, sizeof hc, hipMemcpyHostToDevice));
-    MIPT_HIP_OR(cleanup(), hipEventRecord(e0, nullptr));
+    MIPT_HIP(hipMemcpy(d_ctrl, &hc, sizeof hc, hipMemcpyHostToDevice));
+    MIPT_HIP(hipEventRecord(e0, nullptr));
     hipLaunchKernelGGL(make_proxies, dim3(2048), dim3(256), 0, nullptr, d_tris, n_tris, d_px[0], d_root);
     hipLaunchKernelGGL(init_root, dim3(1), dim3(1), 0, nullptr, d_bn, d_root, n_tris);
     std::vector<uint32_t> lvl_begin;
@@ -1457,9 +1446,9 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         if (nb) {                                       // top of the tree: nodes too large for one workgroup (chunks of kChunk);
                                                         // its own stream: these 8 launches overlap the level's wave / group / thread kernels
             const uint32_t nc = n_tris / kChunk + nb;   // bound on sum(ceil(n_j / kChunk)); the real count lives in ctrl->n_chunks
-            if (nb > big_cap || nc > chunk_cap) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity"); }
+            if (nb > big_cap || nc > chunk_cap) return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity");
             const dim3 gb((nb + 63) / 64), tb(64);
-            if (hc.cnt[row][kClasses].v > big_cap) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity"); }
+            if (hc.cnt[row][kClasses].v > big_cap) return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: internal capacity");
             hipLaunchKernelGGL(big_setup, dim3(1), dim3(kSetupT), 0, sg, d_big, d_bn, ls.l[parity][CLS_BIG], nb, d_chunks, d_cbeg, d_ctrl, d_root, d_crange + (size_t)parity * big_cap * 6);
             hipLaunchKernelGGL(big_bin, dim3(nc), dim3(kT), 0, sg, d_big, d_chunks, d_cbins, d_px[cur], d_ctrl);
             hipLaunchKernelGGL(big_choose, dim3(nb), dim3(64), 0, sg, d_big, nb, d_px[cur]);
@@ -1481,7 +1470,7 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
         if (ng16) hipLaunchKernelGGL((build_level_group<16, kTiny, 16u>), dim3((ng16 + 31u) / 32u), dim3(512), 0, sw2, d_bn, ls.l[parity][CLS_G16], ng16, d_px[cur], d_px[cur ^ 1], d_ctrl, ls, next);
         if (ntin) hipLaunchKernelGGL(build_level_tiny, dim3((ntin + 63u) / 64u), dim3(64), 0, st, d_bn, ls.l[parity][CLS_TINY], ntin, d_px[cur], d_px[cur ^ 1], d_ctrl, ls, next);
         if (nsub) hipLaunchKernelGGL(build_subtree_tiny, dim3((nsub + 63u) / 64u), dim3(64), 0, ss, d_bn, ls.l[parity][CLS_SUB], nsub, d_px[cur], d_px[0], d_px[1], d_pool, d_ctrl);
-        MIPT_HIP_OR(cleanup(), hipGetLastError());
+        MIPT_HIP(hipGetLastError());
         {   // the level's barrier and the next level's counts: level_mark on every stream that got work, then poll its flag
             hipStream_t used[4];
             uint32_t n_used = 0;
@@ -1494,12 +1483,11 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
                 const size_t lvl = lvl_begin.size();                    // level + 1: never 0
                 LevelSnap *snap = h_snap + (lvl & 1u);
                 for (uint32_t i = 0; i < n_used; i++) hipLaunchKernelGGL(level_mark, dim3(1), dim3(64), 0, used[i], d_ctrl, n_used, row_next, row, snap, (uint32_t)lvl);
-                MIPT_HIP_OR(cleanup(), hipGetLastError());
+                MIPT_HIP(hipGetLastError());
                 const auto t_spin = std::chrono::steady_clock::now();
                 for (uint32_t spins = 0; snap->flag != (uint32_t)lvl; spins++) {
                     if ((spins & 0xfffffu) == 0xfffffu && std::chrono::steady_clock::now() - t_spin > std::chrono::seconds(20)) {
-                        const hipError_t e = hipDeviceSynchronize();    // a kernel that faulted never raises the flag
-                        cleanup();
+                        const hipError_t e = hipDeviceSynchronize();    // a kernel that faulted never raises the flag; then the owners free
                         mipt_internal_set_error(e != hipSuccess ? hipGetErrorString(e) : "mipt_bvh_build_device: level barrier timed out");
                         return MIPT_ERR_HIP;
                     }
@@ -1510,14 +1498,14 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
             }
         }
         const uint32_t total = hc.n_nodes.v;
-        if (total > max_nodes) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow"); }
+        if (total > max_nodes) return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow");
         begin = end; end = total; cur ^= 1; parity ^= 1u; row = row_next;
-        if (lvl_begin.size() > 4096) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: tree deeper than 4096 levels"); }
+        if (lvl_begin.size() > 4096) return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: tree deeper than 4096 levels");
     }
     const uint32_t n_bn = end;                                  // nodes built level by level; the finished subtrees' nodes live in the pool
     const uint32_t n_nodes = n_bn + hc.sub_nodes.v;
     lvl_begin.push_back(n_bn);
-    if (n_nodes > max_nodes) { cleanup(); return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow"); }
+    if (n_nodes > max_nodes) return mipt::fail(MIPT_ERR_BVH, "mipt_bvh_build_device: node overflow");
     hipLaunchKernelGGL(extract_order, dim3(2048), dim3(256), 0, sw, d_px[cur], n_tris, d_order);      // beside the two tree passes below (every stream is idle here: the last level's barrier has been seen)
     {   // subtree sizes bottom-up, then depth-first bases top-down (which also writes the nodes): runs of small levels in one launch each, wide levels one by one
         const int n_lvl = (int)lvl_begin.size() - 1;
@@ -1553,14 +1541,12 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
             l = hi + 1;
         }
     }
-    MIPT_HIP_OR(cleanup(), hipEventRecord(e1, nullptr));
-    MIPT_HIP_OR(cleanup(), hipDeviceSynchronize());
+    MIPT_HIP(hipEventRecord(e1, nullptr));
+    MIPT_HIP(hipDeviceSynchronize());
     float ms = 0.0f;
-    MIPT_HIP_OR(cleanup(), hipEventElapsedTime(&ms, e0, e1));
-    res->d_nodes = d_nodes; res->n_nodes = n_nodes; res->d_tri_order = d_order; res->build_ms = ms;
+    MIPT_HIP(hipEventElapsedTime(&ms, e0, e1));
+    res->d_nodes = std::move(d_nodes); res->n_nodes = n_nodes; res->d_tri_order = std::move(d_order); res->build_ms = ms;
     res->levels = (uint32_t)lvl_begin.size();
-    d_nodes = nullptr; d_order = nullptr;                   // the caller's now
-    cleanup();
     return MIPT_OK;
 }
 
@@ -1568,37 +1554,30 @@ int mipt::bvh_build_resident(const MiptTriangle *d_tris, uint32_t n_tris, int de
 extern "C" int mipt_bvh_build_device(MiptTriangle *tris, uint32_t n_tris, MiptNode *nodes_out, uint32_t nodes_cap,
                                      uint32_t *n_nodes_out, int device_id, double *build_ms_out) {
     if (!tris || !nodes_out || n_tris == 0 || nodes_cap == 0) { return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: bad argument (empty scene: the reference panics)"); }
-    MiptTriangle *d_tris = nullptr, *d_out = nullptr;
+    mipt::Event g0, g1;                                     // the 112-byte gather belongs to the build (bvh.rs:105 swaps the triangles themselves)
+    mipt::DevPtr<MiptTriangle> d_tris, d_out;
     mipt::ResidentBvh r;
-    auto cleanup = [&]() {
-        if (d_tris) (void)hipFree(d_tris);
-        if (d_out) (void)hipFree(d_out);
-        if (r.d_nodes) (void)hipFree(r.d_nodes);
-        if (r.d_tri_order) (void)hipFree(r.d_tri_order);
-    };
-    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
+    MIPT_HIP(hipSetDevice(device_id));
     const size_t nb = (size_t)n_tris * sizeof(MiptTriangle);
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tris, nb));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_out, nb));
-    MIPT_HIP_OR(cleanup(), hipMemcpy(d_tris, tris, nb, hipMemcpyHostToDevice));
+    MIPT_HIP(d_tris.alloc(n_tris));
+    MIPT_HIP(d_out.alloc(n_tris));
+    MIPT_HIP(hipMemcpy(d_tris, tris, nb, hipMemcpyHostToDevice));
     const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &r);
-    if (rc != MIPT_OK) { cleanup(); return rc; }
-    if (r.n_nodes > nodes_cap) { cleanup(); return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: nodes_cap too small"); }
-    hipEvent_t g0 = nullptr, g1 = nullptr;                  // the 112-byte gather belongs to the build (bvh.rs:105 swaps the triangles themselves)
-    MIPT_HIP_OR(cleanup(), hipEventCreate(&g0));
-    if (hipEventCreate(&g1) != hipSuccess) { (void)hipEventDestroy(g0); cleanup(); return mipt::fail(MIPT_ERR_HIP, "mipt_bvh_build_device: hipEventCreate failed"); }
+    if (rc != MIPT_OK) return rc;
+    if (r.n_nodes > nodes_cap) return mipt::fail(MIPT_ERR_INVALID_ARG, "mipt_bvh_build_device: nodes_cap too small");
+    MIPT_HIP(hipEventCreate(g0.put()));
+    if (hipEventCreate(g1.put()) != hipSuccess) return mipt::fail(MIPT_ERR_HIP, "mipt_bvh_build_device: hipEventCreate failed");
     (void)hipEventRecord(g0, nullptr);
     hipLaunchKernelGGL(gather_tris, dim3(4096), dim3(256), 0, nullptr, d_tris, r.d_tri_order, n_tris, d_out);
     (void)hipEventRecord(g1, nullptr);
     hipError_t e = hipDeviceSynchronize();
     float gms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&gms, g0, g1);
-    (void)hipEventDestroy(g0); (void)hipEventDestroy(g1);
-    MIPT_HIP_OR(cleanup(), e);
-    MIPT_HIP_OR(cleanup(), hipMemcpy(tris, d_out, nb, hipMemcpyDeviceToHost));
-    MIPT_HIP_OR(cleanup(), hipMemcpy(nodes_out, r.d_nodes, (size_t)r.n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
+    g0.reset(); g1.reset();
+    MIPT_HIP(e);
+    MIPT_HIP(hipMemcpy(tris, d_out, nb, hipMemcpyDeviceToHost));
+    MIPT_HIP(hipMemcpy(nodes_out, r.d_nodes, (size_t)r.n_nodes * sizeof(MiptNode), hipMemcpyDeviceToHost));
     if (n_nodes_out) *n_nodes_out = r.n_nodes;
     if (build_ms_out) *build_ms_out = r.build_ms + gms;
-    cleanup();
     return MIPT_OK;
 }

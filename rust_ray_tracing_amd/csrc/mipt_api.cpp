@@ -4,9 +4,7 @@
 // without a HIP device the entry points return MIPT_ERR_HIP.
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
-#include "mipt_internal.h"
-#include "mipt_scene.h"
-#include "mipt_host_util.h"
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
 #include <atomic>
 #include <chrono>
@@ -189,7 +187,7 @@ static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
             if (pe != hipSuccess) (void)hipGetLastError();          // hipErrorPeerAccessAlreadyEnabled included
         }
     }
-    MiptScene *s = new (std::nothrow) MiptScene();
+    mipt::ScenePtr s(new (std::nothrow) MiptScene());
     if (!s) return fail(MIPT_ERR_INVALID_ARG, "out of host memory");
     s->device = device;
     s->dev = src->dev;
@@ -208,9 +206,9 @@ static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
         if (!p.from) continue;
         hipError_t e = hipMalloc(p.dst, p.alloc ? p.alloc : 16);
         if (e == hipSuccess && p.copy) e = hipMemcpyPeerAsync(*p.dst, device, p.from, src->device, p.copy, nullptr);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(nullptr); free_scene(s); return fail(MIPT_ERR_HIP, "replica copy %d -> %d: %s", src->device, device, hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(nullptr); return fail(MIPT_ERR_HIP, "replica copy %d -> %d: %s", src->device, device, hipGetErrorString(e)); }
     }
-    *out = s;
+    *out = s.release();
     return MIPT_OK;
 }
 static int clone_finish(const MiptScene *src, MiptScene *s, double t0) {

@@ -7,6 +7,7 @@
 #include "../../include/mipt_diag.h"
 #include "pt_device_math.h"
 #include "pt_device_wgsl.h"
+#include "mipt_host_util.h"
 #include "pt_kernel.h"
 
 #include <stdio.h>
@@ -114,11 +115,6 @@ __global__ void debug_wgsl_kernel(int op, const float *__restrict__ in, unsigned
     }
 }
 
-struct DevBuf {                       // frees on every exit path
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 int fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
     return -2;   // MIPT_ERR_HIP
@@ -130,30 +126,30 @@ extern "C" {
 
 int mipt_debug_eval(int op, const float *a, const float *b, uint64_t n, float *out) {
     if (!a || !out || n == 0) { snprintf(g_err, sizeof g_err, "mipt_debug_eval: bad argument"); return -1; }
-    DevBuf da, db, dout;
+    mipt::DevPtr<float> da, db, dout;
     hipError_t e;
-    if ((e = hipMalloc(&da.p, n * 4)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMalloc(&dout.p, n * 4)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(da.p, a, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = da.alloc(n)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dout.alloc(n)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     if (b) {
-        if ((e = hipMalloc(&db.p, n * 4)) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(db.p, b, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+        if ((e = db.alloc(n)) != hipSuccess) return fail(e, "hipMalloc");
+        if ((e = hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     }
-    hipLaunchKernelGGL(debug_eval_kernel, dim3(1024), dim3(256), 0, nullptr, op, (const float *)da.p, (const float *)db.p, 0.0f,
-                       (unsigned long long)n, (float *)dout.p);
+    hipLaunchKernelGGL(debug_eval_kernel, dim3(1024), dim3(256), 0, nullptr, op, da.get(), db.get(), 0.0f,
+                       (unsigned long long)n, dout.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-    if ((e = hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
 }
 
 int mipt_debug_eval_range(int op, uint32_t first_bits, uint64_t n, float y, float *out) {
     if (!out || n == 0 || (uint64_t)first_bits + n > (1ull << 32)) { snprintf(g_err, sizeof g_err, "mipt_debug_eval_range: bad argument"); return -1; }
-    DevBuf dout;
+    mipt::DevPtr<float> dout;
     hipError_t e;
-    if ((e = hipMalloc(&dout.p, n * 4)) != hipSuccess) return fail(e, "hipMalloc");
-    hipLaunchKernelGGL(debug_eval_range_kernel, dim3(2048), dim3(256), 0, nullptr, op, first_bits, y, (unsigned long long)n, (float *)dout.p);
+    if ((e = dout.alloc(n)) != hipSuccess) return fail(e, "hipMalloc");
+    hipLaunchKernelGGL(debug_eval_range_kernel, dim3(2048), dim3(256), 0, nullptr, op, first_bits, y, (unsigned long long)n, dout.get());
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-    if ((e = hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
 }
 
@@ -164,20 +160,20 @@ int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels,
         return -1;
     }
     const uint64_t in_bytes = n * kWgslIn[op] * 4, out_bytes = n * kWgslOut[op] * 4;
-    DevBuf din, dtex, dout;
+    mipt::DevPtr<char> din, dtex, dout;
     hipError_t e;
-    if ((e = hipMalloc(&din.p, in_bytes)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMalloc(&dout.p, out_bytes)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(din.p, in, in_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = din.alloc(in_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dout.alloc(out_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     if (op == 0) {
         const uint64_t tex_bytes = (uint64_t)tex_w * tex_h * 4;
-        if ((e = hipMalloc(&dtex.p, tex_bytes)) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(dtex.p, texels, tex_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+        if ((e = dtex.alloc(tex_bytes)) != hipSuccess) return fail(e, "hipMalloc");
+        if ((e = hipMemcpy(dtex, texels, tex_bytes, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     }
-    hipLaunchKernelGGL(debug_wgsl_kernel, dim3(1024), dim3(256), 0, nullptr, op, (const float *)din.p, (unsigned long long)n,
-                       (const uint32_t *)dtex.p, tex_w, tex_h, (float *)dout.p, kWgslIn[op], kWgslOut[op]);
+    hipLaunchKernelGGL(debug_wgsl_kernel, dim3(1024), dim3(256), 0, nullptr, op, (const float *)din.get(), (unsigned long long)n,
+                       (const uint32_t *)dtex.get(), tex_w, tex_h, (float *)dout.get(), kWgslIn[op], kWgslOut[op]);
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-    if ((e = hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
 }
 

@@ -1,8 +1,8 @@
 // mipt_internal.h -- functions shared between the translation units of libmipt.so.  None of them is exported: the library is built
 // with -fvisibility=hidden and only the MIPT_API declarations of include/mipt.h leave it.  (Host C++ only: no HIP types here, so the
 // CPU sanitizer builds of tests/cpp/ can include it.)
-// The error plumbing that needs no HIP type lives here: mipt::fail (defined below) and the MIPT_NO_THROW fence.  The HIP-call
-// macros and the grow-on-demand device buffer are in mipt_host_util.h.
+// The plumbing that needs no HIP type lives here: mipt::fail (defined below), the MIPT_NO_THROW fence and mipt::Owned, the owner of
+// one handle.  The HIP-call macros, Owned's HIP instances and the grow-on-demand device buffer are in mipt_host_util.h.
 #pragma once
 #include "../../include/mipt.h"
 
@@ -48,6 +48,28 @@ inline int fail(int code, const char *fmt, ...) {
 #define MIPT_NO_THROW(call) MIPT_NO_THROW_AS(MIPT_ERR_INVALID_ARG, call)
 
 namespace mipt {
+
+// The one owner of a handle that `Free` releases (a device pointer and hipFree, a stream and hipStreamDestroy, ...; the HIP instances
+// are in mipt_host_util.h).  Move-only (the move operations delete the copies); empty (T{}) by default and after a move.  The
+// destructor releases a non-empty handle exactly once and ignores Free's status.  Locals go in reverse order of declaration.
+template <class T, auto Free>
+class Owned {
+  public:
+    Owned() = default;
+    explicit Owned(T h) : h_(h) {}
+    Owned(Owned &&o) noexcept : h_(o.release()) {}
+    Owned &operator=(Owned &&o) noexcept { if (this != &o) reset(o.release()); return *this; }
+    ~Owned() { reset(); }
+    T get() const { return h_; }
+    operator T() const { return h_; }                            // a kernel argument, a HIP call's stream: used like the bare handle --
+                                                                 // but NEVER handed to Free (hipFree(d_x)): reset() is the early release
+    explicit operator bool() const { return h_ != T{}; }
+    T release() { const T h = h_; h_ = T{}; return h; }          // gives the handle up; nothing is freed
+    void reset(T h = T{}) { if (h_ != T{}) (void)Free(h_); h_ = h; }
+    T *put() { reset(); return &h_; }                            // for the call that allocates: hipStreamCreate(s.put())
+  private:
+    T h_{};
+};
 
 // ---- device-layout orders ----
 // Number of breadth-first levels at the top of the pair-record order (scene_device.hip LevelOp; 8 ... 14 measure the same, 2.005 - 2.03 G

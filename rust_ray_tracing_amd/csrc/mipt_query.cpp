@@ -2,9 +2,7 @@
 // staging for the host entries and the launch of ray_query.hip's kernel.  Host C++ only; every device operation is stream-ordered HIP.
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
-#include "mipt_internal.h"
-#include "mipt_scene.h"
-#include "mipt_host_util.h"
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
 #include <cmath>
 #include <cstring>

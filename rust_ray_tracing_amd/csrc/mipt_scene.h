@@ -2,13 +2,16 @@
 // and use it -- mipt_api.cpp (host checks, materials, replicas, renders), scene_device.hip (tree and layout built on the GPU),
 // bvh_build_device.hip (the builder), scene_update.hip (refit / rebuild), scene_mesh.hip (the resident mesh), mipt_query.cpp (ray
 // queries), mipt_multi.cpp (one replica per GPU) -- and by the test library's checksum hook (tests/cpp/scene_hooks.hip,
-// libmipt_diag.so).  Internal: HIP types, not part of include/mipt.h.
+// libmipt_diag.so).  Internal: HIP types, not part of include/mipt.h.  At the end, the launch scaffold of the traversal kernels, which
+// works on a scene's workspace.
 #pragma once
 #include "../../include/mipt.h"
+#include "mipt_host_util.h"
 #include "pt_kernel.h"
 
 #include <stddef.h>
 
+#include <memory>
 #include <vector>
 
 namespace mipt { struct SceneMesh; }
@@ -54,6 +57,8 @@ struct MiptScene {
 namespace mipt {
 
 void free_scene(MiptScene *s);
+struct SceneDeleter { void operator()(MiptScene *s) const { free_scene(s); } };
+using ScenePtr = std::unique_ptr<MiptScene, SceneDeleter>;      // a scene under construction: freed unless release()d to the caller
 // the resident mesh of `s` (if any) freed, on the current device (scene_mesh.hip); geometry, materials and workspace stay
 void free_mesh(MiptScene *s);
 // stats buffer, events, CU count: everything a scene needs besides its geometry.  On failure the scene is left for free_scene.
@@ -79,12 +84,15 @@ int build_material_tables(const MiptSceneDesc *desc, MaterialTables *out, bool g
 // on the current device.  With an empty `texels` the pool is allocated (n_texels) but not filled.
 int upload_material_tables(MiptScene *s, const MaterialTables &t);
 
+// ---- who frees what: ResidentBvh and SceneGeometry own their device arrays.  They are move-only, what one still holds when it goes
+// out of scope is freed on every outcome, and arrays change hands by a move or release(), never by copying a pointer.  The members of
+// MiptScene are the other kind: raw pointers that live as long as the handle, released by free_scene / release_geometry alone. ----
 // BVH::build (bvh.rs:13-161) on the GPU with everything staying in HBM (bvh_build_device.hip): `d_tris` in, the node array in the
-// reference's order and the triangle permutation out (reordered[t] = original[d_tri_order[t]]); both hipMalloc'ed, owned by the caller.
+// reference's order and the triangle permutation out (reordered[t] = original[d_tri_order[t]]).
 struct ResidentBvh {
-    MiptNode *d_nodes = nullptr;
+    DevPtr<MiptNode> d_nodes;
     uint32_t n_nodes = 0;
-    uint32_t *d_tri_order = nullptr;
+    DevPtr<uint32_t> d_tri_order;
     uint32_t levels = 0;                  // levels the level-synchronous part ran
     double build_ms = 0.0;                // HIP events around the build kernels
 };
@@ -95,20 +103,20 @@ void bvh_builder_resolve_kernels();
 // The geometry half of a device-built scene (scene_device.hip): the tree and the layout kernels, from triangles already in HBM --
 // what mipt_scene_create_from_triangles / mipt_scene_create run after their upload, and what REBUILD runs on a live scene.
 struct SceneGeometry {
-    void *d_geom = nullptr, *d_tri_attr = nullptr;
+    DevPtr<char> d_geom, d_tri_attr;
     size_t geom_alloc = 0, attr_bytes = 0, pairs_bytes = 0, pos_bytes = 0;
-    MiptNode *d_nodes = nullptr;            // the tree and the triangle permutation (BVH::build only; host nodes: null)
-    uint32_t *d_tri_order = nullptr;
+    DevPtr<MiptNode> d_nodes;               // the tree and the triangle permutation (BVH::build only; host nodes: null)
+    DevPtr<uint32_t> d_tri_order;
     uint32_t n_tris = 0, n_nodes = 0, n_records_padded = 0, max_leaf = 0, tiny_axes = 0, root_a = 0, root_n = 0;
     double build_ms = 0.0, t_build = 0.0;
 };
-// `bvh` in: with host_nodes, the caller's (validated) node array already in HBM (freed here on success); else filled by the build.
-// No scene is touched; on failure everything allocated here is freed and bvh's arrays are left to the caller.
+// `bvh` in: with host_nodes, the caller's (validated) node array already in HBM; else empty, filled by the build.  On success `out`
+// holds the geometry and, unless host_nodes, the tree (the caller's uploaded nodes are freed: the caller has them on the host).
+// No scene is touched; on failure `out` is as it was and `bvh` still holds what the caller put there, or what the build made.
 int build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n_materials, int device_id, bool host_nodes, ResidentBvh *bvh,
                    SceneGeometry *out);
-void free_geometry(SceneGeometry *g);
-// moves g's buffers into s (whose own geometry must be freed or moved out first) and sets dev / info geometry fields
-void attach_geometry(MiptScene *s, SceneGeometry *g);
+// g's buffers become s's (whose own geometry must be freed or moved out first), and the dev / info geometry fields are set
+void attach_geometry(MiptScene *s, SceneGeometry &&g);
 // the geometry, tree and refit plan of `s` (not its materials or workspace) freed; the MIPT_FLAG_TOUCHED bitmap too (sized by geometry)
 void release_geometry(MiptScene *s);
 // host -> device copy of a large pageable array through a ring of pinned buffers (scene_device.hip); blocks until it has arrived
@@ -118,5 +126,46 @@ int upload_staged(void *d_dst, const void *h_src, size_t bytes);
 // scene that owns a mesh: its resident mesh and the triangles would disagree)
 int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info,
                         bool expanded_mesh = false);
+
+// ---- the launch scaffold of the traversal kernels (mipt_api.cpp: the trace kernels; mipt_query.cpp: the ray queries) ----
+// Renders and queries of one scene share its workspace: d_stats, the events and the spill slots of the traversal stack (d_ovf, one
+// set per wave of the grid).  These two functions are the only code that sizes, grows and hands out that workspace.
+//
+// The grid of a launch: n_cu x blocks_per_cu blocks, at most ceil(work / kBlockThreads), at least 1; the scene's spill slots are
+// grown to the grid's wave count (the current device is the scene's).
+inline int traversal_grid(MiptScene *scene, int blocks_per_cu, unsigned long long work, int *grid_out) {
+    long long grid = (long long)scene->n_cu * blocks_per_cu;
+    const long long need_blocks = (long long)((work + kBlockThreads - 1) / kBlockThreads);
+    if (grid > need_blocks) grid = need_blocks;
+    if (grid < 1) grid = 1;
+    const size_t waves = (size_t)grid * kWavesPerBlock;
+    if (waves > scene->ovf_waves) {
+        if (scene->d_ovf) { (void)hipFree(scene->d_ovf); scene->d_ovf = nullptr; scene->ovf_waves = 0; }
+        MIPT_HIP(hipMalloc((void **)&scene->d_ovf, waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t)));
+        scene->ovf_waves = waves;
+    }
+    *grid_out = (int)grid;
+    return MIPT_OK;
+}
+
+// One timed launch on `stream`: d_stats zeroed, ev0, launch(), ev1, after_ev1(), the counters copied to `hs`, the stream
+// synchronised, `ms` = ev0 ... ev1 (the kernel alone).  `launch` and `after_ev1` queue their work on `stream` and return a status.
+// MIPT_ERR_STACK (hs and ms are valid, the results are written) when a traversal stack overflowed.
+template <class Launch, class After>
+int traversal_launch(MiptScene *scene, hipStream_t stream, Launch launch, After after_ev1, DevStats &hs, float &ms) {
+    int rc;
+    MIPT_HIP(hipMemsetAsync(scene->d_stats, 0, sizeof(mipt::DevStats), stream));
+    MIPT_HIP(hipEventRecord(scene->ev0, stream));
+    if ((rc = launch())) return rc;
+    MIPT_HIP(hipEventRecord(scene->ev1, stream));
+    if ((rc = after_ev1())) return rc;
+    MIPT_HIP(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
+    MIPT_HIP(hipStreamSynchronize(stream));
+    MIPT_HIP(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
+    if (hs.stack_overflows)
+        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
+                    hs.stack_overflows, kStackLds + kStackOvf);
+    return MIPT_OK;
+}
 
 } // namespace mipt

@@ -18,10 +18,8 @@
 // The scan kernels are written here (reduce / scan-of-sums / apply over a fixed grid, 4 x u32 lanes per element) rather than taken
 // from rocPRIM: they read their element count from device memory, which is what lets the level walk run without host synchronisation.
 #include "../../include/mipt.h"
-#include "mipt_internal.h"
-#include "mipt_scene.h"
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 #include "copy_crew.h"
-#include "mipt_host_util.h"
 
 #include <hip/hip_runtime.h>
 
@@ -334,9 +332,9 @@ class StagedUploader {
     void shut() {
         crew_.stop();
         if (stream_) (void)hipStreamSynchronize(stream_);
-        for (int i = 0; i < kRing; i++) { if (pin_[i]) (void)hipHostFree(pin_[i]); if (ev_[i]) (void)hipEventDestroy(ev_[i]); pin_[i] = nullptr; ev_[i] = nullptr; }
-        if (stream_) (void)hipStreamDestroy(stream_);
-        stream_ = nullptr; ready_ = false;
+        for (int i = 0; i < kRing; i++) { pin_[i].reset(); ev_[i].reset(); }
+        stream_.reset();
+        ready_ = false;
     }
 
   private:
@@ -345,19 +343,19 @@ class StagedUploader {
         return e == hipSuccess ? MIPT_OK : fail(MIPT_ERR_HIP, "upload: %s", hipGetErrorString(e));
     }
     int init() {                                               // 0 ok, 1 = no pinned memory / stream: fall back to hipMemcpy, < 0 error
-        hipError_t e = hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
+        hipError_t e = hipStreamCreateWithFlags(stream_.put(), hipStreamNonBlocking);
         for (int i = 0; i < kRing && e == hipSuccess; i++) {
-            e = hipHostMalloc((void **)&pin_[i], kChunk, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_[i], hipEventDisableTiming);
+            e = pin_[i].alloc(kChunk);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev_[i].put(), hipEventDisableTiming);
         }
         if (e != hipSuccess) { (void)hipGetLastError(); shut(); return 1; }
         crew_.start();
         ready_ = true;
         return 0;
     }
-    hipStream_t stream_ = nullptr;
-    char *pin_[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_[kRing] = {nullptr, nullptr, nullptr, nullptr};
+    mipt::Stream stream_;
+    mipt::PinnedPtr<char> pin_[kRing];
+    mipt::Event ev_[kRing];
     mipt::CopyCrew crew_{4};
     size_t seq_ = 0;
     bool ready_ = false;
@@ -367,23 +365,20 @@ class StagedUploader {
 
 // The geometry half of both ways in (and of mipt_scene_update_triangles' REBUILD): the tree -- BVH::build in HBM, or the caller's node
 // array already uploaded to bvh->d_nodes (host_nodes) -- and the layout kernels, from triangles that are already in HBM.  Nothing of a
-// scene is touched: on success `g` owns the new geometry (and, unless host_nodes, the tree); on failure everything made here is freed.
+// scene is touched: on success `g` owns the new geometry (and, unless host_nodes, the tree); on failure everything made here is freed
+// and `bvh_io` keeps what it held.
 int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n_materials, int device_id, bool host_nodes, ResidentBvh *bvh_io,
                          SceneGeometry *g) {
     mipt::ResidentBvh &bvh = *bvh_io;
-    char *arena = nullptr;
     SceneGeometry out;
-    auto cleanup = [&]() {
-        if (arena) (void)hipFree(arena);
-        mipt::free_geometry(&out);
-    };
+    mipt::DevPtr<char> arena;
     // ---- 2. BVH::build in HBM (or the caller's tree) ----
-    if (!host_nodes) { const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &bvh); if (rc) { cleanup(); return rc; } }
+    if (!host_nodes) { const int rc = mipt::bvh_build_resident(d_tris, n_tris, device_id, &bvh); if (rc) return rc; }
     out.t_build = now_ms();
     const uint32_t n_nodes = bvh.n_nodes;
-    if ((n_nodes & 1u) == 0u) { cleanup(); return fail(MIPT_ERR_BVH, "device builder returned an even node count"); }
+    if ((n_nodes & 1u) == 0u) return fail(MIPT_ERR_BVH, "device builder returned an even node count");
     const uint32_t n_pairs = (n_nodes - 1u) / 2u;
-    if (n_pairs > mipt::kMaxPairs) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "%u node pairs exceed the 2^24 device-format limit", n_pairs); }
+    if (n_pairs > mipt::kMaxPairs) return fail(MIPT_ERR_SCENE_LIMIT, "%u node pairs exceed the 2^24 device-format limit", n_pairs);
 
     // ---- 3. layout kernels.  One arena for the temporaries ----
     const size_t np = n_pairs ? n_pairs : 1, order_cap = 2 * (size_t)n_pairs + 4;
@@ -391,7 +386,7 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
     const size_t o_ctl = 0, o_sums = up(sizeof(Ctl)), o_slot = o_sums + up(sizeof(U4) * kScanGrid), o_placed = o_slot + up((size_t)n_tris * 4),
                  o_lvl0 = o_placed + up(n_tris), o_lvl1 = o_lvl0 + up(np * 4), o_lone = o_lvl1 + up(np * 4), o_taken = o_lone + up(np * 4),
                  o_order = o_taken + up(np), o_newof = o_order + up(order_cap * 4), arena_bytes = o_newof + up(np * 4);
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&arena, arena_bytes));
+    MIPT_HIP(arena.alloc(arena_bytes));
     Ctl *ctl = (Ctl *)(arena + o_ctl);
     U4 *sums = (U4 *)(arena + o_sums);
     uint32_t *slot = (uint32_t *)(arena + o_slot), *lvl[2] = {(uint32_t *)(arena + o_lvl0), (uint32_t *)(arena + o_lvl1)},
@@ -403,11 +398,11 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
         memset(&h, 0, sizeof h);
         h.lv[0].cnt = n_pairs ? 1u : 0u;                           // level 0 = { pair 0 } (the root's children)
         h.bad_tri = 0xffffffffu;
-        MIPT_HIP_OR(cleanup(), hipMemcpy(ctl, &h, sizeof h, hipMemcpyHostToDevice));
-        MIPT_HIP_OR(cleanup(), hipMemsetAsync(placed, 0, n_tris, st));
-        MIPT_HIP_OR(cleanup(), hipMemsetAsync(taken, 0, np, st));
-        MIPT_HIP_OR(cleanup(), hipMemsetAsync(order, 0xff, order_cap * 4, st));     // every entry a pad until a pair is written there
-        MIPT_HIP_OR(cleanup(), hipMemsetAsync(lvl[0], 0, 4, st));
+        MIPT_HIP(hipMemcpy(ctl, &h, sizeof h, hipMemcpyHostToDevice));
+        MIPT_HIP(hipMemsetAsync(placed, 0, n_tris, st));
+        MIPT_HIP(hipMemsetAsync(taken, 0, np, st));
+        MIPT_HIP(hipMemsetAsync(order, 0xff, order_cap * 4, st));     // every entry a pad until a pair is written there
+        MIPT_HIP(hipMemsetAsync(lvl[0], 0, 4, st));
     }
     hipLaunchKernelGGL(check_nodes, dim3(1024), dim3(kT), 0, st, bvh.d_nodes, n_nodes, ctl);
     if (n_pairs) run_scan(DoublesOp{bvh.d_nodes, n_pairs, slot, placed, ctl}, sums, st);
@@ -421,48 +416,47 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
         for (;;) {
             for (int b = 0; b < 16; b++, depth++)
                 run_scan(LevelOp{bvh.d_nodes, lvl[depth & 1u], lvl[(depth & 1u) ^ 1u], taken, order, lone, ctl, depth & 1u, depth >= top ? 1u : 0u}, sums, st);
-            MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-            MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+            MIPT_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+            MIPT_HIP(hipStreamSynchronize(st));
             if (hctl.lv[depth & 1u].cnt == 0u) break;
-            if (depth > 8192u) { cleanup(); return fail(MIPT_ERR_BVH, "BVH deeper than 8192 levels"); }
+            if (depth > 8192u) return fail(MIPT_ERR_BVH, "BVH deeper than 8192 levels");
         }
         hipLaunchKernelGGL(append_lone, dim3(1024), dim3(kT), 0, st, lone, order, ctl, depth & 1u);
     } else {
-        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+        MIPT_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+        MIPT_HIP(hipStreamSynchronize(st));
     }
-    if (hctl.bad_bound) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40"); }
+    if (hctl.bad_bound) return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40");
     const LevelState fin = hctl.lv[depth & 1u];
     uint32_t n_records = n_pairs ? ((fin.order_base + 1u) & ~1u) + fin.lone_base : 0u;
-    if ((size_t)n_records + 1 > order_cap) { cleanup(); return fail(MIPT_ERR_BVH, "pair-record order overflow (internal)"); }
+    if ((size_t)n_records + 1 > order_cap) return fail(MIPT_ERR_BVH, "pair-record order overflow (internal)");
     const uint32_t n_records_padded = (n_records + 1u) & ~1u;      // one zero pad record: the triangle stream behind starts on a 128-B line
-    if (n_records_padded > mipt::kMaxPairs) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "pair records (with line padding) exceed the 2^24 device-format limit"); }
+    if (n_records_padded > mipt::kMaxPairs) return fail(MIPT_ERR_SCENE_LIMIT, "pair records (with line padding) exceed the 2^24 device-format limit");
     const size_t pairs_bytes = (size_t)n_records_padded * 64, pos_bytes = (size_t)n_tris * 64 + 16;
-    if (pairs_bytes + pos_bytes >= 0xffffffffull) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "BVH + triangle stream exceed 4 GiB"); }
+    if (pairs_bytes + pos_bytes >= 0xffffffffull) return fail(MIPT_ERR_SCENE_LIMIT, "BVH + triangle stream exceed 4 GiB");
 
     out.n_tris = n_tris;
     out.geom_alloc = pairs_bytes + pos_bytes + 64;
     out.attr_bytes = (size_t)n_tris * 64;
-    MIPT_HIP_OR(cleanup(), hipMalloc(&out.d_geom, out.geom_alloc));
-    MIPT_HIP_OR(cleanup(), hipMalloc(&out.d_tri_attr, out.attr_bytes));
-    float4 *d_pairs = (float4 *)out.d_geom, *d_pos = (float4 *)((char *)out.d_geom + pairs_bytes);
+    MIPT_HIP(out.d_geom.alloc(out.geom_alloc));
+    MIPT_HIP(out.d_tri_attr.alloc(out.attr_bytes));
+    float4 *d_pairs = (float4 *)out.d_geom.get(), *d_pos = (float4 *)(out.d_geom + pairs_bytes);
     if (n_records) hipLaunchKernelGGL(write_new_of, dim3(2048), dim3(kT), 0, st, order, n_records, new_of);
     if (n_records_padded) hipLaunchKernelGGL(write_pairs, dim3(2048), dim3(kT), 0, st, bvh.d_nodes, order, n_records, n_records_padded, new_of, slot, d_pairs);
-    hipLaunchKernelGGL(write_tris, dim3(4096), dim3(kT), 0, st, d_tris, bvh.d_tri_order, n_tris, n_materials, slot, d_pos, (float4 *)out.d_tri_attr, ctl);
-    MIPT_HIP_OR(cleanup(), hipGetLastError());
+    hipLaunchKernelGGL(write_tris, dim3(4096), dim3(kT), 0, st, d_tris, bvh.d_tri_order, n_tris, n_materials, slot, d_pos, (float4 *)out.d_tri_attr.get(), ctl);
+    MIPT_HIP(hipGetLastError());
     MiptNode root;
     uint32_t root_slot = 0;
-    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
-    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&root, bvh.d_nodes, sizeof root, hipMemcpyDeviceToHost, st));
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+    MIPT_HIP(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, st));
+    MIPT_HIP(hipMemcpyAsync(&root, bvh.d_nodes, sizeof root, hipMemcpyDeviceToHost, st));
+    MIPT_HIP(hipStreamSynchronize(st));
     if (hctl.bad_tri != 0xffffffffu) {
-        cleanup();
         return host_nodes ? fail(MIPT_ERR_INVALID_ARG, "triangle %u has material_id >= n_materials %u", hctl.bad_tri, n_materials)
                           : fail(MIPT_ERR_INVALID_ARG, "a triangle has material_id >= n_materials %u (position %u of the BVH order)", n_materials, hctl.bad_tri);
     }
-    if (root.num_tris > 0u) MIPT_HIP_OR(cleanup(), hipMemcpy(&root_slot, slot + root.first_tri_or_child, 4, hipMemcpyDeviceToHost));
-    else if (root.first_tri_or_child != 1u) { cleanup(); return fail(MIPT_ERR_BVH, "root's children must be nodes 1 and 2 (bvh.rs:121)"); }
-    (void)hipFree(arena); arena = nullptr;
+    if (root.num_tris > 0u) MIPT_HIP(hipMemcpy(&root_slot, slot + root.first_tri_or_child, 4, hipMemcpyDeviceToHost));
+    else if (root.first_tri_or_child != 1u) return fail(MIPT_ERR_BVH, "root's children must be nodes 1 and 2 (bvh.rs:121)");
+    arena.reset();
 
     out.max_leaf = hctl.max_leaf;
     out.tiny_axes = hctl.tiny_axes;
@@ -472,42 +466,33 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
     out.root_a = root.num_tris > 0u ? root_slot : 0u;
     out.root_n = root.num_tris;
     out.build_ms = host_nodes ? 0.0 : bvh.build_ms;
-    if (host_nodes) { (void)hipFree(bvh.d_nodes); bvh.d_nodes = nullptr; }          // the caller has them
+    if (host_nodes) bvh.d_nodes.reset();                                             // the caller has them
     else {                                                                           // kept for mipt_scene_get_bvh
-        out.d_nodes = bvh.d_nodes; bvh.d_nodes = nullptr;
-        out.d_tri_order = bvh.d_tri_order; bvh.d_tri_order = nullptr;
+        out.d_nodes = std::move(bvh.d_nodes);
+        out.d_tri_order = std::move(bvh.d_tri_order);
     }
-    *g = out;
-    out = SceneGeometry();
+    *g = std::move(out);
     return MIPT_OK;
 }
 
-void mipt::free_geometry(SceneGeometry *g) {
-    void *ptrs[] = {g->d_geom, g->d_tri_attr, g->d_nodes, g->d_tri_order};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    *g = SceneGeometry();
-}
-
-void mipt::attach_geometry(MiptScene *s, SceneGeometry *g) {
-    s->n_tris = g->n_tris;
-    s->geom_alloc = g->geom_alloc; s->attr_bytes = g->attr_bytes;
-    s->d_geom = g->d_geom; s->d_tri_attr = g->d_tri_attr;
-    s->d_nodes = g->d_nodes; s->d_tri_order = g->d_tri_order;
-    s->max_leaf = g->max_leaf;
-    s->n_nodes = g->n_nodes;
+void mipt::attach_geometry(MiptScene *s, SceneGeometry &&g) {
+    s->n_tris = g.n_tris;
+    s->geom_alloc = g.geom_alloc; s->attr_bytes = g.attr_bytes;
+    s->d_geom = g.d_geom.release(); s->d_tri_attr = g.d_tri_attr.release();
+    s->d_nodes = g.d_nodes.release(); s->d_tri_order = g.d_tri_order.release();
+    s->max_leaf = g.max_leaf;
+    s->n_nodes = g.n_nodes;
     s->dev.pairs = (const float4 *)s->d_geom;
-    s->dev.tri_pos = (const float4 *)((const char *)s->d_geom + g->pairs_bytes);
-    s->dev.tri_off_bytes = (uint32_t)g->pairs_bytes;
-    s->dev.geom_bytes = (uint32_t)(g->pairs_bytes + g->pos_bytes);
-    s->dev.tiny_axes = g->tiny_axes;
+    s->dev.tri_pos = (const float4 *)((const char *)s->d_geom + g.pairs_bytes);
+    s->dev.tri_off_bytes = (uint32_t)g.pairs_bytes;
+    s->dev.geom_bytes = (uint32_t)(g.pairs_bytes + g.pos_bytes);
+    s->dev.tiny_axes = g.tiny_axes;
     s->dev.tri_attr = (const float4 *)s->d_tri_attr;
-    s->dev.n_pairs = g->n_records_padded; s->dev.n_tris = g->n_tris;
-    s->dev.root_a = g->root_a;
-    s->dev.root_n = g->root_n;
-    s->info.n_tris = g->n_tris; s->info.n_nodes = g->n_nodes; s->info.n_pair_records = g->n_records_padded; s->info.max_leaf = g->max_leaf;
-    s->info.geometry_bytes = (uint64_t)g->pairs_bytes + g->pos_bytes + g->attr_bytes;
-    *g = SceneGeometry();
+    s->dev.n_pairs = g.n_records_padded; s->dev.n_tris = g.n_tris;
+    s->dev.root_a = g.root_a;
+    s->dev.root_n = g.root_n;
+    s->info.n_tris = g.n_tris; s->info.n_nodes = g.n_nodes; s->info.n_pair_records = g.n_records_padded; s->info.max_leaf = g.max_leaf;
+    s->info.geometry_bytes = (uint64_t)g.pairs_bytes + g.pos_bytes + g.attr_bytes;
 }
 
 // Both ways in end here.  `host_nodes`: the caller's node array (validated by mipt_scene_create, mipt_api.cpp) is uploaded beside the
@@ -533,55 +518,46 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
         if (e != hipSuccess) return fail(MIPT_ERR_HIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
         if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device %d not available (%d visible)", device_id, ndev);
     }
-    MiptTriangle *d_tris = nullptr;
+    mipt::DevPtr<MiptTriangle> d_tris;
     mipt::ResidentBvh bvh;
     mipt::SceneGeometry geo;
-    MiptScene *s = nullptr;
-    StagedUploader up_ring;
-    auto cleanup = [&]() {
-        up_ring.shut();
-        if (d_tris) (void)hipFree(d_tris);
-        if (bvh.d_nodes) (void)hipFree(bvh.d_nodes);
-        if (bvh.d_tri_order) (void)hipFree(bvh.d_tri_order);
-        mipt::free_geometry(&geo);
-        if (s) mipt::free_scene(s);
-    };
-    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
+    mipt::ScenePtr s;
+    StagedUploader up_ring;                                   // shuts (and waits for its stream) before the buffers above are freed
+    MIPT_HIP(hipSetDevice(device_id));
     // ---- 1. the one host -> device copy ----
-    if (!d_resident) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle)));
-    if (host_nodes) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&bvh.d_nodes, (size_t)desc->n_nodes * sizeof(MiptNode)));
+    if (!d_resident) MIPT_HIP(d_tris.alloc(n_tris));
+    if (host_nodes) MIPT_HIP(bvh.d_nodes.alloc(desc->n_nodes));
     {
-        std::thread warm;
-        if (!host_nodes) warm = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
+        mipt::JoinOnExit warm;
+        if (!host_nodes) warm.t = std::thread([device_id]() { if (hipSetDevice(device_id) == hipSuccess) mipt::bvh_builder_resolve_kernels(); });   // beside the copies
         int rc = d_resident ? MIPT_OK : up_ring.copy(d_tris, desc->tris, (size_t)n_tris * sizeof(MiptTriangle));
         if (rc == MIPT_OK && host_nodes) rc = up_ring.copy(bvh.d_nodes, desc->nodes, (size_t)desc->n_nodes * sizeof(MiptNode));
         if (rc == MIPT_OK) rc = up_ring.finish();
-        if (warm.joinable()) warm.join();
+        if (warm.t.joinable()) warm.t.join();
         up_ring.pause();                                      // back for the textures, after the build
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
     }
     const double t_up = now_ms();
     if (host_nodes) bvh.n_nodes = desc->n_nodes;
     // ---- 2. + 3. the tree and the layout, from the triangles in HBM ----
-    { const int rc = mipt::build_geometry(d_resident ? d_resident : d_tris, n_tris, desc->n_materials, device_id, host_nodes, &bvh, &geo); if (rc) { cleanup(); return rc; } }
-    if (d_tris) (void)hipFree(d_tris);
-    d_tris = nullptr;
+    { const int rc = mipt::build_geometry(d_resident ? d_resident : d_tris, n_tris, desc->n_materials, device_id, host_nodes, &bvh, &geo); if (rc) return rc; }
+    d_tris.reset();
     const double t_build = geo.t_build, t_layout = now_ms();
 
-    s = new (std::nothrow) MiptScene();
-    if (!s) { cleanup(); return fail(MIPT_ERR_INVALID_ARG, "out of host memory"); }
+    s.reset(new (std::nothrow) MiptScene());
+    if (!s) return fail(MIPT_ERR_INVALID_ARG, "out of host memory");
     s->device = device_id;
     const double build_ms = geo.build_ms;
-    mipt::attach_geometry(s, &geo);
+    mipt::attach_geometry(s.get(), std::move(geo));
     {   // materials + the texel pool; the textures go through the same pinned ring, straight from the caller's buffers
-        int rc = mipt::upload_material_tables(s, tables);
+        int rc = mipt::upload_material_tables(s.get(), tables);
         for (uint32_t i = 0; i < desc->n_textures && rc == MIPT_OK; i++)
             rc = up_ring.copy((uint32_t *)s->d_texels + tables.tex_offset[i], desc->textures[i].rgba8, (size_t)desc->textures[i].width * desc->textures[i].height * 4);
         if (rc == MIPT_OK) rc = up_ring.finish();
         up_ring.shut();
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
     }
-    { const int rc = mipt::scene_finish_workspace(s); if (rc) { cleanup(); return rc; } }
+    { const int rc = mipt::scene_finish_workspace(s.get()); if (rc) return rc; }
     s->dev.n_mats = desc->n_materials; s->dev.n_texs = desc->n_textures;
     const double t_end = now_ms();
     s->info.built_on_device = host_nodes ? 0u : 1u;
@@ -589,8 +565,7 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     s->info.build_ms = build_ms;
     s->info.layout_ms = t_layout - t_build;
     s->info.total_ms = t_end - t_begin;
-    *out = s;
-    s = nullptr;
+    *out = s.release();
     return MIPT_OK;
 }
 
@@ -599,8 +574,7 @@ int mipt::upload_staged(void *d_dst, const void *h_src, size_t bytes) {
     StagedUploader up_ring;
     int rc = up_ring.copy(d_dst, h_src, bytes);
     if (rc == MIPT_OK) rc = up_ring.finish();
-    up_ring.shut();
-    return rc;
+    return rc;                                                 // up_ring shuts on the way out
 }
 
 int mipt::scene_create_from_triangles(const MiptSceneDesc *desc, int device_id, MiptScene **out) { return create_on_device(desc, device_id, false, out); }

@@ -18,15 +18,14 @@
 // arrays are read from the caller's buffers by the expansion, and only after the REFIT / REBUILD committed are the tables swapped
 // and the arrays copied over the resident ones.
 #include "../../include/mipt.h"
-#include "mipt_internal.h"
-#include "mipt_scene.h"
-#include "mipt_host_util.h"
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 
 static_assert(sizeof(MiptMeshPart) == 16 && sizeof(MiptMeshInfo) == 56 && sizeof(MiptMeshDesc) == 104, "mesh ABI structs (rust_ray_tracing_amd/_lib.py)");
@@ -233,21 +232,17 @@ void free_mesh_buffers(SceneMesh *m) {
 uint32_t grid_for(size_t n, uint32_t per_block) { return (uint32_t)((n + per_block - 1) / per_block); }
 
 // expansion of the resident mesh -- with `pos` / `nrm` in place of the resident arrays where given -- through PartRec table `rec` into
-// d_expanded, queued on `st`; *ms = HIP-event time of the kernels once the caller has synchronised on e1
-struct ExpandTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~ExpandTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-hipError_t queue_expand(const SceneMesh *m, const float *pos, const float *nrm, const float *d_xf, bool new_records, int rec, hipStream_t st, ExpandTimer *tm) {
-    hipError_t e = hipEventCreate(&tm->e0);
-    if (e == hipSuccess) e = hipEventCreate(&tm->e1);
-    if (e == hipSuccess) e = hipEventRecord(tm->e0, st);
+// d_expanded, queued on `st`; e0 ... e1 = HIP-event time of the kernels once the caller has synchronised on e1
+hipError_t queue_expand(const SceneMesh *m, const float *pos, const float *nrm, const float *d_xf, bool new_records, int rec, hipStream_t st, mipt::Event &e0, mipt::Event &e1) {
+    hipError_t e = hipEventCreate(e0.put());
+    if (e == hipSuccess) e = hipEventCreate(e1.put());
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
     if (e != hipSuccess) return e;
     if (new_records) hipLaunchKernelGGL(mesh_prepare_parts, dim3(grid_for(m->n_parts, 64)), dim3(64), 0, st, m->d_parts, m->n_parts, d_xf, m->d_rec[rec]);
     const MeshView v{pos ? pos : m->d_pos, nrm ? nrm : m->d_nrm, m->d_tex, m->d_idx[0], m->d_idx[1], m->d_idx[2], m->n_pos, m->n_nrm, m->n_tex, m->n_tris};
     hipLaunchKernelGGL(mesh_expand, dim3(grid_for(m->n_tris, kT)), dim3(kT), 0, st, v, m->d_rec[rec], m->n_parts, (float4 *)m->d_expanded, m->d_flag);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(tm->e1, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
     return e;
 }
 
@@ -267,15 +262,14 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
         if (e != hipSuccess) return fail(MIPT_ERR_HIP, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
         if (device_id < 0 || device_id >= ndev) return fail(MIPT_ERR_HIP, "HIP device %d not available (%d visible)", device_id, ndev);
     }
-    SceneMesh *m = new (std::nothrow) SceneMesh();
+    std::unique_ptr<SceneMesh, void (*)(SceneMesh *)> mesh_owner(new (std::nothrow) SceneMesh(), free_mesh_buffers);
+    SceneMesh *const m = mesh_owner.get();
     if (!m) return fail(MIPT_ERR_INVALID_ARG, "out of host memory");
-    MiptScene *s = nullptr;
-    auto cleanup = [&]() {
-        (void)hipDeviceSynchronize();
-        if (s) { s->mesh = nullptr; mipt::free_scene(s); s = nullptr; }
-        free_mesh_buffers(m); m = nullptr;
-    };
-    MIPT_HIP_OR(cleanup(), hipSetDevice(device_id));
+    // Holds the scene only from its creation to the hand-over below, three assignments that cannot fail: it is here so that an exception
+    // or a later edit in that window still detaches the mesh from the half-made scene before both go (the mesh once, by its own owner).
+    std::unique_ptr<MiptScene, void (*)(MiptScene *)> scene_owner(nullptr, [](MiptScene *p) { p->mesh = nullptr; mipt::free_scene(p); });
+    mipt::SyncOnExit sync(mipt::SyncOnExit::kWholeDevice);              // a failure waits for the device, then the scene goes, then the mesh
+    MIPT_HIP(hipSetDevice(device_id));
     m->n_pos = mesh->n_positions;
     m->n_nrm = mesh->normals ? mesh->n_normals : 0u;
     m->n_tex = mesh->tex_coords ? mesh->n_tex_coords : 0u;
@@ -294,42 +288,45 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
     for (const Up &u : ups) {
         const bool stage = u.dst == (void **)&m->d_xf_stage;              // allocated even without transforms: mipt_scene_set_transforms fills it
         if (!u.bytes || (!u.src && !stage)) continue;
-        MIPT_HIP_OR(cleanup(), hipMalloc(u.dst, u.bytes));
+        MIPT_HIP(hipMalloc(u.dst, u.bytes));
         m->array_bytes += u.bytes;
-        if (u.src) { const int rc = mipt::upload_staged(*u.dst, u.src, u.bytes); if (rc) { cleanup(); return rc; } }
+        if (u.src) { const int rc = mipt::upload_staged(*u.dst, u.src, u.bytes); if (rc) return rc; }
     }
     m->streams = 1u + (m->d_idx[1] ? 1u : 0u) + (m->d_idx[2] ? 1u : 0u);
     if (!m->d_idx[1]) m->d_idx[1] = m->d_idx[0];
     if (!m->d_idx[2]) m->d_idx[2] = m->d_idx[0];
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_rec[0], rec_b));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_rec[1], rec_b));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_flag, 4));
+    MIPT_HIP(hipMalloc((void **)&m->d_rec[0], rec_b));
+    MIPT_HIP(hipMalloc((void **)&m->d_rec[1], rec_b));
+    MIPT_HIP(hipMalloc((void **)&m->d_flag, 4));
     m->array_bytes += 2 * rec_b + 4;
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&m->d_expanded, exp_b));
+    MIPT_HIP(hipMalloc((void **)&m->d_expanded, exp_b));
     const double t_up = now_ms();
     // ---- expansion; a position index out of range ends the call here ----
-    MIPT_HIP_OR(cleanup(), hipMemset(m->d_flag, 0xff, 4));
+    MIPT_HIP(hipMemset(m->d_flag, 0xff, 4));
     float expand_ms = 0.0f;
     {
-        ExpandTimer tm;
-        MIPT_HIP_OR(cleanup(), queue_expand(m, nullptr, nullptr, mesh->transforms ? m->d_xf_stage : nullptr, true, 0, nullptr, &tm));
+        mipt::Event e0, e1;
+        MIPT_HIP(queue_expand(m, nullptr, nullptr, mesh->transforms ? m->d_xf_stage : nullptr, true, 0, nullptr, e0, e1));
         uint32_t bad = kNoIndex;
-        MIPT_HIP_OR(cleanup(), hipMemcpy(&bad, m->d_flag, 4, hipMemcpyDeviceToHost));      // null stream: after the kernels
-        (void)hipEventElapsedTime(&expand_ms, tm.e0, tm.e1);
+        MIPT_HIP(hipMemcpy(&bad, m->d_flag, 4, hipMemcpyDeviceToHost));      // null stream: after the kernels
+        (void)hipEventElapsedTime(&expand_ms, e0, e1);
         if (bad != kNoIndex) {
             uint32_t value = 0;
-            MIPT_HIP_OR(cleanup(), hipMemcpy(&value, m->d_idx[0] + bad, 4, hipMemcpyDeviceToHost));
-            cleanup();
+            MIPT_HIP(hipMemcpy(&value, m->d_idx[0] + bad, 4, hipMemcpyDeviceToHost));
             return bad_position_index(bad, value, mesh->n_positions);
         }
     }
     // ---- from here on it is mipt_scene_create_from_triangles with the triangles already in HBM ----
-    { const int rc = mipt::scene_create_from_resident_triangles(desc, m->d_expanded, m->n_tris, device_id, &s); if (rc) { s = nullptr; cleanup(); return rc; } }
+    MiptScene *s = nullptr;
+    { const int rc = mipt::scene_create_from_resident_triangles(desc, m->d_expanded, m->n_tris, device_id, &s); if (rc) return rc; }
+    scene_owner.reset(s);
     s->mesh = m;
     s->info.upload_ms += t_up - t_begin;
     s->info.build_ms += expand_ms;
     s->info.total_ms = now_ms() - t_begin;
-    *out = s;
+    sync.dismiss();
+    mesh_owner.release();                                                // the scene's from here on
+    *out = scene_owner.release();
     return MIPT_OK;
 }
 
@@ -337,24 +334,25 @@ int create_from_mesh(const MiptSceneDesc *desc, const MiptMeshDesc *mesh, int de
 // the REFIT / REBUILD, and only then the commit.  xf_change: 0 = keep the table, 1 = d_xf holds new matrices, 2 = back to none.
 int apply(MiptScene *s, const float *d_pos, const float *d_nrm, const float *d_xf, int xf_change, uint32_t mode, hipStream_t st, MiptUpdateInfo *inf) {
     SceneMesh *m = s->mesh;
-    auto cleanup = [&]() { (void)hipStreamSynchronize(st); };
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));                                      // ordered after the caller's earlier work on `st`
+    mipt::SyncOnExit sync(st);                                                            // a failure leaves nothing of this update queued on `st`
+    MIPT_HIP(hipStreamSynchronize(st));                                                    // ordered after the caller's earlier work on `st`
     const int rec = xf_change ? m->cur ^ 1 : m->cur;
     float expand_ms = 0.0f;
     {
-        ExpandTimer tm;
-        MIPT_HIP_OR(cleanup(), queue_expand(m, d_pos, d_nrm, xf_change == 1 ? d_xf : nullptr, xf_change != 0, rec, st, &tm));
-        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
-        (void)hipEventElapsedTime(&expand_ms, tm.e0, tm.e1);
+        mipt::Event e0, e1;
+        MIPT_HIP(queue_expand(m, d_pos, d_nrm, xf_change == 1 ? d_xf : nullptr, xf_change != 0, rec, st, e0, e1));
+        MIPT_HIP(hipStreamSynchronize(st));
+        (void)hipEventElapsedTime(&expand_ms, e0, e1);
     }
     { const int rc = mipt::scene_update_device(s, m->d_expanded, m->n_tris, mode, st, inf, true); if (rc) return rc; }
     // ---- commit ----
-    if (d_pos) MIPT_HIP_OR(cleanup(), hipMemcpyAsync(m->d_pos, d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
-    if (d_nrm) MIPT_HIP_OR(cleanup(), hipMemcpyAsync(m->d_nrm, d_nrm, (size_t)m->n_nrm * 12, hipMemcpyDeviceToDevice, st));
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+    if (d_pos) MIPT_HIP(hipMemcpyAsync(m->d_pos, d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
+    if (d_nrm) MIPT_HIP(hipMemcpyAsync(m->d_nrm, d_nrm, (size_t)m->n_nrm * 12, hipMemcpyDeviceToDevice, st));
+    MIPT_HIP(hipStreamSynchronize(st));
     m->cur = rec;
     if (xf_change) m->has_xf = xf_change == 1 ? 1u : 0u;
     inf->build_ms += expand_ms;
+    sync.dismiss();
     return MIPT_OK;
 }
 

@@ -13,9 +13,7 @@
 //           allocations; the old geometry is freed only after that succeeded.
 // Both run from triangles in HBM: the host entry stages its array into HBM first (one path, not two).
 #include "../../include/mipt.h"
-#include "mipt_internal.h"
-#include "mipt_scene.h"
-#include "mipt_host_util.h"
+#include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
 #include <hip/hip_runtime.h>
 
@@ -227,81 +225,74 @@ uint32_t grid_for(size_t n, uint32_t cap) {
 int ensure_plan(MiptScene *s, hipStream_t st) {
     if (!s->refit_level_off.empty() || s->dev.n_pairs == 0) return MIPT_OK;
     const uint32_t cap = s->dev.n_pairs;
-    uint32_t *plan = nullptr, *pair_of = nullptr, *lv = nullptr;
-    Ctl *ctl = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)plan, (void *)pair_of, (void *)lv, (void *)ctl}) if (p) (void)hipFree(p);
-    };
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&plan, (size_t)cap * 4));
-    if (s->d_nodes) MIPT_HIP_OR(cleanup(), hipMalloc((void **)&pair_of, (size_t)cap * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&lv, (size_t)(2 * kMaxLevels + 1) * 4));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&ctl, sizeof(Ctl)));
-    MIPT_HIP_OR(cleanup(), hipMemsetAsync(lv, 0, (size_t)(2 * kMaxLevels + 1) * 4, st));
-    MIPT_HIP_OR(cleanup(), hipMemsetAsync(ctl, 0, sizeof(Ctl), st));
-    MIPT_HIP_OR(cleanup(), hipMemsetAsync(plan, 0, 4, st));                             // level 0 = { record 0 } (pair 0)
-    if (pair_of) MIPT_HIP_OR(cleanup(), hipMemsetAsync(pair_of, 0, 4, st));
+    mipt::DevPtr<uint32_t> plan, pair_of, lv;
+    mipt::DevPtr<Ctl> ctl;
+    mipt::SyncOnExit sync(st);                                           // a failure waits for the queued kernels before the buffers go
+    MIPT_HIP(plan.alloc(cap));
+    if (s->d_nodes) MIPT_HIP(pair_of.alloc(cap));
+    MIPT_HIP(lv.alloc(2 * kMaxLevels + 1));
+    MIPT_HIP(ctl.alloc(1));
+    MIPT_HIP(hipMemsetAsync(lv, 0, (size_t)(2 * kMaxLevels + 1) * 4, st));
+    MIPT_HIP(hipMemsetAsync(ctl, 0, sizeof(Ctl), st));
+    MIPT_HIP(hipMemsetAsync(plan, 0, 4, st));                             // level 0 = { record 0 } (pair 0)
+    if (pair_of) MIPT_HIP(hipMemsetAsync(pair_of, 0, 4, st));
     {
         const uint32_t one = 1;
-        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(lv, &one, 4, hipMemcpyHostToDevice, st));
-        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+        MIPT_HIP(hipMemcpyAsync(lv, &one, 4, hipMemcpyHostToDevice, st));
+        MIPT_HIP(hipStreamSynchronize(st));
     }
     std::vector<uint32_t> h_lv(2 * kMaxLevels + 1);
     uint32_t depth = 0;
     for (;;) {                                                          // batches of levels, then one look at the next level's size
         for (int b = 0; b < 16 && depth + 1 < kMaxLevels; b++, depth++)
             hipLaunchKernelGGL(plan_level, dim3(1024), dim3(kT), 0, st, (const float4 *)s->dev.pairs, s->d_nodes, plan, pair_of, cap, lv, depth, ctl);
-        MIPT_HIP_OR(cleanup(), hipGetLastError());
-        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(h_lv.data(), lv, h_lv.size() * 4, hipMemcpyDeviceToHost, st));
-        MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+        MIPT_HIP(hipGetLastError());
+        MIPT_HIP(hipMemcpyAsync(h_lv.data(), lv, h_lv.size() * 4, hipMemcpyDeviceToHost, st));
+        MIPT_HIP(hipStreamSynchronize(st));
         if (h_lv[depth] == 0u) break;
-        if (depth + 1 >= kMaxLevels) { cleanup(); return fail(MIPT_ERR_BVH, "refit plan: tree deeper than %u levels", kMaxLevels); }
+        if (depth + 1 >= kMaxLevels) return fail(MIPT_ERR_BVH, "refit plan: tree deeper than %u levels", kMaxLevels);
     }
     Ctl hc;
-    MIPT_HIP_OR(cleanup(), hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
-    if (hc.overflow) { cleanup(); return fail(MIPT_ERR_BVH, "refit plan: more records reached than the scene holds (internal)"); }
-    (void)hipFree(lv); lv = nullptr;
-    (void)hipFree(ctl); ctl = nullptr;
+    MIPT_HIP(hipMemcpy(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost));
+    if (hc.overflow) return fail(MIPT_ERR_BVH, "refit plan: more records reached than the scene holds (internal)");
+    lv.reset();
+    ctl.reset();
     std::vector<uint32_t> off(depth + 1);                               // levels 0 .. depth-1 and the end
     for (uint32_t d = 0; d <= depth; d++) off[d] = h_lv[kMaxLevels + d];
-    s->d_refit_plan = plan;
-    s->d_refit_pair = pair_of;
+    s->d_refit_plan = plan.release();
+    s->d_refit_pair = pair_of.release();
     s->refit_level_off = std::move(off);
+    sync.dismiss();
     return MIPT_OK;
 }
 
 int refit(MiptScene *s, const MiptTriangle *d_tris, hipStream_t st, MiptUpdateInfo *inf) {
     const uint32_t n_tris = (uint32_t)s->n_tris, n_records = s->dev.n_pairs;
     { const int rc = ensure_plan(s, st); if (rc) return rc; }
-    float4 *scratch = nullptr;
-    uint32_t *big = nullptr;
-    Ctl *ctl = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)scratch, (void *)big, (void *)ctl}) if (p) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    MIPT_HIP_OR(cleanup(), hipEventCreate(&e0));
-    MIPT_HIP_OR(cleanup(), hipEventCreate(&e1));
-    MIPT_HIP_OR(cleanup(), hipMalloc((void **)&ctl, sizeof(Ctl)));
+    mipt::Event e0, e1;
+    mipt::DevPtr<float4> scratch;
+    mipt::DevPtr<uint32_t> big;
+    mipt::DevPtr<Ctl> ctl;
+    mipt::SyncOnExit sync(st);                                           // on every way out, success included: `st` is idle before the buffers go
+    MIPT_HIP(hipEventCreate(e0.put()));
+    MIPT_HIP(hipEventCreate(e1.put()));
+    MIPT_HIP(ctl.alloc(1));
     if (n_records) {
-        MIPT_HIP_OR(cleanup(), hipMalloc((void **)&scratch, (size_t)n_records * 64));
-        MIPT_HIP_OR(cleanup(), hipMalloc((void **)&big, (size_t)n_records * 2 * 4));
+        MIPT_HIP(scratch.alloc((size_t)n_records * 4));
+        MIPT_HIP(big.alloc((size_t)n_records * 2));
     }
     {
         Ctl h;
         memset(&h, 0, sizeof h);
         h.bad_tri = 0xffffffffu;
-        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
+        MIPT_HIP(hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
     }
     const float4 *pairs = s->dev.pairs, *tri_pos = s->dev.tri_pos;
     const uint32_t *order = s->d_tri_order;
-    MIPT_HIP_OR(cleanup(), hipEventRecord(e0, st));
+    MIPT_HIP(hipEventRecord(e0, st));
     hipLaunchKernelGGL(check_materials, dim3(grid_for(n_tris, 4096)), dim3(kT), 0, st, d_tris, n_tris, s->dev.n_mats, ctl);
     if (n_records) {
-        MIPT_HIP_OR(cleanup(), hipMemcpyAsync(scratch, pairs, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
+        MIPT_HIP(hipMemcpyAsync(scratch, pairs, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(refit_leaves, dim3(grid_for(n_records, 4096)), dim3(kT), 0, st, pairs, scratch, n_records, tri_pos, d_tris, order, big, ctl);
         hipLaunchKernelGGL(refit_big_leaves, dim3(1024), dim3(kT), 0, st, pairs, scratch, tri_pos, d_tris, order, big, ctl);
         const std::vector<uint32_t> &off = s->refit_level_off;
@@ -312,35 +303,33 @@ int refit(MiptScene *s, const MiptTriangle *d_tris, hipStream_t st, MiptUpdateIn
     }
     hipLaunchKernelGGL(refit_root, dim3(1), dim3(kT), 0, st, scratch, n_records ? 1u : 0u, s->dev.root_a, s->dev.root_n, tri_pos, d_tris, order, ctl);
     hipLaunchKernelGGL(check_bounds, dim3(grid_for(2 * (size_t)n_records + 1, 2048)), dim3(kT), 0, st, scratch, n_records, ctl);
-    MIPT_HIP_OR(cleanup(), hipGetLastError());
-    MIPT_HIP_OR(cleanup(), hipEventRecord(e1, st));
+    MIPT_HIP(hipGetLastError());
+    MIPT_HIP(hipEventRecord(e1, st));
     Ctl hc;
-    MIPT_HIP_OR(cleanup(), hipMemcpyAsync(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost, st));
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+    MIPT_HIP(hipMemcpyAsync(&hc, ctl, sizeof hc, hipMemcpyDeviceToHost, st));
+    MIPT_HIP(hipStreamSynchronize(st));
     float build_ms = 0.0f;
     (void)hipEventElapsedTime(&build_ms, e0, e1);
-    if (hc.bad_bound) { cleanup(); return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40"); }
+    if (hc.bad_bound) return fail(MIPT_ERR_SCENE_LIMIT, "a node has a non-finite bound or one beyond 2^40");
     if (hc.bad_tri != 0xffffffffu) {
         MiptTriangle t;
         const hipError_t e = hipMemcpy(&t, d_tris + hc.bad_tri, sizeof t, hipMemcpyDeviceToHost);
-        cleanup();
         if (e != hipSuccess) return fail(MIPT_ERR_HIP, "reading a triangle back: %s", hipGetErrorString(e));
         return fail(MIPT_ERR_INVALID_ARG, "triangle %u has material_id %u >= n_materials %u", hc.bad_tri, t.material_id, s->dev.n_mats);
     }
     // ---- commit: nothing below can fail on the data, only on the runtime ----
     const double t_commit = now_ms();
-    if (n_records) MIPT_HIP_OR(cleanup(), hipMemcpyAsync((void *)pairs, scratch, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
+    if (n_records) MIPT_HIP(hipMemcpyAsync((void *)pairs, scratch, (size_t)n_records * 64, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(rewrite_tris, dim3(grid_for(n_tris, 4096)), dim3(kT), 0, st, d_tris, order, n_tris, (float4 *)tri_pos, (float4 *)s->dev.tri_attr);
     if (s->d_nodes) {
         const uint32_t n_plan = s->refit_level_off.empty() ? 0u : s->refit_level_off.back();
         hipLaunchKernelGGL(refit_nodes, dim3(grid_for(n_plan, 2048)), dim3(kT), 0, st, scratch, s->d_refit_plan, n_plan, s->d_refit_pair, s->d_nodes, ctl);
     }
-    MIPT_HIP_OR(cleanup(), hipGetLastError());
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(st));
+    MIPT_HIP(hipGetLastError());
+    MIPT_HIP(hipStreamSynchronize(st));
     s->dev.tiny_axes = hc.tiny_axes;
     inf->build_ms = build_ms;
     inf->layout_ms = now_ms() - t_commit;
-    cleanup();
     return MIPT_OK;
 }
 
@@ -348,13 +337,11 @@ int rebuild(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, MiptUpdat
     mipt::ResidentBvh bvh;
     mipt::SceneGeometry geo;
     const int rc = mipt::build_geometry(d_tris, n_tris, s->dev.n_mats, s->device, false, &bvh, &geo);
-    if (bvh.d_nodes) (void)hipFree(bvh.d_nodes);                      // left here only on failure
-    if (bvh.d_tri_order) (void)hipFree(bvh.d_tri_order);
-    if (rc) return rc;
+    if (rc) return rc;                                                // with what the build left in `bvh`
     const double t_build = geo.t_build;
     inf->build_ms = geo.build_ms;
     mipt::release_geometry(s);
-    mipt::attach_geometry(s, &geo);
+    mipt::attach_geometry(s, std::move(geo));
     s->info.built_on_device = 1u;
     inf->layout_ms = now_ms() - t_build;
     return MIPT_OK;
@@ -409,15 +396,15 @@ int mipt::scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_t
     { const int rc = check_args("mipt_scene_update_triangles", s, tris, n_tris, mode); if (rc) return rc; }
     if (s->mesh) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_update_triangles: scene owns a mesh (use mipt_scene_set_transforms / mipt_scene_update_mesh_device)");
     hipError_t e = hipSetDevice(s->device);
-    MiptTriangle *d_tris = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tris, (size_t)n_tris * sizeof(MiptTriangle));
+    mipt::DevPtr<MiptTriangle> d_tris;
+    if (e == hipSuccess) e = d_tris.alloc(n_tris);
     if (e != hipSuccess) return fail(MIPT_ERR_HIP, "mipt_scene_update_triangles: %s", hipGetErrorString(e));
     int rc = mipt::upload_staged(d_tris, tris, (size_t)n_tris * sizeof(MiptTriangle));
     const double t_up = now_ms();
     MiptUpdateInfo inf{};
     if (rc == MIPT_OK) rc = mipt::scene_update_device(s, d_tris, n_tris, mode, nullptr, &inf, false);
     (void)hipSetDevice(s->device);
-    (void)hipFree(d_tris);
+    d_tris.reset();
     if (rc) return rc;
     inf.upload_ms = t_up - t0;
     finish_info(s, &inf, t0);
@@ -430,8 +417,8 @@ int mipt::scene_update_host(MiptScene *s, const MiptTriangle *tris, uint32_t n_t
 int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
     const int device = dst->device;
     SceneGeometry g;
-    auto cleanup = [&]() { (void)hipSetDevice(device); (void)hipStreamSynchronize(nullptr); free_geometry(&g); };
-    MIPT_HIP_OR(cleanup(), hipSetDevice(device));
+    mipt::SyncOnExit sync(nullptr, device);                              // a failed copy: the others are waited for before g's buffers go
+    MIPT_HIP(hipSetDevice(device));
     if (device != src->device) {
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, device, src->device) == hipSuccess && can) {
@@ -440,21 +427,21 @@ int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
         }
     }
     struct Part { void **dst; const void *from; size_t alloc, copy; };
-    const Part parts[] = {{&g.d_geom, src->d_geom, src->geom_alloc, (size_t)src->dev.geom_bytes},
-                          {&g.d_tri_attr, src->d_tri_attr, src->attr_bytes < 16 ? 16 : src->attr_bytes, src->attr_bytes},
-                          {(void **)&g.d_nodes, src->d_nodes, (size_t)src->n_nodes * sizeof(MiptNode), (size_t)src->n_nodes * sizeof(MiptNode)},
-                          {(void **)&g.d_tri_order, src->d_tri_order, src->n_tris * 4, src->n_tris * 4}};
+    const Part parts[] = {{(void **)g.d_geom.put(), src->d_geom, src->geom_alloc, (size_t)src->dev.geom_bytes},
+                          {(void **)g.d_tri_attr.put(), src->d_tri_attr, src->attr_bytes < 16 ? 16 : src->attr_bytes, src->attr_bytes},
+                          {(void **)g.d_nodes.put(), src->d_nodes, (size_t)src->n_nodes * sizeof(MiptNode), (size_t)src->n_nodes * sizeof(MiptNode)},
+                          {(void **)g.d_tri_order.put(), src->d_tri_order, src->n_tris * 4, src->n_tris * 4}};
     for (const Part &p : parts) {
         if (!p.from) continue;
-        MIPT_HIP_OR(cleanup(), hipMalloc(p.dst, p.alloc ? p.alloc : 16));
-        if (p.copy) MIPT_HIP_OR(cleanup(), hipMemcpyPeerAsync(*p.dst, device, p.from, src->device, p.copy, nullptr));
+        MIPT_HIP(hipMalloc(p.dst, p.alloc ? p.alloc : 16));
+        if (p.copy) MIPT_HIP(hipMemcpyPeerAsync(*p.dst, device, p.from, src->device, p.copy, nullptr));
     }
-    MIPT_HIP_OR(cleanup(), hipStreamSynchronize(nullptr));
+    MIPT_HIP(hipStreamSynchronize(nullptr));
     release_geometry(dst);
     dst->n_tris = src->n_tris; dst->n_nodes = src->n_nodes; dst->max_leaf = src->max_leaf;
     dst->geom_alloc = src->geom_alloc; dst->attr_bytes = src->attr_bytes;
-    dst->d_geom = g.d_geom; dst->d_tri_attr = g.d_tri_attr; dst->d_nodes = g.d_nodes; dst->d_tri_order = g.d_tri_order;
-    g = SceneGeometry();
+    dst->d_geom = g.d_geom.release(); dst->d_tri_attr = g.d_tri_attr.release(); dst->d_nodes = g.d_nodes.release(); dst->d_tri_order = g.d_tri_order.release();
+    sync.dismiss();
     mipt::DevScene d = src->dev;                                          // sizes, root, tiny_axes; this replica's own buffers
     d.pairs = (const float4 *)dst->d_geom;
     d.tri_pos = (const float4 *)((const char *)dst->d_geom + src->dev.tri_off_bytes);

@@ -109,6 +109,18 @@ def test_host_code_under_asan_ubsan(built, tmp_path):
     assert out.returncode == 0 and "WARNING: ThreadSanitizer" not in out.stderr, out.stdout + out.stderr[-3000:]
 
 
+def test_owned_guard_under_asan_ubsan(tmp_path):
+    """mipt::Owned (mipt_internal.h), the owner of every device buffer, stream and event a libmipt function holds for the length
+    of a call, over a counting release function: one release per handle, none for an empty or moved-from owner, reverse
+    declaration order, also when an exception leaves the scope (tests/cpp/owned_guard.cpp)."""
+    exe = str(tmp_path / "owned_guard")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "owned_guard.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    assert "owned_guard ok" in out.stdout
+
+
 def test_oracle_under_asan_ubsan(built, tmp_path):
     """The oracle itself (test infrastructure) under ASan/UBSan: a small render through a standalone driver."""
     drv = tmp_path / "drv.c"

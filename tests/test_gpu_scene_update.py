@@ -370,6 +370,81 @@ def test_sequences_and_memory(rrt):
     assert free0 - free1 < geom, f"{(free0 - free1) / 2**20:.1f} MiB more in use after 21 updates (geometry: {geom / 2**20:.1f} MiB)"
 
 
+def test_failed_calls_give_their_memory_back(rrt):
+    """Every call the library refuses -- by a check in its own kernels or host code, late enough that its device buffers exist --
+    frees what it allocated: after eight refusals of each kind free device memory has fallen by less than ONE triangle array
+    (n_tris x 112 B; a call that kept its triangles, or any of its larger builder buffers, would lose that much per call)."""
+    import torch
+    import mesh_model
+    from rust_ray_tracing_amd import _lib as L
+    from rust_ray_tracing_amd import synth
+    lib = rrt.load()
+    tris, mats, texs, cam = synth.make_scene("atrium", n_target=200000, tex_size=16)
+    sc = rrt.Scene.from_arrays(tris, mats, texs, build_bvh=False)
+    h = sc.upload_from_triangles(0)                                    # tris stay in the caller's order
+    good = sc.tris.copy()
+    n, one_array = len(good), len(good) * 112
+    bad_mat, far = good.copy(), good.copy()
+    bad_mat["material_id"][n // 2] = len(mats)
+    far["vertices"]["position"][n // 3, 1, 0] = np.float32(3e12)
+    mesh, _ = mesh_model.mesh_from_triangles(good, 6)
+    bad_mesh = dict(mesh, indices=mesh["indices"].copy())
+    bad_mesh["indices"][bad_mesh["indices"].size // 2] = len(mesh["positions"])
+    nodes = np.zeros(2 * n, dtype=L.NODE)
+    n_nodes = C.c_uint32(0)
+
+    def create(t):
+        s = rrt.Scene.from_arrays(t, mats, texs, build_bvh=False)
+        d, out = s.desc(), C.c_void_p(0x1234)
+        rc = lib.mipt_scene_create_from_triangles(C.byref(d), 0, C.byref(out))
+        assert rc != 0 and out.value is None
+        return rc
+
+    def create_mesh():
+        s = rrt.Scene.from_mesh(materials=mats, textures=texs, **bad_mesh)
+        d, md, out = s.desc(), s.mesh_desc(), C.c_void_p(0x1234)
+        rc = lib.mipt_scene_create_from_mesh(C.byref(d), C.byref(md), 0, C.byref(out))
+        assert rc != 0 and out.value is None
+        return rc
+
+    def build(cap):
+        t = good.copy()                                                # a successful build reorders its triangles in place
+        return lib.mipt_bvh_build_device(L.ptr(t), n, L.ptr(nodes), cap, C.byref(n_nodes), 0, None)
+
+    # every kind of call once with success first: what a process pays once (streams, kernels, the scene's cached REFIT plan) is paid
+    warm = rrt.Scene.from_arrays(good, mats, texs, build_bvh=False)
+    warm.upload_from_triangles(0)
+    warm.release()
+    warm = rrt.Scene.from_mesh(materials=mats, textures=texs, **mesh)
+    warm.upload_from_mesh(0)
+    warm.release()
+    assert build(len(nodes)) == 0, lib.mipt_last_error()
+    cap_short = n_nodes.value - 1
+    assert lib.mipt_scene_update_triangles(h, L.ptr(good), n, 1, None) == 0, lib.mipt_last_error()
+    assert lib.mipt_scene_update_triangles(h, L.ptr(good), n, 0, None) == 0, lib.mipt_last_error()
+    cases = [
+        ("create, material_id out of range", lambda: create(bad_mat), L.ERR_INVALID_ARG, b"material_id"),
+        ("create, coordinate 3e12", lambda: create(far), L.ERR_SCENE_LIMIT, b"2^40"),
+        ("REFIT, material_id out of range", lambda: lib.mipt_scene_update_triangles(h, L.ptr(bad_mat), n, 0, None), L.ERR_INVALID_ARG, b"material_id"),
+        ("REBUILD, material_id out of range", lambda: lib.mipt_scene_update_triangles(h, L.ptr(bad_mat), n, 1, None), L.ERR_INVALID_ARG, b"material_id"),
+        ("REFIT, coordinate 3e12", lambda: lib.mipt_scene_update_triangles(h, L.ptr(far), n, 0, None), L.ERR_SCENE_LIMIT, b"2^40"),
+        ("REBUILD, coordinate 3e12", lambda: lib.mipt_scene_update_triangles(h, L.ptr(far), n, 1, None), L.ERR_SCENE_LIMIT, b"2^40"),
+        ("create from mesh, position index out of range", create_mesh, L.ERR_INVALID_ARG, b"index entry"),
+        ("mipt_bvh_build_device, nodes_cap one short", lambda: build(cap_short), L.ERR_INVALID_ARG, b"nodes_cap"),
+    ]
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    for what, call, status, words in cases:
+        for _ in range(8):
+            rc = call()
+            assert rc == status and words in lib.mipt_last_error(), (what, rc, lib.mipt_last_error())
+        torch.cuda.synchronize()
+        lost = free0 - torch.cuda.mem_get_info(0)[0]
+        print(f"{what}: {lost / 2**20:.1f} MiB less free than at the start (one triangle array: {one_array / 2**20:.1f} MiB)")
+        assert lost < one_array, f"{what}: {lost / 2**20:.1f} MiB lost after 8 refused calls (one triangle array: {one_array / 2**20:.1f} MiB)"
+    assert lib.mipt_scene_update_triangles(h, L.ptr(good), n, 0, None) == 0, lib.mipt_last_error()   # and the scene still takes an update
+
+
 @pytest.mark.parametrize("ranks", [2, 3])
 @pytest.mark.parametrize("from_triangles", [True, False])
 def test_multi_replicas_follow_the_root(rrt, ranks, from_triangles):
