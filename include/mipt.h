@@ -295,6 +295,81 @@ MIPT_API int mipt_query_occluded(MiptScene *scene, const MiptRay *rays, uint64_t
 MIPT_API int mipt_query_occluded_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt,
                                         uint8_t *d_occluded, void *hip_stream, MiptStats *stats);
 
+/* ---- first-hit feature buffers: depth, ids, position, uv, normal, albedo, emission per pixel --------------------------------------
+ * What the camera ray of every pixel hits and what the surface looks like there: the guide images of a denoiser, the id and depth
+ * planes of a compositor, G-buffers for training data (csrc/first_hit.hip).  No path is traced: a sample ends at its first hit.
+ *
+ * Camera ray.  The camera ray of sample s of a pixel is exactly the ray mipt_render traces first for that sample with the same opt:
+ * cpu.rs:28-50 with MIPT_SEED_PIXEL_STREAM (seed 987612486 * (index + 87636354), cpu.rs:28-29; y flip of cpu.rs:32); with
+ * MIPT_SEED_PER_SAMPLE the stream is reseeded per sample as rt_compute.wgsl:102 does (sample_begin normalised 0 -> 1 as in
+ * mipt_render).  The arithmetic is the trace kernel's: two rand_f32 draws, * 2 - 1, * 0.0005 (cpu.rs:38-42), the upper 3x3 of
+ * look_at in the operation order of mat4.rs:143-152, normalized (cpu.rs:43-45), origin = camera position.
+ *
+ * Samples.  With MIPT_SEED_PER_SAMPLE opt->samples camera rays are traced per pixel, the samples sample_begin ... sample_begin +
+ * samples - 1, which are independent of each other.  With MIPT_SEED_PIXEL_STREAM a pixel's second camera ray depends on how many
+ * numbers the first sample's whole path drew (cpu.rs:37-58): only the first is defined without path tracing, so samples must be 1
+ * (anything else: MIPT_ERR_INVALID_ARG with a message that says why).
+ *
+ * Hit.  Ray::traverse_bvh (ray.rs:84-139) with hit_info.distance = 1e30 in the arm opt->traversal / opt->cull_margin select:
+ * exactly what mipt_query_closest returns for that ray.
+ *
+ * Per-sample values of a hit -- the fields intersect_tri (ray.rs:19-67) and trace (ray.rs:141-202) compute for the winner:
+ *   t         the hit distance
+ *   prim      MiptHit.prim: the triangle in the caller's order, bit 31 (MIPT_HIT_FRONT_FACE) = front face (ray.rs:39)
+ *   material  the triangle's material_id (ray.rs:153)
+ *   position  origin + direction * t (ray.rs:60)
+ *   uv        ray.rs:50-53
+ *   normal    ray.rs:45-48: interpolated, NOT normalised, reversed on a back face
+ *   albedo    the factor ray_color is multiplied by at ray.rs:162-169: base_color, or color_at(uv) / 255 from the base-colour texture
+ *   emission  the term added at ray.rs:170-176: emission, or color_at(uv) / 255 from the emission texture
+ * of a miss: t = 1e30, prim = MIPT_HIT_NONE, material = UINT32_MAX, position = uv = normal = 0 (HitInfo::default, ray.rs:214-226),
+ * albedo = (1,1,1) (sky_color, ray.rs:185) and emission = (1,1,1) (sky_strength, ray.rs:186).
+ *
+ * What is written.  depth (= t), prim, material, position and uv come from the FIRST sample of the call.  normal, albedo and
+ * emission are the MEAN over the samples, formed as final_color is (cpu.rs:30,52,60): the sum starts at +0.0f, the samples are added
+ * in order and the sum is divided by `samples as f32` once at the end -- also for one sample, so a -0 comes out as +0.  One
+ * rounded f32 operation per operator, nothing fused.  The NaN rule of the query section applies: a NaN this arithmetic produces is
+ * a NaN everywhere, and its sign and payload are the implementation's.
+ *
+ * Layout.  View-major, row 0 = top, exactly like mipt_render_batch: view v occupies [v*W*H*k, (v+1)*W*H*k) of a buffer with k
+ * values per pixel.  n_views == 1 is the ordinary single frame; `cameras` are in HOST memory, read during the call only.  Any
+ * buffer pointer may be NULL = not wanted (nothing is computed or fetched for it, and it is never written); at least one must be set.
+ *
+ * Options.  Honoured: width, height, samples, seed_mode, sample_begin, traversal, cull_margin.  max_ray_depth must be > 0 and is
+ * otherwise ignored.  flags: MIPT_FLAG_COUNT only.  tile_world must be 0 or 1 (tile_rank 0).  shading must be MIPT_SHADING_CPU:
+ * the first hit of the wgpu material model (normal maps, bilinear sampler, cut-outs) is out of scope and refused.  reserved must be
+ * zero.  n_views >= 1 and n_views*W*H < MIPT_BATCH_MAX_PIXELS.
+ *
+ * Stats (may be NULL).  Always: kernel_ms, stack_overflows, tex_clamped, pixels = n_views*W*H.  With MIPT_FLAG_COUNT also rays,
+ * inner_steps, tri_tests, hits, texel_fetches, max_stack.  A texture is fetched only for a buffer that is wanted, so texel_fetches
+ * counts the fetches actually made.  Every other field 0.
+ *
+ * Errors.  Every argument is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names
+ * the offending field -- a null scene, cameras, opt or buffers; no buffer wanted; a non-NULL reserved pointer; any option rule
+ * above; for the _device entry a wanted pointer that is not 4-byte aligned or not device memory of the scene's device.  A
+ * traversal-stack overflow is MIPT_ERR_STACK after the buffers are written, as in mipt_render.  After any error the scene renders
+ * and queries as before.  Both entries work on a replica handle from mipt_multi_scene and see the geometry of the last successful
+ * update. */
+typedef struct {
+    float    *depth;      /* 1 f32  / pixel */
+    uint32_t *prim;       /* 1 u32  / pixel, MiptHit.prim convention */
+    uint32_t *material;   /* 1 u32  / pixel */
+    float    *position;   /* 3 f32 */
+    float    *uv;         /* 2 f32 */
+    float    *normal;     /* 3 f32 */
+    float    *albedo;     /* 3 f32 */
+    float    *emission;   /* 3 f32 */
+    void     *reserved[4];/* must be NULL */
+} MiptFeatureBuffers;     /* 96 B; any pointer may be NULL = not wanted; at least one must be set */
+
+/* Into HOST buffers; blocks until done. */
+MIPT_API int mipt_render_features(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                  const MiptFeatureBuffers *host_out, MiptStats *stats);
+/* Into DEVICE buffers (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream); the camera table is copied on that
+ * stream.  Blocks until the kernel has finished (stats are read back), like mipt_render_batch_device. */
+MIPT_API int mipt_render_features_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                         const MiptFeatureBuffers *device_out, void *hip_stream, MiptStats *stats);
+
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);
 /* d_packed_all: tile_world slices of mipt_packed_pixels()*3 floats, rank-major (the layout an

@@ -81,6 +81,35 @@ inline int query_occluded_on(MiptScene *scene, const std::vector<MiptRay> &rays,
     return rc;
 }
 
+// mipt_render_features on any resident scene handle: first-hit feature buffers (include/mipt.h "first-hit feature buffers") for
+// `cameras` with `opt`.  `wanted`: FeatureBit flags; only those images are computed and filled, each view-major [view][row][column][k]
+// with row 0 the top row; the others are left empty.  MIPT_ERR_STACK leaves the images written.
+enum FeatureBit : uint32_t {
+    FEATURE_DEPTH = 1u << 0, FEATURE_PRIM = 1u << 1, FEATURE_MATERIAL = 1u << 2, FEATURE_POSITION = 1u << 3,
+    FEATURE_UV = 1u << 4, FEATURE_NORMAL = 1u << 5, FEATURE_ALBEDO = 1u << 6, FEATURE_EMISSION = 1u << 7, FEATURE_ALL = 0xffu
+};
+struct FeatureImages {
+    uint32_t n_views = 0, width = 0, height = 0;
+    std::vector<float> depth;                              // 1 f32 / pixel; 1e30f = miss
+    std::vector<uint32_t> prim, material;                  // MiptHit.prim convention (MIPT_HIT_NONE = miss); material_id (UINT32_MAX = miss)
+    std::vector<float> position, uv, normal, albedo, emission;   // 3, 2, 3, 3, 3 f32 / pixel
+};
+inline int render_features_on(MiptScene *scene, const std::vector<MiptCamera> &cameras, const MiptOptions &opt, uint32_t wanted,
+                              FeatureImages &out, MiptStats *stats = nullptr) {
+    const uint64_t n_pix = (uint64_t)cameras.size() * opt.width * opt.height;
+    const size_t n = n_pix < MIPT_BATCH_MAX_PIXELS ? (size_t)n_pix : 0;      // an impossible size is left to the library to refuse
+    out.n_views = (uint32_t)cameras.size(); out.width = opt.width; out.height = opt.height;
+    MiptFeatureBuffers b{};
+    auto take = [&](auto &v, uint32_t bit, size_t k) { v.assign((wanted & bit) ? (n ? n * k : 1) : 0, 0); return (wanted & bit) ? v.data() : nullptr; };
+    b.depth = take(out.depth, FEATURE_DEPTH, 1); b.prim = take(out.prim, FEATURE_PRIM, 1); b.material = take(out.material, FEATURE_MATERIAL, 1);
+    b.position = take(out.position, FEATURE_POSITION, 3); b.uv = take(out.uv, FEATURE_UV, 2); b.normal = take(out.normal, FEATURE_NORMAL, 3);
+    b.albedo = take(out.albedo, FEATURE_ALBEDO, 3); b.emission = take(out.emission, FEATURE_EMISSION, 3);
+    static const MiptCamera no_camera{};
+    const int rc = mipt_render_features(scene, cameras.empty() ? &no_camera : cameras.data(), (uint32_t)cameras.size(), &opt, &b, stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -309,6 +338,24 @@ class Renderer {                                           // src/renderer.rs:8-
                 log_error(mipt_last_error());
         }
         return out;
+    }
+
+    // First-hit feature buffers of the frame(s) this renderer would render (mipt_render_features): `cameras` empty = the scene's camera;
+    // `wanted`: FeatureBit flags.  Width, height, samples, max_ray_depth and traversal are this renderer's options; seed_mode is a
+    // MiptSeedMode (more than one sample needs MIPT_SEED_PER_SAMPLE).  Runs on the root replica of the scene's device residency
+    // (created on first use, like render_node's).  Returns a MiptStatus.
+    int render_features(const Scene &scene, const std::vector<MiptCamera> &cameras, uint32_t wanted, FeatureImages &out,
+                        uint32_t seed_mode = MIPT_SEED_PIXEL_STREAM, uint32_t flags = 0, MiptStats *stats = nullptr) const {
+        if (options.backend != RendererBackend::MI355X) { log_error("this build only provides RendererBackend::MI355X"); return MIPT_ERR_INVALID_ARG; }
+        MiptOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.samples = (uint32_t)options.samples; o.max_ray_depth = (uint32_t)options.max_ray_depth;
+        o.seed_mode = seed_mode; o.flags = flags;
+        o.traversal = options.traversal; o.cull_margin = MIPT_CULL_MARGIN_SAFE;
+        const std::vector<MiptCamera> own{scene.camera.uniform};
+        const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
+        MiptMulti *m = scene.node_handle(1);
+        return m ? render_features_on(mipt_multi_scene(m, 0), cams, o, wanted, out, stats) : MIPT_ERR_HIP;
     }
 
     // The same arm over EVERY GPU of the node from this single-threaded host (mipt_render_multi: scene replicas, RCCL

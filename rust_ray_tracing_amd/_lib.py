@@ -99,6 +99,17 @@ class MiptQueryOptions(C.Structure):
     _fields_ = [("traversal", C.c_uint32), ("cull_margin", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+# ---- first-hit feature buffers (include/mipt.h "first-hit feature buffers") ----
+FEATURES = (("depth", 1, np.float32), ("prim", 1, np.uint32), ("material", 1, np.uint32), ("position", 3, np.float32),
+            ("uv", 2, np.float32), ("normal", 3, np.float32), ("albedo", 3, np.float32), ("emission", 3, np.float32))   # name, values per pixel, type
+
+
+class MiptFeatureBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in FEATURES] + [("reserved", C.c_void_p * 4)]
+
+
+assert C.sizeof(MiptFeatureBuffers) == 96
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -146,6 +157,7 @@ EXPORTS = [
     "mipt_scene_update_triangles", "mipt_scene_update_triangles_device", "mipt_multi_update_triangles",
     "mipt_render_batch", "mipt_render_batch_device",
     "mipt_query_closest", "mipt_query_closest_device", "mipt_query_occluded", "mipt_query_occluded_device",
+    "mipt_render_features", "mipt_render_features_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
 ]
 
@@ -270,6 +282,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_query_occluded.restype = C.c_int
     lib.mipt_query_occluded_device.argtypes = [vp, vp, u64, qo, vp, vp, C.POINTER(MiptStats)]
     lib.mipt_query_occluded_device.restype = C.c_int
+    fb = C.POINTER(MiptFeatureBuffers)
+    lib.mipt_render_features.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, C.POINTER(MiptStats)]
+    lib.mipt_render_features.restype = C.c_int
+    lib.mipt_render_features_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_features_device.restype = C.c_int
     return lib
 
 

@@ -1,7 +1,7 @@
 // mipt_scene.h -- the device-resident scene behind the opaque MiptScene handle, shared by the translation units that build, change
 // and use it -- mipt_api.cpp (host checks, materials, replicas, renders), scene_device.hip (tree and layout built on the GPU),
 // bvh_build_device.hip (the builder), scene_update.hip (refit / rebuild), scene_mesh.hip (the resident mesh), mipt_query.cpp (ray
-// queries), mipt_multi.cpp (one replica per GPU) -- and by the test library's checksum hook (tests/cpp/scene_hooks.hip,
+// queries), mipt_features.cpp (first-hit feature buffers), mipt_multi.cpp (one replica per GPU) -- and by the test library's checksum hook (tests/cpp/scene_hooks.hip,
 // libmipt_diag.so).  Internal: HIP types, not part of include/mipt.h.  At the end, the launch scaffold of the traversal kernels, which
 // works on a scene's workspace.
 #pragma once
@@ -127,8 +127,9 @@ int upload_staged(void *d_dst, const void *h_src, size_t bytes);
 int scene_update_device(MiptScene *s, const MiptTriangle *d_tris, uint32_t n_tris, uint32_t mode, hipStream_t stream, MiptUpdateInfo *info,
                         bool expanded_mesh = false);
 
-// ---- the launch scaffold of the traversal kernels (mipt_api.cpp: the trace kernels; mipt_query.cpp: the ray queries) ----
-// Renders and queries of one scene share its workspace: d_stats, the events and the spill slots of the traversal stack (d_ovf, one
+// ---- the launch scaffold of the traversal kernels (mipt_api.cpp: the trace kernels; mipt_query.cpp: the ray queries;
+// mipt_features.cpp: the first-hit feature pass) ----
+// Renders, queries and feature passes of one scene share its workspace: d_stats, the events and the spill slots of the traversal stack (d_ovf, one
 // set per wave of the grid).  These two functions are the only code that sizes, grows and hands out that workspace.
 //
 // The grid of a launch: n_cu x blocks_per_cu blocks, at most ceil(work / kBlockThreads), at least 1; the scene's spill slots are

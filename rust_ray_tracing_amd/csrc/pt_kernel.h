@@ -119,6 +119,27 @@ struct DevQuery {
 hipError_t launch_ray_query(const DevScene &sc, const DevQuery &q, bool count, bool cull, bool anyhit, int grid_blocks, hipStream_t stream);
 int query_blocks_per_cu(bool count, bool cull, bool anyhit);                 // occupancy query
 
+// ---- first-hit feature buffers (first_hit.hip; mipt_render_features*) ----
+struct DevFeatures {
+    const float4 *cams;                     // n_views x 64 B, the records of DevBatch::cams
+    // planar outputs, view-major, NULL = not wanted: 1, 1, 1, 3, 2, 3, 3, 3 words per pixel
+    float *depth; uint32_t *prim; uint32_t *material; float *position; float *uv; float *normal; float *albedo; float *emission;
+    const uint32_t *tri_order;              // tree order -> the caller's order (the scene's d_tri_order); NULL = they are the same
+    uint32_t width, height, samples, seed_mode;
+    uint32_t sample_begin;                  // first sample number (already normalised 0 -> 1)
+    uint32_t tiles_x, n_tiles;              // 8x8 tiles per row / per view
+    uint32_t tiles_recip;                   // floor((2^32 - 1) / n_tiles), as DevBatch::tiles_recip
+    uint32_t view_pixels;                   // width * height
+    unsigned long long total_work;          // n_views * n_tiles * 64
+    float aspect;                           // width as f32 / height as f32 (cpu.rs:34)
+    float samples_f;                        // samples as f32 (cpu.rs:60)
+    float cull_scale;                       // 1 + cull_margin
+    uint32_t *ovf;                          // traversal-stack overflow area [wave][entry][lane]
+    DevStats *stats;                        // zeroed before the launch; `queue` hands out the work indices
+};
+hipError_t launch_first_hit(const DevScene &sc, const DevFeatures &f, bool count, bool cull, int grid_blocks, hipStream_t stream);
+int first_hit_blocks_per_cu(bool count, bool cull);                          // occupancy query
+
 // number of set bits in words [0, n_words) of `bitmap`, added to *out (a device counter)
 hipError_t launch_popcount(const uint32_t *bitmap, unsigned long long n_words, unsigned long long *out, hipStream_t stream);
 hipError_t launch_divide(float *hdr, unsigned long long n_floats, float divisor, hipStream_t stream);

@@ -718,6 +718,59 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = st.as_dict()
         return hdr, rgba, self.last_stats
 
+    def render_features(self, scene: Scene, cameras=None, features=("depth", "normal", "albedo"), device: bool = False, stream=None,
+                        flags: int = 0, handle=None):
+        """First-hit feature buffers (mipt_render_features / _device): per pixel what the camera ray hits and what the surface looks
+        like there, with this renderer's width, height, samples, seed mode and traversal.  ``cameras``: a sequence of Camera (or CAMERA
+        records), None = the scene's camera.  ``features``: names out of depth, prim, material, position, uv, normal, albedo, emission;
+        only these are computed.  Returns ({name: array}, stats): numpy arrays [V,H,W] or [V,H,W,k] (depth / position / uv / normal /
+        albedo / emission float32, prim / material uint32 -- prim as MiptHit.prim: bit 31 = front face, HIT_NONE = miss), or with
+        ``device=True`` torch tensors of the same shapes on the scene's device (prim / material int32, the same bits), written on
+        ``stream`` (a torch stream, a raw hipStream_t or None = torch's current stream).  ``handle``: another resident handle of the
+        scene on ``options.device_id``, e.g. a replica of ``upload_multi``.  A stack overflow leaves the buffers written (stats["stack_overflows"] > 0)."""
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        known = {name: (k, dt) for name, k, dt in L.FEATURES}
+        names = list(features)
+        if not names or len(set(names)) != len(names) or any(n not in known for n in names):
+            raise ValueError(f"features: expected distinct names out of {', '.join(known)}; got {features!r}")
+        cams = [scene.camera] if cameras is None else list(cameras)
+        if not cams:
+            raise ValueError("render_features: no cameras")
+        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        n = len(cams)
+        w, h = o.output_image_dimensions
+        hnd = handle if handle is not None else scene.upload(o.device_id)
+        opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, cull_margin=o.cull_margin, shading=o.shading)
+        bufs, out = L.MiptFeatureBuffers(), {}
+        st = L.MiptStats()
+        lib = L.load()
+        if device:
+            import torch
+            dev = torch.device("cuda", o.device_id)
+            for name in names:
+                k, dt = known[name]
+                out[name] = torch.empty((n, h, w) + ((k,) if k > 1 else ()), dtype=torch.float32 if dt is np.float32 else torch.int32, device=dev)
+                setattr(bufs, name, out[name].data_ptr())
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            rc = lib.mipt_render_features_device(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), stream, C.byref(st))
+            where = "mipt_render_features_device"
+        else:
+            for name in names:
+                k, dt = known[name]
+                out[name] = np.zeros((n, h, w) + ((k,) if k > 1 else ()), dtype=dt)
+                setattr(bufs, name, out[name].ctypes.data)
+            rc = lib.mipt_render_features(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
+            where = "mipt_render_features"
+        if rc != L.ERR_STACK:
+            L.check(rc, where)
+        self.last_stats = st.as_dict()
+        return out, self.last_stats
+
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
                              want_rgba8: bool = True, flags: int = 0):
         """The same arm over all GPUs of the node in one call (mipt_render_multi): image tiles + one RCCL gather, or
