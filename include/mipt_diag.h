@@ -56,6 +56,17 @@ MIPT_DIAG_API int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uin
 MIPT_DIAG_API int mipt_debug_divide(float *d_buf, uint64_t n_floats, float divisor, void *stream);
 MIPT_DIAG_API int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words, uint64_t *d_out, void *stream);
 
+/* The tile order of the trace kernel (pt_kernel.hip "tile order"), for tests/test_gpu_tile_order.py.
+ *   mipt_debug_tile_order       the product's sort kernel on host arrays: order_out[] = the n_tiles tiles by decreasing cost[] --
+ *                               bucket min(1023, floor(cost * 16 / (64 * samples))) descending, tile index ascending within a bucket
+ *   mipt_diag_scene_tile_order  what a scene handle of libmipt.so keeps after its last plain single-view launch: info_out[0] = local
+ *                               tiles (0 = no valid state), [1] = the state is valid, [2] = that launch itself ran in the order made
+ *                               before it; with non-NULL buffers of `cap` words, that launch's rays per local tile and the order
+ *                               sorted from them.
+ * Return as mipt_debug_eval. */
+MIPT_DIAG_API int mipt_debug_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order_out);
+MIPT_DIAG_API int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *order_out, uint32_t cap, uint32_t info_out[3]);
+
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 
 /* The library-internal device-layout orders of libmipt.so (rust_ray_tracing_amd/csrc/bvh_build.cpp, hidden there), re-exported for

@@ -312,7 +312,7 @@ def load_multitest() -> C.CDLL:
 
 
 DIAG_LIB_PATH = os.path.join(_HERE, "libmipt_diag.so")
-DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_divide", "mipt_debug_popcount", "mipt_diag_last_error",
+DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_divide", "mipt_debug_popcount", "mipt_debug_tile_order", "mipt_diag_scene_tile_order", "mipt_diag_last_error",
                 "mipt_internal_pair_order", "mipt_internal_pair_order_top", "mipt_internal_tri_slots",
                 "mipt_diag_scene_sizes", "mipt_diag_scene_read", "mipt_diag_scene_hash", "mipt_diag_write_obj", "mipt_diag_host_layout", "mipt_diag_hash_words"]
 _diag = None
@@ -339,6 +339,10 @@ def load_diag() -> C.CDLL:
     lib.mipt_debug_divide.restype = C.c_int
     lib.mipt_debug_popcount.argtypes = [vp, C.c_uint64, vp, vp]
     lib.mipt_debug_popcount.restype = C.c_int
+    lib.mipt_debug_tile_order.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    lib.mipt_debug_tile_order.restype = C.c_int
+    lib.mipt_diag_scene_tile_order.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32 * 3)]
+    lib.mipt_diag_scene_tile_order.restype = C.c_int
     lib.mipt_diag_last_error.argtypes = []
     lib.mipt_diag_last_error.restype = C.c_char_p
     u32p = C.POINTER(C.c_uint32)

@@ -9,6 +9,7 @@
 #include "pt_device_wgsl.h"
 #include "mipt_host_util.h"
 #include "pt_kernel.h"
+#include "mipt_scene.h"
 
 #include <stdio.h>
 
@@ -189,6 +190,34 @@ int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words, uint64_t *d_
     if (!d_bitmap || !d_out || n_words == 0) { snprintf(g_err, sizeof g_err, "mipt_debug_popcount: bad argument"); return -1; }
     const hipError_t e = mipt::launch_popcount(d_bitmap, (unsigned long long)n_words, (unsigned long long *)d_out, (hipStream_t)stream);
     return e == hipSuccess ? 0 : fail(e, "launch_popcount");
+}
+
+// the tile order (pt_kernel.hip "tile order"): the product's sort on host arrays, and the state a scene handle keeps
+int mipt_debug_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order_out) {
+    if (!cost || !order_out || n_tiles == 0 || samples == 0) { snprintf(g_err, sizeof g_err, "mipt_debug_tile_order: bad argument"); return -1; }
+    mipt::DevPtr<uint32_t> dcost, dorder;
+    hipError_t e;
+    if ((e = dcost.alloc(n_tiles)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dorder.alloc(n_tiles)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(dcost, cost, (size_t)n_tiles * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemset(dorder, 0xff, (size_t)n_tiles * 4)) != hipSuccess) return fail(e, "hipMemset");
+    if ((e = mipt::launch_tile_order(dcost, n_tiles, samples, dorder, nullptr)) != hipSuccess) return fail(e, "launch_tile_order");
+    if ((e = hipMemcpy(order_out, dorder, (size_t)n_tiles * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *order_out, uint32_t cap, uint32_t info_out[3]) {
+    const MiptScene *s = (const MiptScene *)scene;
+    if (!s || !info_out) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_tile_order: bad argument"); return -1; }
+    const uint32_t n = s->tile_order_valid ? s->tile_key[4] : 0u;
+    info_out[0] = n; info_out[1] = s->tile_order_valid ? 1u : 0u; info_out[2] = s->tile_order_used ? 1u : 0u;
+    if (n == 0u || !cost_out || !order_out) return 0;
+    if (cap < n) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_tile_order: cap %u < %u tiles", cap, n); return -1; }
+    hipError_t e;
+    if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
+    if ((e = hipMemcpy(cost_out, s->d_tile_cost, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(order_out, s->d_tile_order, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
 }
 
 const char *mipt_diag_last_error(void) { return g_err; }

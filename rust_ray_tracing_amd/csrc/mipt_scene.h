@@ -40,6 +40,16 @@ struct MiptScene {
     float4 *d_cams = nullptr;               // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
     size_t cams_bytes = 0;
     std::vector<float4> h_cams;             // its host staging copy (outlives the stream-ordered upload)
+    // tile order (mipt_api.cpp render_launch, pt_kernel.hip): rays per local tile as the last plain single-view launch measured them,
+    // the tiles sorted by that cost, and what that launch was -- {width, height, tile world, tile rank, local tiles, seed mode,
+    // samples} and its camera.  A launch with the same key and camera hands its tiles out in that order; any other runs in the plain
+    // order and measures.
+    uint32_t *d_tile_cost = nullptr, *d_tile_order = nullptr;
+    size_t tile_cost_bytes = 0, tile_order_bytes = 0;
+    uint32_t tile_key[7] = {0, 0, 0, 0, 0, 0, 0};
+    float tile_cam[12] = {0};               // DevParams::cam of that launch, compared bit for bit
+    bool tile_order_valid = false;          // d_tile_order is the order of d_tile_cost, both of the launch tile_key describes
+    bool tile_order_used = false;           // that launch itself handed its tiles out by the order before it (read by the test hook)
     void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
     size_t qrays_bytes = 0, qout_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -77,6 +77,8 @@ struct DevParams {
     float *hdr;                             // full-frame or rank-packed, 3 f32 per pixel
     uint32_t *ovf;                          // traversal-stack overflow area [wave][entry][lane]
     DevStats *stats;
+    const uint32_t *tile_order;             // local tile handed out at queue position i (NULL = plain order); pt_kernel.hip "tile order"
+    uint32_t *tile_cost;                    // rays traced per local tile, added up by this launch (NULL = not measured)
     uint32_t *touched;                      // COUNT build + MIPT_FLAG_TOUCHED: one bit per 128-B line of [geom | tri_attr] (else NULL)
     uint32_t touched_attr_base;             // first bit of the tri_attr stream in `touched`
 };
@@ -140,6 +142,9 @@ struct DevFeatures {
 hipError_t launch_first_hit(const DevScene &sc, const DevFeatures &f, bool count, bool cull, int grid_blocks, hipStream_t stream);
 int first_hit_blocks_per_cu(bool count, bool cull);                          // occupancy query
 
+// order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
+// stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
+hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);
 // number of set bits in words [0, n_words) of `bitmap`, added to *out (a device counter)
 hipError_t launch_popcount(const uint32_t *bitmap, unsigned long long n_words, unsigned long long *out, hipStream_t stream);
 hipError_t launch_divide(float *hdr, unsigned long long n_floats, float divisor, hipStream_t stream);

@@ -311,6 +311,8 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
             }
             if (state == ST_S) {
                 if (path_done) {
+                    // tile order: this path's rays, added to its local tile's cost (slot = local tile * 64 + pixel of the tile)
+                    if (!BATCH && pr.tile_cost) atomicAdd(&pr.tile_cost[slot >> 6], bounces + ((best_tri == kNoTri) ? 1u : 0u));
                     const V3 res = (bounces == 0u) ? incoming : incoming / (float)bounces; // ray.rs:197-201
                     final_color = final_color + res;                                 // cpu.rs:52
                     sample += 1;
@@ -318,7 +320,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                         state = ST_G;
                     } else {
                         if (!pr.sum_only) final_color = final_color / pr.samples_f;  // cpu.rs:60
-                        float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)slot) * 3;
+                        float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)(pr.packed ? slot : pix)) * 3;
                         if (pr.accumulate) {      // progressive rendering: add this call's samples to the running sum
                             final_color = mk(dst[0] + final_color.x, dst[1] + final_color.y, dst[2] + final_color.z);
                         }
@@ -359,13 +361,15 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                                 if (r >= n) { q += 1u; r -= n; }
                                 view = q; lt = r;
                             }
-                            const uint32_t lt_o = pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt;
+                            // tile order: queue position -> local tile by the previous frame's cost, most expensive first, so that
+                            // the frame ends with its cheapest tiles and the waves run dry together (the host: mipt_api.cpp)
+                            const uint32_t lt_o = (!BATCH && pr.tile_order) ? pr.tile_order[lt] : (pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt);
                             const uint32_t gt = lt_o * pr.tile_world + pr.tile_rank;
                             const uint32_t px = (gt % pr.tiles_x) * 8u + (p & 7u);
                             const uint32_t py = (gt / pr.tiles_x) * 8u + (p >> 3);
                             if (px < pr.width && py < pr.height) {            // ragged edge tiles: skip, stay ST_P
                                 pix = py * pr.width + px;
-                                if (!BATCH) slot = pr.packed ? (lt_o * 64u + p) : pix;
+                                if (!BATCH) slot = lt_o * 64u + p;                    // the rank-packed output slot; its tile: slot >> 6
                                 rng = 987612486u * (pix + 87636354u);                 // cpu.rs:28-29
                                 const uint32_t y = pr.height - py;                    // cpu.rs:32
                                 screen_x = ((((float)px / (float)pr.width) * 2.0f) - 1.0f) * pr.aspect; // cpu.rs:33-34
@@ -590,6 +594,68 @@ __global__ void unpack_tiles_kernel(const float *__restrict__ packed_all, uint32
         hdr[i * 3 + 1] = packed_all[src * 3 + 1];
         hdr[i * 3 + 2] = packed_all[src * 3 + 2];
     }
+}
+
+// ---- tile order: order[] = the tiles by decreasing cost[] of the frame just traced ----
+// A stable counting sort in ONE block: 1 024 buckets of rays per path x 16 (bucket 0 = the most expensive), tile index ascending
+// within a bucket, so the order is a function of the costs alone -- no atomic cursor decides a place.  Wave w owns the contiguous
+// tiles [w * per, (w + 1) * per) and a private row of counters; after the scan row w holds, per bucket, the place of the wave's
+// next tile.  Within a group of 64 tiles a lane's rank among the lanes of its bucket comes from ten ballots (one per bucket bit).
+constexpr uint32_t kOrderBuckets = 1024, kOrderWaves = 8, kOrderThreads = 64 * kOrderWaves;
+__device__ __forceinline__ uint32_t tile_bucket(uint32_t cost, float scale) {
+    const float b = (float)cost * scale;
+    return (kOrderBuckets - 1u) - (b < (float)(kOrderBuckets - 1u) ? (uint32_t)b : (kOrderBuckets - 1u));
+}
+__global__ __launch_bounds__(kOrderThreads) void tile_order_kernel(const uint32_t *__restrict__ cost, uint32_t n, float scale, uint32_t *__restrict__ order) {
+    __shared__ uint32_t s_cnt[kOrderWaves][kOrderBuckets];
+    __shared__ uint32_t s_scan[kOrderThreads];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    for (uint32_t i = t; i < kOrderWaves * kOrderBuckets; i += kOrderThreads) (&s_cnt[0][0])[i] = 0u;
+    __syncthreads();
+    const uint32_t per = ((n + kOrderThreads - 1u) / kOrderThreads) * 64u;             // tiles per wave: whole groups of 64
+    const unsigned long long lo64 = (unsigned long long)w * per;
+    const uint32_t lo = lo64 < n ? (uint32_t)lo64 : n, hi = (lo64 + per < n) ? (uint32_t)(lo64 + per) : n;
+    for (uint32_t i = lo + lane; i < hi; i += 64u) atomicAdd(&s_cnt[w][tile_bucket(cost[i], scale)], 1u);
+    __syncthreads();
+    // thread t scans buckets 2t and 2t + 1 over the waves (bucket-major, wave-minor), then the block scans the threads' totals
+    uint32_t tot = 0u;
+    for (uint32_t k = 0; k < 2u; k++)
+        for (uint32_t ww = 0; ww < kOrderWaves; ww++) { const uint32_t c = s_cnt[ww][2u * t + k]; s_cnt[ww][2u * t + k] = tot; tot += c; }
+    s_scan[t] = tot;
+    __syncthreads();
+    for (uint32_t o = 1u; o < kOrderThreads; o <<= 1) {
+        const uint32_t y = t >= o ? s_scan[t - o] : 0u;
+        __syncthreads();
+        s_scan[t] += y;
+        __syncthreads();
+    }
+    const uint32_t base = s_scan[t] - tot;
+    for (uint32_t k = 0; k < 2u; k++)
+        for (uint32_t ww = 0; ww < kOrderWaves; ww++) s_cnt[ww][2u * t + k] += base;
+    __syncthreads();
+    for (uint32_t i0 = lo; i0 < hi; i0 += 64u) {                                         // wave-uniform
+        const uint32_t i = i0 + lane;
+        const bool valid = i < hi;
+        const uint32_t b = valid ? tile_bucket(cost[i], scale) : 0u;
+        unsigned long long peers = __ballot(valid);                                     // -> the valid lanes of this lane's bucket
+        for (uint32_t k = 0; k < 10u; k++) {
+            const bool bit = ((b >> k) & 1u) != 0u;
+            const unsigned long long m = __ballot(valid && bit);
+            peers &= bit ? m : ~m;
+        }
+        if (valid) {
+            const uint32_t rank = lane_rank(peers);
+            const uint32_t at = s_cnt[w][b];                                            // the same word for all peers, read before the add below
+            if (rank == 0u) s_cnt[w][b] = at + (uint32_t)__popcll(peers);
+            order[at + rank] = i;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                           // the next group reads the counters this one moved
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream) {
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(kOrderThreads), 0, stream, cost, n_tiles, 16.0f / (64.0f * (float)samples), order);
+    return hipGetLastError();
 }
 
 // ---- MIPT_FLAG_TOUCHED: the set bits of the line bitmap, added to *out ----
