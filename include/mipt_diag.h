@@ -5,7 +5,10 @@
  * Evaluates one device arithmetic primitive of the path-tracing kernel element-wise on the GPU, so tests can pin the
  * kernel's f32/f64 building blocks against the CPU oracle bit for bit.  The functions evaluated are the very ones the
  * kernel inlines (rust_ray_tracing_amd/csrc/pt_device_math.h): the restatement of glibc 2.35's cosf / log10f / powf
- * that stands in for Rust std f32::cos / f32::log10 / f32::powf (reference src/math.rs:15-19, src/math/vec3.rs:80-90).
+ * that stands in for Rust std f32::cos / f32::log10 / f32::powf (reference src/math.rs:15-19, src/math/vec3.rs:80-90);
+ * pt_device_wgsl.h: the material model of shading mode 1; pt_texel.h: the nearest-texel lookup of the default shading path.
+ * Beside the probes: the product's epilogue and tile-order launchers on the caller's buffers, the library-internal layout orders,
+ * and read-back hooks for what a scene handle of libmipt.so holds in device memory (geometry, attributes, texel pool, material tables).
  */
 #ifndef MIPT_DIAG_H
 #define MIPT_DIAG_H
@@ -47,6 +50,15 @@ MIPT_DIAG_API int mipt_debug_eval_range(int op, uint32_t first_bits, uint64_t n,
  * tex_* are read by op 0 only (texels may be NULL otherwise).  n <= 2^26.  Returns as mipt_debug_eval. */
 MIPT_DIAG_API int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels, uint32_t tex_w, uint32_t tex_h, float *out);
 
+/* The nearest-texel lookup of the default shading path (rust_ray_tracing_amd/csrc/pt_texel.h texel_rgb: Texture::color_at, texture.rs:33-38,
+ * then / 255), the one function the trace kernels and the first-hit pass inline, element-wise: rgb_out[3i .. 3i+3) = the colour of texture
+ * {offset, w, h} -- w * h packed RGBA8 words from word `offset` of `pool`, rows of w -- at (uv[2i], uv[2i+1]).  The pool is uploaded as the
+ * texel pool of a device scene and the lookup runs against a zeroed counter block, whose tex_clamped (lookups whose index left the
+ * texture and was clamped) comes back in *clamped_out.  Host buffers; n <= 2^26, pool_words <= 2^28; offset + w*h > pool_words is refused.
+ * Returns as mipt_debug_eval. */
+MIPT_DIAG_API int mipt_debug_texel(const float *uv, uint64_t n, const uint32_t *pool, uint64_t pool_words, uint32_t offset, uint32_t w, uint32_t h,
+                                   float *rgb_out, uint64_t *clamped_out);
+
 /* The two kernels of the frame epilogue that include/mipt.h reaches only through mipt_render_multi and MIPT_FLAG_TOUCHED, launched by the
  * product's own launchers (pt_kernel.hip launch_divide / launch_popcount, linked into this library unchanged) on the CALLER'S DEVICE
  * buffers, stream-ordered on `stream` (a hipStream_t, NULL = the null stream) without synchronising:
@@ -79,8 +91,11 @@ MIPT_DIAG_API int mipt_internal_tri_slots(const void *nodes, uint32_t n_nodes, u
 
 /* The device layout behind a MiptScene handle of libmipt.so (tests/cpp/scene_hooks.hip), for comparing the layout the GPU kernels
  * build (mipt_scene_create_from_triangles) with the host-built one (mipt_scene_create): sizes in bytes of [pair records | intersection
- * stream] and of the attribute stream; a copy of either (which = 0 / 1) to the host; an order-dependent 64-bit fingerprint of each. */
+ * stream] and of the attribute stream; a copy of either (which = 0 / 1) to the host; an order-dependent 64-bit fingerprint of each.
+ * mipt_diag_scene_tables (mipt_diag.hip, beside mipt_diag_scene_tile_order, the other reader of a handle's state): the payload bytes of the texel pool (texels * 4), of the 64-B material table and of the 128-B material table
+ * (materials * 64 / * 128) -- not the padded allocations; mipt_diag_scene_read copies them with which = 2 / 3 / 4. */
 MIPT_DIAG_API int mipt_diag_scene_sizes(const void *scene, uint64_t out[2]);
+MIPT_DIAG_API int mipt_diag_scene_tables(const void *scene, uint64_t out[3]);
 MIPT_DIAG_API int mipt_diag_scene_read(const void *scene, int which, void *dst, uint64_t bytes);
 MIPT_DIAG_API int mipt_diag_scene_hash(const void *scene, uint64_t out[2]);
 

@@ -81,6 +81,8 @@ def load() -> C.CDLL:
     lib.orc_quantize.restype = None
     lib.orc_texture_color_at.argtypes = [C.POINTER(OrcTexture), f32, f32, C.POINTER(C.c_uint8 * 4)]
     lib.orc_texture_color_at.restype = None
+    lib.orc_texture_lookup_many.argtypes = [C.POINTER(OrcTexture), vp, vp, C.c_uint64, vp, vp]
+    lib.orc_texture_lookup_many.restype = C.c_uint64
     lib.orc_pixel_screen.argtypes = [u32, u32, u32, C.POINTER(f32 * 2)]
     lib.orc_pixel_screen.restype = None
     for name in ("orc_glibc_cosf", "orc_glibc_log10f", "orc_glibc_sinf", "orc_glibc_expf", "orc_glibc_logf"):
@@ -126,6 +128,17 @@ def wgsl_sample_texture(tex, u, v):
     out, idx = np.zeros((u.size, 4), np.float32), np.zeros((u.size, 4), np.int64)
     load().orc_wgsl_sample_texture(C.byref(t), u.ctypes.data, v.ctypes.data, u.size, out.ctypes.data, idx.ctypes.data)
     return out, idx
+
+
+def texture_lookup_many(tex, u, v):
+    """Texture::color_at (tex_lookup) on n pairs.  tex: (h, w, 4) uint8.  Returns (rgba [n,4] u8, clamped flags [n] u8, their sum)."""
+    tex = np.ascontiguousarray(tex, dtype=np.uint8)
+    u, v = _f32(u).reshape(-1), _f32(v).reshape(-1)
+    assert u.size == v.size
+    t = OrcTexture(tex.shape[1], tex.shape[0], tex.ctypes.data)
+    out, flags = np.zeros((u.size, 4), np.uint8), np.zeros(u.size, np.uint8)
+    total = load().orc_texture_lookup_many(C.byref(t), u.ctypes.data, v.ctypes.data, u.size, out.ctypes.data, flags.ctypes.data)
+    return out, flags, int(total)
 
 
 def wgsl_onb(normal):

@@ -208,6 +208,16 @@ static int tex_lookup(const OrcTexture *t, float u, float v, uint8_t out[4]) { /
     return clamped;
 }
 void orc_texture_color_at(const OrcTexture *t, float u, float v, uint8_t out[4]) { tex_lookup(t, u, v, out); }
+/* tex_lookup on n coordinate pairs: rgba_out[4i..4i+4) and clamped_out[i] (0 / 1, what trace adds to tex_clamped); returns their sum */
+uint64_t orc_texture_lookup_many(const OrcTexture *t, const float *u, const float *v, uint64_t n, uint8_t *rgba_out, uint8_t *clamped_out) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const int c = tex_lookup(t, u[i], v[i], rgba_out + 4 * i);
+        if (clamped_out) clamped_out[i] = (uint8_t)c;
+        total += (uint64_t)c;
+    }
+    return total;
+}
 
 void orc_pixel_screen(uint32_t index, uint32_t w, uint32_t h, float out[2]) { /* cpu.rs:31-35 (T9) */
     uint32_t x = index % w;

@@ -150,6 +150,8 @@ void     orc_intersect_tri(const float o[3], const float d[3], const OrcTriangle
 void     orc_linear_to_srgb(const float in[3], int libm, float out[3]);  /* vec3.rs:80-90 */
 void     orc_quantize(const float in[3], uint8_t out[3]);       /* vec3.rs:262-270 */
 void     orc_texture_color_at(const OrcTexture *t, float u, float v, uint8_t out[4]); /* texture.rs:33-38 */
+/* the same lookup on n pairs, with the flag trace adds to tex_clamped per lookup (clamped_out may be NULL); returns the flags' sum */
+uint64_t orc_texture_lookup_many(const OrcTexture *t, const float *u, const float *v, uint64_t n, uint8_t *rgba_out, uint8_t *clamped_out);
 void     orc_pixel_screen(uint32_t index, uint32_t w, uint32_t h, float out[2]); /* cpu.rs:31-35 */
 float    orc_glibc_cosf(float x);
 float    orc_glibc_sinf(float x);

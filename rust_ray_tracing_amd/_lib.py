@@ -312,9 +312,9 @@ def load_multitest() -> C.CDLL:
 
 
 DIAG_LIB_PATH = os.path.join(_HERE, "libmipt_diag.so")
-DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_divide", "mipt_debug_popcount", "mipt_debug_tile_order", "mipt_diag_scene_tile_order", "mipt_diag_last_error",
+DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_texel", "mipt_debug_divide", "mipt_debug_popcount", "mipt_debug_tile_order", "mipt_diag_scene_tile_order", "mipt_diag_last_error",
                 "mipt_internal_pair_order", "mipt_internal_pair_order_top", "mipt_internal_tri_slots",
-                "mipt_diag_scene_sizes", "mipt_diag_scene_read", "mipt_diag_scene_hash", "mipt_diag_write_obj", "mipt_diag_host_layout", "mipt_diag_hash_words"]
+                "mipt_diag_scene_sizes", "mipt_diag_scene_tables", "mipt_diag_scene_read", "mipt_diag_scene_hash", "mipt_diag_write_obj", "mipt_diag_host_layout", "mipt_diag_hash_words"]
 _diag = None
 
 
@@ -335,6 +335,8 @@ def load_diag() -> C.CDLL:
     lib.mipt_debug_eval_range.restype = C.c_int
     lib.mipt_debug_wgsl.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp]
     lib.mipt_debug_wgsl.restype = C.c_int
+    lib.mipt_debug_texel.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint64)]
+    lib.mipt_debug_texel.restype = C.c_int
     lib.mipt_debug_divide.argtypes = [vp, C.c_uint64, C.c_float, vp]
     lib.mipt_debug_divide.restype = C.c_int
     lib.mipt_debug_popcount.argtypes = [vp, C.c_uint64, vp, vp]
@@ -354,6 +356,8 @@ def load_diag() -> C.CDLL:
     lib.mipt_internal_tri_slots.restype = C.c_int
     lib.mipt_diag_scene_sizes.argtypes = [vp, C.POINTER(C.c_uint64 * 2)]
     lib.mipt_diag_scene_sizes.restype = C.c_int
+    lib.mipt_diag_scene_tables.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.mipt_diag_scene_tables.restype = C.c_int
     lib.mipt_diag_scene_read.argtypes = [vp, C.c_int, vp, C.c_uint64]
     lib.mipt_diag_scene_read.restype = C.c_int
     lib.mipt_diag_scene_hash.argtypes = [vp, C.POINTER(C.c_uint64 * 2)]

@@ -13,6 +13,7 @@
 // pixel's next sample or take a new pixel from the global counter with one wave-aggregated atomic.
 #include "pt_kernel.h"
 #include "pt_device_math.h"
+#include "pt_texel.h"
 #include "pt_traverse.h"
 
 namespace mipt {
@@ -32,24 +33,6 @@ enum : uint32_t {
     FS_N = 2,   // needs a pixel
     FS_X = 3    // queue exhausted, lane retired
 };
-
-// Texture::color_at (texture.rs:33-38) / 255 (vec3.rs:252-260), restated from pt_kernel.hip's texel_rgb: out-of-range indices
-// (reference: panic) are clamped and counted
-__device__ __forceinline__ V3 texel_rgb(const DevScene &sc, uint32_t offset, uint32_t width, uint32_t height, float u, float v, DevStats *st) {
-    const float fu = u - truncf(u), fv = v - truncf(v);            // f32::fract
-    const float fi = fu * (float)width, fj = fv * (float)height;
-    // Rust `as i32`: saturating, NaN -> 0
-    const long long i = (fi != fi) ? 0ll : (fi >= 2147483648.0f ? 2147483647ll : (fi <= -2147483648.0f ? -2147483648ll : (long long)(int)fi));
-    const long long j = (fj != fj) ? 0ll : (fj >= 2147483648.0f ? 2147483647ll : (fj <= -2147483648.0f ? -2147483648ll : (long long)(int)fj));
-    long long index = i + j * (long long)width;
-    const long long n = (long long)width * (long long)height;
-    if (index < 0 || index >= n) {
-        index = index < 0 ? 0 : n - 1;
-        atomicAdd(&st->tex_clamped, 1ull);
-    }
-    const uint32_t px = sc.texels[(size_t)offset + (size_t)index];
-    return mk(u8_over_255(px & 255u), u8_over_255((px >> 8) & 255u), u8_over_255((px >> 16) & 255u));
-}
 
 // One step of a pixel's mean, formed as final_color is (cpu.rs:30,52,60): the sum starts at +0, takes the samples in order and is
 // divided by the sample count once, after the last -- also when that is the only one.  The running sum lives in the pixel's output

@@ -153,10 +153,13 @@ int mipt::upload_material_tables(MiptScene *s, const MaterialTables &t) {
     int rc;
     if ((rc = upload(&s->d_mats, t.mats, 64)) || (rc = upload(&s->d_mats_full, t.mats_full, 128))) return rc;
     if (!t.texels.empty() || t.n_texels == 0) { if ((rc = upload(&s->d_texels, t.texels, 16))) return rc; }
-    else MIPT_HIP(hipMalloc(&s->d_texels, (size_t)t.n_texels * 4));              // filled by the caller (scene_device.hip stages the textures itself)
+    // else filled by the caller (scene_device.hip stages the textures itself).  Never less than the 16 bytes texel_bytes records
+    // below: a replica copies texel_bytes from this allocation (clone_issue), also for a pool of one to three texels.
+    else MIPT_HIP(hipMalloc(&s->d_texels, (size_t)t.n_texels * 4 < 16 ? 16 : (size_t)t.n_texels * 4));
     s->mats_bytes = t.mats.size() * sizeof(mipt::DevMaterial) < 64 ? 64 : t.mats.size() * sizeof(mipt::DevMaterial);
     s->mats_full_bytes = t.mats_full.size() * sizeof(mipt::DevMaterialFull) < 128 ? 128 : t.mats_full.size() * sizeof(mipt::DevMaterialFull);
     s->texel_bytes = (size_t)t.n_texels * 4 < 16 ? 16 : (size_t)t.n_texels * 4;
+    s->n_texels = t.n_texels;
     s->dev.mats = (const mipt::DevMaterial *)s->d_mats;
     s->dev.mats_full = (const mipt::DevMaterialFull *)s->d_mats_full;
     s->dev.texels = (const uint32_t *)s->d_texels;
@@ -194,7 +197,7 @@ static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
     s->dev = src->dev;
     s->max_leaf = src->max_leaf; s->n_tris = src->n_tris; s->n_nodes = src->n_nodes; s->info = src->info;
     s->geom_alloc = src->geom_alloc; s->attr_bytes = src->attr_bytes; s->mats_bytes = src->mats_bytes;
-    s->mats_full_bytes = src->mats_full_bytes; s->texel_bytes = src->texel_bytes;
+    s->mats_full_bytes = src->mats_full_bytes; s->texel_bytes = src->texel_bytes; s->n_texels = src->n_texels;
     struct Part { void **dst; const void *from; size_t alloc, copy; };
     const Part parts[] = {{&s->d_geom, src->d_geom, src->geom_alloc, (size_t)src->dev.geom_bytes},
                           {&s->d_tri_attr, src->d_tri_attr, src->attr_bytes < 16 ? 16 : src->attr_bytes, src->attr_bytes},

@@ -2,11 +2,13 @@
 //
 // NOT part of the product library: libmipt.so exports nothing from this file.  The probe evaluates the kernel's own
 // arithmetic building blocks (pt_device_math.h: the glibc 2.35 restatement, the exact per-ray division, RNG, sRGB
-// quantisation; pt_device_wgsl.h: the sampler, basis, VNDF, hemisphere and Fresnel / reflect / refract of shading mode 1)
-// element-wise, so tests can compare them bit for bit with the CPU oracle on millions of arguments.
+// quantisation; pt_device_wgsl.h: the sampler, basis, VNDF, hemisphere and Fresnel / reflect / refract of shading mode 1;
+// pt_texel.h: the nearest-texel lookup of the default shading path) element-wise, so tests can compare them bit for bit with the
+// CPU oracle on millions of arguments.
 #include "../../include/mipt_diag.h"
 #include "pt_device_math.h"
 #include "pt_device_wgsl.h"
+#include "pt_texel.h"
 #include "mipt_host_util.h"
 #include "pt_kernel.h"
 #include "mipt_scene.h"
@@ -116,6 +118,18 @@ __global__ void debug_wgsl_kernel(int op, const float *__restrict__ in, unsigned
     }
 }
 
+// texel_rgb (pt_texel.h) of texture {offset, w, h} in the pool sc.texels at (uv[2i], uv[2i+1]) -> rgb[3i .. 3i+3); the clamp count
+// goes where the kernels' goes, into st->tex_clamped
+__global__ void debug_texel_kernel(mipt::DevScene sc, const float *__restrict__ uv, unsigned long long n, uint32_t offset, uint32_t w, uint32_t h,
+                                   float *__restrict__ rgb, mipt::DevStats *st) {
+    using namespace mipt;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const V3 c = texel_rgb(sc, offset, w, h, uv[2 * i], uv[2 * i + 1], st);
+        rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+    }
+}
+
 int fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
     return -2;   // MIPT_ERR_HIP
@@ -178,6 +192,37 @@ int mipt_debug_wgsl(int op, const float *in, uint64_t n, const uint32_t *texels,
     return 0;
 }
 
+int mipt_debug_texel(const float *uv, uint64_t n, const uint32_t *pool, uint64_t pool_words, uint32_t offset, uint32_t w, uint32_t h,
+                     float *rgb_out, uint64_t *clamped_out) {
+    if (!uv || !pool || !rgb_out || !clamped_out || n == 0 || n > (1ull << 26) || w == 0 || h == 0 || pool_words == 0 ||
+        pool_words > (1ull << 28) || (uint64_t)offset + (uint64_t)w * h > pool_words) {
+        snprintf(g_err, sizeof g_err, "mipt_debug_texel: bad argument");
+        return -1;
+    }
+    mipt::DevPtr<float> duv, drgb;
+    mipt::DevPtr<uint32_t> dpool;
+    mipt::DevPtr<mipt::DevStats> dst;
+    hipError_t e;
+    if ((e = duv.alloc(n * 2)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = drgb.alloc(n * 3)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dpool.alloc(pool_words)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dst.alloc(1)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(duv, uv, n * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(dpool, pool, pool_words * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemset(dst, 0, sizeof(mipt::DevStats))) != hipSuccess) return fail(e, "hipMemset");
+    mipt::DevScene sc{};
+    sc.texels = dpool.get();
+    sc.n_texs = 1;
+    hipLaunchKernelGGL(debug_texel_kernel, dim3(1024), dim3(256), 0, nullptr, sc, (const float *)duv.get(), (unsigned long long)n, offset, w, h,
+                       drgb.get(), dst.get());
+    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
+    if ((e = hipMemcpy(rgb_out, drgb, n * 12, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    mipt::DevStats hs;
+    if ((e = hipMemcpy(&hs, dst, sizeof hs, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    *clamped_out = hs.tex_clamped;
+    return 0;
+}
+
 // the frame epilogue's two helpers that have no entry point of their own in include/mipt.h: the product's launchers (pt_kernel.hip,
 // linked into this library unchanged) on the caller's device buffers, stream-ordered, no synchronisation
 int mipt_debug_divide(float *d_buf, uint64_t n_floats, float divisor, void *stream) {
@@ -217,6 +262,15 @@ int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *
     if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
     if ((e = hipMemcpy(cost_out, s->d_tile_cost, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     if ((e = hipMemcpy(order_out, s->d_tile_order, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+// payload, not allocation: the pool is n_texels words, a table one record per material (both allocations are padded when tiny).
+// tests/cpp/scene_hooks.hip copies the three to the host (mipt_diag_scene_read, which = 2 / 3 / 4).
+int mipt_diag_scene_tables(const void *scene, uint64_t out[3]) {
+    const MiptScene *s = (const MiptScene *)scene;
+    if (!s || !out) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_tables: bad argument"); return -1; }
+    out[0] = s->n_texels * 4; out[1] = (uint64_t)s->dev.n_mats * sizeof(mipt::DevMaterial); out[2] = (uint64_t)s->dev.n_mats * sizeof(mipt::DevMaterialFull);
     return 0;
 }
 

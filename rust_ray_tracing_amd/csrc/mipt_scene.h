@@ -20,7 +20,11 @@ struct MiptScene {
     int device = 0;
     mipt::DevScene dev{};
     void *d_geom = nullptr, *d_tri_attr = nullptr, *d_mats = nullptr, *d_mats_full = nullptr, *d_texels = nullptr;
-    size_t geom_alloc = 0, attr_bytes = 0, mats_bytes = 0, mats_full_bytes = 0, texel_bytes = 0;   // allocation / payload sizes (replicas copy these)
+    // Sizes a replica allocates and copies (clone_issue, replica_refresh): every one is at most what its buffer was allocated with.
+    // geom_alloc is the allocation (the payload, dev.geom_bytes, is copied); attr_bytes is allocation and payload; mats_bytes,
+    // mats_full_bytes and texel_bytes are the allocations -- the payload, or one record / 16 bytes when that is more.
+    size_t geom_alloc = 0, attr_bytes = 0, mats_bytes = 0, mats_full_bytes = 0, texel_bytes = 0;
+    uint64_t n_texels = 0;                  // texels in the pool (its payload is n_texels * 4 bytes)
     // a scene whose BVH was built on the device keeps the tree for mipt_scene_get_bvh: nodes in the reference's order and the
     // triangle permutation BVH::build applied (reordered[t] = original[tri_order[t]])
     MiptNode *d_nodes = nullptr;

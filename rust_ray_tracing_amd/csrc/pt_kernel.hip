@@ -17,6 +17,7 @@
 #include "pt_kernel.h"
 #include "pt_device_math.h"
 #include "pt_device_wgsl.h"
+#include "pt_texel.h"
 #include "pt_traverse.h"
 
 namespace mipt {
@@ -44,23 +45,6 @@ __device__ __forceinline__ float min3_abs(float a, float b, float c) { float r; 
 __device__ __forceinline__ void mark_line(uint32_t *bitmap, uint32_t line) {
     const uint32_t bit = 1u << (line & 31u);
     if (!(__builtin_nontemporal_load(&bitmap[line >> 5]) & bit)) atomicOr(&bitmap[line >> 5], bit);
-}
-
-// texture.rs:33-38; out-of-range indices (reference: panic) are clamped and counted
-__device__ __forceinline__ V3 texel_rgb(const DevScene &sc, uint32_t offset, uint32_t width, uint32_t height, float u, float v, DevStats *st) {
-    float fu = u - truncf(u), fv = v - truncf(v);                  // f32::fract
-    float fi = fu * (float)width, fj = fv * (float)height;
-    // Rust `as i32`: saturating, NaN -> 0
-    long long i = (fi != fi) ? 0ll : (fi >= 2147483648.0f ? 2147483647ll : (fi <= -2147483648.0f ? -2147483648ll : (long long)(int)fi));
-    long long j = (fj != fj) ? 0ll : (fj >= 2147483648.0f ? 2147483647ll : (fj <= -2147483648.0f ? -2147483648ll : (long long)(int)fj));
-    long long index = i + j * (long long)width;
-    long long n = (long long)width * (long long)height;
-    if (index < 0 || index >= n) {
-        index = index < 0 ? 0 : n - 1;
-        atomicAdd(&st->tex_clamped, 1ull);
-    }
-    uint32_t px = sc.texels[(size_t)offset + (size_t)index];
-    return mk(u8_over_255(px & 255u), u8_over_255((px >> 8) & 255u), u8_over_255((px >> 16) & 255u)); // vec3.rs:252-260
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 
 # the kernel and its math; the launch parameters and the host-built device layout (mipt_api.cpp); the record orders (bvh_build.cpp);
 # the same layout built on the GPU (scene_device.hip)
-KERNEL_SOURCES = ("pt_kernel.hip", "pt_device_math.h", "pt_kernel.h", "glibc_flt32_data.h", "mipt_api.cpp", "bvh_build.cpp", "scene_device.hip")
+KERNEL_SOURCES = ("pt_kernel.hip", "pt_device_math.h", "pt_kernel.h", "pt_texel.h", "glibc_flt32_data.h", "mipt_api.cpp", "bvh_build.cpp", "scene_device.hip")
 
 
 def kernel_source_sha() -> str:

@@ -27,12 +27,19 @@ int mipt_diag_scene_sizes(const void *scene, uint64_t out[2]) {
     return 0;
 }
 
+// which = 0 / 1: geometry and attribute stream; 2 / 3 / 4: the texel pool and the two material tables, by their payload sizes
+// (mipt_diag_scene_tables, mipt_diag.hip)
 int mipt_diag_scene_read(const void *scene, int which, void *dst, uint64_t bytes) {
     const MiptScene *s = (const MiptScene *)scene;
-    if (!s || !dst || which < 0 || which > 1) return -1;
-    const void *src = which == 0 ? s->d_geom : s->d_tri_attr;
-    const uint64_t have = which == 0 ? s->dev.geom_bytes : s->attr_bytes;
-    if (bytes > have) return -1;
+    if (!s || !dst || which < 0 || which > 4) return -1;
+    uint64_t tables[3] = {0, 0, 0};
+    (void)mipt_diag_scene_tables(scene, tables);
+    const void *const srcs[5] = {s->d_geom, s->d_tri_attr, s->d_texels, s->d_mats, s->d_mats_full};
+    const uint64_t haves[5] = {s->dev.geom_bytes, s->attr_bytes, tables[0], tables[1], tables[2]};
+    const void *src = srcs[which];
+    const uint64_t have = haves[which];
+    if (bytes > have || !src) return -1;
+    if (bytes == 0) return 0;
     if (hipSetDevice(s->device) != hipSuccess || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return -2;
     return 0;
 }
