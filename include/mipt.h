@@ -370,6 +370,69 @@ MIPT_API int mipt_render_features(MiptScene *scene, const MiptCamera *cameras, u
 MIPT_API int mipt_render_features_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
                                          const MiptFeatureBuffers *device_out, void *hip_stream, MiptStats *stats);
 
+/* ---- a-trous denoiser: a few-sample frame plus its first-hit guides -> a usable image -----------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with optional albedo demodulation (csrc/denoise.hip), for the
+ * buffers mipt_render{,_batch}_device and mipt_render_features_device leave in HBM.  The reference has no denoiser: the filter is
+ * defined HERE, and the kernels and tests/tools/denoise_model.py obey it bit for bit.  Every operator is one rounded f32 operation,
+ * nothing is fused, and the operations run in the order written.
+ *
+ * Buffers.  View-major planar, row 0 = top -- the layouts mipt_render_batch and mipt_render_features write:
+ *   hdr     3 f32 / pixel, required
+ *   normal  3 f32 / pixel, optional; used as given, not normalised
+ *   depth   1 f32 / pixel, optional; a miss is 1e30
+ *   albedo  3 f32 / pixel, optional
+ *   out     3 f32 / pixel, required
+ * A NULL guide means its term is left out: not computed, not fetched.
+ *
+ * Demodulation.  With albedo, per channel: a = albedo > 1/256 ? albedo : 1/256 (a comparison-select: a NaN albedo gives the floor),
+ * c0 = hdr / a, and after the last iteration out = c * a.  Without albedo c0 = hdr and out = c.
+ *
+ * Iteration i = 0 ... iterations - 1 (1 <= iterations <= 8) has step s = 1 << i, reads the previous iteration's colours c and writes
+ * new ones.  For pixel p = (x, y) of view v:
+ *   - taps q = (x + s*dx, y + s*dy), dy = -2 ... 2 the outer loop and dx = -2 ... 2 the inner one.  A tap outside [0,W) x [0,H) is
+ *     skipped -- neither weighted nor added -- and views never see each other.
+ *   - h = [1/16, 1/4, 3/8, 1/4, 1/16]; the tap's kernel weight h[dy+2] * h[dx+2] is an exact constant.
+ *   - dc = ((dr*dr) + (dg*dg)) + (db*db) with dr = c_p.r - c_q.r and so on; dn likewise from the normals; dz = (z_p - z_q) * (z_p - z_q).
+ *   - e = ((dc * kc_i) + (dn * kn)) + (dz * kz), an absent guide's term left out of the sum.  The constants are formed on the host in
+ *     f32: kn = 1.0f / (sigma_normal * sigma_normal), kz likewise from sigma_depth, kc_i = 1.0f / (sc * sc) with
+ *     sc = sigma_color * 2^-i.
+ *   - e = e < 128.0f ? e : 128.0f (a NaN gives 128).
+ *   - w = (h[dy+2] * h[dx+2]) * expf(-e), expf being glibc 2.35's (the one the render's libm restatement pins) on [-128, -0], where
+ *     expf(-128) = 0.  The centre tap has weight 9/64 without evaluation.
+ *   - sum_ch = sum_ch + (w * c_q.ch) and wsum = wsum + w, both starting at +0.
+ *   - the new colour is, per channel, wsum > 0 ? sum_ch / wsum : c_p.ch.
+ * A NaN this arithmetic produces is a NaN everywhere; its sign and payload are the implementation's (the rule of the query section).
+ *
+ * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- a null opt, buffers, hdr or out; zero width, height or n_views; n_views*W*H >= MIPT_BATCH_MAX_PIXELS; iterations outside
+ * 1 ... 8; a sigma that is not finite and greater than 0 or whose k (kc_i for every i) does not come out finite and greater than 0
+ * (a sigma given for an absent guide is ignored); non-zero flags or reserved fields; buffers that overlap (out == hdr alone is
+ * allowed); for the device entry a workspace that is NULL, too small, not 16-byte aligned or overlapped by a buffer, a pointer that
+ * is not 4-byte aligned, and a pointer that is not device memory of one common device (hdr's). */
+typedef struct {
+    uint32_t width, height, n_views;
+    uint32_t iterations;          /* 1 ... 8 */
+    float    sigma_color, sigma_normal, sigma_depth;
+    uint32_t flags;               /* must be 0 */
+    uint32_t reserved[8];         /* must be 0 */
+} MiptDenoiseOptions;             /* 64 B */
+typedef struct {
+    const float *hdr, *normal, *depth, *albedo;   /* normal, depth, albedo: NULL = absent */
+    float       *out;                             /* may be hdr */
+    void        *reserved[3];                     /* must be NULL */
+} MiptDenoiseBuffers;             /* 64 B */
+
+/* Bytes of workspace mipt_denoise_device needs for this size: three float4 planes, 48 B per pixel.  0 = an invalid size. */
+MIPT_API uint64_t mipt_denoise_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views);
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_denoise(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *host, int device_id);
+/* DEVICE buffers of one device (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream).  Stream-ordered: it does
+ * not block and allocates nothing, like mipt_tonemap_device.  d_workspace is the caller's: 16-byte aligned device memory of at least
+ * mipt_denoise_workspace_bytes().  The call writes `out` and the first mipt_denoise_workspace_bytes() bytes of the workspace and
+ * nothing else. */
+MIPT_API int mipt_denoise_device(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *device, void *d_workspace,
+                                 uint64_t workspace_bytes, void *hip_stream);
+
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);
 /* d_packed_all: tile_world slices of mipt_packed_pixels()*3 floats, rank-major (the layout an

@@ -110,6 +110,12 @@ inline int render_features_on(MiptScene *scene, const std::vector<MiptCamera> &c
     return rc;
 }
 
+// Renderer::denoise: the filter's settings (MiptDenoiseOptions; the defaults of the Python mirror)
+struct DenoiseSettings {
+    uint32_t iterations = 5;                               // 1 ... 8; iteration i has step 1 << i
+    float sigma_color = 4.0f, sigma_normal = 0.5f, sigma_depth = 0.5f;
+};
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -356,6 +362,39 @@ class Renderer {                                           // src/renderer.rs:8-
         const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
         MiptMulti *m = scene.node_handle(1);
         return m ? render_features_on(mipt_multi_scene(m, 0), cams, o, wanted, out, stats) : MIPT_ERR_HIP;
+    }
+
+    // The a-trous denoiser (mipt_denoise, include/mipt.h "a-trous denoiser") over host images of this renderer's width and height:
+    // `hdr` holds n_views frames of 3 f32 per pixel, view-major, row 0 the top row -- what mipt_render_batch writes.  The guides are
+    // the normal, depth and albedo images of `guides` (render_features); an empty one is absent and its term is left out.  `out` is
+    // resized and filled; it may be `hdr` itself.  Returns a MiptStatus; a size that does not fit is MIPT_ERR_INVALID_ARG before the
+    // library is called.
+    int denoise(const std::vector<float> &hdr, uint32_t n_views, const FeatureImages &guides, std::vector<float> &out,
+                const DenoiseSettings &settings = DenoiseSettings()) const {
+        MiptDenoiseOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.n_views = n_views; o.iterations = settings.iterations;
+        o.sigma_color = settings.sigma_color; o.sigma_normal = settings.sigma_normal; o.sigma_depth = settings.sigma_depth;
+        const uint64_t n = (uint64_t)o.width * o.height * n_views;
+        auto fits = [&](const std::vector<float> &v, uint64_t k, const char *name, bool required) {
+            if ((v.empty() && !required) || v.size() == n * k) return true;
+            log_error(std::string("Renderer::denoise: ") + name + " holds " + std::to_string(v.size()) + " values, expected " + std::to_string(n * k));
+            return false;
+        };
+        if (n != 0 && n < MIPT_BATCH_MAX_PIXELS &&                         // an impossible size is left to the library to refuse
+            !(fits(hdr, 3, "hdr", true) && fits(guides.normal, 3, "normal", false) && fits(guides.depth, 1, "depth", false) && fits(guides.albedo, 3, "albedo", false)))
+            return MIPT_ERR_INVALID_ARG;
+        static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
+        if (&out != &hdr) out.assign(n != 0 && n < MIPT_BATCH_MAX_PIXELS ? (size_t)n * 3 : 3, 0.0f);
+        MiptDenoiseBuffers b{};
+        b.hdr = hdr.empty() ? no_pixel : hdr.data();
+        b.normal = guides.normal.empty() ? nullptr : guides.normal.data();
+        b.depth = guides.depth.empty() ? nullptr : guides.depth.data();
+        b.albedo = guides.albedo.empty() ? nullptr : guides.albedo.data();
+        b.out = out.data();
+        const int rc = mipt_denoise(&o, &b, options.device_id);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
     }
 
     // The same arm over EVERY GPU of the node from this single-threaded host (mipt_render_multi: scene replicas, RCCL

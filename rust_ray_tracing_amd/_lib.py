@@ -110,6 +110,21 @@ class MiptFeatureBuffers(C.Structure):
 
 assert C.sizeof(MiptFeatureBuffers) == 96
 
+
+# ---- a-trous denoiser (include/mipt.h "a-trous denoiser") ----
+class MiptDenoiseOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class MiptDenoiseBuffers(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p), ("out", C.c_void_p),
+                ("reserved", C.c_void_p * 3)]
+
+
+assert C.sizeof(MiptDenoiseOptions) == 64 and C.sizeof(MiptDenoiseBuffers) == 64
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -158,6 +173,7 @@ EXPORTS = [
     "mipt_render_batch", "mipt_render_batch_device",
     "mipt_query_closest", "mipt_query_closest_device", "mipt_query_occluded", "mipt_query_occluded_device",
     "mipt_render_features", "mipt_render_features_device",
+    "mipt_denoise_workspace_bytes", "mipt_denoise", "mipt_denoise_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
 ]
 
@@ -287,6 +303,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_render_features.restype = C.c_int
     lib.mipt_render_features_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, vp, C.POINTER(MiptStats)]
     lib.mipt_render_features_device.restype = C.c_int
+    do, db = C.POINTER(MiptDenoiseOptions), C.POINTER(MiptDenoiseBuffers)
+    lib.mipt_denoise_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.mipt_denoise_workspace_bytes.restype = u64
+    lib.mipt_denoise.argtypes = [do, db, C.c_int]
+    lib.mipt_denoise.restype = C.c_int
+    lib.mipt_denoise_device.argtypes = [do, db, vp, u64, vp]
+    lib.mipt_denoise_device.restype = C.c_int
     return lib
 
 

@@ -59,15 +59,7 @@ int validate(const char *who, const MiptScene *scene, const MiptCamera *cameras,
     return MIPT_OK;
 }
 
-int device_buffer_check(const char *who, const void *p, int device, const char *name) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) (void)hipGetLastError();         // an unregistered host pointer is reported as an error: clear it
-    if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: %s is not device memory of the scene's device %d", who, name, device);
-    return MIPT_OK;
-}
+using mipt::device_buffer_check;                               // mipt_host_util.h
 
 // the launch, with every argument already checked; the wanted buffers in HBM of the scene's device
 int features_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, const MiptFeatureBuffers *d_out,

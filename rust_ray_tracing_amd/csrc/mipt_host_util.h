@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <thread>
 
 // A HIP call, or `return MIPT_ERR_HIP` with "<the call> failed: <HIP's text>" as mipt_last_error().  MIPT_HIP_OR first runs
@@ -68,6 +69,22 @@ inline int grow_device_buffer(void **p, size_t *have, size_t want_bytes) {
     if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
     MIPT_HIP(hipMalloc(p, want_bytes));
     *have = want_bytes;
+    return MIPT_OK;
+}
+
+// MIPT_OK if `p` is device memory of HIP device `device`, else MIPT_ERR_INVALID_ARG with "<who>: <name> is not device memory of
+// <whose> <device>".  device < 0: of any device.  *found (may be NULL) receives the device `p` lives on.
+inline int device_buffer_check(const char *who, const void *p, int device, const char *name, const char *whose = "the scene's device",
+                               int *found = nullptr) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) (void)hipGetLastError();         // an unregistered host pointer is reported as an error: clear it
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice || (device >= 0 && a.device != device)) {
+        if (device < 0) return fail(MIPT_ERR_INVALID_ARG, "%s: %s is not device memory", who, name);
+        return fail(MIPT_ERR_INVALID_ARG, "%s: %s is not device memory of %s %d", who, name, whose, device);
+    }
+    if (found) *found = a.device;
     return MIPT_OK;
 }
 

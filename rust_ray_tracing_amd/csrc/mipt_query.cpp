@@ -28,15 +28,7 @@ int validate(const char *who, const MiptScene *scene, const void *rays, const vo
     return MIPT_OK;
 }
 
-int device_buffer_check(const char *who, const void *p, int device, const char *name) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) (void)hipGetLastError();         // an unregistered host pointer is reported as an error: clear it
-    if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: %s is not device memory of the scene's device %d", who, name, device);
-    return MIPT_OK;
-}
+using mipt::device_buffer_check;                               // mipt_host_util.h
 
 // the launch, with every argument already checked; d_rays / d_out in HBM of the scene's device
 int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, void *d_out, bool anyhit,

@@ -142,6 +142,20 @@ struct DevFeatures {
 hipError_t launch_first_hit(const DevScene &sc, const DevFeatures &f, bool count, bool cull, int grid_blocks, hipStream_t stream);
 int first_hit_blocks_per_cu(bool count, bool cull);                          // occupancy query
 
+// ---- a-trous denoiser (denoise.hip; mipt_denoise*) ----
+struct DevDenoise {
+    // planar inputs, view-major; normal / depth / albedo NULL = absent (the term is left out).  out may be hdr.
+    const float *hdr, *normal, *depth, *albedo;
+    float *out;
+    // the workspace: three float4 planes of n_pixels each -- the packed guides {n.x, n.y, n.z, z}, then the two colour planes
+    float4 *guides, *colour[2];
+    uint32_t width, height, n_views, iterations;
+    uint32_t tiles_x, tiles_y;              // 64x4-pixel tiles per row / per column of a view
+    float kc[8], kn, kz;                    // 1 / sigma^2, the colour one per iteration (include/mipt.h)
+};
+// the pack pass and `iterations` filter passes, one launch each (stream-ordered; no allocation, no synchronisation inside)
+hipError_t launch_denoise(const DevDenoise &d, hipStream_t stream);
+
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);

@@ -771,6 +771,115 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = st.as_dict()
         return out, self.last_stats
 
+    # -- a-trous denoiser (include/mipt.h "a-trous denoiser") ------------------------------------
+    @staticmethod
+    def _denoise_planes(hdr, normal, depth, albedo):
+        """-> (torch?, (V, H, W), {name: contiguous float32 array or tensor}); ValueError naming the argument for anything else."""
+        torch_in = Scene._is_torch(hdr)
+        if not torch_in:
+            hdr = np.asarray(hdr)
+        if hdr.ndim not in (3, 4) or hdr.shape[-1] != 3:
+            raise ValueError(f"hdr: expected shape [V,H,W,3] or [H,W,3]; got {tuple(hdr.shape)}")
+        lead = tuple(hdr.shape[:-1])
+        planes = {}
+        for name, a, want in (("hdr", hdr, lead + (3,)), ("normal", normal, lead + (3,)), ("depth", depth, lead), ("albedo", albedo, lead + (3,))):
+            if a is None:
+                continue
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: hdr and the guides must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                if a.dtype != torch.float32 or not a.is_cuda or a.device != hdr.device:
+                    raise ValueError(f"{name}: expected a float32 tensor on hdr's device {hdr.device}")
+                if tuple(a.shape) != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
+                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                planes[name] = a
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.float32:
+                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
+                if a.shape != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
+                planes[name] = np.ascontiguousarray(a)
+        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
+        return torch_in, (v, h, w), planes
+
+    def denoise(self, hdr, normal=None, depth=None, albedo=None, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.5,
+                sigma_depth: float = 0.5, stream=None):
+        """The edge-avoiding a-trous filter of include/mipt.h over a frame or a batch of views: ``hdr`` [V,H,W,3] or [H,W,3] float32,
+        the optional guides ``normal`` [..,3], ``depth`` [..] and ``albedo`` [..,3] of the same leading shape (None = the term is left
+        out; with ``albedo`` the frame is demodulated before and re-modulated after).  numpy arrays go through mipt_denoise on
+        ``options.device_id``; contiguous torch tensors through mipt_denoise_device on ``stream`` (a torch stream, a raw hipStream_t or None =
+        torch's current stream) without blocking, with a torch tensor as the workspace.  Returns a new array / tensor of ``hdr``'s
+        kind and shape."""
+        torch_in, (v, h, w), p = self._denoise_planes(hdr, normal, depth, albedo)
+        opt = L.MiptDenoiseOptions()
+        opt.width, opt.height, opt.n_views, opt.iterations = w, h, v, iterations
+        opt.sigma_color, opt.sigma_normal, opt.sigma_depth = sigma_color, sigma_normal, sigma_depth
+        bufs = L.MiptDenoiseBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            dev = p["hdr"].device
+            out = torch.empty_like(p["hdr"])
+            for name, a in p.items():
+                setattr(bufs, name, a.data_ptr())
+            bufs.out = out.data_ptr()
+            need = int(lib.mipt_denoise_workspace_bytes(w, h, v))
+            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            for t in list(p.values()) + [out, workspace]:
+                t.record_stream(s)
+            L.check(lib.mipt_denoise_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), "mipt_denoise_device")
+            return out
+        out = np.empty_like(p["hdr"])
+        for name, a in p.items():
+            setattr(bufs, name, a.ctypes.data)
+        bufs.out = out.ctypes.data
+        L.check(lib.mipt_denoise(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise")
+        return out
+
+    def render_denoised(self, scene: Scene, cameras=None, **denoise_args):
+        """Render, guides and filter on one stream with nothing crossing PCIe in between: mipt_render_batch_device with this renderer's
+        options, mipt_render_features_device for depth, normal and albedo (one sample, this renderer's seed mode) and
+        mipt_denoise_device (``denoise_args``: iterations, the sigmas, stream).  ``cameras``: a sequence of Camera (or CAMERA records),
+        None = the scene's camera.  Returns (denoised, noisy, features, stats): float32 tensors [V,H,W,3] on ``options.device_id``,
+        the feature dict of ``render_features`` and the stats of the render launch."""
+        import torch
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        cams = [scene.camera] if cameras is None else list(cameras)
+        if not cams:
+            raise ValueError("render_denoised: no cameras")
+        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        n = len(cams)
+        w, h = o.output_image_dimensions
+        dev = torch.device("cuda", o.device_id)
+        stream = denoise_args.pop("stream", None)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        handle = scene.upload(o.device_id)
+        opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, cull_margin=o.cull_margin, shading=o.shading)
+        noisy = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+        st = L.MiptStats()
+        L.check(L.load().mipt_render_batch_device(handle, L.ptr(table), n, C.byref(opt), noisy.data_ptr(), None, raw, C.byref(st)),
+                "mipt_render_batch_device")
+        stats = st.as_dict()
+        one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
+        features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo"), device=True, stream=raw, handle=handle)
+        denoised = self.denoise(noisy, features["normal"], features["depth"], features["albedo"], stream=raw, **denoise_args)
+        self.last_stats = stats
+        return denoised, noisy, features, stats
+
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
                              want_rgba8: bool = True, flags: int = 0):
         """The same arm over all GPUs of the node in one call (mipt_render_multi): image tiles + one RCCL gather, or

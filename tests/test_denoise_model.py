@@ -1,0 +1,257 @@
+"""CPU: the model of the a-trous denoiser (tests/tools/denoise_model.py) has the properties the contract of include/mipt.h promises --
+views do not bleed, a guide edge stops the filter exactly, and a few-sample frame of the oracle comes out at most half as far from the
+converged one -- and every argument check of mipt_denoise / mipt_denoise_device / Renderer.denoise runs before any device work."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import denoise_model as D  # noqa: E402
+import features_model as FM  # noqa: E402
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ---- the model ------------------------------------------------------------------------------------------------------------------
+def test_views_do_not_bleed(orc):
+    """view 0 all 1.0, view 1 all 2.0, no guides, 7x5, 8 iterations (steps up to 128: most taps fall outside): sum w*c is exact for
+    these values, so both views come out unchanged bit for bit"""
+    hdr = np.empty((2, 5, 7, 3), dtype=np.float32)
+    hdr[0], hdr[1] = 1.0, 2.0
+    out = D.denoise(orc, hdr, iterations=8)
+    assert np.array_equal(_bits(out), _bits(hdr))
+
+
+@pytest.mark.parametrize("guide", ["normal", "depth"])
+def test_an_edge_stops_the_filter(orc, guide):
+    h, w = 9, 12
+    hdr = np.empty((h, w, 3), dtype=np.float32)
+    hdr[:, : w // 2], hdr[:, w // 2:] = 1.0, 2.0
+    kw = {}
+    if guide == "normal":                                               # |dn|^2 = 2, kn = 400: e clamps to 128, expf(-128) = 0
+        n = np.zeros((h, w, 3), dtype=np.float32)
+        n[:, : w // 2] = (0, 0, 1)
+        n[:, w // 2:] = (1, 0, 0)
+        kw = dict(normal=n, sigma_normal=0.05)
+    else:                                                               # a hit at depth 1 beside a miss
+        z = np.empty((h, w), dtype=np.float32)
+        z[:, : w // 2], z[:, w // 2:] = 1.0, 1e30
+        kw = dict(depth=z)
+    out = D.denoise(orc, hdr, iterations=5, **kw)
+    assert np.array_equal(_bits(out), _bits(hdr))
+    # without the guide the halves do mix
+    assert not np.array_equal(_bits(D.denoise(orc, hdr, iterations=5, sigma_color=4.0)), _bits(hdr))
+
+
+def test_expf_of_the_clamp_is_zero_and_the_centre_weight(orc):
+    assert orc.eval_array(D.EXPF, np.float32([-128.0, -0.0])).tolist() == [0.0, 1.0]
+    assert D.H5[2] * D.H5[2] == np.float32(9.0 / 64.0)
+
+
+_atrium = {}
+
+
+def _atrium_frames(rrt, orc):
+    """the 20 k-triangle atrium at 64x36, depth 8: the 1024-sample target (per-sample seeds from 1000) and the guides, computed once"""
+    if not _atrium:
+        from rust_ray_tracing_amd import _lib as L
+        from rust_ray_tracing_amd import synth
+        tris, mats, texs, cam = synth.make_scene("atrium", n_target=20000, tex_size=64)
+        sc = rrt.Scene.from_arrays(tris, mats, texs, build_bvh=False)
+        t, nodes = orc.bvh_build(sc.tris)
+        sc.tris, sc.bvh_nodes = t, nodes.view(L.NODE).reshape(-1)
+        sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+        w, h = 64, 36
+        args = (sc.tris, sc.bvh_nodes, sc.materials_array(), sc.textures, sc.camera.uniform, w, h)
+        target = orc.render(*args, 1024, 8, seed_mode=1, sample_begin=1000, want_rgba8=False)[0]
+        guides = FM.frame(orc, sc, sc.camera.uniform, w, h, 0)[0]
+        _atrium.update(args=args, target=target, guides=guides)
+    return _atrium
+
+
+@pytest.mark.parametrize("spp", [1, 2, 4])
+def test_it_denoises(rrt, orc, spp):
+    a = _atrium_frames(rrt, orc)
+    noisy = orc.render(*a["args"], spp, 8, want_rgba8=False)[0]         # pixel-stream seeds
+    g = a["guides"]
+    out = D.denoise(orc, noisy, g["normal"], g["depth"], g["albedo"], iterations=5, sigma_color=4.0, sigma_normal=0.5, sigma_depth=0.5)
+    before, after = D.rmse(noisy, a["target"]), D.rmse(out, a["target"])
+    print(f"spp {spp}: rmse noisy {before:.4f}, denoised {after:.4f}, ratio {after / before:.3f}")
+    assert np.isfinite(out).all()
+    assert after <= 0.5 * before, (spp, before, after)
+
+
+# ---- the argument checks: before any device work, each message names its field -----------------------------------------------------
+W, H, V = 6, 4, 2
+N = W * H * V
+
+
+def _opt(L, **kw):
+    o = L.MiptDenoiseOptions()
+    o.width, o.height, o.n_views, o.iterations = W, H, V, 5
+    o.sigma_color, o.sigma_normal, o.sigma_depth = 4.0, 0.5, 0.5
+    for k, v in kw.items():
+        if k == "reserved":
+            o.reserved[v] = 1
+        else:
+            setattr(o, k, v)
+    return o
+
+
+class _Planes:
+    """host planes for one call; a 16-byte aligned workspace"""
+
+    def __init__(self):
+        self.a = {k: np.zeros(N * n + 4, dtype=np.float32) for k, n in (("hdr", 3), ("normal", 3), ("depth", 1), ("albedo", 3), ("out", 3))}
+        raw = np.zeros(N * 12 + 8, dtype=np.float32)
+        off = (-raw.ctypes.data % 16) // 4
+        self.ws = raw[off: off + N * 12]
+        assert self.ws.ctypes.data % 16 == 0
+
+    def bufs(self, L, **kw):
+        b = L.MiptDenoiseBuffers()
+        for k, a in self.a.items():
+            setattr(b, k, a.ctypes.data)
+        for k, v in kw.items():
+            if k == "reserved":
+                b.reserved[v] = self.a["hdr"].ctypes.data
+            else:
+                setattr(b, k, v)
+        return b
+
+
+def _calls(lib, p):
+    """both entries with the same (opt, bufs) -> status"""
+    return (("mipt_denoise", lambda o, b: lib.mipt_denoise(o, b, 0)),
+            ("mipt_denoise_device", lambda o, b: lib.mipt_denoise_device(o, b, p.ws.ctypes.data, p.ws.nbytes, None)))
+
+
+def test_struct_sizes_and_workspace_bytes(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    assert C.sizeof(L.MiptDenoiseOptions) == 64 and C.sizeof(L.MiptDenoiseBuffers) == 64
+    assert lib.mipt_denoise_workspace_bytes(1920, 1080, 1) == 1920 * 1080 * 48
+    assert lib.mipt_denoise_workspace_bytes(W, H, V) == N * 48
+    assert lib.mipt_denoise_workspace_bytes(65535, 65535, 1) == 65535 * 65535 * 48
+    for bad in ((0, 4, 1), (4, 0, 1), (4, 4, 0), (65536, 65536, 1), (1 << 15, 1 << 15, 4), (0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF)):
+        assert lib.mipt_denoise_workspace_bytes(*bad) == 0, bad
+
+
+def test_argument_checks_of_both_entries(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    p = _Planes()
+    inf, nan = float("inf"), float("nan")
+    option_cases = [
+        (dict(width=0), "width"), (dict(height=0), "height"), (dict(n_views=0), "n_views"),
+        (dict(width=1 << 15, height=1 << 15, n_views=4), "below 2^32"), (dict(width=1 << 16, height=1 << 16, n_views=1), "below 2^32"),
+        (dict(iterations=0), "iterations"), (dict(iterations=9), "iterations"),
+        (dict(sigma_color=0.0), "sigma_color"), (dict(sigma_color=-1.0), "sigma_color"), (dict(sigma_color=inf), "sigma_color"),
+        (dict(sigma_color=nan), "sigma_color"),
+        (dict(sigma_color=1e-20), "sigma_color"),                       # sc * sc underflows to 0: k = inf
+        (dict(sigma_color=1e-18, iterations=8), "sigma_color"),         # fine for i = 0 (k = 1e36), not once 2^-i has shrunk it
+        (dict(sigma_color=1e20), "sigma_color"),                        # sc * sc overflows: k = 0
+        (dict(sigma_normal=0.0), "sigma_normal"), (dict(sigma_normal=nan), "sigma_normal"), (dict(sigma_normal=1e25), "sigma_normal"),
+        (dict(sigma_depth=-0.5), "sigma_depth"), (dict(sigma_depth=inf), "sigma_depth"), (dict(sigma_depth=1e-25), "sigma_depth"),
+        (dict(flags=1), "flags"), (dict(reserved=0), "reserved"), (dict(reserved=7), "reserved"),
+    ]
+    hdr = p.a["hdr"].ctypes.data
+    buffer_cases = [
+        (dict(hdr=None), "hdr"), (dict(out=None), "out"), (dict(reserved=0), "reserved buffer pointers"), (dict(reserved=2), "reserved buffer pointers"),
+        (dict(normal=hdr), "normal overlaps hdr"), (dict(albedo=hdr + 12 * N - 4), "albedo overlaps hdr"), (dict(out=hdr + 4), "out overlaps hdr"),
+        (dict(out=p.a["albedo"].ctypes.data), "out overlaps albedo"), (dict(depth=p.a["normal"].ctypes.data + 4 * N), "depth overlaps normal"), (dict(albedo=p.a["normal"].ctypes.data + 8), "albedo overlaps normal"),
+    ]
+    for name, call in _calls(lib, p):
+        for kw, msg in option_cases:
+            assert call(C.byref(_opt(L, **kw)), C.byref(p.bufs(L))) == L.ERR_INVALID_ARG, (name, kw)
+            err = lib.mipt_last_error().decode()
+            assert msg in err and err.startswith(name + ":"), (name, kw, err)
+        for kw, msg in buffer_cases:
+            assert call(C.byref(_opt(L)), C.byref(p.bufs(L, **kw))) == L.ERR_INVALID_ARG, (name, kw)
+            err = lib.mipt_last_error().decode()
+            assert msg in err and err.startswith(name + ":"), (name, kw, err)
+        assert call(None, C.byref(p.bufs(L))) == L.ERR_INVALID_ARG and "opt" in lib.mipt_last_error().decode()
+        assert call(C.byref(_opt(L)), None) == L.ERR_INVALID_ARG and "buffers" in lib.mipt_last_error().decode()
+    # a sigma given for an absent guide is ignored: these get past the checks, to the device (the host entry) or the device-memory
+    # check (the device entry)
+    for kw, absent in ((dict(sigma_normal=nan), "normal"), (dict(sigma_depth=0.0), "depth")):
+        rc = lib.mipt_denoise(C.byref(_opt(L, **kw)), C.byref(p.bufs(L, **{absent: None})), 0)
+        assert rc in (L.OK, L.ERR_HIP), (kw, rc, lib.mipt_last_error())
+        assert lib.mipt_denoise_device(C.byref(_opt(L, **kw)), C.byref(p.bufs(L, **{absent: None})), p.ws.ctypes.data, p.ws.nbytes, None) == L.ERR_INVALID_ARG
+        assert "hdr is not device memory" in lib.mipt_last_error().decode()
+    # out == hdr is allowed
+    rc = lib.mipt_denoise(C.byref(_opt(L)), C.byref(p.bufs(L, out=hdr)), 0)
+    assert rc in (L.OK, L.ERR_HIP), (rc, lib.mipt_last_error())
+    for a in p.a.values():
+        assert not a.any()                                              # no refused call wrote anything (zeros filter to zeros)
+
+
+def test_device_entry_checks_workspace_alignment_and_memory(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    p = _Planes()
+    f = lib.mipt_denoise_device
+    o, b = _opt(L), p.bufs(L)
+    ws, need = p.ws.ctypes.data, N * 48
+    for args, msg in [((None, need), "null workspace"), ((ws, need - 1), "too small"), ((ws, 0), "too small"), ((ws + 4, need + 16), "workspace must be 16-byte aligned")]:
+        assert f(C.byref(o), C.byref(b), *args, None) == L.ERR_INVALID_ARG, msg
+        assert msg in lib.mipt_last_error().decode(), (msg, lib.mipt_last_error())
+    for name in ("hdr", "normal", "depth", "albedo", "out"):
+        bad = p.bufs(L, **{name: p.a[name].ctypes.data + 2})
+        assert f(C.byref(o), C.byref(bad), ws, need, None) == L.ERR_INVALID_ARG
+        assert f"{name} must be 4-byte aligned" in lib.mipt_last_error().decode(), (name, lib.mipt_last_error())
+        inside = p.bufs(L, **{name: ws + 16 * N})
+        assert f(C.byref(o), C.byref(inside), ws, need, None) == L.ERR_INVALID_ARG
+        assert f"{name} overlaps the workspace" in lib.mipt_last_error().decode(), (name, lib.mipt_last_error())
+    # host memory is not device memory: refused by name, with or without a device
+    assert f(C.byref(o), C.byref(b), ws, need, None) == L.ERR_INVALID_ARG
+    assert "hdr is not device memory" in lib.mipt_last_error().decode()
+
+
+def test_host_entry_fails_loudly_without_a_device(rrt):
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present; the no-device path is exercised on the CPU-only box")
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    p = _Planes()
+    assert lib.mipt_denoise(C.byref(_opt(L)), C.byref(p.bufs(L)), 0) == L.ERR_HIP
+    assert "hipSetDevice" in lib.mipt_last_error().decode()
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=1, output_image_dimensions=(W, H), output_image_path="x.png"))
+    with pytest.raises(rrt.MiptError) as e:
+        r.denoise(np.zeros((H, W, 3), dtype=np.float32))
+    assert e.value.code == L.ERR_HIP
+
+
+def test_renderer_denoise_checks_its_arguments(rrt):
+    from rust_ray_tracing_amd import _lib as L
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=1, output_image_dimensions=(W, H), output_image_path="x.png"))
+    hdr = np.zeros((V, H, W, 3), dtype=np.float32)
+    z = np.zeros((V, H, W), dtype=np.float32)
+    for kw, msg in [(dict(hdr=np.zeros((H, W), dtype=np.float32)), "hdr"), (dict(hdr=np.zeros((H, W, 4), dtype=np.float32)), "hdr"),
+                    (dict(hdr=hdr.astype(np.float64)), "hdr"), (dict(normal=z), "normal"), (dict(normal=hdr[0]), "normal"),
+                    (dict(depth=hdr), "depth"), (dict(depth=z.astype(np.float64)), "depth"), (dict(albedo=hdr[:, :, :, :2]), "albedo"),
+                    (dict(albedo=np.zeros((V, H, W + 1, 3), dtype=np.float32)), "albedo")]:
+        args = dict(dict(hdr=hdr), **kw)
+        with pytest.raises(ValueError) as e:
+            r.denoise(**args)
+        assert str(e.value).startswith(msg + ":"), (kw, str(e.value))
+    import torch
+    with pytest.raises(ValueError) as e:
+        r.denoise(hdr, normal=torch.zeros((V, H, W, 3)))
+    assert str(e.value).startswith("normal:")
+    with pytest.raises(ValueError) as e:
+        r.denoise(torch.zeros((V, H, W, 3)))                            # a host tensor
+    assert str(e.value).startswith("hdr:")
+    # what the library checks comes back as its status and message
+    for kw, msg in [(dict(iterations=0), "iterations"), (dict(iterations=9), "iterations"), (dict(sigma_color=0.0), "sigma_color"),
+                    (dict(normal=hdr.copy(), sigma_normal=float("nan")), "sigma_normal"), (dict(depth=z, sigma_depth=-1.0), "sigma_depth")]:
+        with pytest.raises(rrt.MiptError) as e:
+            r.denoise(hdr, **kw)
+        assert e.value.code == L.ERR_INVALID_ARG and msg in str(e.value), (kw, str(e.value))

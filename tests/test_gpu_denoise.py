@@ -1,0 +1,357 @@
+"""GPU: mipt_denoise / mipt_denoise_device (csrc/denoise.hip) against the model of tests/tools/denoise_model.py, which
+tests/test_denoise_model.py holds to the contract's properties.  Every comparison is bit for bit on uint32 views (a NaN equals a NaN:
+its sign and payload are the implementation's).  The frames are the smallest at which the kernels can go wrong: one pixel, less than
+a tap's reach, one lane short of and one lane past the 64-pixel tile row, more than one block both ways; steps up to 128 on all of
+them.  Each model frame is computed once per input."""
+import ctypes as C
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import denoise_model as D  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(1, 1), (3, 2), (5, 5), (63, 5), (65, 9), (61, 37)]
+GUIDES = ("normal", "depth", "albedo")
+COMBOS = [tuple(g for g, on in zip(GUIDES, bits) if on) for bits in itertools.product((0, 1), repeat=3)]     # all eight
+WORDS = dict(hdr=3, normal=3, depth=1, albedo=3, out=3)
+POISON_F, POISON_I = 0x7FA5A5A5, 0x25A5A5A5                     # what a word nobody wrote holds (host buffers / int32 tensors)
+SIGMAS = dict(sigma_color=4.0, sigma_normal=0.5, sigma_depth=0.5)
+
+
+def _fields(size, views, seed=0):
+    """random planes [V,H,W(,k)]: radiance in [0, 4), normals of length about 1 in a few directions, depths in smooth patches with
+    misses (1e30) beside hits, albedo in (0, 1]"""
+    w, h = size
+    rng = np.random.default_rng(1000 * w + 10 * h + views + seed)
+    hdr = (rng.random((views, h, w, 3)) ** 2 * 4.0).astype(np.float32)
+    dirs = np.array([(0, 0, 1), (0, 1, 0), (0.6, 0, 0.8), (-1, 0, 0)], dtype=np.float32)
+    normal = dirs[rng.integers(0, 4, (views, h, w)) * (rng.random((views, h, w)) < 0.3)] + rng.normal(0, 0.05, (views, h, w, 3)).astype(np.float32)
+    depth = (2.0 + 0.01 * np.arange(w)[None, None, :] + rng.random((views, h, w)) * 0.3).astype(np.float32)
+    depth[rng.random((views, h, w)) < 0.15] = np.float32(1e30)
+    albedo = (0.02 + 0.98 * rng.random((views, h, w, 3))).astype(np.float32)
+    return dict(hdr=hdr, normal=np.ascontiguousarray(normal, dtype=np.float32), depth=depth, albedo=albedo)
+
+
+def _opt(L, size, views, iterations, **sig):
+    o = L.MiptDenoiseOptions()
+    o.width, o.height, o.n_views, o.iterations = size[0], size[1], views, iterations
+    s = dict(SIGMAS, **sig)
+    o.sigma_color, o.sigma_normal, o.sigma_depth = s["sigma_color"], s["sigma_normal"], s["sigma_depth"]
+    return o
+
+
+def _host(rrt, planes, combo, iterations, inplace=False, **sig):
+    """mipt_denoise on copies of the planes, a sentinel word behind out -> out [V,H,W,3]"""
+    from rust_ray_tracing_amd import _lib as L
+    v, h, w = planes["depth"].shape
+    n = v * h * w
+    b, keep = L.MiptDenoiseBuffers(), {}
+    for k in ("hdr",) + tuple(combo):
+        keep[k] = np.concatenate([planes[k].reshape(-1).view(np.uint32), [POISON_F]]).astype(np.uint32)
+        setattr(b, k, keep[k].ctypes.data)
+    out = keep["hdr"] if inplace else np.full(n * 3 + 1, POISON_F, dtype=np.uint32)
+    b.out = out.ctypes.data
+    rc = rrt.load().mipt_denoise(C.byref(_opt(L, (w, h), v, iterations, **sig)), C.byref(b), 0)
+    assert rc == 0, (rc, rrt.load().mipt_last_error())
+    for k, a in keep.items():
+        assert a[-1] == POISON_F, k
+        if not (inplace and k == "hdr"):
+            assert np.array_equal(a[:-1], planes[k].reshape(-1).view(np.uint32)), k           # an input is not written
+    assert out[-1] == POISON_F
+    return out[:-1].view(np.float32).reshape(v, h, w, 3)
+
+
+def _device(rrt, planes, combo, iterations, inplace=False, stream=None, **sig):
+    """mipt_denoise_device: all five planes are slices of one tensor, a guide that is not passed holds poison and must keep it; a
+    sentinel word behind every plane and behind the workspace's declared size -> out [V,H,W,3]"""
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    v, h, w = planes["depth"].shape
+    n = v * h * w
+    off, total = {}, 0
+    for k, words in WORDS.items():
+        off[k], total = total, total + n * words + 1
+    host = np.full(total, POISON_I, dtype=np.uint32)
+    for k in ("hdr",) + tuple(combo):
+        host[off[k]: off[k] + n * WORDS[k]] = planes[k].reshape(-1).view(np.uint32)
+    before = host.copy()
+    t = torch.from_numpy(host.view(np.int32)).cuda()
+    need = int(lib.mipt_denoise_workspace_bytes(w, h, v))
+    assert need == n * 48
+    ws = torch.full((need // 4 + 4,), POISON_I, dtype=torch.int32, device="cuda")
+    b = L.MiptDenoiseBuffers()
+    for k in ("hdr",) + tuple(combo):
+        setattr(b, k, t.data_ptr() + 4 * off[k])
+    b.out = t.data_ptr() + 4 * off["hdr" if inplace else "out"]
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()                                                # the fills above ran on torch's current stream, which need not be `stream`
+    rc = lib.mipt_denoise_device(C.byref(_opt(L, (w, h), v, iterations, **sig)), C.byref(b), ws.data_ptr(), need, stream)
+    assert rc == 0, (rc, lib.mipt_last_error())
+    torch.cuda.synchronize()
+    got = t.cpu().numpy().view(np.uint32)
+    written = "hdr" if inplace else "out"
+    for k, words in WORDS.items():
+        lo, hi = off[k], off[k] + n * words
+        assert got[hi] == POISON_I, k                                      # nothing is written behind a plane
+        if k != written:
+            assert np.array_equal(got[lo:hi], before[lo:hi]), k            # inputs, and a plane that was not passed, are untouched
+    assert bool(torch.all(ws[need // 4:] == POISON_I))                      # nor behind the workspace's declared size
+    lo = off[written]
+    return got[lo: lo + n * 3].view(np.float32).reshape(v, h, w, 3)
+
+
+def _model(orc, planes, combo, iterations, **sig):
+    return D.denoise(orc, planes["hdr"], **{k: planes[k] for k in combo}, iterations=iterations, **dict(SIGMAS, **sig))
+
+
+# ---- sizes x views x iterations x guide combinations x entries ----------------------------------------------------------------------
+@pytest.mark.parametrize("views", [1, 3])
+@pytest.mark.parametrize("size", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
+def test_random_fields_against_the_model(rrt, orc, size, views):
+    planes = _fields(size, views)
+    changed = 0
+    for iterations in (1, 5, 8):
+        for combo in COMBOS:
+            want = _model(orc, planes, combo, iterations)
+            assert np.isfinite(want).all()
+            changed += not D.same_bits(want, planes["hdr"])
+            for entry in (_host, _device):
+                got = entry(rrt, planes, combo, iterations)
+                assert D.same_bits(got, want), (size, views, iterations, combo, entry.__name__, int((got.view(np.uint32) != want.view(np.uint32)).sum()))
+    assert changed == 24 or size == (1, 1)                                   # the filter does something on every frame but the single pixel
+
+
+@pytest.mark.parametrize("entry", ["host", "device"])
+def test_out_may_be_hdr(rrt, orc, entry):
+    f = _host if entry == "host" else _device
+    for size, views, iterations in (((65, 9), 3, 5), ((61, 37), 1, 8), ((3, 2), 1, 1)):
+        planes = _fields(size, views, seed=1)
+        for combo in (COMBOS[0], COMBOS[-1]):
+            want = _model(orc, planes, combo, iterations)
+            assert D.same_bits(f(rrt, planes, combo, iterations, inplace=True), want), (size, combo)
+
+
+def test_special_values(rrt, orc):
+    """an inf and a NaN radiance, a zero, a negative and a NaN albedo, a NaN normal and misses beside hits: the NaN rule of the header"""
+    size, views = (61, 37), 1
+    planes = _fields(size, views, seed=2)
+    planes["hdr"][0, 5, 7, 1] = np.inf
+    planes["hdr"][0, 30, 50] = np.nan
+    planes["hdr"][0, 20, 3, 2] = -np.inf
+    planes["albedo"][0, 10, 10] = 0.0
+    planes["albedo"][0, 11, 40, 0] = np.nan
+    planes["albedo"][0, 12, 41, 2] = -0.5
+    planes["albedo"][0, 2, 2] = np.float32(1.0 / 256.0)                      # the floor itself: the comparison is strict
+    planes["normal"][0, 25, 25, 0] = np.nan
+    planes["depth"][0, 15:20, 30:35] = 1e30
+    planes["depth"][0, 17, 32] = 3.0                                         # one hit in a patch of misses
+    for iterations in (1, 2):                                                # a NaN reaches 2 * (1 + 2) pixels each way: most of the frame stays finite
+        for combo in COMBOS:
+            want = _model(orc, planes, combo, iterations)
+            assert np.isnan(want).any() and np.isfinite(want).sum() > want.size // 2
+            for entry in (_host, _device):
+                got = entry(rrt, planes, combo, iterations)
+                assert D.same_bits(got, want), (iterations, combo, entry.__name__)
+    # a NaN or zero albedo alone leaves everything finite (the floor), and out = c * floor
+    clean = _fields(size, views, seed=2)
+    clean["albedo"][0, 10, 10] = 0.0
+    clean["albedo"][0, 11, 40, 0] = np.nan
+    want = _model(orc, clean, ("albedo",), 5)
+    assert np.isfinite(want).all() and D.same_bits(_device(rrt, clean, ("albedo",), 5), want)
+
+
+def test_sigmas_reach_the_kernel(rrt, orc):
+    planes = _fields((61, 37), 1, seed=3)
+    base = _model(orc, planes, GUIDES, 5)
+    for sig in (dict(sigma_color=0.37), dict(sigma_normal=2.5), dict(sigma_depth=7.0), dict(sigma_color=1e-3, sigma_normal=1e4, sigma_depth=1e-4)):
+        want = _model(orc, planes, GUIDES, 5, **sig)
+        assert not D.same_bits(want, base), sig
+        for entry in (_host, _device):
+            assert D.same_bits(entry(rrt, planes, GUIDES, 5, **sig), want), (sig, entry.__name__)
+
+
+def test_many_tiny_views(rrt, orc):
+    """more views than one grid dimension could index the naive way is out of a test's reach; 700 views of 3x2 still walk the
+    (view, tile) decode far past one block"""
+    planes = _fields((3, 2), 700, seed=4)
+    want = _model(orc, planes, GUIDES, 2)
+    assert D.same_bits(_device(rrt, planes, GUIDES, 2), want)
+    assert D.same_bits(want[5], _model(orc, {k: a[5:6] for k, a in planes.items()}, GUIDES, 2)[0])     # views never see each other
+
+
+# ---- real frames: the buffers the render and the feature pass leave in HBM ------------------------------------------------------------
+_scenes = {}
+
+
+def _scene(rrt, kind):
+    if kind not in _scenes:
+        from rust_ray_tracing_amd import synth
+        kw = dict(n_target=20000, tex_size=64) if kind == "atrium" else {}
+        tris, mats, texs, cam = synth.make_scene(kind, **kw)
+        sc = rrt.Scene.from_arrays(tris, mats, texs)
+        sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+        sc.upload(0)
+        _scenes[kind] = sc
+    return _scenes[kind]
+
+
+def _cameras(rrt, sc):
+    cam = sc.camera
+    more = [rrt.Camera(position=(cam.position[0] + 0.3, cam.position[1] - 0.2, cam.position[2] + 0.1), pitch=cam.pitch + 7.0, yaw=cam.yaw - 11.0),
+            rrt.Camera(position=(cam.position[0] - 0.4, cam.position[1] + 0.1, cam.position[2]), pitch=cam.pitch - 5.0, yaw=cam.yaw + 9.0)]
+    for c in more:
+        c.update_view()
+    return [cam] + more
+
+
+@pytest.mark.parametrize("kind,size,spp,seed_mode", [("cornell", (61, 37), 1, 0), ("atrium", (64, 36), 2, 1)])
+def test_render_denoised_is_the_three_calls_and_the_model(rrt, orc, kind, size, spp, seed_mode):
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc = _scene(rrt, kind)
+    cams = _cameras(rrt, sc)
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=spp, max_ray_depth=8, output_image_dimensions=size, output_image_path="/dev/null", seed_mode=seed_mode,
+                                             traversal=L.TRAVERSAL_CULLED))
+    den, noisy, feat, stats = r.render_denoised(sc, cams)
+    torch.cuda.synchronize()
+    w, h = size
+    assert tuple(den.shape) == (3, h, w, 3) and den.is_cuda and set(feat) == {"depth", "normal", "albedo"} and stats["pixels"] == 3 * w * h
+    # the three calls made separately
+    table = np.ascontiguousarray(np.stack([np.asarray(c.uniform, dtype=L.CAMERA).reshape(()) for c in cams]))
+    opt = rrt.make_options(w, h, spp, 8, seed_mode=seed_mode, traversal=L.TRAVERSAL_CULLED)
+    hdr = torch.zeros((3, h, w, 3), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    assert lib.mipt_render_batch_device(sc._handle, L.ptr(table), 3, C.byref(opt), hdr.data_ptr(), None, stream, None) == 0
+    one = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=8, output_image_dimensions=size, output_image_path="/dev/null", seed_mode=seed_mode,
+                                               traversal=L.TRAVERSAL_CULLED))
+    sep, _ = one.render_features(sc, cams, ("depth", "normal", "albedo"), device=True)
+    assert torch.equal(hdr.view(torch.int32), noisy.view(torch.int32))
+    for k in sep:
+        assert torch.equal(sep[k].view(torch.int32), feat[k].view(torch.int32)), k
+    planes = dict(hdr=noisy.cpu().numpy(), **{k: v.cpu().numpy() for k, v in feat.items()})
+    assert D.same_bits(_device(rrt, planes, GUIDES, 5), den.cpu().numpy())
+    # and the model, applied to the buffers the GPU produced; numpy arrays and a single view through Renderer.denoise
+    want = _model(orc, planes, GUIDES, 5)
+    assert D.same_bits(den.cpu().numpy(), want)
+    assert not D.same_bits(want, planes["hdr"])
+    got = r.denoise(planes["hdr"][1], planes["normal"][1], planes["depth"][1], planes["albedo"][1])
+    assert isinstance(got, np.ndarray) and got.shape == (h, w, 3) and D.same_bits(got, want[1])
+    got = r.denoise(noisy, depth=feat["depth"], iterations=3, sigma_depth=0.25)
+    assert D.same_bits(got.cpu().numpy(), _model(orc, planes, ("depth",), 3, sigma_depth=0.25))
+
+
+def test_torch_tensors_on_a_side_stream(rrt, orc):
+    import torch
+    planes = _fields((65, 9), 3, seed=5)
+    want = _model(orc, planes, GUIDES, 5)
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=1, output_image_dimensions=(65, 9), output_image_path="/dev/null"))
+    dev = {k: torch.from_numpy(a).cuda() for k, a in planes.items()}
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        busy = torch.ones((1 << 22,), device="cuda").cumsum(0)               # work in front of the passes on the side stream
+        a = r.denoise(dev["hdr"], dev["normal"], dev["depth"], dev["albedo"])                     # torch's current stream
+    b = r.denoise(dev["hdr"], dev["normal"], dev["depth"], dev["albedo"], stream=side)            # the one given
+    c = _device(rrt, planes, GUIDES, 5, stream=side.cuda_stream)
+    side.synchronize()
+    assert busy[-1].item() == float(1 << 22)
+    assert a.is_cuda and tuple(a.shape) == planes["hdr"].shape
+    assert D.same_bits(a.cpu().numpy(), want) and D.same_bits(b.cpu().numpy(), want) and D.same_bits(c, want)
+    for k, t in dev.items():
+        assert np.array_equal(t.cpu().numpy().view(np.uint32), planes[k].view(np.uint32)), k       # the inputs are not written
+
+
+# ---- refusals: status, a message naming the field, nothing written, and everything works as before ------------------------------------
+def test_refusals_leave_everything_as_before(rrt, orc):
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc = _scene(rrt, "cornell")
+    hdr0 = np.zeros((12, 16, 3), dtype=np.float32)
+    ro = rrt.make_options(16, 12, 2, 3)
+    L.check(lib.mipt_render(sc._handle, L.ptr(sc.camera.uniform), C.byref(ro), L.ptr(hdr0), None, None), "mipt_render")
+    size, views = (61, 37), 1
+    w, h = size
+    n = w * h
+    planes = _fields(size, views, seed=6)
+    want = _model(orc, planes, GUIDES, 5)
+    assert D.same_bits(_device(rrt, planes, GUIDES, 5), want)
+    need = n * 48
+    t = torch.full((n * 13 + 24,), POISON_I, dtype=torch.int32, device="cuda")
+    ws = torch.full((need // 4 + 4,), POISON_I, dtype=torch.int32, device="cuda")
+    host = np.full(n * 3, POISON_F, dtype=np.uint32)
+    base = t.data_ptr()
+    ptr = dict(hdr=base, normal=base + 12 * n + 16, depth=base + 24 * n + 32, albedo=base + 28 * n + 48, out=base + 40 * n + 64)   # 16 bytes between planes
+
+    def bufs(**kw):
+        b = L.MiptDenoiseBuffers()
+        for k, v in dict(ptr, **kw).items():
+            if k == "reserved":
+                b.reserved[v] = base
+            else:
+                setattr(b, k, v)
+        return b
+
+    def opt(**kw):
+        o = _opt(L, size, views, 5)
+        for k, v in kw.items():
+            if k == "reserved":
+                o.reserved[v] = 1
+            else:
+                setattr(o, k, v)
+        return o
+
+    def refused(msg, o=None, b=None, workspace=None, nbytes=need):
+        o = opt() if o is None else o
+        b = bufs() if b is None else b
+        rc = lib.mipt_denoise_device(C.byref(o) if o != "null" else None, C.byref(b) if b != "null" else None,
+                                     ws.data_ptr() if workspace is None else workspace, nbytes, None)
+        err = lib.mipt_last_error().decode()
+        assert rc == L.ERR_INVALID_ARG and msg in err and err.startswith("mipt_denoise_device:"), (msg, rc, err)
+
+    inf, nan = float("inf"), float("nan")
+    refused("opt", o="null")
+    refused("buffers", b="null")
+    refused("hdr", b=bufs(hdr=None))
+    refused("out", b=bufs(out=None))
+    for kw, msg in [(dict(width=0), "width"), (dict(height=0), "height"), (dict(n_views=0), "n_views"), (dict(width=1 << 16, height=1 << 16), "below 2^32"),
+                    (dict(iterations=0), "iterations"), (dict(iterations=9), "iterations"), (dict(sigma_color=0.0), "sigma_color"),
+                    (dict(sigma_color=nan), "sigma_color"), (dict(sigma_color=1e-18, iterations=8), "sigma_color"), (dict(sigma_normal=inf), "sigma_normal"),
+                    (dict(sigma_depth=-1.0), "sigma_depth"), (dict(sigma_depth=1e-25), "sigma_depth"), (dict(flags=2), "flags"), (dict(reserved=3), "reserved")]:
+        refused(msg, o=opt(**kw))
+    refused("reserved buffer pointers", b=bufs(reserved=1))
+    refused("normal overlaps hdr", b=bufs(normal=base + 4))
+    refused("out overlaps albedo", b=bufs(out=ptr["albedo"]))
+    refused("out overlaps hdr", b=bufs(out=base + 12 * n - 4, normal=None))
+    refused("null workspace", workspace=0)
+    refused("too small", nbytes=need - 16)
+    refused("workspace must be 16-byte aligned", workspace=ws.data_ptr() + 8)
+    refused("depth must be 4-byte aligned", b=bufs(depth=ptr["depth"] + 1))
+    refused("out overlaps the workspace", b=bufs(out=ws.data_ptr() + 32 * n))
+    assert base % 16 == 0
+    refused("hdr overlaps the workspace", workspace=base)
+    refused("albedo is not device memory of hdr's device", b=bufs(albedo=host.ctypes.data))
+    refused("workspace is not device memory of hdr's device", workspace=(host.ctypes.data + 15) & ~15, nbytes=1 << 40)
+    refused("hdr is not device memory", b=bufs(hdr=host.ctypes.data))
+    assert bool(torch.all(t == POISON_I)) and bool(torch.all(ws == POISON_I)) and np.all(host == POISON_F)      # no refused call wrote anything
+    # the host entry refuses the same way
+    b = L.MiptDenoiseBuffers()
+    b.hdr, b.out = host.ctypes.data, host.ctypes.data + 4
+    assert lib.mipt_denoise(C.byref(opt()), C.byref(b), 0) == L.ERR_INVALID_ARG and "out overlaps hdr" in lib.mipt_last_error().decode()
+    b.out = host.ctypes.data
+    assert lib.mipt_denoise(C.byref(opt()), C.byref(b), 1 << 20) == L.ERR_HIP and np.all(host == POISON_F)        # no such device
+    # the scene renders and a following denoise works as before
+    hdr1 = np.zeros_like(hdr0)
+    L.check(lib.mipt_render(sc._handle, L.ptr(sc.camera.uniform), C.byref(ro), L.ptr(hdr1), None, None), "mipt_render")
+    assert np.array_equal(hdr0.view(np.uint32), hdr1.view(np.uint32))
+    assert D.same_bits(_device(rrt, planes, GUIDES, 5), want) and D.same_bits(_host(rrt, planes, GUIDES, 5), want)
