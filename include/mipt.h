@@ -433,6 +433,107 @@ MIPT_API int mipt_denoise(const MiptDenoiseOptions *opt, const MiptDenoiseBuffer
 MIPT_API int mipt_denoise_device(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *device, void *d_workspace,
                                  uint64_t workspace_bytes, void *hip_stream);
 
+/* ---- temporal accumulation: last frame's history, reprojected into this frame and blended with it ----------------------------------
+ * The step from a denoised still to a moving sequence (the first half of an SVGF-style pipeline; the a-trous filter above is the
+ * second): every pixel looks up where its surface point was in the previous frame, gathers that frame's accumulated colour with four
+ * bilinear taps that must agree with it in material, normal and depth, and blends this frame's sample into it (csrc/temporal.hip).
+ * The reference has nothing of this kind: the operation is defined HERE, and the kernel and tests/tools/temporal_model.py obey it bit
+ * for bit.  Every operator is one rounded f32 operation, nothing is fused, and the operations run in the order written.
+ *
+ * Buffers.  View-major planar, row 0 = top -- what mipt_render_batch and mipt_render_features write:
+ *   hdr       3 f32 / pixel, required: this frame's radiance
+ *   position  3 f32 / pixel, required: the first hit's world position
+ *   normal    3 f32 / pixel, required; used as given, not normalised
+ *   depth     1 f32 / pixel, required; a miss is 1e30
+ *   material  1 u32 / pixel, required
+ *   albedo    3 f32 / pixel, optional: the colour is demodulated before the blend and re-modulated after
+ *   out       3 f32 / pixel, required; may be hdr
+ *   length    1 f32 / pixel, optional: the history length of the pixel after this frame
+ *   variance  1 f32 / pixel, optional: the variance of the luminance over the history
+ * `cameras` holds n_views MiptCamera records in HOST memory, for both entries: the cameras that produced this frame.  The previous
+ * frame's cameras are not passed in: a history carries the camera that made it.
+ *
+ * History.  mipt_temporal_history_bytes() = 64*V + 48*N bytes, N = V*W*H, 16-byte aligned, everything view-major:
+ *   byte 0           V camera records of 16 f32: B[3][3] row-major, C[3], four zeros
+ *   byte 64*V        plane 0: N float4 {c.r, c.g, c.b, len}   the accumulated (demodulated) colour and the history length
+ *   byte 64*V + 16*N plane 1: N float4 {n.x, n.y, n.z, z}     the normal and depth of the frame that wrote it
+ *   byte 64*V + 32*N plane 2: N float4 {m1, m2, bits(material), 0}   the first two moments of the luminance, the material id's bits
+ * history_in = NULL is the first frame: every pixel starts anew.  history_out is always written in full and must not overlap
+ * history_in; a sequence keeps two and swaps them.
+ *
+ * Camera record of view v, formed on the host in binary64 with nothing contracted: a[r][c] = look_at[c][r] (the matrix
+ * mat4.rs:143-152 applies to the screen vector);
+ *   k00 = (a11*a22) - (a12*a21)   k01 = (a12*a20) - (a10*a22)   k02 = (a10*a21) - (a11*a20)
+ *   k10 = (a02*a21) - (a01*a22)   k11 = (a00*a22) - (a02*a20)   k12 = (a01*a20) - (a00*a21)
+ *   k20 = (a01*a12) - (a02*a11)   k21 = (a02*a10) - (a00*a12)   k22 = (a00*a11) - (a01*a10)
+ *   det = ((a00*k00) + (a01*k01)) + (a02*k02);   B[i][j] = k[j][i] / det rounded to f32 (the inverse of a);   C = camera.position.
+ * A det that is 0 or not finite, or a B entry that is not finite, is MIPT_ERR_INVALID_ARG naming cameras[v].look_at.
+ *
+ * Pixel p = (x, y) of view v, in f32.  Every comparison is written so that a NaN takes the "reject / reset" side.
+ *   - a = albedo > 1/256 ? albedo : 1/256 per channel and cc = hdr / a; without albedo cc = hdr.
+ *   - l = ((0.2126f*cc.r) + (0.7152f*cc.g)) + (0.0722f*cc.b).
+ *   - RESET means c = cc, len = 1, m1 = l, m2 = l*l.
+ *   - reset if history_in is NULL; reset if !(depth < 1e30f).
+ *   - with B, C of history_in's record for view v: d = position - C, v_i = ((B[i][0]*d.x) + (B[i][1]*d.y)) + (B[i][2]*d.z);
+ *     reset if !(v_z > 0).
+ *   - sx = -(v_x / v_z), sy = v_y / v_z, aspect = (float)W / (float)H;
+ *     fx = (((sx / aspect) + 1) * 0.5f) * W and fy = H - (((sy + 1) * 0.5f) * H), W and H as f32: the exact inverse of
+ *     cpu.rs:31-35,44 -- pixel column and row are integer coordinates, row 0 the top.
+ *   - reset unless fx >= -1 && fx < W && fy >= -1 && fy < H.  Only then x0 = floorf(fx) as an integer, wx = fx - floorf(fx), and
+ *     likewise y0, wy.
+ *   - d2 = ((d.x*d.x) + (d.y*d.y)) + (d.z*d.z).
+ *   - taps q in the order (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) of view v of history_in, with the weights
+ *     (1-wx)*(1-wy), wx*(1-wy), (1-wx)*wy, wx*wy.
+ *   - a tap is accepted when it lies inside [0,W) x [0,H), its material bits equal the pixel's,
+ *     ((dx*dx) + (dy*dy)) + (dz*dz) <= normal_tol for (dx,dy,dz) = n_p - n_q, and fabsf(d2 - (z_q*z_q)) <= depth_tol * d2.
+ *   - an accepted tap adds: sw = sw + w, s_ch = s_ch + (w*c_q.ch), sl = sl + (w*len_q), s1 = s1 + (w*m1_q), s2 = s2 + (w*m2_q), all
+ *     sums starting at +0.  A rejected tap is not added at all.
+ *   - reset unless sw > 1/64.
+ *   - otherwise cp = s/sw per channel, lp = sl/sw; ln = lp + 1, ln = ln < max_history ? ln : max_history; al = 1/ln,
+ *     al = al > alpha_min ? al : alpha_min; c = cp + ((cc - cp) * al), m1 = (s1/sw) + ((l - (s1/sw)) * al),
+ *     m2 = (s2/sw) + (((l*l) - (s2/sw)) * al), len = ln.
+ *   - written: history_out {c, len}, {normal, depth}, {m1, m2, material, 0} and this frame's camera record in its header;
+ *     out = c * a (c without albedo); length = len; variance = m2 - (m1*m1), then variance > 0 ? variance : 0.
+ * The NaN rule of the query section applies: a NaN this arithmetic produces is a NaN everywhere, sign and payload the implementation's.
+ *
+ * Scope.  The geometry is taken to be static between the two frames.  After mipt_scene_update_* the material, normal and depth
+ * checks reject what they catch and the rest ghosts; motion vectors for moving parts are not part of this entry.
+ *
+ * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- a null opt, cameras, buffers or required plane; zero width, height or n_views; n_views*W*H >= MIPT_BATCH_MAX_PIXELS;
+ * alpha_min outside 0 ... 1, max_history not finite and >= 1, a tolerance not finite and >= 0; non-zero flags or reserved fields; a
+ * singular camera; buffers that overlap (out == hdr alone is allowed); for the device entry a pointer that is not 4-byte aligned (a
+ * history: 16-byte) and a pointer that is not device memory of one common device (hdr's). */
+typedef struct {
+    uint32_t width, height, n_views;
+    uint32_t flags;               /* must be 0 */
+    float    alpha_min;           /* 0 ... 1: floor of the blend factor; 0 = plain running mean up to max_history */
+    float    max_history;         /* >= 1, finite: cap of the history length */
+    float    normal_tol;          /* >= 0, finite: largest |n_p - n_q|^2 of an accepted tap */
+    float    depth_tol;           /* >= 0, finite: largest |d2 - z_q^2| / d2 of an accepted tap */
+    uint32_t reserved[8];         /* must be 0 */
+} MiptTemporalOptions;            /* 64 B */
+typedef struct {
+    const float    *hdr, *position, *normal, *depth;   /* 3,3,3,1 f32 / pixel, required */
+    const uint32_t *material;                          /* 1 u32 / pixel, required */
+    const float    *albedo;                            /* 3 f32, optional: demodulate before, re-modulate after */
+    const void     *history_in;                        /* NULL = first frame: every pixel starts anew */
+    void           *history_out;                       /* required; must not overlap history_in */
+    float          *out;                               /* 3 f32, required; may be hdr */
+    float          *length, *variance;                 /* 1 f32 each, optional */
+    void           *reserved[5];                       /* must be NULL */
+} MiptTemporalBuffers;            /* 128 B */
+
+/* Bytes of one history for this size: 64*V + 48*V*W*H.  0 = an invalid size. */
+MIPT_API uint64_t mipt_temporal_history_bytes(uint32_t width, uint32_t height, uint32_t n_views);
+/* HOST buffers and HOST histories, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_temporal(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *host, int device_id);
+/* DEVICE buffers and histories of one device (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream).
+ * Stream-ordered: it does not block and allocates nothing, like mipt_denoise_device; the camera table is host memory and may be
+ * freed on return.  The call writes history_out, out and the optional outputs that are given, and nothing else. */
+MIPT_API int mipt_temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
+                                  void *hip_stream);
+
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);
 /* d_packed_all: tile_world slices of mipt_packed_pixels()*3 floats, rank-major (the layout an

@@ -116,6 +116,17 @@ struct DenoiseSettings {
     float sigma_color = 4.0f, sigma_normal = 0.5f, sigma_depth = 0.5f;
 };
 
+// Renderer::temporal: the blend's settings (MiptTemporalOptions; the defaults of the Python mirror) and what a call keeps
+struct TemporalSettings {
+    float alpha_min = 0.0f, max_history = 32.0f;           // floor of the blend factor; cap of the history length
+    float normal_tol = 0.1f, depth_tol = 0.1f;             // largest |n_p - n_q|^2 and |d2 - z_q^2| / d2 of an accepted tap
+    bool want_length = false, want_variance = false;
+};
+struct TemporalState {
+    std::vector<uint32_t> history;                         // mipt_temporal_history_bytes() / 4 words in the header's layout; empty = no frame yet
+    std::vector<float> length, variance;                   // 1 f32 / pixel where asked for
+};
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -394,6 +405,55 @@ class Renderer {                                           // src/renderer.rs:8-
         b.out = out.data();
         const int rc = mipt_denoise(&o, &b, options.device_id);
         if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+
+    // The temporal accumulation (mipt_temporal, include/mipt.h "temporal accumulation") over host images of this renderer's width and
+    // height: `hdr` holds cameras.size() frames of 3 f32 per pixel, view-major; `guides` the position, normal, depth and material
+    // images of render_features for the same cameras, and the albedo image if the frame is to be demodulated (empty = absent).
+    // `state.history` is the previous call's (empty = the first frame) and is replaced by this frame's; `out` is resized and filled
+    // and may be `hdr` itself.  Returns a MiptStatus; a size that does not fit is MIPT_ERR_INVALID_ARG before the library is called.
+    int temporal(const std::vector<float> &hdr, const std::vector<MiptCamera> &cameras, const FeatureImages &guides, TemporalState &state,
+                 std::vector<float> &out, const TemporalSettings &settings = TemporalSettings()) const {
+        MiptTemporalOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.n_views = (uint32_t)cameras.size();
+        o.alpha_min = settings.alpha_min; o.max_history = settings.max_history; o.normal_tol = settings.normal_tol; o.depth_tol = settings.depth_tol;
+        const uint64_t n = (uint64_t)o.width * o.height * o.n_views;
+        const bool sized = n != 0 && n < MIPT_BATCH_MAX_PIXELS;              // an impossible size is left to the library to refuse
+        const uint64_t words = mipt_temporal_history_bytes(o.width, o.height, o.n_views) / 4;
+        auto fits = [&](size_t have, uint64_t want, const char *name, bool required) {
+            if ((have == 0 && !required) || have == want) return true;
+            log_error(std::string("Renderer::temporal: ") + name + " holds " + std::to_string(have) + " values, expected " + std::to_string(want));
+            return false;
+        };
+        if (sized && !(fits(hdr.size(), n * 3, "hdr", true) && fits(guides.position.size(), n * 3, "position", true) &&
+                       fits(guides.normal.size(), n * 3, "normal", true) && fits(guides.depth.size(), n, "depth", true) &&
+                       fits(guides.material.size(), n, "material", true) && fits(guides.albedo.size(), n * 3, "albedo", false) &&
+                       fits(state.history.size(), words, "history", false)))
+            return MIPT_ERR_INVALID_ARG;
+        static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
+        static const uint32_t no_material = 0;
+        static const MiptCamera no_camera{};
+        if (&out != &hdr) out.assign(sized ? (size_t)n * 3 : 3, 0.0f);
+        std::vector<uint32_t> next(sized ? (size_t)words : 4, 0u);
+        state.length.assign(settings.want_length ? (sized ? (size_t)n : 1) : 0, 0.0f);
+        state.variance.assign(settings.want_variance ? (sized ? (size_t)n : 1) : 0, 0.0f);
+        MiptTemporalBuffers b{};
+        b.hdr = hdr.empty() ? no_pixel : hdr.data();
+        b.position = guides.position.empty() ? no_pixel : guides.position.data();
+        b.normal = guides.normal.empty() ? no_pixel : guides.normal.data();
+        b.depth = guides.depth.empty() ? no_pixel : guides.depth.data();
+        b.material = guides.material.empty() ? &no_material : guides.material.data();
+        b.albedo = guides.albedo.empty() ? nullptr : guides.albedo.data();
+        b.history_in = state.history.empty() ? nullptr : state.history.data();
+        b.history_out = next.data();
+        b.out = out.data();
+        b.length = settings.want_length ? state.length.data() : nullptr;
+        b.variance = settings.want_variance ? state.variance.data() : nullptr;
+        const int rc = mipt_temporal(&o, cameras.empty() ? &no_camera : cameras.data(), &b, options.device_id);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        else state.history.swap(next);
         return rc;
     }
 

@@ -125,6 +125,22 @@ class MiptDenoiseBuffers(C.Structure):
 
 assert C.sizeof(MiptDenoiseOptions) == 64 and C.sizeof(MiptDenoiseBuffers) == 64
 
+
+# ---- temporal accumulation (include/mipt.h "temporal accumulation") ----
+class MiptTemporalOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("flags", C.c_uint32),
+                ("alpha_min", C.c_float), ("max_history", C.c_float), ("normal_tol", C.c_float), ("depth_tol", C.c_float),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class MiptTemporalBuffers(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("material", C.c_void_p),
+                ("albedo", C.c_void_p), ("history_in", C.c_void_p), ("history_out", C.c_void_p), ("out", C.c_void_p),
+                ("length", C.c_void_p), ("variance", C.c_void_p), ("reserved", C.c_void_p * 5)]
+
+
+assert C.sizeof(MiptTemporalOptions) == 64 and C.sizeof(MiptTemporalBuffers) == 128
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -174,6 +190,7 @@ EXPORTS = [
     "mipt_query_closest", "mipt_query_closest_device", "mipt_query_occluded", "mipt_query_occluded_device",
     "mipt_render_features", "mipt_render_features_device",
     "mipt_denoise_workspace_bytes", "mipt_denoise", "mipt_denoise_device",
+    "mipt_temporal_history_bytes", "mipt_temporal", "mipt_temporal_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
 ]
 
@@ -310,6 +327,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_denoise.restype = C.c_int
     lib.mipt_denoise_device.argtypes = [do, db, vp, u64, vp]
     lib.mipt_denoise_device.restype = C.c_int
+    to, tb = C.POINTER(MiptTemporalOptions), C.POINTER(MiptTemporalBuffers)
+    lib.mipt_temporal_history_bytes.argtypes = [u32, u32, u32]
+    lib.mipt_temporal_history_bytes.restype = u64
+    lib.mipt_temporal.argtypes = [to, vp, tb, C.c_int]
+    lib.mipt_temporal.restype = C.c_int
+    lib.mipt_temporal_device.argtypes = [to, vp, tb, vp]
+    lib.mipt_temporal_device.restype = C.c_int
     return lib
 
 

@@ -24,23 +24,11 @@ void unpack(const MiptDenoiseBuffers *b, const void *p[kBuffers]) {
     p[0] = b->hdr; p[1] = b->normal; p[2] = b->depth; p[3] = b->albedo; p[4] = b->out;
 }
 
-uint64_t pixels_of(uint32_t width, uint32_t height, uint32_t n_views) {     // 0 = an invalid size
-    if (width == 0 || height == 0 || n_views == 0) return 0;
-    const uint64_t wh = (uint64_t)width * height;                            // < 2^64
-    if (wh >= MIPT_BATCH_MAX_PIXELS || wh * n_views >= MIPT_BATCH_MAX_PIXELS) return 0;
-    return wh * n_views;
-}
-
 // 1 / sigma^2 in f32 as include/mipt.h forms it; false unless sigma and the result are finite and greater than 0
 bool inverse_square(float sigma, float *k) {
     if (!std::isfinite(sigma) || !(sigma > 0.0f)) return false;
     *k = 1.0f / (sigma * sigma);
     return std::isfinite(*k) && *k > 0.0f;
-}
-
-bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 // everything that needs no device: on success d holds the sizes and the filter constants
@@ -51,7 +39,7 @@ int validate(const char *who, const MiptDenoiseOptions *opt, const MiptDenoiseBu
     if (!buf->out) return fail(MIPT_ERR_INVALID_ARG, "%s: null out", who);
     if (opt->width == 0 || opt->height == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: width and height must be greater than 0", who);
     if (opt->n_views == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: n_views == 0", who);
-    n_pix = pixels_of(opt->width, opt->height, opt->n_views);
+    n_pix = mipt::batch_pixels(opt->width, opt->height, opt->n_views);
     if (n_pix == 0)
         return fail(MIPT_ERR_INVALID_ARG, "%s: %u views of %ux%u: n_views*width*height must stay below 2^32", who, opt->n_views, opt->width, opt->height);
     if (opt->iterations < 1 || opt->iterations > 8) return fail(MIPT_ERR_INVALID_ARG, "%s: iterations %u: must be 1 ... 8", who, opt->iterations);
@@ -81,7 +69,7 @@ int validate(const char *who, const MiptDenoiseOptions *opt, const MiptDenoiseBu
     for (int i = 0; i < kBuffers; i++)
         for (int j = i + 1; j < kBuffers; j++) {
             if (!p[i] || !p[j] || (i == 0 && j == 4 && p[i] == p[j])) continue;
-            if (overlap(p[i], n_pix * kFields[i].words * 4, p[j], n_pix * kFields[j].words * 4))
+            if (mipt::ranges_overlap(p[i], n_pix * kFields[i].words * 4, p[j], n_pix * kFields[j].words * 4))
                 return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps %s (only out == hdr is allowed)", who, kFields[j].name, kFields[i].name);
         }
 
@@ -114,7 +102,7 @@ int denoise_device(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *buf,
     unpack(buf, p);
     for (int i = 0; i < kBuffers; i++) {
         if ((uintptr_t)p[i] & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be 4-byte aligned", who, kFields[i].name);
-        if (p[i] && overlap(p[i], n_pix * kFields[i].words * 4, d_workspace, need))
+        if (p[i] && mipt::ranges_overlap(p[i], n_pix * kFields[i].words * 4, d_workspace, need))
             return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps the workspace", who, kFields[i].name);
     }
     int device = -1;
@@ -161,7 +149,7 @@ int denoise_host(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *buf, i
 extern "C" {
 
 uint64_t mipt_denoise_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views) {
-    return pixels_of(width, height, n_views) * kWorkspaceBytesPerPixel;
+    return mipt::batch_pixels(width, height, n_views) * kWorkspaceBytesPerPixel;
 }
 int mipt_denoise(const MiptDenoiseOptions *opt, const MiptDenoiseBuffers *host, int device_id) {
     MIPT_NO_THROW(denoise_host(opt, host, device_id))

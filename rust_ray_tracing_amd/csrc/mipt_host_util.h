@@ -72,6 +72,21 @@ inline int grow_device_buffer(void **p, size_t *have, size_t want_bytes) {
     return MIPT_OK;
 }
 
+// n_views * width * height for the entries that take planes of n_views frames (denoise, temporal); 0 = an invalid size: a zero, or
+// not below MIPT_BATCH_MAX_PIXELS
+inline uint64_t batch_pixels(uint32_t width, uint32_t height, uint32_t n_views) {
+    if (width == 0 || height == 0 || n_views == 0) return 0;
+    const uint64_t wh = (uint64_t)width * height;                            // < 2^64
+    if (wh >= MIPT_BATCH_MAX_PIXELS || wh * n_views >= MIPT_BATCH_MAX_PIXELS) return 0;
+    return wh * n_views;
+}
+
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
 // MIPT_OK if `p` is device memory of HIP device `device`, else MIPT_ERR_INVALID_ARG with "<who>: <name> is not device memory of
 // <whose> <device>".  device < 0: of any device.  *found (may be NULL) receives the device `p` lives on.
 inline int device_buffer_check(const char *who, const void *p, int device, const char *name, const char *whose = "the scene's device",

@@ -156,6 +156,27 @@ struct DevDenoise {
 // the pack pass and `iterations` filter passes, one launch each (stream-ordered; no allocation, no synchronisation inside)
 hipError_t launch_denoise(const DevDenoise &d, hipStream_t stream);
 
+// ---- temporal accumulation (temporal.hip; mipt_temporal*) ----
+constexpr uint32_t kTemporalGroupViews = 8;     // views one launch covers: their camera records travel as kernel arguments
+struct DevTemporal {
+    // planar inputs, view-major; albedo NULL = absent.  out may be hdr.  length / variance NULL = not written.
+    const float *hdr, *position, *normal, *depth, *albedo;
+    const uint32_t *material;
+    float *out, *length, *variance;
+    // the histories (include/mipt.h): n_views records of 16 f32, then three float4 planes of n_pixels each.  in NULL = the first frame.
+    const float *history_in;
+    float *history_out;
+    unsigned long long n_pixels;            // n_views * width * height
+    uint32_t width, height, n_views;
+    uint32_t tiles_x, tiles_y;              // 64x4-pixel tiles per row / per column of a view
+    uint32_t view_begin, view_count;        // this launch: views view_begin ... view_begin + view_count - 1 (at most kTemporalGroupViews)
+    float alpha_min, max_history, normal_tol, depth_tol;
+    float camera[kTemporalGroupViews][16];  // this frame's records of the launch's views, for history_out's header
+};
+// one launch per group of kTemporalGroupViews views; `records` holds n_views * 16 f32 (stream-ordered; no allocation, no
+// synchronisation inside, and `records` is not read after the call returns)
+hipError_t launch_temporal(DevTemporal d, const float *records, hipStream_t stream);
+
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);

@@ -1,0 +1,163 @@
+// temporal.hip -- the temporal accumulation of include/mipt.h ("temporal accumulation"): mipt_temporal*.
+//
+// One gather kernel.  Every pixel projects its first hit's world position through the camera record the previous history carries,
+// gathers that history with four bilinear taps that must agree with it in material, normal and depth, blends this frame's sample in
+// and writes the new history, the output frame and the optional length / variance planes.  A history keeps three float4 per pixel
+// ({colour, length}, {normal, depth}, {moments, material}), so a tap costs three 16-byte loads.
+//
+// One pixel per lane.  A 256-thread block covers 64x4 pixels, as in denoise.hip; the blocks walk (view, tile row, tile column) with a
+// grid stride.  Whether there is an albedo plane and whether this is the first frame are template arguments: the absent branches do
+// not exist in the code.  The camera records of this frame travel as kernel arguments, eight views to a launch, and the first tile
+// of each view writes its record into history_out's header, so the entry neither allocates nor copies.
+//
+// Every operator below is one rounded f32 operation in the order the header gives (the translation unit is built with
+// -ffp-contract=off); every comparison is written so that a NaN takes the reject / reset side.
+#include "pt_kernel.h"
+
+namespace mipt {
+
+namespace {
+
+constexpr uint32_t kTileW = 64, kTileH = 4;                  // pixels a block covers: one wave per row
+constexpr uint32_t kMaxGrid = 1u << 20;                      // blocks per launch; a block walks the tiles with this stride
+static_assert(kTileW * kTileH == (uint32_t)kBlockThreads, "one pixel per lane");
+
+constexpr float kAlbedoFloor = 1.0f / 256.0f;
+constexpr float kMinWeight = 1.0f / 64.0f;
+constexpr float kMiss = 1e30f;
+
+__device__ __forceinline__ float floored(float albedo) { return albedo > kAlbedoFloor ? albedo : kAlbedoFloor; }   // a NaN gives the floor
+
+struct Sums { float w, r, g, b, len, m1, m2; };
+
+// One tap of view `base` of the previous history: added to `s` if it lies inside the frame and agrees with the pixel.  q < 2^32.
+__device__ __forceinline__ void tap(const DevTemporal &d, const float4 *h0, const float4 *h1, const float4 *h2, size_t base, long long qx,
+                                    long long qy, float w, uint32_t material, float nx, float ny, float nz, float d2, Sums &s) {
+    if (qx < 0 || qx >= (long long)d.width || qy < 0 || qy >= (long long)d.height) return;
+    const size_t q = base + ((size_t)qy * d.width + (size_t)qx);
+    const float4 c = h0[q], g = h1[q], m = h2[q];
+    const float dx = nx - g.x, dy = ny - g.y, dz = nz - g.z;
+    const float dn = ((dx * dx) + (dy * dy)) + (dz * dz);
+    const bool ok = __float_as_uint(m.z) == material && dn <= d.normal_tol && fabsf(d2 - (g.w * g.w)) <= d.depth_tol * d2;
+    if (!ok) return;
+    s.w = s.w + w;
+    s.r = s.r + (w * c.x); s.g = s.g + (w * c.y); s.b = s.b + (w * c.z);
+    s.len = s.len + (w * c.w);
+    s.m1 = s.m1 + (w * m.x); s.m2 = s.m2 + (w * m.y);
+}
+
+template <bool ALBEDO, bool FIRST>
+__global__ __launch_bounds__(kBlockThreads) void temporal_kernel(DevTemporal d, unsigned long long n_tiles) {
+    const uint32_t per_view = d.tiles_x * d.tiles_y;
+    const size_t header = (size_t)d.n_views * 16;            // f32 in front of the planes
+    const float4 *in0 = nullptr, *in1 = nullptr, *in2 = nullptr;
+    if (!FIRST) {
+        in0 = (const float4 *)(d.history_in + header);
+        in1 = in0 + d.n_pixels;
+        in2 = in1 + d.n_pixels;
+    }
+    float4 *out0 = (float4 *)(d.history_out + header), *out1 = out0 + d.n_pixels, *out2 = out1 + d.n_pixels;
+    const float wf = (float)d.width, hf = (float)d.height;
+    const float aspect = wf / hf;
+    for (unsigned long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint32_t local = (uint32_t)(t / per_view), r = (uint32_t)(t % per_view);   // local < view_count <= kTemporalGroupViews
+        const uint32_t view = d.view_begin + local;
+        if (r == 0 && threadIdx.x < 16) d.history_out[(size_t)view * 16 + threadIdx.x] = d.camera[local][threadIdx.x];
+        const uint32_t x = (r % d.tiles_x) * kTileW + (threadIdx.x & (kTileW - 1u));
+        const uint32_t y = (r / d.tiles_x) * kTileH + (threadIdx.x / kTileW);
+        if (x >= d.width || y >= d.height) continue;         // a ragged edge tile
+        const size_t base = (size_t)view * d.width * d.height;
+        const size_t i = base + ((size_t)y * d.width + x);   // < 2^32 (MIPT_BATCH_MAX_PIXELS)
+
+        const float *h = d.hdr + i * 3;
+        float ccr = h[0], ccg = h[1], ccb = h[2];
+        float ar = 1.0f, ag = 1.0f, ab = 1.0f;
+        if (ALBEDO) {
+            const float *a = d.albedo + i * 3;
+            ar = floored(a[0]); ag = floored(a[1]); ab = floored(a[2]);
+            ccr = ccr / ar; ccg = ccg / ag; ccb = ccb / ab;
+        }
+        const float l = ((0.2126f * ccr) + (0.7152f * ccg)) + (0.0722f * ccb);
+        const float *n = d.normal + i * 3;
+        const float nx = n[0], ny = n[1], nz = n[2];
+        const float depth = d.depth[i];
+        const uint32_t material = d.material[i];
+
+        float cr = ccr, cg = ccg, cb = ccb, len = 1.0f, m1 = l, m2 = l * l;      // RESET
+        if (!FIRST && depth < kMiss) {
+            const float *rec = d.history_in + (size_t)view * 16;                 // B[3][3], C[3]: the same for the whole block
+            const float *p = d.position + i * 3;
+            const float dx = p[0] - rec[9], dy = p[1] - rec[10], dz = p[2] - rec[11];
+            const float vx = ((rec[0] * dx) + (rec[1] * dy)) + (rec[2] * dz);
+            const float vy = ((rec[3] * dx) + (rec[4] * dy)) + (rec[5] * dz);
+            const float vz = ((rec[6] * dx) + (rec[7] * dy)) + (rec[8] * dz);
+            if (vz > 0.0f) {
+                const float sx = -(vx / vz), sy = vy / vz;
+                const float fx = (((sx / aspect) + 1.0f) * 0.5f) * wf;
+                const float fy = hf - (((sy + 1.0f) * 0.5f) * hf);
+                if (fx >= -1.0f && fx < wf && fy >= -1.0f && fy < hf) {
+                    const float flx = floorf(fx), fly = floorf(fy);
+                    const long long x0 = (long long)flx, y0 = (long long)fly;
+                    const float wx = fx - flx, wy = fy - fly;
+                    const float ox = 1.0f - wx, oy = 1.0f - wy;
+                    const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+                    Sums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                    tap(d, in0, in1, in2, base, x0, y0, ox * oy, material, nx, ny, nz, d2, s);
+                    tap(d, in0, in1, in2, base, x0 + 1, y0, wx * oy, material, nx, ny, nz, d2, s);
+                    tap(d, in0, in1, in2, base, x0, y0 + 1, ox * wy, material, nx, ny, nz, d2, s);
+                    tap(d, in0, in1, in2, base, x0 + 1, y0 + 1, wx * wy, material, nx, ny, nz, d2, s);
+                    if (s.w > kMinWeight) {
+                        const float pr = s.r / s.w, pg = s.g / s.w, pb = s.b / s.w, lp = s.len / s.w;
+                        const float p1 = s.m1 / s.w, p2 = s.m2 / s.w;
+                        float ln = lp + 1.0f;
+                        ln = ln < d.max_history ? ln : d.max_history;
+                        float al = 1.0f / ln;
+                        al = al > d.alpha_min ? al : d.alpha_min;
+                        cr = pr + ((ccr - pr) * al); cg = pg + ((ccg - pg) * al); cb = pb + ((ccb - pb) * al);
+                        m1 = p1 + ((l - p1) * al);
+                        m2 = p2 + (((l * l) - p2) * al);
+                        len = ln;
+                    }
+                }
+            }
+        }
+
+        out0[i] = make_float4(cr, cg, cb, len);
+        out1[i] = make_float4(nx, ny, nz, depth);
+        out2[i] = make_float4(m1, m2, __uint_as_float(material), 0.0f);
+        float *o = d.out + i * 3;
+        if (ALBEDO) { o[0] = cr * ar; o[1] = cg * ag; o[2] = cb * ab; }
+        else { o[0] = cr; o[1] = cg; o[2] = cb; }
+        if (d.length) d.length[i] = len;
+        if (d.variance) {
+            const float var = m2 - (m1 * m1);
+            d.variance[i] = var > 0.0f ? var : 0.0f;
+        }
+    }
+}
+
+template <bool ALBEDO, bool FIRST>
+hipError_t launch_group(const DevTemporal &d, hipStream_t stream) {
+    const unsigned long long n_tiles = (unsigned long long)d.tiles_x * d.tiles_y * d.view_count;
+    const uint32_t grid = n_tiles < kMaxGrid ? (uint32_t)n_tiles : kMaxGrid;
+    hipLaunchKernelGGL((temporal_kernel<ALBEDO, FIRST>), dim3(grid), dim3(kBlockThreads), 0, stream, d, n_tiles);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_temporal(DevTemporal d, const float *records, hipStream_t stream) {
+    for (uint32_t v = 0; v < d.n_views; v += kTemporalGroupViews) {
+        d.view_begin = v;
+        d.view_count = d.n_views - v < kTemporalGroupViews ? d.n_views - v : kTemporalGroupViews;
+        for (uint32_t k = 0; k < d.view_count; k++)
+            for (int j = 0; j < 16; j++) d.camera[k][j] = records[(size_t)(v + k) * 16 + j];
+        hipError_t e;
+        if (d.albedo) e = d.history_in ? launch_group<true, false>(d, stream) : launch_group<true, true>(d, stream);
+        else e = d.history_in ? launch_group<false, false>(d, stream) : launch_group<false, true>(d, stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+} // namespace mipt

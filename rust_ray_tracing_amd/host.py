@@ -880,6 +880,175 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = stats
         return denoised, noisy, features, stats
 
+    # -- temporal accumulation (include/mipt.h "temporal accumulation") ---------------------------
+    _TEMPORAL_PLANES = (("position", 3, True), ("normal", 3, True), ("depth", 1, True), ("material", 1, True), ("albedo", 3, False))
+
+    @staticmethod
+    def _temporal_planes(hdr, features):
+        """-> (torch?, (V, H, W), {name: contiguous array or tensor}); ValueError naming the argument for anything else."""
+        torch_in = Scene._is_torch(hdr)
+        if not torch_in:
+            hdr = np.asarray(hdr)
+        if hdr.ndim not in (3, 4) or hdr.shape[-1] != 3:
+            raise ValueError(f"hdr: expected shape [V,H,W,3] or [H,W,3]; got {tuple(hdr.shape)}")
+        if not isinstance(features, dict):
+            raise ValueError("features: expected a dict with position, normal, depth, material and optionally albedo")
+        lead = tuple(hdr.shape[:-1])
+        planes = {}
+        for name, k, required in (("hdr", 3, True),) + Renderer._TEMPORAL_PLANES:
+            a = hdr if name == "hdr" else features.get(name)
+            if a is None:
+                if required:
+                    raise ValueError(f"{name}: features must hold it (render_features with position, normal, depth, material)")
+                continue
+            want = lead + ((k,) if k > 1 else ())
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: hdr and the features must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                dt = torch.int32 if name == "material" else torch.float32
+                if a.dtype != dt or not a.is_cuda or a.device != hdr.device:
+                    raise ValueError(f"{name}: expected a {str(dt).replace('torch.', '')} tensor on hdr's device {hdr.device}")
+                if tuple(a.shape) != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
+                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                planes[name] = a
+            else:
+                a = np.asarray(a)
+                dt = np.uint32 if name == "material" else np.float32
+                if a.dtype != dt:
+                    raise ValueError(f"{name}: expected {np.dtype(dt).name}; got {a.dtype}")
+                if a.shape != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
+                planes[name] = np.ascontiguousarray(a)
+        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
+        return torch_in, (v, h, w), planes
+
+    def temporal(self, hdr, features, cameras, history=None, alpha_min: float = 0.0, max_history: float = 32.0, normal_tol: float = 0.1,
+                 depth_tol: float = 0.1, want_length: bool = False, want_variance: bool = False, stream=None, history_out=None):
+        """The temporal accumulation of include/mipt.h over a frame or a batch of views: ``hdr`` [V,H,W,3] or [H,W,3] float32 is blended
+        with the previous frame's ``history`` reprojected through the camera it carries.  ``features``: a dict with ``position``
+        [..,3], ``normal`` [..,3], ``depth`` [..] float32 and ``material`` [..] (uint32 arrays / int32 tensors, the same bits) of the
+        same leading shape -- what ``render_features`` returns -- and optionally ``albedo`` [..,3] (the frame is demodulated before
+        and re-modulated after).  ``cameras``: the V Camera (or CAMERA records) that produced this frame.  ``history``: what the last
+        call returned, None = the first frame.  numpy arrays go through mipt_temporal on ``options.device_id``; contiguous torch
+        tensors through mipt_temporal_device on ``stream`` (a torch stream, a raw hipStream_t or None = torch's current stream)
+        without blocking.  ``history_out``: an int32 tensor of mipt_temporal_history_bytes() to write instead of a new one (it must
+        not be ``history``).  Returns (out, history, extras): ``out`` of ``hdr``'s kind and shape, the new history (a flat uint32
+        array / int32 tensor in the header's layout) and a dict with ``length`` and ``variance`` [..] where asked for."""
+        torch_in, (v, h, w), p = self._temporal_planes(hdr, features)
+        cams = list(cameras.reshape(-1)) if isinstance(cameras, np.ndarray) else ([cameras] if isinstance(cameras, Camera) else list(cameras))
+        if len(cams) != v:
+            raise ValueError(f"cameras: expected {v} cameras, one per view; got {len(cams)}")
+        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        opt = L.MiptTemporalOptions()
+        opt.width, opt.height, opt.n_views = w, h, v
+        opt.alpha_min, opt.max_history, opt.normal_tol, opt.depth_tol = alpha_min, max_history, normal_tol, depth_tol
+        bufs = L.MiptTemporalBuffers()
+        lib = L.load()
+        words = max(int(lib.mipt_temporal_history_bytes(w, h, v)), 16) // 4          # an impossible size is left to the library to refuse
+        lead = tuple(p["hdr"].shape[:-1])
+        extras = {}
+        if torch_in:
+            import torch
+            dev = p["hdr"].device
+            for name, t in (("history", history), ("history_out", history_out)):
+                if t is not None and not (Scene._is_torch(t) and t.dtype == torch.int32 and t.is_cuda and t.device == dev and t.is_contiguous()
+                                          and t.numel() == words):
+                    raise ValueError(f"{name}: expected a contiguous int32 tensor of {words} words on hdr's device {dev}")
+            out = torch.empty_like(p["hdr"])
+            new = history_out if history_out is not None else torch.empty((words,), dtype=torch.int32, device=dev)
+            for name, a in p.items():
+                setattr(bufs, name, a.data_ptr())
+            bufs.out, bufs.history_out = out.data_ptr(), new.data_ptr()
+            bufs.history_in = history.data_ptr() if history is not None else None
+            for name, on in (("length", want_length), ("variance", want_variance)):
+                if on:
+                    extras[name] = torch.empty(lead, dtype=torch.float32, device=dev)
+                    setattr(bufs, name, extras[name].data_ptr())
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            # the launches are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            for t in list(p.values()) + [out, new] + list(extras.values()) + ([history] if history is not None else []):
+                t.record_stream(s)
+            L.check(lib.mipt_temporal_device(C.byref(opt), L.ptr(table), C.byref(bufs), stream), "mipt_temporal_device")
+            return out, new, extras
+        if history is not None:
+            history = np.ascontiguousarray(history)
+            if history.dtype != np.uint32 or history.size != words:
+                raise ValueError(f"history: expected a uint32 array of {words} words; got {history.dtype} of {history.size}")
+        out = np.empty_like(p["hdr"])
+        new = np.zeros(words, dtype=np.uint32)
+        for name, a in p.items():
+            setattr(bufs, name, a.ctypes.data)
+        bufs.out, bufs.history_out = out.ctypes.data, new.ctypes.data
+        bufs.history_in = history.ctypes.data if history is not None else None
+        for name, on in (("length", want_length), ("variance", want_variance)):
+            if on:
+                extras[name] = np.zeros(lead, dtype=np.float32)
+                setattr(bufs, name, extras[name].ctypes.data)
+        L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
+        return out, new, extras
+
+    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, **args):
+        """A camera path without flicker, nothing crossing PCIe in between: a generator that per frame runs mipt_render_batch_device
+        with this renderer's options, mipt_render_features_device (depth, normal, albedo, position, material; one sample),
+        mipt_temporal_device and, with ``denoise``, mipt_denoise_device on one stream, the history in two tensors that swap roles.
+        ``cameras_per_frame``: per frame a Camera (or CAMERA record) or a sequence of them, one per view; every frame has the same
+        number of views.  ``args``: alpha_min, max_history, normal_tol, depth_tol (temporal), iterations, sigma_color, sigma_normal,
+        sigma_depth (denoise), stream.  The renderer must use SEED_PER_SAMPLE -- the pixel stream repeats the same noise every frame,
+        and averaging it gains nothing: frame f renders the samples from 1 + f * samples on.  Yields per frame a dict with ``out``
+        (the denoised frame, or the accumulated one), ``accumulated``, ``noisy`` [V,H,W,3], ``features``, ``history`` (valid until the
+        frame after the next is produced: the two tensors are reused), ``length``, ``variance`` and ``stats``."""
+        import torch
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        if o.seed_mode != L.SEED_PER_SAMPLE:
+            raise ValueError("render_sequence: the renderer's seed_mode must be SEED_PER_SAMPLE; the pixel stream repeats the same noise every frame")
+        t_names, d_names = ("alpha_min", "max_history", "normal_tol", "depth_tol"), ("iterations", "sigma_color", "sigma_normal", "sigma_depth")
+        stream = args.pop("stream", None)
+        unknown = [k for k in args if k not in t_names + d_names]
+        if unknown:
+            raise ValueError(f"render_sequence: unknown arguments {unknown}")
+        t_args, d_args = {k: args[k] for k in t_names if k in args}, {k: args[k] for k in d_names if k in args}
+        w, h = o.output_image_dimensions
+        dev = torch.device("cuda", o.device_id)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
+        lib = L.load()
+        handle, pair, history, n = None, None, None, None
+        for frame, cams in enumerate(cameras_per_frame):
+            cams = [cams] if isinstance(cams, (Camera, np.void)) or (isinstance(cams, np.ndarray) and cams.ndim == 0) else list(cams)
+            if not cams or (n is not None and len(cams) != n):
+                raise ValueError(f"render_sequence: frame {frame} has {len(cams)} cameras; every frame needs the same number, at least 1")
+            table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+            if n is None:
+                n = len(cams)
+                handle = scene.upload(o.device_id)
+                words = int(lib.mipt_temporal_history_bytes(w, h, n)) // 4
+                pair = [torch.empty((max(words, 4),), dtype=torch.int32, device=dev) for _ in range(2)]
+            opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, sample_begin=1 + frame * o.samples,
+                               cull_margin=o.cull_margin, shading=o.shading)
+            noisy = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+            st = L.MiptStats()
+            L.check(lib.mipt_render_batch_device(handle, L.ptr(table), n, C.byref(opt), noisy.data_ptr(), None, raw, C.byref(st)),
+                    "mipt_render_batch_device")
+            stats = st.as_dict()
+            features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo", "position", "material"), device=True, stream=raw, handle=handle)
+            acc, history, extras = self.temporal(noisy, features, table, history=history, want_length=True, want_variance=True, stream=raw,
+                                                 history_out=pair[frame & 1], **t_args)
+            out = self.denoise(acc, features["normal"], features["depth"], features["albedo"], stream=raw, **d_args) if denoise else acc
+            self.last_stats = stats
+            yield dict(frame=frame, out=out, accumulated=acc, noisy=noisy, features=features, history=history, length=extras["length"],
+                       variance=extras["variance"], stats=stats)
+
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
                              want_rgba8: bool = True, flags: int = 0):
         """The same arm over all GPUs of the node in one call (mipt_render_multi): image tiles + one RCCL gather, or
