@@ -496,8 +496,12 @@ MIPT_API int mipt_denoise_device(const MiptDenoiseOptions *opt, const MiptDenois
  *     out = c * a (c without albedo); length = len; variance = m2 - (m1*m1), then variance > 0 ? variance : 0.
  * The NaN rule of the query section applies: a NaN this arithmetic produces is a NaN everywhere, sign and payload the implementation's.
  *
- * Scope.  The geometry is taken to be static between the two frames.  After mipt_scene_update_* the material, normal and depth
- * checks reject what they catch and the rest ghosts; motion vectors for moving parts are not part of this entry.
+ * Scope.  `position` is where the pixel's surface point was WHEN THE HISTORY WAS WRITTEN.  For geometry that has not moved since,
+ * that is the first hit's position (mipt_render_features).  After mipt_scene_update_*, mipt_scene_set_transforms or
+ * mipt_scene_update_mesh_device it is the prev_position plane of mipt_render_motion ("previous positions" below): the lookup and
+ * the depth check are then right for a moving surface.  Handing this entry the current position after an update instead leaves the
+ * material, normal and depth checks to reject what they catch, and the rest ghosts.  The normal check compares this frame's normal
+ * with the history's either way: a part that turns by more than normal_tol allows starts anew.
  *
  * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
  * field -- a null opt, cameras, buffers or required plane; zero width, height or n_views; n_views*W*H >= MIPT_BATCH_MAX_PIXELS;
@@ -533,6 +537,64 @@ MIPT_API int mipt_temporal(const MiptTemporalOptions *opt, const MiptCamera *cam
  * freed on return.  The call writes history_out, out and the optional outputs that are given, and nothing else. */
 MIPT_API int mipt_temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
                                   void *hip_stream);
+
+/* ---- previous positions: where every pixel's surface point was in the previous geometry ------------------------------------------------
+ * The link between the geometry updates and the temporal accumulation above: per pixel the world position that the first hit's
+ * surface point had before the last update, to be passed to mipt_temporal as `position` (csrc/first_hit.hip, the MOTION form of the
+ * feature kernel).  The reference has nothing of this kind: the value is defined HERE, and the kernel and tests/tools/motion_model.py
+ * obey it bit for bit.  Every operator is one rounded f32 operation, nothing is fused, and the operations run in the order written.
+ *
+ * Ray and hit.  The camera ray of pixel (x, y) of view v is the ray mipt_render_features traces for the FIRST sample of a call with
+ * the same opt: the same seed rule, the same sample_begin normalisation (0 -> 1), the same arithmetic.  The hit is
+ * Ray::traverse_bvh's winner in the arm opt->traversal / opt->cull_margin select; its u, v and triangle are bit for bit those of
+ * mipt_query_closest.  T = the triangle in the caller's order (the `prim` convention without bit 31).
+ *
+ * Previous corners.  P0, P1, P2 = the positions of corners 0, 1, 2 of triangle T in the previous geometry, from one of two sources:
+ *   explicit  prev_tris != NULL: the previous frame's triangle array in the order of mipt_scene_update_triangles, host memory for
+ *             mipt_render_motion and device memory for mipt_render_motion_device; n_prev_tris must equal the scene's triangle
+ *             count.  Pc = prev_tris[T].vertex[c].position.  Works on any scene and on the replicas of mipt_multi_scene; it suits
+ *             callers of mipt_scene_update_triangles_device, who hold two arrays anyway.
+ *   tracked   prev_tris == NULL: the previous generation a mesh scene keeps while mipt_scene_track_motion(scene, 1) is on.  Right
+ *             after enabling, the previous generation equals the current one.  Every successful mipt_scene_set_transforms or
+ *             mipt_scene_update_mesh_device makes what was resident -- the positions array and the part table, with or without
+ *             transforms -- the previous generation; a failed update leaves both generations as they were.  Pc = the expansion rule
+ *             ("resident indexed meshes") applied to previous position indices[3T + c] with the previous matrix of T's part, so it
+ *             equals mipt_mesh_expand(previous mesh)[T].vertex[c].position bit for bit.  Two updates between two frames leave only
+ *             the second step tracked: the motion pass then sees the geometry between them as the previous one.
+ *             mipt_scene_track_motion(scene, 0) frees what tracking holds (a copy of the positions and a third part table);
+ *             MiptMeshInfo.array_bytes and hbm_bytes include it while tracking is on.  A scene without a mesh is refused.
+ *
+ * Value.  w = (1.0f - u) - v; per component prev = ((P0*w) + (P1*u)) + (P2*v) -- the order the feature pass uses for the normal.  A
+ * miss writes (0, 0, 0), as `position` does.  The NaN rule of the query section applies.
+ *
+ * Options and stats.  opt is read exactly as mipt_render_features reads it; samples is validated as there and otherwise unused (only
+ * the first sample is traced); MIPT_FLAG_COUNT is refused.  Stats (may be NULL): kernel_ms, stack_overflows, tex_clamped = 0,
+ * pixels = n_views*W*H; every other field 0.
+ *
+ * Normal check.  With prev_position as mipt_temporal's `position` the normal check still compares this frame's normal with the
+ * history's: a part that turns by more than normal_tol allows starts anew instead of ghosting.  A previous-frame normal is out of scope.
+ *
+ * Errors.  Every argument is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- everything mipt_render_features checks; a null prev_position; a non-zero reserved0 or non-NULL reserved pointer;
+ * n_prev_tris that is not the scene's triangle count; prev_tris == NULL on a scene that is not a mesh tracking motion; for the
+ * _device entry a pointer that is not 4-byte aligned or not device memory of the scene's device.  A traversal-stack overflow is
+ * MIPT_ERR_STACK after the buffer is written.  After any error the scene renders and queries as before. */
+typedef struct {
+    const MiptTriangle *prev_tris;   /* NULL = the generation the scene tracks (mesh scenes) */
+    uint32_t n_prev_tris, reserved0; /* reserved0 must be 0 */
+    float   *prev_position;          /* 3 f32 / pixel, view-major, row 0 = top; required */
+    void    *reserved[5];            /* must be NULL */
+} MiptMotionBuffers;                 /* 64 B */
+
+/* Into a HOST buffer, prev_tris (if given) in HOST memory; blocks until done. */
+MIPT_API int mipt_render_motion(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                const MiptMotionBuffers *host, MiptStats *stats);
+/* Into a DEVICE buffer, prev_tris (if given) in DEVICE memory, on `hip_stream` (hipStream_t, NULL = the null stream); blocks until the
+ * kernel has finished (stats are read back), like mipt_render_features_device. */
+MIPT_API int mipt_render_motion_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                       const MiptMotionBuffers *device, void *hip_stream, MiptStats *stats);
+/* enable != 0: keep the previous generation of a mesh scene from now on (it starts equal to the current one); 0: free it. */
+MIPT_API int mipt_scene_track_motion(MiptScene *scene, uint32_t enable);
 
 /* Tile-shard helpers (image tiles shard across GPUs; one RCCL all-gather of packed slices). */
 MIPT_API uint64_t mipt_packed_pixels(uint32_t width, uint32_t height, uint32_t tile_world);

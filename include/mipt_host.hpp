@@ -110,6 +110,25 @@ inline int render_features_on(MiptScene *scene, const std::vector<MiptCamera> &c
     return rc;
 }
 
+// mipt_render_motion on any resident scene handle (include/mipt.h "previous positions"): per pixel of `cameras` with `opt` the world
+// position the first hit's surface point had in the previous geometry, 3 f32 / pixel, view-major [view][row][column][3].  `prev_tris`:
+// the previous frame's triangles in the caller's order; empty = the generation a mesh scene tracks (mipt_scene_track_motion).
+// MIPT_ERR_STACK leaves the image written.
+inline int render_motion_on(MiptScene *scene, const std::vector<MiptCamera> &cameras, const MiptOptions &opt, const std::vector<MiptTriangle> &prev_tris,
+                            std::vector<float> &prev_position, MiptStats *stats = nullptr) {
+    const uint64_t n_pix = (uint64_t)cameras.size() * opt.width * opt.height;
+    const size_t n = n_pix < MIPT_BATCH_MAX_PIXELS ? (size_t)n_pix : 0;      // an impossible size is left to the library to refuse
+    prev_position.assign(n ? n * 3 : 1, 0.0f);
+    MiptMotionBuffers b{};
+    b.prev_tris = prev_tris.empty() ? nullptr : prev_tris.data();
+    b.n_prev_tris = (uint32_t)prev_tris.size();
+    b.prev_position = prev_position.data();
+    static const MiptCamera no_camera{};
+    const int rc = mipt_render_motion(scene, cameras.empty() ? &no_camera : cameras.data(), (uint32_t)cameras.size(), &opt, &b, stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+
 // Renderer::denoise: the filter's settings (MiptDenoiseOptions; the defaults of the Python mirror)
 struct DenoiseSettings {
     uint32_t iterations = 5;                               // 1 ... 8; iteration i has step 1 << i
@@ -373,6 +392,23 @@ class Renderer {                                           // src/renderer.rs:8-
         const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
         MiptMulti *m = scene.node_handle(1);
         return m ? render_features_on(mipt_multi_scene(m, 0), cams, o, wanted, out, stats) : MIPT_ERR_HIP;
+    }
+
+    // Previous positions of the frame(s) this renderer would render (mipt_render_motion): what Renderer::temporal takes as the
+    // position image when triangles have moved since the last frame.  `cameras` empty = the scene's camera; `prev_tris`: the previous
+    // frame's scene.tris (the order the replicas were built from).  Options and residency as render_features.  Returns a MiptStatus.
+    int render_motion(const Scene &scene, const std::vector<MiptCamera> &cameras, const std::vector<MiptTriangle> &prev_tris,
+                      std::vector<float> &prev_position, uint32_t seed_mode = MIPT_SEED_PIXEL_STREAM, MiptStats *stats = nullptr) const {
+        if (options.backend != RendererBackend::MI355X) { log_error("this build only provides RendererBackend::MI355X"); return MIPT_ERR_INVALID_ARG; }
+        MiptOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.samples = (uint32_t)options.samples; o.max_ray_depth = (uint32_t)options.max_ray_depth;
+        o.seed_mode = seed_mode;
+        o.traversal = options.traversal; o.cull_margin = MIPT_CULL_MARGIN_SAFE;
+        const std::vector<MiptCamera> own{scene.camera.uniform};
+        const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
+        MiptMulti *m = scene.node_handle(1);
+        return m ? render_motion_on(mipt_multi_scene(m, 0), cams, o, prev_tris, prev_position, stats) : MIPT_ERR_HIP;
     }
 
     // The a-trous denoiser (mipt_denoise, include/mipt.h "a-trous denoiser") over host images of this renderer's width and height:

@@ -111,6 +111,15 @@ class MiptFeatureBuffers(C.Structure):
 assert C.sizeof(MiptFeatureBuffers) == 96
 
 
+# ---- previous positions (include/mipt.h "previous positions") ----
+class MiptMotionBuffers(C.Structure):
+    _fields_ = [("prev_tris", C.c_void_p), ("n_prev_tris", C.c_uint32), ("reserved0", C.c_uint32), ("prev_position", C.c_void_p),
+                ("reserved", C.c_void_p * 5)]
+
+
+assert C.sizeof(MiptMotionBuffers) == 64
+
+
 # ---- a-trous denoiser (include/mipt.h "a-trous denoiser") ----
 class MiptDenoiseOptions(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("iterations", C.c_uint32),
@@ -192,6 +201,7 @@ EXPORTS = [
     "mipt_denoise_workspace_bytes", "mipt_denoise", "mipt_denoise_device",
     "mipt_temporal_history_bytes", "mipt_temporal", "mipt_temporal_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
+    "mipt_render_motion", "mipt_render_motion_device", "mipt_scene_track_motion",
 ]
 
 _lib = None
@@ -320,6 +330,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_render_features.restype = C.c_int
     lib.mipt_render_features_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, vp, C.POINTER(MiptStats)]
     lib.mipt_render_features_device.restype = C.c_int
+    mb = C.POINTER(MiptMotionBuffers)
+    lib.mipt_render_motion.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), mb, C.POINTER(MiptStats)]
+    lib.mipt_render_motion.restype = C.c_int
+    lib.mipt_render_motion_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), mb, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_motion_device.restype = C.c_int
+    lib.mipt_scene_track_motion.argtypes = [vp, u32]
+    lib.mipt_scene_track_motion.restype = C.c_int
     do, db = C.POINTER(MiptDenoiseOptions), C.POINTER(MiptDenoiseBuffers)
     lib.mipt_denoise_workspace_bytes.argtypes = [u32, u32, u32]
     lib.mipt_denoise_workspace_bytes.restype = u64

@@ -11,10 +11,16 @@
 // pt_trace_batch_kernel, so a wave's primary rays are neighbours.  Finished lanes wait until a quarter of the wave's live lanes are
 // idle (or none traverses), then read their hit's attributes, store or add them into their pixel's output slots and either start their
 // pixel's next sample or take a new pixel from the global counter with one wave-aggregated atomic.
+//
+// The motion pass (mipt_render_motion*, include/mipt.h "previous positions") is the same kernel with MOTION != 0: the first sample's
+// traversal, and in the finished-lane step, instead of the attributes, the hit triangle's three corners in the PREVIOUS geometry --
+// from the caller's triangle array (kMotionExplicit) or from the scene's previous mesh generation through the expansion rule
+// (kMotionTracked) -- interpolated with the hit's barycentrics.
 #include "pt_kernel.h"
 #include "pt_device_math.h"
 #include "pt_texel.h"
 #include "pt_traverse.h"
+#include "pt_mesh_rule.h"
 
 namespace mipt {
 
@@ -52,10 +58,33 @@ __device__ __forceinline__ void accumulate(float *p, V3 v, bool first, bool last
 #ifndef MIPT_FIRST_HIT_WAVES
 #define MIPT_FIRST_HIT_WAVES 8
 #endif
-#define MIPT_FIRST_HIT_BOUNDS(COUNT) __launch_bounds__(kBlockThreads, COUNT ? 5 : MIPT_FIRST_HIT_WAVES)
+// the tracked motion pass (MOTION == 2) holds a part's matrix next to three corners: 7 waves (72 VGPRs) keep it out of scratch, which 8 do not
+#define MIPT_FIRST_HIT_BOUNDS(COUNT, MOTION) __launch_bounds__(kBlockThreads, COUNT ? 5 : (MOTION == 2 ? 7 : MIPT_FIRST_HIT_WAVES))
 
-template <bool COUNT, bool CULL>
-__global__ MIPT_FIRST_HIT_BOUNDS(COUNT) void first_hit_kernel(DevScene sc, DevFeatures f) {
+enum : int { kMotionNone = 0, kMotionExplicit = 1, kMotionTracked = 2 };
+
+// corner c of triangle T (the caller's order) in the previous geometry.  Explicit: a 12-byte run of the fat triangle array, 112 T +
+// 32 c.  Tracked: the expansion rule (pt_mesh_rule.h) on the previous position array with the previous matrix of T's part, `part`.
+template <int MOTION>
+__device__ __forceinline__ V3 prev_corner(const DevFeatures &f, uint32_t T, uint32_t c, uint32_t part) {
+    float p[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (MOTION == kMotionExplicit) {
+        const float *q = f.prev_tris + ((size_t)T * 28u + c * 8u);
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+    } else {
+        const uint32_t ip = f.prev_idx[(size_t)T * 3u + c];
+        if (ip < f.prev_n_pos) {                                          // as expand_corner: an index out of range leaves zero
+            const float *q = f.prev_pos + (size_t)ip * 3u;
+            p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+        }
+        const PartRec &r = f.prev_rec[part];
+        if (r.has_xf) xf_position(r, p);
+    }
+    return mk(p[0], p[1], p[2]);
+}
+
+template <bool COUNT, bool CULL, int MOTION = kMotionNone>
+__global__ MIPT_FIRST_HIT_BOUNDS(COUNT, MOTION) void first_hit_kernel(DevScene sc, DevFeatures f) {
     __shared__ uint32_t s_stack[kWavesPerBlock][kStackLds + 1][64];   // row kStackLds: scratch target of the branch-free push
 
     const uint32_t lane = threadIdx.x & 63u;
@@ -88,6 +117,25 @@ __global__ MIPT_FIRST_HIT_BOUNDS(COUNT) void first_hit_kernel(DevScene sc, DevFe
         // ---------------- refill: finish samples, write pixels, fetch pixels, camera rays ------------
         if (n_need != 0u && (n_t == 0u || n_need * kRefillDen >= (n_t + n_need) * kRefillNum)) {
             bool gen = false, wrote = false;                              // this lane starts a camera ray / has written its pixel in this pass
+            if constexpr (MOTION != kMotionNone) {
+                if (state == FS_D) {                                      // one sample per pixel: the lane's pixel is done here
+                    const size_t slot = (size_t)view * f.view_pixels + ((size_t)py * f.width + px);
+                    V3 prev = mk(0.0f, 0.0f, 0.0f);                       // a miss, as `position`
+                    if (best_tri != kNoTri) {
+                        const uint32_t tri = best_tri & ~kFrontBit;
+                        const uint32_t T = f.tri_order ? f.tri_order[tri] : tri;             // the `prim` store's mapping
+                        uint32_t part = 0u;
+                        if constexpr (MOTION == kMotionTracked) part = part_of(f.prev_rec, f.prev_n_parts, T);
+                        const float u = best_u, v = best_v;
+                        const float w = (1.0f - u) - v;
+                        prev = prev_corner<MOTION>(f, T, 0u, part) * w;
+                        prev = prev + prev_corner<MOTION>(f, T, 1u, part) * u;
+                        prev = prev + prev_corner<MOTION>(f, T, 2u, part) * v;
+                    }
+                    float *p = f.prev_position + slot * 3; p[0] = prev.x; p[1] = prev.y; p[2] = prev.z;
+                    wrote = true; state = FS_N;
+                }
+            } else
             if (state == FS_D) {
                 const bool hit = best_tri != kNoTri;
                 const size_t slot = (size_t)view * f.view_pixels + ((size_t)py * f.width + px);
@@ -319,15 +367,15 @@ __global__ MIPT_FIRST_HIT_BOUNDS(COUNT) void first_hit_kernel(DevScene sc, DevFe
     if (lane == 0u && w_pixels) atomicAdd(&f.stats->pixels, (unsigned long long)w_pixels);
 }
 
-template <bool COUNT, bool CULL>
+template <bool COUNT, bool CULL, int MOTION = kMotionNone>
 static hipError_t launch_f(const DevScene &sc, const DevFeatures &f, int grid, hipStream_t stream) {
-    hipLaunchKernelGGL((first_hit_kernel<COUNT, CULL>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, f);
+    hipLaunchKernelGGL((first_hit_kernel<COUNT, CULL, MOTION>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, f);
     return hipGetLastError();
 }
-template <bool COUNT, bool CULL>
+template <bool COUNT, bool CULL, int MOTION = kMotionNone>
 static int occ_f() {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, first_hit_kernel<COUNT, CULL>, kBlockThreads, 0) != hipSuccess) n = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, first_hit_kernel<COUNT, CULL, MOTION>, kBlockThreads, 0) != hipSuccess) n = 1;
     return n;
 }
 
@@ -338,6 +386,19 @@ hipError_t launch_first_hit(const DevScene &sc, const DevFeatures &f, bool count
 }
 int first_hit_blocks_per_cu(bool count, bool cull) {
     int n = count ? (cull ? occ_f<true, true>() : occ_f<true, false>()) : (cull ? occ_f<false, true>() : occ_f<false, false>());
+    if (n < 1) n = 1;
+    if (n > 8) n = 8;
+    return n;
+}
+
+// the motion pass: {cull} x {explicit, tracked}; tracked = f.prev_tris is null
+hipError_t launch_motion(const DevScene &sc, const DevFeatures &f, bool cull, int grid, hipStream_t stream) {
+    if (f.prev_tris) return cull ? launch_f<false, true, kMotionExplicit>(sc, f, grid, stream) : launch_f<false, false, kMotionExplicit>(sc, f, grid, stream);
+    return cull ? launch_f<false, true, kMotionTracked>(sc, f, grid, stream) : launch_f<false, false, kMotionTracked>(sc, f, grid, stream);
+}
+int motion_blocks_per_cu(bool explicit_source, bool cull) {
+    int n = explicit_source ? (cull ? occ_f<false, true, kMotionExplicit>() : occ_f<false, false, kMotionExplicit>())
+                            : (cull ? occ_f<false, true, kMotionTracked>() : occ_f<false, false, kMotionTracked>());
     if (n < 1) n = 1;
     if (n > 8) n = 8;
     return n;

@@ -22,10 +22,13 @@ void unpack(const MiptFeatureBuffers *b, void *p[kBuffers]) {
     p[0] = b->depth; p[1] = b->prim; p[2] = b->material; p[3] = b->position; p[4] = b->uv; p[5] = b->normal; p[6] = b->albedo; p[7] = b->emission;
 }
 
-// everything that needs neither the scene's contents nor a device
-int validate(const char *who, const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
-             const MiptFeatureBuffers *out) {
-    if (!scene || !cameras || !opt || !out) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, cameras, opt or buffers", who);
+} // namespace
+
+// the checks of a first-hit pass that concern neither its buffers nor a device (mipt_scene.h): mipt_render_features* and, with
+// count_allowed = false, mipt_render_motion*
+int mipt::first_hit_check(const char *who, const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                          const void *buffers, bool count_allowed) {
+    if (!scene || !cameras || !opt || !buffers) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, cameras, opt or buffers", who);
     if (n_views == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: n_views == 0", who);
     if (opt->width == 0 || opt->height == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: width and height must be greater than 0", who);
     if (opt->max_ray_depth == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: max_ray_depth must be greater than 0", who);
@@ -36,6 +39,7 @@ int validate(const char *who, const MiptScene *scene, const MiptCamera *cameras,
                     "first sample's whole path drew, so only one sample is defined without path tracing (use MIPT_SEED_PER_SAMPLE)", who, opt->samples);
     if (opt->traversal > MIPT_TRAVERSAL_CULLED) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown traversal %u", who, opt->traversal);
     if (!(opt->cull_margin >= 0.0f) || opt->cull_margin > 1.0f) return fail(MIPT_ERR_INVALID_ARG, "%s: cull_margin must be in [0, 1]", who);
+    if (!count_allowed && opt->flags) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: no flag is accepted (MIPT_FLAG_COUNT included)", who, opt->flags);
     if (opt->flags & ~(uint32_t)MIPT_FLAG_COUNT) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_FLAG_COUNT is accepted", who, opt->flags);
     if (opt->tile_world > 1 || opt->tile_rank != 0)
         return fail(MIPT_ERR_INVALID_ARG, "%s: tile_rank %u / tile_world %u: a feature pass is not tile-sharded (tile_world 0 or 1)", who, opt->tile_rank, opt->tile_world);
@@ -49,6 +53,52 @@ int validate(const char *who, const MiptScene *scene, const MiptCamera *cameras,
         return fail(MIPT_ERR_INVALID_ARG, "%s: width*height too large for the reference's 32-bit pixel seed", who);
     if ((uint64_t)n_views * opt->width * opt->height >= MIPT_BATCH_MAX_PIXELS)
         return fail(MIPT_ERR_INVALID_ARG, "%s: %u views of %ux%u: n_views*width*height must stay below 2^32", who, n_views, opt->width, opt->height);
+    return MIPT_OK;
+}
+
+// what every first-hit launch needs besides its buffers (mipt_scene.h): the frame and tile constants, the grid with the scene's spill
+// slots, and the camera table -- one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream
+// (mipt_render_batch_device's).  The current device is the scene's.
+int mipt::first_hit_setup(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, int blocks_per_cu,
+                          hipStream_t stream, DevFeatures *fp, int *grid_out) {
+    mipt::DevFeatures &f = *fp;
+    f.tri_order = scene->d_tri_order;
+    f.width = opt->width; f.height = opt->height; f.samples = opt->samples; f.seed_mode = opt->seed_mode;
+    f.sample_begin = opt->sample_begin ? opt->sample_begin : 1u;
+    f.tiles_x = (opt->width + 7u) / 8u;
+    f.n_tiles = f.tiles_x * ((opt->height + 7u) / 8u);
+    f.tiles_recip = 0xffffffffu / f.n_tiles;
+    f.view_pixels = opt->width * opt->height;
+    f.total_work = (unsigned long long)f.n_tiles * 64ull * n_views;
+    f.aspect = (float)opt->width / (float)opt->height;        // cpu.rs:34
+    f.samples_f = (float)opt->samples;                        // cpu.rs:60
+    f.cull_scale = 1.0f + opt->cull_margin;
+    f.stats = scene->d_stats;
+
+    int grid = 0, rc = mipt::traversal_grid(scene, blocks_per_cu, f.total_work, &grid);
+    if (rc) return rc;
+    f.ovf = scene->d_ovf;
+
+    scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t v = 0; v < n_views; v++) {
+        const MiptCamera &c = cameras[v];
+        for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
+        scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
+    }
+    const size_t cam_bytes = scene->h_cams.size() * sizeof(float4);
+    if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, cam_bytes))) return rc;
+    MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), cam_bytes, hipMemcpyHostToDevice, stream));
+    f.cams = scene->d_cams;
+    *grid_out = grid;
+    return MIPT_OK;
+}
+
+namespace {
+
+// everything that needs neither the scene's contents nor a device
+int validate(const char *who, const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+             const MiptFeatureBuffers *out) {
+    { const int rc = mipt::first_hit_check(who, scene, cameras, n_views, opt, out, true); if (rc) return rc; }
     for (const void *r : out->reserved)
         if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved buffer pointers must be NULL", who);
     void *p[kBuffers];
@@ -72,34 +122,9 @@ int features_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_view
     mipt::DevFeatures f{};
     f.depth = d_out->depth; f.prim = d_out->prim; f.material = d_out->material; f.position = d_out->position;
     f.uv = d_out->uv; f.normal = d_out->normal; f.albedo = d_out->albedo; f.emission = d_out->emission;
-    f.tri_order = scene->d_tri_order;
-    f.width = opt->width; f.height = opt->height; f.samples = opt->samples; f.seed_mode = opt->seed_mode;
-    f.sample_begin = opt->sample_begin ? opt->sample_begin : 1u;
-    f.tiles_x = (opt->width + 7u) / 8u;
-    f.n_tiles = f.tiles_x * ((opt->height + 7u) / 8u);
-    f.tiles_recip = 0xffffffffu / f.n_tiles;
-    f.view_pixels = opt->width * opt->height;
-    f.total_work = (unsigned long long)f.n_tiles * 64ull * n_views;
-    f.aspect = (float)opt->width / (float)opt->height;        // cpu.rs:34
-    f.samples_f = (float)opt->samples;                        // cpu.rs:60
-    f.cull_scale = 1.0f + opt->cull_margin;
-    f.stats = scene->d_stats;
 
-    int grid = 0, rc = mipt::traversal_grid(scene, mipt::first_hit_blocks_per_cu(count, cull), f.total_work, &grid);
+    int grid = 0, rc = mipt::first_hit_setup(scene, cameras, n_views, opt, mipt::first_hit_blocks_per_cu(count, cull), stream, &f, &grid);
     if (rc) return rc;
-    f.ovf = scene->d_ovf;
-
-    // the camera table: one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream (mipt_render_batch_device's)
-    scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t v = 0; v < n_views; v++) {
-        const MiptCamera &c = cameras[v];
-        for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
-        scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
-    }
-    const size_t cam_bytes = scene->h_cams.size() * sizeof(float4);
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, cam_bytes))) return rc;
-    MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), cam_bytes, hipMemcpyHostToDevice, stream));
-    f.cams = scene->d_cams;
 
     mipt::DevStats hs;
     float ms = 0.0f;

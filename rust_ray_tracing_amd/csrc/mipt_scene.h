@@ -75,6 +75,12 @@ struct SceneDeleter { void operator()(MiptScene *s) const { free_scene(s); } };
 using ScenePtr = std::unique_ptr<MiptScene, SceneDeleter>;      // a scene under construction: freed unless release()d to the caller
 // the resident mesh of `s` (if any) freed, on the current device (scene_mesh.hip); geometry, materials and workspace stay
 void free_mesh(MiptScene *s);
+// The previous generation of a mesh scene that tracks motion (mipt_scene_track_motion), as the motion pass reads it: the part table
+// and the position array of the geometry before the last successful update, and the position index stream.  false: `s` is no
+// tracked mesh.
+struct PartRec;
+struct MeshMotionSource { const PartRec *prev_rec; const float *prev_pos; const uint32_t *idx; uint32_t n_parts, n_pos; };
+bool mesh_motion_source(const MiptScene *s, MeshMotionSource *out);
 // stats buffer, events, CU count: everything a scene needs besides its geometry.  On failure the scene is left for free_scene.
 int scene_finish_workspace(MiptScene *s);
 // A replica of `src` in the memory of `device` by device-to-device copies (xGMI between GPUs of a node; a plain copy on the same
@@ -182,5 +188,13 @@ int traversal_launch(MiptScene *scene, hipStream_t stream, Launch launch, After 
                     hs.stack_overflows, kStackLds + kStackOvf);
     return MIPT_OK;
 }
+
+// ---- the first-hit passes (mipt_features.cpp: the feature buffers; mipt_motion.cpp: previous positions) ----
+// the checks that concern neither the buffers nor a device; `buffers` is only tested for null.  count_allowed: MIPT_FLAG_COUNT passes
+int first_hit_check(const char *who, const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                    const void *buffers, bool count_allowed);
+// the frame constants, the grid and the camera table of a launch, on `stream`; the output pointers of `f` are the caller's to set
+int first_hit_setup(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, int blocks_per_cu,
+                    hipStream_t stream, DevFeatures *f, int *grid_out);
 
 } // namespace mipt

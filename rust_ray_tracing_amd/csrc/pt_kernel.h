@@ -122,6 +122,7 @@ hipError_t launch_ray_query(const DevScene &sc, const DevQuery &q, bool count, b
 int query_blocks_per_cu(bool count, bool cull, bool anyhit);                 // occupancy query
 
 // ---- first-hit feature buffers (first_hit.hip; mipt_render_features*) ----
+struct PartRec;                             // pt_mesh_rule.h
 struct DevFeatures {
     const float4 *cams;                     // n_views x 64 B, the records of DevBatch::cams
     // planar outputs, view-major, NULL = not wanted: 1, 1, 1, 3, 2, 3, 3, 3 words per pixel
@@ -138,9 +139,19 @@ struct DevFeatures {
     float cull_scale;                       // 1 + cull_margin
     uint32_t *ovf;                          // traversal-stack overflow area [wave][entry][lane]
     DevStats *stats;                        // zeroed before the launch; `queue` hands out the work indices
+    // ---- the motion pass only (launch_motion; the feature kernels read nothing below) ----
+    float *prev_position;                   // 3 words per pixel, view-major
+    const float *prev_tris;                 // explicit source: the previous frame's fat triangles (28 words each); NULL = tracked source:
+    const PartRec *prev_rec;                //   the previous generation's part table,
+    const float *prev_pos;                  //   its position array
+    const uint32_t *prev_idx;               //   and the mesh's position index stream
+    uint32_t prev_n_parts, prev_n_pos;
 };
 hipError_t launch_first_hit(const DevScene &sc, const DevFeatures &f, bool count, bool cull, int grid_blocks, hipStream_t stream);
 int first_hit_blocks_per_cu(bool count, bool cull);                          // occupancy query
+// the motion pass (mipt_render_motion*): first_hit.hip's kernel with the previous-position step; explicit source = f.prev_tris set
+hipError_t launch_motion(const DevScene &sc, const DevFeatures &f, bool cull, int grid_blocks, hipStream_t stream);
+int motion_blocks_per_cu(bool explicit_source, bool cull);                   // occupancy query
 
 // ---- a-trous denoiser (denoise.hip; mipt_denoise*) ----
 struct DevDenoise {

@@ -1,5 +1,6 @@
 // scene_mesh.hip -- resident indexed meshes: mipt_mesh_expand, mipt_scene_create_from_mesh, mipt_scene_set_transforms,
-// mipt_scene_update_mesh_device, mipt_scene_mesh_info (include/mipt.h, "resident indexed meshes").
+// mipt_scene_update_mesh_device, mipt_scene_mesh_info (include/mipt.h, "resident indexed meshes") and the previous generation a
+// mesh keeps for the motion pass, mipt_scene_track_motion ("previous positions").
 //
 // The reference expands its OBJ's vertex buffer + index triples into 112-byte fat triangles on the host (scene.rs:48-76) and every
 // other geometry entry of this library takes that fat array.  Here the indexed arrays stay in HBM and the expansion is a kernel:
@@ -14,11 +15,12 @@
 // compiled for host and device (xf_position / xf_normal below) under the file-wide -ffp-contract=off and correctly rounded
 // divide / sqrt, so mipt_mesh_expand is the byte-for-byte yardstick of the kernel.
 //
-// Nothing resident is replaced before an update has succeeded: new transforms are prepared into the spare PartRec table, new vertex
+// Nothing resident is replaced before an update has succeeded: new transforms are prepared into a spare PartRec table, new vertex
 // arrays are read from the caller's buffers by the expansion, and only after the REFIT / REBUILD committed are the tables swapped
 // and the arrays copied over the resident ones.
 #include "../../include/mipt.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
+#include "pt_mesh_rule.h"                                        // PartRec, xf_position, part_of: shared with the motion pass
 
 #include <hip/hip_runtime.h>
 
@@ -33,19 +35,18 @@ static_assert(sizeof(MiptTriangle) == 112, "Triangle");
 
 namespace mipt {
 
-// one part as the expansion reads it (24 dwords)
-struct PartRec {
-    float a[4][3];          // matrix columns a0, a1, a2 and the translation
-    float c[3][3];          // cofactor columns cross(a1,a2), cross(a2,a0), cross(a0,a1)
-    uint32_t first_tri, material_id, has_xf;
-};
-
 struct SceneMesh {
     float *d_pos = nullptr, *d_nrm = nullptr, *d_tex = nullptr;
     uint32_t *d_idx[3] = {nullptr, nullptr, nullptr};     // position / normal / tex-coord stream; [1], [2] may alias [0]
     MiptMeshPart *d_parts = nullptr;
-    PartRec *d_rec[2] = {nullptr, nullptr};               // [cur] = the table of the resident geometry, the other one is the spare
-    int cur = 0;
+    PartRec *d_rec[3] = {nullptr, nullptr, nullptr};      // [cur] = the table of the resident geometry; a table that is neither [cur]
+    int cur = 0;                                          // nor [prev] is a spare.  [2] exists only while motion is tracked
+    // mipt_scene_track_motion: the generation before the last successful update = d_prev_pos + d_rec[prev] (prev == cur: the
+    // update kept the table, or there was none yet)
+    bool track = false, prev_pos_same = false;            // prev_pos_same: d_prev_pos holds what d_pos holds
+    int prev = 0;
+    float *d_prev_pos = nullptr;
+    uint64_t track_bytes = 0;                             // what tracking holds; part of array_bytes while it is on
     float *d_xf_stage = nullptr;                          // n_parts x 16 f32: where mipt_scene_set_transforms puts the host matrices
     uint32_t *d_flag = nullptr;                           // first position index entry out of range (0xffffffff = none)
     MiptTriangle *d_expanded = nullptr;
@@ -59,6 +60,7 @@ namespace {
 
 using mipt::PartRec;
 using mipt::SceneMesh;
+using mipt::xf_position;
 
 constexpr int kT = 256;                                   // lanes = triangles of a workgroup of mesh_expand
 constexpr uint32_t kNoIndex = 0xffffffffu;
@@ -83,10 +85,6 @@ __host__ __device__ inline void part_record(const float *m, uint32_t first_tri, 
     cross3(r->a[1], r->a[2], r->c[0]);
     cross3(r->a[2], r->a[0], r->c[1]);
     cross3(r->a[0], r->a[1], r->c[2]);
-}
-__host__ __device__ inline void xf_position(const PartRec &r, float *p) {               // mat4.rs:146-149, then + translation
-    const float x = p[0], y = p[1], z = p[2];
-    for (int k = 0; k < 3; k++) p[k] = (((r.a[0][k] * x) + (r.a[1][k] * y)) + (r.a[2][k] * z)) + r.a[3][k];
 }
 __host__ __device__ inline void xf_normal(const PartRec &r, float *n) {
     const float l0 = length3(n);
@@ -135,12 +133,7 @@ __global__ __launch_bounds__(kT) void mesh_expand(MeshView m, const PartRec *par
     __shared__ float4 stage[kT * 7];
     const uint32_t base = blockIdx.x * (uint32_t)kT, t = base + threadIdx.x;
     if (t < m.n_tris) {
-        uint32_t lo = 0u, hi = n_parts;                                    // the last part with first_tri <= t (empty parts own nothing)
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (parts[mid].first_tri <= t) lo = mid; else hi = mid;
-        }
-        const PartRec r = parts[lo];
+        const PartRec r = parts[mipt::part_of(parts, n_parts, t)];
         float4 *dst = stage + threadIdx.x * 7u;
 #pragma unroll
         for (uint32_t c = 0; c < 3u; c++) {
@@ -223,7 +216,8 @@ int mesh_expand_host(const MiptMeshDesc *m, MiptTriangle *out, uint32_t cap, uin
 void free_mesh_buffers(SceneMesh *m) {
     if (!m) return;
     void *ptrs[] = {m->d_pos, m->d_nrm, m->d_tex, m->d_idx[0], m->d_idx[1] != m->d_idx[0] ? m->d_idx[1] : nullptr,
-                    m->d_idx[2] != m->d_idx[0] ? m->d_idx[2] : nullptr, m->d_parts, m->d_rec[0], m->d_rec[1], m->d_xf_stage, m->d_flag, m->d_expanded};
+                    m->d_idx[2] != m->d_idx[0] ? m->d_idx[2] : nullptr, m->d_parts, m->d_rec[0], m->d_rec[1], m->d_rec[2], m->d_prev_pos, m->d_xf_stage,
+                    m->d_flag, m->d_expanded};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete m;
@@ -336,7 +330,8 @@ int apply(MiptScene *s, const float *d_pos, const float *d_nrm, const float *d_x
     SceneMesh *m = s->mesh;
     mipt::SyncOnExit sync(st);                                                            // a failure leaves nothing of this update queued on `st`
     MIPT_HIP(hipStreamSynchronize(st));                                                    // ordered after the caller's earlier work on `st`
-    const int rec = xf_change ? m->cur ^ 1 : m->cur;
+    int rec = m->cur;                                                                      // new matrices go into a spare table
+    if (xf_change) for (rec = 0; rec == m->cur || (m->track && rec == m->prev); rec++) {}
     float expand_ms = 0.0f;
     {
         mipt::Event e0, e1;
@@ -345,10 +340,14 @@ int apply(MiptScene *s, const float *d_pos, const float *d_nrm, const float *d_x
         (void)hipEventElapsedTime(&expand_ms, e0, e1);
     }
     { const int rc = mipt::scene_update_device(s, m->d_expanded, m->n_tris, mode, st, inf, true); if (rc) return rc; }
-    // ---- commit ----
+    // ---- commit: with motion tracked, what is resident becomes the previous generation first (its positions are copied unless the
+    // copy already holds them; its part table changes roles below) ----
+    if (m->track && !m->prev_pos_same)
+        MIPT_HIP(hipMemcpyAsync(m->d_prev_pos, m->d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
     if (d_pos) MIPT_HIP(hipMemcpyAsync(m->d_pos, d_pos, (size_t)m->n_pos * 12, hipMemcpyDeviceToDevice, st));
     if (d_nrm) MIPT_HIP(hipMemcpyAsync(m->d_nrm, d_nrm, (size_t)m->n_nrm * 12, hipMemcpyDeviceToDevice, st));
     MIPT_HIP(hipStreamSynchronize(st));
+    if (m->track) { m->prev = m->cur; m->prev_pos_same = !d_pos; }
     m->cur = rec;
     if (xf_change) m->has_xf = xf_change == 1 ? 1u : 0u;
     inf->build_ms += expand_ms;
@@ -397,14 +396,50 @@ int mesh_info(const MiptScene *s, MiptMeshInfo *out) {
     MiptMeshInfo i{};
     i.n_positions = m->n_pos; i.n_normals = m->n_nrm; i.n_tex_coords = m->n_tex; i.n_indices = m->n_idx;
     i.n_tris = m->n_tris; i.n_parts = m->n_parts; i.has_transforms = m->has_xf; i.index_streams = m->streams;
-    i.array_bytes = m->array_bytes;
+    i.array_bytes = m->array_bytes + m->track_bytes;
     i.expanded_bytes = (uint64_t)m->n_tris * sizeof(MiptTriangle);
     i.hbm_bytes = i.array_bytes + i.expanded_bytes;
     *out = i;
     return MIPT_OK;
 }
 
+int track_motion(MiptScene *s, uint32_t enable) {
+    if (!s) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_track_motion: null scene");
+    if (!s->mesh) return fail(MIPT_ERR_INVALID_ARG, "mipt_scene_track_motion: the scene has no mesh (it was not made by mipt_scene_create_from_mesh)");
+    SceneMesh *m = s->mesh;
+    if ((enable != 0u) == m->track) return MIPT_OK;
+    MIPT_HIP(hipSetDevice(s->device));
+    const size_t pos_b = (size_t)m->n_pos * 12, rec_b = (size_t)m->n_parts * sizeof(PartRec);
+    if (enable) {
+        mipt::DevPtr<PartRec> rec;
+        mipt::DevPtr<float> pos;
+        MIPT_HIP(rec.alloc(m->n_parts));
+        MIPT_HIP(pos.alloc((size_t)m->n_pos * 3));
+        MIPT_HIP(hipMemcpy(pos.get(), m->d_pos, pos_b, hipMemcpyDeviceToDevice));       // the previous generation = the current one
+        m->d_rec[2] = rec.release(); m->d_prev_pos = pos.release();
+        m->prev = m->cur; m->prev_pos_same = true;
+        m->track_bytes = pos_b + rec_b;
+        m->track = true;
+    } else {
+        MIPT_HIP(hipDeviceSynchronize());                                                // nothing in flight reads what goes
+        if (m->cur == 2) { PartRec *t = m->d_rec[0]; m->d_rec[0] = m->d_rec[2]; m->d_rec[2] = t; m->cur = 0; }
+        (void)hipFree(m->d_rec[2]); m->d_rec[2] = nullptr;
+        (void)hipFree(m->d_prev_pos); m->d_prev_pos = nullptr;
+        m->prev = m->cur; m->track_bytes = 0; m->track = false;
+    }
+    return MIPT_OK;
+}
+
 } // namespace
+
+bool mipt::mesh_motion_source(const MiptScene *s, MeshMotionSource *out) {
+    if (!s || !s->mesh || !s->mesh->track) return false;
+    const SceneMesh *m = s->mesh;
+    out->prev_rec = m->d_rec[m->prev]; out->n_parts = m->n_parts;
+    out->prev_pos = m->d_prev_pos; out->n_pos = m->n_pos;
+    out->idx = m->d_idx[0];
+    return true;
+}
 
 void mipt::free_mesh(MiptScene *s) {
     if (!s || !s->mesh) return;
@@ -430,5 +465,7 @@ int mipt_scene_update_mesh_device(MiptScene *scene, const float *d_positions, co
 }
 
 int mipt_scene_mesh_info(const MiptScene *scene, MiptMeshInfo *out) { MIPT_NO_THROW(mesh_info(scene, out)) }
+
+int mipt_scene_track_motion(MiptScene *scene, uint32_t enable) { MIPT_NO_THROW(track_motion(scene, enable)) }
 
 } // extern "C"

@@ -116,6 +116,7 @@ class Scene:  # scene.rs:12-19
         self._handle_device = -1
         self._tri_order: Optional[np.ndarray] = None   # fetch_bvh: tris = (the device's input order)[_tri_order]
         self.mesh: Optional[dict] = None               # from_mesh: the indexed arrays behind MiptMeshDesc
+        self._tracks_motion = False                    # track_motion: the resident mesh keeps its previous generation
 
     # -- construction ------------------------------------------------------------------------
     @staticmethod
@@ -408,6 +409,14 @@ class Scene:  # scene.rs:12-19
         L.check(L.load().mipt_scene_mesh_info(self._handle, C.byref(inf)), "mipt_scene_mesh_info")
         return inf.as_dict()
 
+    def track_motion(self, on: bool = True) -> None:
+        """mipt_scene_track_motion: keep the previous generation of the resident mesh from now on (it starts equal to the current
+        one), so that ``Renderer.render_motion`` can take it as its source; ``on=False`` frees it."""
+        if self._handle is None:
+            raise RuntimeError("scene is not resident on a device")
+        L.check(L.load().mipt_scene_track_motion(self._handle, 1 if on else 0), "mipt_scene_track_motion")
+        self._tracks_motion = bool(on)
+
     def _fetch_bvh(self, handle) -> None:
         n = len(self.tris)
         nodes = np.zeros(max(2 * n, 1), dtype=L.NODE)
@@ -574,6 +583,7 @@ class Scene:  # scene.rs:12-19
         if self._handle is not None:
             L.load().mipt_scene_destroy(self._handle)
             self._handle = None
+            self._tracks_motion = False
         if getattr(self, "_multi", None) is not None:
             L.load().mipt_multi_destroy(self._multi)
             self._multi = None
@@ -766,6 +776,69 @@ class Renderer:  # renderer.rs:8-85
                 setattr(bufs, name, out[name].ctypes.data)
             rc = lib.mipt_render_features(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
             where = "mipt_render_features"
+        if rc != L.ERR_STACK:
+            L.check(rc, where)
+        self.last_stats = st.as_dict()
+        return out, self.last_stats
+
+    def render_motion(self, scene: Scene, cameras=None, prev_tris=None, device: bool = False, stream=None, handle=None):
+        """Previous positions (mipt_render_motion / _device): per pixel the world position that the first hit's surface point had in
+        the previous geometry, with this renderer's width, height, seed mode and traversal -- what ``temporal`` takes as ``position``
+        when parts move.  ``prev_tris``: the previous frame's TRIANGLE array in the caller's order (a numpy array; with ``device=True``
+        a numpy array, which is copied to the device, a contiguous uint8 / float32 tensor of it or a raw device pointer), None = the
+        generation the scene tracks (``Scene.track_motion``).  ``cameras``, ``device``, ``stream`` and ``handle`` as in
+        ``render_features``.  Returns ([V,H,W,3] float32 array or tensor, stats)."""
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        cams = [scene.camera] if cameras is None else list(cameras)
+        if not cams:
+            raise ValueError("render_motion: no cameras")
+        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        n = len(cams)
+        w, h = o.output_image_dimensions
+        keep = None
+        if prev_tris is not None and not isinstance(prev_tris, int) and not Scene._is_torch(prev_tris):
+            keep = np.ascontiguousarray(prev_tris)
+            if keep.dtype != L.TRIANGLE or keep.ndim != 1:
+                raise ValueError(f"prev_tris: expected a 1-d TRIANGLE array; got {keep.dtype} of shape {keep.shape}")
+        elif Scene._is_torch(prev_tris) and not device:
+            raise ValueError("prev_tris: a tensor needs device=True")
+        elif isinstance(prev_tris, int) and not device:
+            raise ValueError("prev_tris: a raw device pointer needs device=True")
+        hnd = handle if handle is not None else scene.upload(o.device_id)
+        opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, 0, cull_margin=o.cull_margin, shading=o.shading)
+        bufs, st, lib = L.MiptMotionBuffers(), L.MiptStats(), L.load()
+        if device:
+            import torch
+            dev = torch.device("cuda", o.device_id)
+            if keep is not None:
+                keep = torch.from_numpy(keep.view(np.uint8).copy()).to(dev)
+                bufs.prev_tris, bufs.n_prev_tris = keep.data_ptr(), keep.numel() // L.TRIANGLE.itemsize
+            elif isinstance(prev_tris, int):
+                bufs.prev_tris, bufs.n_prev_tris = prev_tris, scene.info(hnd)["n_tris"]       # a bare pointer: the scene's count
+            elif prev_tris is not None:
+                if not prev_tris.is_cuda or not prev_tris.is_contiguous() or (prev_tris.numel() * prev_tris.element_size()) % L.TRIANGLE.itemsize:
+                    raise ValueError("prev_tris: expected a contiguous device tensor holding whole TRIANGLE records")
+                keep = prev_tris
+                bufs.prev_tris, bufs.n_prev_tris = keep.data_ptr(), keep.numel() * keep.element_size() // L.TRIANGLE.itemsize
+            out = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+            bufs.prev_position = out.data_ptr()
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            if keep is not None and stream != torch.cuda.current_stream(dev).cuda_stream:
+                torch.cuda.current_stream(dev).synchronize()      # the copy above ran on torch's stream
+            rc = lib.mipt_render_motion_device(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), stream, C.byref(st))
+            where = "mipt_render_motion_device"
+        else:
+            if keep is not None:
+                bufs.prev_tris, bufs.n_prev_tris = keep.ctypes.data, len(keep)
+            out = np.zeros((n, h, w, 3), dtype=np.float32)
+            bufs.prev_position = out.ctypes.data
+            rc = lib.mipt_render_motion(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
+            where = "mipt_render_motion"
         if rc != L.ERR_STACK:
             L.check(rc, where)
         self.last_stats = st.as_dict()
@@ -994,7 +1067,7 @@ class Renderer:  # renderer.rs:8-85
         L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
         return out, new, extras
 
-    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, **args):
+    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, **args):
         """A camera path without flicker, nothing crossing PCIe in between: a generator that per frame runs mipt_render_batch_device
         with this renderer's options, mipt_render_features_device (depth, normal, albedo, position, material; one sample),
         mipt_temporal_device and, with ``denoise``, mipt_denoise_device on one stream, the history in two tensors that swap roles.
@@ -1003,13 +1076,19 @@ class Renderer:  # renderer.rs:8-85
         sigma_depth (denoise), stream.  The renderer must use SEED_PER_SAMPLE -- the pixel stream repeats the same noise every frame,
         and averaging it gains nothing: frame f renders the samples from 1 + f * samples on.  Yields per frame a dict with ``out``
         (the denoised frame, or the accumulated one), ``accumulated``, ``noisy`` [V,H,W,3], ``features``, ``history`` (valid until the
-        frame after the next is produced: the two tensors are reused), ``length``, ``variance`` and ``stats``."""
+        frame after the next is produced: the two tensors are reused), ``length``, ``variance`` and ``stats``.  ``motion=True`` is for
+        parts that move: the scene must be a resident mesh that tracks motion (``Scene.track_motion``), the caller moves its parts
+        with ``scene.set_transforms`` / ``update_mesh_device`` between two ``next()`` calls (at most one update per frame), and each
+        frame also runs mipt_render_motion_device with the options of its feature pass, hands that plane to the temporal step as
+        ``position`` and yields it as ``prev_position``; ``features["position"]`` stays the current one."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
             raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
         if o.seed_mode != L.SEED_PER_SAMPLE:
             raise ValueError("render_sequence: the renderer's seed_mode must be SEED_PER_SAMPLE; the pixel stream repeats the same noise every frame")
+        if motion and (scene.mesh is None or scene._handle is None or not scene._tracks_motion):
+            raise ValueError("render_sequence: motion=True needs a resident mesh scene that tracks motion (upload_from_mesh, track_motion)")
         t_names, d_names = ("alpha_min", "max_history", "normal_tol", "depth_tol"), ("iterations", "sigma_color", "sigma_normal", "sigma_depth")
         stream = args.pop("stream", None)
         unknown = [k for k in args if k not in t_names + d_names]
@@ -1042,12 +1121,19 @@ class Renderer:  # renderer.rs:8-85
                     "mipt_render_batch_device")
             stats = st.as_dict()
             features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo", "position", "material"), device=True, stream=raw, handle=handle)
-            acc, history, extras = self.temporal(noisy, features, table, history=history, want_length=True, want_variance=True, stream=raw,
+            t_features, prev_position = features, None
+            if motion:
+                prev_position, _ = one.render_motion(scene, cams, device=True, stream=raw, handle=handle)
+                t_features = {**features, "position": prev_position}
+            acc, history, extras = self.temporal(noisy, t_features, table, history=history, want_length=True, want_variance=True, stream=raw,
                                                  history_out=pair[frame & 1], **t_args)
             out = self.denoise(acc, features["normal"], features["depth"], features["albedo"], stream=raw, **d_args) if denoise else acc
             self.last_stats = stats
-            yield dict(frame=frame, out=out, accumulated=acc, noisy=noisy, features=features, history=history, length=extras["length"],
-                       variance=extras["variance"], stats=stats)
+            result = dict(frame=frame, out=out, accumulated=acc, noisy=noisy, features=features, history=history, length=extras["length"],
+                          variance=extras["variance"], stats=stats)
+            if motion:
+                result["prev_position"] = prev_position
+            yield result
 
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
                              want_rgba8: bool = True, flags: int = 0):
