@@ -538,6 +538,85 @@ MIPT_API int mipt_temporal(const MiptTemporalOptions *opt, const MiptCamera *cam
 MIPT_API int mipt_temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
                                   void *hip_stream);
 
+/* ---- variance-guided a-trous filter: the accumulated frame plus its variance and history length -> the frame to show ----------------
+ * The second half of the SVGF-style pipeline (Schied et al. 2017) whose first half is the temporal accumulation above: the a-trous
+ * filter of the denoiser section with a colour bandwidth that follows each pixel's own noise instead of a fixed sigma_color * 2^-i
+ * (csrc/denoise_variance.hip).  A pixel whose history has converged is left alone, one disoccluded a frame ago is filtered hard.  The
+ * reference has nothing of this kind: the operation is defined HERE, and the kernels and tests/tools/variance_model.py obey it bit
+ * for bit.  Every operator is one rounded f32 operation, nothing is fused, and the operations run in the order written.
+ *
+ * Buffers.  View-major planar, row 0 = top:
+ *   hdr           3 f32 / pixel, required: the accumulated frame (mipt_temporal's out), or one noisy frame
+ *   normal        3 f32 / pixel, optional; used as given, not normalised
+ *   depth         1 f32 / pixel, optional; a miss is 1e30
+ *   albedo        3 f32 / pixel, optional
+ *   variance      1 f32 / pixel  } what mipt_temporal writes.  Both or neither; neither means a single frame without history.
+ *   length        1 f32 / pixel  }
+ *   out           3 f32 / pixel, required; may be hdr
+ *   variance_out  1 f32 / pixel, optional: the filtered variance after the last iteration
+ * A NULL guide means its term is left out: not computed, not fetched.  A tap outside [0,W) x [0,H) is skipped -- neither weighted nor
+ * added -- in every sum below, and views never see each other.
+ *
+ * Pack.  a and c0 = hdr / a as in the denoiser section; without albedo c0 = hdr.  var0 = variance > 0 ? variance : 0 (a NaN gives 0)
+ * and len = length; with neither plane given var0 = 0 and len = 1 for every pixel.  Luminance everywhere below is
+ * l(c) = ((0.2126f*c.r) + (0.7152f*c.g)) + (0.0722f*c.b).  kn and kz are the denoiser section's, formed on the host.
+ *
+ * Spatial estimate, for a pixel with short_history > 0 && !(len >= short_history), so a NaN length takes this side unless
+ * short_history is 0 -- a history too short for its own variance to mean much borrows one from its neighbourhood:
+ *   - taps q = (x + dx, y + dy), dy = -2 ... 2 the outer loop and dx = -2 ... 2 the inner one, reading the packed c0.
+ *   - the centre has weight w = 1 without evaluation.  Any other tap has eg = (dn*kn) + (dz*kz), dn and dz as in the denoiser
+ *     section and an absent guide's term left out, eg = eg < 128.0f ? eg : 128.0f and w = expf(-eg); with no guide at all w = 1
+ *     without evaluation.
+ *   - s1 = s1 + (w*l_q), s2 = s2 + (w*(l_q*l_q)), ws = ws + w with l_q = l(c0_q), all starting at +0.
+ *   - mu = s1/ws, v = (s2/ws) - (mu*mu), v = v > 0 ? v : 0; lc = len > 1 ? len : 1; var = v * (short_history / lc).
+ * Every other pixel keeps var = var0.
+ *
+ * Iteration i = 0 ... iterations - 1 (1 <= iterations <= 8) has step s = 1 << i, reads the previous iteration's {c, var} and writes
+ * new ones.  For pixel p = (x, y) of view v:
+ *   - prefilter: gv = gs / gw with gs = gs + ((g[dy+1]*g[dx+1]) * var_q) and gw = gw + (g[dy+1]*g[dx+1]) over the neighbours
+ *     q = (x + dx, y + dy) at distance 1 (not s), dy = -1 ... 1 outer and dx = -1 ... 1 inner, the centre included, both sums
+ *     starting at +0; g = [1/4, 1/2, 1/4].
+ *   - kl = 1.0f / ((sigma_luminance * sqrtf(gv)) + 1e-8f), sqrtf correctly rounded.
+ *   - the 25 taps of the denoiser section at step s: e = ((fabsf(l(c_p) - l(c_q)) * kl) + (dn*kn)) + (dz*kz), an absent guide's
+ *     term left out; e = e < 128.0f ? e : 128.0f (a NaN gives 128); w = (h[dy+2]*h[dx+2]) * expf(-e); the centre has weight 9/64
+ *     without evaluation.
+ *   - sum_ch = sum_ch + (w*c_q.ch), sv = sv + ((w*w)*var_q), wsum = wsum + w, all starting at +0.
+ *   - the new colour is, per channel, wsum > 0 ? sum_ch / wsum : c_p.ch; the new variance wsum > 0 ? sv / (wsum*wsum) : var_p.
+ * After the last iteration out = c * a (c without albedo) and variance_out = var.  With var = 0 and neighbouring luminances that
+ * differ by more than 128e-8 every off-centre weight is 0: a converged frame comes back as it went in.  The NaN rule of the query
+ * section applies: a NaN this arithmetic produces is a NaN everywhere, sign and payload the implementation's.
+ *
+ * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- the checks of mipt_denoise (sigma_normal and sigma_depth included), and: only one of variance / length given; a
+ * short_history that is not finite and at least 0; a sigma_luminance that is not finite and greater than 0; variance_out, variance or
+ * length overlapping anything (out == hdr alone is allowed). */
+typedef struct {
+    uint32_t width, height, n_views;
+    uint32_t iterations;          /* 1 ... 8 */
+    float    sigma_luminance, sigma_normal, sigma_depth;
+    float    short_history;       /* >= 0, finite: a pixel with a shorter history takes the spatial estimate; 0 = never */
+    uint32_t flags;               /* must be 0 */
+    uint32_t reserved[7];         /* must be 0 */
+} MiptVarianceOptions;            /* 64 B */
+typedef struct {
+    const float *hdr, *normal, *depth, *albedo;   /* normal, depth, albedo: NULL = absent */
+    const float *variance, *length;               /* both or neither */
+    float       *out;                             /* may be hdr */
+    float       *variance_out;                    /* NULL = not written */
+    void        *reserved[8];                     /* must be NULL */
+} MiptVarianceBuffers;            /* 128 B */
+
+/* Bytes of workspace mipt_denoise_variance_device needs for this size: three float4 planes, 48 B per pixel.  0 = an invalid size. */
+MIPT_API uint64_t mipt_denoise_variance_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views);
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_denoise_variance(const MiptVarianceOptions *opt, const MiptVarianceBuffers *host, int device_id);
+/* DEVICE buffers of one device (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream).  Stream-ordered: it does
+ * not block and allocates nothing, like mipt_denoise_device.  d_workspace is the caller's: 16-byte aligned device memory of at least
+ * mipt_denoise_variance_workspace_bytes().  The call writes `out`, `variance_out` if given and the first
+ * mipt_denoise_variance_workspace_bytes() bytes of the workspace, and nothing else. */
+MIPT_API int mipt_denoise_variance_device(const MiptVarianceOptions *opt, const MiptVarianceBuffers *device, void *d_workspace,
+                                          uint64_t workspace_bytes, void *hip_stream);
+
 /* ---- previous positions: where every pixel's surface point was in the previous geometry ------------------------------------------------
  * The link between the geometry updates and the temporal accumulation above: per pixel the world position that the first hit's
  * surface point had before the last update, to be passed to mipt_temporal as `position` (csrc/first_hit.hip, the MOTION form of the

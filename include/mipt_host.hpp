@@ -146,6 +146,13 @@ struct TemporalState {
     std::vector<float> length, variance;                   // 1 f32 / pixel where asked for
 };
 
+// Renderer::denoise_variance: the filter's settings (MiptVarianceOptions; the defaults of the Python mirror)
+struct VarianceSettings {
+    uint32_t iterations = 5;                               // 1 ... 8; iteration i has step 1 << i
+    float sigma_luminance = 16.0f, sigma_normal = 0.5f, sigma_depth = 0.5f;
+    float short_history = 4.0f;                            // a pixel with a shorter history takes the spatial estimate; 0 = never
+};
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -440,6 +447,46 @@ class Renderer {                                           // src/renderer.rs:8-
         b.albedo = guides.albedo.empty() ? nullptr : guides.albedo.data();
         b.out = out.data();
         const int rc = mipt_denoise(&o, &b, options.device_id);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+
+    // The variance-guided a-trous filter (mipt_denoise_variance, include/mipt.h "variance-guided a-trous filter") over host images of
+    // this renderer's width and height: `hdr` as for denoise, typically what temporal() wrote; `variance` and `length` hold 1 f32 per
+    // pixel -- TemporalState's -- and are both empty for a single frame without history; the guides as for denoise.  `out` is resized
+    // and filled and may be `hdr` itself; `variance_out`, if given, receives the filtered variance.  Returns a MiptStatus; a size that
+    // does not fit is MIPT_ERR_INVALID_ARG before the library is called.
+    int denoise_variance(const std::vector<float> &hdr, uint32_t n_views, const std::vector<float> &variance, const std::vector<float> &length,
+                         const FeatureImages &guides, std::vector<float> &out, const VarianceSettings &settings = VarianceSettings(),
+                         std::vector<float> *variance_out = nullptr) const {
+        MiptVarianceOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.n_views = n_views; o.iterations = settings.iterations;
+        o.sigma_luminance = settings.sigma_luminance; o.sigma_normal = settings.sigma_normal; o.sigma_depth = settings.sigma_depth;
+        o.short_history = settings.short_history;
+        const uint64_t n = (uint64_t)o.width * o.height * n_views;
+        const bool sized = n != 0 && n < MIPT_BATCH_MAX_PIXELS;            // an impossible size is left to the library to refuse
+        auto fits = [&](const std::vector<float> &v, uint64_t k, const char *name, bool required) {
+            if ((v.empty() && !required) || v.size() == n * k) return true;
+            log_error(std::string("Renderer::denoise_variance: ") + name + " holds " + std::to_string(v.size()) + " values, expected " + std::to_string(n * k));
+            return false;
+        };
+        if (sized && !(fits(hdr, 3, "hdr", true) && fits(guides.normal, 3, "normal", false) && fits(guides.depth, 1, "depth", false) &&
+                       fits(guides.albedo, 3, "albedo", false) && fits(variance, 1, "variance", false) && fits(length, 1, "length", false)))
+            return MIPT_ERR_INVALID_ARG;
+        static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
+        if (&out != &hdr) out.assign(sized ? (size_t)n * 3 : 3, 0.0f);
+        if (variance_out) variance_out->assign(sized ? (size_t)n : 1, 0.0f);
+        MiptVarianceBuffers b{};
+        b.hdr = hdr.empty() ? no_pixel : hdr.data();
+        b.normal = guides.normal.empty() ? nullptr : guides.normal.data();
+        b.depth = guides.depth.empty() ? nullptr : guides.depth.data();
+        b.albedo = guides.albedo.empty() ? nullptr : guides.albedo.data();
+        b.variance = variance.empty() ? nullptr : variance.data();
+        b.length = length.empty() ? nullptr : length.data();
+        b.out = out.data();
+        b.variance_out = variance_out ? variance_out->data() : nullptr;
+        const int rc = mipt_denoise_variance(&o, &b, options.device_id);
         if (rc != MIPT_OK) log_error(mipt_last_error());
         return rc;
     }

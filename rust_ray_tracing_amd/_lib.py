@@ -150,6 +150,21 @@ class MiptTemporalBuffers(C.Structure):
 
 assert C.sizeof(MiptTemporalOptions) == 64 and C.sizeof(MiptTemporalBuffers) == 128
 
+
+# ---- variance-guided a-trous filter (include/mipt.h "variance-guided a-trous filter") ----
+class MiptVarianceOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("short_history", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class MiptVarianceBuffers(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p), ("variance", C.c_void_p),
+                ("length", C.c_void_p), ("out", C.c_void_p), ("variance_out", C.c_void_p), ("reserved", C.c_void_p * 8)]
+
+
+assert C.sizeof(MiptVarianceOptions) == 64 and C.sizeof(MiptVarianceBuffers) == 128
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -200,6 +215,7 @@ EXPORTS = [
     "mipt_render_features", "mipt_render_features_device",
     "mipt_denoise_workspace_bytes", "mipt_denoise", "mipt_denoise_device",
     "mipt_temporal_history_bytes", "mipt_temporal", "mipt_temporal_device",
+    "mipt_denoise_variance_workspace_bytes", "mipt_denoise_variance", "mipt_denoise_variance_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
     "mipt_render_motion", "mipt_render_motion_device", "mipt_scene_track_motion",
 ]
@@ -351,6 +367,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_temporal.restype = C.c_int
     lib.mipt_temporal_device.argtypes = [to, vp, tb, vp]
     lib.mipt_temporal_device.restype = C.c_int
+    vo, vb = C.POINTER(MiptVarianceOptions), C.POINTER(MiptVarianceBuffers)
+    lib.mipt_denoise_variance_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.mipt_denoise_variance_workspace_bytes.restype = u64
+    lib.mipt_denoise_variance.argtypes = [vo, vb, C.c_int]
+    lib.mipt_denoise_variance.restype = C.c_int
+    lib.mipt_denoise_variance_device.argtypes = [vo, vb, vp, u64, vp]
+    lib.mipt_denoise_variance_device.restype = C.c_int
     return lib
 
 

@@ -188,6 +188,23 @@ struct DevTemporal {
 // synchronisation inside, and `records` is not read after the call returns)
 hipError_t launch_temporal(DevTemporal d, const float *records, hipStream_t stream);
 
+// ---- variance-guided a-trous filter (denoise_variance.hip; mipt_denoise_variance*) ----
+struct DevVariance {
+    // planar inputs, view-major; normal / depth / albedo NULL = absent (the term is left out); variance and length NULL together = a
+    // single frame without history.  out may be hdr.  variance_out NULL = not written.
+    const float *hdr, *normal, *depth, *albedo, *variance, *length;
+    float *out, *variance_out;
+    // the workspace: three float4 planes of n_pixels each -- the packed guides {n.x, n.y, n.z, z}, then two planes of {r, g, b, var}
+    float4 *guides, *colour[2];
+    uint32_t width, height, n_views, iterations;
+    uint32_t tiles_x, tiles_y;              // 64x4-pixel tiles per row / per column of a view
+    float sigma_l, kn, kz;                  // sigma_luminance as given; 1 / sigma^2 of the guides (include/mipt.h)
+    float short_history;                    // 0 = the spatial-estimate pass is not launched
+};
+// the pack pass, the spatial-estimate pass and `iterations` filter passes, one launch each (stream-ordered; no allocation, no
+// synchronisation inside)
+hipError_t launch_denoise_variance(const DevVariance &d, hipStream_t stream);
+
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);

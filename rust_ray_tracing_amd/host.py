@@ -919,12 +919,85 @@ class Renderer:  # renderer.rs:8-85
         L.check(lib.mipt_denoise(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise")
         return out
 
-    def render_denoised(self, scene: Scene, cameras=None, **denoise_args):
+    # -- variance-guided a-trous filter (include/mipt.h "variance-guided a-trous filter") -----------
+    def denoise_variance(self, hdr, variance=None, length=None, normal=None, depth=None, albedo=None, iterations: int = 5,
+                         sigma_luminance: float = 16.0, sigma_normal: float = 0.5, sigma_depth: float = 0.5, short_history: float = 4.0,
+                         want_variance: bool = False, stream=None):
+        """The variance-guided a-trous filter of include/mipt.h over a frame or a batch of views: ``hdr`` [V,H,W,3] or [H,W,3] float32
+        (the accumulated frame of ``temporal``), ``variance`` and ``length`` [..] as ``temporal`` returns them (both or neither;
+        neither = a single frame without history) and the optional guides of ``denoise``.  numpy arrays go through
+        mipt_denoise_variance on ``options.device_id``; contiguous torch tensors through mipt_denoise_variance_device on ``stream``
+        (a torch stream, a raw hipStream_t or None = torch's current stream) without blocking, with a torch tensor as the workspace.
+        Returns a new array / tensor of ``hdr``'s kind and shape, or with ``want_variance`` the pair (out, variance_out [..])."""
+        torch_in, (v, h, w), p = self._denoise_planes(hdr, normal, depth, albedo)
+        lead = tuple(p["hdr"].shape[:-1])
+        for name, a in (("variance", variance), ("length", length)):
+            if a is None:
+                continue
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: hdr, the guides, variance and length must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                if a.dtype != torch.float32 or not a.is_cuda or a.device != p["hdr"].device:
+                    raise ValueError(f"{name}: expected a float32 tensor on hdr's device {p['hdr'].device}")
+                if tuple(a.shape) != lead:
+                    raise ValueError(f"{name}: expected shape {lead}; got {tuple(a.shape)}")
+                if not a.is_contiguous():
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                p[name] = a
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.float32:
+                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
+                if a.shape != lead:
+                    raise ValueError(f"{name}: expected shape {lead}; got {a.shape}")
+                p[name] = np.ascontiguousarray(a)
+        opt = L.MiptVarianceOptions()
+        opt.width, opt.height, opt.n_views, opt.iterations = w, h, v, iterations
+        opt.sigma_luminance, opt.sigma_normal, opt.sigma_depth, opt.short_history = sigma_luminance, sigma_normal, sigma_depth, short_history
+        bufs = L.MiptVarianceBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            dev = p["hdr"].device
+            out = torch.empty_like(p["hdr"])
+            var_out = torch.empty(lead, dtype=torch.float32, device=dev) if want_variance else None
+            for name, a in p.items():
+                setattr(bufs, name, a.data_ptr())
+            bufs.out = out.data_ptr()
+            if want_variance:
+                bufs.variance_out = var_out.data_ptr()
+            need = int(lib.mipt_denoise_variance_workspace_bytes(w, h, v))
+            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            for t in list(p.values()) + [out, workspace] + ([var_out] if want_variance else []):
+                t.record_stream(s)
+            L.check(lib.mipt_denoise_variance_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream),
+                    "mipt_denoise_variance_device")
+            return (out, var_out) if want_variance else out
+        out = np.empty_like(p["hdr"])
+        var_out = np.zeros(lead, dtype=np.float32) if want_variance else None
+        for name, a in p.items():
+            setattr(bufs, name, a.ctypes.data)
+        bufs.out = out.ctypes.data
+        if want_variance:
+            bufs.variance_out = var_out.ctypes.data
+        L.check(lib.mipt_denoise_variance(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise_variance")
+        return (out, var_out) if want_variance else out
+
+    def render_denoised(self, scene: Scene, cameras=None, variance: bool = False, **denoise_args):
         """Render, guides and filter on one stream with nothing crossing PCIe in between: mipt_render_batch_device with this renderer's
         options, mipt_render_features_device for depth, normal and albedo (one sample, this renderer's seed mode) and
-        mipt_denoise_device (``denoise_args``: iterations, the sigmas, stream).  ``cameras``: a sequence of Camera (or CAMERA records),
-        None = the scene's camera.  Returns (denoised, noisy, features, stats): float32 tensors [V,H,W,3] on ``options.device_id``,
-        the feature dict of ``render_features`` and the stats of the render launch."""
+        mipt_denoise_device (``denoise_args``: iterations, the sigmas, stream).  ``variance=True`` filters with
+        mipt_denoise_variance_device instead, as a single frame without history (``denoise_args``: iterations, sigma_luminance,
+        sigma_normal, sigma_depth, short_history, stream).  ``cameras``: a sequence of Camera (or CAMERA records), None = the scene's
+        camera.  Returns (denoised, noisy, features, stats): float32 tensors [V,H,W,3] on ``options.device_id``, the feature dict of
+        ``render_features`` and the stats of the render launch."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
@@ -949,7 +1022,10 @@ class Renderer:  # renderer.rs:8-85
         stats = st.as_dict()
         one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
         features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo"), device=True, stream=raw, handle=handle)
-        denoised = self.denoise(noisy, features["normal"], features["depth"], features["albedo"], stream=raw, **denoise_args)
+        if variance:
+            denoised = self.denoise_variance(noisy, None, None, features["normal"], features["depth"], features["albedo"], stream=raw, **denoise_args)
+        else:
+            denoised = self.denoise(noisy, features["normal"], features["depth"], features["albedo"], stream=raw, **denoise_args)
         self.last_stats = stats
         return denoised, noisy, features, stats
 
@@ -1073,7 +1149,9 @@ class Renderer:  # renderer.rs:8-85
         mipt_temporal_device and, with ``denoise``, mipt_denoise_device on one stream, the history in two tensors that swap roles.
         ``cameras_per_frame``: per frame a Camera (or CAMERA record) or a sequence of them, one per view; every frame has the same
         number of views.  ``args``: alpha_min, max_history, normal_tol, depth_tol (temporal), iterations, sigma_color, sigma_normal,
-        sigma_depth (denoise), stream.  The renderer must use SEED_PER_SAMPLE -- the pixel stream repeats the same noise every frame,
+        sigma_depth (denoise), stream.  ``denoise="variance"`` runs mipt_denoise_variance_device in mipt_denoise_device's place, fed
+        with the temporal step's ``length`` and ``variance`` on the same stream; its ``args`` are iterations, sigma_luminance,
+        sigma_normal, sigma_depth and short_history.  The renderer must use SEED_PER_SAMPLE -- the pixel stream repeats the same noise every frame,
         and averaging it gains nothing: frame f renders the samples from 1 + f * samples on.  Yields per frame a dict with ``out``
         (the denoised frame, or the accumulated one), ``accumulated``, ``noisy`` [V,H,W,3], ``features``, ``history`` (valid until the
         frame after the next is produced: the two tensors are reused), ``length``, ``variance`` and ``stats``.  ``motion=True`` is for
@@ -1089,7 +1167,11 @@ class Renderer:  # renderer.rs:8-85
             raise ValueError("render_sequence: the renderer's seed_mode must be SEED_PER_SAMPLE; the pixel stream repeats the same noise every frame")
         if motion and (scene.mesh is None or scene._handle is None or not scene._tracks_motion):
             raise ValueError("render_sequence: motion=True needs a resident mesh scene that tracks motion (upload_from_mesh, track_motion)")
-        t_names, d_names = ("alpha_min", "max_history", "normal_tol", "depth_tol"), ("iterations", "sigma_color", "sigma_normal", "sigma_depth")
+        guided = isinstance(denoise, str)
+        if guided and denoise != "variance":
+            raise ValueError(f"render_sequence: denoise must be True, False or \"variance\"; got {denoise!r}")
+        t_names = ("alpha_min", "max_history", "normal_tol", "depth_tol")
+        d_names = ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth", "short_history") if guided else ("iterations", "sigma_color", "sigma_normal", "sigma_depth")
         stream = args.pop("stream", None)
         unknown = [k for k in args if k not in t_names + d_names]
         if unknown:
@@ -1127,7 +1209,11 @@ class Renderer:  # renderer.rs:8-85
                 t_features = {**features, "position": prev_position}
             acc, history, extras = self.temporal(noisy, t_features, table, history=history, want_length=True, want_variance=True, stream=raw,
                                                  history_out=pair[frame & 1], **t_args)
-            out = self.denoise(acc, features["normal"], features["depth"], features["albedo"], stream=raw, **d_args) if denoise else acc
+            if guided:
+                out = self.denoise_variance(acc, extras["variance"], extras["length"], features["normal"], features["depth"], features["albedo"],
+                                            stream=raw, **d_args)
+            else:
+                out = self.denoise(acc, features["normal"], features["depth"], features["albedo"], stream=raw, **d_args) if denoise else acc
             self.last_stats = stats
             result = dict(frame=frame, out=out, accumulated=acc, noisy=noisy, features=features, history=history, length=extras["length"],
                           variance=extras["variance"], stats=stats)
