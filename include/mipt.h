@@ -617,6 +617,89 @@ MIPT_API int mipt_denoise_variance(const MiptVarianceOptions *opt, const MiptVar
 MIPT_API int mipt_denoise_variance_device(const MiptVarianceOptions *opt, const MiptVarianceBuffers *device, void *d_workspace,
                                           uint64_t workspace_bytes, void *hip_stream);
 
+/* ---- guided upsampling: a frame traced and filtered at W/k x H/k plus guides at both resolutions -> the frame at W x H ----------------
+ * The step that closes the pipeline of the four sections above: a joint-bilateral upsampling filter (Kopf et al. 2007) with albedo
+ * demodulation (csrc/upsample.hip).  The trace's cost is linear in the pixels it traces; the first-hit planes cost the same whatever
+ * was traced.  So the frame is traced, accumulated and filtered at 1/k of the resolution, and the geometric edges and the textures
+ * of the full-resolution frame come from the full-resolution normal, depth, material and albedo planes.  The reference has nothing
+ * of this kind: the operation is defined HERE, and the kernels and tests/tools/upsample_model.py obey it bit for bit.  Every
+ * operator is one rounded f32 operation, nothing is fused, and the operations run in the order written.
+ *
+ * Geometry.  width = k*w and height = k*h, k = scale.  cpu.rs:31-35 maps pixel column x to x / width and row r to
+ * (height - r) / height: pixel corners, not centres.  Under the same MiptCamera low-resolution pixel (x, y) therefore traces the ray
+ * of full-resolution pixel (k*x, k*y) up to the jitter, and full-resolution pixel (X, Y) sits at the low-resolution coordinate
+ * (X/k, Y/k) with no half-pixel offset.
+ *
+ * Buffers.  View-major planar, row 0 = top, the low frame w x h and the full frame width x height:
+ *   lo_hdr       3 f32 / low pixel, required: the low-resolution frame, filtered or not
+ *   lo_normal    3 f32 / low pixel  }
+ *   lo_depth     1 f32 / low pixel  } the guides of the low frame, each optional
+ *   lo_albedo    3 f32 / low pixel  }
+ *   lo_material  1 u32 / low pixel  }
+ *   normal, depth, albedo, material   the same planes per full pixel
+ *   out          3 f32 / full pixel, required
+ *   weight       1 f32 / full pixel, optional: wsum below; 0 marks a pixel that found no accepted tap
+ * A guide is given at both resolutions or at neither; one alone is an error that names the missing one.  An absent guide's term is
+ * not computed and not fetched.  The workspace is 32 B per low pixel: two float4 planes.
+ *
+ * Pack, over the low frame.  a_q = lo_albedo > 1/256 ? lo_albedo : 1/256 per channel (the floor of the denoiser section: a NaN gives
+ * the floor) and c_q = lo_hdr / a_q; without albedo c_q = lo_hdr.
+ *
+ * Full-resolution pixel P = (X, Y) of view v:
+ *   - x0 = X / k and rx = X - x0*k in integers; wx = (float)rx / (float)k, ux = 1.0f - wx.  Likewise y0, ry, wy, uy.
+ *   - taps q in the order (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) of view v of the low frame, with the bilinear weights
+ *     b = ux*uy, wx*uy, ux*wy, wx*wy.
+ *   - a tap is skipped when it lies outside [0,w) x [0,h), or when its b is 0 because rx == 0 or ry == 0.  A skipped tap is neither
+ *     fetched, nor weighted, nor added to any sum, and views never see each other.
+ *   - every tap that takes part adds to the plain bilinear sums: sb_ch = sb_ch + (b * c_q.ch) and bsum = bsum + b, all starting at +0.
+ *   - with material: a tap whose lo_material bits differ from the pixel's material bits takes no further part.
+ *   - otherwise e = (dn * kn) + (dz * kz), an absent guide's term left out, with dn = ((dx*dx) + (dy*dy)) + (dz*dz) from n_P - n_q,
+ *     dz = (z_P - z_q) * (z_P - z_q), and kn, kz formed on the host as in the denoiser section; e = e < 128.0f ? e : 128.0f (a NaN
+ *     gives 128); w = b * expf(-e), expf as in the denoiser section.  With neither normal nor depth w = b without evaluation.
+ *   - the tap adds to the guided sums: sum_ch = sum_ch + (w * c_q.ch) and wsum = wsum + w, all starting at +0.
+ *   - the colour is, per channel, c = wsum > 0 ? sum_ch / wsum : sb_ch / bsum.  bsum > 0 always holds: tap (x0, y0) is never skipped
+ *     and its b is above 0.  The second arm is the fallback of a pixel none of whose taps was accepted: plain bilinear.
+ *   - a_P = the floor rule applied to the full-resolution albedo; out = c * a_P (c without albedo); weight = wsum.
+ * A pixel whose X and Y are multiples of k has one tap, (x0, y0) with b = 1.  The NaN rule of the query section applies: a NaN this
+ * arithmetic produces is a NaN everywhere, sign and payload the implementation's.
+ *
+ * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- a null opt, buffers, lo_hdr or out; zero width, height or n_views; scale outside 2 ... 8; width or height not a multiple
+ * of scale; n_views*W*H >= MIPT_BATCH_MAX_PIXELS; a sigma that fails the denoiser's rule (a sigma given for an absent guide is
+ * ignored); a guide given at one resolution only; non-zero flags or reserved fields; any two buffers that overlap -- nothing may
+ * alias here; for the device entry a workspace that is NULL, too small, not 16-byte aligned or overlapped by a buffer, a pointer
+ * that is not 4-byte aligned, and a pointer that is not device memory of one common device (lo_hdr's). */
+typedef struct {
+    uint32_t width, height, n_views;   /* the FULL frame */
+    uint32_t scale;                    /* k, 2 ... 8; width and height must be multiples of it */
+    float    sigma_normal, sigma_depth;
+    uint32_t flags;                    /* must be 0 */
+    uint32_t reserved[9];              /* must be 0 */
+} MiptUpsampleOptions;                 /* 64 B */
+typedef struct {
+    const float    *lo_hdr;                          /* 3 f32 / low pixel, required */
+    const float    *lo_normal, *lo_depth, *lo_albedo;/* 3, 1, 3 f32 / low pixel */
+    const uint32_t *lo_material;                     /* 1 u32 / low pixel */
+    const float    *normal, *depth, *albedo;         /* the same planes at full resolution */
+    const uint32_t *material;
+    float          *out;                             /* 3 f32 / full pixel, required */
+    float          *weight;                          /* 1 f32 / full pixel, optional: wsum */
+    void           *reserved[5];                     /* must be NULL */
+} MiptUpsampleBuffers;                 /* 128 B */
+
+/* Bytes of workspace mipt_upsample_device needs for this size: two float4 planes over the low frame, 32 B per low pixel.  0 = an
+ * invalid size: a zero, n_views*width*height not below MIPT_BATCH_MAX_PIXELS, a scale outside 2 ... 8 or one that does not divide
+ * width and height. */
+MIPT_API uint64_t mipt_upsample_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views, uint32_t scale);
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_upsample(const MiptUpsampleOptions *opt, const MiptUpsampleBuffers *host, int device_id);
+/* DEVICE buffers of one device (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream).  Stream-ordered: it does
+ * not block and allocates nothing, like mipt_denoise_device.  d_workspace is the caller's: 16-byte aligned device memory of at least
+ * mipt_upsample_workspace_bytes().  The call writes `out`, `weight` if given and the first mipt_upsample_workspace_bytes() bytes of
+ * the workspace, and nothing else. */
+MIPT_API int mipt_upsample_device(const MiptUpsampleOptions *opt, const MiptUpsampleBuffers *device, void *d_workspace,
+                                  uint64_t workspace_bytes, void *hip_stream);
+
 /* ---- previous positions: where every pixel's surface point was in the previous geometry ------------------------------------------------
  * The link between the geometry updates and the temporal accumulation above: per pixel the world position that the first hit's
  * surface point had before the last update, to be passed to mipt_temporal as `position` (csrc/first_hit.hip, the MOTION form of the

@@ -153,6 +153,12 @@ struct VarianceSettings {
     float short_history = 4.0f;                            // a pixel with a shorter history takes the spatial estimate; 0 = never
 };
 
+// Renderer::upsample: the filter's settings (MiptUpsampleOptions; the defaults of the Python mirror)
+struct UpsampleSettings {
+    uint32_t scale = 2;                                    // k, 2 ... 8: the low frame is width/k x height/k
+    float sigma_normal = 0.5f, sigma_depth = 0.5f;
+};
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -487,6 +493,49 @@ class Renderer {                                           // src/renderer.rs:8-
         b.out = out.data();
         b.variance_out = variance_out ? variance_out->data() : nullptr;
         const int rc = mipt_denoise_variance(&o, &b, options.device_id);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+
+    // The guided upsampling (mipt_upsample, include/mipt.h "guided upsampling") over host images: this renderer's width and height are
+    // the FULL frame, `lo_hdr` holds n_views frames of (width/scale) x (height/scale) pixels, 3 f32 each, view-major; `lo_guides` and
+    // `guides` the normal, depth, albedo and material images of render_features at the low and at the full resolution, each at both
+    // or at neither (empty = absent).  `out` is resized to the full frame and filled; `weight`, if given, receives the sum of the
+    // accepted taps' weights, 0 where a pixel fell back to plain bilinear.  Returns a MiptStatus; a size that does not fit is
+    // MIPT_ERR_INVALID_ARG before the library is called.
+    int upsample(const std::vector<float> &lo_hdr, uint32_t n_views, const FeatureImages &lo_guides, const FeatureImages &guides,
+                 std::vector<float> &out, const UpsampleSettings &settings = UpsampleSettings(), std::vector<float> *weight = nullptr) const {
+        MiptUpsampleOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.n_views = n_views; o.scale = settings.scale;
+        o.sigma_normal = settings.sigma_normal; o.sigma_depth = settings.sigma_depth;
+        const uint64_t n = (uint64_t)o.width * o.height * n_views;
+        // an impossible size or scale is left to the library to refuse
+        const bool sized = n != 0 && n < MIPT_BATCH_MAX_PIXELS && o.scale >= 2 && o.scale <= 8 && o.width % o.scale == 0 && o.height % o.scale == 0;
+        const uint64_t n_lo = sized ? n / ((uint64_t)o.scale * o.scale) : 0;
+        auto fits = [&](size_t have, uint64_t want, const char *name, bool required) {
+            if ((have == 0 && !required) || have == want) return true;
+            log_error(std::string("Renderer::upsample: ") + name + " holds " + std::to_string(have) + " values, expected " + std::to_string(want));
+            return false;
+        };
+        if (sized && !(fits(lo_hdr.size(), n_lo * 3, "lo_hdr", true) && fits(lo_guides.normal.size(), n_lo * 3, "lo_normal", false) &&
+                       fits(lo_guides.depth.size(), n_lo, "lo_depth", false) && fits(lo_guides.albedo.size(), n_lo * 3, "lo_albedo", false) &&
+                       fits(lo_guides.material.size(), n_lo, "lo_material", false) && fits(guides.normal.size(), n * 3, "normal", false) &&
+                       fits(guides.depth.size(), n, "depth", false) && fits(guides.albedo.size(), n * 3, "albedo", false) &&
+                       fits(guides.material.size(), n, "material", false)))
+            return MIPT_ERR_INVALID_ARG;
+        static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
+        out.assign(sized ? (size_t)n * 3 : 3, 0.0f);
+        if (weight) weight->assign(sized ? (size_t)n : 1, 0.0f);
+        auto plane = [](const auto &v) { return v.empty() ? nullptr : v.data(); };
+        MiptUpsampleBuffers b{};
+        b.lo_hdr = lo_hdr.empty() ? no_pixel : lo_hdr.data();
+        b.lo_normal = plane(lo_guides.normal); b.lo_depth = plane(lo_guides.depth); b.lo_albedo = plane(lo_guides.albedo);
+        b.lo_material = plane(lo_guides.material);
+        b.normal = plane(guides.normal); b.depth = plane(guides.depth); b.albedo = plane(guides.albedo); b.material = plane(guides.material);
+        b.out = out.data();
+        b.weight = weight ? weight->data() : nullptr;
+        const int rc = mipt_upsample(&o, &b, options.device_id);
         if (rc != MIPT_OK) log_error(mipt_last_error());
         return rc;
     }

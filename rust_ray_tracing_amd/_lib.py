@@ -165,6 +165,21 @@ class MiptVarianceBuffers(C.Structure):
 
 assert C.sizeof(MiptVarianceOptions) == 64 and C.sizeof(MiptVarianceBuffers) == 128
 
+
+# ---- guided upsampling (include/mipt.h "guided upsampling") ----
+class MiptUpsampleOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("scale", C.c_uint32),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 9)]
+
+
+class MiptUpsampleBuffers(C.Structure):
+    _fields_ = [("lo_hdr", C.c_void_p), ("lo_normal", C.c_void_p), ("lo_depth", C.c_void_p), ("lo_albedo", C.c_void_p),
+                ("lo_material", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("albedo", C.c_void_p),
+                ("material", C.c_void_p), ("out", C.c_void_p), ("weight", C.c_void_p), ("reserved", C.c_void_p * 5)]
+
+
+assert C.sizeof(MiptUpsampleOptions) == 64 and C.sizeof(MiptUpsampleBuffers) == 128
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -216,6 +231,7 @@ EXPORTS = [
     "mipt_denoise_workspace_bytes", "mipt_denoise", "mipt_denoise_device",
     "mipt_temporal_history_bytes", "mipt_temporal", "mipt_temporal_device",
     "mipt_denoise_variance_workspace_bytes", "mipt_denoise_variance", "mipt_denoise_variance_device",
+    "mipt_upsample_workspace_bytes", "mipt_upsample", "mipt_upsample_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
     "mipt_render_motion", "mipt_render_motion_device", "mipt_scene_track_motion",
 ]
@@ -374,6 +390,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_denoise_variance.restype = C.c_int
     lib.mipt_denoise_variance_device.argtypes = [vo, vb, vp, u64, vp]
     lib.mipt_denoise_variance_device.restype = C.c_int
+    uo, ub = C.POINTER(MiptUpsampleOptions), C.POINTER(MiptUpsampleBuffers)
+    lib.mipt_upsample_workspace_bytes.argtypes = [u32, u32, u32, u32]
+    lib.mipt_upsample_workspace_bytes.restype = u64
+    lib.mipt_upsample.argtypes = [uo, ub, C.c_int]
+    lib.mipt_upsample.restype = C.c_int
+    lib.mipt_upsample_device.argtypes = [uo, ub, vp, u64, vp]
+    lib.mipt_upsample_device.restype = C.c_int
     return lib
 
 

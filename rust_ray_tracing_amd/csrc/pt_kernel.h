@@ -205,6 +205,27 @@ struct DevVariance {
 // synchronisation inside)
 hipError_t launch_denoise_variance(const DevVariance &d, hipStream_t stream);
 
+// ---- guided upsampling (upsample.hip; mipt_upsample*) ----
+struct DevUpsample {
+    // planar inputs, view-major: the low frame (lo_width x lo_height) and its guides, then the same guides at full resolution.  A
+    // guide is given at both resolutions or at neither (NULL = the term is left out).  weight NULL = not written.
+    const float *lo_hdr, *lo_normal, *lo_depth, *lo_albedo;
+    const uint32_t *lo_material;
+    const float *normal, *depth, *albedo;
+    const uint32_t *material;
+    float *out, *weight;
+    // the workspace: two float4 planes of one entry per LOW pixel -- {c.r, c.g, c.b, bits(lo_material)}, then {n.x, n.y, n.z, z}
+    float4 *colour, *guides;
+    uint32_t width, height, n_views, scale; // the full frame; lo_width * scale == width, lo_height * scale == height
+    uint32_t lo_width, lo_height;
+    uint32_t tiles_x, tiles_y;              // 64x4-pixel tiles per row / per column of a full-resolution view
+    uint32_t lo_tiles_x, lo_tiles_y;        // and of a low-resolution view
+    float kn, kz;                           // 1 / sigma^2 of the guides (include/mipt.h)
+};
+// the pack pass over the low frame and the upsampling pass over the full frame, one launch each (stream-ordered; no allocation, no
+// synchronisation inside)
+hipError_t launch_upsample(const DevUpsample &d, hipStream_t stream);
+
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);

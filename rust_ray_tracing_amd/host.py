@@ -990,18 +990,156 @@ class Renderer:  # renderer.rs:8-85
         L.check(lib.mipt_denoise_variance(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise_variance")
         return (out, var_out) if want_variance else out
 
-    def render_denoised(self, scene: Scene, cameras=None, variance: bool = False, **denoise_args):
+    # -- guided upsampling (include/mipt.h "guided upsampling") ---------------------------------------
+    _UPSAMPLE_GUIDES = (("normal", 3), ("depth", 1), ("albedo", 3), ("material", 1))
+
+    @staticmethod
+    def _upsample_planes(lo_hdr, lo_guides, guides, scale):
+        """-> (torch?, (V, H, W), {buffer field: contiguous array or tensor}); ValueError naming the argument for anything else."""
+        torch_in = Scene._is_torch(lo_hdr)
+        if not torch_in:
+            lo_hdr = np.asarray(lo_hdr)
+        if lo_hdr.ndim not in (3, 4) or lo_hdr.shape[-1] != 3:
+            raise ValueError(f"lo_hdr: expected shape [V,h,w,3] or [h,w,3]; got {tuple(lo_hdr.shape)}")
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 2 <= scale <= 8:
+            raise ValueError(f"scale: expected an integer 2 ... 8; got {scale!r}")
+        for name, g in (("lo_guides", lo_guides), ("guides", guides)):
+            if g is not None and not isinstance(g, dict):
+                raise ValueError(f"{name}: expected a dict with any of normal, depth, albedo, material, or None")
+        lo_guides, guides = lo_guides or {}, guides or {}
+        lo_lead = tuple(lo_hdr.shape[:-1])
+        lead = lo_lead[:-2] + (lo_lead[-2] * scale, lo_lead[-1] * scale)
+        planes = {}
+        todo = [("lo_hdr", lo_hdr, lo_lead, 3, False)]
+        for name, k in Renderer._UPSAMPLE_GUIDES:
+            lo, hi = lo_guides.get(name), guides.get(name)
+            if (lo is None) != (hi is None):
+                where = "guides" if lo is None else "lo_guides"
+                raise ValueError(f"{'lo_' + name if lo is None else name}: {name} is given at both resolutions or at neither; only {where} holds it")
+            if lo is not None:
+                todo += [("lo_" + name, lo, lo_lead, k, name == "material"), (name, hi, lead, k, name == "material")]
+        for name, a, ld, k, ids in todo:
+            want = ld + ((k,) if k > 1 else ())
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: lo_hdr and the guides must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                dt = torch.int32 if ids else torch.float32
+                if a.dtype != dt or not a.is_cuda or a.device != lo_hdr.device:
+                    raise ValueError(f"{name}: expected a {str(dt).replace('torch.', '')} tensor on lo_hdr's device {lo_hdr.device}")
+                if tuple(a.shape) != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
+                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                planes[name] = a
+            else:
+                a = np.asarray(a)
+                dt = np.uint32 if ids else np.float32
+                if a.dtype != dt:
+                    raise ValueError(f"{name}: expected {np.dtype(dt).name}; got {a.dtype}")
+                if a.shape != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
+                planes[name] = np.ascontiguousarray(a)
+        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
+        return torch_in, (v, h, w), lead, planes
+
+    def upsample(self, lo_hdr, lo_guides, guides, scale, sigma_normal: float = 0.5, sigma_depth: float = 0.5, want_weight: bool = False,
+                 stream=None):
+        """The guided upsampling of include/mipt.h over a frame or a batch of views: ``lo_hdr`` [V,h,w,3] or [h,w,3] float32, the
+        frame traced (and filtered) at 1/``scale`` of the resolution, comes back at [..,h*scale,w*scale,3].  ``lo_guides`` and
+        ``guides``: dicts as ``render_features`` returns them at the low and at the full resolution; the keys used are ``normal``
+        [..,3], ``depth`` [..], ``albedo`` [..,3] float32 and ``material`` [..] (uint32 arrays / int32 tensors, the same bits), each
+        in both dicts or in neither (None = no guides); other keys are ignored.  numpy arrays go through mipt_upsample on
+        ``options.device_id``; contiguous torch tensors through mipt_upsample_device on ``stream`` (a torch stream, a raw hipStream_t
+        or None = torch's current stream) without blocking, with a torch tensor as the workspace.  Returns a new array / tensor of
+        ``lo_hdr``'s kind, or with ``want_weight`` the pair (out, weight [..,h*scale,w*scale]): the sum of the accepted taps'
+        weights, 0 where a pixel fell back to plain bilinear."""
+        torch_in, (v, h, w), lead, p = self._upsample_planes(lo_hdr, lo_guides, guides, scale)
+        opt = L.MiptUpsampleOptions()
+        opt.width, opt.height, opt.n_views, opt.scale = w, h, v, int(scale)
+        opt.sigma_normal, opt.sigma_depth = sigma_normal, sigma_depth
+        bufs = L.MiptUpsampleBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            dev = p["lo_hdr"].device
+            out = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
+            weight = torch.empty(lead, dtype=torch.float32, device=dev) if want_weight else None
+            for name, a in p.items():
+                setattr(bufs, name, a.data_ptr())
+            bufs.out = out.data_ptr()
+            if want_weight:
+                bufs.weight = weight.data_ptr()
+            need = int(lib.mipt_upsample_workspace_bytes(w, h, v, int(scale)))
+            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            for t in list(p.values()) + [out, workspace] + ([weight] if want_weight else []):
+                t.record_stream(s)
+            L.check(lib.mipt_upsample_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), "mipt_upsample_device")
+            return (out, weight) if want_weight else out
+        out = np.empty(lead + (3,), dtype=np.float32)
+        weight = np.zeros(lead, dtype=np.float32) if want_weight else None
+        for name, a in p.items():
+            setattr(bufs, name, a.ctypes.data)
+        bufs.out = out.ctypes.data
+        if want_weight:
+            bufs.weight = weight.ctypes.data
+        L.check(lib.mipt_upsample(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_upsample")
+        return (out, weight) if want_weight else out
+
+    _FULL_FEATURES = ("depth", "normal", "albedo", "material")
+
+    def _low_resolution(self, upsample, who):
+        """the renderer that traces at 1/upsample of this one's output_image_dimensions; ValueError unless they are multiples of it"""
+        w, h = self.options.output_image_dimensions
+        if isinstance(upsample, bool) or not isinstance(upsample, (int, np.integer)) or not 2 <= upsample <= 8:
+            raise ValueError(f"{who}: upsample must be None or an integer 2 ... 8; got {upsample!r}")
+        if w % upsample or h % upsample:
+            raise ValueError(f"{who}: output_image_dimensions {w}x{h} are not multiples of upsample={upsample}")
+        return Renderer(RendererOptions(**{**self.options.__dict__, "output_image_dimensions": (w // upsample, h // upsample)}))
+
+    def render_denoised(self, scene: Scene, cameras=None, variance: bool = False, upsample=None, **denoise_args):
         """Render, guides and filter on one stream with nothing crossing PCIe in between: mipt_render_batch_device with this renderer's
         options, mipt_render_features_device for depth, normal and albedo (one sample, this renderer's seed mode) and
         mipt_denoise_device (``denoise_args``: iterations, the sigmas, stream).  ``variance=True`` filters with
         mipt_denoise_variance_device instead, as a single frame without history (``denoise_args``: iterations, sigma_luminance,
         sigma_normal, sigma_depth, short_history, stream).  ``cameras``: a sequence of Camera (or CAMERA records), None = the scene's
         camera.  Returns (denoised, noisy, features, stats): float32 tensors [V,H,W,3] on ``options.device_id``, the feature dict of
-        ``render_features`` and the stats of the render launch."""
+        ``render_features`` and the stats of the render launch.  ``upsample=k`` (2 ... 8; ``output_image_dimensions`` must be
+        multiples of it) traces, takes the guides (material as well) and filters at (W/k, H/k) exactly as above, then runs one
+        full-resolution feature pass (depth, normal, albedo, material; one sample; the same cameras) and mipt_upsample_device on the
+        same stream (``denoise_args`` may hold upsample_sigma_normal and upsample_sigma_depth).  It returns (full, denoised, noisy,
+        features, features_full, stats): ``full`` [V,H,W,3] and the dict ``features_full`` at ``output_image_dimensions``, the other
+        four as above at (W/k, H/k)."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
             raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        if upsample is not None:
+            low = self._low_resolution(upsample, "render_denoised")
+            u_args = {k[len("upsample_"):]: denoise_args.pop(k) for k in ("upsample_sigma_normal", "upsample_sigma_depth") if k in denoise_args}
+            stream = denoise_args.get("stream")
+            if stream is None:
+                stream = denoise_args["stream"] = torch.cuda.current_stream(torch.device("cuda", o.device_id))
+            denoised, noisy, features, stats = low._render_denoised_low(scene, cameras, variance, ("depth", "normal", "albedo", "material"), denoise_args)
+            cams = [scene.camera] if cameras is None else list(cameras)
+            raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+            one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
+            features_full, _ = one.render_features(scene, cams, self._FULL_FEATURES, device=True, stream=raw)
+            full = self.upsample(denoised, features, features_full, upsample, stream=raw, **u_args)
+            self.last_stats = stats
+            return full, denoised, noisy, features, features_full, stats
+        return self._render_denoised_low(scene, cameras, variance, ("depth", "normal", "albedo"), denoise_args)
+
+    def _render_denoised_low(self, scene, cameras, variance, names, denoise_args):
+        """render_denoised at this renderer's own size, with the feature planes `names`"""
+        import torch
+        o = self.options
         cams = [scene.camera] if cameras is None else list(cameras)
         if not cams:
             raise ValueError("render_denoised: no cameras")
@@ -1021,7 +1159,7 @@ class Renderer:  # renderer.rs:8-85
                 "mipt_render_batch_device")
         stats = st.as_dict()
         one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
-        features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo"), device=True, stream=raw, handle=handle)
+        features, _ = one.render_features(scene, cams, names, device=True, stream=raw, handle=handle)
         if variance:
             denoised = self.denoise_variance(noisy, None, None, features["normal"], features["depth"], features["albedo"], stream=raw, **denoise_args)
         else:
@@ -1143,7 +1281,7 @@ class Renderer:  # renderer.rs:8-85
         L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
         return out, new, extras
 
-    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, **args):
+    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, upsample=None, **args):
         """A camera path without flicker, nothing crossing PCIe in between: a generator that per frame runs mipt_render_batch_device
         with this renderer's options, mipt_render_features_device (depth, normal, albedo, position, material; one sample),
         mipt_temporal_device and, with ``denoise``, mipt_denoise_device on one stream, the history in two tensors that swap roles.
@@ -1158,7 +1296,12 @@ class Renderer:  # renderer.rs:8-85
         parts that move: the scene must be a resident mesh that tracks motion (``Scene.track_motion``), the caller moves its parts
         with ``scene.set_transforms`` / ``update_mesh_device`` between two ``next()`` calls (at most one update per frame), and each
         frame also runs mipt_render_motion_device with the options of its feature pass, hands that plane to the temporal step as
-        ``position`` and yields it as ``prev_position``; ``features["position"]`` stays the current one."""
+        ``position`` and yields it as ``prev_position``; ``features["position"]`` stays the current one.  ``upsample=k`` (2 ... 8;
+        ``output_image_dimensions`` must be multiples of it): the trace, the feature and motion passes, the temporal step with its
+        histories and the filter all run at (W/k, H/k) exactly as above, then one full-resolution feature pass (depth, normal, albedo,
+        material; one sample; the same cameras) and mipt_upsample_device run on the same stream (``args`` may hold
+        upsample_sigma_normal and upsample_sigma_depth).  Every key above keeps its meaning at (W/k, H/k); the dict gains ``out_full``
+        [V,H,W,3], ``out`` upsampled to ``output_image_dimensions``, and ``features_full``, the dict of that feature pass."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
@@ -1173,6 +1316,10 @@ class Renderer:  # renderer.rs:8-85
         t_names = ("alpha_min", "max_history", "normal_tol", "depth_tol")
         d_names = ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth", "short_history") if guided else ("iterations", "sigma_color", "sigma_normal", "sigma_depth")
         stream = args.pop("stream", None)
+        u_args = {}
+        if upsample is not None:
+            o = self._low_resolution(upsample, "render_sequence").options
+            u_args = {k[len("upsample_"):]: args.pop(k) for k in ("upsample_sigma_normal", "upsample_sigma_depth") if k in args}
         unknown = [k for k in args if k not in t_names + d_names]
         if unknown:
             raise ValueError(f"render_sequence: unknown arguments {unknown}")
@@ -1183,6 +1330,7 @@ class Renderer:  # renderer.rs:8-85
             stream = torch.cuda.current_stream(dev)
         raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
+        one_full = Renderer(RendererOptions(**{**self.options.__dict__, "samples": 1})) if upsample is not None else None
         lib = L.load()
         handle, pair, history, n = None, None, None, None
         for frame, cams in enumerate(cameras_per_frame):
@@ -1219,6 +1367,9 @@ class Renderer:  # renderer.rs:8-85
                           variance=extras["variance"], stats=stats)
             if motion:
                 result["prev_position"] = prev_position
+            if upsample is not None:
+                result["features_full"], _ = one_full.render_features(scene, cams, self._FULL_FEATURES, device=True, stream=raw, handle=handle)
+                result["out_full"] = self.upsample(out, features, result["features_full"], upsample, stream=raw, **u_args)
             yield result
 
     def render_buffers_multi(self, scene: Scene, mode: int = L.MULTI_TILES, device_ids=None, want_hdr: bool = True,
