@@ -79,6 +79,19 @@ MIPT_DIAG_API int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words
 MIPT_DIAG_API int mipt_debug_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order_out);
 MIPT_DIAG_API int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *order_out, uint32_t cap, uint32_t info_out[3]);
 
+/* The hot pixels of the trace kernel (pt_kernel.hip "hot pixels"), for tests/test_gpu_hot_pixels.py.
+ *   mipt_debug_hot_select       the product's selection kernels on host arrays: hot_out[0 .. n_hot) = the n_hot of the n_slots slots of
+ *                               highest cost[] -- bucket min(1023, floor(cost * 16 / samples)) descending, slot index ascending within
+ *                               a bucket -- and bits_out = one bit per slot, set for those, (n_slots + 63) / 64 * 2 words.
+ *                               1 <= n_hot <= n_slots.
+ *   mipt_diag_scene_hot_pixels  what a scene handle of libmipt.so keeps beside its tile order: info_out[0] = slots, 64 per local tile
+ *                               (0 = no valid state), [1] = H, the entries of the list made behind that launch, [2] = the entries
+ *                               that launch itself took from the list made before it (0 = it ran without one); with non-NULL
+ *                               buffers of cap_slots / cap_hot words, that launch's rays per slot and the list.
+ * Return as mipt_debug_eval. */
+MIPT_DIAG_API int mipt_debug_hot_select(const uint32_t *cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *hot_out, uint32_t *bits_out);
+MIPT_DIAG_API int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint32_t cap_slots, uint32_t *hot_out, uint32_t cap_hot, uint32_t info_out[3]);
+
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 
 /* The library-internal device-layout orders of libmipt.so (rust_ray_tracing_amd/csrc/bvh_build.cpp, hidden there), re-exported for

@@ -47,7 +47,7 @@ void mipt::free_scene(MiptScene *s) {
     mipt::free_mesh(s);
     void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
                     s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams, s->d_qrays, s->d_qout,
-                    s->d_tile_cost, s->d_tile_order};
+                    s->d_tile_cost, s->d_tile_order, s->d_pixel_cost, s->d_hot, s->d_hot_bits, s->d_hot_work};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -504,6 +504,15 @@ static int validate_batch(const MiptScene *scene, const MiptCamera *cameras, uin
 }
 
 } // extern "C"
+// Hot pixels (render_launch): H = resident lanes x NUM / DEN, at most a quarter of the local pixels.  Config M, the same view again,
+// kernel ms median: 72.6 / 71.6 / 70.4 / 70.1 at 1/4, 1/2, 1 and 2 per lane against 74.1 - 74.4 without (0 / 1 = no hot list, the
+// pixels' costs are still measured: 74.4 - 74.6); tools/experiments/hot_pixels_result.txt.
+#ifndef MIPT_HOT_LANES_NUM
+#define MIPT_HOT_LANES_NUM 2
+#endif
+#ifndef MIPT_HOT_LANES_DEN
+#define MIPT_HOT_LANES_DEN 1
+#endif
 // `pack_single`: honour MIPT_FLAG_PACKED also at tile_world == 1 (mipt_render_multi with one device keeps the same
 // gather + unpack path as with eight); through the public entry PACKED at world 1 means full-frame, as documented.
 // `batch` (mipt_render_batch*, validated by validate_batch): `cameras` holds n_views cameras and the frame is n_views views of
@@ -591,22 +600,50 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     // better than chance while the order gives up the plain one's locality (neighbouring tiles in flight together), +1 % of kernel
     // time; at 0.5 degrees it is a wash.  A launch with another key or camera runs in the plain order and only
     // measures; counting, batch, wgpu-shading and accumulating launches and a rank without tiles neither use nor touch the state.
-    const bool order_on = !count && !batch && opt->shading == MIPT_SHADING_CPU && !(opt->flags & MIPT_FLAG_ACCUM) && pr.n_local_tiles != 0u;
-    pr.tile_order = nullptr; pr.tile_cost = nullptr;
+    // Hot pixels.  Single heavy pixels make that tail (measured on config M: the heaviest is 4.4 x the mean, a sequential chain of
+    // ~70 % of the frame, yet adds 5 % to its tile's sum): so the cost is measured per pixel -- the tile costs are the sums, taken
+    // behind the launch -- and the H most expensive pixels -- two per resident lane of the launch that measured them, at most a
+    // quarter of the local pixels -- are handed out before everything else, so that every long chain starts with the frame; the
+    // pass over the ordered tiles skips them.  Same key, same valid flag; the frame's tail share 7.5 -> 5.6 % of its wave-cycles.
+    // H is NOT a function of the key: the grid depends on the traversal mode (5 blocks per CU culled, 4 un-culled), which the key
+    // leaves out.  So a launch takes the list with the H it was made with (hot_n), whatever its own grid, the list's buffer is sized
+    // by the key alone (the cap), and a buffer that has to grow takes the state with it.
+    const bool order_on = !count && !batch && opt->shading == MIPT_SHADING_CPU && !(opt->flags & MIPT_FLAG_ACCUM) && pr.n_local_tiles != 0u &&
+                          pr.n_local_tiles < (1u << 26);                  // a slot (local tile * 64 + pixel) is 32 bits
+    pr.tile_order = nullptr; pr.pixel_cost = nullptr; pr.hot = nullptr; pr.hot_bits = nullptr; pr.n_hot = 0u;
+    const uint32_t n_slots = order_on ? pr.n_local_tiles * 64u : 0u;
+    uint32_t hot_next = 0u;                                               // H of the list made behind this launch
+    if (order_on) {
+        const unsigned long long lanes = (unsigned long long)grid * mipt::kBlockThreads * MIPT_HOT_LANES_NUM / MIPT_HOT_LANES_DEN;
+        hot_next = (uint32_t)(lanes < n_slots / 4u ? lanes : n_slots / 4u);
+    }
     if (order_on) {
         const uint32_t key[7] = {opt->width, opt->height, world, opt->tile_rank, pr.n_local_tiles, pr.seed_mode, opt->samples};
         const size_t bytes = (size_t)pr.n_local_tiles * sizeof(uint32_t);
-        if (scene->tile_cost_bytes < bytes || scene->tile_order_bytes < bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
+        // every buffer of the state is sized by the key alone; one that is too small is replaced without its contents
+        const size_t hot_bytes = (size_t)(n_slots / 4u) * sizeof(uint32_t), work_bytes = mipt::hot_work_words(n_slots) * sizeof(uint32_t);
+        if (scene->tile_cost_bytes < bytes || scene->tile_order_bytes < bytes || scene->pixel_cost_bytes < bytes * 64 || scene->hot_bytes < hot_bytes ||
+            scene->hot_bits_bytes < bytes * 2 || scene->hot_work_bytes < work_bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
             memcmp(pr.cam, scene->tile_cam, sizeof pr.cam) != 0)
             scene->tile_order_valid = false;
         if ((rc = mipt::grow_device_buffer((void **)&scene->d_tile_cost, &scene->tile_cost_bytes, bytes))) return rc;
         if ((rc = mipt::grow_device_buffer((void **)&scene->d_tile_order, &scene->tile_order_bytes, bytes))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_pixel_cost, &scene->pixel_cost_bytes, bytes * 64))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot, &scene->hot_bytes, hot_bytes))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot_bits, &scene->hot_bits_bytes, bytes * 2))) return rc;
+        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot_work, &scene->hot_work_bytes, work_bytes))) return rc;
         memcpy(scene->tile_key, key, sizeof key);
         memcpy(scene->tile_cam, pr.cam, sizeof pr.cam);
-        MIPT_HIP(hipMemsetAsync(scene->d_tile_cost, 0, bytes, stream));      // the sort behind the last launch has read them
-        pr.tile_cost = scene->d_tile_cost;
+        MIPT_HIP(hipMemsetAsync(scene->d_pixel_cost, 0, bytes * 64, stream));   // the kernels behind the last launch have read them
+        pr.pixel_cost = scene->d_pixel_cost;
         pr.tile_order = scene->tile_order_valid ? scene->d_tile_order : nullptr;
         scene->tile_order_used = scene->tile_order_valid;
+        scene->hot_used = 0u;
+        if (scene->tile_order_valid && scene->hot_n != 0u) {
+            pr.hot = scene->d_hot; pr.hot_bits = scene->d_hot_bits; pr.n_hot = scene->hot_n;
+            pr.total_work += scene->hot_n;
+            scene->hot_used = scene->hot_n;
+        }
         scene->tile_order_valid = false;                          // until the sort behind this launch is queued
     }
     // the batch's camera table: one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream
@@ -635,7 +672,11 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         },
         [&]() -> int {
             if (order_on) {                                       // behind ev1: kernel_ms stays the trace alone
+                MIPT_HIP(mipt::launch_pixel_reduce(scene->d_pixel_cost, n_slots, opt->samples, scene->d_tile_cost, scene->d_hot_work, stream));
                 MIPT_HIP(mipt::launch_tile_order(scene->d_tile_cost, pr.n_local_tiles, opt->samples, scene->d_tile_order, stream));
+                if (hot_next != 0u)
+                    MIPT_HIP(mipt::launch_hot_select(scene->d_pixel_cost, n_slots, opt->samples, hot_next, scene->d_hot_work, scene->d_hot, scene->d_hot_bits, stream));
+                scene->hot_n = hot_next;
                 scene->tile_order_valid = true;
             }
             if (touched) {

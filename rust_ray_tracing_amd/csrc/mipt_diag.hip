@@ -265,6 +265,43 @@ int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *
     return 0;
 }
 
+// hot pixels (pt_kernel.hip "hot pixels"): the product's selection on host arrays, and the state a scene handle keeps
+int mipt_debug_hot_select(const uint32_t *cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *hot_out, uint32_t *bits_out) {
+    if (!cost || !hot_out || !bits_out || n_slots == 0 || samples == 0 || n_hot == 0 || n_hot > n_slots) {
+        snprintf(g_err, sizeof g_err, "mipt_debug_hot_select: bad argument");
+        return -1;
+    }
+    const size_t bit_words = ((size_t)n_slots + 63) / 64 * 2;
+    mipt::DevPtr<uint32_t> dcost, dwork, dhot, dbits;
+    hipError_t e;
+    if ((e = dcost.alloc(n_slots)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dwork.alloc(mipt::hot_work_words(n_slots))) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dhot.alloc(n_hot)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = dbits.alloc(bit_words)) != hipSuccess) return fail(e, "hipMalloc");
+    if ((e = hipMemcpy(dcost, cost, (size_t)n_slots * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemset(dhot, 0xff, (size_t)n_hot * 4)) != hipSuccess) return fail(e, "hipMemset");
+    if ((e = hipMemset(dbits, 0xff, bit_words * 4)) != hipSuccess) return fail(e, "hipMemset");
+    if ((e = mipt::launch_pixel_reduce(dcost, n_slots, samples, nullptr, dwork, nullptr)) != hipSuccess) return fail(e, "launch_pixel_reduce");
+    if ((e = mipt::launch_hot_select(dcost, n_slots, samples, n_hot, dwork, dhot, dbits, nullptr)) != hipSuccess) return fail(e, "launch_hot_select");
+    if ((e = hipMemcpy(hot_out, dhot, (size_t)n_hot * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if ((e = hipMemcpy(bits_out, dbits, bit_words * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint32_t cap_slots, uint32_t *hot_out, uint32_t cap_hot, uint32_t info_out[3]) {
+    const MiptScene *s = (const MiptScene *)scene;
+    if (!s || !info_out) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_hot_pixels: bad argument"); return -1; }
+    const uint32_t n = s->tile_order_valid ? s->tile_key[4] * 64u : 0u, h = s->tile_order_valid ? s->hot_n : 0u;
+    info_out[0] = n; info_out[1] = h; info_out[2] = s->tile_order_valid ? s->hot_used : 0u;
+    if (n == 0u || !pixel_cost_out || !hot_out) return 0;
+    if (cap_slots < n || cap_hot < h) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_hot_pixels: cap %u / %u < %u slots / %u hot", cap_slots, cap_hot, n, h); return -1; }
+    hipError_t e;
+    if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
+    if ((e = hipMemcpy(pixel_cost_out, s->d_pixel_cost, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    if (h != 0u && (e = hipMemcpy(hot_out, s->d_hot, (size_t)h * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
 // payload, not allocation: the pool is n_texels words, a table one record per material (both allocations are padded when tiny).
 // tests/cpp/scene_hooks.hip copies the three to the host (mipt_diag_scene_read, which = 2 / 3 / 4).
 int mipt_diag_scene_tables(const void *scene, uint64_t out[3]) {

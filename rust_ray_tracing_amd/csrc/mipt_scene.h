@@ -54,6 +54,13 @@ struct MiptScene {
     float tile_cam[12] = {0};               // DevParams::cam of that launch, compared bit for bit
     bool tile_order_valid = false;          // d_tile_order is the order of d_tile_cost, both of the launch tile_key describes
     bool tile_order_used = false;           // that launch itself handed its tiles out by the order before it (read by the test hook)
+    // hot pixels, part of the same state (one key, one valid flag): rays per slot (local tile * 64 + pixel of the tile) of that launch,
+    // the tile costs being their sums; the hot_n slots of highest cost, which the next launch with the key and camera hands out first,
+    // their bitmap (2 words per tile) and the scratch of the selection kernels (mipt::hot_work_words)
+    uint32_t *d_pixel_cost = nullptr, *d_hot = nullptr, *d_hot_bits = nullptr, *d_hot_work = nullptr;
+    size_t pixel_cost_bytes = 0, hot_bytes = 0, hot_bits_bytes = 0, hot_work_bytes = 0;
+    uint32_t hot_n = 0;                     // entries of d_hot (0 = the launch was too large for 32-bit slots: no hot list)
+    uint32_t hot_used = 0;                  // entries that launch itself took from the list made before it (0 = it ran without)
     void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
     size_t qrays_bytes = 0, qout_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

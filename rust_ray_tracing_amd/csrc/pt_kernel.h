@@ -64,8 +64,9 @@ struct DevParams {
     uint32_t seed_mode, sample_begin, sum_only, packed;
     uint32_t accumulate, pad1;              // accumulate: hdr += this call's result (progressive rendering)
     uint32_t tile_rank, tile_world, tiles_x, tiles_y;
-    uint32_t n_local_tiles, pad0;
-    unsigned long long total_work;          // n_local_tiles * 64
+    uint32_t n_local_tiles;
+    uint32_t n_hot;                         // H: work indices [0, H) take slot hot[wi] (0 = no hot list); pt_kernel.hip "hot pixels"
+    unsigned long long total_work;          // n_local_tiles * 64 (+ n_hot)
     float aspect;                           // width as f32 / height as f32 (cpu.rs:34)
     float samples_f;
     float cull_scale;                       // 1 + cull_margin
@@ -78,7 +79,9 @@ struct DevParams {
     uint32_t *ovf;                          // traversal-stack overflow area [wave][entry][lane]
     DevStats *stats;
     const uint32_t *tile_order;             // local tile handed out at queue position i (NULL = plain order); pt_kernel.hip "tile order"
-    uint32_t *tile_cost;                    // rays traced per local tile, added up by this launch (NULL = not measured)
+    uint32_t *pixel_cost;                   // rays traced per slot (local tile * 64 + pixel of the tile), added up by this launch (NULL = not measured)
+    const uint32_t *hot;                    // n_hot != 0: the n_hot most expensive slots of the frame before, handed out first ...
+    const uint32_t *hot_bits;               // ... and one bit per slot, set for those: the pass over tile_order skips them
     uint32_t *touched;                      // COUNT build + MIPT_FLAG_TOUCHED: one bit per 128-B line of [geom | tri_attr] (else NULL)
     uint32_t touched_attr_base;             // first bit of the tri_attr stream in `touched`
 };
@@ -229,6 +232,16 @@ hipError_t launch_upsample(const DevUpsample &d, hipStream_t stream);
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream);
+// Hot pixels (pt_kernel.hip "hot pixels"), two launchers around launch_tile_order, stream-ordered.  pixel_cost[] holds rays per slot,
+// n_slots of them (a pixel has `samples` paths); `work` is hot_work_words(n_slots) words of scratch shared by the two.
+//   launch_pixel_reduce  tile_cost[t] = the sum of pixel_cost[64 t .. 64 t + 64) (NULL = not wanted), and the bucket counts in `work`
+//   launch_hot_select    hot[0 .. n_hot) = the n_hot slots of highest cost, by decreasing bucket (1 024 buckets of rays per path x 16),
+//                        slot index ascending within a bucket; hot_bits = one bit per slot, (n_slots + 63) / 64 * 2 words, all written.
+//                        n_hot <= n_slots.
+size_t hot_work_words(uint32_t n_slots);
+hipError_t launch_pixel_reduce(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t *tile_cost, uint32_t *work, hipStream_t stream);
+hipError_t launch_hot_select(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *work, uint32_t *hot,
+                             uint32_t *hot_bits, hipStream_t stream);
 // number of set bits in words [0, n_words) of `bitmap`, added to *out (a device counter)
 hipError_t launch_popcount(const uint32_t *bitmap, unsigned long long n_words, unsigned long long *out, hipStream_t stream);
 hipError_t launch_divide(float *hdr, unsigned long long n_floats, float divisor, hipStream_t stream);

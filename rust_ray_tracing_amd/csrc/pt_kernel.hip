@@ -295,8 +295,9 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
             }
             if (state == ST_S) {
                 if (path_done) {
-                    // tile order: this path's rays, added to its local tile's cost (slot = local tile * 64 + pixel of the tile)
-                    if (!BATCH && pr.tile_cost) atomicAdd(&pr.tile_cost[slot >> 6], bounces + ((best_tri == kNoTri) ? 1u : 0u));
+                    // tile order, hot pixels: this path's rays, added to its pixel's cost (slot = local tile * 64 + pixel of the tile);
+                    // the sums per tile are taken behind the launch (pixel_reduce_kernel)
+                    if (!BATCH && pr.pixel_cost) atomicAdd(&pr.pixel_cost[slot], bounces + ((best_tri == kNoTri) ? 1u : 0u));
                     const V3 res = (bounces == 0u) ? incoming : incoming / (float)bounces; // ray.rs:197-201
                     final_color = final_color + res;                                 // cpu.rs:52
                     sample += 1;
@@ -334,8 +335,13 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                             if (COUNT && g_t_first_x == 0) g_t_first_x = clock64();
                         } else {
                             // 8x8 pixel tiles, round-robin over ranks: global tile = local*world + rank
-                            uint32_t lt = (uint32_t)(wi >> 6);
-                            const uint32_t p = (uint32_t)wi & 63u;
+                            // hot pixels: the first pr.n_hot work indices are the most expensive pixels of the frame before, one by
+                            // one (slot hot[wi]), so that every long chain starts with the frame; the indices behind them run over
+                            // the tiles as ever and skip those pixels by their bit.  Every pixel is still traced exactly once.
+                            const bool is_hot = !BATCH && wi < (unsigned long long)pr.n_hot;
+                            const unsigned long long wj = (BATCH || is_hot) ? wi : wi - pr.n_hot;
+                            uint32_t lt = (uint32_t)(wj >> 6);
+                            uint32_t p = (uint32_t)wj & 63u;
                             if (BATCH) {                                      // work index -> view, tile within the view
                                 // lt / n_local_tiles by the host's reciprocal (DevBatch::tiles_recip): both operands are kernel
                                 // arguments, so no per-lane reciprocal is built and kept live through the loop
@@ -347,11 +353,19 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                             }
                             // tile order: queue position -> local tile by the previous frame's cost, most expensive first, so that
                             // the frame ends with its cheapest tiles and the waves run dry together (the host: mipt_api.cpp)
-                            const uint32_t lt_o = (!BATCH && pr.tile_order) ? pr.tile_order[lt] : (pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt);
+                            uint32_t lt_o;
+                            bool taken = false;                               // a hot pixel met again in its tile: skipped like a ragged edge
+                            if (is_hot) {
+                                const uint32_t s = pr.hot[(uint32_t)wi];
+                                lt_o = s >> 6; p = s & 63u;
+                            } else {
+                                lt_o = (!BATCH && pr.tile_order) ? pr.tile_order[lt] : (pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt);
+                                if (!BATCH && pr.n_hot != 0u) taken = ((pr.hot_bits[lt_o * 2u + (p >> 5)] >> (p & 31u)) & 1u) != 0u;
+                            }
                             const uint32_t gt = lt_o * pr.tile_world + pr.tile_rank;
                             const uint32_t px = (gt % pr.tiles_x) * 8u + (p & 7u);
                             const uint32_t py = (gt / pr.tiles_x) * 8u + (p >> 3);
-                            if (px < pr.width && py < pr.height) {            // ragged edge tiles: skip, stay ST_P
+                            if (px < pr.width && py < pr.height && !taken) {  // ragged edge tiles: skip, stay ST_P
                                 pix = py * pr.width + px;
                                 if (!BATCH) slot = lt_o * 64u + p;                    // the rank-packed output slot; its tile: slot >> 6
                                 rng = 987612486u * (pix + 87636354u);                 // cpu.rs:28-29
@@ -639,6 +653,108 @@ __global__ __launch_bounds__(kOrderThreads) void tile_order_kernel(const uint32_
 }
 hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order, hipStream_t stream) {
     hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(kOrderThreads), 0, stream, cost, n_tiles, 16.0f / (64.0f * (float)samples), order);
+    return hipGetLastError();
+}
+
+// ---- hot pixels: hot[] = the n_hot slots of highest pixel_cost[] of the frame just traced, hot_bits = their bitmap ----
+// The same stable counting sort (the same 1 024 buckets, here of one pixel's rays per path x 16, slot index ascending within a
+// bucket), cut off after n_hot places and spread over blocks, for a frame has 64 x as many slots as tiles.  Block b owns the slots
+// [b * kHotChunk, (b + 1) * kHotChunk).  pixel_reduce_kernel counts its block's slots per bucket into work[b][bucket] -- and, being
+// the pass that reads every pixel's cost anyway, writes the sums per tile the tile order sorts.  hot_scan_kernel (one block) turns
+// every column of counts into running sums over the blocks and writes the first place of every bucket behind them.
+// hot_select_kernel places its block's slots as tile_order_kernel does its tiles, wave w owning a contiguous quarter; a place below
+// n_hot is written to hot[] and sets the slot's bit.  The result is a function of the costs alone: no atomic cursor decides a place.
+constexpr uint32_t kHotThreads = 256, kHotWaves = kHotThreads / 64, kHotChunk = 8192, kHotWaveSlots = kHotChunk / kHotWaves;
+static_assert(kHotWaveSlots % 64u == 0u && kOrderBuckets % kHotThreads == 0u, "whole groups of 64 per wave, whole buckets per thread");
+__global__ __launch_bounds__(kHotThreads) void pixel_reduce_kernel(const uint32_t *__restrict__ cost, uint32_t n, float scale,
+                                                                   uint32_t *__restrict__ tile_cost, uint32_t *__restrict__ work) {
+    __shared__ uint32_t s_cnt[kOrderBuckets];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    for (uint32_t i = t; i < kOrderBuckets; i += kHotThreads) s_cnt[i] = 0u;
+    __syncthreads();
+    const unsigned long long lo64 = (unsigned long long)blockIdx.x * kHotChunk + (unsigned long long)w * kHotWaveSlots;
+    const uint32_t lo = lo64 < n ? (uint32_t)lo64 : n, hi = (lo64 + kHotWaveSlots < n) ? (uint32_t)(lo64 + kHotWaveSlots) : n;
+    for (uint32_t i0 = lo; i0 < hi; i0 += 64u) {                                         // wave-uniform; i0 is a multiple of 64
+        const uint32_t i = i0 + lane;
+        uint32_t c = 0u;
+        if (i < hi) { c = cost[i]; atomicAdd(&s_cnt[tile_bucket(c, scale)], 1u); }
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+        if (tile_cost && lane == 0u) tile_cost[i0 >> 6] = c;
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < kOrderBuckets; i += kHotThreads) work[(size_t)blockIdx.x * kOrderBuckets + i] = s_cnt[i];
+}
+// work[b][k] := the slots of bucket k in the blocks before b; work[n_blocks][k] := the slots of the buckets before k
+__global__ __launch_bounds__(kOrderBuckets) void hot_scan_kernel(uint32_t *__restrict__ work, uint32_t n_blocks) {
+    __shared__ uint32_t s_scan[kOrderBuckets];
+    const uint32_t t = threadIdx.x;
+    uint32_t tot = 0u;
+    for (uint32_t b = 0; b < n_blocks; b++) { const uint32_t c = work[(size_t)b * kOrderBuckets + t]; work[(size_t)b * kOrderBuckets + t] = tot; tot += c; }
+    s_scan[t] = tot;
+    __syncthreads();
+    for (uint32_t o = 1u; o < kOrderBuckets; o <<= 1) {
+        const uint32_t y = t >= o ? s_scan[t - o] : 0u;
+        __syncthreads();
+        s_scan[t] += y;
+        __syncthreads();
+    }
+    work[(size_t)n_blocks * kOrderBuckets + t] = s_scan[t] - tot;
+}
+__global__ __launch_bounds__(kHotThreads) void hot_select_kernel(const uint32_t *__restrict__ cost, uint32_t n, float scale, uint32_t n_hot,
+                                                                 const uint32_t *__restrict__ work, uint32_t *__restrict__ hot,
+                                                                 uint32_t *__restrict__ hot_bits) {
+    __shared__ uint32_t s_cnt[kHotWaves][kOrderBuckets];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    for (uint32_t i = t; i < kHotWaves * kOrderBuckets; i += kHotThreads) (&s_cnt[0][0])[i] = 0u;
+    __syncthreads();
+    const unsigned long long lo64 = (unsigned long long)blockIdx.x * kHotChunk + (unsigned long long)w * kHotWaveSlots;
+    const uint32_t lo = lo64 < n ? (uint32_t)lo64 : n, hi = (lo64 + kHotWaveSlots < n) ? (uint32_t)(lo64 + kHotWaveSlots) : n;
+    for (uint32_t i = lo + lane; i < hi; i += 64u) atomicAdd(&s_cnt[w][tile_bucket(cost[i], scale)], 1u);
+    __syncthreads();
+    // row w := per bucket, the place of wave w's next slot: the bucket's first place + the blocks before + the waves before
+    const uint32_t *bucket_base = work + (size_t)gridDim.x * kOrderBuckets, *block_base = work + (size_t)blockIdx.x * kOrderBuckets;
+    for (uint32_t k = t; k < kOrderBuckets; k += kHotThreads) {
+        uint32_t at = bucket_base[k] + block_base[k];
+        for (uint32_t ww = 0; ww < kHotWaves; ww++) { const uint32_t c = s_cnt[ww][k]; s_cnt[ww][k] = at; at += c; }
+    }
+    __syncthreads();
+    for (uint32_t i0 = lo; i0 < hi; i0 += 64u) {                                         // wave-uniform; i0 is a multiple of 64
+        const uint32_t i = i0 + lane;
+        const bool valid = i < hi;
+        const uint32_t b = valid ? tile_bucket(cost[i], scale) : 0u;
+        unsigned long long peers = __ballot(valid);                                     // -> the valid lanes of this lane's bucket
+        for (uint32_t k = 0; k < 10u; k++) {
+            const bool bit = ((b >> k) & 1u) != 0u;
+            const unsigned long long m = __ballot(valid && bit);
+            peers &= bit ? m : ~m;
+        }
+        bool is_hot = false;
+        if (valid) {
+            const uint32_t rank = lane_rank(peers);
+            const uint32_t at = s_cnt[w][b];                                            // the same word for all peers, read before the add below
+            if (rank == 0u) s_cnt[w][b] = at + (uint32_t)__popcll(peers);
+            is_hot = at + rank < n_hot;
+            if (is_hot) hot[at + rank] = i;
+        }
+        const unsigned long long m_hot = __ballot(is_hot);
+        if (lane < 2u) hot_bits[(i0 >> 5) + lane] = (uint32_t)(m_hot >> (32u * lane));  // every word of the bitmap, set or clear
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                           // the next group reads the counters this one moved
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+static uint32_t hot_blocks(uint32_t n_slots) { return (uint32_t)(((unsigned long long)n_slots + kHotChunk - 1u) / kHotChunk); }
+size_t hot_work_words(uint32_t n_slots) { return ((size_t)hot_blocks(n_slots) + 1u) * kOrderBuckets; }
+hipError_t launch_pixel_reduce(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t *tile_cost, uint32_t *work, hipStream_t stream) {
+    hipLaunchKernelGGL(pixel_reduce_kernel, dim3(hot_blocks(n_slots)), dim3(kHotThreads), 0, stream, pixel_cost, n_slots, 16.0f / (float)samples, tile_cost, work);
+    return hipGetLastError();
+}
+hipError_t launch_hot_select(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *work, uint32_t *hot,
+                             uint32_t *hot_bits, hipStream_t stream) {
+    const uint32_t n_blocks = hot_blocks(n_slots);
+    hipLaunchKernelGGL(hot_scan_kernel, dim3(1), dim3(kOrderBuckets), 0, stream, work, n_blocks);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hot_select_kernel, dim3(n_blocks), dim3(kHotThreads), 0, stream, pixel_cost, n_slots, 16.0f / (float)samples, n_hot, (const uint32_t *)work, hot, hot_bits);
     return hipGetLastError();
 }
 
