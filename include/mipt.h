@@ -700,6 +700,95 @@ MIPT_API int mipt_upsample(const MiptUpsampleOptions *opt, const MiptUpsampleBuf
 MIPT_API int mipt_upsample_device(const MiptUpsampleOptions *opt, const MiptUpsampleBuffers *device, void *d_workspace,
                                   uint64_t workspace_bytes, void *hip_stream);
 
+/* ---- adaptive sampling: per-pixel sample counts, and the map that makes them from the variance plane ----------------------------------
+ * The pipeline above measures per pixel how noisy the frame still is; these two operations spend the samples of the next frame where
+ * that measurement says they pay.  mipt_render_adaptive* is mipt_render_batch* with one u32 per pixel saying how many samples the pixel
+ * gets (csrc/pt_kernel.hip, pt_trace_adaptive_kernel); mipt_sample_map* makes such a plane from a variance plane under a budget on the
+ * frame's mean (csrc/sample_map.hip).
+ *
+ * mipt_render_adaptive.  Everything is as in mipt_render_batch / mipt_render_batch_device -- view-major planes, the same limits, the
+ * same flag rules, tile_world 0 or 1 -- with one more argument:
+ *   counts : one u32 per pixel, view-major like hdr (pixel p of view v at counts[v*W*H + p]), row 0 = top.
+ * Pixel p of view v is traced with n = min(counts[v*W*H + p], opt->samples) samples: opt->samples is the cap the caller promises, so no
+ * plane makes a launch longer than mipt_render_batch with the same options.
+ *   n > 0  : the pixel's three hdr values are exactly the bytes mipt_render writes for cameras[v] with opt and samples = n -- the mean
+ *            over n samples, divided by (float)n as cpu.rs:60 divides by samples as f32 -- in both seed modes, both traversal modes
+ *            and both shading modes, and with sample_begin.  With MIPT_FLAG_SUM the pixel holds the undivided sum; with SUM | ACCUM
+ *            (device entry) the sum is added to what is there.  rgba8, when given, is the tone-map epilogue over the mean; rgba8
+ *            together with MIPT_FLAG_SUM is MIPT_ERR_INVALID_ARG.
+ *   n == 0 : no ray is traced.  hdr is +0, +0, +0, or left untouched under MIPT_FLAG_ACCUM.
+ *   stats  : pixels counts the pixels with n > 0; under MIPT_FLAG_COUNT the counters are the sums over the traced paths, as in the
+ *            batch call.
+ * The pixels are handed out in the batch call's order, (view, tile, pixel).  MIPT_FLAG_PACKED and MIPT_FLAG_TOUCHED are refused.
+ * Errors: every argument is checked before any device work, with the messages of the batch entry, and: a null counts; for the device
+ * entry a counts or d_hdr_rgb that is not 4-byte aligned, a counts that is not device memory of d_hdr_rgb's device, and a counts that
+ * overlaps d_hdr_rgb or d_rgba8.  The tile-order and hot-pixel state of the scene handle is neither used nor touched. */
+MIPT_API int mipt_render_adaptive(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                  const uint32_t *counts, float *hdr_rgb, uint8_t *rgba8, MiptStats *stats);
+/* Same, with DEVICE buffers (d_counts: n_views*W*H u32; d_hdr_rgb: n_views*W*H*3 f32, required; d_rgba8: n_views*W*H*4 bytes, may be
+ * NULL) on `hip_stream` (may be NULL).  Blocks until the kernel has finished (stats are read back). */
+MIPT_API int mipt_render_adaptive_device(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,
+                                         const uint32_t *d_counts, float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats);
+
+/* mipt_sample_map: noise in, counts out.  The reference has nothing of this kind: the operation is defined HERE, and the kernels and
+ * tests/tools/sample_map_model.py obey it bit for bit.  Every operator is rounded once, nothing is fused, and every comparison is
+ * written so that a NaN takes the "zero" side.
+ *
+ * Buffers.  View-major planar, row 0 = top, N = n_views*width*height pixels:
+ *   variance  1 f32 / pixel, required: e.g. variance_out of mipt_denoise_variance, or variance of mipt_temporal
+ *   hdr       3 f32 / pixel, optional: the frame the variance belongs to; makes the weight relative
+ *   albedo    3 f32 / pixel, optional, only with hdr: hdr is demodulated first
+ *   counts    1 u32 / pixel, required: the result
+ *
+ * Per pixel, in f32:
+ *   v = variance > 0 ? variance : 0;  s = sqrtf(v), correctly rounded.
+ *   without hdr: w = s.
+ *   with hdr: c = hdr, or per channel hdr / a with a = albedo > 1/256 ? albedo : 1/256 (the temporal section's rule);
+ *             l = ((0.2126f*c.r) + (0.7152f*c.g)) + (0.0722f*c.b);  l = l > 0 ? l : 0;  w = s / (l + 0.00390625f)
+ *             -- the relative standard deviation, so that bright and dark regions compete fairly.
+ *   q = w * 4096.0f;  qi = q > 0 ? (q < 16777215.0f ? (uint32_t)q : 16777215u) : 0u.
+ * The frame: S = the sum of qi over all N pixels in uint64 -- an integer sum, exact in any order.  The host forms
+ * T = (uint64_t)floor((double)budget * (double)N) and E = T - (uint64_t)min_samples * N.
+ *   S == 0 : e = min((uint32_t)(E / N), max_samples - min_samples) for every pixel.
+ *   else   : in binary64, one rounded operation each: r = (double)E / (double)S, formed once on the device; x = (double)qi * r;
+ *            e = x < (double)(max_samples - min_samples) ? (uint32_t)x : max_samples - min_samples.
+ *   counts = min_samples + e.
+ * So min_samples <= counts <= max_samples and the sum of counts is at most T.  What the clamp at max_samples cuts off is NOT
+ * redistributed: budget is an upper bound on the frame's mean sample count, not a target that is met.
+ *
+ * Errors.  Everything is checked before any device work: MIPT_ERR_INVALID_ARG with a message in mipt_last_error() that names the
+ * field -- a null opt, buffers, variance or counts; albedo without hdr; zero width, height or n_views; n_views*W*H >=
+ * MIPT_BATCH_MAX_PIXELS; max_samples outside 1 ... 65535; min_samples > max_samples; a budget that is not finite or outside
+ * [min_samples, max_samples]; non-zero flags or reserved fields; any two buffers that overlap; for the device entry a workspace that is
+ * NULL, not 16-byte aligned or overlapped by a buffer, a pointer that is not 4-byte aligned, and a pointer that is not device memory
+ * of one common device (variance's). */
+typedef struct {
+    uint32_t width, height, n_views;
+    uint32_t flags;                   /* must be 0 */
+    uint32_t min_samples;             /* 0 <= min_samples <= max_samples */
+    uint32_t max_samples;             /* 1 ... 65535 */
+    float    budget;                  /* finite, min_samples <= budget <= max_samples: the upper bound on the mean of counts */
+    uint32_t reserved[9];             /* must be 0 */
+} MiptSampleMapOptions;               /* 64 B */
+typedef struct {
+    const float *variance;            /* 1 f32 / pixel, required */
+    const float *hdr;                 /* 3 f32 / pixel, optional */
+    const float *albedo;              /* 3 f32 / pixel, optional, only with hdr */
+    uint32_t    *counts;              /* 1 u32 / pixel, required */
+    void        *reserved[4];         /* must be NULL */
+} MiptSampleMapBuffers;               /* 64 B */
+
+/* Bytes of workspace mipt_sample_map_device needs for this size: S, r and the reduction's ticket, 32 B whatever the size.  0 = an
+ * invalid size. */
+MIPT_API uint64_t mipt_sample_map_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views);
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_sample_map(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *host, int device_id);
+/* DEVICE buffers of one device (e.g. torch tensors) on `hip_stream` (hipStream_t, NULL = the null stream).  Stream-ordered: it does
+ * not block and allocates nothing, like mipt_denoise_device.  d_workspace is the caller's: 16-byte aligned device memory of at least
+ * mipt_sample_map_workspace_bytes().  The call writes `counts` and the first mipt_sample_map_workspace_bytes() bytes of the
+ * workspace, and nothing else. */
+MIPT_API int mipt_sample_map_device(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *device, void *d_workspace, void *hip_stream);
+
 /* ---- previous positions: where every pixel's surface point was in the previous geometry ------------------------------------------------
  * The link between the geometry updates and the temporal accumulation above: per pixel the world position that the first hit's
  * surface point had before the last update, to be passed to mipt_temporal as `position` (csrc/first_hit.hip, the MOTION form of the

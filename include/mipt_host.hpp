@@ -159,6 +159,13 @@ struct UpsampleSettings {
     float sigma_normal = 0.5f, sigma_depth = 0.5f;
 };
 
+// Renderer::sample_map: the map's settings (MiptSampleMapOptions; the defaults of the Python mirror: max_samples 0 = options.samples,
+// a negative budget = min_samples)
+struct SampleMapSettings {
+    uint32_t min_samples = 1, max_samples = 0;
+    float budget = -1.0f;
+};
+
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
 // it.  The vectors are the caller's to edit between create() calls; the device copy follows set_transforms / update_device only.
 class Mesh {
@@ -536,6 +543,73 @@ class Renderer {                                           // src/renderer.rs:8-
         b.out = out.data();
         b.weight = weight ? weight->data() : nullptr;
         const int rc = mipt_upsample(&o, &b, options.device_id);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+
+    // A batch render with a count plane (mipt_render_adaptive, include/mipt.h "adaptive sampling"): `counts` holds one u32 per pixel of
+    // every view, view-major; pixel p of view v is traced with min(counts, options.samples) samples and holds what a render with that
+    // many samples gives, a pixel with 0 is not traced and holds 0.  `cameras` empty = the scene's camera.  `hdr` is resized and
+    // filled (3 f32 per pixel); `rgba8`, if given, receives the tone-mapped frame.  seed_mode and flags as render_features
+    // (MIPT_FLAG_COUNT, MIPT_FLAG_SUM).  Runs on the root replica of the scene's device residency.  Returns a MiptStatus; a count
+    // plane of the wrong size is MIPT_ERR_INVALID_ARG before the library is called.
+    int render_adaptive(const Scene &scene, const std::vector<MiptCamera> &cameras, const std::vector<uint32_t> &counts, std::vector<float> &hdr,
+                        std::vector<uint8_t> *rgba8 = nullptr, uint32_t seed_mode = MIPT_SEED_PIXEL_STREAM, uint32_t flags = 0,
+                        uint32_t sample_begin = 0, MiptStats *stats = nullptr) const {
+        if (options.backend != RendererBackend::MI355X) { log_error("this build only provides RendererBackend::MI355X"); return MIPT_ERR_INVALID_ARG; }
+        MiptOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.samples = (uint32_t)options.samples; o.max_ray_depth = (uint32_t)options.max_ray_depth;
+        o.seed_mode = seed_mode; o.flags = flags; o.sample_begin = sample_begin;
+        o.traversal = options.traversal; o.cull_margin = MIPT_CULL_MARGIN_SAFE;
+        const std::vector<MiptCamera> own{scene.camera.uniform};
+        const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
+        const uint64_t n = (uint64_t)o.width * o.height * cams.size();
+        const bool sized = n != 0 && n < MIPT_BATCH_MAX_PIXELS;            // an impossible size is left to the library to refuse
+        if (sized && counts.size() != n) {
+            log_error("Renderer::render_adaptive: counts holds " + std::to_string(counts.size()) + " values, expected " + std::to_string(n));
+            return MIPT_ERR_INVALID_ARG;
+        }
+        MiptMulti *m = scene.node_handle(1);
+        if (!m) return MIPT_ERR_HIP;
+        hdr.assign(sized ? (size_t)n * 3 : 3, 0.0f);
+        if (rgba8) rgba8->assign(sized ? (size_t)n * 4 : 4, 0);
+        const int rc = mipt_render_adaptive(mipt_multi_scene(m, 0), cams.data(), (uint32_t)cams.size(), &o, counts.empty() ? nullptr : counts.data(),
+                                            hdr.data(), rgba8 ? rgba8->data() : nullptr, stats);
+        if (rc != MIPT_OK) log_error(mipt_last_error());
+        return rc;
+    }
+
+    // The sample map (mipt_sample_map, include/mipt.h "adaptive sampling") over host images of this renderer's width and height:
+    // `variance` holds n_views planes of 1 f32 per pixel -- denoise_variance's variance_out, or TemporalState's -- and becomes
+    // `counts`, one u32 per pixel in [min_samples, max_samples] with a mean of at most `budget`, for render_adaptive.  `hdr` (3 f32
+    // per pixel, empty = absent) makes the weight relative to the frame's luminance; `albedo` (only with hdr) demodulates it first.
+    // `counts` is resized and filled.  Returns a MiptStatus; a size that does not fit is MIPT_ERR_INVALID_ARG before the library is
+    // called.
+    int sample_map(const std::vector<float> &variance, uint32_t n_views, const std::vector<float> &hdr, const std::vector<float> &albedo,
+                   std::vector<uint32_t> &counts, const SampleMapSettings &settings = SampleMapSettings()) const {
+        MiptSampleMapOptions o{};
+        o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
+        o.n_views = n_views;
+        o.min_samples = settings.min_samples;
+        o.max_samples = settings.max_samples ? settings.max_samples : (uint32_t)options.samples;
+        o.budget = settings.budget < 0.0f ? (float)settings.min_samples : settings.budget;
+        const uint64_t n = (uint64_t)o.width * o.height * n_views;
+        const bool sized = n != 0 && n < MIPT_BATCH_MAX_PIXELS;            // an impossible size is left to the library to refuse
+        auto fits = [&](const std::vector<float> &v, uint64_t k, const char *name, bool required) {
+            if ((v.empty() && !required) || v.size() == n * k) return true;
+            log_error(std::string("Renderer::sample_map: ") + name + " holds " + std::to_string(v.size()) + " values, expected " + std::to_string(n * k));
+            return false;
+        };
+        if (sized && !(fits(variance, 1, "variance", true) && fits(hdr, 3, "hdr", false) && fits(albedo, 3, "albedo", false))) return MIPT_ERR_INVALID_ARG;
+        static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
+        counts.assign(sized ? (size_t)n : 1, 0u);
+        MiptSampleMapBuffers b{};
+        b.variance = variance.empty() ? no_pixel : variance.data();
+        b.hdr = hdr.empty() ? nullptr : hdr.data();
+        b.albedo = albedo.empty() ? nullptr : albedo.data();
+        b.counts = counts.data();
+        const int rc = mipt_sample_map(&o, &b, options.device_id);
         if (rc != MIPT_OK) log_error(mipt_last_error());
         return rc;
     }

@@ -180,6 +180,18 @@ class MiptUpsampleBuffers(C.Structure):
 
 assert C.sizeof(MiptUpsampleOptions) == 64 and C.sizeof(MiptUpsampleBuffers) == 128
 
+# ---- adaptive sampling (include/mipt.h "adaptive sampling") ----
+class MiptSampleMapOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("flags", C.c_uint32),
+                ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("budget", C.c_float), ("reserved", C.c_uint32 * 9)]
+
+
+class MiptSampleMapBuffers(C.Structure):
+    _fields_ = [("variance", C.c_void_p), ("hdr", C.c_void_p), ("albedo", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_void_p * 4)]
+
+
+assert C.sizeof(MiptSampleMapOptions) == 64 and C.sizeof(MiptSampleMapBuffers) == 64
+
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
 
@@ -234,6 +246,7 @@ EXPORTS = [
     "mipt_upsample_workspace_bytes", "mipt_upsample", "mipt_upsample_device",
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
     "mipt_render_motion", "mipt_render_motion_device", "mipt_scene_track_motion",
+    "mipt_render_adaptive", "mipt_render_adaptive_device", "mipt_sample_map_workspace_bytes", "mipt_sample_map", "mipt_sample_map_device",
 ]
 
 _lib = None
@@ -397,6 +410,17 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_upsample.restype = C.c_int
     lib.mipt_upsample_device.argtypes = [uo, ub, vp, u64, vp]
     lib.mipt_upsample_device.restype = C.c_int
+    lib.mipt_render_adaptive.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), vp, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_adaptive.restype = C.c_int
+    lib.mipt_render_adaptive_device.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), vp, vp, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_render_adaptive_device.restype = C.c_int
+    so, sb = C.POINTER(MiptSampleMapOptions), C.POINTER(MiptSampleMapBuffers)
+    lib.mipt_sample_map_workspace_bytes.argtypes = [u32, u32, u32]
+    lib.mipt_sample_map_workspace_bytes.restype = u64
+    lib.mipt_sample_map.argtypes = [so, sb, C.c_int]
+    lib.mipt_sample_map.restype = C.c_int
+    lib.mipt_sample_map_device.argtypes = [so, sb, vp, vp]
+    lib.mipt_sample_map_device.restype = C.c_int
     return lib
 
 

@@ -702,6 +702,10 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the frame and the stats delivered
 }
 
+int mipt::check_batch_args(const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, const char *who) {
+    return validate_batch(scene, cameras, n_views, opt, who);
+}
+
 int mipt::render_device_impl(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt,
                              float *d_hdr_rgb, uint8_t *d_rgba8, void *hip_stream, MiptStats *stats, bool pack_single) {
     return render_launch(scene, camera, 1u, false, opt, d_hdr_rgb, d_rgba8, hip_stream, stats, pack_single);

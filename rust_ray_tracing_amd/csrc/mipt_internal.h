@@ -104,6 +104,9 @@ int replica_refresh(const MiptScene *src, MiptScene *dst);
 // One scene on device_ids[0] -- from the caller's nodes or, with from_triangles, built on that device -- and device-to-device
 // replicas on the others.
 int scene_create_replicas(const MiptSceneDesc *desc, const int *device_ids, int n_dev, MiptScene **outs, bool from_triangles);
+// the argument checks of mipt_render_batch* that need no device: scene, cameras, n_views, the options and the batch limits (used by
+// mipt_adaptive.cpp, whose entries take the same arguments under the same rules)
+int check_batch_args(const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt, const char *who);
 // mipt_render_device with `pack_single`: honour MIPT_FLAG_PACKED also at tile_world == 1.
 int render_device_impl(MiptScene *scene, const MiptCamera *camera, const MiptOptions *opt, float *d_hdr_rgb, uint8_t *d_rgba8,
                        void *hip_stream, MiptStats *stats, bool pack_single);

@@ -106,6 +106,11 @@ constexpr uint32_t kMaxPairs = 1u << 24;    // 24-bit pair index in the child-re
 hipError_t launch_trace(const DevScene &sc, const DevParams &pr, const DevBatch *batch, bool count, bool cull, int shading,
                         int grid_blocks, hipStream_t stream);
 int trace_blocks_per_cu(bool batch, bool count, bool cull, int shading);     // occupancy query
+// The batch launch with a count plane (pt_trace_adaptive_kernel; mipt_render_adaptive*): pixel p of view v runs
+// min(counts[v * batch.view_pixels + p], pr.samples) samples; 0 = not traced.  pr and batch as for a batch launch.
+hipError_t launch_trace_adaptive(const DevScene &sc, const DevParams &pr, const DevBatch &batch, const uint32_t *counts, bool count, bool cull,
+                                 int shading, int grid_blocks, hipStream_t stream);
+int trace_adaptive_blocks_per_cu(bool count, bool cull, int shading);        // occupancy query
 hipError_t launch_unpack_tiles(const float *packed_all, uint32_t width, uint32_t height,
                                uint32_t tile_world, float *hdr, hipStream_t stream);
 hipError_t launch_tonemap(const float *hdr, unsigned long long n_pixels, float divisor,
@@ -228,6 +233,25 @@ struct DevUpsample {
 // the pack pass over the low frame and the upsampling pass over the full frame, one launch each (stream-ordered; no allocation, no
 // synchronisation inside)
 hipError_t launch_upsample(const DevUpsample &d, hipStream_t stream);
+
+// ---- the sample map (sample_map.hip; mipt_sample_map*) ----
+struct SampleMapWork {                      // the workspace, zeroed on the stream before the reduction (32 B)
+    unsigned long long sum;                 // S: the sum of every pixel's weight qi
+    double ratio;                           // r = E / S, formed once by the last block of the reduction (0 when S == 0)
+    uint32_t done, pad[3];                  // blocks of the reduction that have added their part
+};
+struct DevSampleMap {
+    // planar inputs, view-major; hdr NULL = the weight is the standard deviation itself; albedo NULL = hdr is not demodulated
+    const float *variance, *hdr, *albedo;
+    uint32_t *counts;
+    SampleMapWork *work;
+    unsigned long long n_pixels;            // N = n_views * width * height
+    unsigned long long extra;               // E = T - min_samples * N: the samples to hand out above the floor (include/mipt.h)
+    uint32_t min_samples, span;             // span = max_samples - min_samples
+    uint32_t uniform_extra;                 // min(E / N, span): every pixel's share when S == 0
+};
+// the workspace's memset, the reduction and the assignment, one launch each (stream-ordered; no allocation, no synchronisation inside)
+hipError_t launch_sample_map(const DevSampleMap &d, hipStream_t stream);
 
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.

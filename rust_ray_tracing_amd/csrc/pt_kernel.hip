@@ -164,8 +164,14 @@ __device__ __forceinline__ bool shade_wgsl(const DevScene &sc, V3 &o, V3 &d, V3 
 // The trace loop of both kernels below.  BATCH (pt_trace_batch_kernel, mipt_render_batch*): the work queue runs over
 // (view, tile, pixel) -- pr.n_local_tiles tiles per view, pr.total_work = n_views * n_local_tiles * 64 -- and a lane's camera is
 // its view's record in bt.cams; the in-view tile / pixel math, hence pix, the seed and the screen position, is the single-view one.
-template <bool COUNT, bool CULL, int SHADING, bool BATCH>
-__device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch bt) {
+// ADAPT (with BATCH only; pt_trace_adaptive_kernel, mipt_render_adaptive*): pixel p of view v runs n = min(counts[v][p], pr.samples)
+// samples instead of pr.samples.  n is not kept in a register through the loop: it is read again at every path end -- one pixel's
+// word, in L2 since the fetch -- where the single-view kernel issues its pixel_cost atomic.  A pixel with n == 0 is dropped at the
+// fetch like a ragged-edge slot: the lane stays ST_P, nothing is traced, counted or written (the host has zeroed the frame before
+// the launch unless it accumulates).  Writing the zeros here instead costs 8 B of scratch per lane.
+template <bool COUNT, bool CULL, int SHADING, bool BATCH, bool ADAPT = false>
+__device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch bt, const uint32_t *__restrict__ counts = nullptr) {
+    static_assert(BATCH || !ADAPT, "the count plane is addressed by (view, pixel): batch launches only");
     __shared__ uint32_t s_stack[kWavesPerBlock][kStackLds + 1][64];   // row kStackLds: scratch target of the branch-free push
     __shared__ double s_logtab[32];                                    // __logf_data.tab (16 x {invc, logc}) for gl_log10f
     __shared__ __attribute__((aligned(16))) float s_draw[kWavesPerBlock][64 * 6];                   // scatter draws of a service pass: 3 x {u_theta, u_rho} per hit lane, compacted
@@ -301,10 +307,15 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                     const V3 res = (bounces == 0u) ? incoming : incoming / (float)bounces; // ray.rs:197-201
                     final_color = final_color + res;                                 // cpu.rs:52
                     sample += 1;
-                    if (sample < pr.samples) {
+                    uint32_t n_samples = pr.samples;
+                    if (ADAPT) {
+                        const uint32_t c = counts[view * bt.view_pixels + pix];
+                        n_samples = c < pr.samples ? c : pr.samples;
+                    }
+                    if (sample < n_samples) {
                         state = ST_G;
                     } else {
-                        if (!pr.sum_only) final_color = final_color / pr.samples_f;  // cpu.rs:60
+                        if (!pr.sum_only) final_color = final_color / (ADAPT ? (float)n_samples : pr.samples_f);  // cpu.rs:60
                         float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)(pr.packed ? slot : pix)) * 3;
                         if (pr.accumulate) {      // progressive rendering: add this call's samples to the running sum
                             final_color = mk(dst[0] + final_color.x, dst[1] + final_color.y, dst[2] + final_color.z);
@@ -365,7 +376,8 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                             const uint32_t gt = lt_o * pr.tile_world + pr.tile_rank;
                             const uint32_t px = (gt % pr.tiles_x) * 8u + (p & 7u);
                             const uint32_t py = (gt / pr.tiles_x) * 8u + (p >> 3);
-                            if (px < pr.width && py < pr.height && !taken) {  // ragged edge tiles: skip, stay ST_P
+                            if (px < pr.width && py < pr.height && !taken &&
+                                (!ADAPT || counts[view * bt.view_pixels + py * pr.width + px] != 0u)) {  // ragged edge tiles, pixels without a sample: skip, stay ST_P
                                 pix = py * pr.width + px;
                                 if (!BATCH) slot = lt_o * 64u + p;                    // the rank-packed output slot; its tile: slot >> 6
                                 rng = 987612486u * (pix + 87636354u);                 // cpu.rs:28-29
@@ -839,6 +851,22 @@ static int occ_t() {
     if (e != hipSuccess) n = 1;
     return n;
 }
+// A batch of views with a count plane: counts[v * width * height + p] samples, at most pr.samples, for pixel p of view v.
+template <bool COUNT, bool CULL, int SHADING>
+__global__ MIPT_TRACE_BOUNDS(COUNT, CULL, SHADING) void pt_trace_adaptive_kernel(DevScene sc, DevParams pr, DevBatch bt, const uint32_t *__restrict__ counts) {
+    trace_body<COUNT, CULL, SHADING, true, true>(sc, pr, bt, counts);
+}
+template <bool COUNT, bool CULL, int SHADING, bool>
+static hipError_t launch_a(const DevScene &sc, const DevParams &pr, const DevBatch &bt, const uint32_t *counts, int grid, hipStream_t stream) {
+    hipLaunchKernelGGL((pt_trace_adaptive_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr, bt, counts);
+    return hipGetLastError();
+}
+template <bool COUNT, bool CULL, int SHADING, bool>
+static int occ_a() {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pt_trace_adaptive_kernel<COUNT, CULL, SHADING>, kBlockThreads, 0) != hipSuccess) n = 1;
+    return n;
+}
 // instantiations: {single view, batch} x {CPU-backend shading, wgpu-shader shading} x {count, cull}
 #define MIPT_DISPATCH_B(FN, B, ...)                                                                                     \
     do {                                                                                                                \
@@ -860,6 +888,18 @@ hipError_t launch_trace(const DevScene &sc, const DevParams &pr, const DevBatch 
     MIPT_DISPATCH(launch_t, sc, pr, batch, grid, stream);
 }
 static int occ_dispatch(bool batch, bool count, bool cull, int shading) { MIPT_DISPATCH(occ_t); }
+// the adaptive instantiations: {CPU-backend shading, wgpu-shader shading} x {count, cull}
+hipError_t launch_trace_adaptive(const DevScene &sc, const DevParams &pr, const DevBatch &batch, const uint32_t *counts, bool count, bool cull,
+                                 int shading, int grid, hipStream_t stream) {
+    MIPT_DISPATCH_B(launch_a, true, sc, pr, batch, counts, grid, stream);
+}
+static int occ_dispatch_adaptive(bool count, bool cull, int shading) { MIPT_DISPATCH_B(occ_a, true); }
+int trace_adaptive_blocks_per_cu(bool count, bool cull, int shading) {
+    int n = occ_dispatch_adaptive(count, cull, shading);
+    if (n < 1) n = 1;
+    if (n > 8) n = 8;
+    return n;
+}
 int trace_blocks_per_cu(bool batch, bool count, bool cull, int shading) {
     int n = occ_dispatch(batch, count, cull, shading);
     if (n < 1) n = 1;

@@ -1,0 +1,105 @@
+// sample_map.hip -- the sample map of include/mipt.h ("adaptive sampling"): mipt_sample_map*.  The variance plane the temporal and
+// variance passes leave in HBM becomes a per-pixel sample count for mipt_render_adaptive*, under a budget on the frame's mean.
+//
+// Two launches.  sample_map_reduce_kernel forms every pixel's weight qi, an integer, and adds them up: per lane in 64 bits, per wave
+// by shuffles, per block through LDS, one atomic per block.  An integer sum is exact in any order, so the result is the model's S
+// whatever the grid.  The last block to finish (a ticket in the workspace) forms the ratio r = E / S once, in binary64, and leaves
+// it beside S.  sample_map_assign_kernel forms qi again -- the same function on the same operands, the same bits; 16 or 28 B read per
+// pixel are cheaper than a plane of weights written and read back -- and writes the count.
+//
+// Every f32 operator below is one rounded operation in the order the header gives (the translation unit is built with
+// -ffp-contract=off and correctly rounded f32 divide and sqrt); the binary64 divide is the compiler's IEEE expansion (v_div_scale,
+// v_rcp, the Newton steps in FMAs, v_div_fmas, v_div_fixup), which is correctly rounded.
+#include "pt_kernel.h"
+
+namespace mipt {
+
+namespace {
+
+constexpr uint32_t kMapThreads = 256, kMapWaves = kMapThreads / 64;
+constexpr uint32_t kMapMaxGrid = 2048;                       // blocks per launch; a block walks the pixels with this stride
+constexpr float kAlbedoFloor = 1.0f / 256.0f;
+
+__device__ __forceinline__ float floored(float albedo) { return albedo > kAlbedoFloor ? albedo : kAlbedoFloor; }   // a NaN gives the floor
+
+// qi of pixel i.  MODE 0: variance alone; 1: relative to hdr's luminance; 2: to the luminance of hdr / albedo.
+template <int MODE>
+__device__ __forceinline__ uint32_t pixel_weight(const DevSampleMap &d, unsigned long long i) {
+    const float var = d.variance[i];
+    const float v = var > 0.0f ? var : 0.0f;
+    const float s = sqrtf(v);
+    float w = s;
+    if (MODE != 0) {
+        const float *h = d.hdr + i * 3;
+        float r = h[0], g = h[1], b = h[2];
+        if (MODE == 2) {
+            const float *a = d.albedo + i * 3;
+            r = r / floored(a[0]); g = g / floored(a[1]); b = b / floored(a[2]);
+        }
+        float l = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b);
+        l = l > 0.0f ? l : 0.0f;
+        w = s / (l + 0.00390625f);
+    }
+    const float q = w * 4096.0f;
+    return q > 0.0f ? (q < 16777215.0f ? (uint32_t)q : 16777215u) : 0u;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kMapThreads) void sample_map_reduce_kernel(DevSampleMap d) {
+    __shared__ unsigned long long s_part[kMapWaves];
+    unsigned long long acc = 0ull;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kMapThreads + threadIdx.x; i < d.n_pixels;
+         i += (unsigned long long)gridDim.x * kMapThreads)
+        acc += (unsigned long long)pixel_weight<MODE>(d, i);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        unsigned long long block = 0ull;
+        for (uint32_t w = 0; w < kMapWaves; w++) block += s_part[w];
+        if (block) atomicAdd(&d.work->sum, block);
+        __threadfence();                                      // the sum before the ticket
+        if (atomicAdd(&d.work->done, 1u) == gridDim.x - 1u) {
+            const unsigned long long sum = atomicAdd(&d.work->sum, 0ull);
+            d.work->ratio = sum ? (double)d.extra / (double)sum : 0.0;
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kMapThreads) void sample_map_assign_kernel(DevSampleMap d) {
+    const unsigned long long sum = d.work->sum;
+    const double r = d.work->ratio;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kMapThreads + threadIdx.x; i < d.n_pixels;
+         i += (unsigned long long)gridDim.x * kMapThreads) {
+        uint32_t e = d.uniform_extra;                         // S == 0: nothing to tell the pixels apart
+        if (sum != 0ull) {
+            const double x = (double)pixel_weight<MODE>(d, i) * r;
+            e = x < (double)d.span ? (uint32_t)x : d.span;
+        }
+        d.counts[i] = d.min_samples + e;
+    }
+}
+
+template <int MODE>
+hipError_t launch_mode(const DevSampleMap &d, uint32_t grid, hipStream_t stream) {
+    hipLaunchKernelGGL(sample_map_reduce_kernel<MODE>, dim3(grid), dim3(kMapThreads), 0, stream, d);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sample_map_assign_kernel<MODE>, dim3(grid), dim3(kMapThreads), 0, stream, d);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_sample_map(const DevSampleMap &d, hipStream_t stream) {
+    const unsigned long long blocks = (d.n_pixels + kMapThreads - 1u) / kMapThreads;
+    const uint32_t grid = (uint32_t)(blocks < kMapMaxGrid ? blocks : kMapMaxGrid);
+    hipError_t e = hipMemsetAsync(d.work, 0, sizeof(SampleMapWork), stream);
+    if (e != hipSuccess) return e;
+    if (d.hdr && d.albedo) return launch_mode<2>(d, grid, stream);
+    if (d.hdr) return launch_mode<1>(d, grid, stream);
+    return launch_mode<0>(d, grid, stream);
+}
+
+} // namespace mipt

@@ -1167,6 +1167,140 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = stats
         return denoised, noisy, features, stats
 
+    # -- adaptive sampling (include/mipt.h "adaptive sampling") -------------------------------------
+    def render_adaptive(self, scene: Scene, counts, cameras=None, flags: int = 0, sample_begin: int = 0, want_rgba8: bool = False,
+                        stream=None, handle=None, out=None):
+        """A batch render with a count plane (mipt_render_adaptive / _device): pixel p of view v is traced with
+        min(counts[v, p], options.samples) samples -- ``options.samples`` is the cap -- and holds exactly what ``render_buffers``
+        gives for that camera with that many samples; a pixel with 0 is not traced and holds 0.  ``counts``: [V,H,W] or [H,W], a
+        uint32 numpy array (host entry) or a contiguous int32 tensor on ``options.device_id`` (the same bits; device entry, on
+        ``stream``: a torch stream, a raw hipStream_t or None = torch's current stream).  ``cameras``: a sequence of Camera (or CAMERA
+        records), None = the scene's camera.  ``flags``: FLAG_COUNT, FLAG_SUM and, with tensors and ``out``, FLAG_ACCUM.  ``out``: a
+        float32 tensor [V,H,W,3] to write (to add to, under FLAG_ACCUM) instead of a new one.  ``handle`` as in ``render_features``.
+        Returns (hdr [V,H,W,3] float32, rgba8 [V,H,W,4] uint8 | None, stats) as numpy arrays or tensors, after ``counts``' kind."""
+        o = self.options
+        if o.backend != RendererBackend.MI355X:
+            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        cams = [scene.camera] if cameras is None else list(cameras)
+        if not cams:
+            raise ValueError("render_adaptive: no cameras")
+        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        n = len(cams)
+        w, h = o.output_image_dimensions
+        torch_in = Scene._is_torch(counts)
+        if not torch_in:
+            counts = np.asarray(counts)
+        if tuple(counts.shape) not in ((n, h, w), (h, w)) or (counts.ndim == 2 and n != 1):
+            raise ValueError(f"counts: expected shape {(n, h, w)}; got {tuple(counts.shape)}")
+        hnd = handle if handle is not None else scene.upload(o.device_id)
+        opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, sample_begin=sample_begin,
+                           cull_margin=o.cull_margin, shading=o.shading)
+        st, lib = L.MiptStats(), L.load()
+        if torch_in:
+            import torch
+            dev = torch.device("cuda", o.device_id)
+            if counts.dtype != torch.int32 or not counts.is_cuda or counts.device != dev or not counts.is_contiguous():
+                raise ValueError(f"counts: expected a contiguous int32 tensor on {dev}")
+            if out is None:
+                out = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+            elif not (Scene._is_torch(out) and out.dtype == torch.float32 and out.is_cuda and out.device == dev and out.is_contiguous()
+                      and tuple(out.shape) == (n, h, w, 3)):
+                raise ValueError(f"out: expected a contiguous float32 tensor of shape {(n, h, w, 3)} on {dev}")
+            rgba = torch.empty((n, h, w, 4), dtype=torch.uint8, device=dev) if want_rgba8 else None
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            rc = lib.mipt_render_adaptive_device(hnd, L.ptr(table), n, C.byref(opt), counts.data_ptr(), out.data_ptr(),
+                                                 rgba.data_ptr() if want_rgba8 else None, stream, C.byref(st))
+            where, hdr = "mipt_render_adaptive_device", out
+        else:
+            if out is not None:
+                raise ValueError("out: a tensor to write needs counts as a tensor")
+            if counts.dtype != np.uint32:
+                raise ValueError(f"counts: expected uint32; got {counts.dtype}")
+            counts = np.ascontiguousarray(counts)
+            hdr = np.zeros((n, h, w, 3), dtype=np.float32)
+            rgba = np.zeros((n, h, w, 4), dtype=np.uint8) if want_rgba8 else None
+            rc = lib.mipt_render_adaptive(hnd, L.ptr(table), n, C.byref(opt), L.ptr(counts), L.ptr(hdr), L.ptr(rgba) if want_rgba8 else None,
+                                          C.byref(st))
+            where = "mipt_render_adaptive"
+        if rc != L.ERR_STACK:
+            L.check(rc, where)
+        self.last_stats = st.as_dict()
+        return hdr, rgba, self.last_stats
+
+    def sample_map(self, variance, hdr=None, albedo=None, min_samples: int = 1, max_samples=None, budget=None, stream=None):
+        """The sample map of include/mipt.h: a variance plane [V,H,W] or [H,W] float32 -- ``variance_out`` of ``denoise_variance``, or
+        ``variance`` of ``temporal`` -- becomes a count plane of the same shape for ``render_adaptive``, every count in
+        [min_samples, max_samples] and their mean at most ``budget``.  ``hdr`` [..,3] makes the weight the standard deviation
+        relative to the frame's luminance, ``albedo`` [..,3] (only with ``hdr``) demodulates the frame first.  ``max_samples``
+        defaults to ``options.samples``, ``budget`` to ``min_samples``.  numpy arrays go through mipt_sample_map on
+        ``options.device_id`` and give a uint32 array; contiguous torch tensors through mipt_sample_map_device on ``stream`` (a torch
+        stream, a raw hipStream_t or None = torch's current stream) without blocking and give an int32 tensor (the same bits)."""
+        torch_in = Scene._is_torch(variance)
+        if not torch_in:
+            variance = np.asarray(variance)
+        if variance.ndim not in (2, 3):
+            raise ValueError(f"variance: expected shape [V,H,W] or [H,W]; got {tuple(variance.shape)}")
+        if albedo is not None and hdr is None:
+            raise ValueError("albedo: given only with hdr")
+        lead = tuple(variance.shape)
+        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
+        p = {}
+        for name, a, k in (("variance", variance, 1), ("hdr", hdr, 3), ("albedo", albedo, 3)):
+            if a is None:
+                continue
+            want = lead + ((k,) if k > 1 else ())
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: variance, hdr and albedo must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                if a.dtype != torch.float32 or not a.is_cuda or a.device != variance.device:
+                    raise ValueError(f"{name}: expected a float32 tensor on variance's device {variance.device}")
+                if tuple(a.shape) != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
+                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                p[name] = a
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.float32:
+                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
+                if a.shape != want:
+                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
+                p[name] = np.ascontiguousarray(a)
+        opt = L.MiptSampleMapOptions()
+        opt.width, opt.height, opt.n_views = w, h, v
+        opt.min_samples = min_samples
+        opt.max_samples = self.options.samples if max_samples is None else max_samples
+        opt.budget = float(min_samples if budget is None else budget)
+        bufs, lib = L.MiptSampleMapBuffers(), L.load()
+        if torch_in:
+            import torch
+            dev = variance.device
+            counts = torch.empty(lead, dtype=torch.int32, device=dev)
+            for name, a in p.items():
+                setattr(bufs, name, a.data_ptr())
+            bufs.counts = counts.data_ptr()
+            workspace = torch.empty((max(int(lib.mipt_sample_map_workspace_bytes(w, h, v)), 16) // 16, 4), dtype=torch.float32, device=dev)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            # the launches are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+            for t in list(p.values()) + [counts, workspace]:
+                t.record_stream(s)
+            L.check(lib.mipt_sample_map_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_device")
+            return counts
+        counts = np.zeros(lead, dtype=np.uint32)
+        for name, a in p.items():
+            setattr(bufs, name, a.ctypes.data)
+        bufs.counts = counts.ctypes.data
+        L.check(lib.mipt_sample_map(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_sample_map")
+        return counts
+
     # -- temporal accumulation (include/mipt.h "temporal accumulation") ---------------------------
     _TEMPORAL_PLANES = (("position", 3, True), ("normal", 3, True), ("depth", 1, True), ("material", 1, True), ("albedo", 3, False))
 
@@ -1281,7 +1415,7 @@ class Renderer:  # renderer.rs:8-85
         L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
         return out, new, extras
 
-    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, upsample=None, **args):
+    def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, upsample=None, adaptive=None, **args):
         """A camera path without flicker, nothing crossing PCIe in between: a generator that per frame runs mipt_render_batch_device
         with this renderer's options, mipt_render_features_device (depth, normal, albedo, position, material; one sample),
         mipt_temporal_device and, with ``denoise``, mipt_denoise_device on one stream, the history in two tensors that swap roles.
@@ -1301,11 +1435,24 @@ class Renderer:  # renderer.rs:8-85
         histories and the filter all run at (W/k, H/k) exactly as above, then one full-resolution feature pass (depth, normal, albedo,
         material; one sample; the same cameras) and mipt_upsample_device run on the same stream (``args`` may hold
         upsample_sigma_normal and upsample_sigma_depth).  Every key above keeps its meaning at (W/k, H/k); the dict gains ``out_full``
-        [V,H,W,3], ``out`` upsampled to ``output_image_dimensions``, and ``features_full``, the dict of that feature pass."""
+        [V,H,W,3], ``out`` upsampled to ``output_image_dimensions``, and ``features_full``, the dict of that feature pass.
+        ``adaptive=dict(min_samples=..., max_samples=..., budget=...)`` (with ``denoise="variance"`` only) spends the samples where
+        the last frame was noisy: the trace is mipt_render_adaptive_device with ``max_samples`` as its cap in
+        mipt_render_batch_device's place.  Frame 0 gives every pixel max(1, floor(budget)) samples; frame f > 0 takes its counts from
+        mipt_sample_map_device over frame f - 1's ``variance_out`` (the filter's, which is asked for it), with frame f - 1's ``out``
+        as hdr and its albedo, on the same stream, and renders the samples from 1 + f * max_samples on, so that no pixel ever reuses a
+        sample number.  The map is used at the same pixel, it is NOT reprojected: a fast camera smears it by its motion, and the
+        pixels it misses still get ``min_samples``.  The dict gains ``counts`` (int32 [V,H,W]) and ``variance_out``; ``stats`` is the
+        adaptive launch's.  With ``upsample=k`` all of this happens at (W/k, H/k)."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
             raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        if adaptive is not None:
+            if denoise != "variance":
+                raise ValueError("render_sequence: adaptive needs denoise=\"variance\": the sample map is made from the filter's variance_out")
+            if not isinstance(adaptive, dict) or sorted(adaptive) != ["budget", "max_samples", "min_samples"]:
+                raise ValueError(f"render_sequence: adaptive must be None or dict(min_samples=, max_samples=, budget=); got {adaptive!r}")
         if o.seed_mode != L.SEED_PER_SAMPLE:
             raise ValueError("render_sequence: the renderer's seed_mode must be SEED_PER_SAMPLE; the pixel stream repeats the same noise every frame")
         if motion and (scene.mesh is None or scene._handle is None or not scene._tracks_motion):
@@ -1333,6 +1480,9 @@ class Renderer:  # renderer.rs:8-85
         one_full = Renderer(RendererOptions(**{**self.options.__dict__, "samples": 1})) if upsample is not None else None
         lib = L.load()
         handle, pair, history, n = None, None, None, None
+        capped, counts = None, None
+        if adaptive is not None:
+            capped = Renderer(RendererOptions(**{**o.__dict__, "samples": adaptive["max_samples"]}))
         for frame, cams in enumerate(cameras_per_frame):
             cams = [cams] if isinstance(cams, (Camera, np.void)) or (isinstance(cams, np.ndarray) and cams.ndim == 0) else list(cams)
             if not cams or (n is not None and len(cams) != n):
@@ -1343,13 +1493,20 @@ class Renderer:  # renderer.rs:8-85
                 handle = scene.upload(o.device_id)
                 words = int(lib.mipt_temporal_history_bytes(w, h, n)) // 4
                 pair = [torch.empty((max(words, 4),), dtype=torch.int32, device=dev) for _ in range(2)]
-            opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, sample_begin=1 + frame * o.samples,
-                               cull_margin=o.cull_margin, shading=o.shading)
-            noisy = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
-            st = L.MiptStats()
-            L.check(lib.mipt_render_batch_device(handle, L.ptr(table), n, C.byref(opt), noisy.data_ptr(), None, raw, C.byref(st)),
-                    "mipt_render_batch_device")
-            stats = st.as_dict()
+            if adaptive is not None:
+                if counts is None:
+                    counts = torch.full((n, h, w), max(1, int(adaptive["budget"])), dtype=torch.int32, device=dev)
+                    if raw != torch.cuda.current_stream(dev).cuda_stream:
+                        torch.cuda.current_stream(dev).synchronize()      # the fill above ran on torch's stream
+                noisy, _, stats = capped.render_adaptive(scene, counts, cams, sample_begin=1 + frame * adaptive["max_samples"], stream=raw, handle=handle)
+            else:
+                opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, sample_begin=1 + frame * o.samples,
+                                   cull_margin=o.cull_margin, shading=o.shading)
+                noisy = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
+                st = L.MiptStats()
+                L.check(lib.mipt_render_batch_device(handle, L.ptr(table), n, C.byref(opt), noisy.data_ptr(), None, raw, C.byref(st)),
+                        "mipt_render_batch_device")
+                stats = st.as_dict()
             features, _ = one.render_features(scene, cams, ("depth", "normal", "albedo", "position", "material"), device=True, stream=raw, handle=handle)
             t_features, prev_position = features, None
             if motion:
@@ -1357,7 +1514,11 @@ class Renderer:  # renderer.rs:8-85
                 t_features = {**features, "position": prev_position}
             acc, history, extras = self.temporal(noisy, t_features, table, history=history, want_length=True, want_variance=True, stream=raw,
                                                  history_out=pair[frame & 1], **t_args)
-            if guided:
+            variance_out = None
+            if adaptive is not None:
+                out, variance_out = self.denoise_variance(acc, extras["variance"], extras["length"], features["normal"], features["depth"],
+                                                          features["albedo"], want_variance=True, stream=raw, **d_args)
+            elif guided:
                 out = self.denoise_variance(acc, extras["variance"], extras["length"], features["normal"], features["depth"], features["albedo"],
                                             stream=raw, **d_args)
             else:
@@ -1367,6 +1528,9 @@ class Renderer:  # renderer.rs:8-85
                           variance=extras["variance"], stats=stats)
             if motion:
                 result["prev_position"] = prev_position
+            if adaptive is not None:
+                result["counts"], result["variance_out"] = counts, variance_out
+                counts = self.sample_map(variance_out, out, features["albedo"], stream=raw, **adaptive)      # the next frame's
             if upsample is not None:
                 result["features_full"], _ = one_full.render_features(scene, cams, self._FULL_FEATURES, device=True, stream=raw, handle=handle)
                 result["out_full"] = self.upsample(out, features, result["features_full"], upsample, stream=raw, **u_args)
