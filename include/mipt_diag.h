@@ -88,9 +88,13 @@ MIPT_DIAG_API int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_o
  *                               (0 = no valid state), [1] = H, the entries of the list made behind that launch, [2] = the entries
  *                               that launch itself took from the list made before it (0 = it ran without one); with non-NULL
  *                               buffers of cap_slots / cap_hot words, that launch's rays per slot and the list.
+ *   mipt_diag_scene_list        the whole list, of which the H hot pixels are the head: info_out[0] = its entries (0 = no valid state;
+ *                               the local slots where the list is complete, slots of cost 0 last), [1] = the entries that launch
+ *                               itself took from the list made before it; with a non-NULL buffer of `cap` words, the list.
  * Return as mipt_debug_eval. */
 MIPT_DIAG_API int mipt_debug_hot_select(const uint32_t *cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *hot_out, uint32_t *bits_out);
 MIPT_DIAG_API int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint32_t cap_slots, uint32_t *hot_out, uint32_t cap_hot, uint32_t info_out[3]);
+MIPT_DIAG_API int mipt_diag_scene_list(const void *scene, uint32_t *list_out, uint32_t cap, uint32_t info_out[2]);
 
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 

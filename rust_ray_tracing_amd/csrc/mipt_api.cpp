@@ -513,6 +513,15 @@ static int validate_batch(const MiptScene *scene, const MiptCamera *cameras, uin
 #ifndef MIPT_HOT_LANES_DEN
 #define MIPT_HOT_LANES_DEN 1
 #endif
+// The list behind the hot pixels (render_launch): the same stable sort goes on past its first H entries, to NUM / DEN of the local
+// slots (never fewer than H; 0 / 1 = the H hot pixels alone, as before).  1 / 1 is every local pixel in cost order: the launch then
+// has no walk over the tiles at all.  tools/experiments/full_list_result.txt has the sweep.
+#ifndef MIPT_LIST_NUM
+#define MIPT_LIST_NUM 1
+#endif
+#ifndef MIPT_LIST_DEN
+#define MIPT_LIST_DEN 1
+#endif
 // `pack_single`: honour MIPT_FLAG_PACKED also at tile_world == 1 (mipt_render_multi with one device keeps the same
 // gather + unpack path as with eight); through the public entry PACKED at world 1 means full-frame, as documented.
 // `batch` (mipt_render_batch*, validated by validate_batch): `cameras` holds n_views cameras and the frame is n_views views of
@@ -608,20 +617,29 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     // H is NOT a function of the key: the grid depends on the traversal mode (5 blocks per CU culled, 4 un-culled), which the key
     // leaves out.  So a launch takes the list with the H it was made with (hot_n), whatever its own grid, the list's buffer is sized
     // by the key alone (the cap), and a buffer that has to grow takes the state with it.
+    // The list behind them.  The sort that finds the H hot pixels goes on to every local slot (MIPT_LIST_NUM / DEN above), and the
+    // next launch takes all its work indices from that list, in cost order: longest first over ALL pixels, so the frame ends with
+    // its one-ray pixels and no walk over the tiles is left (total_work is the list's length).  Config M, the same view again,
+    // kernel ms median 69.7 / 68.4 / 68.0 / 65.2 with the H hot pixels alone, 1/2, 3/4 and all of the slots listed, the parent
+    // 70.2 (tools/experiments/full_list_result.txt): the locality of neighbouring pixels in flight together, which the full order
+    // gives up, is worth less than the tail.  hot_n / hot_used and the tile order are kept and reported as before; list_n /
+    // list_used say what really ran.
     const bool order_on = !count && !batch && opt->shading == MIPT_SHADING_CPU && !(opt->flags & MIPT_FLAG_ACCUM) && pr.n_local_tiles != 0u &&
                           pr.n_local_tiles < (1u << 26);                  // a slot (local tile * 64 + pixel) is 32 bits
-    pr.tile_order = nullptr; pr.pixel_cost = nullptr; pr.hot = nullptr; pr.hot_bits = nullptr; pr.n_hot = 0u;
+    pr.tile_order = nullptr; pr.pixel_cost = nullptr; pr.hot = nullptr; pr.hot_bits = nullptr; pr.n_list = 0u;
     const uint32_t n_slots = order_on ? pr.n_local_tiles * 64u : 0u;
-    uint32_t hot_next = 0u;                                               // H of the list made behind this launch
+    uint32_t hot_next = 0u, list_next = 0u;                               // H and the length of the list made behind this launch
     if (order_on) {
         const unsigned long long lanes = (unsigned long long)grid * mipt::kBlockThreads * MIPT_HOT_LANES_NUM / MIPT_HOT_LANES_DEN;
         hot_next = (uint32_t)(lanes < n_slots / 4u ? lanes : n_slots / 4u);
+        const uint32_t share = (uint32_t)((unsigned long long)n_slots * MIPT_LIST_NUM / MIPT_LIST_DEN);
+        list_next = hot_next == 0u ? 0u : (share > hot_next ? share : hot_next);
     }
     if (order_on) {
         const uint32_t key[7] = {opt->width, opt->height, world, opt->tile_rank, pr.n_local_tiles, pr.seed_mode, opt->samples};
         const size_t bytes = (size_t)pr.n_local_tiles * sizeof(uint32_t);
         // every buffer of the state is sized by the key alone; one that is too small is replaced without its contents
-        const size_t hot_bytes = (size_t)(n_slots / 4u) * sizeof(uint32_t), work_bytes = mipt::hot_work_words(n_slots) * sizeof(uint32_t);
+        const size_t hot_bytes = (size_t)n_slots * sizeof(uint32_t), work_bytes = mipt::hot_work_words(n_slots) * sizeof(uint32_t);
         if (scene->tile_cost_bytes < bytes || scene->tile_order_bytes < bytes || scene->pixel_cost_bytes < bytes * 64 || scene->hot_bytes < hot_bytes ||
             scene->hot_bits_bytes < bytes * 2 || scene->hot_work_bytes < work_bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
             memcmp(pr.cam, scene->tile_cam, sizeof pr.cam) != 0)
@@ -638,11 +656,12 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         pr.pixel_cost = scene->d_pixel_cost;
         pr.tile_order = scene->tile_order_valid ? scene->d_tile_order : nullptr;
         scene->tile_order_used = scene->tile_order_valid;
-        scene->hot_used = 0u;
+        scene->hot_used = 0u; scene->list_used = 0u;
         if (scene->tile_order_valid && scene->hot_n != 0u) {
-            pr.hot = scene->d_hot; pr.hot_bits = scene->d_hot_bits; pr.n_hot = scene->hot_n;
-            pr.total_work += scene->hot_n;
-            scene->hot_used = scene->hot_n;
+            pr.hot = scene->d_hot; pr.hot_bits = scene->d_hot_bits; pr.n_list = scene->list_n;
+            // a list of every slot leaves the walk over the tiles nothing: the work is the list (slots that are no pixel end it)
+            if (scene->list_n == n_slots) pr.total_work = n_slots; else pr.total_work += scene->list_n;
+            scene->hot_used = scene->hot_n; scene->list_used = scene->list_n;
         }
         scene->tile_order_valid = false;                          // until the sort behind this launch is queued
     }
@@ -674,9 +693,9 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
             if (order_on) {                                       // behind ev1: kernel_ms stays the trace alone
                 MIPT_HIP(mipt::launch_pixel_reduce(scene->d_pixel_cost, n_slots, opt->samples, scene->d_tile_cost, scene->d_hot_work, stream));
                 MIPT_HIP(mipt::launch_tile_order(scene->d_tile_cost, pr.n_local_tiles, opt->samples, scene->d_tile_order, stream));
-                if (hot_next != 0u)
-                    MIPT_HIP(mipt::launch_hot_select(scene->d_pixel_cost, n_slots, opt->samples, hot_next, scene->d_hot_work, scene->d_hot, scene->d_hot_bits, stream));
-                scene->hot_n = hot_next;
+                if (list_next != 0u)
+                    MIPT_HIP(mipt::launch_hot_select(scene->d_pixel_cost, n_slots, opt->samples, list_next, scene->d_hot_work, scene->d_hot, scene->d_hot_bits, stream));
+                scene->hot_n = hot_next; scene->list_n = list_next;
                 scene->tile_order_valid = true;
             }
             if (touched) {

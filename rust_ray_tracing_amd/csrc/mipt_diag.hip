@@ -302,6 +302,19 @@ int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint
     return 0;
 }
 
+int mipt_diag_scene_list(const void *scene, uint32_t *list_out, uint32_t cap, uint32_t info_out[2]) {
+    const MiptScene *s = (const MiptScene *)scene;
+    if (!s || !info_out) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_list: bad argument"); return -1; }
+    const uint32_t n = s->tile_order_valid ? s->list_n : 0u;
+    info_out[0] = n; info_out[1] = s->tile_order_valid ? s->list_used : 0u;
+    if (n == 0u || !list_out) return 0;
+    if (cap < n) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_list: cap %u < %u entries", cap, n); return -1; }
+    hipError_t e;
+    if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
+    if ((e = hipMemcpy(list_out, s->d_hot, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
 // payload, not allocation: the pool is n_texels words, a table one record per material (both allocations are padded when tiny).
 // tests/cpp/scene_hooks.hip copies the three to the host (mipt_diag_scene_read, which = 2 / 3 / 4).
 int mipt_diag_scene_tables(const void *scene, uint64_t out[3]) {

@@ -61,6 +61,10 @@ struct MiptScene {
     size_t pixel_cost_bytes = 0, hot_bytes = 0, hot_bits_bytes = 0, hot_work_bytes = 0;
     uint32_t hot_n = 0;                     // entries of d_hot (0 = the launch was too large for 32-bit slots: no hot list)
     uint32_t hot_used = 0;                  // entries that launch itself took from the list made before it (0 = it ran without)
+    // the list goes on behind its first hot_n entries, in the same cost order: list_n >= hot_n entries of d_hot, all local slots where
+    // the compiled-in ratio says so (mipt_api.cpp MIPT_LIST_NUM / DEN); a launch hands out all of them before it walks the tiles
+    uint32_t list_n = 0;                    // entries of d_hot in cost order (0 exactly when hot_n is 0)
+    uint32_t list_used = 0;                 // entries that launch itself took, hot_used of them as "the hot pixels"
     void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
     size_t qrays_bytes = 0, qout_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

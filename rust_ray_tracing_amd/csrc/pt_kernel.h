@@ -65,8 +65,8 @@ struct DevParams {
     uint32_t accumulate, pad1;              // accumulate: hdr += this call's result (progressive rendering)
     uint32_t tile_rank, tile_world, tiles_x, tiles_y;
     uint32_t n_local_tiles;
-    uint32_t n_hot;                         // H: work indices [0, H) take slot hot[wi] (0 = no hot list); pt_kernel.hip "hot pixels"
-    unsigned long long total_work;          // n_local_tiles * 64 (+ n_hot)
+    uint32_t n_list;                        // work indices [0, n_list) take slot hot[wi] (0 = no list); pt_kernel.hip "hot pixels"
+    unsigned long long total_work;          // n_local_tiles * 64 + n_list, or n_list alone when the list holds every slot
     float aspect;                           // width as f32 / height as f32 (cpu.rs:34)
     float samples_f;
     float cull_scale;                       // 1 + cull_margin
@@ -80,7 +80,7 @@ struct DevParams {
     DevStats *stats;
     const uint32_t *tile_order;             // local tile handed out at queue position i (NULL = plain order); pt_kernel.hip "tile order"
     uint32_t *pixel_cost;                   // rays traced per slot (local tile * 64 + pixel of the tile), added up by this launch (NULL = not measured)
-    const uint32_t *hot;                    // n_hot != 0: the n_hot most expensive slots of the frame before, handed out first ...
+    const uint32_t *hot;                    // n_list != 0: the n_list most expensive slots of the frame before, in cost order, handed out first ...
     const uint32_t *hot_bits;               // ... and one bit per slot, set for those: the pass over tile_order skips them
     uint32_t *touched;                      // COUNT build + MIPT_FLAG_TOUCHED: one bit per 128-B line of [geom | tri_attr] (else NULL)
     uint32_t touched_attr_base;             // first bit of the tri_attr stream in `touched`
@@ -261,7 +261,7 @@ hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t sa
 //   launch_pixel_reduce  tile_cost[t] = the sum of pixel_cost[64 t .. 64 t + 64) (NULL = not wanted), and the bucket counts in `work`
 //   launch_hot_select    hot[0 .. n_hot) = the n_hot slots of highest cost, by decreasing bucket (1 024 buckets of rays per path x 16),
 //                        slot index ascending within a bucket; hot_bits = one bit per slot, (n_slots + 63) / 64 * 2 words, all written.
-//                        n_hot <= n_slots.
+//                        n_hot <= n_slots; n_hot == n_slots is the complete sort (slots of cost 0, which are no pixels, come last).
 size_t hot_work_words(uint32_t n_slots);
 hipError_t launch_pixel_reduce(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t *tile_cost, uint32_t *work, hipStream_t stream);
 hipError_t launch_hot_select(const uint32_t *pixel_cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *work, uint32_t *hot,

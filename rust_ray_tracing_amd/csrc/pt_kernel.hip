@@ -346,11 +346,12 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                             if (COUNT && g_t_first_x == 0) g_t_first_x = clock64();
                         } else {
                             // 8x8 pixel tiles, round-robin over ranks: global tile = local*world + rank
-                            // hot pixels: the first pr.n_hot work indices are the most expensive pixels of the frame before, one by
-                            // one (slot hot[wi]), so that every long chain starts with the frame; the indices behind them run over
-                            // the tiles as ever and skip those pixels by their bit.  Every pixel is still traced exactly once.
-                            const bool is_hot = !BATCH && wi < (unsigned long long)pr.n_hot;
-                            const unsigned long long wj = (BATCH || is_hot) ? wi : wi - pr.n_hot;
+                            // hot pixels: the first pr.n_list work indices are the most expensive pixels of the frame before, one by
+                            // one in cost order (slot hot[wi]), so that every long chain starts with the frame; the indices behind
+                            // them run over the tiles as ever and skip those pixels by their bit -- no index is left behind a list
+                            // that holds every slot (total_work == n_list).  Every pixel is still traced exactly once.
+                            const bool is_hot = !BATCH && wi < (unsigned long long)pr.n_list;
+                            const unsigned long long wj = (BATCH || is_hot) ? wi : wi - pr.n_list;
                             uint32_t lt = (uint32_t)(wj >> 6);
                             uint32_t p = (uint32_t)wj & 63u;
                             if (BATCH) {                                      // work index -> view, tile within the view
@@ -371,7 +372,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                                 lt_o = s >> 6; p = s & 63u;
                             } else {
                                 lt_o = (!BATCH && pr.tile_order) ? pr.tile_order[lt] : (pr.reverse_tiles ? (pr.n_local_tiles - 1u - lt) : lt);
-                                if (!BATCH && pr.n_hot != 0u) taken = ((pr.hot_bits[lt_o * 2u + (p >> 5)] >> (p & 31u)) & 1u) != 0u;
+                                if (!BATCH && pr.n_list != 0u) taken = ((pr.hot_bits[lt_o * 2u + (p >> 5)] >> (p & 31u)) & 1u) != 0u;
                             }
                             const uint32_t gt = lt_o * pr.tile_world + pr.tile_rank;
                             const uint32_t px = (gt % pr.tiles_x) * 8u + (p & 7u);
@@ -676,6 +677,8 @@ hipError_t launch_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t sa
 // every column of counts into running sums over the blocks and writes the first place of every bucket behind them.
 // hot_select_kernel places its block's slots as tile_order_kernel does its tiles, wave w owning a contiguous quarter; a place below
 // n_hot is written to hot[] and sets the slot's bit.  The result is a function of the costs alone: no atomic cursor decides a place.
+// n_hot == n is the complete sort: the product asks for it (mipt_api.cpp MIPT_LIST_NUM / DEN), the H hot pixels being its head, and
+// the slots of cost 0 -- no pixels of the image -- fall into the last bucket and so end the list.
 constexpr uint32_t kHotThreads = 256, kHotWaves = kHotThreads / 64, kHotChunk = 8192, kHotWaveSlots = kHotChunk / kHotWaves;
 static_assert(kHotWaveSlots % 64u == 0u && kOrderBuckets % kHotThreads == 0u, "whole groups of 64 per wave, whole buckets per thread");
 __global__ __launch_bounds__(kHotThreads) void pixel_reduce_kernel(const uint32_t *__restrict__ cost, uint32_t n, float scale,

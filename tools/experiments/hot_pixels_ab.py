@@ -9,8 +9,10 @@ per frame, and a re-render with per-sample seeds.  Last, the per-pixel costs, th
 of --sim-lib through libmipt_diag.so (so the tree's own libraries must be built from the same source as that library) and a list
 scheduling of those costs over --lanes resident lanes -- a lane takes the next pixel of the queue when it is free and is busy for the
 pixel's rays -- gives, for the plain order, the tile order and the hot list, the makespan against the ideal, the idle share and when
-the 1 000 most expensive pixels start.  Variants with another H:
+the 1 000 most expensive pixels start; the same for the list behind the hot pixels cut at 1/2, 3/4 and all of the local slots (read
+through mipt_diag_scene_list, so --sim-lib must be a build whose list is complete).  Variants with another H or another list length:
     make -C rust_ray_tracing_amd/csrc variant NAME=hot_q EXTRA="-DMIPT_HOT_LANES_NUM=1 -DMIPT_HOT_LANES_DEN=4"      (0 / 1 = no hot list)
+    make -C rust_ray_tracing_amd/csrc variant NAME=list_half EXTRA="-DMIPT_LIST_NUM=1 -DMIPT_LIST_DEN=2"          (0 / 1 = the hot list alone)
 """
 import argparse, ctypes as C, os, sys, time, zlib, json, heapq
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -142,6 +144,16 @@ if args.sim_lib:
     simulate(plain, "plain order")
     simulate(ordered, "tile order")
     simulate(with_hot, "hot list + tile order")
+    li = (C.c_uint32 * 2)()
+    assert diag.mipt_diag_scene_list(hnd, None, 0, C.byref(li)) == 0
+    full = np.zeros(max(int(li[0]), 1), dtype=np.uint32)
+    assert diag.mipt_diag_scene_list(hnd, full.ctypes.data, int(li[0]), C.byref(li)) == 0
+    print(f"list: {li[0]} entries, the last launch took {li[1]}")
+    if int(li[0]) == n:
+        for num, den in ((1, 2), (3, 4), (1, 1)):
+            m = max(nh, n * num // den)
+            inlist = np.zeros(n, dtype=bool); inlist[full[:m]] = True
+            simulate(np.concatenate([full[:m].astype(np.int64), ordered[~inlist[ordered]]]), f"list of {num}/{den} of the slots + tile order")
 for lib, hnd in libs.values():
     lib.mipt_scene_destroy(hnd)
 print(f"done {time.time() - t0:.1f} s", flush=True)
