@@ -180,12 +180,50 @@ def test_sigmas_reach_the_kernel(rrt, orc):
 
 
 def test_many_tiny_views(rrt, orc):
-    """more views than one grid dimension could index the naive way is out of a test's reach; 700 views of 3x2 still walk the
-    (view, tile) decode far past one block"""
+    """700 views of 3x2 walk the (view, tile) decode far past one block (more tiles than a launch has workgroups:
+    test_more_tiles_than_the_grid_holds)"""
     planes = _fields((3, 2), 700, seed=4)
     want = _model(orc, planes, GUIDES, 2)
     assert D.same_bits(_device(rrt, planes, GUIDES, 2), want)
     assert D.same_bits(want[5], _model(orc, {k: a[5:6] for k, a in planes.items()}, GUIDES, 2)[0])     # views never see each other
+
+
+CAP = 1 << 20                                                   # kMaxGrid: workgroups per launch, one 64x4 tile per trip
+
+
+def _past_cap_subset(views):
+    """views 0-7, the last 8, both sides of the first tile of the second trip, and 2000 seeded others"""
+    rng = np.random.default_rng(views)
+    return np.unique(np.concatenate([np.arange(8), np.arange(views - 8, views), np.arange(CAP - 8, CAP + 8), rng.choice(views, 2000, replace=False)]))
+
+
+def test_more_tiles_than_the_grid_holds(rrt, orc):
+    """2^20 + 700 views of 2x1 pixels are as many tiles: 700 workgroups of the pack and of both passes take a second trip, and the
+    (view, tile) decode runs past 2^20.  Every pixel has one neighbour, so a tap beside the centre is weighed.  The output starts
+    as poison.  Views never see each other (test_many_tiny_views), so the model on a subset of the views, and every view against the
+    same call made in chunks of 2^19 views -- below the cap, the path the tests above hold to the model -- cover every word."""
+    views = CAP + 700
+    planes = _fields((2, 1), views, seed=7)
+    got = _device(rrt, planes, GUIDES, 2)
+    assert not (got.view(np.uint32) == POISON_I).any()                      # every pixel was written
+    idx = _past_cap_subset(views)
+    want = _model(orc, {k: a[idx] for k, a in planes.items()}, GUIDES, 2)
+    assert not D.same_bits(want, planes["hdr"][idx])
+    assert D.same_bits(got[idx], want), int((got[idx].view(np.uint32) != want.view(np.uint32)).sum())
+    for lo in range(0, views, CAP // 2):
+        part = _device(rrt, {k: a[lo: lo + CAP // 2] for k, a in planes.items()}, GUIDES, 2)
+        assert np.array_equal(got[lo: lo + CAP // 2].view(np.uint32), part.view(np.uint32)), lo
+
+
+def test_more_tiles_than_the_grid_holds_in_one_tall_view(rrt, orc):
+    """one view of 1 x (4 * 2^20 + 8) pixels: 2^20 + 2 tiles stacked, so the passes' vertical taps at steps 1 and 2 cross from a
+    tile of the first trip into one of the second and back.  The model runs on the whole frame."""
+    h = 4 * CAP + 8
+    planes = _fields((1, h), 1, seed=8)
+    want = _model(orc, planes, GUIDES, 2)
+    got = _device(rrt, planes, GUIDES, 2)
+    assert not D.same_bits(want, planes["hdr"])
+    assert D.same_bits(got, want), int((got.view(np.uint32) != want.view(np.uint32)).sum())
 
 
 # ---- real frames: the buffers the render and the feature pass leave in HBM ------------------------------------------------------------

@@ -1,5 +1,6 @@
 """-m gpu: mipt_sample_map / mipt_sample_map_device equal the numpy model of tests/tools/sample_map_model.py on every u32 count, stay
-within the budget, and the device entry writes nothing but `counts` and its workspace."""
+within the budget, and the device entry writes nothing but `counts` and its workspace -- also on planes of more pixels than one
+launch has threads (2048 x 256), where every further pixel is a thread's second trip, and with a sum of weights past 2^32."""
 import ctypes as C
 import os
 import sys
@@ -94,6 +95,83 @@ def test_kernels_equal_the_model(rrt, shape, buffers):
         assert np.array_equal(got_d, want) and clean
         assert int(want.sum(dtype=np.uint64)) <= SM.total(budget, want.size)
         assert int(got_d.sum(dtype=np.uint64)) <= SM.total(budget, want.size)
+
+
+# ---- past the grid cap: 2048 blocks x 256 threads hold 524 288 pixels, every pixel beyond is a thread's second or later trip ---------
+CAP = 2048 * 256
+PAST_CAP = [(1, 513, 1023),      # 524 799 pixels: 511 threads take a second trip, the others do not
+            (3, 601, 599)]       # 1 080 003 pixels: two whole trips and a ragged third
+TRIPLES = ((1, 8, 2.0), (0, 16, 1.5), (1, 65535, 700.5))
+
+
+@pytest.mark.parametrize("buffers", ["variance", "hdr", "albedo"])
+@pytest.mark.parametrize("shape", PAST_CAP, ids=["x".join(map(str, s)) for s in PAST_CAP])
+def test_kernels_equal_the_model_past_the_grid_cap(rrt, shape, buffers):
+    """both kernels' stride loops: the sum takes in the pixels of the later trips, and every one of them gets its count"""
+    assert CAP < int(np.prod(shape)) and (shape != PAST_CAP[0] or int(np.prod(shape)) < CAP + 2 * 256)
+    variance, hdr, albedo = _planes(shape, sum(shape))
+    hdr = hdr if buffers != "variance" else None
+    albedo = albedo if buffers == "albedo" else None
+    # special values and noisy pixels behind the first trip too (_planes scatters 40 over the whole plane, which may miss it)
+    tail = variance.reshape(-1)[CAP:]
+    tail[:8] = [np.nan, np.inf, -1.0, 1e-42, 0.0, 3e38, 0.25, 1.5]
+    tail[-3:] = [0.75, np.nan, 2.0]
+    for lo, hi, budget in TRIPLES:
+        want = SM.sample_map(variance, hdr, albedo, lo, hi, budget)
+        assert np.unique(want.reshape(-1)[CAP:]).size > 1                      # the later trips hold more than one answer
+        got_h = _host(rrt, variance, hdr, albedo, lo, hi, budget)
+        got_d, clean = _device(rrt, variance, hdr, albedo, lo, hi, budget)
+        assert np.array_equal(got_h, want), (lo, hi, budget, int(np.count_nonzero(got_h != want)))
+        assert np.array_equal(got_d, want) and clean, (lo, hi, budget, int(np.count_nonzero(got_d != want)))
+        assert int(want.sum(dtype=np.uint64)) <= SM.total(budget, want.size)
+
+
+def _saturated(shape, seed):
+    """ordinary pixels (_planes) mixed with more than 300 000 whose variance lies between 1e7 and 1e9: q at the clamp of 16 777 215
+    for a variance above 16 777 215 (sqrt(v) * 4096 >= 2^24), a little below it for the others"""
+    variance = _planes(shape, seed)[0]
+    rng = np.random.default_rng(seed + 1)
+    flat = variance.reshape(-1)
+    idx = rng.choice(flat.size, size=310000, replace=False)
+    flat[idx] = rng.uniform(1e7, 1e9, idx.size).astype(F)
+    flat[CAP + 5] = F(1e9)                                                   # one at the clamp in the second trip for certain
+    return variance
+
+
+def test_sum_past_2_to_32_past_the_grid_cap(rrt):
+    """the 64-bit sum: more than 300 000 pixels at or near the clamp make S about 5e12, in a plane past the cap so that every lane's
+    accumulator, the shuffles, the LDS step and the atomic all carry more than 32 bits"""
+    shape = PAST_CAP[0]
+    variance = _saturated(shape, 11)
+    lo, hi, budget = 0, 65535, 700.5
+    qi = SM.weights(variance)
+    s = int(qi.sum(dtype=np.uint64))
+    assert s > 2 ** 32 and int(np.count_nonzero(qi >= SM.QMAX - (1 << 22))) >= 300000        # conditions on the input
+    assert int(np.count_nonzero(qi == SM.QMAX)) > 256 and int(np.count_nonzero((qi > 0) & (qi < SM.QMAX))) > 256
+    x = qi.astype(np.float64) * (np.float64(SM.total(budget, qi.size) - lo * qi.size) / np.float64(s))
+    assert (x >= 1.0).any() and (x < 1.0).any() and (x < hi - lo).all()          # r * qi is neither 0 nor >= span everywhere
+    want = SM.sample_map(variance, None, None, lo, hi, budget)
+    assert np.unique(want).size > 100                                        # counts differ between pixels
+    got_h = _host(rrt, variance, None, None, lo, hi, budget)
+    got_d, clean = _device(rrt, variance, None, None, lo, hi, budget)
+    assert np.array_equal(got_h, want), int(np.count_nonzero(got_h != want))
+    assert np.array_equal(got_d, want) and clean, int(np.count_nonzero(got_d != want))
+    assert int(got_d.sum(dtype=np.uint64)) <= SM.total(budget, want.size)
+
+
+def test_zero_sum_and_equal_clamps_past_the_grid_cap(rrt):
+    """S == 0 gives uniform_extra on every trip; min == max gives the clamp on every trip whatever the weights are"""
+    shape = PAST_CAP[0]
+    zero = np.zeros(shape, dtype=F)
+    zero.reshape(-1)[[0, 1, CAP - 1, CAP, CAP + 300, -1]] = [np.nan, -1.0, -np.inf, -0.0, np.nan, -2.5]
+    for lo, hi, budget, value in ((1, 8, 3.75, 3), (0, 8, 0.5, 0), (2, 4, 4.0, 4)):
+        got, clean = _device(rrt, zero, None, None, lo, hi, budget)
+        assert np.all(got == value) and clean and np.array_equal(got, SM.sample_map(zero, None, None, lo, hi, budget))
+        assert np.array_equal(_host(rrt, zero, None, None, lo, hi, budget), got)
+    for variance in (np.full(shape, 0.5, dtype=F), _planes(shape, 13)[0], _saturated(shape, 17)):
+        for entry in (_host, lambda *a: _device(*a)[0]):
+            got = entry(rrt, variance, None, None, 4, 4, 4.0)
+            assert np.all(got == 4) and np.array_equal(got, SM.sample_map(variance, None, None, 4, 4, 4.0))
 
 
 def test_zero_sum_saturation_and_min_zero(rrt):

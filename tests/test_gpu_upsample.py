@@ -260,6 +260,31 @@ def test_many_tiny_views(rrt, orc):
     assert UM.same_bits(want[0][5], alone[0][0]) and UM.same_bits(want[1][5], alone[1][0])     # views never see each other
 
 
+CAP = 1 << 20                                                   # kMaxGrid: workgroups per launch, one 64x4 tile per trip
+
+
+def test_more_tiles_than_the_grid_holds(rrt, orc):
+    """2^20 + 700 views of 2x2 pixels from 1x1 at k = 2 are as many tiles at both resolutions: 700 workgroups of the pack and of the
+    upsampling kernel take a second trip, and the (view, tile) decode runs past 2^20.  Both outputs start as poison.  Views never
+    see each other (test_many_tiny_views), so the model on a subset of the views -- the first and last 8, both sides of the first
+    tile of the second trip, 2000 seeded others -- and every view against the same call made in chunks of 2^19 views -- below the
+    cap, the path the tests above hold to the model -- cover every word of out and weight."""
+    views = CAP + 700
+    planes = _fields((1, 1), 2, views, seed=7)
+    cut = lambda sl: {f: (a[sl] if f != "scale" else a) for f, a in planes.items()}  # noqa: E731
+    got = _device(rrt, planes, GUIDES)
+    assert not (got[0].view(np.uint32) == POISON_I).any() and not (got[1].view(np.uint32) == POISON_I).any()
+    rng = np.random.default_rng(views)
+    idx = np.unique(np.concatenate([np.arange(8), np.arange(views - 8, views), np.arange(CAP - 8, CAP + 8), rng.choice(views, 2000, replace=False)]))
+    want = _model(orc, cut(idx), GUIDES)
+    assert (want[1] > 0).any() and (want[1] == 0).any()                     # accepted taps and pixels without one
+    assert _same((got[0][idx], got[1][idx]), want), _differ((got[0][idx], got[1][idx]), want)
+    for lo in range(0, views, CAP // 2):
+        part = _device(rrt, cut(slice(lo, lo + CAP // 2)), GUIDES)
+        for g, p in zip(got, part):
+            assert np.array_equal(g[lo: lo + CAP // 2].view(np.uint32), p.view(np.uint32)), lo
+
+
 def _dicts(planes, conv):
     return {g: conv(planes["lo_" + g]) for g in GUIDES}, {g: conv(planes[g]) for g in GUIDES}
 

@@ -239,6 +239,31 @@ def test_many_tiny_views(rrt, orc):
     assert VM.same_bits(want[0][5], alone[0][0]) and VM.same_bits(want[1][5], alone[1][0])     # views never see each other
 
 
+CAP = 1 << 20                                                   # kMaxGrid: workgroups per launch, one 64x4 tile per trip
+
+
+def test_more_tiles_than_the_grid_holds(rrt, orc):
+    """2^20 + 700 views of 2x1 pixels are as many tiles: 700 workgroups of the pack, the estimate and both passes take a second trip,
+    and the (view, tile) decode runs past 2^20.  Every pixel has one neighbour, so a tap beside the centre is weighed.  Both outputs
+    start as poison.  Views never see each other (test_many_tiny_views), so the model on a subset of the views -- the first and last
+    8, both sides of the first tile of the second trip, 2000 seeded others -- and every view against the same call made in chunks
+    of 2^19 views -- below the cap, the path the tests above hold to the model -- cover every word of out and variance_out."""
+    views = CAP + 700
+    planes = _fields((2, 1), views, seed=7)
+    combo = GUIDES + HISTORY
+    got = _device(rrt, planes, combo, 2)
+    assert not (got[0].view(np.uint32) == POISON_I).any() and not (got[1].view(np.uint32) == POISON_I).any()
+    rng = np.random.default_rng(views)
+    idx = np.unique(np.concatenate([np.arange(8), np.arange(views - 8, views), np.arange(CAP - 8, CAP + 8), rng.choice(views, 2000, replace=False)]))
+    want = _model(orc, {k: a[idx] for k, a in planes.items()}, combo, 2)
+    assert not VM.same_bits(want[0], planes["hdr"][idx])
+    assert _same((got[0][idx], got[1][idx]), want), _differ((got[0][idx], got[1][idx]), want)
+    for lo in range(0, views, CAP // 2):
+        part = _device(rrt, {k: a[lo: lo + CAP // 2] for k, a in planes.items()}, combo, 2)
+        for g, p in zip(got, part):
+            assert np.array_equal(g[lo: lo + CAP // 2].view(np.uint32), p.view(np.uint32)), lo
+
+
 def test_torch_tensors_on_a_side_stream(rrt, orc):
     import torch
     planes = _fields((65, 9), 3, seed=5)

@@ -305,7 +305,7 @@ def test_struct_sizes_offsets_and_workspace_bytes(rrt):
     assert lib.mipt_abi_version() == 4
 
 
-def test_argument_checks_of_both_entries(rrt):
+def test_argument_checks_of_both_entries(rrt, orc):
     from rust_ray_tracing_amd import _lib as L
     lib = rrt.load()
     p = _Planes()
@@ -348,16 +348,33 @@ def test_argument_checks_of_both_entries(rrt):
         assert call(None, C.byref(p.bufs(L))) == L.ERR_INVALID_ARG and "opt" in lib.mipt_last_error().decode()
         assert call(C.byref(_opt(L)), None) == L.ERR_INVALID_ARG and "buffers" in lib.mipt_last_error().decode()
     # what may be absent and a sigma given for an absent guide get past the checks: to the device (the host entry) or the
-    # device-memory check (the device entry)
+    # device-memory check (the device entry).  These calls get planes of their own: where a device exists the host entry runs, and
+    # zeros upsample to zeros in `out` but not in `weight`, which is the sum of the accepted taps' weights -- the model's, bit for bit
+    zeros = np.zeros((V, H // K, W // K, 3), dtype=F)
+    guide_planes = lambda h, w: dict(normal=np.zeros((V, h, w, 3), dtype=F), depth=np.zeros((V, h, w), dtype=F),  # noqa: E731
+                                     albedo=np.zeros((V, h, w, 3), dtype=F), material=np.zeros((V, h, w), dtype=np.uint32))
     for okw, bkw in ((dict(sigma_normal=nan), dict(lo_normal=None, normal=None)), (dict(sigma_depth=0.0), dict(lo_depth=None, depth=None)),
                      ({}, dict(lo_albedo=None, albedo=None)), ({}, dict(lo_material=None, material=None)), ({}, dict(weight=None)),
                      ({}, {k: None for k in WORDS if k not in ("lo_hdr", "out")})):
-        rc = lib.mipt_upsample(C.byref(_opt(L, **okw)), C.byref(p.bufs(L, **bkw)), 0)
+        q = _Planes()
+        rc = lib.mipt_upsample(C.byref(_opt(L, **okw)), C.byref(q.bufs(L, **bkw)), 0)
         assert rc in (L.OK, L.ERR_HIP), (okw, bkw, rc, lib.mipt_last_error())
-        assert lib.mipt_upsample_device(C.byref(_opt(L, **okw)), C.byref(p.bufs(L, **bkw)), p.ws.ctypes.data, p.ws.nbytes, None) == L.ERR_INVALID_ARG
+        assert lib.mipt_upsample_device(C.byref(_opt(L, **okw)), C.byref(q.bufs(L, **bkw)), q.ws.ctypes.data, q.ws.nbytes, None) == L.ERR_INVALID_ARG
         assert "lo_hdr is not device memory" in lib.mipt_last_error().decode()
+        for k, a in q.a.items():
+            if k != "weight":
+                assert not a.any(), (okw, bkw, k)                       # inputs untouched, out all zero, nothing behind a plane
+        weight = q.a["weight"]
+        if rc == L.OK and "weight" not in bkw:
+            passed = [g for g in GUIDES if g not in bkw]
+            lo_g, hi_g = guide_planes(H // K, W // K), guide_planes(H, W)
+            want = UM.upsample(orc, zeros, K, {g: lo_g[g] for g in passed}, {g: hi_g[g] for g in passed})[1]
+            assert (want > 0).all() and np.array_equal(_bits(weight[: N]), _bits(want.reshape(-1))), (okw, bkw)
+            assert not weight[N:].any()
+        else:
+            assert not weight.any(), (okw, bkw)                         # no device, or no weight plane passed: not written
     for a in p.a.values():
-        assert not a.any()                                              # no refused call wrote anything (zeros upsample to zeros)
+        assert not a.any()                                              # no refused call wrote anything
 
 
 def test_device_entry_checks_workspace_alignment_and_memory(rrt):
