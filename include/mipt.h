@@ -538,6 +538,37 @@ MIPT_API int mipt_temporal(const MiptTemporalOptions *opt, const MiptCamera *cam
 MIPT_API int mipt_temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
                                   void *hip_stream);
 
+/* mipt_temporal_counts: the same accumulation with the history length counted in SAMPLES, for frames traced by mipt_render_adaptive.
+ * The structs, the buffers, the checks, the history layout and mipt_temporal_history_bytes() are mipt_temporal's; flags and reserved
+ * fields are refused as there.  Two more arguments:
+ *   counts      : one u32 per pixel, view-major -- the plane mipt_render_adaptive was given for this frame;
+ *   samples_cap : that call's opt->samples, 1 ... 65535.
+ * Pixel i was traced with n = min(counts[i], samples_cap) samples; nf = (float)n.  The contract is the one above, every operator one
+ * rounded f32 operation, nothing fused, every comparison with a NaN on the reject / reset side, with these changes and no others:
+ *   - a tap is additionally rejected unless len_q > 0 (a pixel no sample has reached yet carries no colour).  A history written by
+ *     mipt_temporal never has such a tap.
+ *   - RESET with n > 0: c = cc, len = nf < max_history ? nf : max_history, m1 = l, m2 = l*l.
+ *   - an accepted history (sw > 1/64) with n > 0: ln = lp + nf, ln = ln < max_history ? ln : max_history; al = nf / ln,
+ *     al = al > alpha_min ? al : alpha_min, al = al < 1 ? al : 1; c, m1 and m2 are blended with al as above; len = ln.
+ *     max_history is therefore a number of samples.
+ *   - n == 0 (the pixel was not traced: hdr holds nothing of this frame): hdr[i] is NOT READ -- a NaN there changes nothing.
+ *     With an accepted history: c = cp, len = lp < max_history ? lp : max_history, m1 = s1/sw, m2 = s2/sw -- pure reprojection
+ *     (lp is a mean of lengths that are at most max_history, but sl/sw can round one ulp past it: no stored length ever exceeds
+ *     max_history).  Otherwise c = +0, len = 0, m1 = m2 = +0.
+ *   - written as above: the three history planes, the camera record, out = c * a, length, variance.
+ * Consequences.  (a) With counts all 1 (any samples_cap) every output byte and every history byte equals mipt_temporal's.
+ * (b) Histories interchange: either entry accepts the other's history_out as history_in.
+ * `variance` is the variance of the FRAME MEANS over the history, each weighted by its samples; it is not a per-sample variance (the
+ * mean of n samples enters as one value with the weight n).  With min_samples = 0 in the map, a pixel that is never traced and never
+ * reprojected keeps len 0 and variance 0, so the map never gives it a sample: it stays starved, which is the caller's choice.
+ * Errors, before any device work and naming the field: everything of mipt_temporal, and a null counts; samples_cap outside
+ * 1 ... 65535; for the device entry a counts that is not 4-byte aligned, not device memory of hdr's device, or that overlaps any
+ * buffer or history. */
+MIPT_API int mipt_temporal_counts(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *host,
+                                  const uint32_t *counts, uint32_t samples_cap, int device_id);
+MIPT_API int mipt_temporal_counts_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
+                                         const uint32_t *d_counts, uint32_t samples_cap, void *hip_stream);
+
 /* ---- variance-guided a-trous filter: the accumulated frame plus its variance and history length -> the frame to show ----------------
  * The second half of the SVGF-style pipeline (Schied et al. 2017) whose first half is the temporal accumulation above: the a-trous
  * filter of the denoiser section with a colour bandwidth that follows each pixel's own noise instead of a fixed sigma_color * 2^-i
@@ -788,6 +819,44 @@ MIPT_API int mipt_sample_map(const MiptSampleMapOptions *opt, const MiptSampleMa
  * mipt_sample_map_workspace_bytes().  The call writes `counts` and the first mipt_sample_map_workspace_bytes() bytes of the
  * workspace, and nothing else. */
 MIPT_API int mipt_sample_map_device(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *device, void *d_workspace, void *hip_stream);
+
+/* mipt_sample_map_fill: the same map, but what the clamp at max_samples cuts off is handed on, `rounds` times.  The buffers, qi, S, T,
+ * E and span = max_samples - min_samples are mipt_sample_map's, and round 1 is mipt_sample_map itself: it gives e_1(p), the uniform
+ * value at S == 0 included.  For each round k = 2 ... rounds:
+ *   A   = the sum of e_{k-1}(p) over all pixels, S_k = the sum of qi(p) over the pixels with e_{k-1}(p) < span: uint64 sums, exact in
+ *         any order.  E_k = A < E ? E - A : 0.
+ *   If S_k == 0 or E_k == 0 the round changes nothing -- and then no later round does, as its sums are the same.
+ *   Otherwise r_k = (double)E_k / (double)S_k, formed once on the device, and for each pixel with e_{k-1} < span, in binary64, one
+ *   rounded operation each: x = (double)qi * r_k; room = span - e_{k-1}; add = x < (double)room ? (uint32_t)x : room;
+ *   e_k = e_{k-1} + add.  Every other pixel keeps e_k = e_{k-1}.
+ *   counts = min_samples + e_rounds.
+ * So rounds = 1 is mipt_sample_map bit for bit; every count stays in [min_samples, max_samples]; no count falls from one round count
+ * to the next, so the sum of counts does not decrease in `rounds`; and the sum never exceeds T, in the rounded arithmetic too.  Round 1
+ * leaves A <= E (the argument above).  In round k the exact shares qi * E_k / S_k of the pixels below the span add up to E_k, S_k
+ * being the sum of exactly their qi.  (double)S_k, r_k and qi * r_k carry three relative errors of 2^-53, so a pixel's `add` can pass
+ * the floor of its exact share only if that share lay within share * 3 * 2^-53 below an integer (the clamp at `room`, an integer, is
+ * such a crossing too); `add` is at most span < 2^16, so over N < 2^32 pixels those excesses add up to less than 2^-3, and a sum of
+ * integers that exceeds E_k by less than 1 does not exceed it.  The sum of e_k is thus at most A + E_k = E, which is the next round's
+ * A <= E; and the sum of counts is at most min_samples * N + E = T after every round.
+ * `rounds` passes cost rounds + 1 kernel launches (each pass also forms the next round's two sums). */
+typedef struct {
+    uint32_t width, height, n_views;
+    uint32_t flags;                   /* must be 0 */
+    uint32_t min_samples;             /* 0 <= min_samples <= max_samples */
+    uint32_t max_samples;             /* 1 ... 65535 */
+    float    budget;                  /* finite, min_samples <= budget <= max_samples: the upper bound on the mean of counts */
+    uint32_t rounds;                  /* 1 ... 8; 1 = mipt_sample_map */
+    uint32_t reserved[8];             /* must be 0 */
+} MiptSampleMapFillOptions;           /* 64 B: MiptSampleMapOptions with `rounds` taken from its reserved words */
+
+/* Bytes of workspace mipt_sample_map_fill_device needs: 32 B per round ({S_k, r_k, the ticket, A}).  0 = an invalid size or a
+ * `rounds` outside 1 ... 8. */
+MIPT_API uint64_t mipt_sample_map_fill_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views, uint32_t rounds);
+/* As mipt_sample_map / mipt_sample_map_device, with their errors and: rounds outside 1 ... 8.  The device entry writes `counts` and
+ * the first mipt_sample_map_fill_workspace_bytes() bytes of the workspace, and nothing else. */
+MIPT_API int mipt_sample_map_fill(const MiptSampleMapFillOptions *opt, const MiptSampleMapBuffers *host, int device_id);
+MIPT_API int mipt_sample_map_fill_device(const MiptSampleMapFillOptions *opt, const MiptSampleMapBuffers *device, void *d_workspace,
+                                         void *hip_stream);
 
 /* ---- previous positions: where every pixel's surface point was in the previous geometry ------------------------------------------------
  * The link between the geometry updates and the temporal accumulation above: per pixel the world position that the first hit's

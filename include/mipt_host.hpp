@@ -160,10 +160,12 @@ struct UpsampleSettings {
 };
 
 // Renderer::sample_map: the map's settings (MiptSampleMapOptions; the defaults of the Python mirror: max_samples 0 = options.samples,
-// a negative budget = min_samples)
+// a negative budget = min_samples).  rounds 0 = mipt_sample_map; 1 ... 8 = mipt_sample_map_fill, which hands on what the clamp at
+// max_samples cuts off (MiptSampleMapFillOptions).
 struct SampleMapSettings {
     uint32_t min_samples = 1, max_samples = 0;
     float budget = -1.0f;
+    uint32_t rounds = 0;
 };
 
 // An indexed mesh kept resident on one device (include/mipt.h "resident indexed meshes"): what OBJ holds before scene.rs:48-76 expands
@@ -609,7 +611,15 @@ class Renderer {                                           // src/renderer.rs:8-
         b.hdr = hdr.empty() ? nullptr : hdr.data();
         b.albedo = albedo.empty() ? nullptr : albedo.data();
         b.counts = counts.data();
-        const int rc = mipt_sample_map(&o, &b, options.device_id);
+        int rc;
+        if (settings.rounds) {
+            MiptSampleMapFillOptions f{};
+            f.width = o.width; f.height = o.height; f.n_views = o.n_views;
+            f.min_samples = o.min_samples; f.max_samples = o.max_samples; f.budget = o.budget; f.rounds = settings.rounds;
+            rc = mipt_sample_map_fill(&f, &b, options.device_id);
+        } else {
+            rc = mipt_sample_map(&o, &b, options.device_id);
+        }
         if (rc != MIPT_OK) log_error(mipt_last_error());
         return rc;
     }
@@ -621,6 +631,20 @@ class Renderer {                                           // src/renderer.rs:8-
     // and may be `hdr` itself.  Returns a MiptStatus; a size that does not fit is MIPT_ERR_INVALID_ARG before the library is called.
     int temporal(const std::vector<float> &hdr, const std::vector<MiptCamera> &cameras, const FeatureImages &guides, TemporalState &state,
                  std::vector<float> &out, const TemporalSettings &settings = TemporalSettings()) const {
+        return temporal_call(hdr, cameras, guides, state, out, nullptr, 0, settings);
+    }
+    // The same with the history length counted in samples (mipt_temporal_counts): `counts` is the plane render_adaptive was given for
+    // this frame, one u32 per pixel, and `samples_cap` that call's cap (0 = options.samples).  settings.max_history is then a
+    // number of samples.
+    int temporal(const std::vector<float> &hdr, const std::vector<MiptCamera> &cameras, const FeatureImages &guides, TemporalState &state,
+                 std::vector<float> &out, const std::vector<uint32_t> &counts, uint32_t samples_cap = 0,
+                 const TemporalSettings &settings = TemporalSettings()) const {
+        return temporal_call(hdr, cameras, guides, state, out, &counts, samples_cap ? samples_cap : (uint32_t)options.samples, settings);
+    }
+
+  private:
+    int temporal_call(const std::vector<float> &hdr, const std::vector<MiptCamera> &cameras, const FeatureImages &guides, TemporalState &state,
+                      std::vector<float> &out, const std::vector<uint32_t> *counts, uint32_t samples_cap, const TemporalSettings &settings) const {
         MiptTemporalOptions o{};
         o.width = (uint32_t)options.output_image_dimensions.first; o.height = (uint32_t)options.output_image_dimensions.second;
         o.n_views = (uint32_t)cameras.size();
@@ -636,7 +660,7 @@ class Renderer {                                           // src/renderer.rs:8-
         if (sized && !(fits(hdr.size(), n * 3, "hdr", true) && fits(guides.position.size(), n * 3, "position", true) &&
                        fits(guides.normal.size(), n * 3, "normal", true) && fits(guides.depth.size(), n, "depth", true) &&
                        fits(guides.material.size(), n, "material", true) && fits(guides.albedo.size(), n * 3, "albedo", false) &&
-                       fits(state.history.size(), words, "history", false)))
+                       fits(state.history.size(), words, "history", false) && (!counts || fits(counts->size(), n, "counts", true))))
             return MIPT_ERR_INVALID_ARG;
         static const float no_pixel[3] = {0.0f, 0.0f, 0.0f};
         static const uint32_t no_material = 0;
@@ -657,11 +681,15 @@ class Renderer {                                           // src/renderer.rs:8-
         b.out = out.data();
         b.length = settings.want_length ? state.length.data() : nullptr;
         b.variance = settings.want_variance ? state.variance.data() : nullptr;
-        const int rc = mipt_temporal(&o, cameras.empty() ? &no_camera : cameras.data(), &b, options.device_id);
+        const MiptCamera *cams = cameras.empty() ? &no_camera : cameras.data();
+        const int rc = counts ? mipt_temporal_counts(&o, cams, &b, counts->empty() ? nullptr : counts->data(), samples_cap, options.device_id)
+                              : mipt_temporal(&o, cams, &b, options.device_id);
         if (rc != MIPT_OK) log_error(mipt_last_error());
         else state.history.swap(next);
         return rc;
     }
+
+  public:
 
     // The same arm over EVERY GPU of the node from this single-threaded host (mipt_render_multi: scene replicas, RCCL
     // communicators and the one gather / sum-reduce per frame live inside the library).  mode = MIPT_MULTI_TILES reproduces

@@ -190,7 +190,13 @@ class MiptSampleMapBuffers(C.Structure):
     _fields_ = [("variance", C.c_void_p), ("hdr", C.c_void_p), ("albedo", C.c_void_p), ("counts", C.c_void_p), ("reserved", C.c_void_p * 4)]
 
 
-assert C.sizeof(MiptSampleMapOptions) == 64 and C.sizeof(MiptSampleMapBuffers) == 64
+class MiptSampleMapFillOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_views", C.c_uint32), ("flags", C.c_uint32),
+                ("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("budget", C.c_float), ("rounds", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+assert C.sizeof(MiptSampleMapOptions) == 64 and C.sizeof(MiptSampleMapBuffers) == 64 and C.sizeof(MiptSampleMapFillOptions) == 64
 
 MESH_PART = np.dtype([("first_tri", "<u4"), ("n_tris", "<u4"), ("material_id", "<u4"), ("reserved", "<u4")])   # MiptMeshPart
 assert MESH_PART.itemsize == 16
@@ -247,6 +253,8 @@ EXPORTS = [
     "mipt_mesh_expand", "mipt_scene_create_from_mesh", "mipt_scene_set_transforms", "mipt_scene_update_mesh_device", "mipt_scene_mesh_info",
     "mipt_render_motion", "mipt_render_motion_device", "mipt_scene_track_motion",
     "mipt_render_adaptive", "mipt_render_adaptive_device", "mipt_sample_map_workspace_bytes", "mipt_sample_map", "mipt_sample_map_device",
+    "mipt_temporal_counts", "mipt_temporal_counts_device",
+    "mipt_sample_map_fill_workspace_bytes", "mipt_sample_map_fill", "mipt_sample_map_fill_device",
 ]
 
 _lib = None
@@ -396,6 +404,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_temporal.restype = C.c_int
     lib.mipt_temporal_device.argtypes = [to, vp, tb, vp]
     lib.mipt_temporal_device.restype = C.c_int
+    lib.mipt_temporal_counts.argtypes = [to, vp, tb, vp, u32, C.c_int]
+    lib.mipt_temporal_counts.restype = C.c_int
+    lib.mipt_temporal_counts_device.argtypes = [to, vp, tb, vp, u32, vp]
+    lib.mipt_temporal_counts_device.restype = C.c_int
     vo, vb = C.POINTER(MiptVarianceOptions), C.POINTER(MiptVarianceBuffers)
     lib.mipt_denoise_variance_workspace_bytes.argtypes = [u32, u32, u32]
     lib.mipt_denoise_variance_workspace_bytes.restype = u64
@@ -421,6 +433,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_sample_map.restype = C.c_int
     lib.mipt_sample_map_device.argtypes = [so, sb, vp, vp]
     lib.mipt_sample_map_device.restype = C.c_int
+    fo = C.POINTER(MiptSampleMapFillOptions)
+    lib.mipt_sample_map_fill_workspace_bytes.argtypes = [u32, u32, u32, u32]
+    lib.mipt_sample_map_fill_workspace_bytes.restype = u64
+    lib.mipt_sample_map_fill.argtypes = [fo, sb, C.c_int]
+    lib.mipt_sample_map_fill.restype = C.c_int
+    lib.mipt_sample_map_fill_device.argtypes = [fo, sb, vp, vp]
+    lib.mipt_sample_map_fill_device.restype = C.c_int
     return lib
 
 

@@ -1,5 +1,5 @@
 // mipt_adaptive.cpp -- the adaptive-sampling entry points of include/mipt.h (mipt_render_adaptive, mipt_render_adaptive_device,
-// mipt_sample_map_workspace_bytes, mipt_sample_map, mipt_sample_map_device): argument checks, device staging for the host entries, the
+// mipt_sample_map_workspace_bytes, mipt_sample_map, mipt_sample_map_device and their _fill forms): argument checks, device staging for the host entries, the
 // camera table and the launches of pt_kernel.hip's adaptive kernel and of sample_map.hip.  Host C++ only; every device operation is
 // stream-ordered HIP.
 #include "../../include/mipt.h"
@@ -11,6 +11,7 @@
 
 static_assert(sizeof(MiptSampleMapOptions) == 64 && sizeof(MiptSampleMapBuffers) == 64, "ABI struct sizes (tests/test_adaptive_abi.py)");
 static_assert(sizeof(mipt::SampleMapWork) == 32, "mipt_sample_map_workspace_bytes");
+static_assert(sizeof(MiptSampleMapFillOptions) == 64 && sizeof(mipt::SampleMapFillWork) == 32, "ABI struct size, mipt_sample_map_fill_workspace_bytes");
 
 namespace {
 
@@ -210,12 +211,28 @@ int map_validate(const char *who, const MiptSampleMapOptions *opt, const MiptSam
     return MIPT_OK;
 }
 
-int map_device(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, void *d_workspace, void *hip_stream) {
-    const char *who = "mipt_sample_map_device";
+// the fill entries' options as the plain map's, for map_validate: the same fields in the same places, `rounds` checked apart
+int fill_options(const char *who, const MiptSampleMapFillOptions *fill, MiptSampleMapOptions &opt) {
+    if (!fill) return fail(MIPT_ERR_INVALID_ARG, "%s: null opt", who);
+    opt = MiptSampleMapOptions{};
+    opt.width = fill->width; opt.height = fill->height; opt.n_views = fill->n_views; opt.flags = fill->flags;
+    opt.min_samples = fill->min_samples; opt.max_samples = fill->max_samples; opt.budget = fill->budget;
+    for (int i = 0; i < 8; i++) opt.reserved[i] = fill->reserved[i];
+    return MIPT_OK;
+}
+int fill_rounds(const char *who, const MiptSampleMapFillOptions *fill) {
+    if (fill->rounds < 1 || fill->rounds > mipt::kSampleMapMaxRounds)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: rounds %u: must be 1 ... %u", who, fill->rounds, mipt::kSampleMapMaxRounds);
+    return MIPT_OK;
+}
+
+// rounds == 0: mipt_sample_map_device; otherwise mipt_sample_map_fill_device
+int map_device(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, uint32_t rounds, void *d_workspace,
+               void *hip_stream) {
     mipt::DevSampleMap d;
     int rc = map_validate(who, opt, buf, d);
     if (rc) return rc;
-    const uint64_t need = sizeof(mipt::SampleMapWork);
+    const uint64_t need = rounds ? sizeof(mipt::SampleMapFillWork) * rounds : sizeof(mipt::SampleMapWork);
     if (!d_workspace) return fail(MIPT_ERR_INVALID_ARG, "%s: null workspace", who);
     if ((uintptr_t)d_workspace & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: workspace must be 16-byte aligned", who);
     const void *p[kBuffers];
@@ -231,13 +248,16 @@ int map_device(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf,
         if (p[i] && (rc = mipt::device_buffer_check(who, p[i], device, kFields[i].name, "variance's device"))) return rc;
     if ((rc = mipt::device_buffer_check(who, d_workspace, device, "workspace", "variance's device"))) return rc;
     MIPT_HIP(hipSetDevice(device));
+    if (rounds) {
+        MIPT_HIP(mipt::launch_sample_map_fill(d, (mipt::SampleMapFillWork *)d_workspace, rounds, (hipStream_t)hip_stream));
+        return MIPT_OK;
+    }
     d.work = (mipt::SampleMapWork *)d_workspace;
     MIPT_HIP(mipt::launch_sample_map(d, (hipStream_t)hip_stream));
     return MIPT_OK;
 }
 
-int map_host(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, int device_id) {
-    const char *who = "mipt_sample_map";
+int map_host(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, uint32_t rounds, int device_id) {
     mipt::DevSampleMap d;
     const int rc = map_validate(who, opt, buf, d);
     if (rc) return rc;
@@ -250,19 +270,40 @@ int map_host(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, i
     unpack(buf, h);
     mipt::DevPtr<float> dev[kCounts];                             // variance, hdr, albedo
     mipt::DevPtr<uint32_t> counts;
-    mipt::DevPtr<mipt::SampleMapWork> work;
+    mipt::DevPtr<mipt::SampleMapFillWork> work;                  // one slot is also the plain map's workspace: the same 32 B
     for (int i = 0; i < kCounts; i++)
         if (h[i]) {
             MIPT_HIP(dev[i].alloc(d.n_pixels * kFields[i].words));
             MIPT_HIP(hipMemcpy(dev[i].get(), h[i], d.n_pixels * kFields[i].words * sizeof(float), hipMemcpyHostToDevice));
         }
     MIPT_HIP(counts.alloc(d.n_pixels));
-    MIPT_HIP(work.alloc(1));
+    MIPT_HIP(work.alloc(rounds ? rounds : 1u));
     d.variance = dev[kVariance].get(); d.hdr = dev[kHdrBuf].get(); d.albedo = dev[kAlbedo].get();
-    d.counts = counts.get(); d.work = work.get();
-    MIPT_HIP(mipt::launch_sample_map(d, nullptr));
+    d.counts = counts.get(); d.work = (mipt::SampleMapWork *)work.get();
+    if (rounds) MIPT_HIP(mipt::launch_sample_map_fill(d, work.get(), rounds, nullptr));
+    else MIPT_HIP(mipt::launch_sample_map(d, nullptr));
     MIPT_HIP(hipMemcpy(buf->counts, counts.get(), d.n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));   // ordered after the passes: blocks until done
     return MIPT_OK;
+}
+
+int fill_host(const MiptSampleMapFillOptions *fill, const MiptSampleMapBuffers *buf, int device_id) {
+    const char *who = "mipt_sample_map_fill";
+    MiptSampleMapOptions opt;
+    int rc = fill_options(who, fill, opt);
+    if (rc) return rc;
+    if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
+    if ((rc = fill_rounds(who, fill))) return rc;
+    return map_host(who, &opt, buf, fill->rounds, device_id);
+}
+
+int fill_device(const MiptSampleMapFillOptions *fill, const MiptSampleMapBuffers *buf, void *d_workspace, void *hip_stream) {
+    const char *who = "mipt_sample_map_fill_device";
+    MiptSampleMapOptions opt;
+    int rc = fill_options(who, fill, opt);
+    if (rc) return rc;
+    if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
+    if ((rc = fill_rounds(who, fill))) return rc;
+    return map_device(who, &opt, buf, fill->rounds, d_workspace, hip_stream);
 }
 
 } // namespace
@@ -282,10 +323,21 @@ uint64_t mipt_sample_map_workspace_bytes(uint32_t width, uint32_t height, uint32
     return mipt::batch_pixels(width, height, n_views) ? sizeof(mipt::SampleMapWork) : 0u;
 }
 int mipt_sample_map(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *host, int device_id) {
-    MIPT_NO_THROW(map_host(opt, host, device_id))
+    MIPT_NO_THROW(map_host("mipt_sample_map", opt, host, 0u, device_id))
 }
 int mipt_sample_map_device(const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *device, void *d_workspace, void *hip_stream) {
-    MIPT_NO_THROW(map_device(opt, device, d_workspace, hip_stream))
+    MIPT_NO_THROW(map_device("mipt_sample_map_device", opt, device, 0u, d_workspace, hip_stream))
+}
+
+uint64_t mipt_sample_map_fill_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_views, uint32_t rounds) {
+    if (rounds < 1 || rounds > mipt::kSampleMapMaxRounds || !mipt::batch_pixels(width, height, n_views)) return 0u;
+    return sizeof(mipt::SampleMapFillWork) * rounds;
+}
+int mipt_sample_map_fill(const MiptSampleMapFillOptions *opt, const MiptSampleMapBuffers *host, int device_id) {
+    MIPT_NO_THROW(fill_host(opt, host, device_id))
+}
+int mipt_sample_map_fill_device(const MiptSampleMapFillOptions *opt, const MiptSampleMapBuffers *device, void *d_workspace, void *hip_stream) {
+    MIPT_NO_THROW(fill_device(opt, device, d_workspace, hip_stream))
 }
 
 } // extern "C"

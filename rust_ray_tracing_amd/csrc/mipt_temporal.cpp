@@ -1,5 +1,6 @@
 // mipt_temporal.cpp -- the temporal-accumulation entry points of include/mipt.h (mipt_temporal_history_bytes, mipt_temporal,
-// mipt_temporal_device): argument checks, the camera records, device staging for the host entry and the launches of temporal.hip.
+// mipt_temporal_device, mipt_temporal_counts, mipt_temporal_counts_device): argument checks, the camera records, device staging for
+// the host entry and the launches of temporal.hip.
 // Host C++ only; every device operation is stream-ordered HIP.
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
@@ -62,9 +63,13 @@ bool camera_record(const MiptCamera &cam, float rec[16]) {
     return true;
 }
 
+// The count plane of the _counts entries; `counted` false = the plain entries, which have none.
+struct Counts { bool counted; const uint32_t *plane; uint32_t cap; };
+constexpr Counts kNoCounts = {false, nullptr, 0u};
+
 // everything that needs no device: on success d holds the sizes, the options and the caller's pointers, records the camera records
-int validate(const char *who, const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, mipt::DevTemporal &d,
-             std::vector<float> &records) {
+int validate(const char *who, const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, const Counts &cnt,
+             mipt::DevTemporal &d, std::vector<float> &records) {
     if (!opt) return fail(MIPT_ERR_INVALID_ARG, "%s: null opt", who);
     if (!cameras) return fail(MIPT_ERR_INVALID_ARG, "%s: null cameras", who);
     if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
@@ -90,6 +95,10 @@ int validate(const char *who, const MiptTemporalOptions *opt, const MiptCamera *
         if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
     for (const void *r : buf->reserved)
         if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved buffer pointers must be NULL", who);
+    if (cnt.counted) {
+        if (!cnt.plane) return fail(MIPT_ERR_INVALID_ARG, "%s: null counts", who);
+        if (cnt.cap < 1 || cnt.cap > 65535) return fail(MIPT_ERR_INVALID_ARG, "%s: samples_cap %u: must be 1 ... 65535", who, cnt.cap);
+    }
 
     records.assign((size_t)opt->n_views * 16, 0.0f);
     for (uint32_t v = 0; v < opt->n_views; v++)
@@ -119,14 +128,22 @@ int validate(const char *who, const MiptTemporalOptions *opt, const MiptCamera *
     return MIPT_OK;
 }
 
-int temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, void *hip_stream) {
-    const char *who = "mipt_temporal_device";
+int temporal_device(const char *who, const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, const Counts &cnt,
+                    void *hip_stream) {
     mipt::DevTemporal d;
     std::vector<float> records;
-    int rc = validate(who, opt, cameras, buf, d, records);
+    int rc = validate(who, opt, cameras, buf, cnt, d, records);
     if (rc) return rc;
     const void *p[kBuffers];
     unpack(buf, p);
+    if (cnt.counted) {
+        if ((uintptr_t)cnt.plane & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: counts must be 4-byte aligned", who);
+        for (int i = 0; i < kBuffers; i++) {
+            const uint64_t bytes = kFields[i].bytes ? d.n_pixels * kFields[i].bytes : history_bytes(d.n_pixels, d.n_views);
+            if (p[i] && mipt::ranges_overlap(cnt.plane, d.n_pixels * 4, p[i], bytes))
+                return fail(MIPT_ERR_INVALID_ARG, "%s: counts overlaps %s", who, kFields[i].name);
+        }
+    }
     for (int i = 0; i < kBuffers; i++) {
         const uintptr_t mask = kFields[i].bytes ? 3u : 15u;
         if ((uintptr_t)p[i] & mask) return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be %u-byte aligned", who, kFields[i].name, (unsigned)mask + 1u);
@@ -135,16 +152,17 @@ int temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, c
     if ((rc = mipt::device_buffer_check(who, buf->hdr, -1, "hdr", "", &device))) return rc;
     for (int i = 1; i < kBuffers; i++)
         if (p[i] && (rc = mipt::device_buffer_check(who, p[i], device, kFields[i].name, "hdr's device"))) return rc;
+    if (cnt.counted && (rc = mipt::device_buffer_check(who, cnt.plane, device, "counts", "hdr's device"))) return rc;
     MIPT_HIP(hipSetDevice(device));
-    MIPT_HIP(mipt::launch_temporal(d, records.data(), (hipStream_t)hip_stream));
+    MIPT_HIP(mipt::launch_temporal(d, records.data(), (hipStream_t)hip_stream, cnt.plane, cnt.cap));
     return MIPT_OK;
 }
 
-int temporal_host(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, int device_id) {
-    const char *who = "mipt_temporal";
+int temporal_host(const char *who, const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *buf, const Counts &cnt,
+                  int device_id) {
     mipt::DevTemporal d;
     std::vector<float> records;
-    const int rc = validate(who, opt, cameras, buf, d, records);
+    const int rc = validate(who, opt, cameras, buf, cnt, d, records);
     if (rc) return rc;
     const hipError_t e = hipSetDevice(device_id);
     if (e != hipSuccess) {
@@ -161,11 +179,16 @@ int temporal_host(const MiptTemporalOptions *opt, const MiptCamera *cameras, con
         MIPT_HIP(dev[i].alloc(bytes));
         if (i < kHistoryOut) MIPT_HIP(hipMemcpy(dev[i].get(), h[i], bytes, hipMemcpyHostToDevice));
     }
+    mipt::DevPtr<uint32_t> d_counts;
+    if (cnt.counted) {
+        MIPT_HIP(d_counts.alloc((size_t)n_pix));
+        MIPT_HIP(hipMemcpy(d_counts.get(), cnt.plane, n_pix * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     d.hdr = (const float *)dev[0].get(); d.position = (const float *)dev[1].get(); d.normal = (const float *)dev[2].get();
     d.depth = (const float *)dev[3].get(); d.material = (const uint32_t *)dev[4].get(); d.albedo = (const float *)dev[kAlbedo].get();
     d.history_in = (const float *)dev[kHistoryIn].get(); d.history_out = (float *)dev[kHistoryOut].get();
     d.out = (float *)dev[kHdr].get(); d.length = (float *)dev[kLength].get(); d.variance = (float *)dev[kVariance].get();
-    MIPT_HIP(mipt::launch_temporal(d, records.data(), nullptr));
+    MIPT_HIP(mipt::launch_temporal(d, records.data(), nullptr, d_counts.get(), cnt.cap));
     // ordered after the launches on the null stream: each copy blocks until they are done
     MIPT_HIP(hipMemcpy(buf->history_out, dev[kHistoryOut].get(), hist, hipMemcpyDeviceToHost));
     MIPT_HIP(hipMemcpy(buf->out, dev[kHdr].get(), n_pix * 12, hipMemcpyDeviceToHost));
@@ -183,10 +206,20 @@ uint64_t mipt_temporal_history_bytes(uint32_t width, uint32_t height, uint32_t n
     return n_pix ? history_bytes(n_pix, n_views) : 0;
 }
 int mipt_temporal(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *host, int device_id) {
-    MIPT_NO_THROW(temporal_host(opt, cameras, host, device_id))
+    MIPT_NO_THROW(temporal_host("mipt_temporal", opt, cameras, host, kNoCounts, device_id))
 }
 int mipt_temporal_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device, void *hip_stream) {
-    MIPT_NO_THROW(temporal_device(opt, cameras, device, hip_stream))
+    MIPT_NO_THROW(temporal_device("mipt_temporal_device", opt, cameras, device, kNoCounts, hip_stream))
+}
+int mipt_temporal_counts(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *host, const uint32_t *counts,
+                         uint32_t samples_cap, int device_id) {
+    const Counts cnt = {true, counts, samples_cap};
+    MIPT_NO_THROW(temporal_host("mipt_temporal_counts", opt, cameras, host, cnt, device_id))
+}
+int mipt_temporal_counts_device(const MiptTemporalOptions *opt, const MiptCamera *cameras, const MiptTemporalBuffers *device,
+                                const uint32_t *d_counts, uint32_t samples_cap, void *hip_stream) {
+    const Counts cnt = {true, d_counts, samples_cap};
+    MIPT_NO_THROW(temporal_device("mipt_temporal_counts_device", opt, cameras, device, cnt, hip_stream))
 }
 
 } // extern "C"

@@ -192,9 +192,17 @@ struct DevTemporal {
     float alpha_min, max_history, normal_tol, depth_tol;
     float camera[kTemporalGroupViews][16];  // this frame's records of the launch's views, for history_out's header
 };
+// mipt_temporal_counts*: the plain kernels' arguments, and behind them the plane mipt_render_adaptive was given and its cap.  The
+// plain kernels keep DevTemporal as their argument, so nothing of theirs moves.
+struct DevTemporalCounts {
+    DevTemporal t;
+    const uint32_t *counts;                 // one u32 per pixel, view-major
+    uint32_t samples_cap;
+};
 // one launch per group of kTemporalGroupViews views; `records` holds n_views * 16 f32 (stream-ordered; no allocation, no
-// synchronisation inside, and `records` is not read after the call returns)
-hipError_t launch_temporal(DevTemporal d, const float *records, hipStream_t stream);
+// synchronisation inside, and `records` is not read after the call returns).  counts NULL = mipt_temporal*: every pixel counts as one
+// sample and samples_cap is not used.
+hipError_t launch_temporal(DevTemporal d, const float *records, hipStream_t stream, const uint32_t *counts = nullptr, uint32_t samples_cap = 0u);
 
 // ---- variance-guided a-trous filter (denoise_variance.hip; mipt_denoise_variance*) ----
 struct DevVariance {
@@ -252,6 +260,18 @@ struct DevSampleMap {
 };
 // the workspace's memset, the reduction and the assignment, one launch each (stream-ordered; no allocation, no synchronisation inside)
 hipError_t launch_sample_map(const DevSampleMap &d, hipStream_t stream);
+// mipt_sample_map_fill*: one slot per round, all zeroed by one memset.  Slot 0 begins like SampleMapWork, so round 1's sum is
+// sample_map.hip's own reduction; slot k - 1 holds what round k's pass reads, left there by round k - 1's pass.
+struct SampleMapFillWork {                  // 32 B
+    unsigned long long sum;                 // S_k: the sum of qi over the pixels round k may still raise (round 1: over all)
+    double ratio;                           // r_k = E_k / S_k, formed once by the last block to add its part
+    uint32_t done;                          // blocks that have added their part
+    uint32_t active;                        // rounds 2 ...: 1 when S_k != 0 and E_k != 0, else the round changes nothing
+    unsigned long long assigned;            // A: the sum of e_{k-1} over all pixels
+};
+constexpr uint32_t kSampleMapMaxRounds = 8;
+// the memset and rounds + 1 launches; d.work is not used, `slots` holds `rounds` slots
+hipError_t launch_sample_map_fill(const DevSampleMap &d, SampleMapFillWork *slots, uint32_t rounds, hipStream_t stream);
 
 // order[] = the n tiles by decreasing cost[] (1 024 buckets of rays per path x 16, tile index within a bucket): one block,
 // stream-ordered (pt_kernel.hip "tile order").  A tile has 64 x samples paths.

@@ -1230,14 +1230,16 @@ class Renderer:  # renderer.rs:8-85
         self.last_stats = st.as_dict()
         return hdr, rgba, self.last_stats
 
-    def sample_map(self, variance, hdr=None, albedo=None, min_samples: int = 1, max_samples=None, budget=None, stream=None):
+    def sample_map(self, variance, hdr=None, albedo=None, min_samples: int = 1, max_samples=None, budget=None, stream=None, rounds=None):
         """The sample map of include/mipt.h: a variance plane [V,H,W] or [H,W] float32 -- ``variance_out`` of ``denoise_variance``, or
         ``variance`` of ``temporal`` -- becomes a count plane of the same shape for ``render_adaptive``, every count in
         [min_samples, max_samples] and their mean at most ``budget``.  ``hdr`` [..,3] makes the weight the standard deviation
         relative to the frame's luminance, ``albedo`` [..,3] (only with ``hdr``) demodulates the frame first.  ``max_samples``
         defaults to ``options.samples``, ``budget`` to ``min_samples``.  numpy arrays go through mipt_sample_map on
         ``options.device_id`` and give a uint32 array; contiguous torch tensors through mipt_sample_map_device on ``stream`` (a torch
-        stream, a raw hipStream_t or None = torch's current stream) without blocking and give an int32 tensor (the same bits)."""
+        stream, a raw hipStream_t or None = torch's current stream) without blocking and give an int32 tensor (the same bits).
+        ``rounds`` (1 ... 8; None = the plain map) goes through mipt_sample_map_fill / _device instead: what the clamp at
+        ``max_samples`` cuts off is handed on to the pixels below it, ``rounds`` - 1 times; ``rounds=1`` gives the plain map's counts."""
         torch_in = Scene._is_torch(variance)
         if not torch_in:
             variance = np.asarray(variance)
@@ -1270,7 +1272,9 @@ class Renderer:  # renderer.rs:8-85
                 if a.shape != want:
                     raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
                 p[name] = np.ascontiguousarray(a)
-        opt = L.MiptSampleMapOptions()
+        opt = L.MiptSampleMapOptions() if rounds is None else L.MiptSampleMapFillOptions()
+        if rounds is not None:
+            opt.rounds = rounds
         opt.width, opt.height, opt.n_views = w, h, v
         opt.min_samples = min_samples
         opt.max_samples = self.options.samples if max_samples is None else max_samples
@@ -1283,7 +1287,8 @@ class Renderer:  # renderer.rs:8-85
             for name, a in p.items():
                 setattr(bufs, name, a.data_ptr())
             bufs.counts = counts.data_ptr()
-            workspace = torch.empty((max(int(lib.mipt_sample_map_workspace_bytes(w, h, v)), 16) // 16, 4), dtype=torch.float32, device=dev)
+            need = lib.mipt_sample_map_workspace_bytes(w, h, v) if rounds is None else lib.mipt_sample_map_fill_workspace_bytes(w, h, v, rounds)
+            workspace = torch.empty((max(int(need), 16) // 16, 4), dtype=torch.float32, device=dev)   # an impossible size is the library's to refuse
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
             elif hasattr(stream, "cuda_stream"):
@@ -1292,13 +1297,19 @@ class Renderer:  # renderer.rs:8-85
             s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
             for t in list(p.values()) + [counts, workspace]:
                 t.record_stream(s)
-            L.check(lib.mipt_sample_map_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_device")
+            if rounds is None:
+                L.check(lib.mipt_sample_map_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_device")
+            else:
+                L.check(lib.mipt_sample_map_fill_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_fill_device")
             return counts
         counts = np.zeros(lead, dtype=np.uint32)
         for name, a in p.items():
             setattr(bufs, name, a.ctypes.data)
         bufs.counts = counts.ctypes.data
-        L.check(lib.mipt_sample_map(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_sample_map")
+        if rounds is None:
+            L.check(lib.mipt_sample_map(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_sample_map")
+        else:
+            L.check(lib.mipt_sample_map_fill(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_sample_map_fill")
         return counts
 
     # -- temporal accumulation (include/mipt.h "temporal accumulation") ---------------------------
@@ -1347,7 +1358,8 @@ class Renderer:  # renderer.rs:8-85
         return torch_in, (v, h, w), planes
 
     def temporal(self, hdr, features, cameras, history=None, alpha_min: float = 0.0, max_history: float = 32.0, normal_tol: float = 0.1,
-                 depth_tol: float = 0.1, want_length: bool = False, want_variance: bool = False, stream=None, history_out=None):
+                 depth_tol: float = 0.1, want_length: bool = False, want_variance: bool = False, stream=None, history_out=None,
+                 counts=None, samples_cap=None):
         """The temporal accumulation of include/mipt.h over a frame or a batch of views: ``hdr`` [V,H,W,3] or [H,W,3] float32 is blended
         with the previous frame's ``history`` reprojected through the camera it carries.  ``features``: a dict with ``position``
         [..,3], ``normal`` [..,3], ``depth`` [..] float32 and ``material`` [..] (uint32 arrays / int32 tensors, the same bits) of the
@@ -1357,7 +1369,11 @@ class Renderer:  # renderer.rs:8-85
         tensors through mipt_temporal_device on ``stream`` (a torch stream, a raw hipStream_t or None = torch's current stream)
         without blocking.  ``history_out``: an int32 tensor of mipt_temporal_history_bytes() to write instead of a new one (it must
         not be ``history``).  Returns (out, history, extras): ``out`` of ``hdr``'s kind and shape, the new history (a flat uint32
-        array / int32 tensor in the header's layout) and a dict with ``length`` and ``variance`` [..] where asked for."""
+        array / int32 tensor in the header's layout) and a dict with ``length`` and ``variance`` [..] where asked for.
+        ``counts`` [..] (a uint32 array with arrays, a contiguous int32 tensor with tensors: the plane ``render_adaptive`` was given
+        for this frame) goes through mipt_temporal_counts / _device instead: the history length counts samples, a pixel with n
+        samples is blended in with the weight n, one with 0 is reprojected only, and ``max_history`` is then a number of samples.
+        ``samples_cap`` is that render's cap and defaults to ``options.samples``."""
         torch_in, (v, h, w), p = self._temporal_planes(hdr, features)
         cams = list(cameras.reshape(-1)) if isinstance(cameras, np.ndarray) else ([cameras] if isinstance(cameras, Camera) else list(cameras))
         if len(cams) != v:
@@ -1371,9 +1387,25 @@ class Renderer:  # renderer.rs:8-85
         words = max(int(lib.mipt_temporal_history_bytes(w, h, v)), 16) // 4          # an impossible size is left to the library to refuse
         lead = tuple(p["hdr"].shape[:-1])
         extras = {}
+        if counts is None:
+            if samples_cap is not None:
+                raise ValueError("samples_cap: given only with counts")
+        else:
+            samples_cap = self.options.samples if samples_cap is None else samples_cap
+            if Scene._is_torch(counts) != torch_in:
+                raise ValueError("counts: hdr and counts must both be numpy arrays or both torch tensors")
+            if not torch_in:
+                counts = np.asarray(counts)
+                if counts.dtype != np.uint32:
+                    raise ValueError(f"counts: expected uint32; got {counts.dtype}")
+                counts = np.ascontiguousarray(counts)
+            if tuple(counts.shape) != lead:
+                raise ValueError(f"counts: expected shape {lead}; got {tuple(counts.shape)}")
         if torch_in:
             import torch
             dev = p["hdr"].device
+            if counts is not None and (counts.dtype != torch.int32 or not counts.is_cuda or counts.device != dev or not counts.is_contiguous()):
+                raise ValueError(f"counts: expected a contiguous int32 tensor on hdr's device {dev}")
             for name, t in (("history", history), ("history_out", history_out)):
                 if t is not None and not (Scene._is_torch(t) and t.dtype == torch.int32 and t.is_cuda and t.device == dev and t.is_contiguous()
                                           and t.numel() == words):
@@ -1394,9 +1426,14 @@ class Renderer:  # renderer.rs:8-85
                 stream = stream.cuda_stream
             # the launches are queued, not finished: tell torch's allocator that `stream` still uses these blocks
             s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [out, new] + list(extras.values()) + ([history] if history is not None else []):
+            for t in list(p.values()) + [out, new] + list(extras.values()) + ([history] if history is not None else []) + (
+                    [counts] if counts is not None else []):
                 t.record_stream(s)
-            L.check(lib.mipt_temporal_device(C.byref(opt), L.ptr(table), C.byref(bufs), stream), "mipt_temporal_device")
+            if counts is None:
+                L.check(lib.mipt_temporal_device(C.byref(opt), L.ptr(table), C.byref(bufs), stream), "mipt_temporal_device")
+            else:
+                L.check(lib.mipt_temporal_counts_device(C.byref(opt), L.ptr(table), C.byref(bufs), counts.data_ptr(), samples_cap, stream),
+                        "mipt_temporal_counts_device")
             return out, new, extras
         if history is not None:
             history = np.ascontiguousarray(history)
@@ -1412,7 +1449,11 @@ class Renderer:  # renderer.rs:8-85
             if on:
                 extras[name] = np.zeros(lead, dtype=np.float32)
                 setattr(bufs, name, extras[name].ctypes.data)
-        L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
+        if counts is None:
+            L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
+        else:
+            L.check(lib.mipt_temporal_counts(C.byref(opt), L.ptr(table), C.byref(bufs), counts.ctypes.data, samples_cap, self.options.device_id),
+                    "mipt_temporal_counts")
         return out, new, extras
 
     def render_sequence(self, scene: Scene, cameras_per_frame, denoise: bool = True, motion: bool = False, upsample=None, adaptive=None, **args):
@@ -1443,7 +1484,11 @@ class Renderer:  # renderer.rs:8-85
         as hdr and its albedo, on the same stream, and renders the samples from 1 + f * max_samples on, so that no pixel ever reuses a
         sample number.  The map is used at the same pixel, it is NOT reprojected: a fast camera smears it by its motion, and the
         pixels it misses still get ``min_samples``.  The dict gains ``counts`` (int32 [V,H,W]) and ``variance_out``; ``stats`` is the
-        adaptive launch's.  With ``upsample=k`` all of this happens at (W/k, H/k)."""
+        adaptive launch's.  With ``upsample=k`` all of this happens at (W/k, H/k).  Two optional keys of ``adaptive``:
+        ``blend="counts"`` runs mipt_temporal_counts_device in the temporal step's place, with the plane the frame was rendered
+        with (frame 0: the uniform one) and ``max_samples`` as the cap -- ``max_history`` is passed through unchanged and is then a
+        number of SAMPLES, not of frames; ``rounds=R`` (1 ... 8) makes the map mipt_sample_map_fill_device, which hands on what the
+        clamp at ``max_samples`` cuts off.  With neither key the call sequence is the one above, call for call."""
         import torch
         o = self.options
         if o.backend != RendererBackend.MI355X:
@@ -1451,8 +1496,10 @@ class Renderer:  # renderer.rs:8-85
         if adaptive is not None:
             if denoise != "variance":
                 raise ValueError("render_sequence: adaptive needs denoise=\"variance\": the sample map is made from the filter's variance_out")
-            if not isinstance(adaptive, dict) or sorted(adaptive) != ["budget", "max_samples", "min_samples"]:
-                raise ValueError(f"render_sequence: adaptive must be None or dict(min_samples=, max_samples=, budget=); got {adaptive!r}")
+            if not isinstance(adaptive, dict) or sorted(k for k in adaptive if k not in ("blend", "rounds")) != ["budget", "max_samples", "min_samples"]:
+                raise ValueError(f"render_sequence: adaptive must be None or dict(min_samples=, max_samples=, budget=[, blend=\"counts\"][, rounds=]); got {adaptive!r}")
+            if adaptive.get("blend", "counts") != "counts":
+                raise ValueError(f"render_sequence: adaptive[\"blend\"] must be \"counts\" or absent; got {adaptive['blend']!r}")
         if o.seed_mode != L.SEED_PER_SAMPLE:
             raise ValueError("render_sequence: the renderer's seed_mode must be SEED_PER_SAMPLE; the pixel stream repeats the same noise every frame")
         if motion and (scene.mesh is None or scene._handle is None or not scene._tracks_motion):
@@ -1481,7 +1528,10 @@ class Renderer:  # renderer.rs:8-85
         lib = L.load()
         handle, pair, history, n = None, None, None, None
         capped, counts = None, None
+        by_counts, map_args = False, None
         if adaptive is not None:
+            by_counts = "blend" in adaptive
+            map_args = {k: v for k, v in adaptive.items() if k != "blend"}
             capped = Renderer(RendererOptions(**{**o.__dict__, "samples": adaptive["max_samples"]}))
         for frame, cams in enumerate(cameras_per_frame):
             cams = [cams] if isinstance(cams, (Camera, np.void)) or (isinstance(cams, np.ndarray) and cams.ndim == 0) else list(cams)
@@ -1512,8 +1562,9 @@ class Renderer:  # renderer.rs:8-85
             if motion:
                 prev_position, _ = one.render_motion(scene, cams, device=True, stream=raw, handle=handle)
                 t_features = {**features, "position": prev_position}
+            c_args = dict(counts=counts, samples_cap=adaptive["max_samples"]) if by_counts else {}
             acc, history, extras = self.temporal(noisy, t_features, table, history=history, want_length=True, want_variance=True, stream=raw,
-                                                 history_out=pair[frame & 1], **t_args)
+                                                 history_out=pair[frame & 1], **t_args, **c_args)
             variance_out = None
             if adaptive is not None:
                 out, variance_out = self.denoise_variance(acc, extras["variance"], extras["length"], features["normal"], features["depth"],
@@ -1530,7 +1581,7 @@ class Renderer:  # renderer.rs:8-85
                 result["prev_position"] = prev_position
             if adaptive is not None:
                 result["counts"], result["variance_out"] = counts, variance_out
-                counts = self.sample_map(variance_out, out, features["albedo"], stream=raw, **adaptive)      # the next frame's
+                counts = self.sample_map(variance_out, out, features["albedo"], stream=raw, **map_args)      # the next frame's
             if upsample is not None:
                 result["features_full"], _ = one_full.render_features(scene, cams, self._FULL_FEATURES, device=True, stream=raw, handle=handle)
                 result["out_full"] = self.upsample(out, features, result["features_full"], upsample, stream=raw, **u_args)
