@@ -1,7 +1,8 @@
 // mipt_adaptive.cpp -- the adaptive-sampling entry points of include/mipt.h (mipt_render_adaptive, mipt_render_adaptive_device,
-// mipt_sample_map_workspace_bytes, mipt_sample_map, mipt_sample_map_device and their _fill forms): argument checks, device staging for the host entries, the
-// camera table and the launches of pt_kernel.hip's adaptive kernel and of sample_map.hip.  Host C++ only; every device operation is
-// stream-ordered HIP.
+// mipt_sample_map_workspace_bytes, mipt_sample_map, mipt_sample_map_device and their _fill forms): the render's argument checks, device
+// staging and the launch of pt_kernel.hip's adaptive kernel; the sample map's plane table, the checks of its own options, the frame
+// constants and the launches of sample_map.hip.  The checks every image-space entry makes, the device-entry checks and the host
+// entry's staging are mipt_planes.h's and mipt_host_util.h's.  Host C++ only; every device operation is stream-ordered HIP.
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
@@ -73,15 +74,7 @@ int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views,
     pr.ovf = scene->d_ovf;
 
     // the camera table of a batch launch: one 64-B record per view, copied on the launch stream
-    scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t v = 0; v < n_views; v++) {
-        const MiptCamera &c = cameras[v];
-        for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
-        scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
-    }
-    const size_t cam_bytes = scene->h_cams.size() * sizeof(float4);
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, cam_bytes))) return rc;
-    MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), cam_bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = mipt::upload_camera_table(scene, cameras, n_views, stream))) return rc;
     mipt::DevBatch bt{};
     bt.cams = scene->d_cams;
     bt.view_pixels = opt->width * opt->height;
@@ -104,16 +97,7 @@ int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views,
         },
         hs, ms);
     if (rc && rc != MIPT_ERR_STACK) return rc;
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->kernel_ms = ms;
-        stats->rays = hs.rays; stats->inner_steps = hs.inner_steps; stats->tri_tests = hs.tri_tests;
-        stats->hits = hs.hits; stats->texel_fetches = hs.texel_fetches; stats->stack_overflows = hs.stack_overflows;
-        stats->tex_clamped = hs.tex_clamped; stats->max_stack = hs.max_stack; stats->pixels = hs.pixels;
-        stats->diag[0] = hs.d_iters; stats->diag[1] = hs.d_inner_lanes; stats->diag[2] = hs.d_leaf_lanes;
-        stats->diag[3] = hs.d_iters_inner; stats->diag[4] = hs.d_iters_leaf; stats->diag[5] = hs.d_services;
-        stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
-    }
+    if (stats) mipt::stats_from_device(hs, ms, stats);
     return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the frame and the stats delivered
 }
 
@@ -162,44 +146,34 @@ int render_host(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, c
 // mipt_sample_map*
 // ---------------------------------------------------------------------------------------------------------------------------------
 
-constexpr int kBuffers = 4, kVariance = 0, kHdrBuf = 1, kAlbedo = 2, kCounts = 3;
-struct BufferField { const char *name; uint32_t words; };           // in the order of MiptSampleMapBuffers; every value is 4 bytes
-constexpr BufferField kFields[kBuffers] = {{"variance", 1}, {"hdr", 3}, {"albedo", 3}, {"counts", 1}};
+// in the order of MiptSampleMapBuffers
+constexpr int kBuffers = 4;
+constexpr mipt::Plane kPlanes[kBuffers] = {{"variance", 4, 4, true, mipt::kPlaneIn, -1}, {"hdr", 12, 4, false, mipt::kPlaneIn, -1},
+                                           {"albedo", 12, 4, false, mipt::kPlaneIn, -1}, {"counts", 4, 4, true, mipt::kPlaneOut, -1}};
+static_assert(kBuffers <= mipt::kMaxPlanes, "a PlaneSet holds the table");
 
-void unpack(const MiptSampleMapBuffers *b, const void *p[kBuffers]) { p[0] = b->variance; p[1] = b->hdr; p[2] = b->albedo; p[3] = b->counts; }
-
-// everything that needs no device: on success d holds the sizes and the frame constants T, E and the S == 0 share
-int map_validate(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, mipt::DevSampleMap &d) {
-    if (!opt) return fail(MIPT_ERR_INVALID_ARG, "%s: null opt", who);
-    if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
-    if (!buf->variance) return fail(MIPT_ERR_INVALID_ARG, "%s: null variance", who);
-    if (!buf->counts) return fail(MIPT_ERR_INVALID_ARG, "%s: null counts", who);
+// everything that needs no device: on success d holds the sizes and the frame constants T, E and the S == 0 share, set the caller's planes
+int map_validate(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, mipt::DevSampleMap &d, mipt::PlaneSet &set) {
+    int rc;
+    if ((rc = mipt::not_null(who, opt, "opt")) || (rc = mipt::not_null(who, buf, "buffers"))) return rc;
+    mipt::planes_bind(set, kPlanes, kBuffers, buf);
+    if ((rc = mipt::planes_required(who, set))) return rc;
     if (buf->albedo && !buf->hdr) return fail(MIPT_ERR_INVALID_ARG, "%s: null hdr: albedo is given only with hdr", who);
-    if (opt->width == 0 || opt->height == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: width and height must be greater than 0", who);
-    if (opt->n_views == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: n_views == 0", who);
-    const uint64_t n_pix = mipt::batch_pixels(opt->width, opt->height, opt->n_views);
-    if (n_pix == 0)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: %u views of %ux%u: n_views*width*height must stay below 2^32", who, opt->n_views, opt->width, opt->height);
-    if (opt->flags) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: must be 0", who, opt->flags);
-    for (uint32_t r : opt->reserved)
-        if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
-    for (const void *r : buf->reserved)
-        if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved buffer pointers must be NULL", who);
+    uint64_t n_pix = 0;
+    if ((rc = mipt::frame_nonzero(who, opt->width, opt->height, opt->n_views)) ||
+        (rc = mipt::frame_pixels(who, opt->width, opt->height, opt->n_views, &n_pix)) || (rc = mipt::flags_zero(who, opt->flags)) ||
+        (rc = mipt::reserved_zero(who, opt->reserved, buf->reserved)))
+        return rc;
     if (opt->max_samples < 1 || opt->max_samples > 65535) return fail(MIPT_ERR_INVALID_ARG, "%s: max_samples %u: must be 1 ... 65535", who, opt->max_samples);
     if (opt->min_samples > opt->max_samples)
         return fail(MIPT_ERR_INVALID_ARG, "%s: min_samples %u: must be at most max_samples %u", who, opt->min_samples, opt->max_samples);
     if (!std::isfinite(opt->budget) || !(opt->budget >= (float)opt->min_samples) || !(opt->budget <= (float)opt->max_samples))
         return fail(MIPT_ERR_INVALID_ARG, "%s: budget %g: must be finite and in [min_samples, max_samples] = [%u, %u]", who, (double)opt->budget,
                     opt->min_samples, opt->max_samples);
-    const void *p[kBuffers];
-    unpack(buf, p);
-    for (int i = 0; i < kBuffers; i++)
-        for (int j = i + 1; j < kBuffers; j++)
-            if (p[i] && p[j] && mipt::ranges_overlap(p[i], n_pix * kFields[i].words * 4, p[j], n_pix * kFields[j].words * 4))
-                return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps %s", who, kFields[j].name, kFields[i].name);
+    mipt::planes_size(set, n_pix);
+    if ((rc = mipt::planes_disjoint(who, set))) return rc;
 
     d = mipt::DevSampleMap{};
-    d.variance = buf->variance; d.hdr = buf->hdr; d.albedo = buf->albedo; d.counts = buf->counts;
     d.n_pixels = n_pix;
     d.min_samples = opt->min_samples;
     d.span = opt->max_samples - opt->min_samples;
@@ -211,18 +185,28 @@ int map_validate(const char *who, const MiptSampleMapOptions *opt, const MiptSam
     return MIPT_OK;
 }
 
-// the fill entries' options as the plain map's, for map_validate: the same fields in the same places, `rounds` checked apart
-int fill_options(const char *who, const MiptSampleMapFillOptions *fill, MiptSampleMapOptions &opt) {
-    if (!fill) return fail(MIPT_ERR_INVALID_ARG, "%s: null opt", who);
+// the planes (the caller's, or the host entry's staged copies) and the launch: rounds == 0 = the plain map, whose workspace is one
+// SampleMapWork; otherwise the fill form's `rounds` slots of the same 32 B
+int map_launch(mipt::DevSampleMap &d, const void *const p[], void *workspace, uint32_t rounds, hipStream_t stream) {
+    d.variance = (const float *)p[0]; d.hdr = (const float *)p[1]; d.albedo = (const float *)p[2]; d.counts = (uint32_t *)p[3];
+    d.work = (mipt::SampleMapWork *)workspace;
+    if (rounds) MIPT_HIP(mipt::launch_sample_map_fill(d, (mipt::SampleMapFillWork *)workspace, rounds, stream));
+    else MIPT_HIP(mipt::launch_sample_map(d, stream));
+    return MIPT_OK;
+}
+uint64_t map_workspace_bytes(uint32_t rounds) { return rounds ? sizeof(mipt::SampleMapFillWork) * rounds : sizeof(mipt::SampleMapWork); }
+
+// what the fill entries check before the plain map's checks -- the two structs, `rounds` -- and their options as the plain map's for
+// map_validate: the same fields in the same places
+int fill_args(const char *who, const MiptSampleMapFillOptions *fill, const MiptSampleMapBuffers *buf, MiptSampleMapOptions &opt) {
+    int rc;
+    if ((rc = mipt::not_null(who, fill, "opt")) || (rc = mipt::not_null(who, buf, "buffers"))) return rc;
+    if (fill->rounds < 1 || fill->rounds > mipt::kSampleMapMaxRounds)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: rounds %u: must be 1 ... %u", who, fill->rounds, mipt::kSampleMapMaxRounds);
     opt = MiptSampleMapOptions{};
     opt.width = fill->width; opt.height = fill->height; opt.n_views = fill->n_views; opt.flags = fill->flags;
     opt.min_samples = fill->min_samples; opt.max_samples = fill->max_samples; opt.budget = fill->budget;
     for (int i = 0; i < 8; i++) opt.reserved[i] = fill->reserved[i];
-    return MIPT_OK;
-}
-int fill_rounds(const char *who, const MiptSampleMapFillOptions *fill) {
-    if (fill->rounds < 1 || fill->rounds > mipt::kSampleMapMaxRounds)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: rounds %u: must be 1 ... %u", who, fill->rounds, mipt::kSampleMapMaxRounds);
     return MIPT_OK;
 }
 
@@ -230,80 +214,39 @@ int fill_rounds(const char *who, const MiptSampleMapFillOptions *fill) {
 int map_device(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, uint32_t rounds, void *d_workspace,
                void *hip_stream) {
     mipt::DevSampleMap d;
-    int rc = map_validate(who, opt, buf, d);
+    mipt::PlaneSet set;
+    int rc = map_validate(who, opt, buf, d, set);
     if (rc) return rc;
-    const uint64_t need = rounds ? sizeof(mipt::SampleMapFillWork) * rounds : sizeof(mipt::SampleMapWork);
-    if (!d_workspace) return fail(MIPT_ERR_INVALID_ARG, "%s: null workspace", who);
-    if ((uintptr_t)d_workspace & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: workspace must be 16-byte aligned", who);
-    const void *p[kBuffers];
-    unpack(buf, p);
-    for (int i = 0; i < kBuffers; i++) {
-        if ((uintptr_t)p[i] & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be 4-byte aligned", who, kFields[i].name);
-        if (p[i] && mipt::ranges_overlap(p[i], d.n_pixels * kFields[i].words * 4, d_workspace, need))
-            return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps the workspace", who, kFields[i].name);
-    }
-    int device = -1;
-    if ((rc = mipt::device_buffer_check(who, buf->variance, -1, "variance", "", &device))) return rc;
-    for (int i = 1; i < kBuffers; i++)
-        if (p[i] && (rc = mipt::device_buffer_check(who, p[i], device, kFields[i].name, "variance's device"))) return rc;
-    if ((rc = mipt::device_buffer_check(who, d_workspace, device, "workspace", "variance's device"))) return rc;
-    MIPT_HIP(hipSetDevice(device));
-    if (rounds) {
-        MIPT_HIP(mipt::launch_sample_map_fill(d, (mipt::SampleMapFillWork *)d_workspace, rounds, (hipStream_t)hip_stream));
-        return MIPT_OK;
-    }
-    d.work = (mipt::SampleMapWork *)d_workspace;
-    MIPT_HIP(mipt::launch_sample_map(d, (hipStream_t)hip_stream));
-    return MIPT_OK;
+    const mipt::Workspace ws = {d_workspace, 0, map_workspace_bytes(rounds), nullptr};
+    if ((rc = mipt::device_entry_check(who, set, &ws))) return rc;
+    return map_launch(d, set.ptr, d_workspace, rounds, (hipStream_t)hip_stream);
 }
 
 int map_host(const char *who, const MiptSampleMapOptions *opt, const MiptSampleMapBuffers *buf, uint32_t rounds, int device_id) {
     mipt::DevSampleMap d;
-    const int rc = map_validate(who, opt, buf, d);
-    if (rc) return rc;
-    const hipError_t e = hipSetDevice(device_id);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();                                  // or the next launch of this thread would report this ordinal's error
-        return fail(MIPT_ERR_HIP, "%s: hipSetDevice(device_id = %d) failed: %s", who, device_id, hipGetErrorString(e));
-    }
-    const void *h[kBuffers];
-    unpack(buf, h);
-    mipt::DevPtr<float> dev[kCounts];                             // variance, hdr, albedo
-    mipt::DevPtr<uint32_t> counts;
-    mipt::DevPtr<mipt::SampleMapFillWork> work;                  // one slot is also the plain map's workspace: the same 32 B
-    for (int i = 0; i < kCounts; i++)
-        if (h[i]) {
-            MIPT_HIP(dev[i].alloc(d.n_pixels * kFields[i].words));
-            MIPT_HIP(hipMemcpy(dev[i].get(), h[i], d.n_pixels * kFields[i].words * sizeof(float), hipMemcpyHostToDevice));
-        }
-    MIPT_HIP(counts.alloc(d.n_pixels));
-    MIPT_HIP(work.alloc(rounds ? rounds : 1u));
-    d.variance = dev[kVariance].get(); d.hdr = dev[kHdrBuf].get(); d.albedo = dev[kAlbedo].get();
-    d.counts = counts.get(); d.work = (mipt::SampleMapWork *)work.get();
-    if (rounds) MIPT_HIP(mipt::launch_sample_map_fill(d, work.get(), rounds, nullptr));
-    else MIPT_HIP(mipt::launch_sample_map(d, nullptr));
-    MIPT_HIP(hipMemcpy(buf->counts, counts.get(), d.n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));   // ordered after the passes: blocks until done
-    return MIPT_OK;
+    mipt::PlaneSet set;
+    int rc = map_validate(who, opt, buf, d, set);
+    if (rc || (rc = mipt::select_device(who, device_id))) return rc;
+    mipt::StagedPlanes staged;
+    mipt::DevPtr<unsigned char> workspace;
+    if ((rc = staged.stage(set))) return rc;
+    MIPT_HIP(workspace.alloc(map_workspace_bytes(rounds)));
+    if ((rc = map_launch(d, staged.ptr, workspace.get(), rounds, nullptr))) return rc;
+    return staged.fetch(set);
 }
 
 int fill_host(const MiptSampleMapFillOptions *fill, const MiptSampleMapBuffers *buf, int device_id) {
     const char *who = "mipt_sample_map_fill";
     MiptSampleMapOptions opt;
-    int rc = fill_options(who, fill, opt);
-    if (rc) return rc;
-    if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
-    if ((rc = fill_rounds(who, fill))) return rc;
-    return map_host(who, &opt, buf, fill->rounds, device_id);
+    const int rc = fill_args(who, fill, buf, opt);
+    return rc ? rc : map_host(who, &opt, buf, fill->rounds, device_id);
 }
 
 int fill_device(const MiptSampleMapFillOptions *fill, const MiptSampleMapBuffers *buf, void *d_workspace, void *hip_stream) {
     const char *who = "mipt_sample_map_fill_device";
     MiptSampleMapOptions opt;
-    int rc = fill_options(who, fill, opt);
-    if (rc) return rc;
-    if (!buf) return fail(MIPT_ERR_INVALID_ARG, "%s: null buffers", who);
-    if ((rc = fill_rounds(who, fill))) return rc;
-    return map_device(who, &opt, buf, fill->rounds, d_workspace, hip_stream);
+    const int rc = fill_args(who, fill, buf, opt);
+    return rc ? rc : map_device(who, &opt, buf, fill->rounds, d_workspace, hip_stream);
 }
 
 } // namespace

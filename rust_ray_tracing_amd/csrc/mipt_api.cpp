@@ -668,15 +668,7 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     // the batch's camera table: one 64-B record per view {look_at column 0, 1, 2, position}, copied on the launch stream
     mipt::DevBatch bt{};
     if (batch) {
-        scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (uint32_t v = 0; v < n_views; v++) {
-            const MiptCamera &c = cameras[v];
-            for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
-            scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
-        }
-        const size_t bytes = scene->h_cams.size() * sizeof(float4);
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, bytes))) return rc;
-        MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
+        if ((rc = mipt::upload_camera_table(scene, cameras, n_views, stream))) return rc;
         bt.cams = scene->d_cams;
         bt.view_pixels = opt->width * opt->height;
         bt.tiles_recip = 0xffffffffu / pr.n_local_tiles;
@@ -708,14 +700,7 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         hs, ms);
     if (rc && rc != MIPT_ERR_STACK) return rc;
     if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->kernel_ms = ms;
-        stats->rays = hs.rays; stats->inner_steps = hs.inner_steps; stats->tri_tests = hs.tri_tests;
-        stats->hits = hs.hits; stats->texel_fetches = hs.texel_fetches; stats->stack_overflows = hs.stack_overflows;
-        stats->tex_clamped = hs.tex_clamped; stats->max_stack = hs.max_stack; stats->pixels = hs.pixels;
-        stats->diag[0] = hs.d_iters; stats->diag[1] = hs.d_inner_lanes; stats->diag[2] = hs.d_leaf_lanes;
-        stats->diag[3] = hs.d_iters_inner; stats->diag[4] = hs.d_iters_leaf; stats->diag[5] = hs.d_services;
-        stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
+        mipt::stats_from_device(hs, ms, stats);
         stats->touched_lines[0] = hs.touched_geom; stats->touched_lines[1] = hs.touched_attr;
     }
     return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the frame and the stats delivered

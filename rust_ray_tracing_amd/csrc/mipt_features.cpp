@@ -79,15 +79,7 @@ int mipt::first_hit_setup(MiptScene *scene, const MiptCamera *cameras, uint32_t 
     if (rc) return rc;
     f.ovf = scene->d_ovf;
 
-    scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t v = 0; v < n_views; v++) {
-        const MiptCamera &c = cameras[v];
-        for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
-        scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
-    }
-    const size_t cam_bytes = scene->h_cams.size() * sizeof(float4);
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, cam_bytes))) return rc;
-    MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), cam_bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = mipt::upload_camera_table(scene, cameras, n_views, stream))) return rc;
     f.cams = scene->d_cams;
     *grid_out = grid;
     return MIPT_OK;

@@ -1,9 +1,10 @@
 // mipt_host_util.h -- the host plumbing every translation unit of libmipt.so shares and that needs HIP types: the HIP-call macro,
-// the owners of device memory, pinned memory, streams and events, the scope guards and the grow-on-demand device buffer.  Internal;
-// mipt_scene.h includes it.  What needs no HIP type -- mipt::fail, the MIPT_NO_THROW fence, mipt::Owned -- is in mipt_internal.h,
-// which the CPU builds of tests/cpp/ include.
+// the owners of device memory, pinned memory, streams and events, the scope guards, the grow-on-demand device buffer and, at the
+// end, the device half of an image-space entry: its device-entry checks and the staging of its host entry.  Internal; mipt_scene.h
+// includes it.  What needs no HIP type -- mipt::fail, the MIPT_NO_THROW fence, mipt::Owned in mipt_internal.h, the plane description
+// and its checks in mipt_planes.h -- is what the CPU builds of tests/cpp/ include.
 #pragma once
-#include "mipt_internal.h"
+#include "mipt_planes.h"                                         // and with it mipt_internal.h
 
 #include <hip/hip_runtime.h>
 
@@ -72,21 +73,6 @@ inline int grow_device_buffer(void **p, size_t *have, size_t want_bytes) {
     return MIPT_OK;
 }
 
-// n_views * width * height for the entries that take planes of n_views frames (denoise, temporal); 0 = an invalid size: a zero, or
-// not below MIPT_BATCH_MAX_PIXELS
-inline uint64_t batch_pixels(uint32_t width, uint32_t height, uint32_t n_views) {
-    if (width == 0 || height == 0 || n_views == 0) return 0;
-    const uint64_t wh = (uint64_t)width * height;                            // < 2^64
-    if (wh >= MIPT_BATCH_MAX_PIXELS || wh * n_views >= MIPT_BATCH_MAX_PIXELS) return 0;
-    return wh * n_views;
-}
-
-// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
-inline bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // MIPT_OK if `p` is device memory of HIP device `device`, else MIPT_ERR_INVALID_ARG with "<who>: <name> is not device memory of
 // <whose> <device>".  device < 0: of any device.  *found (may be NULL) receives the device `p` lives on.
 inline int device_buffer_check(const char *who, const void *p, int device, const char *name, const char *whose = "the scene's device",
@@ -102,5 +88,68 @@ inline int device_buffer_check(const char *who, const void *p, int device, const
     if (found) *found = a.device;
     return MIPT_OK;
 }
+
+// ---- the device half of an image-space entry (mipt_planes.h has the plane description and what needs no device) ----
+// The workspace a device entry is handed.  `need` bytes of it are used; sizer: the entry's *_workspace_bytes function, which the
+// caller is told of when `bytes` is less (null: the entry is not given a size).
+struct Workspace { const void *p; uint64_t bytes, need; const char *sizer; };
+
+// What a device entry checks after mipt_planes.h's: the workspace (if the entry takes one) is there, large enough and 16-byte
+// aligned, every plane is aligned and apart from it, and all of it is memory of one device -- the first plane's, which becomes the
+// current device.
+inline int device_entry_check(const char *who, const PlaneSet &set, const Workspace *ws) {
+    if (ws) {
+        if (!ws->p) return fail(MIPT_ERR_INVALID_ARG, "%s: null workspace", who);
+        if (ws->sizer && ws->bytes < ws->need)
+            return fail(MIPT_ERR_INVALID_ARG, "%s: workspace of %llu bytes is too small: %s() is %llu", who, (unsigned long long)ws->bytes, ws->sizer,
+                        (unsigned long long)ws->need);
+        if ((uintptr_t)ws->p & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: workspace must be 16-byte aligned", who);
+    }
+    int rc, device = -1;
+    for (int i = 0; i < set.n; i++) {
+        if ((rc = plane_aligned(who, set, i))) return rc;
+        if (ws && set.ptr[i] && ranges_overlap(set.ptr[i], set.bytes[i], ws->p, ws->need))
+            return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps the workspace", who, set.plane[i].name);
+    }
+    if ((rc = device_buffer_check(who, set.ptr[0], -1, set.plane[0].name, "", &device))) return rc;
+    const std::string whose = std::string(set.plane[0].name) + "'s device";
+    for (int i = 1; i < set.n; i++)
+        if (set.ptr[i] && (rc = device_buffer_check(who, set.ptr[i], device, set.plane[i].name, whose.c_str()))) return rc;
+    if (ws && (rc = device_buffer_check(who, ws->p, device, "workspace", whose.c_str()))) return rc;
+    MIPT_HIP(hipSetDevice(device));
+    return MIPT_OK;
+}
+
+// the device a host entry was asked for becomes the current one
+inline int select_device(const char *who, int device_id) {
+    const hipError_t e = hipSetDevice(device_id);
+    if (e == hipSuccess) return MIPT_OK;
+    (void)hipGetLastError();                                      // or the next launch of this thread would report this ordinal's error
+    return fail(MIPT_ERR_HIP, "%s: hipSetDevice(device_id = %d) failed: %s", who, device_id, hipGetErrorString(e));
+}
+
+// The planes of a host entry in memory of the current device, freed when it goes out of scope.  stage(): every given plane gets its
+// bytes and the inputs are copied in; an output that may go over an input (Plane::over) gets none and is that input's copy.  ptr[] is
+// then what PlaneSet::ptr is for a device entry.  fetch(), after the launches on the null stream: the outputs back to the caller's
+// planes; each copy blocks until the launches are done.
+struct StagedPlanes {
+    DevPtr<unsigned char> mem[kMaxPlanes];
+    void *ptr[kMaxPlanes] = {};
+
+    int stage(const PlaneSet &set) {
+        for (int i = 0; i < set.n; i++) {
+            if (!set.ptr[i] || set.plane[i].over >= 0) continue;
+            MIPT_HIP(mem[i].alloc(set.bytes[i]));
+            if (set.plane[i].use == kPlaneIn) MIPT_HIP(hipMemcpy(mem[i].get(), set.ptr[i], set.bytes[i], hipMemcpyHostToDevice));
+        }
+        for (int i = 0; i < set.n; i++) ptr[i] = mem[set.plane[i].over >= 0 ? set.plane[i].over : i].get();
+        return MIPT_OK;
+    }
+    int fetch(const PlaneSet &set) const {
+        for (int i = 0; i < set.n; i++)
+            if (set.ptr[i] && set.plane[i].use == kPlaneOut) MIPT_HIP(hipMemcpy((void *)set.ptr[i], ptr[i], set.bytes[i], hipMemcpyDeviceToHost));
+        return MIPT_OK;
+    }
+};
 
 } // namespace mipt

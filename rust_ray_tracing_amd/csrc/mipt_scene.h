@@ -200,6 +200,34 @@ int traversal_launch(MiptScene *scene, hipStream_t stream, Launch launch, After 
     return MIPT_OK;
 }
 
+// The camera table of a launch over `n_views` views: one 64-B record per view {look_at column 0, 1, 2, position} in scene->h_cams,
+// scene->d_cams grown to hold it and the copy queued on `stream` (the current device is the scene's).
+inline int upload_camera_table(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, hipStream_t stream) {
+    scene->h_cams.assign((size_t)n_views * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t v = 0; v < n_views; v++) {
+        const MiptCamera &c = cameras[v];
+        for (int col = 0; col < 3; col++) scene->h_cams[(size_t)v * 4 + col] = make_float4(c.look_at[col][0], c.look_at[col][1], c.look_at[col][2], 0.0f);
+        scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
+    }
+    const size_t bytes = scene->h_cams.size() * sizeof(float4);
+    const int rc = grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, bytes);
+    if (rc) return rc;
+    MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
+    return MIPT_OK;
+}
+
+// *stats = the counters of a trace launch and its kernel time; every other field 0 (touched_lines: mipt_api.cpp adds them)
+inline void stats_from_device(const DevStats &hs, float kernel_ms, MiptStats *stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->rays = hs.rays; stats->inner_steps = hs.inner_steps; stats->tri_tests = hs.tri_tests;
+    stats->hits = hs.hits; stats->texel_fetches = hs.texel_fetches; stats->stack_overflows = hs.stack_overflows;
+    stats->tex_clamped = hs.tex_clamped; stats->max_stack = hs.max_stack; stats->pixels = hs.pixels;
+    stats->diag[0] = hs.d_iters; stats->diag[1] = hs.d_inner_lanes; stats->diag[2] = hs.d_leaf_lanes;
+    stats->diag[3] = hs.d_iters_inner; stats->diag[4] = hs.d_iters_leaf; stats->diag[5] = hs.d_services;
+    stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
+}
+
 // ---- the first-hit passes (mipt_features.cpp: the feature buffers; mipt_motion.cpp: previous positions) ----
 // the checks that concern neither the buffers nor a device; `buffers` is only tested for null.  count_allowed: MIPT_FLAG_COUNT passes
 int first_hit_check(const char *who, const MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, const MiptOptions *opt,

@@ -121,6 +121,18 @@ def test_owned_guard_under_asan_ubsan(tmp_path):
     assert "owned_guard ok" in out.stdout
 
 
+def test_plane_checks_under_asan_ubsan(tmp_path):
+    """The device-free argument checks of the image-space entries (csrc/mipt_planes.h) over plane sets of zero, one and the most
+    planes, absent optional planes, touching and overlapping ranges, the allowed alias, ranges at the top of the address space and
+    inverse_square at the edges of f32 (tests/cpp/plane_checks.cpp): no HIP, no libmipt.so, every result held to a written value."""
+    exe = str(tmp_path / "plane_checks")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "plane_checks.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    assert "plane_checks ok" in out.stdout
+
+
 def test_oracle_under_asan_ubsan(built, tmp_path):
     """The oracle itself (test infrastructure) under ASan/UBSan: a small render through a standalone driver."""
     drv = tmp_path / "drv.c"
