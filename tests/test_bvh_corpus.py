@@ -6,7 +6,11 @@
    k = 1, with n - k = 1 and with an even split, every class as a leaf that is not the root, roots at every class and chunk edge, child
    counts on and next to a chunk edge, a tree taller than two renumbering runs, a wide level between runs, nodes with a single usable
    axis, planes deciding on axis 1 and on axis 2.  These are conditions on the INPUTS: a generator edited so that a case is lost fails
-   here, on the CPU, before tests/test_gpu_bvh_corpus.py would silently check less."""
+   here, on the CPU, before tests/test_gpu_bvh_corpus.py would silently check less.
+3. The LARGE entries (574 674 to 3.4 M triangles, past the caps of the device builder's and the layout's launches) have the HOST
+   builder as their reference on the GPU, because the oracle takes 23 s and more for one of them.  Here the host builder is held to
+   the oracle on the smallest, to itself with one thread on two more, and the census of the host trees meets the conditions each
+   entry exists for."""
 import os
 import sys
 
@@ -168,3 +172,92 @@ def test_census_axes(corpus):
     assert "bunch300_y" in one_axis
     assert "chain_y" in axis1 and "chain_z" in axis2, (axis1, axis2)
     assert "bunch300_yz" in axis1 or "bunch300_yz" in axis2
+
+
+# ---- the LARGE entries: the host builder as the GPU file's reference, and what its trees reach ----------------------------------------
+LARGE = list(bc.LARGE)
+
+
+def test_large_host_builder_matches_oracle(rrt, orc):
+    """The host builder equals the oracle on `large_soup`, 574 674 triangles.  One entry only: the oracle's build of it takes about
+    23 s, and 40 s and more for each of the other three, which are therefore held to the host builder with one thread instead
+    (below) -- the single-threaded build is the plain recursion, the default one hands subtrees to threads."""
+    tris, ref_tris, ref_nodes = bc.reference(orc, "large_soup")
+    _, host_tris, host_nodes = bc.reference_host(rrt, "large_soup")
+    _assert_same(host_tris, host_nodes, ref_tris, ref_nodes, "large_soup")
+
+
+@pytest.mark.parametrize("name", ["large_halves", "large_edge"])
+def test_large_host_builder_one_thread(rrt, name):
+    tris, ref_tris, ref_nodes = bc.reference_host(rrt, name)
+    _assert_same(*_host(rrt, tris, 1), ref_tris, ref_nodes, f"{name}, 1 thread against the default")
+
+
+def test_large_positions(rrt):
+    """what test_subsets_name_corpus_entries asks of a resident scene's input"""
+    assert set(bc.LARGE_REBUILD) <= set(bc.LARGE_RESIDENT) <= set(bc.LARGE) and not set(bc.LARGE) & set(bc.ENTRIES)
+    for name in LARGE + ["late_leaf"]:
+        p = bc.reference_host(rrt, name)[0]["vertices"]["position"]
+        assert np.isfinite(p).all() and np.abs(p).max() < 2.0 ** 40, name
+
+
+def test_late_leaf(rrt, orc):
+    """`late_leaf`, for check_nodes' second trip: host builder == oracle (140 053 triangles), and the one leaf above four triangles
+    is a node past the first trip of that grid."""
+    tris, ref_tris, ref_nodes = bc.reference(orc, "late_leaf")
+    _, host_tris, host_nodes = bc.reference_host(rrt, "late_leaf")
+    _assert_same(host_tris, host_nodes, ref_tris, ref_nodes, "late_leaf")
+    lv = bc.census_host(rrt, "late_leaf")["leaves"]
+    above = lv[lv[:, 1] > bc.SUB_MAX]
+    assert len(above) == 1 and above[0, 1] == bc.LATE_LEAF and above[0, 0] >= bc.GRID_1024, above
+
+
+@pytest.fixture(scope="module")
+def large(rrt):
+    """name -> census of the HOST builder's tree"""
+    return {name: bc.census_host(rrt, name) for name in LARGE}
+
+
+def _chunks(n):
+    return -(-int(n) // bc.CHUNK)
+
+
+def _lone_pairs(rrt, nodes):
+    """A lower bound of the number of mate-less pair records (what append_lone copies) in the host restatement of the record order:
+    they are the order's tail, every one a pair of two leaves, and they start on an even record."""
+    import ctypes as C
+    nodes = np.ascontiguousarray(nodes)
+    out = np.zeros(len(nodes) + 1, dtype=np.uint32)
+    n = C.c_uint32(0)
+    assert rrt.load_diag().mipt_internal_pair_order(nodes.ctypes.data, len(nodes), out.ctypes.data, out.size, C.byref(n)) == 0
+    order = out[: n.value]
+    pad = order == 0xffffffff
+    k = np.where(pad, 0, order).astype(np.int64)
+    two_leaves = (nodes["num_tris"][2 * k + 1] > 0) & (nodes["num_tris"][2 * k + 2] > 0) & ~pad
+    other = np.flatnonzero(~two_leaves)
+    start = int(other[-1]) + 1 if len(other) else 0
+    return len(order) - (start + (start & 1))
+
+
+def test_large_census(rrt, large):
+    """Conditions on the inputs, by the launch they are for.  Not measurements: an edited generator fails here."""
+    for name in LARGE:                                          # make_proxies, extract_order, gather_tris, check_nodes; the scans over triangles and pairs
+        c = large[name]
+        assert c["count"][0] > bc.GRID_2048 and len(c["count"]) > bc.GRID_1024 and len(c["inner"]) > bc.SCAN_ONE_TRIP, name
+    c = large["large_soup"]                                     # big_scan: one node of more than a step; write_new_of, write_pairs
+    assert _chunks(c["count"][0]) >= bc.BIG_SCAN_STEP + 1
+    assert len(c["inner"]) > bc.GRID_2048
+    c = large["large_halves"]                                   # big_scan: three steps, and two nodes of two steps side by side; write_tris
+    assert _chunks(c["count"][0]) >= 2 * bc.BIG_SCAN_STEP + 1
+    assert _chunks(c["count"][1]) >= bc.BIG_SCAN_STEP + 1 and _chunks(c["count"][2]) >= bc.BIG_SCAN_STEP + 1
+    assert c["depth"][1] == 1 and c["depth"][2] == 1
+    assert c["count"][0] > bc.GRID_4096
+    assert np.bincount(c["depth"][c["inner"][:, 0]]).max() > bc.SCAN_ONE_TRIP      # the scan over one level's pairs loops too
+    c = large["large_edge"]                                     # big_scan: k on the step edge
+    assert c["count"][0] == 2 ** 20 + 1 and _chunks(c["count"][0]) == 2 * bc.BIG_SCAN_STEP + 1
+    assert tuple(c["inner"][0]) == (0, bc.BIG_SCAN_STEP * bc.CHUNK, bc.BIG_SCAN_STEP * bc.CHUNK + 1)
+    c = large["large_clusters"]                                 # big_setup's second strip; sizes_level, bases_level; append_lone
+    big = np.bincount(c["depth"][c["count"] > bc.CLASS_EDGES[-1]])
+    assert big.max() >= bc.BIG_SETUP_STRIP + 1 + 64, big        # with room: a few clusters may split otherwise after an edit
+    assert c["build_widths"].max() > bc.GRID_2048
+    assert _lone_pairs(rrt, bc.reference_host(rrt, "large_clusters")[2]) > bc.GRID_1024

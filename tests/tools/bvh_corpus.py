@@ -325,9 +325,49 @@ RESIDENT = tuple(f"bunch{m}" for m in (6, 12, 24, 48, 100, 300, 1000, 3000)) + (
 REBUILD = ("spiral", "chunk_8192_of_16384", "bunch300")
 
 
+# ---- past the caps --------------------------------------------------------------------------------------------------------------------
+# Four entries whose trees take the loops of the device builder and of the layout kernels (csrc/scene_device.hip) on their second
+# trip: grid-stride loops over capped grids, big_scan's steps of BIG_SCAN_STEP chunks, big_setup's strips of BIG_SETUP_STRIP nodes.
+# The oracle needs 23 s and more for one of them, so their reference is the host builder (`reference_host`), which
+# tests/test_bvh_corpus.py holds to the oracle on the smallest and to itself with one thread on the others; the same file asserts on
+# the host trees that every entry reaches what it is here for (DESIGN section 21 names the launch each one passes).
+BIG_SCAN_STEP = 64                                  # chunks of a BIG node that big_scan takes per step, with the prefix carried on
+BIG_SETUP_STRIP = 1024                              # BIG nodes of one level that big_setup takes per strip, with the chunk count carried on
+GRID_2048 = 2048 * 256                              # threads of make_proxies, extract_order, sizes_level, bases_level, write_new_of, write_pairs
+GRID_4096 = 4096 * 256                              # ... of write_tris (gather_tris: seven 16-byte pieces per triangle over as many)
+GRID_1024 = 1024 * 256                              # ... of check_nodes, append_lone
+SCAN_ONE_TRIP = 512 * 256                           # the layout's scans (kScanGrid workgroups of 256): up to this many elements every workgroup
+                                                    # takes one tile; past it the workgroups loop and carry their prefix from tile to tile
+LARGE_CLUSTERS = 1600                               # clusters of 2 049 in `large_clusters`
+
+LARGE = {
+    "large_soup": (at_size, (70 * CHUNK + 1234, 0)),                         # a root of 71 chunks; more pair records than GRID_2048
+    "large_halves": (clusters, ((66 * CHUNK + 5, 65 * CHUNK - 3),)),          # a root of 132 chunks over two children past BIG_SCAN_STEP
+    "large_edge": (clusters, ((64 * CHUNK, 64 * CHUNK + 1),)),                # 2^20 + 1 triangles; the root's k lies on big_scan's step edge
+    "large_clusters": (clusters, ((2049,) * LARGE_CLUSTERS,)),                # more BIG nodes in a level than BIG_SETUP_STRIP
+}
+LATE_LEAF = 48                                      # triangles of the one large leaf of `late_leaf`
+
+
+def late_leaf(n=140000, m=LATE_LEAF, seed=0):
+    """A plain soup of n triangles around x = -50 000 and, where `bunch` puts them, m triangles no builder may split plus 5 lone ones.
+    Every plane of the root falls between the two groups, so the soup is the root's left child and fills the node array up to about
+    2 n; the leaf of m comes behind it, past the GRID_1024 nodes that check_nodes' grid takes in its first trip, and every leaf before
+    it holds at most four triangles: the largest leaf is found in the second trip or not at all."""
+    rng = np.random.default_rng([seed, n, m])
+    p = soup(rng, n)
+    p[:, :, 0] -= 50000.0
+    p = np.concatenate([p.astype(np.float32), bunch(m, seed=seed)])
+    return p[rng.permutation(len(p))]
+
+
+LARGE_RESIDENT = ("large_soup", "large_halves", "large_clusters")            # through the resident setup, tree and layout
+LARGE_REBUILD = ("large_soup",)
+
+
 def make(name):
-    """The corpus entry `name` as TRIANGLE records in input order."""
-    fn, args = ENTRIES[name]
+    """The corpus entry `name` (of ENTRIES or LARGE, or "late_leaf") as TRIANGLE records in input order."""
+    fn, args = (late_leaf, ()) if name == "late_leaf" else ENTRIES[name] if name in ENTRIES else LARGE[name]
     return triangles(fn(*args))
 
 
@@ -343,6 +383,37 @@ def reference(orc, name):
             a.setflags(write=False)
         _reference[name] = (tris, ref_tris, ref_nodes)
     return _reference[name]
+
+
+_reference_host = {}
+reference_host_seconds = {}                         # name -> (generation, host build): what the first test to ask for an entry paid
+
+
+def reference_host(rrt, name):
+    """(input triangles, the HOST builder's reordered triangles, its node array) of entry `name`, with the default thread count; built
+    once, never changed.  The reference of the LARGE entries, for which the oracle is too slow."""
+    if name not in _reference_host:
+        import time
+        t0 = time.perf_counter()
+        tris = make(name)
+        t1 = time.perf_counter()
+        sc = rrt.Scene.from_arrays(tris, [rrt.material_default()])
+        reference_host_seconds[name] = (t1 - t0, time.perf_counter() - t1)
+        out = (tris, sc.tris, sc.bvh_nodes)
+        for a in out:
+            a.setflags(write=False)
+        _reference_host[name] = out
+    return _reference_host[name]
+
+
+_census_host = {}
+
+
+def census_host(rrt, name):
+    """The census of `reference_host`'s tree: a Python loop over the nodes (seconds at these sizes), so made once per entry."""
+    if name not in _census_host:
+        _census_host[name] = census(reference_host(rrt, name)[2])
+    return _census_host[name]
 
 
 def first_difference(nodes, ref_nodes):
