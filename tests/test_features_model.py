@@ -93,6 +93,36 @@ def test_model_mean_over_samples(rrt, orc):
     assert all(F.same_bits(first[k], one[k]) for k in F.NAMES)                       # sample_begin 0 is sample 1
 
 
+@pytest.mark.parametrize("arm", [(False, 0.0), (True, 0.0078125)], ids=["ref", "cullsafe"])
+def test_batch_cameras_refill_waves_that_are_mid_traversal(rrt, orc, arm):
+    """What makes tests/test_gpu_features.py::test_more_views_than_the_launch_holds_lanes reach first_hit_kernel's partial refill: the
+    views of its four cameras hold sky pixels, over after the root's step, and hits of sixteen steps or more in the same tiles, and
+    the kernel's scheduling rule (query_model.wave_refills at ray_query.hip's ratio 1/4, which first_hit.hip restates) fed their step
+    counts in work-item order -- view, tile, pixel of the tile, the ragged edge skipped -- then hands a wave new pixels while other
+    lanes are mid-traversal: with the wave alone on the queue, and with blocks at seeded random bases."""
+    sc = _scene(rrt, "helmet")
+    w, h = 61, 37                                                     # test_gpu_features.py SIZES[0]
+    cams = F.batch_cameras(rrt, sc.camera)
+    steps = [F.pixel_steps(orc, sc, c.uniform, w, h, 0, cull=arm[0], margin=arm[1]) for c in cams]
+    for s in steps:
+        assert s.min() >= 1 and (s <= Q.SHORT_MAX_STEPS).sum() > w * h // 8 and (s >= Q.LONG_MIN_STEPS).sum() > w * h // 20
+        tiles = F.work_order_steps([s]).reshape(-1, 64)
+        mixed = ((tiles >= Q.LONG_MIN_STEPS).any(axis=1) & ((tiles > 0) & (tiles <= Q.SHORT_MAX_STEPS)).any(axis=1)).sum()
+        assert mixed >= 1, mixed                                      # a silhouette tile in every view
+    cycle = F.batch_cycle(2 * len(cams))
+    assert all(cycle[i] != cycle[i + 1] for i in range(len(cycle) - 1)) and set(cycle) == set(range(len(cams)))
+    order = F.work_order_steps([steps[c] for c in cycle])
+    assert len(order) == len(cycle) * 40 * 64 and (order == 0).sum() == len(cycle) * (40 * 64 - w * h)
+    alone = Q.wave_refills(order, None, skips=True)
+    assert alone > 0, "no refill into a partly busy wave with sequential bases"
+    bases = np.random.default_rng(23).integers(0, len(order) - 64, 48)
+    scattered = Q.wave_refills(order, bases, skips=True)
+    assert scattered > 0, "no refill into a partly busy wave with random bases"
+    # the rule without skips is the query kernel's own: an order with none gives the same count either way
+    dense = order[order > 0]
+    assert Q.wave_refills(dense, None) == Q.wave_refills(dense, None, skips=True)
+
+
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------
 def test_feature_symbols_and_struct_size(rrt):
     from rust_ray_tracing_amd import _lib as L

@@ -4,12 +4,13 @@ samples = n; a pixel with 0 is not traced, holds +0 and is not counted.  The ref
 per pixel -- existing code, held to the oracle elsewhere -- and, once, the oracle itself."""
 import ctypes as C
 import functools
+import time
 
 import numpy as np
 import pytest
 
 from test_gpu_batch import CONFIGS as BATCH_CONFIGS
-from test_gpu_batch import COUNTERS, _poses, _same, _scene, _table
+from test_gpu_batch import COUNTERS, LT, _poses, _same, _scene, _table
 
 pytestmark = pytest.mark.gpu
 
@@ -213,6 +214,143 @@ def test_more_pixels_than_resident_lanes(rrt):
         want[0][counts[0] == n] = ref[counts[0] == n]
     assert _same(hdr, want)
     assert st.pixels == int(np.count_nonzero(counts))
+
+
+# ---- launches larger than the lanes in flight, with lanes that move from view to view ------------------------------------------------
+# The test above passes the lanes in flight by 6 % with one view.  These cross the two thresholds of tests/tools/launch_thresholds.py
+# (MID: lanes refill, leaf_period 1; FULL: leaf_period 4, a quarter of the work in flight, a ragged tail) with hundreds to thousands
+# of views of the file's W x H frame, three distinct cameras cycled with stride 2 from camera 1, so that a lane's next pixel has another
+# view, another camera and another row of the count plane.
+BIG_CAMERAS, BIG_LEVELS = 3, (1, 2, 3, 4, 5)
+
+
+@functools.lru_cache(maxsize=None)
+def _big_reference(config, seed_mode):
+    """mipt_render of each of the three cameras at samples = 1 ... CAP -> (hdr [3, CAP + 1, H, W, 3] with zeros at level 0, rgba8
+    [3, CAP + 1, H, W, 4] with opaque black at level 0, counters {(camera, level): dict} of the counting twin, whose frames are checked
+    to be the product build's); computed once per configuration and left unchanged"""
+    import rust_ray_tracing_amd as rrt
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, cam = _scene("cornell")
+    hnd = sc.upload(0)
+    cams = _poses(rrt, cam, BIG_CAMERAS + 1, 0.8, 91)[:BIG_CAMERAS]         # the scene's own and two seeded poses, all distinct
+    hdr = np.zeros((BIG_CAMERAS, CAP + 1, H, W, 3), dtype=np.float32)
+    px = np.zeros((BIG_CAMERAS, CAP + 1, H, W, 4), dtype=np.uint8)
+    px[:, 0, ..., 3] = 255
+    stats = {}
+    for c, camera in enumerate(cams):
+        for n in BIG_LEVELS:
+            o = _options(rrt, config, seed_mode, samples=n)
+            L.check(lib.mipt_render(hnd, L.ptr(camera.uniform), C.byref(o), L.ptr(hdr[c, n]), L.ptr(px[c, n]), None), "mipt_render")
+            oc = _options(rrt, config, seed_mode, samples=n, flags=L.FLAG_COUNT)
+            twin, st = np.zeros((H, W, 3), dtype=np.float32), L.MiptStats()
+            L.check(lib.mipt_render(hnd, L.ptr(camera.uniform), C.byref(oc), L.ptr(twin), None, C.byref(st)), "mipt_render")
+            assert _same(twin, hdr[c, n]), (c, n)
+            stats[c, n] = st.as_dict()
+    assert not _same(hdr[0, 1], hdr[1, 1]) and not _same(hdr[1, 1], hdr[2, 1]) and not _same(hdr[0, 1], hdr[2, 1])
+    hdr.setflags(write=False); px.setflags(write=False)
+    return cams, hdr, px, stats
+
+
+def _big_counts(n_views, seed):
+    """[n_views, H, W] seeded from {0, 1, 2, 3, 4, 5, 9} (9 is clamped to CAP); in a seeded fifth of all (view, tile) pairs the whole
+    8x8 tile is zero, in another fifth zero pixels and full ones alternate: fetches that skip fall in every part of the queue"""
+    rng = np.random.default_rng(seed)
+    c = rng.choice(np.array([0, 1, 2, 3, 4, 5, 9], dtype=np.uint32), size=(n_views, H, W))
+    ty, tx = (H + 7) // 8, (W + 7) // 8
+    kind = rng.integers(0, 5, size=(n_views, ty, tx))
+    kind_px = np.repeat(np.repeat(kind, 8, axis=1), 8, axis=2)[:, :H, :W]
+    yy, xx = np.mgrid[0:H, 0:W]
+    checker = np.where((yy + xx) % 2 == 0, 0, 9).astype(np.uint32)
+    c = np.where(kind_px == 0, 0, np.where(kind_px == 1, checker[None], c))
+    c[0, 0, 0], c[-1, -1, -1] = 5, 0
+    return np.ascontiguousarray(c, dtype=np.uint32)
+
+
+def _run_big_adaptive(lib, hnd, table, n, o, counts, device, prefill_bits):
+    """one call; the frame starts as `prefill_bits` in every word and ends in canary words -> (hdr, rgba8, stats dict, seconds)"""
+    from rust_ray_tracing_amd import _lib as L
+    st = L.MiptStats()
+    n_f, n_b, tail = n * H * W * 3, n * H * W * 4, 64
+    if device:
+        import torch
+        d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
+        d_hdr = torch.full((n_f + tail,), prefill_bits, dtype=torch.int32, device="cuda")
+        d_hdr[n_f:] = 0x4640E400
+        d_px = torch.full((n_b + tail,), 0x5A, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = lib.mipt_render_adaptive_device(hnd, L.ptr(table), n, C.byref(o), d_counts.data_ptr(), d_hdr.data_ptr(), d_px.data_ptr(), None, C.byref(st))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        hdr, px = d_hdr.cpu().numpy().view(np.uint32), d_px.cpu().numpy()
+    else:
+        hdr = np.full(n_f + tail, prefill_bits, dtype=np.uint32)
+        hdr[n_f:] = 0x4640E400
+        px = np.full(n_b + tail, 0x5A, dtype=np.uint8)
+        t0 = time.perf_counter()
+        rc = lib.mipt_render_adaptive(hnd, L.ptr(table), n, C.byref(o), L.ptr(counts), L.ptr(hdr), L.ptr(px), C.byref(st))
+        dt = time.perf_counter() - t0
+    assert rc == 0, lib.mipt_last_error()
+    assert np.all(hdr[n_f:] == 0x4640E400) and np.all(px[n_b:] == 0x5A), "written behind the last view"
+    return hdr[:n_f].view(np.float32).reshape(n, H, W, 3), px[:n_b].reshape(n, H, W, 4), st.as_dict(), dt
+
+
+@pytest.mark.parametrize("config,seed_mode", [("cpu_culled", 1), ("cpu_reference", 0)])
+@pytest.mark.parametrize("size", ["mid", "full"])
+def test_more_views_than_resident_lanes(rrt, size, config, seed_mode):
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    t0 = time.perf_counter()
+    cams, ref_hdr, ref_px, ref_st = _big_reference(config, seed_mode)
+    t_singles = time.perf_counter() - t0
+    sc, _ = _scene("cornell")
+    hnd = sc.upload(0)
+    n_cu = LT.device_n_cu()
+    n = LT.views_for(LT.mid(n_cu) if size == "mid" else LT.full(n_cu), W, H)
+    (LT.check_mid if size == "mid" else LT.check_full)(n_cu, n * LT.view_work(W, H))
+    cam_of_view = (2 * np.arange(n) + 1) % BIG_CAMERAS
+    table = np.ascontiguousarray(_table(cams)[cam_of_view])
+    yy, xx = np.mgrid[0:H, 0:W]
+    t_call = t_cmp = 0.0
+
+    def check(counts, flags, device, what):
+        nonlocal t_call, t_cmp
+        o = _options(rrt, config, seed_mode, flags=flags)
+        hdr, px, st, dt = _run_big_adaptive(lib, hnd, table, n, o, counts, device, POISON)
+        t_call += dt
+        t0 = time.perf_counter()
+        level = np.minimum(counts, CAP)
+        want_hdr = ref_hdr[cam_of_view[:, None, None], level, yy[None], xx[None]]
+        want_px = ref_px[cam_of_view[:, None, None], level, yy[None], xx[None]]
+        g, wn = hdr.view(np.uint32), want_hdr.view(np.uint32)
+        same = ((g == wn) | (np.isnan(hdr) & np.isnan(want_hdr))).all(axis=-1)
+        bad = np.argwhere(~same)
+        assert len(bad) == 0, (what, len(bad), [(tuple(int(x) for x in b), int(counts[tuple(b)])) for b in bad[:6]])   # (view, y, x), its count
+        assert np.all(g[counts == 0] == 0)                                 # the prefill's +0: never traced, never written
+        assert np.array_equal(px, want_px), what
+        assert st["pixels"] == int(np.count_nonzero(counts)) and st["stack_overflows"] == 0 and st["kernel_ms"] > 0, (what, st["pixels"])
+        t_cmp += time.perf_counter() - t0
+        return st
+
+    # a seeded plane, the product build through the host entry and the counting twin through the device entry
+    counts = _big_counts(n, 2027)
+    assert 0.2 < np.count_nonzero(counts) / counts.size < 0.9 and (counts.reshape(n, -1).max(axis=1) == 0).sum() < n // 8
+    st = check(counts, 0, False, "seeded plane, product build, host entry")
+    assert st["rays"] == 0 and st["tri_tests"] == 0
+    check(counts, L.FLAG_COUNT, True, "seeded plane, counting twin, device entry")
+    # one level per view, 0 and the clamped 9 among them: the launch's counters are the sums of the single renders' counters
+    level_of_view = np.array([0, 3, 9, 1, 5, 2, 4], dtype=np.uint32)[(5 * np.arange(n) + 2) % 7]
+    flat = np.ascontiguousarray(np.broadcast_to(level_of_view[:, None, None], (n, H, W)))
+    for device in (False, True):
+        st = check(flat, L.FLAG_COUNT, device, f"one level per view, counting twin, device={device}")
+        traced = [(int(cam_of_view[v]), int(min(level_of_view[v], CAP))) for v in range(n) if level_of_view[v]]
+        for k in ("rays", "inner_steps", "tri_tests", "hits", "texel_fetches"):
+            assert st[k] == sum(ref_st[key][k] for key in traced), (k, device)
+        assert st["max_stack"] == max(ref_st[key]["max_stack"] for key in set(traced))
+    print(f"adaptive-{size}-{config}: {n} views of {W}x{H} = {n * LT.view_work(W, H)} work items on {n_cu} CUs: singles {t_singles:.2f} s, "
+          f"four adaptive calls {t_call:.2f} s, compare {t_cmp:.2f} s")
 
 
 def test_all_zero_plane_and_the_shared_workspace(rrt):

@@ -3,9 +3,15 @@ pixel position and the sample number only, never on the launch, so every view of
 with the same options, bit for bit (u32 patterns, NaN matched to NaN), and the batch's counters must be the sums over those renders."""
 import ctypes as C
 import functools
+import os
+import sys
+import time
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import launch_thresholds as LT  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -314,3 +320,118 @@ def test_batch_after_refit(rrt):
     hdr, px, st = _batch(lib, hnd, cams, o, w, h)
     _check_equal(hdr, px, st, hdrs, rgbas, stats)
     assert not _same(hdr, first)                                           # the geometry did change
+
+
+# ---- launches larger than the lanes in flight: a lane's second pixel belongs to another view ----------------------------------------
+# pt_trace_batch_kernel is persistent: the grid holds a fixed number of lanes and each lane takes work items (view, tile, pixel) from
+# the queue until it is dry.  Every launch above fits into the lanes' first fetch.  These cross the two thresholds of
+# tests/tools/launch_thresholds.py by their number of views, computed from the device: MID, where lanes refill under leaf_period 1,
+# and FULL, the full-frame schedule (leaf_period 4, at most a quarter of the work in flight, a ragged tail).  The views are the small
+# frames test_gpu_parity.py holds to the oracle, its three cameras cycled with stride 2 from camera 1 (1, 0, 2, 1, ...), so a wave's
+# consecutive tiles change view and camera; the reference of view v is the oracle's frame of its camera, bit for bit, and its RGBA8.
+def _big_batch_case(rrt, orc, case, traversal, margin):
+    """(Scene, three cameras, [(oracle HDR, oracle RGBA8)] per camera) of a PRODUCT_CASES entry: test_gpu_parity.py's own cache"""
+    import test_gpu_parity as P
+    sc, cams = P._product_scene(rrt, case)
+    return sc, cams, [P._product_ref(orc, case, v, traversal, margin) for v in range(3)]
+
+
+BIG_NAN, BIG_CANARY = 0x7FA5A5A5, 0x4640E400              # a NaN no render produces in every word; 12345.0 behind the last view
+
+
+def _run_big_batch(lib, hnd, table, n, o, w, h, device):
+    """one call with NaN-filled outputs that end in canary words -> (hdr [n,h,w,3], rgba8 [n,h,w,4], stats dict, seconds)"""
+    from rust_ray_tracing_amd import _lib as L
+    st = L.MiptStats()
+    n_f, n_b, tail = n * h * w * 3, n * h * w * 4, 64
+    if device:
+        import torch
+        d_hdr = torch.full((n_f + tail,), BIG_NAN, dtype=torch.int32, device="cuda")
+        d_hdr[n_f:] = BIG_CANARY
+        d_px = torch.full((n_b + tail,), 0x5A, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rc = lib.mipt_render_batch_device(hnd, L.ptr(table), n, C.byref(o), C.c_void_p(d_hdr.data_ptr()), C.c_void_p(d_px.data_ptr()), None, C.byref(st))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        hdr, px = d_hdr.cpu().numpy().view(np.uint32), d_px.cpu().numpy()
+    else:
+        hdr = np.full(n_f + tail, BIG_NAN, dtype=np.uint32)
+        hdr[n_f:] = BIG_CANARY
+        px = np.full(n_b + tail, 0x5A, dtype=np.uint8)
+        t0 = time.perf_counter()
+        rc = lib.mipt_render_batch(hnd, L.ptr(table), n, C.byref(o), L.ptr(hdr), L.ptr(px), C.byref(st))
+        dt = time.perf_counter() - t0
+    assert rc == 0, lib.mipt_last_error()
+    assert np.all(hdr[n_f:] == BIG_CANARY) and np.all(px[n_b:] == 0x5A), "written behind the last view"
+    assert not np.any(hdr[:n_f] == BIG_NAN), "a pixel was never written"
+    return hdr[:n_f].view(np.float32).reshape(n, h, w, 3), px[:n_b].reshape(n, h, w, 4), st.as_dict(), dt
+
+
+def _first_bad_views(got, want_by_cam, cam_of_view):
+    g = got.reshape(len(cam_of_view), -1).view(np.uint32)
+    wn = np.stack([x.reshape(-1) for x in want_by_cam]).view(np.uint32)[cam_of_view]
+    same = (g == wn) | (np.isnan(g.view(np.float32)) & np.isnan(wn.view(np.float32)))
+    bad = np.flatnonzero(~same.all(axis=1))
+    return [(int(v), int(cam_of_view[v]), int((~same[v]).sum())) for v in bad[:6]], len(bad)
+
+
+BIG_TRAVERSALS = [(0, 0.0), (1, 0.0078125)]
+
+
+def _check_big_batch(rrt, orc, case, size, traversal, margin, label):
+    import test_gpu_parity as P
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    shading, w, h, spp, depth, _ = P.PRODUCT_CASES[case]
+    t0 = time.perf_counter()
+    sc, cams, refs = _big_batch_case(rrt, orc, case, traversal, margin)
+    t_oracle = time.perf_counter() - t0                                # 0 when test_gpu_parity.py's cache already holds the frames
+    hnd = sc.upload(0)
+    n_cu = LT.device_n_cu()
+    n = LT.views_for(LT.mid(n_cu) if size == "mid" else LT.full(n_cu), w, h)
+    (LT.check_mid if size == "mid" else LT.check_full)(n_cu, n * LT.view_work(w, h))
+    cam_of_view = (2 * np.arange(n) + 1) % 3
+    occurs = np.bincount(cam_of_view, minlength=3)
+    assert occurs.min() >= n // 3
+    table = np.ascontiguousarray(_table(cams)[cam_of_view])
+    # the three single renders with counters: the frames are the oracle's, so their counters are those of the oracle's frames
+    t0 = time.perf_counter()
+    o_count = rrt.make_options(w, h, spp, depth, traversal=traversal, flags=L.FLAG_COUNT, cull_margin=margin, shading=shading)
+    o_plain = rrt.make_options(w, h, spp, depth, traversal=traversal, flags=0, cull_margin=margin, shading=shading)
+    hdrs, rgbas, stats = _singles(lib, hnd, cams, o_count, w, h)
+    for v in range(3):
+        assert _same(hdrs[v], refs[v][0]) and np.array_equal(rgbas[v], refs[v][1]), v
+    t_singles = time.perf_counter() - t0
+    t_call = t_cmp = 0.0
+    for device in (False, True):
+        for o in (o_plain, o_count):
+            hdr, px, st, dt = _run_big_batch(lib, hnd, table, n, o, w, h, device)
+            t_call += dt
+            t0 = time.perf_counter()
+            bad, n_bad = _first_bad_views(hdr, [r[0] for r in refs], cam_of_view)
+            assert n_bad == 0, f"{label} device={device} flags={o.flags}: {n_bad} of {n} views differ; first (view, camera, differing words): {bad}"
+            assert np.array_equal(px, np.stack([r[1] for r in refs])[cam_of_view]), (case, size, traversal, device, o.flags)
+            assert st["pixels"] == n * w * h and st["stack_overflows"] == 0 and st["kernel_ms"] > 0
+            if o.flags & L.FLAG_COUNT:
+                for k in ("rays", "inner_steps", "tri_tests", "hits", "texel_fetches"):
+                    assert st[k] == sum(int(occurs[c]) * stats[c][k] for c in range(3)), (k, device)
+                assert st["max_stack"] == max(s["max_stack"] for s in stats)
+            else:
+                assert st["rays"] == 0 and st["tri_tests"] == 0
+            t_cmp += time.perf_counter() - t0
+    print(f"{label}: {n} views of {w}x{h} = {n * LT.view_work(w, h)} work items on {n_cu} CUs: oracle frames {t_oracle:.2f} s, "
+          f"singles {t_singles:.2f} s, four batch calls {t_call:.2f} s, compare {t_cmp:.2f} s")
+
+
+@pytest.mark.parametrize("traversal,margin", BIG_TRAVERSALS, ids=["reference", "culled"])
+@pytest.mark.parametrize("size", ["mid", "full"])
+@pytest.mark.parametrize("case", ["cornell", "helmet"])
+def test_batches_larger_than_the_lanes_in_flight(rrt, orc, case, size, traversal, margin):
+    """both entries, the product build and the counting twin, four launches per case"""
+    _check_big_batch(rrt, orc, case, size, traversal, margin, f"{case}-{size}-{'culled' if traversal else 'reference'}")
+
+
+def test_full_batch_with_the_wgpu_material_model(rrt, orc):
+    """shading 1 on the scene with a texture in every slot, at FULL: the other four of the eight instantiations under leaf_period 4"""
+    _check_big_batch(rrt, orc, "wgsl_pbr", "full", 1, 0.0078125, "wgsl_pbr-full-culled")

@@ -6,6 +6,7 @@ import ctypes as C
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -13,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import features_model as F  # noqa: E402
+import launch_thresholds as LT  # noqa: E402
 import mesh_model  # noqa: E402
 import query_model as Q  # noqa: E402
 
@@ -256,6 +258,84 @@ def test_views_equal_single_view_calls(rrt, orc, seed_mode):
         for k in F.COUNTERS[:-1] + ("pixels",):
             assert st[k] == sum(s[1][k] for s in singles), k
         assert st["max_stack"] == max(s[1]["max_stack"] for s in singles)
+
+
+# ---- more views than the launch holds lanes: every lane takes a second and a third pixel, of other views ---------------------------
+# first_hit_kernel is persistent: n_cu x blocks_per_cu blocks of 256 lanes take work items (view, tile, pixel) from a queue, and every
+# launch above fits into the lanes' first fetch.  These pass tests/tools/launch_thresholds.py's FULL_F -- more than twice the lanes in
+# flight whatever the occupancy, a ragged tail -- with views of SIZES[0], the size test_frames_against_the_model holds to the model,
+# and the four cameras of features_model.batch_cameras cycled with stride 3.  Every buffer of every view must equal the same entry
+# called on its camera alone, bit for bit, and those four single frames must equal features_model.frame: views never see each other,
+# so the two together cover every word.  tests/test_features_model.py shows that this work order refills waves
+# whose other lanes are mid-traversal.
+_big_models = {}
+
+
+def _big_model(rrt, orc, cam_index, cams, seed_mode, samples, arm):
+    key = (cam_index, seed_mode, samples, arm)
+    if key not in _big_models:
+        sc = _scene(rrt, "helmet")
+        rays = _rays.setdefault(("helmet-batch", cam_index, seed_mode), {})
+        _big_models[key] = F.frame(orc, sc, cams[cam_index].uniform, SIZES[0][0], SIZES[0][1], seed_mode, samples, 0, arm[0] == CULL, arm[1], rays=rays)[:2]
+    return _big_models[key]
+
+
+def _check_big_features(rrt, orc, seed_mode, samples, arm, names, runs, label):
+    """runs: (device, count) of each batch call"""
+    sc = _scene(rrt, "helmet")
+    size = SIZES[0]
+    cams = F.batch_cameras(rrt, sc.camera)
+    n_cu = LT.device_n_cu()
+    n = LT.views_for(LT.full_f(n_cu), *size)
+    LT.check_full_f(n_cu, n * LT.view_work(*size))
+    cycle = F.batch_cycle(n, len(cams))
+    occurs = np.bincount(cycle, minlength=len(cams))
+    t0 = time.perf_counter()
+    singles = []
+    for c in range(len(cams)):
+        want, counters = _big_model(rrt, orc, c, cams, seed_mode, samples, arm)
+        got, st = _features(rrt, sc._handle, [cams[c]], size, seed_mode, arm, samples, names=names)
+        assert not _same(got, want, names, view=0), (label, c, _same(got, want, names, view=0))
+        if names == F.NAMES:
+            assert _same_counters(st, counters), (label, c, st, counters)
+        singles.append((got, st))
+    assert all(_same(singles[c][0], singles[0][0], ("depth",)) for c in range(1, len(cams)))   # four different views
+    t_singles = time.perf_counter() - t0
+    t_call = t_cmp = 0.0
+    for device, count in runs:
+        t0 = time.perf_counter()
+        got, st = _features(rrt, sc._handle, [cams[c] for c in cycle], size, seed_mode, arm, samples, names=names, device=device, count=count)
+        t_call += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        for k in names:
+            want = np.concatenate([s[0][k] for s in singles])[cycle]
+            same = (np.ascontiguousarray(got[k]).view(np.uint32) == np.ascontiguousarray(want).view(np.uint32)).reshape(n, -1).all(axis=1)
+            assert same.all(), (label, k, device, count, int((~same).sum()), [(int(v), int(cycle[v])) for v in np.flatnonzero(~same)[:6]])
+        assert st["pixels"] == n * size[0] * size[1] and st["stack_overflows"] == 0 and st["kernel_ms"] > 0
+        if count:
+            for k in F.COUNTERS[:-1]:
+                assert st[k] == sum(int(occurs[c]) * singles[c][1][k] for c in range(len(cams))), (label, k, device)
+            assert st["max_stack"] == max(s[1]["max_stack"] for s in singles)
+        else:
+            assert st["rays"] == 0 and st["tri_tests"] == 0 and st["texel_fetches"] == 0
+        t_cmp += time.perf_counter() - t0
+    print(f"{label}: {n} views of {size[0]}x{size[1]} = {n * LT.view_work(*size)} work items on {n_cu} CUs: models and singles {t_singles:.2f} s, "
+          f"{len(runs)} batch calls {t_call:.2f} s, compare {t_cmp:.2f} s")
+
+
+@pytest.mark.parametrize("arm", [ARMS[0], ARMS[2]], ids=["ref", "cullsafe"])
+@pytest.mark.parametrize("seed_mode,samples", [(0, 1), (1, 3)], ids=["stream-1", "per-sample-3"])
+def test_more_views_than_the_launch_holds_lanes(rrt, orc, seed_mode, samples, arm):
+    """all eight buffers; with three samples a refilled lane restarts `sample` and the running sums in its new pixel's slots"""
+    _check_big_features(rrt, orc, seed_mode, samples, arm, F.NAMES, [(False, True), (True, False), (False, False), (True, True)],
+                        f"features-{'stream-1' if seed_mode == 0 else 'per-sample-3'}-{'ref' if arm[0] == REF else 'cullsafe'}")
+
+
+@pytest.mark.parametrize("names", [("depth", "normal"), ("depth", "prim", "position")], ids=["depth-normal", "no-attributes"])
+def test_more_views_than_the_launch_holds_lanes_buffer_subsets(rrt, orc, names):
+    """depth and normal: the attribute record is read for the normal alone and no texel is fetched; depth, prim and position: want_attr
+    is false and a finished lane reads no record at all -- on refilled lanes as on fresh ones"""
+    _check_big_features(rrt, orc, 1, 3, ARMS[2], names, [(False, True), (True, False)], "features-" + "-".join(names))
 
 
 # ---- scenes made three ways, then REFIT and REBUILD ----------------------------------------------------------------------------------

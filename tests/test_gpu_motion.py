@@ -5,6 +5,7 @@ less than one wave and one pixel.  A model frame's hits are computed once per (g
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -12,6 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import features_model as F  # noqa: E402
+import launch_thresholds as LT  # noqa: E402
 import motion_model as M  # noqa: E402
 import motion_world as MW  # noqa: E402
 import query_model as Q  # noqa: E402
@@ -182,6 +184,41 @@ def test_frame_shapes(rrt, orc, size, views):
     assert M.same_bits(got, _model(orc, sc, ("three", 1), cams, size, 1, 5, ARMS[0], prev))
     got, _ = _motion(rrt, sc._handle, cams, size, None, 1, ARMS[0], 1)
     assert M.same_bits(got, _model(orc, sc, ("three", 1), cams, size, 1, 0, ARMS[0], prev))
+    sc.release()
+
+
+# ---- more views than the launch holds lanes: both motion forms of first_hit_kernel on refilled lanes -----------------------------------
+# As tests/test_gpu_features.py::test_more_views_than_the_launch_holds_lanes: launch_thresholds.FULL_F work items as views of 61 x 37,
+# the three cameras of test_frame_shapes cycled with stride 2 from camera 1.  Every view equals the same entry called on its camera
+# alone, and the three single frames equal motion_model.
+@pytest.mark.parametrize("source", ["explicit", "tracked"])
+def test_more_views_than_the_launch_holds_lanes(rrt, orc, source):
+    sc, prev, _ = _world(rrt, 1)
+    pose = MW.three_parts()[2]
+    cams = [sc.camera, _camera(rrt, pose, dp=(-0.3, 0.2, 0.25), dyaw=6.0), _camera(rrt, pose, dp=(0.1, -0.3, -0.4), dyaw=-9.0)]
+    size = (61, 37)
+    n_cu = LT.device_n_cu()
+    n = LT.views_for(LT.full_f(n_cu), *size)
+    LT.check_full_f(n_cu, n * LT.view_work(*size))
+    cycle = (2 * np.arange(n) + 1) % 3
+    prev_tris = prev if source == "explicit" else None
+    t_singles = t_call = t_cmp = 0.0
+    for (seed_mode, arm), device in zip(((0, ARMS[0]), (1, ARMS[1])), (False, True)):
+        t0 = time.perf_counter()
+        want = _model(orc, sc, ("three", 1), cams, size, seed_mode, 0, arm, prev)
+        singles = np.concatenate([_motion(rrt, sc._handle, [c], size, prev_tris, seed_mode, arm)[0] for c in cams])
+        assert M.same_bits(singles, want), (source, seed_mode)
+        assert not M.same_bits(want[0], want[1]) and not M.same_bits(want[1], want[2]) and not M.same_bits(want[0], want[2])
+        t_singles += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        got, _ = _motion(rrt, sc._handle, [cams[c] for c in cycle], size, prev_tris, seed_mode, arm, device=device)
+        t_call += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        same = (got.view(np.uint32) == singles[cycle].view(np.uint32)).reshape(n, -1).all(axis=1)
+        assert same.all(), (source, seed_mode, device, int((~same).sum()), [(int(v), int(cycle[v])) for v in np.flatnonzero(~same)[:6]])
+        t_cmp += time.perf_counter() - t0
+    print(f"motion-{source}: {n} views of {size[0]}x{size[1]} = {n * LT.view_work(*size)} work items on {n_cu} CUs: models and singles {t_singles:.2f} s, "
+          f"two batch calls {t_call:.2f} s, compare {t_cmp:.2f} s")
     sc.release()
 
 

@@ -107,7 +107,11 @@ def test_sample_map_fill_argument_errors_without_a_device(rrt, which):
     case("min_samples 9", lambda o, b, k: _set(o, min_samples=9))
     case("budget", lambda o, b, k: _set(o, budget=8.5))
     case("budget", lambda o, b, k: _set(o, budget=float("nan")))
-    case("counts overlaps variance", lambda o, b, k: _set(b, counts=k["variance"].ctypes.data + 32))
+    def shifted_counts(o, b, k):
+        # one array of this case's own holds both planes: variance in its first 64 words, counts 8 words behind it -- inside the array
+        k["both"] = np.zeros(64 + 8, dtype=np.float32)
+        _set(b, variance=k["both"].ctypes.data, counts=k["both"].ctypes.data + 32)
+    case("counts overlaps variance", shifted_counts)
     if which == "mipt_sample_map_fill_device":
         case("null workspace", workspace=None)
         case("workspace must be 16-byte aligned", workspace=C.c_void_p(base + 8))
@@ -184,9 +188,19 @@ def test_temporal_counts_argument_errors_without_a_device(rrt, which):
         case("counts must be 4-byte aligned", counts=lambda k: C.c_void_p(k["counts"].ctypes.data + 2))
         case("counts overlaps hdr", counts=lambda k: C.c_void_p(k["hdr"].ctypes.data + 8))
         case("counts overlaps depth", counts=lambda k: C.c_void_p(k["depth"].ctypes.data))
-        case("counts overlaps variance", counts=lambda k: C.c_void_p(k["variance"].ctypes.data + 4 * N - 4))
+        # The count plane is N words.  Starting in the last word of the N-word variance array it ran N - 1 words past the array's end,
+        # over whatever the allocator had put there: when that was another plane of the call, an earlier name of the table was
+        # reported ("counts overlaps length").  Both planes now lie in one array of 2 N words that the case owns.
+        def shared_variance(o, b, k):
+            k["both"] = np.zeros(2 * N, dtype=np.float32)
+            _set(b, variance=k["both"].ctypes.data)
+        case("counts overlaps variance", shared_variance, counts=lambda k: C.c_void_p(k["both"].ctypes.data + 4 * N - 4))
         case("counts overlaps history_in", counts=lambda k: C.c_void_p(((k["history_in"].ctypes.data + 15) & ~15) + 64))
-        case("counts overlaps history_out", counts=lambda k: C.c_void_p(((k["history_out"].ctypes.data + 15) & ~15) + 4 * (16 * V + 12 * N) - 4))
+        def roomy_history_out(o, b, k):                         # the same: N words of room behind the history's last word
+            k["history_out"] = np.zeros(16 * V + 12 * N + 4 + N, dtype=np.uint32)
+            _set(b, history_out=(k["history_out"].ctypes.data + 15) & ~15)
+        case("counts overlaps history_out", roomy_history_out,
+             counts=lambda k: C.c_void_p(((k["history_out"].ctypes.data + 15) & ~15) + 4 * (16 * V + 12 * N) - 4))
         case("is not device memory")                            # well-formed, but host pointers
 
 

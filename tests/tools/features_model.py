@@ -122,6 +122,56 @@ def frame(orc, sc, camera, width, height, seed_mode, samples=1, sample_begin=0, 
     return shaped, counters, (per_sample[0][1], per_sample[0][2])
 
 
+# ---- batches larger than one launch holds in flight: a few distinct cameras, cycled -------------------------------------------------
+# (dx, dy, dz, dpitch, dyaw) from the scene's own camera: poses around it that keep the helmet's silhouette in the frame, so that sky
+# pixels (over after the root's step) and hits (sixteen steps or more) share tiles
+BATCH_POSES = ((0.0, 0.0, 0.0, 0.0, 0.0), (0.3, -0.2, 0.1, 7.0, -11.0), (-0.4, 0.1, 0.0, -5.0, 9.0), (0.1, 0.3, -0.3, 12.0, -25.0))
+
+
+def batch_cameras(rrt, own):
+    """the distinct cameras of a large batch: `own` and the poses of BATCH_POSES around it"""
+    cams = [own]
+    for dx, dy, dz, dp, dyaw in BATCH_POSES[1:]:
+        c = rrt.Camera(position=(own.position[0] + dx, own.position[1] + dy, own.position[2] + dz), pitch=own.pitch + dp, yaw=own.yaw + dyaw)
+        c.update_view()
+        cams.append(c)
+    return cams
+
+
+def batch_cycle(n_views, n_cameras=len(BATCH_POSES)):
+    """camera of view v: stride 3 from camera 1 (coprime to the four cameras), so neighbouring views differ"""
+    assert np.gcd(3, n_cameras) == 1
+    return (3 * np.arange(n_views) + 1) % n_cameras
+
+
+def pixel_steps(orc, sc, camera, width, height, seed_mode, sample=0, cull=False, margin=0.0, rays=None):
+    """What the camera ray of every pixel costs first_hit_kernel: inner_steps + tri_tests of its traversal, one loop iteration each
+    (a fresh counter dict per pixel) -> int64 [height, width].  `rays`: camera_rays(...)[0] of the same frame, if already at hand."""
+    rays = camera_rays(orc, sc, camera, width, height, seed_mode, sample)[0] if rays is None else rays
+    lib = orc.load()
+    out = np.zeros(width * height, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for i in range(width * height):
+            c = {}
+            Q.traverse(lib, sc.tris, sc.bvh_nodes, rays[i], cull, margin, False, c)
+            out[i] = c["inner_steps"] + c["tri_tests"]
+    return out.reshape(height, width)
+
+
+def work_order_steps(steps_by_view):
+    """The step counts of a batch in first_hit_kernel's work-item order -- view, 8x8 tile of the view row-major, pixel of the tile
+    row-major -- from [height, width] arrays, one per view; an item off the frame's ragged edge is 0 (the fetch skips it and the lane
+    asks again) -> int64 [n_views * n_tiles * 64]"""
+    out = []
+    for s in steps_by_view:
+        h, w = s.shape
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        padded = np.zeros((ty * 8, tx * 8), dtype=np.int64)
+        padded[:h, :w] = s
+        out.append(padded.reshape(ty, 8, tx, 8).transpose(0, 2, 1, 3).reshape(-1))
+    return np.concatenate(out)
+
+
 def radiance(albedo, emission):
     """What ray.rs:177,197-201 and cpu.rs:52,60 make of a depth-1 path from the two buffers, as f32: (0 + albedo * emission) + 0"""
     a, e = np.asarray(albedo, dtype=np.float32), np.asarray(emission, dtype=np.float32)

@@ -184,17 +184,18 @@ def tiled(pool_len, classes, n, period=8):
     return np.where(pos < n_short, short[k_short % len(short)], long_[k_long % len(long_)])
 
 
-def wave_refills(n_steps, bases=None, refill_num=1, refill_den=4):
+def wave_refills(n_steps, bases=None, refill_num=1, refill_den=4, skips=False):
     """The scheduling rule of ONE wave of ray_query_kernel, and nothing else, driven by the step count of every ray of a batch
     (`n_steps` [n], each >= 1): the lane states QS_T (traversing) / QS_D (done, result to write) / QS_N (needs a ray) / QS_X
     (retired); a refill pass when `n_need * den >= (n_t + n_need) * num or n_t == 0`; otherwise one step per traversing lane.  A
     refill takes a contiguous block of indices, one per needing lane in lane order, starting at the next value of `bases` (what the
     global counter returned: other waves move it in between); None = the wave is alone and the counter is its own; an exhausted
-    iterator = the queue has run out.  -> the number of refills that delivered at least one ray while another lane was mid-
+    iterator = the queue has run out.  `skips` (first_hit_kernel, whose queue runs over whole 8x8 tiles): an index with 0 steps is
+    off the frame's ragged edge and leaves its lane needing a ray.  -> the number of refills that delivered at least one ray while another lane was mid-
     traversal: the refills no batch that fits into one launch's first fetch can produce."""
     n_steps = np.asarray(n_steps, dtype=np.int64)
     n = len(n_steps)
-    assert n == 0 or n_steps.min() >= 1                  # the root costs one iteration, inner node or leaf
+    assert n == 0 or n_steps.min() >= (0 if skips else 1)  # the root costs one iteration, inner node or leaf
     T, D, N, X = 0, 1, 2, 3
     state = np.full(64, N)
     left = np.zeros(64, dtype=np.int64)
@@ -219,6 +220,9 @@ def wave_refills(n_steps, bases=None, refill_num=1, refill_den=4):
             state[lanes[~got]] = X
             state[lanes[got]] = T
             left[lanes[got]] = n_steps[ray[got]]
+            if skips and n:                              # nothing to trace at this index: the lane asks again
+                got = got & (n_steps[np.minimum(ray, n - 1)] > 0)
+                state[lanes[(ray < n) & ~got]] = N
             if n_t > 0 and got.any():
                 partial += 1
             continue
