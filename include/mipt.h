@@ -279,7 +279,7 @@ MIPT_API int mipt_render_batch_device(MiptScene *scene, const MiptCamera *camera
  * `hip_stream` (hipStream_t, NULL = the null stream) and block until done, like mipt_render_device.  Queries see the geometry of
  * the last successful update (REFIT, REBUILD, mipt_scene_set_transforms, mipt_scene_update_mesh_device) and work on a replica
  * handle from mipt_multi_scene. */
-typedef struct { float origin[3]; float t_max; float direction[3]; uint32_t reserved; } MiptRay;   /* 32 B; reserved is ignored */
+typedef struct { float origin[3]; float t_max; float direction[3]; uint32_t reserved; } MiptRay;   /* 32 B; reserved is ignored here (mipt_query_radiance: the seed) */
 typedef struct { float t, u, v; uint32_t prim; } MiptHit;                                          /* 16 B */
 #define MIPT_HIT_NONE        0xffffffffu   /* prim of a miss; then t = 1e30f (HitInfo::default, ray.rs:214-226), u = v = 0 */
 #define MIPT_HIT_FRONT_FACE  0x80000000u   /* bit 31 of prim: det > 0 (ray.rs:39); triangle = prim & 0x01ffffff */
@@ -294,6 +294,67 @@ MIPT_API int mipt_query_occluded(MiptScene *scene, const MiptRay *rays, uint64_t
                                  uint8_t *occluded, MiptStats *stats);
 MIPT_API int mipt_query_occluded_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt,
                                         uint8_t *d_occluded, void *hip_stream, MiptStats *stats);
+
+/* ---- radiance queries: path-traced radiance along the caller's rays ------------------------------------------------------------
+ * "How much light arrives along my ray": the trace loop of the renders (csrc/pt_kernel.hip) with the caller's rays in place of a
+ * camera -- what a lightmap or vertex baker, an irradiance-probe grid or a radiance cache asks of a resident scene.  Rays in, one
+ * RGB radiance per ray out.
+ *
+ * The ray.  origin and direction are used as given: the direction is not normalised, as in the queries above (the reference's
+ * camera rays are unit vectors; a scatter ray is normalised by Ray::trace itself, so only the first segment sees the caller's
+ * length).  t_max is ignored: every segment of a path starts from HitInfo::default (ray.rs:214-226), as Ray::trace does.  The
+ * fourth word of the record's second half -- `reserved` of MiptRay, still ignored by the two queries above -- is this ray's SEED,
+ * a u32.
+ *
+ * The value, shading = MIPT_SHADING_CPU.  rng = seed; then `samples` times Ray::trace(ray, max_ray_depth, rng) (ray.rs:141-202) on
+ * that one xorshift stream, which continues from sample to sample; the results are summed in f32, in order, from +0, and the sum is
+ * divided by (float)samples unless MIPT_FLAG_SUM is set.  This is cpu.rs:52,60 with the camera ray of cpu.rs:37-50 replaced by the
+ * caller's: no jitter draws, no camera matrix.
+ *
+ * The value, shading = MIPT_SHADING_WGPU.  The same with `trace` of rt_compute.wgsl:126-229.  The per-sample reseed of
+ * rt_compute.wgsl:102 does NOT happen -- there is no pixel to seed from: the stream continues from sample to sample here too.
+ *
+ * The seed is used as given.  Seed 0 is a stuck xorshift stream (every draw 0), exactly as it would be in the reference: give every
+ * ray a non-zero seed, and rays that should be independent different ones.  (The pixel formula of cpu.rs:28-29,
+ * 987612486 * (i + 87636354) mod 2^32, is what the Python wrapper hands out by default, with 1 in place of a 0.)
+ *
+ * MIPT_FLAG_ACCUM (device entry only, with MIPT_FLAG_SUM): d_radiance[i] += this call's sum, one f32 addition per channel.  The
+ * caller brings fresh seeds with every call and divides once at the end: progressive baking.
+ *
+ * Results and indices.  radiance[i * 3 .. i * 3 + 3) depends on rays[i] and the options only -- never on i, on n_rays or on how the
+ * launch was scheduled.  Every ray writes its slot and nothing behind n_rays * 3 floats is touched.  n_rays == 0 is MIPT_OK without
+ * a launch; n_rays >= MIPT_QUERY_MAX_RAYS is MIPT_ERR_INVALID_ARG.
+ *
+ * Options (required): samples and max_ray_depth > 0; traversal / cull_margin / shading as in MiptOptions; flags: MIPT_FLAG_COUNT,
+ * MIPT_FLAG_SUM and MIPT_FLAG_ACCUM -- MIPT_FLAG_TOUCHED, MIPT_FLAG_PACKED and unknown bits are refused; reserved words 0.
+ *
+ * stats (may be NULL).  kernel_ms and stack_overflows always.  With MIPT_FLAG_COUNT also rays, inner_steps, tri_tests, hits,
+ * texel_fetches and max_stack, pixels = n_rays, and diag[] as a batch launch fills it.
+ *
+ * Errors.  Checked before any device work, MIPT_ERR_INVALID_ARG with a message in mipt_last_error(): a null scene, rays, options or
+ * radiance; n_rays >= MIPT_QUERY_MAX_RAYS; zero samples or max_ray_depth; an unknown traversal, shading or flag; a negative or
+ * non-finite cull_margin; non-zero reserved fields; MIPT_FLAG_ACCUM on the host entry or without MIPT_FLAG_SUM; for the device
+ * entry d_rays not 16-byte aligned, d_radiance not 4-byte aligned, the two ranges overlapping, or a pointer that is not device
+ * memory of the scene's device.  A traversal-stack overflow is MIPT_ERR_STACK after the results are written, as in mipt_render.
+ * After any error the scene renders and queries as before.
+ *
+ * The device entry takes buffers in HBM of the scene's device, is ordered after the earlier work of `hip_stream` (NULL = the null
+ * stream) and blocks until done, like the queries above.  Both entries see the geometry of the last successful update (REFIT,
+ * REBUILD, mipt_scene_set_transforms, mipt_scene_update_mesh_device) and work on a replica handle from mipt_multi_scene. */
+typedef struct {
+    uint32_t samples;        /* > 0: paths per ray */
+    uint32_t max_ray_depth;  /* > 0 */
+    uint32_t traversal;      /* MiptTraversal */
+    float    cull_margin;    /* MIPT_TRAVERSAL_CULLED: relative margin (>= 0); see MIPT_CULL_MARGIN_SAFE */
+    uint32_t shading;        /* MiptShading */
+    uint32_t flags;          /* MIPT_FLAG_COUNT, MIPT_FLAG_SUM, MIPT_FLAG_ACCUM (device entry only, needs SUM) */
+    uint32_t reserved[10];   /* must be 0 */
+} MiptRadianceOptions;      /* 64 B */
+
+MIPT_API int mipt_query_radiance(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptRadianceOptions *opt,
+                                 float *radiance /* n_rays*3 */, MiptStats *stats);
+MIPT_API int mipt_query_radiance_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt,
+                                        float *d_radiance /* n_rays*3 */, void *hip_stream, MiptStats *stats);
 
 /* ---- first-hit feature buffers: depth, ids, position, uv, normal, albedo, emission per pixel --------------------------------------
  * What the camera ray of every pixel hits and what the surface looks like there: the guide images of a denoiser, the id and depth

@@ -80,6 +80,17 @@ inline int query_occluded_on(MiptScene *scene, const std::vector<MiptRay> &rays,
     if (rc != MIPT_OK) log_error(mipt_last_error());
     return rc;
 }
+// mipt_query_radiance on any resident scene handle: radiance[3 i .. 3 i + 3) for rays[i], whose `reserved` word is its seed (non-zero;
+// include/mipt.h "radiance queries").  MIPT_ERR_STACK leaves the results written.
+inline int query_radiance_on(MiptScene *scene, const std::vector<MiptRay> &rays, std::vector<float> &radiance, const MiptRadianceOptions &opt,
+                             MiptStats *stats = nullptr) {
+    radiance.assign(rays.size() * 3, 0.0f);
+    static const MiptRay no_ray{};
+    static float no_value = 0.0f;
+    const int rc = mipt_query_radiance(scene, rays.empty() ? &no_ray : rays.data(), rays.size(), &opt, radiance.empty() ? &no_value : radiance.data(), stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
 
 // mipt_render_features on any resident scene handle: first-hit feature buffers (include/mipt.h "first-hit feature buffers") for
 // `cameras` with `opt`.  `wanted`: FeatureBit flags; only those images are computed and filled, each view-major [view][row][column][k]
@@ -337,6 +348,11 @@ class Scene {                                              // src/scene.rs:12-19
         MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
         return m ? query_occluded_on(mipt_multi_scene(m, 0), rays, occluded, opt, stats) : MIPT_ERR_HIP;
     }
+    // path-traced radiance along the caller's rays (mipt_query_radiance), on the same replica
+    int query_radiance(const std::vector<MiptRay> &rays, std::vector<float> &radiance, const MiptRadianceOptions &opt, MiptStats *stats = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? query_radiance_on(mipt_multi_scene(m, 0), rays, radiance, opt, stats) : MIPT_ERR_HIP;
+    }
 
   private:
     mutable std::shared_ptr<MiptMulti> multi_;
@@ -414,6 +430,18 @@ class Renderer {                                           // src/renderer.rs:8-
         const std::vector<MiptCamera> &cams = cameras.empty() ? own : cameras;
         MiptMulti *m = scene.node_handle(1);
         return m ? render_features_on(mipt_multi_scene(m, 0), cams, o, wanted, out, stats) : MIPT_ERR_HIP;
+    }
+
+    // Radiance along the caller's rays (mipt_query_radiance) with this renderer's samples, max_ray_depth and traversal, the safe cull
+    // margin and CPU-backend shading; `flags`: MIPT_FLAG_COUNT / MIPT_FLAG_SUM.  Residency as render_features.  Returns a MiptStatus.
+    int query_radiance(const Scene &scene, const std::vector<MiptRay> &rays, std::vector<float> &radiance, uint32_t flags = 0,
+                       MiptStats *stats = nullptr) const {
+        if (options.backend != RendererBackend::MI355X) { log_error("this build only provides RendererBackend::MI355X"); return MIPT_ERR_INVALID_ARG; }
+        MiptRadianceOptions o{};
+        o.samples = (uint32_t)options.samples; o.max_ray_depth = (uint32_t)options.max_ray_depth;
+        o.traversal = options.traversal; o.cull_margin = MIPT_CULL_MARGIN_SAFE; o.flags = flags;
+        MiptMulti *m = scene.node_handle(1);
+        return m ? query_radiance_on(mipt_multi_scene(m, 0), rays, radiance, o, stats) : MIPT_ERR_HIP;
     }
 
     // Previous positions of the frame(s) this renderer would render (mipt_render_motion): what Renderer::temporal takes as the

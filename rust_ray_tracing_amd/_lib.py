@@ -99,6 +99,15 @@ class MiptQueryOptions(C.Structure):
     _fields_ = [("traversal", C.c_uint32), ("cull_margin", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+# ---- radiance queries (include/mipt.h "radiance queries"): MiptRay's last word is the ray's seed ----
+class MiptRadianceOptions(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("max_ray_depth", C.c_uint32), ("traversal", C.c_uint32), ("cull_margin", C.c_float),
+                ("shading", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 10)]
+
+
+assert C.sizeof(MiptRadianceOptions) == 64
+
+
 # ---- first-hit feature buffers (include/mipt.h "first-hit feature buffers") ----
 FEATURES = (("depth", 1, np.float32), ("prim", 1, np.uint32), ("material", 1, np.uint32), ("position", 3, np.float32),
             ("uv", 2, np.float32), ("normal", 3, np.float32), ("albedo", 3, np.float32), ("emission", 3, np.float32))   # name, values per pixel, type
@@ -255,6 +264,7 @@ EXPORTS = [
     "mipt_render_adaptive", "mipt_render_adaptive_device", "mipt_sample_map_workspace_bytes", "mipt_sample_map", "mipt_sample_map_device",
     "mipt_temporal_counts", "mipt_temporal_counts_device",
     "mipt_sample_map_fill_workspace_bytes", "mipt_sample_map_fill", "mipt_sample_map_fill_device",
+    "mipt_query_radiance", "mipt_query_radiance_device",
 ]
 
 _lib = None
@@ -378,6 +388,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_query_occluded.restype = C.c_int
     lib.mipt_query_occluded_device.argtypes = [vp, vp, u64, qo, vp, vp, C.POINTER(MiptStats)]
     lib.mipt_query_occluded_device.restype = C.c_int
+    ro = C.POINTER(MiptRadianceOptions)
+    lib.mipt_query_radiance.argtypes = [vp, vp, u64, ro, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_radiance.restype = C.c_int
+    lib.mipt_query_radiance_device.argtypes = [vp, vp, u64, ro, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_query_radiance_device.restype = C.c_int
     fb = C.POINTER(MiptFeatureBuffers)
     lib.mipt_render_features.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, C.POINTER(MiptStats)]
     lib.mipt_render_features.restype = C.c_int

@@ -111,6 +111,12 @@ int trace_blocks_per_cu(bool batch, bool count, bool cull, int shading);     // 
 hipError_t launch_trace_adaptive(const DevScene &sc, const DevParams &pr, const DevBatch &batch, const uint32_t *counts, bool count, bool cull,
                                  int shading, int grid_blocks, hipStream_t stream);
 int trace_adaptive_blocks_per_cu(bool count, bool cull, int shading);        // occupancy query
+// The trace launch over the caller's rays (pt_trace_rays_kernel; mipt_query_radiance*): rays = n_rays x 32 B (MiptRay, the last
+// word the ray's seed), pr.total_work = n_rays, pr.hdr = n_rays x 3 f32.  Of pr the kernel reads samples, samples_f, max_depth,
+// sum_only, accumulate, cull_scale, the schedule, hdr, ovf and stats; everything about a frame, its tiles and its camera is unused.
+hipError_t launch_trace_rays(const DevScene &sc, const DevParams &pr, const float4 *rays, bool count, bool cull, int shading,
+                             int grid_blocks, hipStream_t stream);
+int trace_rays_blocks_per_cu(bool count, bool cull, int shading);            // occupancy query
 hipError_t launch_unpack_tiles(const float *packed_all, uint32_t width, uint32_t height,
                                uint32_t tile_world, float *hdr, hipStream_t stream);
 hipError_t launch_tonemap(const float *hdr, unsigned long long n_pixels, float divisor,

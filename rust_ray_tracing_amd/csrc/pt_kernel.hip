@@ -169,9 +169,15 @@ __device__ __forceinline__ bool shade_wgsl(const DevScene &sc, V3 &o, V3 &d, V3 
 // word, in L2 since the fetch -- where the single-view kernel issues its pixel_cost atomic.  A pixel with n == 0 is dropped at the
 // fetch like a ragged-edge slot: the lane stays ST_P, nothing is traced, counted or written (the host has zeroed the frame before
 // the launch unless it accumulates).  Writing the zeros here instead costs 8 B of scratch per lane.
-template <bool COUNT, bool CULL, int SHADING, bool BATCH, bool ADAPT = false>
-__device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch bt, const uint32_t *__restrict__ counts = nullptr) {
+// RAYS (without BATCH or ADAPT; pt_trace_rays_kernel, mipt_query_radiance*): the work is the caller's rays, not pixels.  Work index
+// i is ray i (pr.total_work = n_rays, kept in `pix`), its stream starts at the ray's own seed word and its output slot is i * 3.  No
+// tiles, no hot list, no pixel_cost, no camera: a sample's first segment is rays[i] as given, read again for every sample -- one
+// 32-B record, in L2 since the fetch -- so that origin and direction are not six more registers live through the traversal loop.
+template <bool COUNT, bool CULL, int SHADING, bool BATCH, bool ADAPT = false, bool RAYS = false>
+__device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch bt, const uint32_t *__restrict__ counts = nullptr,
+                                           const float4 *__restrict__ rays = nullptr) {
     static_assert(BATCH || !ADAPT, "the count plane is addressed by (view, pixel): batch launches only");
+    static_assert(!RAYS || (!BATCH && !ADAPT), "a ray launch has no views and no count plane");
     __shared__ uint32_t s_stack[kWavesPerBlock][kStackLds + 1][64];   // row kStackLds: scratch target of the branch-free push
     __shared__ double s_logtab[32];                                    // __logf_data.tab (16 x {invc, logc}) for gl_log10f
     __shared__ __attribute__((aligned(16))) float s_draw[kWavesPerBlock][64 * 6];                   // scatter draws of a service pass: 3 x {u_theta, u_rho} per hit lane, compacted
@@ -303,7 +309,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                 if (path_done) {
                     // tile order, hot pixels: this path's rays, added to its pixel's cost (slot = local tile * 64 + pixel of the tile);
                     // the sums per tile are taken behind the launch (pixel_reduce_kernel)
-                    if (!BATCH && pr.pixel_cost) atomicAdd(&pr.pixel_cost[slot], bounces + ((best_tri == kNoTri) ? 1u : 0u));
+                    if (!BATCH && !RAYS && pr.pixel_cost) atomicAdd(&pr.pixel_cost[slot], bounces + ((best_tri == kNoTri) ? 1u : 0u));
                     const V3 res = (bounces == 0u) ? incoming : incoming / (float)bounces; // ray.rs:197-201
                     final_color = final_color + res;                                 // cpu.rs:52
                     sample += 1;
@@ -316,7 +322,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                         state = ST_G;
                     } else {
                         if (!pr.sum_only) final_color = final_color / (ADAPT ? (float)n_samples : pr.samples_f);  // cpu.rs:60
-                        float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)(pr.packed ? slot : pix)) * 3;
+                        float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)((!RAYS && pr.packed) ? slot : pix)) * 3;
                         if (pr.accumulate) {      // progressive rendering: add this call's samples to the running sum
                             final_color = mk(dst[0] + final_color.x, dst[1] + final_color.y, dst[2] + final_color.z);
                         }
@@ -344,6 +350,12 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                         if (wi >= pr.total_work) {
                             state = ST_X;
                             if (COUNT && g_t_first_x == 0) g_t_first_x = clock64();
+                        } else if (RAYS) {                                    // ray wi: its seed is the last word of its record
+                            pix = (uint32_t)wi;
+                            rng = __float_as_uint(rays[(size_t)pix * 2 + 1].w);
+                            final_color = mk(0.0f, 0.0f, 0.0f);
+                            sample = 0;
+                            state = ST_G;
                         } else {
                             // 8x8 pixel tiles, round-robin over ranks: global tile = local*world + rank
                             // hot pixels: the first pr.n_list work indices are the most expensive pixels of the frame before, one by
@@ -395,28 +407,34 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
             }
             // ---- camera ray (cpu.rs:37-50) ----
             if (state == ST_G) {
-                if (SHADING == 1 || pr.seed_mode != 0u) {                             // rt_compute.wgsl:102
-                    const uint32_t px = pix % pr.width, py = pix / pr.width;
-                    rng = (pr.sample_begin + sample) * 6023u + (757283u * px + 872653746u * py);
-                }
-                const float jx = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
-                const float jy = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
-                const float rx = -screen_x + jx, ry = screen_y + jy, rz = 1.0f;
-                // Mat4f * Vec3f, upper-left 3x3, data[col][row] (mat4.rs:143-152)
-                if (BATCH) {
-                    const float4 *cr = bt.cams + (size_t)view * 4;
-                    const float4 c0 = cr[0], c1 = cr[1], c2 = cr[2], c3 = cr[3];
-                    const V3 dir = mk(c0.x * rx + c1.x * ry + c2.x * rz,
-                                      c0.y * rx + c1.y * ry + c2.y * rz,
-                                      c0.z * rx + c1.z * ry + c2.z * rz);
-                    d = normalized(dir);
-                    o = mk(c3.x, c3.y, c3.z);
+                if (RAYS) {                                                           // the caller's ray, as given: no jitter, no reseed
+                    const float4 r0 = rays[(size_t)pix * 2], r1 = rays[(size_t)pix * 2 + 1];
+                    o = mk(r0.x, r0.y, r0.z);
+                    d = mk(r1.x, r1.y, r1.z);
                 } else {
-                    const V3 dir = mk(pr.cam[0] * rx + pr.cam[3] * ry + pr.cam[6] * rz,
-                                      pr.cam[1] * rx + pr.cam[4] * ry + pr.cam[7] * rz,
-                                      pr.cam[2] * rx + pr.cam[5] * ry + pr.cam[8] * rz);
-                    d = normalized(dir);
-                    o = mk(pr.cam[9], pr.cam[10], pr.cam[11]);
+                    if (SHADING == 1 || pr.seed_mode != 0u) {                             // rt_compute.wgsl:102
+                        const uint32_t px = pix % pr.width, py = pix / pr.width;
+                        rng = (pr.sample_begin + sample) * 6023u + (757283u * px + 872653746u * py);
+                    }
+                    const float jx = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
+                    const float jy = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
+                    const float rx = -screen_x + jx, ry = screen_y + jy, rz = 1.0f;
+                    // Mat4f * Vec3f, upper-left 3x3, data[col][row] (mat4.rs:143-152)
+                    if (BATCH) {
+                        const float4 *cr = bt.cams + (size_t)view * 4;
+                        const float4 c0 = cr[0], c1 = cr[1], c2 = cr[2], c3 = cr[3];
+                        const V3 dir = mk(c0.x * rx + c1.x * ry + c2.x * rz,
+                                          c0.y * rx + c1.y * ry + c2.y * rz,
+                                          c0.z * rx + c1.z * ry + c2.z * rz);
+                        d = normalized(dir);
+                        o = mk(c3.x, c3.y, c3.z);
+                    } else {
+                        const V3 dir = mk(pr.cam[0] * rx + pr.cam[3] * ry + pr.cam[6] * rz,
+                                          pr.cam[1] * rx + pr.cam[4] * ry + pr.cam[7] * rz,
+                                          pr.cam[2] * rx + pr.cam[5] * ry + pr.cam[8] * rz);
+                        d = normalized(dir);
+                        o = mk(pr.cam[9], pr.cam[10], pr.cam[11]);
+                    }
                 }
                 ray_color = mk(1.0f, 1.0f, 1.0f);                                     // ray.rs:142-146
                 incoming = mk(0.0f, 0.0f, 0.0f);
@@ -864,6 +882,22 @@ static hipError_t launch_a(const DevScene &sc, const DevParams &pr, const DevBat
     hipLaunchKernelGGL((pt_trace_adaptive_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr, bt, counts);
     return hipGetLastError();
 }
+// The caller's rays (mipt_query_radiance*): ray i's samples on the stream its own seed starts, the result at radiance[i * 3].
+template <bool COUNT, bool CULL, int SHADING>
+__global__ MIPT_TRACE_BOUNDS(COUNT, CULL, SHADING) void pt_trace_rays_kernel(DevScene sc, DevParams pr, const float4 *__restrict__ rays) {
+    trace_body<COUNT, CULL, SHADING, false, false, true>(sc, pr, DevBatch{}, nullptr, rays);
+}
+template <bool COUNT, bool CULL, int SHADING, bool>
+static hipError_t launch_r(const DevScene &sc, const DevParams &pr, const float4 *rays, int grid, hipStream_t stream) {
+    hipLaunchKernelGGL((pt_trace_rays_kernel<COUNT, CULL, SHADING>), dim3(grid), dim3(kBlockThreads), 0, stream, sc, pr, rays);
+    return hipGetLastError();
+}
+template <bool COUNT, bool CULL, int SHADING, bool>
+static int occ_r() {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pt_trace_rays_kernel<COUNT, CULL, SHADING>, kBlockThreads, 0) != hipSuccess) n = 1;
+    return n;
+}
 template <bool COUNT, bool CULL, int SHADING, bool>
 static int occ_a() {
     int n = 0;
@@ -899,6 +933,18 @@ hipError_t launch_trace_adaptive(const DevScene &sc, const DevParams &pr, const 
 static int occ_dispatch_adaptive(bool count, bool cull, int shading) { MIPT_DISPATCH_B(occ_a, true); }
 int trace_adaptive_blocks_per_cu(bool count, bool cull, int shading) {
     int n = occ_dispatch_adaptive(count, cull, shading);
+    if (n < 1) n = 1;
+    if (n > 8) n = 8;
+    return n;
+}
+// the ray instantiations: {CPU-backend shading, wgpu-shader shading} x {count, cull}
+hipError_t launch_trace_rays(const DevScene &sc, const DevParams &pr, const float4 *rays, bool count, bool cull, int shading, int grid,
+                             hipStream_t stream) {
+    MIPT_DISPATCH_B(launch_r, false, sc, pr, rays, grid, stream);
+}
+static int occ_dispatch_rays(bool count, bool cull, int shading) { MIPT_DISPATCH_B(occ_r, false); }
+int trace_rays_blocks_per_cu(bool count, bool cull, int shading) {
+    int n = occ_dispatch_rays(count, cull, shading);
     if (n < 1) n = 1;
     if (n > 8) n = 8;
     return n;

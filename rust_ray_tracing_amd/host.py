@@ -570,6 +570,74 @@ class Scene:  # scene.rs:12-19
         raw, stats = self._query(True, rays, t_max, traversal, cull_margin, count, handle, stream)
         return raw != 0, stats
 
+    # -- radiance queries (include/mipt.h "radiance queries") -------------------------------------
+    @staticmethod
+    def radiance_default_seeds(n: int, first: int = 0) -> np.ndarray:
+        """The seeds ``query_radiance`` gives rays first ... first + n - 1 when the caller brings none: the pixel formula of
+        cpu.rs:28-29, 987612486 * (i + 87636354) mod 2^32, with 1 where that is 0 (a zero seed is a stuck xorshift stream)."""
+        i = np.arange(first, first + n, dtype=np.uint64)
+        s = ((np.uint64(987612486) * (i + np.uint64(87636354))) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        s[s == 0] = 1
+        return s
+
+    def query_radiance(self, rays, seeds=None, samples: int = 1, max_ray_depth: int = 8, traversal: int = L.TRAVERSAL_REFERENCE,
+                       cull_margin: float = L.CULL_MARGIN_SAFE, shading: int = 0, sum_only: bool = False, accumulate_into=None,
+                       count: bool = False, handle=None, stream=None):
+        """Path-traced radiance along every ray on the resident scene (mipt_query_radiance / _device): ``samples`` paths of at most
+        ``max_ray_depth`` segments per ray on one xorshift stream that starts at the ray's seed, their mean (``sum_only``: their
+        sum).  ``rays`` as for ``query_closest`` (t_max is not used).  ``seeds``: n uint32 values; None = ``radiance_default_seeds``
+        -- except for an (n, 8) device tensor, whose last column is then the caller's seeds (int32 bits).  ``accumulate_into``: a
+        float32 device tensor [n, 3] the call's sums are added to (device rays only; implies ``sum_only``; bring fresh seeds every
+        call).  Returns (radiance [n, 3] float32 array or tensor, stats)."""
+        where, r = self._query_rays(rays, None)
+        h = handle if handle is not None else self._handle
+        if h is None:
+            raise RuntimeError("scene is not resident on a device")
+        n = len(r)
+        given = seeds is not None
+        if given:
+            s = seeds.detach().cpu().numpy() if self._is_torch(seeds) else np.asarray(seeds)
+            if s.shape != (n,) or s.dtype.kind not in "iu" or s.dtype.itemsize != 4:
+                raise ValueError(f"seeds: expected {n} 32-bit integers")
+            s = np.ascontiguousarray(s).view(np.uint32)
+        elif where == "host" or isinstance(rays, (tuple, list)):
+            s, given = self.radiance_default_seeds(n), True
+        opt = L.MiptRadianceOptions()
+        opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading = samples, max_ray_depth, traversal, cull_margin, shading
+        opt.flags = (L.FLAG_COUNT if count else 0) | (L.FLAG_SUM if sum_only or accumulate_into is not None else 0)
+        st = L.MiptStats()
+        lib = L.load()
+        if where == "host":
+            if accumulate_into is not None:
+                raise ValueError("accumulate_into needs device rays: the running sum lives in a device tensor")
+            r = r.copy()                                       # the caller's array keeps its last column
+            r["reserved"] = s
+            out = np.zeros((n, 3), dtype=np.float32)
+            f = lib.mipt_query_radiance
+            rc = f(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out) if n else C.c_void_p(16), C.byref(st))
+        else:
+            import torch
+            if given:
+                if r is rays:
+                    r = r.clone()
+                r[:, 7] = torch.from_numpy(s.view(np.int32)).to(r.device).view(torch.float32)
+            if accumulate_into is not None:
+                out = accumulate_into
+                if not self._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != r.device or not out.is_contiguous():
+                    raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the rays' device")
+                opt.flags |= L.FLAG_ACCUM
+            else:
+                out = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            if stream is None:
+                stream = torch.cuda.current_stream(r.device).cuda_stream
+            elif hasattr(stream, "cuda_stream"):
+                stream = stream.cuda_stream
+            f = lib.mipt_query_radiance_device
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, stream, C.byref(st))
+        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
+            L.check(rc, f.__name__)
+        return out, st.as_dict()
+
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
         h = handle if handle is not None else self._handle

@@ -1,0 +1,396 @@
+"""GPU: mipt_query_radiance / mipt_query_radiance_device (pt_trace_rays_kernel, csrc/pt_kernel.hip) against the model of
+tests/tools/radiance_model.py: a Python loop over the oracle's one-ray entries with one rng word carried across a ray's samples and
+the f32 sum and divide in numpy.  Every comparison is bit for bit on the u32 words.  The distinct rays of a case stay few enough for
+the model; batches larger than one launch holds in flight repeat a modelled pool.  The culled arm runs at margin 0, the rule the
+one-ray oracle entries restate."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import launch_thresholds as LT  # noqa: E402
+import radiance_model as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+REF, CULL = 0, 1
+POOL = 3001                                    # the distinct rays of a scene: every case takes its rays from the head of this pool
+POOL_SEED = 20                                 # chosen on the CPU: with it the oracle alone meets R.conditions on every scene and prefix used
+SENTINEL = 0x7FA5A5A5                          # a NaN pattern no radiance has
+
+
+def _build_scene(rrt, kind):
+    from rust_ray_tracing_amd import synth
+    import wgsl_scenes as S
+    if kind == "wgsl_pbr":                                                         # tests/test_gpu_parity.py PRODUCT_CASES: textures in all six slots
+        return S.pbr_scene(rrt, n_target=20000, tex_size=16)
+    kw = dict(n_target=4000, tex_size=64) if kind == "helmet" else {}
+    tris, mats, texs, cam = synth.make_scene(kind, **kw)
+    sc = rrt.Scene.from_arrays(tris, mats, texs)
+    sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+    return sc
+
+
+_scenes, _models = {}, {}
+
+
+def _case(rrt, orc, kind):
+    """(resident host-built Scene, R.Model, the pool of POOL rays, first-segment hits [POOL]) -- made once per scene, left unchanged"""
+    if kind not in _scenes:
+        sc = _build_scene(rrt, kind)
+        m = R.Model(orc, sc)
+        rays = R.make_rays(sc.tris, POOL, seed=POOL_SEED)
+        first = m.first_hits(rays)
+        sc.upload(0)
+        _scenes[kind] = (sc, m, rays, first)
+    return _scenes[kind]
+
+
+def _model(rrt, orc, kind, n, samples, depth, shading, cull, seeds=None):
+    """the model's output for the first n rays of the pool (optionally with other seeds), computed once, conditions asserted"""
+    key = (kind, n, samples, depth, shading, cull, None if seeds is None else seeds.tobytes())
+    if key not in _models:
+        sc, m, rays, first = _case(rrt, orc, kind)
+        r = rays[:n].copy()
+        if seeds is not None:
+            r["reserved"] = seeds
+        out = m.trace(r, samples, depth, shading=shading, cull=cull)
+        if n >= 40:
+            R.conditions(out, first[:n])
+        else:
+            assert not np.any(np.isnan(out["sum"]))
+        _models[key] = out
+    return _models[key]
+
+
+def _dev(rays):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(rays).view(np.int32).reshape(-1, 8).copy()).cuda().view(torch.float32)
+
+
+def _call(rrt, sc, rays, samples, depth, shading=0, traversal=REF, flags=0, device=False, handle=None, lib=None, d_rays=None, extra=4):
+    """One call of the C entry with a sentinel behind the output -> (rc, radiance [n, 3] f32, stats dict); the sentinel is asserted"""
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = lib or rrt.load()
+    n = len(rays)
+    opt = L.MiptRadianceOptions()
+    opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading, opt.flags = samples, depth, traversal, 0.0, shading, flags
+    st = L.MiptStats()
+    h = handle if handle is not None else sc._handle
+    if device:
+        d_r = d_rays if d_rays is not None else _dev(rays)
+        d_out = torch.full((n * 3 + extra,), SENTINEL, dtype=torch.int32, device="cuda")
+        rc = lib.mipt_query_radiance_device(h, d_r.data_ptr() if n else 16, n, C.byref(opt), d_out.data_ptr(), None, C.byref(st))
+        out = d_out.cpu().numpy().view(np.uint32)
+    else:
+        out = np.full(n * 3 + extra, SENTINEL, dtype=np.uint32)
+        r = np.ascontiguousarray(rays)
+        rc = lib.mipt_query_radiance(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out), C.byref(st))
+    assert np.all(out[n * 3:] == SENTINEL), "written past n * 3 floats"
+    return rc, out[: n * 3].view(np.float32).reshape(n, 3), st.as_dict()
+
+
+def _bad_rows(got, want):
+    g, w = np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)
+    bad = np.flatnonzero((g != w).any(axis=1))
+    return len(bad), [(int(i), g[i].tolist(), w[i].tolist()) for i in bad[:4]]
+
+
+# ---- model parity: the product scenes, both traversals, both shading modes, both entries -------------------------------------------
+@pytest.mark.parametrize("traversal", [REF, CULL])
+@pytest.mark.parametrize("kind,shading", [("cornell", 0), ("cornell", 1), ("helmet", 0), ("helmet", 1), ("wgsl_pbr", 1), ("wgsl_pbr", 0)])
+def test_model_parity(rrt, orc, kind, shading, traversal):
+    from rust_ray_tracing_amd import _lib as L
+    sc, _, rays, _ = _case(rrt, orc, kind)
+    n = 384
+    for samples, depth in ((1, 1), (1, 8), (3, 8)):            # three samples: a ray not read again at its second sample, or a stream reseeded, shows
+        want = _model(rrt, orc, kind, n, samples, depth, shading, traversal)
+        for device in (False, True):
+            for flags in (0, L.FLAG_COUNT):
+                rc, got, st = _call(rrt, sc, rays[:n], samples, depth, shading, traversal, flags, device)
+                assert rc == 0 and R.same_bits(got, want["mean"]), (kind, shading, traversal, samples, depth, device, flags, _bad_rows(got, want["mean"]))
+                assert st["kernel_ms"] > 0 and st["stack_overflows"] == 0 and st["pixels"] == n
+
+
+# ---- ray counts: partial waves, whole waves, one more; nothing is written past the end ----------------------------------------------
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 0])
+def test_ray_counts_and_sentinel(rrt, orc, n):
+    sc, _, rays, _ = _case(rrt, orc, "cornell")
+    want = _model(rrt, orc, "cornell", n, 2, 6, 0, REF)["mean"] if n else np.zeros((0, 3), np.float32)
+    for device in (False, True):
+        rc, got, st = _call(rrt, sc, rays[:n], 2, 6, device=device)
+        assert rc == 0 and R.same_bits(got, want), (n, device, _bad_rows(got, want))
+        if n == 0:
+            assert st["kernel_ms"] == 0.0 and st["pixels"] == 0                    # no launch
+
+
+def test_index_independence(rrt, orc):
+    sc, _, rays, _ = _case(rrt, orc, "helmet")
+    n = 257
+    want = _model(rrt, orc, "helmet", n, 3, 8, 0, REF)["mean"]
+    for order in (np.arange(n)[::-1], np.roll(np.arange(n), 100)):
+        for device in (False, True):
+            rc, got, _ = _call(rrt, sc, rays[:n][order], 3, 8, device=device)
+            assert rc == 0 and R.same_bits(got, want[order]), (device, _bad_rows(got, want[order]))
+
+
+# ---- flags ---------------------------------------------------------------------------------------------------------------------------
+def test_sum_and_accumulate(rrt, orc):
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, _, rays, _ = _case(rrt, orc, "helmet")
+    n, samples, depth = 300, 3, 8
+    a = _model(rrt, orc, "helmet", n, samples, depth, 0, REF)
+    assert not R.same_bits(a["sum"], a["mean"] * np.float32(samples))              # the undivided sum is not the mean multiplied back
+    for device in (False, True):
+        rc, got, _ = _call(rrt, sc, rays[:n], samples, depth, flags=L.FLAG_SUM, device=device)
+        assert rc == 0 and R.same_bits(got, a["sum"]), (device, _bad_rows(got, a["sum"]))
+    # ACCUM twice with two seed sets: the f32 sum of the two SUM results, added in that order, on top of what the buffer held
+    seeds2 = R.default_seeds(n, first=5000)
+    b = _model(rrt, orc, "helmet", n, samples, depth, 0, REF, seeds=seeds2)
+    r2 = rays[:n].copy()
+    r2["reserved"] = seeds2
+    opt = L.MiptRadianceOptions()
+    opt.samples, opt.max_ray_depth, opt.flags = samples, depth, L.FLAG_SUM | L.FLAG_ACCUM
+    d_acc = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    for r in (rays[:n], r2):
+        d_r = _dev(r)
+        assert lib.mipt_query_radiance_device(sc._handle, d_r.data_ptr(), n, C.byref(opt), d_acc.data_ptr(), None, None) == 0
+    want = (np.zeros((n, 3), np.float32) + a["sum"]) + b["sum"]
+    assert R.same_bits(d_acc.cpu().numpy(), want)
+    # the wrapper: the same through accumulate_into, seeds as an argument
+    d_acc2 = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    o, d = torch.from_numpy(rays["origin"][:n].copy()).cuda(), torch.from_numpy(rays["direction"][:n].copy()).cuda()
+    for s in (rays["reserved"][:n], seeds2):
+        out, _ = sc.query_radiance((o, d), seeds=s, samples=samples, max_ray_depth=depth, accumulate_into=d_acc2)
+        assert out is d_acc2
+    assert R.same_bits(d_acc2.cpu().numpy(), want)
+    # refused on the host entry, and the scene answers as before
+    out = np.zeros((n, 3), np.float32)
+    assert lib.mipt_query_radiance(sc._handle, L.ptr(np.ascontiguousarray(rays[:n])), n, C.byref(opt), L.ptr(out), None) == L.ERR_INVALID_ARG
+    assert "mipt_query_radiance_device" in lib.mipt_last_error().decode() and not out.any()
+    rc, got, _ = _call(rrt, sc, rays[:n], samples, depth)
+    assert rc == 0 and R.same_bits(got, a["mean"])
+
+
+def test_wrapper_default_seeds_and_ray_forms(rrt, orc):
+    sc, _, rays, _ = _case(rrt, orc, "cornell")
+    n = 200
+    assert np.array_equal(rays["reserved"][:n], R.default_seeds(n))                # the pool carries the default seeds
+    want = _model(rrt, orc, "cornell", n, 2, 6, 0, CULL)["mean"]
+    o, d = np.ascontiguousarray(rays["origin"][:n]), np.ascontiguousarray(rays["direction"][:n])
+    zeroed = rays[:n].copy()
+    zeroed["reserved"] = 0
+    for form in ((o, d), zeroed, zeroed.view(np.float32).reshape(-1, 8)):          # host arrays: the seed column is not the caller's
+        got, st = sc.query_radiance(form, samples=2, max_ray_depth=6, traversal=CULL, cull_margin=0.0)
+        assert got.shape == (n, 3) and got.dtype == np.float32 and R.same_bits(got, want) and st["pixels"] == n
+    assert not zeroed["reserved"].any()                                            # and the caller's array keeps its own
+    got, _ = sc.query_radiance(_dev(rays[:n]), samples=2, max_ray_depth=6, traversal=CULL, cull_margin=0.0)   # (n, 8) tensor: its own seeds
+    assert got.is_cuda and R.same_bits(got.cpu().numpy(), want)
+
+
+# ---- COUNT ---------------------------------------------------------------------------------------------------------------------------
+KEYS = ("rays", "inner_steps", "tri_tests", "hits", "texel_fetches")
+
+
+@pytest.mark.parametrize("kind,shading", [("helmet", 0), ("wgsl_pbr", 1)])
+def test_counting_build(rrt, orc, kind, shading):
+    from rust_ray_tracing_amd import _lib as L
+    sc, m, rays, first = _case(rrt, orc, kind)
+    n, samples = 300, 3
+    r = rays[:n]
+    for traversal in (REF, CULL):
+        want = _model(rrt, orc, kind, n, samples, 8, shading, traversal)
+        _, plain, st0 = _call(rrt, sc, r, samples, 8, shading, traversal, 0, device=True)
+        rc, got, st = _call(rrt, sc, r, samples, 8, shading, traversal, L.FLAG_COUNT, device=True)
+        assert rc == 0 and R.same_bits(got, plain) and R.same_bits(got, want["mean"])     # the same bits as the product build
+        assert st["pixels"] == n and st["rays"] >= n * samples and st0["rays"] == 0 and st0["pixels"] == n
+        assert st["diag"][0] > 0 and st["diag"][5] > 0 and st["diag"][8] > 0            # iterations, service passes, cycles: filled as by a batch launch
+        if shading == 1:                                                           # the wgsl oracle entry counts
+            assert {k: st[k] for k in KEYS} == dict(zip(KEYS, want["counters"].sum(0).tolist())), (traversal, st)
+        # a batch's counters are the sums of its halves'
+        half = [_call(rrt, sc, part, samples, 8, shading, traversal, L.FLAG_COUNT)[2] for part in (r[: n // 2 + 7], r[n // 2 + 7:])]
+        assert {k: st[k] for k in KEYS} == {k: half[0][k] + half[1][k] for k in KEYS}
+        assert st["max_stack"] == max(half[0]["max_stack"], half[1]["max_stack"]) and half[0]["pixels"] + half[1]["pixels"] == n
+    # one segment per path: every sample traces the ray itself, and hits what mipt_query_closest finds
+    q = r.copy()
+    q["t_max"] = 1e30
+    hits, _ = sc.query_closest(q)
+    n_hit = int(hits["hit"].sum())
+    assert n_hit == int(first[:n].sum()) and 0 < n_hit < n
+    rc, _, st = _call(rrt, sc, r, samples, 1, shading, REF, L.FLAG_COUNT)
+    assert rc == 0 and st["rays"] == n * samples and st["hits"] == samples * n_hit, st
+
+
+# ---- batches past the lanes in flight ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", ["mid", "full"])
+@pytest.mark.parametrize("kind,shading,traversal", [("cornell", 0, REF), ("cornell", 0, CULL), ("wgsl_pbr", 1, CULL)])
+def test_batches_past_the_lanes_in_flight(rrt, orc, kind, shading, traversal, size):
+    from rust_ray_tracing_amd import _lib as L
+    n_cu = LT.device_n_cu()
+    n = LT.mid(n_cu) if size == "mid" else LT.full(n_cu)
+    (LT.check_mid if size == "mid" else LT.check_full)(n_cu, n)
+    sc, _, pool, _ = _case(rrt, orc, kind)
+    samples, depth = 2, 5
+    want = _model(rrt, orc, kind, POOL, samples, depth, shading, traversal)
+    idx = (7 * np.arange(n, dtype=np.int64) + 3) % POOL
+    rays = np.ascontiguousarray(pool[idx])
+    want_rows = want["mean"][idx]
+    d_rays = _dev(rays)
+    for device in (False, True):
+        for flags in (0, L.FLAG_COUNT):
+            rc, got, st = _call(rrt, sc, rays, samples, depth, shading, traversal, flags, device, d_rays=d_rays)
+            assert rc == 0 and R.same_bits(got, want_rows), (kind, size, device, flags, _bad_rows(got, want_rows))
+            assert st["pixels"] == n and st["stack_overflows"] == 0
+            if flags and shading == 1:
+                assert {k: st[k] for k in KEYS} == dict(zip(KEYS, want["counters"][idx].sum(0).tolist()))
+
+
+# ---- scene state -----------------------------------------------------------------------------------------------------------------------
+def _render(rrt, sc):
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=3, output_image_dimensions=(32, 24), output_image_path="/dev/null"))
+    return r.render_buffers(sc)[0].view(np.uint32).copy()
+
+
+def test_radiance_follows_refit_and_rebuild(rrt, orc):
+    from rust_ray_tracing_amd import _lib as L
+    sc = _build_scene(rrt, "helmet")
+    sc.upload(0)
+    rays = R.make_rays(sc.tris, 256, seed=5)
+    before = R.Model(orc, sc).trace(rays, 2, 6)
+    rc, got, _ = _call(rrt, sc, rays, 2, 6)
+    assert rc == 0 and R.same_bits(got, before["mean"])
+    sc.tris["vertices"]["position"][:, :, 1] *= np.float32(0.75)                   # REFIT: squash the geometry, keep the tree
+    sc.update_device(L.UPDATE_REFIT)
+    m = R.Model(orc, sc)
+    after = m.trace(rays, 2, 6)
+    R.conditions(after, m.first_hits(rays))
+    assert not R.same_bits(after["mean"], before["mean"])
+    for device in (False, True):
+        rc, got, _ = _call(rrt, sc, rays, 2, 6, device=device)
+        assert rc == 0 and R.same_bits(got, after["mean"]), ("refit", device, _bad_rows(got, after["mean"]))
+    sc.tris = np.ascontiguousarray(sc.tris[: len(sc.tris) - 37]).copy()            # REBUILD with another triangle count: a new tree
+    sc.update_device(L.UPDATE_REBUILD)
+    m = R.Model(orc, sc)
+    for shading in (0, 1):
+        rebuilt = m.trace(rays, 2, 6, shading=shading, cull=1)
+        R.conditions(rebuilt, m.first_hits(rays))
+        for device in (False, True):
+            rc, got, _ = _call(rrt, sc, rays, 2, 6, shading, CULL, device=device)
+            assert rc == 0 and R.same_bits(got, rebuilt["mean"]), ("rebuild", shading, device, _bad_rows(got, rebuilt["mean"]))
+
+
+def test_replica_handle_answers_the_same(rrt, orc):
+    from rust_ray_tracing_amd import _lib as L
+    mt = L.load_multitest()
+    sc, _, rays, _ = _case(rrt, orc, "cornell")
+    n = 300
+    want = _model(rrt, orc, "cornell", n, 3, 8, 0, REF)["mean"]
+    d = sc.desc()
+    multi = C.c_void_p()
+    assert mt.mipt_multi_create(C.byref(d), (C.c_int * 2)(0, 0), 2, C.byref(multi)) == 0, mt.mipt_last_error()
+    try:
+        for rank in (0, 1):
+            for device in (False, True):
+                rc, got, st = _call(rrt, sc, rays[:n], 3, 8, device=device, handle=mt.mipt_multi_scene(multi, rank), lib=mt)
+                assert rc == 0 and R.same_bits(got, want) and st["pixels"] == n, (rank, device)
+    finally:
+        mt.mipt_multi_destroy(multi)
+
+
+# ---- the torch path and the device entry's refusals ---------------------------------------------------------------------------------
+def test_torch_tensors_on_a_side_stream_match_the_host_entry(rrt, orc):
+    import torch
+    sc, _, rays, _ = _case(rrt, orc, "wgsl_pbr")
+    n = 500
+    kw = dict(samples=2, max_ray_depth=6, traversal=CULL, cull_margin=0.0, shading=1)
+    host, _ = sc.query_radiance(rays[:n], seeds=rays["reserved"][:n], **kw)
+    assert R.same_bits(host, _model(rrt, orc, "wgsl_pbr", n, 2, 6, 1, CULL)["mean"])
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        d_rays = _dev(rays[:n]).clone()                        # produced on the side stream: the query is ordered after it
+        dev, st = sc.query_radiance(d_rays, **kw)
+        dev2, _ = sc.query_radiance(d_rays, stream=side.cuda_stream, **kw)
+    side.synchronize()
+    assert dev.is_cuda and dev.shape == (n, 3) and R.same_bits(dev.cpu().numpy(), host) and R.same_bits(dev2.cpu().numpy(), host)
+
+
+def test_device_entry_refusals_leave_the_scene_rendering(rrt, orc):
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    lib = rrt.load()
+    sc, _, rays, _ = _case(rrt, orc, "cornell")
+    before = _render(rrt, sc)
+    n = 64
+    d_buf = torch.zeros((n * 8 + 8,), dtype=torch.float32, device="cuda")
+    d_buf[: n * 8] = _dev(rays[:n]).reshape(-1)
+    d_out = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    opt = L.MiptRadianceOptions()
+    opt.samples, opt.max_ray_depth = 2, 6
+    h_out = np.zeros(n * 3, dtype=np.float32)
+    h_rays = np.zeros(n * 32 + 16, dtype=np.uint8)                                 # an aligned address inside an over-allocated buffer
+    r_ptr = h_rays.ctypes.data + (-h_rays.ctypes.data) % 16
+    f = lib.mipt_query_radiance_device
+    for args, msg in (((sc._handle, d_buf.data_ptr(), n, C.byref(opt), h_out.ctypes.data, None, None), "d_radiance is not device memory"),
+                      ((sc._handle, r_ptr, n, C.byref(opt), d_out.data_ptr(), None, None), "d_rays is not device memory"),
+                      ((sc._handle, d_buf.data_ptr() + 4, n, C.byref(opt), d_out.data_ptr(), None, None), "d_rays must be 16-byte aligned"),
+                      ((sc._handle, d_buf.data_ptr(), n, C.byref(opt), d_buf.data_ptr() + 32 * (n - 1) + 16, None, None), "d_rays overlaps d_radiance")):
+        assert f(*args) == L.ERR_INVALID_ARG, msg
+        assert msg in lib.mipt_last_error().decode(), lib.mipt_last_error()
+    assert torch.count_nonzero(d_out).item() == 0 and not h_out.any()
+    assert np.array_equal(_render(rrt, sc), before)                                # the scene renders bit-exactly afterwards
+    rc, got, _ = _call(rrt, sc, rays[:n], 2, 6, device=True)
+    assert rc == 0 and R.same_bits(got, _model(rrt, orc, "cornell", n, 2, 6, 0, REF)["mean"])
+
+
+# ---- a tree deeper than the traversal stack --------------------------------------------------------------------------------------------
+def _chain_bvh(rrt, depth):
+    """A hand-built chain: every inner node has a FAR leaf child and a NEAR inner child for a ray along +x, so each level pushes one
+    stack entry and a ray along +x holds `depth` of them."""
+    from rust_ray_tracing_amd import NODE, TRIANGLE
+    n = depth + 1
+    tris = np.zeros(n, dtype=TRIANGLE)
+    xs = 1000.0 - np.arange(n, dtype=np.float32) * 2.0
+    for k in range(n):
+        tris["vertices"]["position"][k] = [(xs[k], -1, -1), (xs[k], 1, -1), (xs[k], 0, 1)]
+    tris["vertices"]["normal"] = (-1, 0, 0)
+    nodes = np.zeros(2 * n - 1, dtype=NODE)
+    nodes[0]["bounds_min"], nodes[0]["bounds_max"], nodes[0]["first_tri_or_child"] = (xs[-1], -1, -1), (xs[0], 1, 1), 1
+    for k in range(n - 1):
+        leaf, rest = 2 * k + 1, 2 * k + 2
+        nodes[leaf]["bounds_min"], nodes[leaf]["bounds_max"] = (xs[k], -1, -1), (xs[k], 1, 1)
+        nodes[leaf]["first_tri_or_child"], nodes[leaf]["num_tris"] = k, 1
+        nodes[rest]["bounds_min"], nodes[rest]["bounds_max"] = (xs[-1], -1, -1), (xs[k + 1], 1, 1)
+        last = k == n - 2
+        nodes[rest]["first_tri_or_child"], nodes[rest]["num_tris"] = (k + 1, 1) if last else (2 * k + 3, 0)
+    sc = rrt.Scene.from_arrays(tris, [rrt.material_default()], build_bvh=False)
+    sc.bvh_nodes = nodes
+    return sc
+
+
+def test_stack_overflow_is_reported_after_the_results(rrt, orc):
+    from rust_ray_tracing_amd import _lib as L
+    rng = np.random.default_rng(3)
+    n = 70
+    rays = np.zeros(n, dtype=R.RAY)
+    rays["origin"][:, 1:] = rng.uniform(-0.2, 0.2, (n, 2)).astype(np.float32)
+    rays["direction"][:, 0] = 1.0
+    rays["reserved"] = R.default_seeds(n)
+    sc = _chain_bvh(rrt, 40)                                                       # 40 entries: 16 in LDS, the rest spilled, none lost
+    sc.upload(0)
+    want = R.Model(orc, sc).trace(rays, 2, 3)
+    rc, got, st = _call(rrt, sc, rays, 2, 3, flags=L.FLAG_COUNT)
+    assert rc == 0 and R.same_bits(got, want["mean"]) and st["max_stack"] > 16 and st["stack_overflows"] == 0
+    deep = _chain_bvh(rrt, 120)                                                    # deeper than the 64-entry stack
+    deep.upload(0)
+    for device in (False, True):
+        rc, got, st = _call(rrt, deep, rays, 2, 3, device=device)
+        assert rc == L.ERR_STACK and st["stack_overflows"] > 0 and "stack" in rrt.load().mipt_last_error().decode()
+        assert not np.any(got.view(np.uint32) == SENTINEL) and st["pixels"] == n    # the output was written all the same
+    rc, got, st = _call(rrt, sc, rays, 2, 3)                                       # a normal scene answers as before
+    assert rc == 0 and R.same_bits(got, want["mean"]) and st["stack_overflows"] == 0
