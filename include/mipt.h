@@ -356,6 +356,103 @@ MIPT_API int mipt_query_radiance(MiptScene *scene, const MiptRay *rays, uint64_t
 MIPT_API int mipt_query_radiance_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt,
                                         float *d_radiance /* n_rays*3 */, void *hip_stream, MiptStats *stats);
 
+/* ---- baking: surface points and the light they gather ----------------------------------------------------------------------------
+ * The two steps a lightmap or vertex baker had to do on the host around mipt_query_radiance: find the surface point behind every
+ * lightmap texel (mipt_bake_texels: the scene's own UV layout, rasterised from tri_attr in HBM) and send one hemisphere ray per
+ * point and sample, sum what comes back (mipt_bake_gather).  Kernels: csrc/bake.hip; the paths run in the ray kernel of the
+ * radiance queries.  Every operator below is one rounded f32 operation, nothing is fused.
+ *
+ * The record.  MiptSurfacePoint = {seed, u, v, prim}.  prim is encoded as MiptHit.prim: the low 25 bits are the triangle in the
+ * caller's order (as for the queries), MIPT_HIT_NONE = no point.  Bit 31 (MIPT_HIT_FRONT_FACE) set selects the side the
+ * interpolated normal points to, bit 31 clear the reversed normal (ray.rs:46-48).  u, v are barycentrics, used as given: no range
+ * check.  An array of MiptHit whose `t` word has been overwritten with a seed is an array of points: what mipt_query_closest found
+ * can be handed to mipt_bake_gather as it is, once every record has its seed.
+ *
+ * mipt_bake_texels: texel -> surface point.  Texel (x, y) of a width x height atlas, index i = y * width + x, has its centre at
+ *     s = ((float)x + 0.5f) / (float)width        t = ((float)y + 0.5f) / (float)height
+ * Atlas row y is UV coordinate t: no flip, no wrap; UVs outside [0, 1] cover nothing there.  For a triangle with corner UVs a, b, c
+ * (tex_coord_x, tex_coord_y of vertices 0, 1, 2):
+ *     bx = b.x - a.x   by = b.y - a.y   cx = c.x - a.x   cy = c.y - a.y   px = s - a.x   py = t - a.y
+ *     d = (bx * cy) - (cx * by)
+ *     u = ((px * cy) - (cx * py)) / d             v = ((bx * py) - (px * by)) / d
+ *     covered  iff  d is finite and != 0  &&  u >= 0 && v >= 0 && (u + v) <= 1                                  (any NaN fails)
+ *                   &&  min(a.x, b.x, c.x) <= s <= max(a.x, b.x, c.x)  &&  min(a.y, b.y, c.y) <= t <= max(a.y, b.y, c.y)
+ * The last line compares f32 values exactly.  In exact arithmetic it follows from the line above it; in f32 it keeps a sliver whose
+ * d is mostly rounding noise from claiming texels along its extension, outside its own UV bounding box -- and makes the answer
+ * independent of which texels a launch visits for a triangle, as long as it visits every texel of that box.
+ * The owner of a texel is the covering triangle with the LOWEST INDEX IN THE CALLER'S ORDER, whatever the launch does.
+ *     points[i] = {seed = i, u, v, prim = owner | MIPT_HIT_FRONT_FACE}     u, v of the owner by the formulas above
+ *     points[i] = {i, 0, 0, MIPT_HIT_NONE}                                  no triangle covers the texel
+ * Every texel is written; nothing behind width * height records is touched.  Consequences: a texel centre exactly on an edge two
+ * triangles share goes to the lower index; rounding can leave such a texel to NEITHER triangle (each computes its own u, v);
+ * dilating the atlas over such holes and over the chart borders is the baker's job and out of scope here.
+ * Options: NULL = all zero; flags and reserved words must be 0.  info (may be NULL): covered_texels, degenerate_tris (triangles
+ * whose d is 0 or not finite) and kernel_ms (HIP events around the memsets and kernels).  Limit: width * height < 2^31; an
+ * atlas without texels (width or height 0) is MIPT_OK without a launch.  The workspace, 8 B per texel, belongs to the scene and
+ * grows on demand.  The device entry wants d_points 16-byte aligned.  Both entries see the UVs of the last successful update, like
+ * the queries, and work on a mesh scene and on a replica handle.
+ *
+ * mipt_bake_gather: the light a surface point gathers.  Point i lies on triangle k = prim & 0x01ffffff of the caller's array:
+ *     P = (v0 + e1 * u) + e2 * v          e1 = v1 - v0, e2 = v2 - v0, each rounded once (ray.rs:24-25)
+ *     N = (n0 * ((1 - u) - v) + n1 * u) + n2 * v       (ray.rs:45), reversed iff bit 31 is clear; not normalised, as in the reference
+ * Sample g = first_sample + s, s < samples, runs on a stream of its own:
+ *     rng = 987612486 * (seed + g * sample_stride + 87636354) mod 2^32, 1 in place of 0      (cpu.rs:28-29 with the point as the
+ *           pixel and the sample as the frame; all of it wraps)
+ *     new_dir = normalized(N + rand_in_unit_sphere(rng))                                       (ray.rs:179-181)
+ *     L = trace(ray = (P + new_dir * 0.0001, new_dir), max_ray_depth, rng)                     the stream continues into the trace
+ * trace is Ray::trace (MIPT_SHADING_CPU) or rt_compute.wgsl's trace (MIPT_SHADING_WGPU), as in the radiance queries.  The first
+ * scatter is the CPU rule in both: the point is a Lambertian receiver, `shading` selects only how the path goes on.
+ * The samples are summed in f32, in order, from +0, and the sum is divided by (float)samples unless MIPT_FLAG_SUM is set.
+ * MIPT_FLAG_ACCUM (device entry only, with MIPT_FLAG_SUM) adds the call's samples to d_radiance[i]: the ordered sum starts from
+ * the value found there instead of +0 and goes back there.  (The radiance query forms its sum apart and adds it with one addition;
+ * here the samples are added one by one ON the running value, so that a sum can be split between calls.)  Hence two SUM|ACCUM
+ * calls of 4 samples each, first_sample 0 and 4, into zeros, equal one SUM call of 8 samples bit for bit -- and so does any other
+ * split of the samples into consecutive calls.
+ * No pi is applied: the value is the mean radiance over the hemisphere (cosine-weighted for a unit N).  A lightmap that stores irradiance
+ * multiplies by pi; one that stores outgoing radiance of a diffuse surface multiplies by its albedo and nothing else.
+ * A MIPT_HIT_NONE point yields 0, 0, 0 and is left untouched under ACCUM.  Every other point's value depends on the point and the
+ * options only -- never on i, on n or on how the work was scheduled.  sample_stride = the number of points (the Python wrapper's
+ * default) gives every (point, sample) of an atlas whose seeds are 0 ... n-1 a seed of its own.
+ * Options (required): samples, max_ray_depth, sample_stride > 0; traversal / cull_margin / shading / flags as MiptRadianceOptions.
+ * stats (may be NULL): the work runs in chunks of at most 2^22 paths; counters are summed over the chunks, max_stack is their
+ * maximum, pixels counts paths, and kernel_ms runs from the first kernel of the call to its last.  The paths of MIPT_HIT_NONE
+ * points are counted as rays that miss.  Staging (32 + 12 B per path of a chunk, about 180 MB at most) and the map from the
+ * caller's triangle index to the device record (4 B per triangle, made on first use, dropped whenever the tree changes) belong to
+ * the scene.
+ * Errors: the radiance queries' list, with `points` for `rays` (d_points 16-byte aligned); sample_stride == 0; a prim whose
+ * triangle is >= the scene's count: MIPT_ERR_INVALID_ARG naming the first such index, found on the host by the host entry and by a
+ * kernel over all points by the device entry, before anything is traced and with the output untouched.  n == 0 is MIPT_OK
+ * without a launch.  MIPT_ERR_STACK is returned after all chunks have run and the results are written.  After any error the scene
+ * renders, queries and bakes as before. */
+typedef struct { uint32_t seed; float u, v; uint32_t prim; } MiptSurfacePoint;   /* 16 B */
+typedef struct { uint32_t flags; uint32_t reserved[7]; } MiptBakeTexelOptions;   /* 32 B; all 0 */
+typedef struct {
+    uint64_t covered_texels;  /* texels that have an owner */
+    uint32_t degenerate_tris; /* triangles whose UV determinant d is 0 or not finite: they cover nothing */
+    float    kernel_ms;
+    uint32_t reserved[4];
+} MiptBakeTexelInfo;         /* 32 B */
+typedef struct {
+    uint32_t samples;        /* > 0: paths per point */
+    uint32_t max_ray_depth;  /* > 0: segments behind the point */
+    uint32_t traversal;      /* MiptTraversal */
+    float    cull_margin;    /* as MiptRadianceOptions */
+    uint32_t shading;        /* MiptShading: how a path goes on behind its first segment */
+    uint32_t flags;          /* MIPT_FLAG_COUNT, MIPT_FLAG_SUM, MIPT_FLAG_ACCUM (device entry only, needs SUM) */
+    uint32_t first_sample;   /* g of this call's first sample */
+    uint32_t sample_stride;  /* > 0 */
+    uint32_t reserved[8];    /* must be 0 */
+} MiptBakeOptions;          /* 64 B */
+
+MIPT_API int mipt_bake_texels(MiptScene *scene, uint32_t width, uint32_t height, const MiptBakeTexelOptions *opt,
+                              MiptSurfacePoint *points /* width*height */, MiptBakeTexelInfo *info);
+MIPT_API int mipt_bake_texels_device(MiptScene *scene, uint32_t width, uint32_t height, const MiptBakeTexelOptions *opt,
+                                     MiptSurfacePoint *d_points /* width*height */, void *hip_stream, MiptBakeTexelInfo *info);
+MIPT_API int mipt_bake_gather(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, const MiptBakeOptions *opt,
+                              float *radiance /* n*3 */, MiptStats *stats);
+MIPT_API int mipt_bake_gather_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeOptions *opt,
+                                     float *d_radiance /* n*3 */, void *hip_stream, MiptStats *stats);
+
 /* ---- first-hit feature buffers: depth, ids, position, uv, normal, albedo, emission per pixel --------------------------------------
  * What the camera ray of every pixel hits and what the surface looks like there: the guide images of a denoiser, the id and depth
  * planes of a compositor, G-buffers for training data (csrc/first_hit.hip).  No path is traced: a sample ends at its first hit.

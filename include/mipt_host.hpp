@@ -91,6 +91,26 @@ inline int query_radiance_on(MiptScene *scene, const std::vector<MiptRay> &rays,
     if (rc != MIPT_OK) log_error(mipt_last_error());
     return rc;
 }
+// mipt_bake_texels on any resident scene handle: points[y * width + x] is the surface point behind texel (x, y) of the atlas the
+// scene's UVs lay out, prim == MIPT_HIT_NONE where no triangle covers the texel's centre (include/mipt.h "baking").
+inline int bake_texels_on(MiptScene *scene, uint32_t width, uint32_t height, std::vector<MiptSurfacePoint> &points, MiptBakeTexelInfo *info = nullptr) {
+    points.assign((size_t)width * height, MiptSurfacePoint{});
+    static MiptSurfacePoint no_point{};
+    const int rc = mipt_bake_texels(scene, width, height, nullptr, points.empty() ? &no_point : points.data(), info);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+// mipt_bake_gather on any resident scene handle: radiance[3 i .. 3 i + 3) is the light points[i] gathers over its hemisphere.
+// MIPT_ERR_STACK leaves the results written.
+inline int bake_gather_on(MiptScene *scene, const std::vector<MiptSurfacePoint> &points, std::vector<float> &radiance, const MiptBakeOptions &opt,
+                          MiptStats *stats = nullptr) {
+    radiance.assign(points.size() * 3, 0.0f);
+    static const MiptSurfacePoint no_point{};
+    static float no_value = 0.0f;
+    const int rc = mipt_bake_gather(scene, points.empty() ? &no_point : points.data(), points.size(), &opt, radiance.empty() ? &no_value : radiance.data(), stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
 
 // mipt_render_features on any resident scene handle: first-hit feature buffers (include/mipt.h "first-hit feature buffers") for
 // `cameras` with `opt`.  `wanted`: FeatureBit flags; only those images are computed and filled, each view-major [view][row][column][k]
@@ -352,6 +372,16 @@ class Scene {                                              // src/scene.rs:12-19
     int query_radiance(const std::vector<MiptRay> &rays, std::vector<float> &radiance, const MiptRadianceOptions &opt, MiptStats *stats = nullptr) const {
         MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
         return m ? query_radiance_on(mipt_multi_scene(m, 0), rays, radiance, opt, stats) : MIPT_ERR_HIP;
+    }
+    // baking (mipt_bake_texels, mipt_bake_gather), on the same replica: the surface points behind the texels of a lightmap atlas, and
+    // the light surface points gather
+    int bake_texels(uint32_t width, uint32_t height, std::vector<MiptSurfacePoint> &points, MiptBakeTexelInfo *info = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? bake_texels_on(mipt_multi_scene(m, 0), width, height, points, info) : MIPT_ERR_HIP;
+    }
+    int bake_gather(const std::vector<MiptSurfacePoint> &points, std::vector<float> &radiance, const MiptBakeOptions &opt, MiptStats *stats = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? bake_gather_on(mipt_multi_scene(m, 0), points, radiance, opt, stats) : MIPT_ERR_HIP;
     }
 
   private:

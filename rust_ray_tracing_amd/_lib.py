@@ -108,6 +108,31 @@ class MiptRadianceOptions(C.Structure):
 assert C.sizeof(MiptRadianceOptions) == 64
 
 
+# ---- baking (include/mipt.h "baking"): a MiptHit with a seed in its t word is a surface point ----
+SURFACE_POINT = np.dtype([("seed", "<u4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])                     # MiptSurfacePoint
+assert SURFACE_POINT.itemsize == 16
+
+
+class MiptBakeTexelOptions(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class MiptBakeTexelInfo(C.Structure):
+    _fields_ = [("covered_texels", C.c_uint64), ("degenerate_tris", C.c_uint32), ("kernel_ms", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class MiptBakeOptions(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("max_ray_depth", C.c_uint32), ("traversal", C.c_uint32), ("cull_margin", C.c_float),
+                ("shading", C.c_uint32), ("flags", C.c_uint32), ("first_sample", C.c_uint32), ("sample_stride", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+assert C.sizeof(MiptBakeOptions) == 64 and C.sizeof(MiptBakeTexelOptions) == 32 and C.sizeof(MiptBakeTexelInfo) == 32
+
+
 # ---- first-hit feature buffers (include/mipt.h "first-hit feature buffers") ----
 FEATURES = (("depth", 1, np.float32), ("prim", 1, np.uint32), ("material", 1, np.uint32), ("position", 3, np.float32),
             ("uv", 2, np.float32), ("normal", 3, np.float32), ("albedo", 3, np.float32), ("emission", 3, np.float32))   # name, values per pixel, type
@@ -265,6 +290,7 @@ EXPORTS = [
     "mipt_temporal_counts", "mipt_temporal_counts_device",
     "mipt_sample_map_fill_workspace_bytes", "mipt_sample_map_fill", "mipt_sample_map_fill_device",
     "mipt_query_radiance", "mipt_query_radiance_device",
+    "mipt_bake_texels", "mipt_bake_texels_device", "mipt_bake_gather", "mipt_bake_gather_device",
 ]
 
 _lib = None
@@ -393,6 +419,15 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_query_radiance.restype = C.c_int
     lib.mipt_query_radiance_device.argtypes = [vp, vp, u64, ro, vp, vp, C.POINTER(MiptStats)]
     lib.mipt_query_radiance_device.restype = C.c_int
+    bt, bi, bo = C.POINTER(MiptBakeTexelOptions), C.POINTER(MiptBakeTexelInfo), C.POINTER(MiptBakeOptions)
+    lib.mipt_bake_texels.argtypes = [vp, u32, u32, bt, vp, bi]
+    lib.mipt_bake_texels.restype = C.c_int
+    lib.mipt_bake_texels_device.argtypes = [vp, u32, u32, bt, vp, vp, bi]
+    lib.mipt_bake_texels_device.restype = C.c_int
+    lib.mipt_bake_gather.argtypes = [vp, vp, u64, bo, vp, C.POINTER(MiptStats)]
+    lib.mipt_bake_gather.restype = C.c_int
+    lib.mipt_bake_gather_device.argtypes = [vp, vp, u64, bo, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_bake_gather_device.restype = C.c_int
     fb = C.POINTER(MiptFeatureBuffers)
     lib.mipt_render_features.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, C.POINTER(MiptStats)]
     lib.mipt_render_features.restype = C.c_int

@@ -47,7 +47,8 @@ void mipt::free_scene(MiptScene *s) {
     mipt::free_mesh(s);
     void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
                     s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams, s->d_qrays, s->d_qout,
-                    s->d_tile_cost, s->d_tile_order, s->d_pixel_cost, s->d_hot, s->d_hot_bits, s->d_hot_work};
+                    s->d_tile_cost, s->d_tile_order, s->d_pixel_cost, s->d_hot, s->d_hot_bits, s->d_hot_work,
+                    s->d_bake_owner, s->d_bake_huge, s->d_bake_ctl, s->d_bake_rays, s->d_bake_path, s->d_bake_inv};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);

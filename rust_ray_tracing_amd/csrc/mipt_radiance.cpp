@@ -36,9 +36,11 @@ int check(const char *who, const MiptScene *scene, const void *rays, uint64_t n_
     return MIPT_OK;
 }
 
+} // namespace
+
 // the launch, with every argument already checked; d_rays / d_radiance in HBM of the scene's device
-int launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance, hipStream_t stream,
-           MiptStats *stats) {
+int mipt::radiance_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance,
+                          hipStream_t stream, MiptStats *stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (n_rays == 0) return MIPT_OK;
     MIPT_HIP(hipSetDevice(scene->device));
@@ -83,6 +85,10 @@ int launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptR
     return rc;                                                    // MIPT_OK, or MIPT_ERR_STACK with the results and the stats delivered
 }
 
+namespace {
+
+using mipt::radiance_launch;
+
 int radiance_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance,
                     void *hip_stream, MiptStats *stats) {
     const char *who = "mipt_query_radiance_device";
@@ -90,24 +96,24 @@ int radiance_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, co
     if (rc) return rc;
     if ((uintptr_t)d_rays & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_rays must be 16-byte aligned", who);
     if ((uintptr_t)d_radiance & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_radiance must be 4-byte aligned", who);
-    if (n_rays == 0) return launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);                     // MIPT_OK, no device work
+    if (n_rays == 0) return radiance_launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);            // MIPT_OK, no device work
     if (mipt::ranges_overlap(d_rays, n_rays * sizeof(MiptRay), d_radiance, n_rays * 12))
         return fail(MIPT_ERR_INVALID_ARG, "%s: d_rays overlaps d_radiance", who);
     if ((rc = mipt::device_buffer_check(who, d_rays, scene->device, "d_rays"))) return rc;
     if ((rc = mipt::device_buffer_check(who, d_radiance, scene->device, "d_radiance"))) return rc;
-    return launch(scene, d_rays, n_rays, opt, d_radiance, (hipStream_t)hip_stream, stats);
+    return radiance_launch(scene, d_rays, n_rays, opt, d_radiance, (hipStream_t)hip_stream, stats);
 }
 
 int radiance_host(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *radiance, MiptStats *stats) {
     int rc = check("mipt_query_radiance", scene, rays, n_rays, opt, radiance, false);
     if (rc) return rc;
-    if (n_rays == 0) return launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);
+    if (n_rays == 0) return radiance_launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);
     MIPT_HIP(hipSetDevice(scene->device));
     const size_t out_bytes = (size_t)n_rays * 3 * sizeof(float);
     if ((rc = mipt::grow_device_buffer(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
     if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
     MIPT_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
-    rc = launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, (float *)scene->d_qout, nullptr, stats);
+    rc = radiance_launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, (float *)scene->d_qout, nullptr, stats);
     if (rc && rc != MIPT_ERR_STACK) return rc;
     MIPT_HIP(hipMemcpy(radiance, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
     return rc;

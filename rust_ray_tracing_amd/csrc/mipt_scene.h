@@ -67,6 +67,12 @@ struct MiptScene {
     uint32_t list_used = 0;                 // entries that launch itself took, hot_used of them as "the hot pixels"
     void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
     size_t qrays_bytes = 0, qout_bytes = 0;
+    // baking (mipt_bake.cpp, bake.hip): the owner word per texel and the list of triangles the whole grid covers (mipt_bake_texels);
+    // the counters of a call; the map from the caller's triangle index to its tri_pos record, made on first use and dropped with the tree (release_geometry); the ray
+    // and radiance staging of a chunk of paths and the two carry slots of a point that spans chunks (mipt_bake_gather).  Grown on demand.
+    void *d_bake_owner = nullptr, *d_bake_huge = nullptr, *d_bake_ctl = nullptr, *d_bake_rays = nullptr, *d_bake_path = nullptr;
+    size_t bake_owner_bytes = 0, bake_huge_bytes = 0, bake_ctl_bytes = 0, bake_rays_bytes = 0, bake_path_bytes = 0;
+    uint32_t *d_bake_inv = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int n_cu = 0;
     uint32_t max_leaf = 0;
@@ -227,6 +233,11 @@ inline void stats_from_device(const DevStats &hs, float kernel_ms, MiptStats *st
     stats->diag[3] = hs.d_iters_inner; stats->diag[4] = hs.d_iters_leaf; stats->diag[5] = hs.d_services;
     stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
 }
+
+// The trace launch of mipt_query_radiance_device with every argument already checked (mipt_radiance.cpp); mipt_bake.cpp runs it per
+// chunk.  d_rays / d_radiance in HBM of the scene's device; blocks until done; MIPT_ERR_STACK with results and stats delivered.
+int radiance_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance, hipStream_t stream,
+                    MiptStats *stats);
 
 // ---- the first-hit passes (mipt_features.cpp: the feature buffers; mipt_motion.cpp: previous positions) ----
 // the checks that concern neither the buffers nor a device; `buffers` is only tested for null.  count_allowed: MIPT_FLAG_COUNT passes

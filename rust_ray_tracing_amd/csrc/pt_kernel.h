@@ -135,6 +135,38 @@ struct DevQuery {
 hipError_t launch_ray_query(const DevScene &sc, const DevQuery &q, bool count, bool cull, bool anyhit, int grid_blocks, hipStream_t stream);
 int query_blocks_per_cu(bool count, bool cull, bool anyhit);                 // occupancy query
 
+// ---- baking (bake.hip; mipt_bake_texels* / mipt_bake_gather*) ----
+struct BakeCtl {                            // counters of one call, zeroed on the stream before its first kernel (32 B)
+    unsigned long long covered;             // texels that found an owner
+    unsigned long long bad_point;           // the first point whose triangle the scene does not have (all ones = none)
+    uint32_t degenerate;                    // triangles whose UV determinant is 0 or not finite
+    uint32_t n_huge;                        // triangles handed to the grid-wide coverage kernel (may count past the list's capacity)
+    uint32_t pad[2];
+};
+// The texel pass: the memsets of `owner` (width * height u64) and `ctl`, the coverage kernels over the tree order and the resolve
+// kernel that writes width * height 16-B records to `points` (stream-ordered; no allocation, no synchronisation inside).  `huge`:
+// huge_cap words of scratch.
+hipError_t launch_bake_texels(const DevScene &sc, const uint32_t *tri_order, uint32_t width, uint32_t height, unsigned long long *owner,
+                              uint32_t *huge, uint32_t huge_cap, BakeCtl *ctl, void *points, int n_cu, hipStream_t stream);
+// inv[the caller's index of the triangle in record q of tri_pos] = q for q < n_tris (tri_order NULL: the tree's order is the caller's)
+hipError_t launch_bake_invert_order(const DevScene &sc, const uint32_t *tri_order, uint32_t *inv, int n_cu, hipStream_t stream);
+// ctl->bad_point = the lowest i < n whose point names a triangle >= n_tris (ctl zeroed first, bad_point all ones)
+hipError_t launch_bake_check_points(const void *points, unsigned long long n, uint32_t n_tris, BakeCtl *ctl, int n_cu, hipStream_t stream);
+struct BakeGather {                         // one chunk of a gather: paths [first_path, first_path + n_paths) of n * samples
+    const uint4 *points;                    // all n records (MiptSurfacePoint)
+    const uint32_t *inv_order;              // the caller's triangle index -> its record in tri_pos
+    unsigned long long first_path, n_paths;
+    uint32_t samples, first_sample, sample_stride;
+    uint32_t sum_only, accumulate;
+    float samples_f;
+    const float *carry_in;                  // 3 f32: the sum so far of the point whose samples began in the chunk before
+    float *carry_out;                       // 3 f32: the sum so far of the point whose samples go on in the next chunk
+};
+// rays[j] (n_paths x 32 B, MiptRay with the stream's state after the draws as its seed) for path first_path + j
+hipError_t launch_bake_rays(const DevScene &sc, const BakeGather &g, float4 *rays, int n_cu, hipStream_t stream);
+// path: n_paths x 3 f32, the chunk's traced radiance; radiance: the caller's n x 3 f32
+hipError_t launch_bake_reduce(const BakeGather &g, const float *path, float *radiance, int n_cu, hipStream_t stream);
+
 // ---- first-hit feature buffers (first_hit.hip; mipt_render_features*) ----
 struct PartRec;                             // pt_mesh_rule.h
 struct DevFeatures {

@@ -366,11 +366,12 @@ void finish_info(const MiptScene *s, MiptUpdateInfo *inf, double t0) {
 
 void mipt::release_geometry(MiptScene *s) {
     (void)hipSetDevice(s->device);
-    void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_nodes, s->d_tri_order, s->d_touched, s->d_refit_plan, s->d_refit_pair};
+    void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_nodes, s->d_tri_order, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_bake_inv};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     s->d_geom = s->d_tri_attr = nullptr;
     s->d_nodes = nullptr; s->d_tri_order = nullptr; s->d_touched = nullptr; s->d_refit_plan = s->d_refit_pair = nullptr;
+    s->d_bake_inv = nullptr;                                              // the caller -> tree map of mipt_bake_gather: the tree it was made for is gone
     s->refit_level_off.clear();
 }
 

@@ -638,6 +638,156 @@ class Scene:  # scene.rs:12-19
             L.check(rc, f.__name__)
         return out, st.as_dict()
 
+    # -- baking (include/mipt.h "baking") ------------------------------------------------------------
+    @staticmethod
+    def _stream_arg(stream, device):
+        import torch
+        if stream is None:
+            return torch.cuda.current_stream(device).cuda_stream
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+    def bake_texels(self, width: int, height: int, stream=None, device: bool = False, handle=None):
+        """The surface point behind every texel of a ``width`` x ``height`` lightmap atlas laid out by the scene's own UVs
+        (mipt_bake_texels / _device).  Returns (points, info): SURFACE_POINT records [width * height], texel (x, y) at index
+        y * width + x, seed = that index, prim = HIT_NONE where no triangle covers the texel centre; with ``device`` an int32 device
+        tensor [width * height, 4] of the same words, made on ``stream`` (a torch stream, a raw hipStream_t or None = torch's current
+        stream).  info: covered_texels, degenerate_tris, kernel_ms."""
+        h = handle if handle is not None else self._handle
+        if h is None:
+            raise RuntimeError("scene is not resident on a device")
+        if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer))) or width < 0 or height < 0 or width >= 1 << 32 or height >= 1 << 32:
+            raise ValueError("width, height: expected two non-negative 32-bit integers")
+        n = int(width) * int(height)
+        info = L.MiptBakeTexelInfo()
+        lib = L.load()
+        if device:
+            import torch
+            dev = torch.device("cuda", self._handle_device if handle is None else torch.cuda.current_device())   # a foreign handle: the caller's current device
+            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            f = lib.mipt_bake_texels_device
+            rc = f(h, width, height, None, out.data_ptr() if n else 16, self._stream_arg(stream, dev), C.byref(info))
+        else:
+            out = np.zeros(n, dtype=L.SURFACE_POINT)
+            f = lib.mipt_bake_texels
+            rc = f(h, width, height, None, L.ptr(out) if n else C.c_void_p(16), C.byref(info))
+        L.check(rc, f.__name__)
+        return out, info.as_dict()
+
+    @staticmethod
+    def _bake_points(points, seeds):
+        """-> ("host", SURFACE_POINT array [n]) or ("device", int32 cuda tensor [n, 4]); ValueError for anything else.  A dict is what
+        ``query_closest`` returns; it needs ``seeds``."""
+        if isinstance(points, dict):
+            if seeds is None:
+                raise ValueError("points: the hits of query_closest carry no seeds: give seeds")
+            u, v, prim, front = points["u"], points["v"], points["prim"], points["front_face"]
+            if Scene._is_torch(u):
+                import torch
+                p = torch.where(prim < 0, torch.full_like(prim, L.HIT_NONE), prim | (front.to(torch.int64) << 31))
+                p = torch.where(p >= 1 << 31, p - (1 << 32), p).to(torch.int32)                 # the u32 word as int32 bits
+                ub, vb = u.contiguous().view(torch.int32), v.contiguous().view(torch.int32)
+                points = torch.stack([torch.zeros_like(ub), ub, vb, p], dim=1).contiguous()
+            else:
+                rec = np.zeros(len(u), dtype=L.SURFACE_POINT)
+                rec["u"], rec["v"] = u, v
+                pr = np.asarray(prim, dtype=np.int64)
+                rec["prim"] = np.where(pr < 0, L.HIT_NONE, pr | (np.asarray(front, dtype=np.int64) << 31)).astype(np.uint32)
+                points = rec
+        if Scene._is_torch(points):
+            import torch
+            if points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_cuda or not points.is_contiguous():
+                raise ValueError("points: expected a contiguous int32 device tensor of shape (n, 4)")
+            where, r = "device", points
+        else:
+            a = np.asarray(points)
+            if a.dtype == L.SURFACE_POINT and a.ndim == 1:
+                r = np.ascontiguousarray(a)
+            elif a.dtype == L.HIT and a.ndim == 1:
+                r = np.ascontiguousarray(a).view(L.SURFACE_POINT)
+            elif a.dtype in (np.dtype(np.uint32), np.dtype(np.int32)) and a.ndim == 2 and a.shape[1] == 4:
+                r = np.ascontiguousarray(a).view(L.SURFACE_POINT).reshape(-1)
+            else:
+                raise ValueError("points: expected SURFACE_POINT or HIT records, an (n, 4) array of 32-bit words, an int32 device tensor "
+                                 "of shape (n, 4) or the dict query_closest returns")
+            where = "host"
+        if seeds is not None:
+            n = len(r)
+            s = seeds.detach().cpu().numpy() if Scene._is_torch(seeds) else np.asarray(seeds)
+            if s.shape != (n,) or s.dtype.kind not in "iu" or s.dtype.itemsize != 4:
+                raise ValueError(f"seeds: expected {n} 32-bit integers")
+            s = np.ascontiguousarray(s).view(np.uint32)
+            if where == "host":
+                r = r.copy()
+                r["seed"] = s
+            else:
+                import torch
+                if r is points:
+                    r = r.clone()
+                r[:, 0] = torch.from_numpy(s.view(np.int32)).to(r.device)
+        return where, r
+
+    def bake_gather(self, points, seeds=None, samples: int = 1, max_ray_depth: int = 8, traversal: int = L.TRAVERSAL_REFERENCE,
+                    cull_margin: float = L.CULL_MARGIN_SAFE, shading: int = 0, sum_only: bool = False, first_sample: int = 0, sample_stride=None,
+                    accumulate_into=None, count: bool = False, handle=None, stream=None):
+        """The light every surface point gathers over its hemisphere (mipt_bake_gather / _device): ``samples`` paths per point, each
+        leaving along normalized(N + rand_in_unit_sphere) on a stream seeded from the point's seed and the sample's number
+        ``first_sample + s``; their mean (``sum_only``: their sum).  ``points``: what ``bake_texels`` returns (host records or the
+        device tensor), HIT records with seeds, an (n, 4) array of the record's words, or the dict ``query_closest`` returns -- the
+        last two kinds of hits need ``seeds`` (n uint32).  ``sample_stride``: None = the number of points.  ``accumulate_into``: a
+        float32 device tensor [n, 3] the call's samples are added to (device points only; implies ``sum_only``).  Returns
+        (radiance [n, 3] float32 array or tensor, stats)."""
+        where, r = self._bake_points(points, seeds)
+        h = handle if handle is not None else self._handle
+        if h is None:
+            raise RuntimeError("scene is not resident on a device")
+        n = len(r)
+        opt = L.MiptBakeOptions()
+        opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading = samples, max_ray_depth, traversal, cull_margin, shading
+        opt.first_sample, opt.sample_stride = first_sample, (max(n, 1) if sample_stride is None else sample_stride)
+        opt.flags = (L.FLAG_COUNT if count else 0) | (L.FLAG_SUM if sum_only or accumulate_into is not None else 0)
+        st = L.MiptStats()
+        lib = L.load()
+        if where == "host":
+            if accumulate_into is not None:
+                raise ValueError("accumulate_into needs device points: the running sum lives in a device tensor")
+            out = np.zeros((n, 3), dtype=np.float32)
+            f = lib.mipt_bake_gather
+            rc = f(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out) if n else C.c_void_p(16), C.byref(st))
+        else:
+            import torch
+            if accumulate_into is not None:
+                out = accumulate_into
+                if not self._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != r.device or not out.is_contiguous():
+                    raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the points' device")
+                opt.flags |= L.FLAG_ACCUM
+            else:
+                out = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            f = lib.mipt_bake_gather_device
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
+        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
+            L.check(rc, f.__name__)
+        return out, st.as_dict()
+
+    def bake_lightmap(self, width: int, height: int, samples: int, device=None, stream=None, **gather_args):
+        """``bake_texels`` then ``bake_gather`` with the texel indices as seeds: the mean radiance every covered texel of the atlas
+        gathers.  With torch and a visible device (``device`` None) or ``device=True`` both steps stay in HBM and tensors come back;
+        otherwise numpy arrays.  Returns (atlas [height, width, 3] float32, covered [height, width] bool, stats); stats carries the
+        texel pass's info under "texels"."""
+        if device is None:
+            try:
+                import torch
+                device = torch.cuda.is_available()
+            except ImportError:
+                device = False
+        points, info = self.bake_texels(width, height, stream=stream, device=device, handle=gather_args.get("handle"))
+        rad, stats = self.bake_gather(points, samples=samples, stream=stream, **gather_args)
+        stats["texels"] = info
+        if device:
+            covered = (points[:, 3] != -1).reshape(height, width)
+        else:
+            covered = (points["prim"] != L.HIT_NONE).reshape(height, width)
+        return rad.reshape(height, width, 3), covered, stats
+
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
         h = handle if handle is not None else self._handle
