@@ -1,7 +1,9 @@
-"""The models of include/mipt.h "baking" for tests/test_bake_abi.py, tests/test_gpu_bake.py and tests/test_cpp_host_bake.py.
+"""The models of include/mipt.h "baking" for tests/test_bake_abi.py, tests/test_bake_model.py, tests/test_gpu_bake.py and
+tests/test_cpp_host_bake.py.
 
 texels(): mipt_bake_texels in numpy f32 -- a brute force over ALL triangles of the caller's array per texel, every operator one
-rounded f32 operation in the header's order.  gather(): mipt_bake_gather as a Python loop over the oracle's orc_rand_in_unit_sphere
+rounded f32 operation in the header's order.  texels_indexed(): the same definition stated a second time, over the (triangle,
+texel) pairs that pass the box clause, for inputs of 10^6 triangles.  gather(): mipt_bake_gather as a Python loop over the oracle's orc_rand_in_unit_sphere
 and orc_trace_ray / orc_trace_ray_wgsl; the interpolation and `normalized` in numpy f32, the seed arithmetic in Python integers
 (checked against orc_pixel_seed).  Nothing of the library under test is used here."""
 import ctypes as C
@@ -30,9 +32,11 @@ def texel_centres(width, height, index):
     return s, t
 
 
-def texels(tris, width, height, index=None):
+def texels(tris, width, height, index=None, box=True):
     """-> (points [len(index)] POINT, info dict).  tris: the caller's array, in the caller's order.  index: the texels wanted
-    (default: all, in order).  info: covered (of the texels asked for) and degenerate (triangles whose d is 0 or not finite)."""
+    (default: all, in order).  info: covered (of the texels asked for) and degenerate (triangles whose d is 0 or not finite).
+    box=False drops the box clause of "covered": NOT the header's definition, only what a test measures its inputs with (how
+    many texels the clause decides)."""
     if index is None:
         index = np.arange(width * height, dtype=np.uint32)
     index = np.asarray(index, dtype=np.uint32)
@@ -41,27 +45,132 @@ def texels(tris, width, height, index=None):
     out = np.zeros(len(index), dtype=POINT)
     out["seed"], out["prim"] = index, NONE
     free = np.ones(len(index), dtype=bool)
-    degenerate = 0
     with np.errstate(all="ignore"):
-        for k in range(len(uv)):                                            # ascending: the first to cover a texel keeps it
-            a, b, c = uv[k]
-            bx, by, cx, cy = b[0] - a[0], b[1] - a[1], c[0] - a[0], c[1] - a[1]
-            d = (bx * cy) - (cx * by)
-            if not (np.isfinite(d) and d != 0):
-                degenerate += 1
+        # what depends on the triangle alone, for all of them at once (the loop below is what takes the time at 10^6 triangles)
+        ax, ay = uv[:, 0, 0], uv[:, 0, 1]
+        bx, by, cx, cy = uv[:, 1, 0] - ax, uv[:, 1, 1] - ay, uv[:, 2, 0] - ax, uv[:, 2, 1] - ay
+        d = (bx * cy) - (cx * by)
+        usable = np.isfinite(d) & (d != 0)
+        lo = np.minimum(np.minimum(uv[:, 0], uv[:, 1]), uv[:, 2])           # [n, 2]; the corners of a usable triangle are no NaNs
+        hi = np.maximum(np.maximum(uv[:, 0], uv[:, 1]), uv[:, 2])
+        assert d.dtype == np.float32
+        for k in np.flatnonzero(usable):                                    # ascending: the first to cover a texel keeps it
+            if box:                                                         # the box clause first: most triangles hold no texel asked for
+                sel = np.flatnonzero((s >= lo[k, 0]) & (s <= hi[k, 0]) & (t >= lo[k, 1]) & (t <= hi[k, 1]) & free)
+            else:
+                sel = np.flatnonzero(free)
+            if len(sel) == 0:
                 continue
-            px, py = s - a[0], t - a[1]
-            u = ((px * cy) - (cx * py)) / d
-            v = ((bx * py) - (px * by)) / d
-            lo_x, hi_x = min(a[0], b[0], c[0]), max(a[0], b[0], c[0])
-            lo_y, hi_y = min(a[1], b[1], c[1]), max(a[1], b[1], c[1])
-            cov = (u >= 0) & (v >= 0) & ((u + v) <= 1) & (s >= lo_x) & (s <= hi_x) & (t >= lo_y) & (t <= hi_y)
-            take = cov & free
+            px, py = s[sel] - ax[k], t[sel] - ay[k]
+            u = ((px * cy[k]) - (cx[k] * py)) / d[k]
+            v = ((bx[k] * py) - (px * by[k])) / d[k]
+            take = (u >= 0) & (v >= 0) & ((u + v) <= 1)
             if take.any():
                 assert u.dtype == np.float32 and v.dtype == np.float32
-                out["u"][take], out["v"][take], out["prim"][take] = u[take], v[take], np.uint32(k | FRONT)
-                free &= ~take
-    return out, dict(covered=int((~free).sum()), degenerate=degenerate)
+                sel = sel[take]
+                out["u"][sel], out["v"][sel], out["prim"][sel] = u[take], v[take], np.uint32(int(k) | FRONT)
+                free[sel] = False
+    return out, dict(covered=int((~free).sum()), degenerate=int((~usable).sum()))
+
+
+def centre_lines(width, height):
+    """the centres of the columns [width] and of the rows [height], by texel_centres' own expression"""
+    return texel_centres(width, 1, np.arange(width))[0], texel_centres(1, height, np.arange(height))[1]
+
+
+def boxes(tris, width, height):
+    """Per triangle, the texel columns [x0, x1) and rows [y0, y1) whose f32 centre passes the box clause, and `usable` (d finite and
+    not 0; the ranges of the others are empty): the centres are monotone in the texel index, so the clause is two binary searches
+    per axis -- `left` for lo (the first centre >= lo), `right` for hi (one past the last centre <= hi).  Exact: no estimate."""
+    uv = corner_uvs(tris)
+    a, b, c = uv[:, 0], uv[:, 1], uv[:, 2]
+    with np.errstate(all="ignore"):
+        d = ((b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1])) - ((c[:, 0] - a[:, 0]) * (b[:, 1] - a[:, 1]))
+        usable = np.isfinite(d) & (d != 0)
+    cen_x, cen_y = centre_lines(width, height)
+    assert np.all(np.diff(cen_x) >= 0) and np.all(np.diff(cen_y) >= 0)
+    out = []
+    for cen, axis in ((cen_x, 0), (cen_y, 1)):
+        lo = np.minimum(np.minimum(a[:, axis], b[:, axis]), c[:, axis])
+        hi = np.maximum(np.maximum(a[:, axis], b[:, axis]), c[:, axis])
+        first = np.where(usable, np.searchsorted(cen, np.where(usable, lo, 0), "left"), 0)
+        end = np.where(usable, np.searchsorted(cen, np.where(usable, hi, 0), "right"), 0)
+        out += [first.astype(np.int64), np.maximum(end, first).astype(np.int64)]
+    return out[0], out[1], out[2], out[3], usable
+
+
+def _uv_of(uv, tri, s, t):
+    """d, u, v of the pairs (triangle tri[i], centre s[i], t[i]): the header's expression tree, every operator one f32 operation"""
+    ax, ay = uv[tri, 0, 0], uv[tri, 0, 1]
+    bx, by, cx, cy = uv[tri, 1, 0] - ax, uv[tri, 1, 1] - ay, uv[tri, 2, 0] - ax, uv[tri, 2, 1] - ay
+    d = (bx * cy) - (cx * by)
+    px, py = s - ax, t - ay
+    u = ((px * cy) - (cx * py)) / d
+    v = ((bx * py) - (px * by)) / d
+    assert u.dtype == np.float32 and v.dtype == np.float32
+    return u, v
+
+
+def texels_indexed(tris, width, height, chunk=1 << 22, stats=None):
+    """texels() of every texel, stated a second time and fast enough for 10^6 triangles: the (triangle, texel) pairs that pass the box
+    clause are enumerated from boxes() in ascending triangle order, at most `chunk` <= 2^24 at a time, u and v are evaluated on the
+    pairs, and a texel goes to the first pair that covers it.  Nothing of the kernel's walk (its estimate of the box, its padding)
+    is used.  stats, a dict, receives `pairs` and per-triangle `owned` counts.  tests/test_bake_model.py holds it to texels()."""
+    assert 0 < chunk <= 1 << 24
+    n_tex = width * height
+    uv = corner_uvs(tris)
+    x0, x1, y0, y1, usable = boxes(tris, width, height)
+    nx = x1 - x0
+    count = nx * (y1 - y0)
+    end = np.cumsum(count)
+    start = end - count
+    total = int(end[-1]) if len(end) else 0
+    cen_x, cen_y = centre_lines(width, height)
+    owner = np.full(n_tex, -1, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for p0 in range(0, total, chunk):
+            p1 = min(p0 + chunk, total)
+            first, last = int(np.searchsorted(end, p0, "right")), int(np.searchsorted(end, p1 - 1, "right"))
+            part = np.minimum(end[first: last + 1], p1) - np.maximum(start[first: last + 1], p0)
+            tri = np.repeat(np.arange(first, last + 1), part)
+            local = np.arange(p0, p1) - start[tri]
+            x, y = x0[tri] + local % nx[tri], y0[tri] + local // nx[tri]
+            u, v = _uv_of(uv, tri, cen_x[x], cen_y[y])
+            cov = (u >= 0) & (v >= 0) & ((u + v) <= 1)
+            tri, tex = tri[cov], (y * width + x)[cov]
+            new = owner[tex] < 0                                            # earlier chunks hold lower triangles
+            owner[tex[new][::-1]] = tri[new][::-1]                          # a repeated index keeps the LAST value assigned: the lowest triangle
+    out = np.zeros(n_tex, dtype=POINT)
+    out["seed"], out["prim"] = np.arange(n_tex, dtype=np.uint32), NONE
+    has = np.flatnonzero(owner >= 0)
+    s, t = texel_centres(width, height, has)
+    with np.errstate(all="ignore"):
+        out["u"][has], out["v"][has] = _uv_of(uv, owner[has], s, t)         # the same operations on the same operands as in the loop
+    out["prim"][has] = owner[has].astype(np.uint32) | np.uint32(FRONT)
+    if stats is not None:
+        stats["pairs"], stats["owned"] = total, np.bincount(owner[has], minlength=len(uv))
+    return out, dict(covered=len(has), degenerate=int((~usable).sum()))
+
+
+def sliver_uvs(width, height, n, k, seed):
+    """[n, 3, 2] f32: slivers laid ALONG LINES OF TEXEL CENTRES, so that centres outside a sliver's box fall within rounding noise of
+    its line and only the box clause keeps them out.  Corner a is the centre (x0, y0), b the centre (x0 + m, y0 +- m), c the centre
+    (x0 + j, y0 +- j) between them with each coordinate's bit pattern moved by -k ... +k ulps; m in 3 ... min(width, height) / 4,
+    x0, y0 in the middle half of the atlas, 0 < j < m, either diagonal.  (Random slivers off the centre lines are decided by the
+    clause on no texel at all.)"""
+    rng = np.random.default_rng(seed)
+    cen_x, cen_y = centre_lines(width, height)
+    m = rng.integers(3, min(width, height) // 4 + 1, n)
+    x0 = rng.integers(width // 4, width - width // 4, n)
+    y0 = rng.integers(height // 4, height - height // 4, n)
+    j = rng.integers(1, m)
+    sign = np.where(rng.random(n) < 0.5, 1, -1)
+    uv = np.zeros((n, 3, 2), dtype=np.float32)
+    for corner, step in ((0, 0 * m), (1, m), (2, j)):
+        uv[:, corner, 0], uv[:, corner, 1] = cen_x[x0 + step], cen_y[y0 + sign * step]
+    moved = uv[:, 2].view(np.int32) + rng.integers(-k, k + 1, (n, 2)).astype(np.int32)      # positive floats: + 1 is the next one up
+    uv[:, 2] = moved.view(np.float32)
+    return uv
 
 
 def sample_seed(seed, g, stride):

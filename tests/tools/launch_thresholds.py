@@ -10,6 +10,9 @@ device at run time, and force nothing.  Edit together with:
 * first_hit_setup, csrc/mipt_features.cpp: the feature and motion grid is n_cu x blocks_per_cu blocks, at most ceil(work / 256);
   first_hit_blocks_per_cu and motion_blocks_per_cu (csrc/first_hit.hip) clamp to 1 ... 8 as well -- checked: the same two lines.
 * query_blocks_per_cu (csrc/ray_query.hip), the same clamp: tests/test_gpu_query.py::_launch_capacity is this module's lanes_cap.
+* grid_for, csrc/bake.hip: every baking launch but cover_huge_kernel is capped at n_cu x 8 blocks of kT = 256 lanes and walks the rest
+  of its input with a grid-stride loop -- not persistent, but the same number: lanes_cap(n_cu) is the most triangles, texels, records,
+  points or paths a bake launch holds before a lane takes a second one.  (cover_huge_kernel launches n_cu x 4 blocks: half of it.)
 
 tests/test_launch_thresholds.py (CPU) asserts what the names below promise, from these formulas alone."""
 
