@@ -129,10 +129,10 @@ int render_host(MiptScene *scene, const MiptCamera *cameras, uint32_t n_views, c
     mipt::DevPtr<uint32_t> d_counts;                              // a local: freed on every way out
     MIPT_HIP(d_counts.alloc((size_t)n_pix));
     MIPT_HIP(hipMemcpy(d_counts.get(), counts, (size_t)n_pix * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_hdr, &scene->hdr_bytes, (size_t)n_pix * 3 * sizeof(float)))) return rc;
+    if ((rc = scene->d_hdr.grow((size_t)n_pix * 3 * sizeof(float)))) return rc;
     uint8_t *d_rgba = nullptr;
     if (rgba8) {
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        if ((rc = scene->d_rgba.grow((size_t)n_pix * 4))) return rc;
         d_rgba = scene->d_rgba;
     }
     rc = render_launch(scene, cameras, n_views, opt, d_counts.get(), scene->d_hdr, d_rgba, nullptr, stats);

@@ -45,15 +45,7 @@ void mipt::free_scene(MiptScene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     mipt::free_mesh(s);
-    void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_mats, s->d_mats_full, s->d_texels, s->d_nodes, s->d_tri_order,
-                    s->d_stats, s->d_ovf, s->d_hdr, s->d_rgba, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_cams, s->d_qrays, s->d_qout,
-                    s->d_tile_cost, s->d_tile_order, s->d_pixel_cost, s->d_hot, s->d_hot_bits, s->d_hot_work,
-                    s->d_bake_owner, s->d_bake_huge, s->d_bake_ctl, s->d_bake_rays, s->d_bake_path, s->d_bake_inv};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
+    delete s;                                                     // every member frees what it owns
 }
 
 namespace {
@@ -64,15 +56,15 @@ using mipt::free_scene;
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 template <class T>
-int upload(void **dst, const T *src, size_t count, size_t min_bytes = 16) {
-    size_t bytes = count * sizeof(T);
+int upload(mipt::DevPtr<T> &owner, const std::vector<T> &table, size_t min_bytes = 16) {
+    const T *src = table.data();
+    size_t bytes = table.size() * sizeof(T);
     size_t alloc = bytes < min_bytes ? min_bytes : bytes;
+    void **dst = (void **)owner.put();
     MIPT_HIP(hipMalloc(dst, alloc));
     if (bytes) MIPT_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     return MIPT_OK;
 }
-template <class T>
-int upload(void **dst, const std::vector<T> &src, size_t min_bytes = 16) { return upload(dst, src.data(), src.size(), min_bytes); }
 
 // host loops over the caller's arrays (the material-id check) on up to 16 threads
 template <class F> void parallel_for(size_t n, F body) {                 // body(begin, end) on disjoint ranges; results must not depend on the split
@@ -152,18 +144,18 @@ int mipt::build_material_tables(const MiptSceneDesc *desc, MaterialTables *out, 
 
 int mipt::upload_material_tables(MiptScene *s, const MaterialTables &t) {
     int rc;
-    if ((rc = upload(&s->d_mats, t.mats, 64)) || (rc = upload(&s->d_mats_full, t.mats_full, 128))) return rc;
-    if (!t.texels.empty() || t.n_texels == 0) { if ((rc = upload(&s->d_texels, t.texels, 16))) return rc; }
+    if ((rc = upload(s->d_mats, t.mats, 64)) || (rc = upload(s->d_mats_full, t.mats_full, 128))) return rc;
+    if (!t.texels.empty() || t.n_texels == 0) { if ((rc = upload(s->d_texels, t.texels, 16))) return rc; }
     // else filled by the caller (scene_device.hip stages the textures itself).  Never less than the 16 bytes texel_bytes records
     // below: a replica copies texel_bytes from this allocation (clone_issue), also for a pool of one to three texels.
-    else MIPT_HIP(hipMalloc(&s->d_texels, (size_t)t.n_texels * 4 < 16 ? 16 : (size_t)t.n_texels * 4));
+    else MIPT_HIP(s->d_texels.alloc((size_t)t.n_texels < 4 ? 4 : (size_t)t.n_texels));
     s->mats_bytes = t.mats.size() * sizeof(mipt::DevMaterial) < 64 ? 64 : t.mats.size() * sizeof(mipt::DevMaterial);
     s->mats_full_bytes = t.mats_full.size() * sizeof(mipt::DevMaterialFull) < 128 ? 128 : t.mats_full.size() * sizeof(mipt::DevMaterialFull);
     s->texel_bytes = (size_t)t.n_texels * 4 < 16 ? 16 : (size_t)t.n_texels * 4;
     s->n_texels = t.n_texels;
-    s->dev.mats = (const mipt::DevMaterial *)s->d_mats;
-    s->dev.mats_full = (const mipt::DevMaterialFull *)s->d_mats_full;
-    s->dev.texels = (const uint32_t *)s->d_texels;
+    s->dev.mats = s->d_mats;
+    s->dev.mats_full = s->d_mats_full;
+    s->dev.texels = s->d_texels;
     return MIPT_OK;
 }
 
@@ -172,8 +164,7 @@ int mipt::scene_finish_workspace(MiptScene *s) {
     hipError_t e = hipGetDeviceProperties(&prop, s->device);
     if (e != hipSuccess) return fail(MIPT_ERR_HIP, "hipGetDeviceProperties: %s", hipGetErrorString(e));
     s->n_cu = prop.multiProcessorCount;
-    if ((e = hipMalloc((void **)&s->d_stats, sizeof(mipt::DevStats))) != hipSuccess ||
-        (e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess)
+    if ((e = s->d_stats.alloc(1)) != hipSuccess || (e = hipEventCreate(s->ev0.put())) != hipSuccess || (e = hipEventCreate(s->ev1.put())) != hipSuccess)
         return fail(MIPT_ERR_HIP, "workspace allocation: %s", hipGetErrorString(e));
     return MIPT_OK;
 }
@@ -200,13 +191,13 @@ static int clone_issue(const MiptScene *src, int device, MiptScene **out) {
     s->geom_alloc = src->geom_alloc; s->attr_bytes = src->attr_bytes; s->mats_bytes = src->mats_bytes;
     s->mats_full_bytes = src->mats_full_bytes; s->texel_bytes = src->texel_bytes; s->n_texels = src->n_texels;
     struct Part { void **dst; const void *from; size_t alloc, copy; };
-    const Part parts[] = {{&s->d_geom, src->d_geom, src->geom_alloc, (size_t)src->dev.geom_bytes},
-                          {&s->d_tri_attr, src->d_tri_attr, src->attr_bytes < 16 ? 16 : src->attr_bytes, src->attr_bytes},
-                          {&s->d_mats, src->d_mats, src->mats_bytes, src->mats_bytes},
-                          {&s->d_mats_full, src->d_mats_full, src->mats_full_bytes, src->mats_full_bytes},
-                          {&s->d_texels, src->d_texels, src->texel_bytes, src->texel_bytes},
-                          {(void **)&s->d_nodes, src->d_nodes, (size_t)src->n_nodes * sizeof(MiptNode), src->d_nodes ? (size_t)src->n_nodes * sizeof(MiptNode) : 0},
-                          {(void **)&s->d_tri_order, src->d_tri_order, src->n_tris * 4, src->d_tri_order ? src->n_tris * 4 : 0}};
+    const Part parts[] = {{(void **)s->d_geom.put(), src->d_geom, src->geom_alloc, (size_t)src->dev.geom_bytes},
+                          {(void **)s->d_tri_attr.put(), src->d_tri_attr, src->attr_bytes < 16 ? 16 : src->attr_bytes, src->attr_bytes},
+                          {(void **)s->d_mats.put(), src->d_mats, src->mats_bytes, src->mats_bytes},
+                          {(void **)s->d_mats_full.put(), src->d_mats_full, src->mats_full_bytes, src->mats_full_bytes},
+                          {(void **)s->d_texels.put(), src->d_texels, src->texel_bytes, src->texel_bytes},
+                          {(void **)s->d_nodes.put(), src->d_nodes, (size_t)src->n_nodes * sizeof(MiptNode), src->d_nodes ? (size_t)src->n_nodes * sizeof(MiptNode) : 0},
+                          {(void **)s->d_tri_order.put(), src->d_tri_order, src->n_tris * 4, src->d_tri_order ? src->n_tris * 4 : 0}};
     for (const Part &p : parts) {
         if (!p.from) continue;
         hipError_t e = hipMalloc(p.dst, p.alloc ? p.alloc : 16);
@@ -226,12 +217,12 @@ static int clone_finish(const MiptScene *src, MiptScene *s, double t0) {
     const int rc = mipt::scene_finish_workspace(s);
     if (rc) return rc;
     const size_t pairs_bytes = src->dev.tri_off_bytes;
-    s->dev.pairs = (const float4 *)s->d_geom;
-    s->dev.tri_pos = (const float4 *)((const char *)s->d_geom + pairs_bytes);
-    s->dev.tri_attr = (const float4 *)s->d_tri_attr;
-    s->dev.mats = (const mipt::DevMaterial *)s->d_mats;
-    s->dev.mats_full = (const mipt::DevMaterialFull *)s->d_mats_full;
-    s->dev.texels = (const uint32_t *)s->d_texels;
+    s->dev.pairs = (const float4 *)s->d_geom.get();
+    s->dev.tri_pos = (const float4 *)(s->d_geom.get() + pairs_bytes);
+    s->dev.tri_attr = (const float4 *)s->d_tri_attr.get();
+    s->dev.mats = s->d_mats;
+    s->dev.mats_full = s->d_mats_full;
+    s->dev.texels = s->d_texels;
     s->info.replica_of_device = (uint32_t)src->device + 1u;
     s->info.upload_ms = now_ms() - t0; s->info.build_ms = 0.0; s->info.layout_ms = 0.0; s->info.total_ms = s->info.upload_ms;
     return MIPT_OK;
@@ -598,7 +589,7 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     const size_t geom_words = (geom_lines + 31) / 32, attr_words = (attr_lines + 31) / 32;
     pr.touched = nullptr; pr.touched_attr_base = (uint32_t)(geom_words * 32);
     if (touched) {
-        if (!scene->d_touched) MIPT_HIP(hipMalloc((void **)&scene->d_touched, (geom_words + attr_words) * sizeof(uint32_t)));
+        if (!scene->d_touched) MIPT_HIP(scene->d_touched.alloc(geom_words + attr_words));
         MIPT_HIP(hipMemsetAsync(scene->d_touched, 0, (geom_words + attr_words) * sizeof(uint32_t), stream));
         pr.touched = scene->d_touched;
     }
@@ -641,16 +632,16 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         const size_t bytes = (size_t)pr.n_local_tiles * sizeof(uint32_t);
         // every buffer of the state is sized by the key alone; one that is too small is replaced without its contents
         const size_t hot_bytes = (size_t)n_slots * sizeof(uint32_t), work_bytes = mipt::hot_work_words(n_slots) * sizeof(uint32_t);
-        if (scene->tile_cost_bytes < bytes || scene->tile_order_bytes < bytes || scene->pixel_cost_bytes < bytes * 64 || scene->hot_bytes < hot_bytes ||
-            scene->hot_bits_bytes < bytes * 2 || scene->hot_work_bytes < work_bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
+        if (scene->d_tile_cost.bytes() < bytes || scene->d_tile_order.bytes() < bytes || scene->d_pixel_cost.bytes() < bytes * 64 || scene->d_hot.bytes() < hot_bytes ||
+            scene->d_hot_bits.bytes() < bytes * 2 || scene->d_hot_work.bytes() < work_bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
             memcmp(pr.cam, scene->tile_cam, sizeof pr.cam) != 0)
             scene->tile_order_valid = false;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_tile_cost, &scene->tile_cost_bytes, bytes))) return rc;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_tile_order, &scene->tile_order_bytes, bytes))) return rc;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_pixel_cost, &scene->pixel_cost_bytes, bytes * 64))) return rc;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot, &scene->hot_bytes, hot_bytes))) return rc;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot_bits, &scene->hot_bits_bytes, bytes * 2))) return rc;
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_hot_work, &scene->hot_work_bytes, work_bytes))) return rc;
+        if ((rc = scene->d_tile_cost.grow(bytes))) return rc;
+        if ((rc = scene->d_tile_order.grow(bytes))) return rc;
+        if ((rc = scene->d_pixel_cost.grow(bytes * 64))) return rc;
+        if ((rc = scene->d_hot.grow(hot_bytes))) return rc;
+        if ((rc = scene->d_hot_bits.grow(bytes * 2))) return rc;
+        if ((rc = scene->d_hot_work.grow(work_bytes))) return rc;
         memcpy(scene->tile_key, key, sizeof key);
         memcpy(scene->tile_cam, pr.cam, sizeof pr.cam);
         MIPT_HIP(hipMemsetAsync(scene->d_pixel_cost, 0, bytes * 64, stream));   // the kernels behind the last launch have read them
@@ -692,8 +683,8 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
                 scene->tile_order_valid = true;
             }
             if (touched) {
-                MIPT_HIP(mipt::launch_popcount(scene->d_touched, geom_words, &scene->d_stats->touched_geom, stream));
-                MIPT_HIP(mipt::launch_popcount(scene->d_touched + geom_words, attr_words, &scene->d_stats->touched_attr, stream));
+                MIPT_HIP(mipt::launch_popcount(scene->d_touched, geom_words, &scene->d_stats.get()->touched_geom, stream));
+                MIPT_HIP(mipt::launch_popcount(scene->d_touched + geom_words, attr_words, &scene->d_stats.get()->touched_attr, stream));
             }
             if (d_rgba8) MIPT_HIP(mipt::launch_tonemap(d_hdr_rgb, (unsigned long long)opt->width * opt->height * n_views, 1.0f, d_rgba8, stream));
             return MIPT_OK;
@@ -732,10 +723,10 @@ int mipt_render_batch(MiptScene *scene, const MiptCamera *cameras, uint32_t n_vi
         return fail(MIPT_ERR_INVALID_ARG, "RGBA8 output needs a full-frame mean buffer (not PACKED / SUM)");
     MIPT_HIP(hipSetDevice(scene->device));
     const uint64_t n_pix = (uint64_t)n_views * opt->width * opt->height;
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_hdr, &scene->hdr_bytes, (size_t)n_pix * 3 * sizeof(float)))) return rc;
+    if ((rc = scene->d_hdr.grow((size_t)n_pix * 3 * sizeof(float)))) return rc;
     uint8_t *d_rgba = nullptr;
     if (rgba8) {
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        if ((rc = scene->d_rgba.grow((size_t)n_pix * 4))) return rc;
         d_rgba = scene->d_rgba;
     }
     rc = mipt_render_batch_device(scene, cameras, n_views, opt, scene->d_hdr, d_rgba, nullptr, stats);
@@ -761,11 +752,11 @@ int mipt_render(MiptScene *scene, const MiptCamera *camera, const MiptOptions *o
     const bool packed = (opt->flags & MIPT_FLAG_PACKED) != 0 && world > 1;
     const uint64_t n_pix = (uint64_t)opt->width * opt->height;
     const uint64_t n_out = packed ? mipt_packed_pixels(opt->width, opt->height, world) : n_pix;
-    if ((rc = mipt::grow_device_buffer((void **)&scene->d_hdr, &scene->hdr_bytes, (size_t)n_out * 3 * sizeof(float)))) return rc;
+    if ((rc = scene->d_hdr.grow((size_t)n_out * 3 * sizeof(float)))) return rc;
     if (world > 1 && !packed) MIPT_HIP(hipMemsetAsync(scene->d_hdr, 0, (size_t)n_out * 3 * sizeof(float), nullptr));
     uint8_t *d_rgba = nullptr;
     if (rgba8) {
-        if ((rc = mipt::grow_device_buffer((void **)&scene->d_rgba, &scene->rgba_bytes, (size_t)n_pix * 4))) return rc;
+        if ((rc = scene->d_rgba.grow((size_t)n_pix * 4))) return rc;
         d_rgba = scene->d_rgba;
     }
     rc = mipt_render_device(scene, camera, opt, scene->d_hdr, d_rgba, nullptr, stats);

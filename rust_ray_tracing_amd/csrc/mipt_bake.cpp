@@ -5,7 +5,6 @@
 #include "pt_kernel.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
-#include <cmath>
 #include <cstring>
 
 static_assert(sizeof(MiptSurfacePoint) == 16 && sizeof(MiptBakeOptions) == 64, "ABI struct sizes (tests/test_bake_abi.py)");
@@ -26,12 +25,9 @@ int texel_check(const char *who, const MiptScene *scene, uint32_t width, uint32_
     if (!scene || !points) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene or points", who);
     if ((uint64_t)width * height >= MIPT_QUERY_MAX_RAYS)
         return fail(MIPT_ERR_INVALID_ARG, "%s: %u x %u texels: width * height must stay below 2^31", who, width, height);
-    if (opt) {
-        if (opt->flags) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: no flag is defined", who, opt->flags);
-        for (uint32_t r : opt->reserved)
-            if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
-    }
-    return MIPT_OK;
+    if (!opt) return MIPT_OK;
+    if (opt->flags) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: no flag is defined", who, opt->flags);
+    return mipt::reserved_check(who, opt->reserved);
 }
 
 // the launch, with every argument already checked; d_points in HBM of the scene's device
@@ -40,13 +36,13 @@ int texel_launch(MiptScene *scene, uint32_t width, uint32_t height, MiptSurfaceP
     MIPT_HIP(hipSetDevice(scene->device));
     int rc;
     const size_t n = (size_t)width * height;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_owner, &scene->bake_owner_bytes, n * 8))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_huge, &scene->bake_huge_bytes, (size_t)kHugeCap * 4))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_ctl, &scene->bake_ctl_bytes, sizeof(mipt::BakeCtl)))) return rc;
+    if ((rc = scene->d_bake_owner.grow(n * 8))) return rc;
+    if ((rc = scene->d_bake_huge.grow((size_t)kHugeCap * 4))) return rc;
+    if ((rc = scene->d_bake_ctl.grow(sizeof(mipt::BakeCtl)))) return rc;
     mipt::BakeCtl ctl;
     MIPT_HIP(hipEventRecord(scene->ev0, stream));
-    MIPT_HIP(mipt::launch_bake_texels(scene->dev, scene->d_tri_order, width, height, (unsigned long long *)scene->d_bake_owner,
-                                      (uint32_t *)scene->d_bake_huge, kHugeCap, (mipt::BakeCtl *)scene->d_bake_ctl, d_points, scene->n_cu, stream));
+    MIPT_HIP(mipt::launch_bake_texels(scene->dev, scene->d_tri_order, width, height, scene->d_bake_owner, scene->d_bake_huge, kHugeCap,
+                                      scene->d_bake_ctl, d_points, scene->n_cu, stream));
     MIPT_HIP(hipEventRecord(scene->ev1, stream));
     MIPT_HIP(hipMemcpyAsync(&ctl, scene->d_bake_ctl, sizeof ctl, hipMemcpyDeviceToHost, stream));
     MIPT_HIP(hipStreamSynchronize(stream));
@@ -63,22 +59,17 @@ int texels_device(MiptScene *scene, uint32_t width, uint32_t height, const MiptB
     const char *who = "mipt_bake_texels_device";
     int rc = texel_check(who, scene, width, height, opt, d_points);
     if (rc) return rc;
-    if ((uintptr_t)d_points & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_points must be 16-byte aligned", who);
-    if (width == 0 || height == 0) { if (info) memset(info, 0, sizeof *info); return MIPT_OK; }      // no texels: no device work
-    if ((rc = mipt::device_buffer_check(who, d_points, scene->device, "d_points"))) return rc;
-    return texel_launch(scene, width, height, d_points, (hipStream_t)hip_stream, info);
+    const mipt::ItemBuffers b{nullptr, nullptr, 0, "d_points", d_points, (uint64_t)width * height * sizeof(MiptSurfacePoint), 16, false, false};
+    return mipt::device_call(who, scene, b, width == 0 || height == 0, info,
+                             [&] { return texel_launch(scene, width, height, d_points, (hipStream_t)hip_stream, info); });
 }
 
 int texels_host(MiptScene *scene, uint32_t width, uint32_t height, const MiptBakeTexelOptions *opt, MiptSurfacePoint *points, MiptBakeTexelInfo *info) {
     int rc = texel_check("mipt_bake_texels", scene, width, height, opt, points);
     if (rc) return rc;
     if (width == 0 || height == 0) { if (info) memset(info, 0, sizeof *info); return MIPT_OK; }
-    MIPT_HIP(hipSetDevice(scene->device));
-    const size_t bytes = (size_t)width * height * sizeof(MiptSurfacePoint);
-    if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, bytes))) return rc;
-    if ((rc = texel_launch(scene, width, height, (MiptSurfacePoint *)scene->d_qout, nullptr, info))) return rc;
-    MIPT_HIP(hipMemcpy(points, scene->d_qout, bytes, hipMemcpyDeviceToHost));
-    return MIPT_OK;
+    return mipt::staged_call(scene, nullptr, 0, points, (size_t)width * height * sizeof(MiptSurfacePoint),
+                             [&](const void *, void *d_out) { return texel_launch(scene, width, height, (MiptSurfacePoint *)d_out, nullptr, info); });
 }
 
 // ---- gather ------------------------------------------------------------------------------------------------------------------------
@@ -86,22 +77,11 @@ int texels_host(MiptScene *scene, uint32_t width, uint32_t height, const MiptBak
 int gather_check(const char *who, const MiptScene *scene, const void *points, uint64_t n, const MiptBakeOptions *opt, const void *radiance,
                  bool device_entry) {
     if (!scene || !points || !opt || !radiance) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, points, options or radiance", who);
-    if (n >= MIPT_QUERY_MAX_RAYS) return fail(MIPT_ERR_INVALID_ARG, "%s: n %llu: must stay below 2^31", who, (unsigned long long)n);
-    if (opt->samples == 0 || opt->max_ray_depth == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: samples and max_ray_depth must be > 0", who);
+    int rc;
+    if ((rc = mipt::ray_count_check(who, "n", n)) || (rc = mipt::ray_sampling_check(who, opt->samples, opt->max_ray_depth))) return rc;
     if (opt->sample_stride == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: sample_stride must be > 0 (every sample of a point would run on one stream)", who);
-    if (opt->traversal > MIPT_TRAVERSAL_CULLED) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown traversal %u", who, opt->traversal);
-    if (opt->shading > MIPT_SHADING_WGPU) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown shading %u", who, opt->shading);
-    if (opt->flags & ~(uint32_t)(MIPT_FLAG_COUNT | MIPT_FLAG_SUM | MIPT_FLAG_ACCUM))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_FLAG_COUNT, MIPT_FLAG_SUM and MIPT_FLAG_ACCUM are accepted", who, opt->flags);
-    if (!(opt->cull_margin >= 0.0f) || !std::isfinite(opt->cull_margin))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: cull_margin must be finite and >= 0", who);
-    for (uint32_t r : opt->reserved)
-        if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
-    if ((opt->flags & MIPT_FLAG_ACCUM) && !(opt->flags & MIPT_FLAG_SUM))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: MIPT_FLAG_ACCUM needs MIPT_FLAG_SUM (a running sum, divided once at the end)", who);
-    if ((opt->flags & MIPT_FLAG_ACCUM) && !device_entry)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: MIPT_FLAG_ACCUM needs a caller-owned device buffer: use mipt_bake_gather_device", who);
-    return MIPT_OK;
+    if ((rc = mipt::path_options_check(who, *opt))) return rc;
+    return mipt::accum_check(who, opt->flags, device_entry ? nullptr : "mipt_bake_gather_device");
 }
 
 int bad_prim(const char *who, uint64_t i, const MiptScene *scene) {
@@ -125,12 +105,12 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
     int rc;
     const uint64_t total = n * opt->samples;                              // < 2^63: n < 2^31, samples < 2^32
     const uint64_t chunk = total < kChunkPaths ? total : kChunkPaths;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_ctl, &scene->bake_ctl_bytes, sizeof(mipt::BakeCtl)))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_rays, &scene->bake_rays_bytes, (size_t)chunk * sizeof(MiptRay)))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_bake_path, &scene->bake_path_bytes, (size_t)chunk * 12 + 32))) return rc;   // + the two carry slots
+    if ((rc = scene->d_bake_ctl.grow(sizeof(mipt::BakeCtl)))) return rc;
+    if ((rc = scene->d_bake_rays.grow((size_t)chunk * sizeof(MiptRay)))) return rc;
+    if ((rc = scene->d_bake_path.grow((size_t)chunk * 12 + 32))) return rc;   // + the two carry slots
     if (check_prims) {
         mipt::BakeCtl ctl;
-        MIPT_HIP(mipt::launch_bake_check_points(d_points, n, (uint32_t)scene->n_tris, (mipt::BakeCtl *)scene->d_bake_ctl, scene->n_cu, stream));
+        MIPT_HIP(mipt::launch_bake_check_points(d_points, n, (uint32_t)scene->n_tris, scene->d_bake_ctl, scene->n_cu, stream));
         MIPT_HIP(hipMemcpyAsync(&ctl, scene->d_bake_ctl, sizeof ctl, hipMemcpyDeviceToHost, stream));
         MIPT_HIP(hipStreamSynchronize(stream));
         if (ctl.bad_point != ~0ull) return bad_prim(who, ctl.bad_point, scene);
@@ -141,7 +121,7 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
         MIPT_HIP(hipMemsetAsync(inv.get(), 0, (scene->n_tris ? scene->n_tris : 1) * sizeof(uint32_t), stream));
         MIPT_HIP(mipt::launch_bake_invert_order(scene->dev, scene->d_tri_order, inv.get(), scene->n_cu, stream));
         MIPT_HIP(hipStreamSynchronize(stream));
-        scene->d_bake_inv = inv.release();
+        scene->d_bake_inv = std::move(inv);
     }
     mipt::Event ev0, ev1;
     MIPT_HIP(hipEventCreate(ev0.put()));
@@ -151,7 +131,7 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
     MiptRadianceOptions ro{};
     ro.samples = 1; ro.max_ray_depth = opt->max_ray_depth; ro.traversal = opt->traversal; ro.cull_margin = opt->cull_margin;
     ro.shading = opt->shading; ro.flags = (opt->flags & MIPT_FLAG_COUNT) | MIPT_FLAG_SUM;
-    float *d_path = (float *)scene->d_bake_path, *d_carry = d_path + (size_t)chunk * 3;
+    float *d_path = scene->d_bake_path, *d_carry = d_path + (size_t)chunk * 3;
     mipt::BakeGather g{};
     g.points = reinterpret_cast<const uint4 *>(d_points); g.inv_order = scene->d_bake_inv;
     g.samples = opt->samples; g.first_sample = opt->first_sample; g.sample_stride = opt->sample_stride;
@@ -163,9 +143,9 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
     for (uint64_t first = 0; first < total; first += chunk, slot ^= 1u) {
         g.first_path = first; g.n_paths = total - first < chunk ? total - first : chunk;
         g.carry_in = d_carry + 4 * (slot ^ 1u); g.carry_out = d_carry + 4 * slot;
-        MIPT_HIP(mipt::launch_bake_rays(scene->dev, g, (float4 *)scene->d_bake_rays, scene->n_cu, stream));
+        MIPT_HIP(mipt::launch_bake_rays(scene->dev, g, scene->d_bake_rays, scene->n_cu, stream));
         MiptStats st;
-        rc = mipt::radiance_launch(scene, (const MiptRay *)scene->d_bake_rays, g.n_paths, &ro, d_path, stream, &st);
+        rc = mipt::radiance_launch(scene, (const MiptRay *)scene->d_bake_rays.get(), g.n_paths, &ro, d_path, stream, &st);
         if (rc && rc != MIPT_ERR_STACK) return rc;
         stack = stack || rc == MIPT_ERR_STACK;
         add_stats(&sum, st);
@@ -177,9 +157,7 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
     MIPT_HIP(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
     sum.kernel_ms = ms;
     if (stats) *stats = sum;
-    if (stack)
-        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
-                    (unsigned long long)sum.stack_overflows, mipt::kStackLds + mipt::kStackOvf);
+    if (stack) return mipt::stack_overflow_fail(sum.stack_overflows);
     return MIPT_OK;
 }
 
@@ -188,15 +166,9 @@ int gather_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n
     const char *who = "mipt_bake_gather_device";
     int rc = gather_check(who, scene, d_points, n, opt, d_radiance, true);
     if (rc) return rc;
-    if ((uintptr_t)d_points & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_points must be 16-byte aligned", who);
-    if ((uintptr_t)d_radiance & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_radiance must be 4-byte aligned", who);
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n == 0) return MIPT_OK;                                           // no device work
-    if (mipt::ranges_overlap(d_points, n * sizeof(MiptSurfacePoint), d_radiance, n * 12))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: d_points overlaps d_radiance", who);
-    if ((rc = mipt::device_buffer_check(who, d_points, scene->device, "d_points"))) return rc;
-    if ((rc = mipt::device_buffer_check(who, d_radiance, scene->device, "d_radiance"))) return rc;
-    return gather_launch(who, scene, d_points, n, opt, d_radiance, (hipStream_t)hip_stream, true, stats);
+    const mipt::ItemBuffers b{"d_points", d_points, n * sizeof(MiptSurfacePoint), "d_radiance", d_radiance, n * 12, 4, true, true};
+    return mipt::device_call(who, scene, b, n == 0, stats,
+                             [&] { return gather_launch(who, scene, d_points, n, opt, d_radiance, (hipStream_t)hip_stream, true, stats); });
 }
 
 int gather_host(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, const MiptBakeOptions *opt, float *radiance, MiptStats *stats) {
@@ -207,15 +179,9 @@ int gather_host(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, co
     if (n == 0) return MIPT_OK;
     for (uint64_t i = 0; i < n; i++)
         if (points[i].prim != MIPT_HIT_NONE && (points[i].prim & 0x01ffffffu) >= scene->n_tris) return bad_prim(who, i, scene);
-    MIPT_HIP(hipSetDevice(scene->device));
-    const size_t out_bytes = (size_t)n * 3 * sizeof(float);
-    if ((rc = mipt::grow_device_buffer(&scene->d_qrays, &scene->qrays_bytes, (size_t)n * sizeof(MiptSurfacePoint)))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
-    MIPT_HIP(hipMemcpy(scene->d_qrays, points, (size_t)n * sizeof(MiptSurfacePoint), hipMemcpyHostToDevice));
-    rc = gather_launch(who, scene, (const MiptSurfacePoint *)scene->d_qrays, n, opt, (float *)scene->d_qout, nullptr, false, stats);
-    if (rc && rc != MIPT_ERR_STACK) return rc;
-    MIPT_HIP(hipMemcpy(radiance, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
-    return rc;
+    return mipt::staged_call(scene, points, (size_t)n * sizeof(MiptSurfacePoint), radiance, (size_t)n * 3 * sizeof(float), [&](const void *d_points, void *d_out) {
+        return gather_launch(who, scene, (const MiptSurfacePoint *)d_points, n, opt, (float *)d_out, nullptr, false, stats);
+    });
 }
 
 } // namespace

@@ -1,10 +1,12 @@
 // mipt_host_util.h -- the host plumbing every translation unit of libmipt.so shares and that needs HIP types: the HIP-call macro,
 // the owners of device memory, pinned memory, streams and events, the scope guards, the grow-on-demand device buffer and, at the
 // end, the device half of an image-space entry: its device-entry checks and the staging of its host entry.  Internal; mipt_scene.h
-// includes it.  What needs no HIP type -- mipt::fail, the MIPT_NO_THROW fence, mipt::Owned in mipt_internal.h, the plane description
-// and its checks in mipt_planes.h -- is what the CPU builds of tests/cpp/ include.
+// includes it.  What needs no HIP type -- mipt::fail, the MIPT_NO_THROW fence, mipt::Owned and mipt::Grown in mipt_internal.h, the
+// plane description and its checks in mipt_planes.h, the option checks of the ray entries in mipt_rays.h -- is what the CPU builds of
+// tests/cpp/ include.
 #pragma once
 #include "mipt_planes.h"                                         // and with it mipt_internal.h
+#include "mipt_rays.h"
 
 #include <hip/hip_runtime.h>
 
@@ -63,15 +65,17 @@ class SyncOnExit {
 // a helper thread that is joined on every way out of the scope (a joinable std::thread's destructor calls std::terminate)
 struct JoinOnExit { std::thread t; ~JoinOnExit() { if (t.joinable()) t.join(); } };
 
-// *p holds at least want_bytes of device memory (current device) afterwards; a buffer that is too small is freed and replaced, its
-// contents are not kept.  *have is its size in bytes.
-inline int grow_device_buffer(void **p, size_t *have, size_t want_bytes) {
-    if (*have >= want_bytes && *p) return MIPT_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    MIPT_HIP(hipMalloc(p, want_bytes));
-    *have = want_bytes;
-    return MIPT_OK;
-}
+// ---- what lives as long as a scene or a multi-GPU handle: a device buffer that grows on demand.  grow(): at least want_bytes of
+// device memory (current device) afterwards; a buffer that is too small is freed and replaced, its contents are not kept.  bytes()
+// is its size.  Freed with its holder. ----
+inline hipError_t device_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+template <class T> struct DevBuf : Grown<T, device_alloc, hipFree> {
+    int grow(size_t want_bytes) {
+        const hipError_t e = Grown<T, device_alloc, hipFree>::grow(want_bytes);
+        if (e != hipSuccess) return fail(MIPT_ERR_HIP, MIPT_HIP_FAIL_FMT, "hipMalloc(p, want_bytes)", hipGetErrorString(e));
+        return MIPT_OK;
+    }
+};
 
 // MIPT_OK if `p` is device memory of HIP device `device`, else MIPT_ERR_INVALID_ARG with "<who>: <name> is not device memory of
 // <whose> <device>".  device < 0: of any device.  *found (may be NULL) receives the device `p` lives on.

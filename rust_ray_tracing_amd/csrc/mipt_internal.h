@@ -1,8 +1,9 @@
 // mipt_internal.h -- functions shared between the translation units of libmipt.so.  None of them is exported: the library is built
 // with -fvisibility=hidden and only the MIPT_API declarations of include/mipt.h leave it.  (Host C++ only: no HIP types here, so the
 // CPU sanitizer builds of tests/cpp/ can include it.)
-// The plumbing that needs no HIP type lives here: mipt::fail (defined below), the MIPT_NO_THROW fence and mipt::Owned, the owner of
-// one handle.  The HIP-call macros, Owned's HIP instances and the grow-on-demand device buffer are in mipt_host_util.h.
+// The plumbing that needs no HIP type lives here: mipt::fail (defined below), the MIPT_NO_THROW fence, mipt::Owned, the owner of
+// one handle, and mipt::Grown, the owner of a block that grows on demand.  The HIP-call macros and the HIP instances of both owners
+// are in mipt_host_util.h.
 #pragma once
 #include "../../include/mipt.h"
 
@@ -11,6 +12,7 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <utility>
 
 void mipt_internal_set_error(const char *msg);          // sets the calling thread's mipt_last_error() text (mipt_api.cpp)
 
@@ -63,12 +65,44 @@ class Owned {
     T get() const { return h_; }
     operator T() const { return h_; }                            // a kernel argument, a HIP call's stream: used like the bare handle --
                                                                  // but NEVER handed to Free (hipFree(d_x)): reset() is the early release
+    template <class U> explicit operator U *() const { return (U *)h_; }   // and cast like it: (const uint32_t *)d_geom
     explicit operator bool() const { return h_ != T{}; }
     T release() { const T h = h_; h_ = T{}; return h; }          // gives the handle up; nothing is freed
     void reset(T h = T{}) { if (h_ != T{}) (void)Free(h_); h_ = h; }
     T *put() { reset(); return &h_; }                            // for the call that allocates: hipStreamCreate(s.put())
   private:
     T h_{};
+};
+
+// The one owner of a block that grows on demand and lives as long as what holds it (a scene's workspace; the HIP instance is
+// mipt::DevBuf in mipt_host_util.h).  Alloc(void **, bytes) returns 0 when it has stored a block, Free releases one.  Move-only;
+// empty, with bytes() 0, by default and after a move.  Used like the bare pointer, and like Owned never handed to Free.
+template <class T, auto Alloc, auto Free>
+class Grown {
+  public:
+    Grown() = default;
+    Grown(Grown &&o) noexcept : p_(std::move(o.p_)), bytes_(o.bytes_) { o.bytes_ = 0; }
+    Grown &operator=(Grown &&o) noexcept {
+        if (this != &o) { p_ = std::move(o.p_); bytes_ = o.bytes_; o.bytes_ = 0; }
+        return *this;
+    }
+    T *get() const { return p_.get(); }
+    operator T *() const { return p_.get(); }
+    explicit operator bool() const { return (bool)p_; }
+    size_t bytes() const { return bytes_; }
+    // At least want_bytes afterwards, or Alloc's status and an empty owner.  A block that is large enough stays, pointer and all; one
+    // that is too small is freed first and replaced: its contents are not kept.
+    auto grow(size_t want_bytes) -> decltype(Alloc((void **)nullptr, want_bytes)) {
+        if (p_ && bytes_ >= want_bytes) return {};
+        reset();
+        const auto status = Alloc((void **)p_.put(), want_bytes);
+        if (status == decltype(status){}) bytes_ = want_bytes; else p_.release();     // a failed Alloc owes no block
+        return status;
+    }
+    void reset() { p_.reset(); bytes_ = 0; }
+  private:
+    Owned<T *, Free> p_;
+    size_t bytes_ = 0;
 };
 
 // ---- device-layout orders ----

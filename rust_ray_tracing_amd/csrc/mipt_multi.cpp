@@ -32,14 +32,10 @@ struct MiptMulti {
     std::vector<MiptScene *> scenes;
     std::vector<ncclComm_t> comms;
     std::vector<hipStream_t> streams;
-    std::vector<float *> d_part;          // per device: packed tile slice / full-frame partial sum
-    std::vector<size_t> part_bytes;
-    float *d_all = nullptr;               // root: gathered slices
-    size_t all_bytes = 0;
-    float *d_frame = nullptr;             // root: assembled frame
-    size_t frame_bytes = 0;
-    uint8_t *d_rgba = nullptr;
-    size_t rgba_bytes = 0;
+    std::vector<mipt::DevBuf<float>> d_part;   // per device: packed tile slice / full-frame partial sum
+    mipt::DevBuf<float> d_all;            // root: gathered slices
+    mipt::DevBuf<float> d_frame;          // root: assembled frame
+    mipt::DevBuf<uint8_t> d_rgba;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<MiptStats> last;          // per device: trace-kernel stats of the last mipt_render_multi* call
 };
@@ -80,11 +76,9 @@ void destroy(MiptMulti *m) {
     for (int i = 0; i < (int)m->devices.size(); i++) {
         (void)hipSetDevice(m->devices[i]);
         if (i < (int)m->streams.size() && m->streams[i]) (void)hipStreamDestroy(m->streams[i]);
-        if (i < (int)m->d_part.size() && m->d_part[i]) (void)hipFree(m->d_part[i]);
+        if (i < (int)m->d_part.size()) m->d_part[i].reset();
         if (i == 0) {
-            if (m->d_all) (void)hipFree(m->d_all);
-            if (m->d_frame) (void)hipFree(m->d_frame);
-            if (m->d_rgba) (void)hipFree(m->d_rgba);
+            m->d_all.reset(); m->d_frame.reset(); m->d_rgba.reset();
             if (m->ev0) (void)hipEventDestroy(m->ev0);
             if (m->ev1) (void)hipEventDestroy(m->ev1);
         }
@@ -112,8 +106,7 @@ int create_impl(const MiptSceneDesc *desc, const int *device_ids, int n_devices,
     }
     m->scenes.assign(n_devices, nullptr);
     m->streams.assign(n_devices, nullptr);
-    m->d_part.assign(n_devices, nullptr);
-    m->part_bytes.assign(n_devices, 0);
+    m->d_part.resize(n_devices);
     m->last.assign(n_devices, MiptStats{});
     // scene replicas: the scene reaches device 0 once (host layout + upload, or built there from the triangles); the others are
     // device-to-device copies
@@ -169,16 +162,16 @@ int render_impl(MiptMulti *m, const MiptCamera *camera, const MiptOptions *opt, 
 
     for (int i = 0; i < n; i++) {
         MIPT_HIP(hipSetDevice(m->devices[i]));
-        const int rc = mipt::grow_device_buffer((void **)&m->d_part[i], &m->part_bytes[i], part_floats * sizeof(float));
+        const int rc = m->d_part[i].grow(part_floats * sizeof(float));
         if (rc) return rc;
     }
     MIPT_HIP(hipSetDevice(m->devices[0]));
     {
-        int rc = mipt::grow_device_buffer((void **)&m->d_all, &m->all_bytes, (mode == MIPT_MULTI_TILES ? (size_t)n * part_floats : 4) * sizeof(float));
+        int rc = m->d_all.grow((mode == MIPT_MULTI_TILES ? (size_t)n * part_floats : 4) * sizeof(float));
         if (rc) return rc;
         if (!device_out) {
-            if ((rc = mipt::grow_device_buffer((void **)&m->d_frame, &m->frame_bytes, (size_t)n_pix * 3 * sizeof(float)))) return rc;
-            if (rgba8 && (rc = mipt::grow_device_buffer((void **)&m->d_rgba, &m->rgba_bytes, (size_t)n_pix * 4))) return rc;
+            if ((rc = m->d_frame.grow((size_t)n_pix * 3 * sizeof(float)))) return rc;
+            if (rgba8 && (rc = m->d_rgba.grow((size_t)n_pix * 4))) return rc;
         }
     }
     float *const d_frame = device_out ? hdr_rgb : m->d_frame;       // where the assembled frame is built (device 0)

@@ -4,7 +4,6 @@
 #include "pt_kernel.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
-#include <cmath>
 #include <cstring>
 
 static_assert(sizeof(MiptRay) == 32 && sizeof(MiptHit) == 16 && sizeof(MiptQueryOptions) == 32, "ABI struct sizes (tests/test_query_abi.py)");
@@ -16,19 +15,10 @@ using mipt::fail;
 // everything that needs neither the scene's contents nor a device
 int validate(const char *who, const MiptScene *scene, const void *rays, const void *out, uint64_t n_rays, const MiptQueryOptions *opt) {
     if (!scene || !rays || !out) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, rays or output", who);
-    if (n_rays >= MIPT_QUERY_MAX_RAYS) return fail(MIPT_ERR_INVALID_ARG, "%s: n_rays %llu: must stay below 2^31", who, (unsigned long long)n_rays);
-    if (opt) {
-        if (opt->traversal > MIPT_TRAVERSAL_CULLED) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown traversal %u", who, opt->traversal);
-        if (opt->flags & ~(uint32_t)MIPT_FLAG_COUNT) return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_FLAG_COUNT is accepted", who, opt->flags);
-        if (!(opt->cull_margin >= 0.0f) || !std::isfinite(opt->cull_margin))
-            return fail(MIPT_ERR_INVALID_ARG, "%s: cull_margin must be finite and >= 0", who);
-        for (uint32_t r : opt->reserved)
-            if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
-    }
-    return MIPT_OK;
+    int rc = mipt::ray_count_check(who, "n_rays", n_rays);
+    if (rc || !opt) return rc;
+    return mipt::ray_options_check(who, *opt, nullptr, MIPT_FLAG_COUNT, "MIPT_FLAG_COUNT is");
 }
-
-using mipt::device_buffer_check;                               // mipt_host_util.h
 
 // the launch, with every argument already checked; d_rays / d_out in HBM of the scene's device
 int query_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptQueryOptions *opt, void *d_out, bool anyhit,
@@ -76,12 +66,11 @@ int query_device(const char *who, MiptScene *scene, const MiptRay *d_rays, uint6
                  bool anyhit, void *hip_stream, MiptStats *stats) {
     int rc = validate(who, scene, d_rays, d_out, n_rays, opt);
     if (rc) return rc;
-    if (((uintptr_t)d_rays & 15u) || (!anyhit && ((uintptr_t)d_out & 15u)))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", who, ((uintptr_t)d_rays & 15u) ? "d_rays" : "d_hits");
-    if (n_rays == 0) return query_launch(scene, nullptr, 0, opt, nullptr, anyhit, nullptr, stats);       // MIPT_OK, no device work
-    if ((rc = device_buffer_check(who, d_rays, scene->device, "d_rays"))) return rc;
-    if ((rc = device_buffer_check(who, d_out, scene->device, anyhit ? "d_occluded" : "d_hits"))) return rc;
-    return query_launch(scene, d_rays, n_rays, opt, d_out, anyhit, (hipStream_t)hip_stream, stats);
+    // overlapping d_rays and d_hits are not refused (a follow-up)
+    const mipt::ItemBuffers b{"d_rays", d_rays, n_rays * sizeof(MiptRay), anyhit ? "d_occluded" : "d_hits", d_out, n_rays * (anyhit ? 1u : sizeof(MiptHit)),
+                              anyhit ? 1u : 16u, false, false};
+    return mipt::device_call(who, scene, b, n_rays == 0, stats,
+                             [&] { return query_launch(scene, d_rays, n_rays, opt, d_out, anyhit, (hipStream_t)hip_stream, stats); });
 }
 
 int query_host(const char *who, MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptQueryOptions *opt, void *out, bool anyhit,
@@ -89,15 +78,8 @@ int query_host(const char *who, MiptScene *scene, const MiptRay *rays, uint64_t 
     int rc = validate(who, scene, rays, out, n_rays, opt);
     if (rc) return rc;
     if (n_rays == 0) return query_launch(scene, nullptr, 0, opt, nullptr, anyhit, nullptr, stats);
-    MIPT_HIP(hipSetDevice(scene->device));
-    const size_t out_bytes = (size_t)n_rays * (anyhit ? 1u : sizeof(MiptHit));
-    if ((rc = mipt::grow_device_buffer(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
-    MIPT_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
-    rc = query_launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, scene->d_qout, anyhit, nullptr, stats);
-    if (rc && rc != MIPT_ERR_STACK) return rc;
-    MIPT_HIP(hipMemcpy(out, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
-    return rc;
+    return mipt::staged_call(scene, rays, (size_t)n_rays * sizeof(MiptRay), out, (size_t)n_rays * (anyhit ? 1u : sizeof(MiptHit)),
+                             [&](const void *d_rays, void *d_out) { return query_launch(scene, (const MiptRay *)d_rays, n_rays, opt, d_out, anyhit, nullptr, stats); });
 }
 
 } // namespace

@@ -5,7 +5,6 @@
 #include "pt_kernel.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
 
-#include <cmath>
 #include <cstring>
 
 static_assert(sizeof(MiptRadianceOptions) == 64 && sizeof(MiptRay) == 32, "ABI struct sizes (tests/test_radiance_abi.py)");
@@ -19,21 +18,11 @@ using mipt::fail;
 int check(const char *who, const MiptScene *scene, const void *rays, uint64_t n_rays, const MiptRadianceOptions *opt, const void *radiance,
           bool device_entry) {
     if (!scene || !rays || !opt || !radiance) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, rays, options or radiance", who);
-    if (n_rays >= MIPT_QUERY_MAX_RAYS) return fail(MIPT_ERR_INVALID_ARG, "%s: n_rays %llu: must stay below 2^31", who, (unsigned long long)n_rays);
-    if (opt->samples == 0 || opt->max_ray_depth == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: samples and max_ray_depth must be > 0", who);
-    if (opt->traversal > MIPT_TRAVERSAL_CULLED) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown traversal %u", who, opt->traversal);
-    if (opt->shading > MIPT_SHADING_WGPU) return fail(MIPT_ERR_INVALID_ARG, "%s: unknown shading %u", who, opt->shading);
-    if (opt->flags & ~(uint32_t)(MIPT_FLAG_COUNT | MIPT_FLAG_SUM | MIPT_FLAG_ACCUM))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_FLAG_COUNT, MIPT_FLAG_SUM and MIPT_FLAG_ACCUM are accepted", who, opt->flags);
-    if (!(opt->cull_margin >= 0.0f) || !std::isfinite(opt->cull_margin))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: cull_margin must be finite and >= 0", who);
-    for (uint32_t r : opt->reserved)
-        if (r) return fail(MIPT_ERR_INVALID_ARG, "%s: reserved option fields must be 0", who);
-    if ((opt->flags & MIPT_FLAG_ACCUM) && !(opt->flags & MIPT_FLAG_SUM))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: MIPT_FLAG_ACCUM needs MIPT_FLAG_SUM (a running sum, divided once at the end)", who);
-    if ((opt->flags & MIPT_FLAG_ACCUM) && !device_entry)
-        return fail(MIPT_ERR_INVALID_ARG, "%s: MIPT_FLAG_ACCUM needs a caller-owned device buffer: use mipt_query_radiance_device", who);
-    return MIPT_OK;
+    int rc;
+    if ((rc = mipt::ray_count_check(who, "n_rays", n_rays)) || (rc = mipt::ray_sampling_check(who, opt->samples, opt->max_ray_depth)) ||
+        (rc = mipt::path_options_check(who, *opt)))
+        return rc;
+    return mipt::accum_check(who, opt->flags, device_entry ? nullptr : "mipt_query_radiance_device");
 }
 
 } // namespace
@@ -94,29 +83,17 @@ int radiance_device(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, co
     const char *who = "mipt_query_radiance_device";
     int rc = check(who, scene, d_rays, n_rays, opt, d_radiance, true);
     if (rc) return rc;
-    if ((uintptr_t)d_rays & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_rays must be 16-byte aligned", who);
-    if ((uintptr_t)d_radiance & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_radiance must be 4-byte aligned", who);
-    if (n_rays == 0) return radiance_launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);            // MIPT_OK, no device work
-    if (mipt::ranges_overlap(d_rays, n_rays * sizeof(MiptRay), d_radiance, n_rays * 12))
-        return fail(MIPT_ERR_INVALID_ARG, "%s: d_rays overlaps d_radiance", who);
-    if ((rc = mipt::device_buffer_check(who, d_rays, scene->device, "d_rays"))) return rc;
-    if ((rc = mipt::device_buffer_check(who, d_radiance, scene->device, "d_radiance"))) return rc;
-    return radiance_launch(scene, d_rays, n_rays, opt, d_radiance, (hipStream_t)hip_stream, stats);
+    const mipt::ItemBuffers b{"d_rays", d_rays, n_rays * sizeof(MiptRay), "d_radiance", d_radiance, n_rays * 12, 4, true, false};
+    return mipt::device_call(who, scene, b, n_rays == 0, stats,
+                             [&] { return radiance_launch(scene, d_rays, n_rays, opt, d_radiance, (hipStream_t)hip_stream, stats); });
 }
 
 int radiance_host(MiptScene *scene, const MiptRay *rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *radiance, MiptStats *stats) {
     int rc = check("mipt_query_radiance", scene, rays, n_rays, opt, radiance, false);
     if (rc) return rc;
     if (n_rays == 0) return radiance_launch(scene, nullptr, 0, opt, nullptr, nullptr, stats);
-    MIPT_HIP(hipSetDevice(scene->device));
-    const size_t out_bytes = (size_t)n_rays * 3 * sizeof(float);
-    if ((rc = mipt::grow_device_buffer(&scene->d_qrays, &scene->qrays_bytes, (size_t)n_rays * sizeof(MiptRay)))) return rc;
-    if ((rc = mipt::grow_device_buffer(&scene->d_qout, &scene->qout_bytes, out_bytes < 16 ? 16 : out_bytes))) return rc;
-    MIPT_HIP(hipMemcpy(scene->d_qrays, rays, (size_t)n_rays * sizeof(MiptRay), hipMemcpyHostToDevice));
-    rc = radiance_launch(scene, (const MiptRay *)scene->d_qrays, n_rays, opt, (float *)scene->d_qout, nullptr, stats);
-    if (rc && rc != MIPT_ERR_STACK) return rc;
-    MIPT_HIP(hipMemcpy(radiance, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
-    return rc;
+    return mipt::staged_call(scene, rays, (size_t)n_rays * sizeof(MiptRay), radiance, (size_t)n_rays * 3 * sizeof(float),
+                             [&](const void *d_rays, void *d_out) { return radiance_launch(scene, (const MiptRay *)d_rays, n_rays, opt, (float *)d_out, nullptr, stats); });
 }
 
 } // namespace

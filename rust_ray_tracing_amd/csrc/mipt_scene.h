@@ -19,7 +19,12 @@ namespace mipt { struct SceneMesh; }
 struct MiptScene {
     int device = 0;
     mipt::DevScene dev{};
-    void *d_geom = nullptr, *d_tri_attr = nullptr, *d_mats = nullptr, *d_mats_full = nullptr, *d_texels = nullptr;
+    // Every device array, buffer and event below is owned by its member and goes with the scene (mipt::free_scene is `delete`):
+    // DevPtr, a fixed array; DevBuf, workspace that grows on demand and knows its size.
+    mipt::DevPtr<char> d_geom, d_tri_attr;
+    mipt::DevPtr<mipt::DevMaterial> d_mats;
+    mipt::DevPtr<mipt::DevMaterialFull> d_mats_full;
+    mipt::DevPtr<uint32_t> d_texels;
     // Sizes a replica allocates and copies (clone_issue, replica_refresh): every one is at most what its buffer was allocated with.
     // geom_alloc is the allocation (the payload, dev.geom_bytes, is copied); attr_bytes is allocation and payload; mats_bytes,
     // mats_full_bytes and texel_bytes are the allocations -- the payload, or one record / 16 bytes when that is more.
@@ -27,29 +32,25 @@ struct MiptScene {
     uint64_t n_texels = 0;                  // texels in the pool (its payload is n_texels * 4 bytes)
     // a scene whose BVH was built on the device keeps the tree for mipt_scene_get_bvh: nodes in the reference's order and the
     // triangle permutation BVH::build applied (reordered[t] = original[tri_order[t]])
-    MiptNode *d_nodes = nullptr;
+    mipt::DevPtr<MiptNode> d_nodes;
     uint32_t n_nodes = 0;
-    uint32_t *d_tri_order = nullptr;
+    mipt::DevPtr<uint32_t> d_tri_order;
     MiptSceneInfo info{};
     // workspace
-    mipt::DevStats *d_stats = nullptr;
-    uint32_t *d_ovf = nullptr;              // spill slots of the traversal stack, one set per wave of the largest grid launched so far:
-    size_t ovf_waves = 0;                   // sized and grown by mipt::traversal_grid (mipt_host_util.h) and by nothing else
-    uint32_t *d_touched = nullptr;          // MIPT_FLAG_TOUCHED: line bitmap, allocated on first use
+    mipt::DevPtr<mipt::DevStats> d_stats;
+    mipt::DevBuf<uint32_t> d_ovf;           // spill slots of the traversal stack, one set per wave of the largest grid launched so far:
+                                            // sized and grown by mipt::traversal_grid (below) and by nothing else
+    mipt::DevPtr<uint32_t> d_touched;       // MIPT_FLAG_TOUCHED: line bitmap, allocated on first use
     size_t n_tris = 0;
-    float *d_hdr = nullptr;
-    size_t hdr_bytes = 0;
-    uint8_t *d_rgba = nullptr;
-    size_t rgba_bytes = 0;
-    float4 *d_cams = nullptr;               // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
-    size_t cams_bytes = 0;
+    mipt::DevBuf<float> d_hdr;
+    mipt::DevBuf<uint8_t> d_rgba;
+    mipt::DevBuf<float4> d_cams;            // mipt_render_batch*: the camera table (DevBatch::cams), grown on demand
     std::vector<float4> h_cams;             // its host staging copy (outlives the stream-ordered upload)
     // tile order (mipt_api.cpp render_launch, pt_kernel.hip): rays per local tile as the last plain single-view launch measured them,
     // the tiles sorted by that cost, and what that launch was -- {width, height, tile world, tile rank, local tiles, seed mode,
     // samples} and its camera.  A launch with the same key and camera hands its tiles out in that order; any other runs in the plain
     // order and measures.
-    uint32_t *d_tile_cost = nullptr, *d_tile_order = nullptr;
-    size_t tile_cost_bytes = 0, tile_order_bytes = 0;
+    mipt::DevBuf<uint32_t> d_tile_cost, d_tile_order;
     uint32_t tile_key[7] = {0, 0, 0, 0, 0, 0, 0};
     float tile_cam[12] = {0};               // DevParams::cam of that launch, compared bit for bit
     bool tile_order_valid = false;          // d_tile_order is the order of d_tile_cost, both of the launch tile_key describes
@@ -57,29 +58,30 @@ struct MiptScene {
     // hot pixels, part of the same state (one key, one valid flag): rays per slot (local tile * 64 + pixel of the tile) of that launch,
     // the tile costs being their sums; the hot_n slots of highest cost, which the next launch with the key and camera hands out first,
     // their bitmap (2 words per tile) and the scratch of the selection kernels (mipt::hot_work_words)
-    uint32_t *d_pixel_cost = nullptr, *d_hot = nullptr, *d_hot_bits = nullptr, *d_hot_work = nullptr;
-    size_t pixel_cost_bytes = 0, hot_bytes = 0, hot_bits_bytes = 0, hot_work_bytes = 0;
+    mipt::DevBuf<uint32_t> d_pixel_cost, d_hot, d_hot_bits, d_hot_work;
     uint32_t hot_n = 0;                     // entries of d_hot (0 = the launch was too large for 32-bit slots: no hot list)
     uint32_t hot_used = 0;                  // entries that launch itself took from the list made before it (0 = it ran without)
     // the list goes on behind its first hot_n entries, in the same cost order: list_n >= hot_n entries of d_hot, all local slots where
     // the compiled-in ratio says so (mipt_api.cpp MIPT_LIST_NUM / DEN); a launch hands out all of them before it walks the tiles
     uint32_t list_n = 0;                    // entries of d_hot in cost order (0 exactly when hot_n is 0)
     uint32_t list_used = 0;                 // entries that launch itself took, hot_used of them as "the hot pixels"
-    void *d_qrays = nullptr, *d_qout = nullptr;   // mipt_query_closest / _occluded (host entries): staging for rays and results, grown on demand
-    size_t qrays_bytes = 0, qout_bytes = 0;
+    mipt::DevBuf<void> d_qrays, d_qout;     // the host entries of the queries, radiance queries and bake: staging for items and results (mipt::staged_call)
     // baking (mipt_bake.cpp, bake.hip): the owner word per texel and the list of triangles the whole grid covers (mipt_bake_texels);
     // the counters of a call; the map from the caller's triangle index to its tri_pos record, made on first use and dropped with the tree (release_geometry); the ray
     // and radiance staging of a chunk of paths and the two carry slots of a point that spans chunks (mipt_bake_gather).  Grown on demand.
-    void *d_bake_owner = nullptr, *d_bake_huge = nullptr, *d_bake_ctl = nullptr, *d_bake_rays = nullptr, *d_bake_path = nullptr;
-    size_t bake_owner_bytes = 0, bake_huge_bytes = 0, bake_ctl_bytes = 0, bake_rays_bytes = 0, bake_path_bytes = 0;
-    uint32_t *d_bake_inv = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    mipt::DevBuf<unsigned long long> d_bake_owner;
+    mipt::DevBuf<uint32_t> d_bake_huge;
+    mipt::DevBuf<mipt::BakeCtl> d_bake_ctl;
+    mipt::DevBuf<float4> d_bake_rays;
+    mipt::DevBuf<float> d_bake_path;
+    mipt::DevPtr<uint32_t> d_bake_inv;
+    mipt::Event ev0, ev1;
     int n_cu = 0;
     uint32_t max_leaf = 0;
     // REFIT plan of mipt_scene_update_triangles (scene_update.hip), made on the first REFIT and kept until the tree changes: the
     // pair records grouped by depth (record indices, level after level from the root) and, for a scene that keeps its tree
     // (d_nodes), the reference pair index of every record
-    uint32_t *d_refit_plan = nullptr, *d_refit_pair = nullptr;
+    mipt::DevPtr<uint32_t> d_refit_plan, d_refit_pair;
     std::vector<uint32_t> refit_level_off;  // level d = plan[off[d], off[d+1]); empty = no plan yet
     // the resident indexed mesh of a scene made by mipt_scene_create_from_mesh (scene_mesh.hip); null for a plain scene
     mipt::SceneMesh *mesh = nullptr;
@@ -123,7 +125,9 @@ int upload_material_tables(MiptScene *s, const MaterialTables &t);
 
 // ---- who frees what: ResidentBvh and SceneGeometry own their device arrays.  They are move-only, what one still holds when it goes
 // out of scope is freed on every outcome, and arrays change hands by a move or release(), never by copying a pointer.  The members of
-// MiptScene are the other kind: raw pointers that live as long as the handle, released by free_scene / release_geometry alone. ----
+// MiptScene are owners of the same kind that live as long as the handle: attach_geometry moves a SceneGeometry's arrays into them,
+// release_geometry resets those of the geometry, and deleting the scene frees whatever is left (free_scene names none of them).  The
+// one exception is MiptScene::mesh, whose arrays scene_mesh.hip still frees by hand (free_mesh). ----
 // BVH::build (bvh.rs:13-161) on the GPU with everything staying in HBM (bvh_build_device.hip): `d_tris` in, the node array in the
 // reference's order and the triangle permutation out (reordered[t] = original[d_tri_order[t]]).
 struct ResidentBvh {
@@ -177,13 +181,14 @@ inline int traversal_grid(MiptScene *scene, int blocks_per_cu, unsigned long lon
     if (grid > need_blocks) grid = need_blocks;
     if (grid < 1) grid = 1;
     const size_t waves = (size_t)grid * kWavesPerBlock;
-    if (waves > scene->ovf_waves) {
-        if (scene->d_ovf) { (void)hipFree(scene->d_ovf); scene->d_ovf = nullptr; scene->ovf_waves = 0; }
-        MIPT_HIP(hipMalloc((void **)&scene->d_ovf, waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t)));
-        scene->ovf_waves = waves;
-    }
     *grid_out = (int)grid;
-    return MIPT_OK;
+    return scene->d_ovf.grow(waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t));
+}
+
+// MIPT_ERR_STACK with the one text every launch that traces reports it in (traversal_launch; mipt_bake.cpp over its chunks)
+inline int stack_overflow_fail(unsigned long long count) {
+    return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)", count,
+                kStackLds + kStackOvf);
 }
 
 // One timed launch on `stream`: d_stats zeroed, ev0, launch(), ev1, after_ev1(), the counters copied to `hs`, the stream
@@ -200,10 +205,50 @@ int traversal_launch(MiptScene *scene, hipStream_t stream, Launch launch, After 
     MIPT_HIP(hipMemcpyAsync(&hs, scene->d_stats, sizeof hs, hipMemcpyDeviceToHost, stream));
     MIPT_HIP(hipStreamSynchronize(stream));
     MIPT_HIP(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
-    if (hs.stack_overflows)
-        return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)",
-                    hs.stack_overflows, kStackLds + kStackOvf);
+    if (hs.stack_overflows) return stack_overflow_fail(hs.stack_overflows);
     return MIPT_OK;
+}
+
+// ---- the entries that take a list of work items (mipt_query.cpp, mipt_radiance.cpp, mipt_bake.cpp; their option checks:
+// mipt_rays.h) ----
+// The buffers of a device entry: the items (`in` null: the entry has none -- the texels), always 16-byte aligned, and the results.
+struct ItemBuffers {
+    const char *in_name; const void *in; uint64_t in_bytes;
+    const char *out_name; const void *out; uint64_t out_bytes; uint32_t out_align;      // out_align 1: any address
+    bool refuse_overlap;
+    bool zero_first;                    // mipt_bake_gather_device zeroes its stats as soon as both buffers are aligned
+};
+// A device entry after its argument and option checks, in the order its caller sees: the alignment of the items, then of the results,
+// also of an empty list; an empty call is done, with *results (the caller's MiptStats or info, may be null) zeroed; no overlap, where
+// the entry refuses it; both buffers memory of the scene's device, which is the first use of the scene; then launch().
+template <class Results, class Launch>
+int device_call(const char *who, const MiptScene *scene, const ItemBuffers &b, bool no_items, Results *results, Launch launch) {
+    if (b.in && ((uintptr_t)b.in & 15u)) return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", who, b.in_name);
+    if ((uintptr_t)b.out & (b.out_align - 1u)) return fail(MIPT_ERR_INVALID_ARG, "%s: %s must be %u-byte aligned", who, b.out_name, b.out_align);
+    if (results && (no_items || b.zero_first)) memset(results, 0, sizeof *results);
+    if (no_items) return MIPT_OK;                                 // no device work
+    if (b.refuse_overlap && ranges_overlap(b.in, b.in_bytes, b.out, b.out_bytes))
+        return fail(MIPT_ERR_INVALID_ARG, "%s: %s overlaps %s", who, b.in_name, b.out_name);
+    int rc;
+    if (b.in && (rc = device_buffer_check(who, b.in, scene->device, b.in_name))) return rc;
+    if ((rc = device_buffer_check(who, b.out, scene->device, b.out_name))) return rc;
+    return launch();
+}
+
+// A host entry on the scene's staging pair: d_qrays and d_qout grown, the items (`in` null: none) copied in, launch(d_in, d_out) on the
+// null stream, the results copied out.  Both copies block.  MIPT_ERR_STACK from the launch means that the results are there: they are
+// fetched and the status is passed on.
+template <class Launch>
+int staged_call(MiptScene *scene, const void *in, size_t in_bytes, void *out, size_t out_bytes, Launch launch) {
+    int rc;
+    MIPT_HIP(hipSetDevice(scene->device));
+    if (in && (rc = scene->d_qrays.grow(in_bytes))) return rc;
+    if ((rc = scene->d_qout.grow(out_bytes < 16 ? 16 : out_bytes))) return rc;
+    if (in) MIPT_HIP(hipMemcpy(scene->d_qrays, in, in_bytes, hipMemcpyHostToDevice));
+    rc = launch(scene->d_qrays.get(), scene->d_qout.get());
+    if (rc && rc != MIPT_ERR_STACK) return rc;
+    MIPT_HIP(hipMemcpy(out, scene->d_qout, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 // The camera table of a launch over `n_views` views: one 64-B record per view {look_at column 0, 1, 2, position} in scene->h_cams,
@@ -216,7 +261,7 @@ inline int upload_camera_table(MiptScene *scene, const MiptCamera *cameras, uint
         scene->h_cams[(size_t)v * 4 + 3] = make_float4(c.position.x, c.position.y, c.position.z, 0.0f);
     }
     const size_t bytes = scene->h_cams.size() * sizeof(float4);
-    const int rc = grow_device_buffer((void **)&scene->d_cams, &scene->cams_bytes, bytes);
+    const int rc = scene->d_cams.grow(bytes);
     if (rc) return rc;
     MIPT_HIP(hipMemcpyAsync(scene->d_cams, scene->h_cams.data(), bytes, hipMemcpyHostToDevice, stream));
     return MIPT_OK;

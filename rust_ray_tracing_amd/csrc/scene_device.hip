@@ -478,16 +478,16 @@ int mipt::build_geometry(const MiptTriangle *d_tris, uint32_t n_tris, uint32_t n
 void mipt::attach_geometry(MiptScene *s, SceneGeometry &&g) {
     s->n_tris = g.n_tris;
     s->geom_alloc = g.geom_alloc; s->attr_bytes = g.attr_bytes;
-    s->d_geom = g.d_geom.release(); s->d_tri_attr = g.d_tri_attr.release();
-    s->d_nodes = g.d_nodes.release(); s->d_tri_order = g.d_tri_order.release();
+    s->d_geom = std::move(g.d_geom); s->d_tri_attr = std::move(g.d_tri_attr);
+    s->d_nodes = std::move(g.d_nodes); s->d_tri_order = std::move(g.d_tri_order);
     s->max_leaf = g.max_leaf;
     s->n_nodes = g.n_nodes;
-    s->dev.pairs = (const float4 *)s->d_geom;
-    s->dev.tri_pos = (const float4 *)((const char *)s->d_geom + g.pairs_bytes);
+    s->dev.pairs = (const float4 *)s->d_geom.get();
+    s->dev.tri_pos = (const float4 *)(s->d_geom.get() + g.pairs_bytes);
     s->dev.tri_off_bytes = (uint32_t)g.pairs_bytes;
     s->dev.geom_bytes = (uint32_t)(g.pairs_bytes + g.pos_bytes);
     s->dev.tiny_axes = g.tiny_axes;
-    s->dev.tri_attr = (const float4 *)s->d_tri_attr;
+    s->dev.tri_attr = (const float4 *)s->d_tri_attr.get();
     s->dev.n_pairs = g.n_records_padded; s->dev.n_tris = g.n_tris;
     s->dev.root_a = g.root_a;
     s->dev.root_n = g.root_n;
@@ -552,7 +552,7 @@ static int create_on_device(const MiptSceneDesc *desc, int device_id, bool host_
     {   // materials + the texel pool; the textures go through the same pinned ring, straight from the caller's buffers
         int rc = mipt::upload_material_tables(s.get(), tables);
         for (uint32_t i = 0; i < desc->n_textures && rc == MIPT_OK; i++)
-            rc = up_ring.copy((uint32_t *)s->d_texels + tables.tex_offset[i], desc->textures[i].rgba8, (size_t)desc->textures[i].width * desc->textures[i].height * 4);
+            rc = up_ring.copy(s->d_texels.get() + tables.tex_offset[i], desc->textures[i].rgba8, (size_t)desc->textures[i].width * desc->textures[i].height * 4);
         if (rc == MIPT_OK) rc = up_ring.finish();
         up_ring.shut();
         if (rc) return rc;

@@ -259,8 +259,8 @@ int ensure_plan(MiptScene *s, hipStream_t st) {
     ctl.reset();
     std::vector<uint32_t> off(depth + 1);                               // levels 0 .. depth-1 and the end
     for (uint32_t d = 0; d <= depth; d++) off[d] = h_lv[kMaxLevels + d];
-    s->d_refit_plan = plan.release();
-    s->d_refit_pair = pair_of.release();
+    s->d_refit_plan = std::move(plan);
+    s->d_refit_pair = std::move(pair_of);
     s->refit_level_off = std::move(off);
     sync.dismiss();
     return MIPT_OK;
@@ -366,12 +366,9 @@ void finish_info(const MiptScene *s, MiptUpdateInfo *inf, double t0) {
 
 void mipt::release_geometry(MiptScene *s) {
     (void)hipSetDevice(s->device);
-    void *ptrs[] = {s->d_geom, s->d_tri_attr, s->d_nodes, s->d_tri_order, s->d_touched, s->d_refit_plan, s->d_refit_pair, s->d_bake_inv};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    s->d_geom = s->d_tri_attr = nullptr;
-    s->d_nodes = nullptr; s->d_tri_order = nullptr; s->d_touched = nullptr; s->d_refit_plan = s->d_refit_pair = nullptr;
-    s->d_bake_inv = nullptr;                                              // the caller -> tree map of mipt_bake_gather: the tree it was made for is gone
+    s->d_geom.reset(); s->d_tri_attr.reset(); s->d_nodes.reset(); s->d_tri_order.reset();
+    s->d_touched.reset(); s->d_refit_plan.reset(); s->d_refit_pair.reset();
+    s->d_bake_inv.reset();                                                // the caller -> tree map of mipt_bake_gather: the tree it was made for is gone
     s->refit_level_off.clear();
 }
 
@@ -441,12 +438,12 @@ int mipt::replica_refresh(const MiptScene *src, MiptScene *dst) {
     release_geometry(dst);
     dst->n_tris = src->n_tris; dst->n_nodes = src->n_nodes; dst->max_leaf = src->max_leaf;
     dst->geom_alloc = src->geom_alloc; dst->attr_bytes = src->attr_bytes;
-    dst->d_geom = g.d_geom.release(); dst->d_tri_attr = g.d_tri_attr.release(); dst->d_nodes = g.d_nodes.release(); dst->d_tri_order = g.d_tri_order.release();
+    dst->d_geom = std::move(g.d_geom); dst->d_tri_attr = std::move(g.d_tri_attr); dst->d_nodes = std::move(g.d_nodes); dst->d_tri_order = std::move(g.d_tri_order);
     sync.dismiss();
     mipt::DevScene d = src->dev;                                          // sizes, root, tiny_axes; this replica's own buffers
-    d.pairs = (const float4 *)dst->d_geom;
-    d.tri_pos = (const float4 *)((const char *)dst->d_geom + src->dev.tri_off_bytes);
-    d.tri_attr = (const float4 *)dst->d_tri_attr;
+    d.pairs = (const float4 *)dst->d_geom.get();
+    d.tri_pos = (const float4 *)(dst->d_geom.get() + src->dev.tri_off_bytes);
+    d.tri_attr = (const float4 *)dst->d_tri_attr.get();
     d.mats = dst->dev.mats; d.mats_full = dst->dev.mats_full; d.texels = dst->dev.texels;
     dst->dev = d;
     dst->info.n_tris = src->info.n_tris; dst->info.n_nodes = src->info.n_nodes; dst->info.n_pair_records = src->info.n_pair_records;

@@ -403,8 +403,7 @@ class Scene:  # scene.rs:12-19
 
     def mesh_info(self) -> dict:
         """MiptMeshInfo of the resident mesh: counts, parts, whether transforms are applied, HBM held."""
-        if self._handle is None:
-            raise RuntimeError("scene is not resident on a device")
+        self._resident()
         inf = L.MiptMeshInfo()
         L.check(L.load().mipt_scene_mesh_info(self._handle, C.byref(inf)), "mipt_scene_mesh_info")
         return inf.as_dict()
@@ -412,8 +411,7 @@ class Scene:  # scene.rs:12-19
     def track_motion(self, on: bool = True) -> None:
         """mipt_scene_track_motion: keep the previous generation of the resident mesh from now on (it starts equal to the current
         one), so that ``Renderer.render_motion`` can take it as its source; ``on=False`` frees it."""
-        if self._handle is None:
-            raise RuntimeError("scene is not resident on a device")
+        self._resident()
         L.check(L.load().mipt_scene_track_motion(self._handle, 1 if on else 0), "mipt_scene_track_motion")
         self._tracks_motion = bool(on)
 
@@ -471,6 +469,45 @@ class Scene:  # scene.rs:12-19
     def _is_torch(a) -> bool:
         return type(a).__module__.split(".")[0] == "torch"
 
+    # what the wrappers of the entries that take a list of work items share (queries, radiance queries, baking)
+    def _resident(self, handle=None):
+        h = handle if handle is not None else self._handle
+        if h is None:
+            raise RuntimeError("scene is not resident on a device")
+        return h
+
+    @staticmethod
+    def _stream_arg(stream, device):
+        import torch
+        if stream is None:
+            return torch.cuda.current_stream(device).cuda_stream
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+    @staticmethod
+    def _seeds(seeds, n: int) -> np.ndarray:
+        s = seeds.detach().cpu().numpy() if Scene._is_torch(seeds) else np.asarray(seeds)
+        if s.shape != (n,) or s.dtype.kind not in "iu" or s.dtype.itemsize != 4:
+            raise ValueError(f"seeds: expected {n} 32-bit integers")
+        return np.ascontiguousarray(s).view(np.uint32)
+
+    @staticmethod
+    def _radiance_out(accumulate_into, n: int, device, what: str):
+        """-> (the [n, 3] float32 result tensor of a device entry on ``device``, whether it is the caller's running sum)"""
+        import torch
+        if accumulate_into is None:
+            return torch.empty((n, 3), dtype=torch.float32, device=device), False
+        out = accumulate_into
+        if not Scene._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != device or not out.is_contiguous():
+            raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the {what}' device")
+        return out, True
+
+    @staticmethod
+    def _traced(rc, f, out, st):
+        """the tail of a call that traces: a stack overflow leaves the results written (stats["stack_overflows"] > 0)"""
+        if rc != L.ERR_STACK:
+            L.check(rc, f.__name__)
+        return out, st.as_dict()
+
     @staticmethod
     def _query_rays(rays, t_max):
         """-> ("host", RAY array [n]) or ("device", float32 cuda tensor [n, 8]); ValueError for anything else."""
@@ -516,9 +553,7 @@ class Scene:  # scene.rs:12-19
         """-> (raw result, stats dict).  Host rays: a HIT record array / uint8 array; device rays: an int32 tensor [n, 4] (the MiptHit
         words) / a uint8 tensor, on the rays' device."""
         where, r = self._query_rays(rays, t_max)
-        h = handle if handle is not None else self._handle
-        if h is None:
-            raise RuntimeError("scene is not resident on a device")
+        h = self._resident(handle)
         opt = L.MiptQueryOptions()
         opt.traversal, opt.cull_margin, opt.flags = traversal, cull_margin, (L.FLAG_COUNT if count else 0)
         st = L.MiptStats()
@@ -532,15 +567,9 @@ class Scene:  # scene.rs:12-19
         else:
             import torch
             out = torch.empty((n,), dtype=torch.uint8, device=r.device) if anyhit else torch.empty((n, 4), dtype=torch.int32, device=r.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(r.device).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
             f = lib.mipt_query_occluded_device if anyhit else lib.mipt_query_closest_device
-            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, stream, C.byref(st))
-        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
-            L.check(rc, f.__name__)
-        return out, st.as_dict()
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
+        return self._traced(rc, f, out, st)
 
     def query_closest(self, rays, t_max=None, traversal: int = L.TRAVERSAL_REFERENCE, cull_margin: float = L.CULL_MARGIN_SAFE,
                       count: bool = False, handle=None, stream=None):
@@ -590,16 +619,11 @@ class Scene:  # scene.rs:12-19
         float32 device tensor [n, 3] the call's sums are added to (device rays only; implies ``sum_only``; bring fresh seeds every
         call).  Returns (radiance [n, 3] float32 array or tensor, stats)."""
         where, r = self._query_rays(rays, None)
-        h = handle if handle is not None else self._handle
-        if h is None:
-            raise RuntimeError("scene is not resident on a device")
+        h = self._resident(handle)
         n = len(r)
         given = seeds is not None
         if given:
-            s = seeds.detach().cpu().numpy() if self._is_torch(seeds) else np.asarray(seeds)
-            if s.shape != (n,) or s.dtype.kind not in "iu" or s.dtype.itemsize != 4:
-                raise ValueError(f"seeds: expected {n} 32-bit integers")
-            s = np.ascontiguousarray(s).view(np.uint32)
+            s = self._seeds(seeds, n)
         elif where == "host" or isinstance(rays, (tuple, list)):
             s, given = self.radiance_default_seeds(n), True
         opt = L.MiptRadianceOptions()
@@ -621,40 +645,20 @@ class Scene:  # scene.rs:12-19
                 if r is rays:
                     r = r.clone()
                 r[:, 7] = torch.from_numpy(s.view(np.int32)).to(r.device).view(torch.float32)
-            if accumulate_into is not None:
-                out = accumulate_into
-                if not self._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != r.device or not out.is_contiguous():
-                    raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the rays' device")
-                opt.flags |= L.FLAG_ACCUM
-            else:
-                out = torch.empty((n, 3), dtype=torch.float32, device=r.device)
-            if stream is None:
-                stream = torch.cuda.current_stream(r.device).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
+            out, accum = self._radiance_out(accumulate_into, n, r.device, "rays")
+            opt.flags |= L.FLAG_ACCUM if accum else 0
             f = lib.mipt_query_radiance_device
-            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, stream, C.byref(st))
-        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
-            L.check(rc, f.__name__)
-        return out, st.as_dict()
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
+        return self._traced(rc, f, out, st)
 
     # -- baking (include/mipt.h "baking") ------------------------------------------------------------
-    @staticmethod
-    def _stream_arg(stream, device):
-        import torch
-        if stream is None:
-            return torch.cuda.current_stream(device).cuda_stream
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-
     def bake_texels(self, width: int, height: int, stream=None, device: bool = False, handle=None):
         """The surface point behind every texel of a ``width`` x ``height`` lightmap atlas laid out by the scene's own UVs
         (mipt_bake_texels / _device).  Returns (points, info): SURFACE_POINT records [width * height], texel (x, y) at index
         y * width + x, seed = that index, prim = HIT_NONE where no triangle covers the texel centre; with ``device`` an int32 device
         tensor [width * height, 4] of the same words, made on ``stream`` (a torch stream, a raw hipStream_t or None = torch's current
         stream).  info: covered_texels, degenerate_tris, kernel_ms."""
-        h = handle if handle is not None else self._handle
-        if h is None:
-            raise RuntimeError("scene is not resident on a device")
+        h = self._resident(handle)
         if not (isinstance(width, (int, np.integer)) and isinstance(height, (int, np.integer))) or width < 0 or height < 0 or width >= 1 << 32 or height >= 1 << 32:
             raise ValueError("width, height: expected two non-negative 32-bit integers")
         n = int(width) * int(height)
@@ -711,11 +715,7 @@ class Scene:  # scene.rs:12-19
                                  "of shape (n, 4) or the dict query_closest returns")
             where = "host"
         if seeds is not None:
-            n = len(r)
-            s = seeds.detach().cpu().numpy() if Scene._is_torch(seeds) else np.asarray(seeds)
-            if s.shape != (n,) or s.dtype.kind not in "iu" or s.dtype.itemsize != 4:
-                raise ValueError(f"seeds: expected {n} 32-bit integers")
-            s = np.ascontiguousarray(s).view(np.uint32)
+            s = Scene._seeds(seeds, len(r))
             if where == "host":
                 r = r.copy()
                 r["seed"] = s
@@ -737,9 +737,7 @@ class Scene:  # scene.rs:12-19
         float32 device tensor [n, 3] the call's samples are added to (device points only; implies ``sum_only``).  Returns
         (radiance [n, 3] float32 array or tensor, stats)."""
         where, r = self._bake_points(points, seeds)
-        h = handle if handle is not None else self._handle
-        if h is None:
-            raise RuntimeError("scene is not resident on a device")
+        h = self._resident(handle)
         n = len(r)
         opt = L.MiptBakeOptions()
         opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading = samples, max_ray_depth, traversal, cull_margin, shading
@@ -754,19 +752,11 @@ class Scene:  # scene.rs:12-19
             f = lib.mipt_bake_gather
             rc = f(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out) if n else C.c_void_p(16), C.byref(st))
         else:
-            import torch
-            if accumulate_into is not None:
-                out = accumulate_into
-                if not self._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != r.device or not out.is_contiguous():
-                    raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the points' device")
-                opt.flags |= L.FLAG_ACCUM
-            else:
-                out = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            out, accum = self._radiance_out(accumulate_into, n, r.device, "points")
+            opt.flags |= L.FLAG_ACCUM if accum else 0
             f = lib.mipt_bake_gather_device
             rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
-        if rc != L.ERR_STACK:                     # a stack overflow leaves the results written (stats["stack_overflows"] > 0)
-            L.check(rc, f.__name__)
-        return out, st.as_dict()
+        return self._traced(rc, f, out, st)
 
     def bake_lightmap(self, width: int, height: int, samples: int, device=None, stream=None, **gather_args):
         """``bake_texels`` then ``bake_gather`` with the texel indices as seeds: the mean radiance every covered texel of the atlas
@@ -790,9 +780,7 @@ class Scene:  # scene.rs:12-19
 
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
-        h = handle if handle is not None else self._handle
-        if h is None:
-            raise RuntimeError("scene is not resident on a device")
+        h = self._resident(handle)
         inf = L.MiptSceneInfo()
         L.check(L.load().mipt_scene_info(h, C.byref(inf)), "mipt_scene_info")
         return inf.as_dict()

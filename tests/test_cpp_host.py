@@ -112,7 +112,9 @@ def test_host_code_under_asan_ubsan(built, tmp_path):
 def test_owned_guard_under_asan_ubsan(tmp_path):
     """mipt::Owned (mipt_internal.h), the owner of every device buffer, stream and event a libmipt function holds for the length
     of a call, over a counting release function: one release per handle, none for an empty or moved-from owner, reverse
-    declaration order, also when an exception leaves the scope (tests/cpp/owned_guard.cpp)."""
+    declaration order, also when an exception leaves the scope; and mipt::Grown, the grow-on-demand owner of a scene's workspace,
+    over a counting allocator: grow from empty, a request that fits keeps the block, a larger one frees it once, a failed
+    allocation leaves the owner empty, one release at scope end and none after a move (tests/cpp/owned_guard.cpp)."""
     exe = str(tmp_path / "owned_guard")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "owned_guard.cpp"), "-o", exe])

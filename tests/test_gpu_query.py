@@ -318,6 +318,48 @@ def test_renders_and_queries_share_one_spill_buffer(rrt):
         assert counters(got_st) == counters(want_st), (i, got_st, want_st)
 
 
+def test_host_entries_share_their_staging(rrt, orc):
+    """The host entries of the queries, the radiance queries and the bake stage their items and results in one pair of scene-owned
+    buffers, which grow on demand, are reused while they are too large and change their element size from call to call (a byte, a
+    16-byte hit or point, a 12-byte radiance; the texels stage no input at all).  Every call of the sequence on one handle returns,
+    bit for bit, what the same call returns on a handle of the same scene that has seen no other call."""
+    _, pool, _ = _case(rrt, orc, "cornell")
+
+    def words(a):
+        return np.ascontiguousarray(a).view(np.uint8)
+
+    def closest(n):
+        return lambda sc, _: words(sc._query(False, np.resize(pool, n), None, REF, 0.0, False, None, None)[0])
+
+    def occluded(n):
+        return lambda sc, _: words(sc.query_occluded(np.resize(pool, n))[0])
+
+    def radiance(n):
+        return lambda sc, _: words(sc.query_radiance(np.resize(pool, n), samples=2, max_ray_depth=4)[0])
+
+    def texels(sc, _):
+        return sc.bake_texels(8, 8)[0]
+
+    def gather(n):
+        return lambda sc, points: words(sc.bake_gather(points[:n])[0])
+
+    calls = [occluded(1), closest(65), radiance(3), texels, gather(64), closest(1000), occluded(1000), radiance(257), gather(5)]
+    shared = _host_scene(rrt, "cornell")
+    shared.upload(0)
+    points = None
+    for i, call in enumerate(calls):
+        fresh = _host_scene(rrt, "cornell")
+        fresh.upload(0)
+        want, got = call(fresh, points), call(shared, points)
+        fresh.release()
+        assert want.dtype == got.dtype and want.shape == got.shape and want.size > 0, i
+        assert np.array_equal(words(got), words(want)), i
+        if call is texels:
+            points = got
+            assert len(points) == 64
+    shared.release()
+
+
 def test_prim_through_tri_order_on_a_batch_larger_than_the_launch(rrt, orc):
     """A device-built scene: the hit's triangle goes through q.tri_order when the refill writes it, after neighbours were refilled"""
     sc, _, hits, _, _, classes = _pool_model(rrt, orc, "helmet-device", ARMS[2], False)

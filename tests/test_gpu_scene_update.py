@@ -549,6 +549,47 @@ def test_failed_calls_give_their_memory_back(rrt):
     assert lib.mipt_scene_update_triangles(h, L.ptr(good), n, 0, None) == 0, lib.mipt_last_error()   # and the scene still takes an update
 
 
+def test_destroy_gives_the_workspace_back(rrt):
+    """mipt_scene_destroy frees the workspace a scene has grown, not only its geometry: a scene is created, renders 512 x 512 with
+    RGBA8 (the frame buffers), answers 2^18 host rays (the staging pair), bakes 512 x 512 texels and gathers at their 2^18 points (the
+    bake buffers, the triangle map) and is destroyed.  After eight such cycles free device memory has fallen by less than the
+    smallest of those buffers, the 1 MiB RGBA8 frame: one buffer left behind per destroy would lose eight times its size."""
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    from rust_ray_tracing_amd import synth
+    tris, mats, texs, cam = synth.make_scene("cornell")
+    n = 1 << 18
+    rng = np.random.default_rng(11)
+    rays = np.zeros(n, dtype=L.RAY)
+    rays["origin"], rays["t_max"] = np.asarray(cam[0], dtype=np.float32), 1e30
+    rays["direction"] = rng.standard_normal((n, 3)).astype(np.float32)
+    r = rrt.Renderer.new(rrt.RendererOptions(samples=1, max_ray_depth=3, output_image_dimensions=(512, 512), output_image_path="/dev/null"))
+
+    def cycle():
+        sc = rrt.Scene.from_arrays(tris, mats, texs)
+        sc.set_camera(rrt.Camera(position=cam[0], pitch=cam[1], yaw=cam[2]))
+        sc.upload(0)
+        _, rgba, _ = r.render_buffers(sc, want_rgba8=True)
+        assert rgba.size == 512 * 512 * 4
+        hits, _ = sc.query_closest(rays)
+        assert hits["hit"].any()
+        points, info = sc.bake_texels(512, 512)
+        assert len(points) == n
+        rad, _ = sc.bake_gather(points, samples=1)
+        assert rad.shape == (n, 3)
+        sc.release()
+
+    cycle()                                                            # what a process pays once (kernels, streams) is paid
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    for _ in range(8):
+        cycle()
+    torch.cuda.synchronize()
+    lost = free0 - torch.cuda.mem_get_info(0)[0]
+    print(f"{lost / 2**20:.2f} MiB less free after 8 create ... destroy cycles")
+    assert lost < 1 << 20, f"{lost / 2**20:.2f} MiB lost after 8 create ... destroy cycles (the RGBA8 frame: 1 MiB)"
+
+
 @pytest.mark.parametrize("ranks", [2, 3])
 @pytest.mark.parametrize("from_triangles", [True, False])
 def test_multi_replicas_follow_the_root(rrt, ranks, from_triangles):
