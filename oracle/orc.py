@@ -107,6 +107,10 @@ def load() -> C.CDLL:
     lib.orc_wgsl_fresnel_step.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     lib.orc_trace_ray_wgsl.argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(OrcTexture), u32, C.POINTER(f32 * 3), C.POINTER(f32 * 3),
                                        u32, C.POINTER(u32), C.c_int, C.c_int, C.POINTER(f32 * 3), C.POINTER(u64 * 5)]
+    for name in ("orc_trace_ray_m", "orc_trace_ray_wgsl_m"):                       # the one-ray entries with a cull margin and counters
+        getattr(lib, name).argtypes = [vp, u32, vp, u32, vp, u32, C.POINTER(OrcTexture), u32, C.POINTER(f32 * 3), C.POINTER(f32 * 3),
+                                       u32, C.POINTER(u32), C.c_int, f32, C.c_int, C.POINTER(f32 * 3), C.POINTER(u64 * 5)]
+        getattr(lib, name).restype = None
     for name in ("orc_wgsl_sample_texture", "orc_wgsl_onb", "orc_wgsl_frame", "orc_wgsl_vndf", "orc_wgsl_cosine_hemisphere",
                  "orc_wgsl_cosine_from", "orc_wgsl_fresnel_step", "orc_trace_ray_wgsl"):
         getattr(lib, name).restype = None

@@ -617,17 +617,31 @@ void orc_intersect_tri(const float o[3], const float d[3], const OrcTriangle *t,
     out[5] = h.normal.x; out[6] = h.normal.y; out[7] = h.normal.z; out[8] = h.uvx; out[9] = h.uvy;
     out[10] = h.point.x; out[11] = h.point.y; out[12] = h.point.z;
 }
+static void counters_of(const Ctx *cx, uint64_t counters_out[5]) {  /* rays, inner_steps, tri_tests, hits, texel_fetches */
+    if (!counters_out) return;
+    counters_out[0] = cx->s.rays; counters_out[1] = cx->s.inner_steps; counters_out[2] = cx->s.tri_tests;
+    counters_out[3] = cx->s.hits; counters_out[4] = cx->s.texel_fetches;
+}
+/* trace on one ray, culled (if cull) at best * (1 + cull_margin) as orc_render culls; counters_out (may be NULL) as below */
+void orc_trace_ray_m(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                     const OrcMaterial *materials, uint32_t n_materials,
+                     const OrcTexture *textures, uint32_t n_textures,
+                     const float o[3], const float d[3], uint32_t max_depth,
+                     uint32_t *rng, int cull, float cull_margin, int libm, float out[3], uint64_t counters_out[5]) {
+    SceneView sc = {tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures};
+    Ctx cx; memset(&cx, 0, sizeof cx);
+    cx.stack_cap = 64; cx.cull = cull; cx.cull_scale = 1.0f + cull_margin; cx.libm = libm;
+    Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
+    v3 c = trace(&r, max_depth, &sc, rng, &cx);
+    out[0] = c.x; out[1] = c.y; out[2] = c.z;
+    counters_of(&cx, counters_out);
+}
 void orc_trace_ray(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
                    const OrcMaterial *materials, uint32_t n_materials,
                    const OrcTexture *textures, uint32_t n_textures,
                    const float o[3], const float d[3], uint32_t max_depth,
                    uint32_t *rng, int cull, int libm, float out[3]) {
-    SceneView sc = {tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures};
-    Ctx cx; memset(&cx, 0, sizeof cx);
-    cx.stack_cap = 64; cx.cull = cull; cx.cull_scale = 1.0f; cx.libm = libm;
-    Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
-    v3 c = trace(&r, max_depth, &sc, rng, &cx);
-    out[0] = c.x; out[1] = c.y; out[2] = c.z;
+    orc_trace_ray_m(tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures, o, d, max_depth, rng, cull, 0.0f, libm, out, NULL);
 }
 
 /* Element-wise entry points for the pieces of the wgpu material model (tests/test_wgsl_kat.py, tests/test_gpu_wgsl.py). */
@@ -683,22 +697,28 @@ void orc_wgsl_fresnel_step(const float *dir, const float *normal, const float *i
         o[9] = f.transmitted_dir.x; o[10] = f.transmitted_dir.y; o[11] = f.transmitted_dir.z; o[12] = f.k;
     }
 }
-/* trace_wgsl on one ray; counters_out (may be NULL) = rays, inner_steps, tri_tests, hits, texel_fetches */
+/* trace_wgsl on one ray, culled (if cull) at best * (1 + cull_margin); counters_out (may be NULL) = rays, inner_steps, tri_tests,
+ * hits, texel_fetches */
+void orc_trace_ray_wgsl_m(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                          const OrcMaterial *materials, uint32_t n_materials,
+                          const OrcTexture *textures, uint32_t n_textures,
+                          const float o[3], const float d[3], uint32_t max_depth,
+                          uint32_t *rng, int cull, float cull_margin, int libm, float out[3], uint64_t counters_out[5]) {
+    SceneView sc = {tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures};
+    Ctx cx; memset(&cx, 0, sizeof cx);
+    cx.stack_cap = 64; cx.cull = cull; cx.cull_scale = 1.0f + cull_margin; cx.libm = libm;
+    Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
+    v3 c = trace_wgsl(&r, max_depth, &sc, rng, &cx);
+    out[0] = c.x; out[1] = c.y; out[2] = c.z;
+    counters_of(&cx, counters_out);
+}
 void orc_trace_ray_wgsl(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
                         const OrcMaterial *materials, uint32_t n_materials,
                         const OrcTexture *textures, uint32_t n_textures,
                         const float o[3], const float d[3], uint32_t max_depth,
                         uint32_t *rng, int cull, int libm, float out[3], uint64_t counters_out[5]) {
-    SceneView sc = {tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures};
-    Ctx cx; memset(&cx, 0, sizeof cx);
-    cx.stack_cap = 64; cx.cull = cull; cx.cull_scale = 1.0f; cx.libm = libm;
-    Ray r = {V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])};
-    v3 c = trace_wgsl(&r, max_depth, &sc, rng, &cx);
-    out[0] = c.x; out[1] = c.y; out[2] = c.z;
-    if (counters_out) {
-        counters_out[0] = cx.s.rays; counters_out[1] = cx.s.inner_steps; counters_out[2] = cx.s.tri_tests;
-        counters_out[3] = cx.s.hits; counters_out[4] = cx.s.texel_fetches;
-    }
+    orc_trace_ray_wgsl_m(tris, n_tris, nodes, n_nodes, materials, n_materials, textures, n_textures, o, d, max_depth, rng, cull, 0.0f, libm,
+                         out, counters_out);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -166,6 +166,13 @@ void     orc_trace_ray(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *
                        const OrcTexture *textures, uint32_t n_textures,
                        const float o[3], const float d[3], uint32_t max_depth,
                        uint32_t *rng, int cull, int libm, float out[3]);
+/* the same, culled (if cull) at best * (1 + cull_margin) as orc_render culls; counters_out (may be NULL) as orc_trace_ray_wgsl's.
+ * orc_trace_ray is this at margin 0 without counters. */
+void     orc_trace_ray_m(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                         const OrcMaterial *materials, uint32_t n_materials,
+                         const OrcTexture *textures, uint32_t n_textures,
+                         const float o[3], const float d[3], uint32_t max_depth,
+                         uint32_t *rng, int cull, float cull_margin, int libm, float out[3], uint64_t counters_out[5]);
 
 /* ---- the wgpu material model (rt_compute.wgsl, shading mode 1) piece by piece, element-wise over n inputs ---- */
 /* linear / repeat sampler (:500-502): out_rgba 4 floats per element; out_idx (may be NULL) the 4 texel indices read: (i0,j0) (i1,j0) (i0,j1) (i1,j1) */
@@ -183,6 +190,12 @@ void     orc_trace_ray_wgsl(const OrcTriangle *tris, uint32_t n_tris, const OrcN
                             const OrcTexture *textures, uint32_t n_textures,
                             const float o[3], const float d[3], uint32_t max_depth,
                             uint32_t *rng, int cull, int libm, float out[3], uint64_t counters_out[5]);
+/* the same with a cull margin; orc_trace_ray_wgsl is this at margin 0 */
+void     orc_trace_ray_wgsl_m(const OrcTriangle *tris, uint32_t n_tris, const OrcNode *nodes, uint32_t n_nodes,
+                              const OrcMaterial *materials, uint32_t n_materials,
+                              const OrcTexture *textures, uint32_t n_textures,
+                              const float o[3], const float d[3], uint32_t max_depth,
+                              uint32_t *rng, int cull, float cull_margin, int libm, float out[3], uint64_t counters_out[5]);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """GPU: mipt_bake_texels / mipt_bake_gather and their _device forms (csrc/bake.hip, csrc/mipt_bake.cpp) against the models of
 tests/tools/bake_model.py: the texel pass as a numpy f32 brute force over all triangles, the gather as a Python loop over the oracle's
 one-ray entries.  Every comparison is on the bytes.  Scenes are built on the device from a shuffled triangle array, so that the
-tree's order is not the caller's; the culled arm of the gather runs at margin 0, the rule the one-ray oracle entries restate.
+tree's order is not the caller's; the culled arm of the gather runs at margin 0 here and at MIPT_CULL_MARGIN_SAFE, with counters and
+hard points, in tests/test_gpu_bake_hard.py.
 The last part takes the texel kernels where no small layout does: past the lanes of their grids, past the
 list of cover_huge_kernel, to atlas sides of 2^19, onto slivers the box clause decides and onto a scene without an order array;
 there the model is B.texels_indexed, which tests/test_bake_model.py holds to the brute force, and each test asserts on the model
@@ -314,14 +315,14 @@ def _dev(points):
 
 
 def _gather(rrt, sc, points, samples, depth, shading=0, traversal=REF, flags=0, device=False, first_sample=0, stride=None, handle=None, lib=None,
-            d_out=None, extra=4):
+            d_out=None, extra=4, cull_margin=0.0):
     """One call of the C entry with a sentinel behind the output -> (rc, radiance [n, 3] f32, stats dict); the sentinel is asserted"""
     import torch
     from rust_ray_tracing_amd import _lib as L
     lib = lib or rrt.load()
     n = len(points)
     opt = L.MiptBakeOptions()
-    opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading, opt.flags = samples, depth, traversal, 0.0, shading, flags
+    opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading, opt.flags = samples, depth, traversal, cull_margin, shading, flags
     opt.first_sample, opt.sample_stride = first_sample, (n if stride is None else stride)
     st = L.MiptStats()
     h = handle if handle is not None else sc._handle

@@ -1,8 +1,8 @@
 """GPU: mipt_query_radiance / mipt_query_radiance_device (pt_trace_rays_kernel, csrc/pt_kernel.hip) against the model of
 tests/tools/radiance_model.py: a Python loop over the oracle's one-ray entries with one rng word carried across a ray's samples and
 the f32 sum and divide in numpy.  Every comparison is bit for bit on the u32 words.  The distinct rays of a case stay few enough for
-the model; batches larger than one launch holds in flight repeat a modelled pool.  The culled arm runs at margin 0, the rule the
-one-ray oracle entries restate."""
+the model; batches larger than one launch holds in flight repeat a modelled pool.  The culled arm here runs at margin 0;
+tests/test_gpu_radiance_hard.py runs the margin the product uses (MIPT_CULL_MARGIN_SAFE), the counters of both shadings and hard rays."""
 import ctypes as C
 import os
 import sys
@@ -71,14 +71,15 @@ def _dev(rays):
     return torch.from_numpy(np.ascontiguousarray(rays).view(np.int32).reshape(-1, 8).copy()).cuda().view(torch.float32)
 
 
-def _call(rrt, sc, rays, samples, depth, shading=0, traversal=REF, flags=0, device=False, handle=None, lib=None, d_rays=None, extra=4):
+def _call(rrt, sc, rays, samples, depth, shading=0, traversal=REF, flags=0, device=False, handle=None, lib=None, d_rays=None, extra=4,
+          cull_margin=0.0):
     """One call of the C entry with a sentinel behind the output -> (rc, radiance [n, 3] f32, stats dict); the sentinel is asserted"""
     import torch
     from rust_ray_tracing_amd import _lib as L
     lib = lib or rrt.load()
     n = len(rays)
     opt = L.MiptRadianceOptions()
-    opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading, opt.flags = samples, depth, traversal, 0.0, shading, flags
+    opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading, opt.flags = samples, depth, traversal, cull_margin, shading, flags
     st = L.MiptStats()
     h = handle if handle is not None else sc._handle
     if device:

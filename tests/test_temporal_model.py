@@ -222,7 +222,7 @@ class _Planes:
     """host planes for one call; two 16-byte aligned histories"""
 
     def __init__(self):
-        self.a = {k: np.zeros(N * n + 4, dtype=np.float32) for k, n in WORDS.items()}
+        self.a = {k: np.zeros(N * n + 4 + 3 * N, dtype=np.float32) for k, n in WORDS.items()}   # + 3 N words: a case that moves a pointer to a plane's end stays inside that plane's own allocation, whatever lies behind it on the heap
         for k in ("history_in", "history_out"):
             raw = np.zeros(HIST_BYTES // 4 + 8, dtype=np.float32)
             off = (-raw.ctypes.data % 16) // 4

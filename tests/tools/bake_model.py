@@ -4,7 +4,7 @@ tests/test_cpp_host_bake.py.
 texels(): mipt_bake_texels in numpy f32 -- a brute force over ALL triangles of the caller's array per texel, every operator one
 rounded f32 operation in the header's order.  texels_indexed(): the same definition stated a second time, over the (triangle,
 texel) pairs that pass the box clause, for inputs of 10^6 triangles.  gather(): mipt_bake_gather as a Python loop over the oracle's orc_rand_in_unit_sphere
-and orc_trace_ray / orc_trace_ray_wgsl; the interpolation and `normalized` in numpy f32, the seed arithmetic in Python integers
+and orc_trace_ray_m / orc_trace_ray_wgsl_m (the one-ray entries with a cull margin and counters); the interpolation and `normalized` in numpy f32, the seed arithmetic in Python integers
 (checked against orc_pixel_seed).  Nothing of the library under test is used here."""
 import ctypes as C
 
@@ -200,7 +200,13 @@ def surface(tris, point):
 
 
 class Gather:
-    """The scene as the oracle takes it (sc.tris and sc.bvh_nodes in the TREE's order) and the caller's triangle array, kept alive"""
+    """The scene as the oracle takes it (sc.tris and sc.bvh_nodes in the TREE's order) and the caller's triangle array, kept alive.
+
+    Counters.  Every path of a real point is one call of the one-ray entry, counted as that entry counts.  A path of a MIPT_HIT_NONE
+    point is "a ray that misses" (include/mipt.h): bake_rays_kernel writes it as a placeholder ray -- origin 0, direction (NaN, NaN,
+    NaN), seed 1 -- and the trace loop runs it like any other.  Every slab quotient of it is a NaN and every triangle test's t is one,
+    so it counts one ray, the one step at the root (one inner step, or the root's triangle tests where the root is a leaf), no hit and
+    no texel fetch, whatever the depth, the shading or the traversal.  The model states this by handing that very ray to the oracle."""
 
     def __init__(self, orc, sc, caller_tris):
         self.orc, self.lib = orc, orc.load()
@@ -211,19 +217,27 @@ class Gather:
         self.caller = np.ascontiguousarray(caller_tris)
         assert len(self.caller) == len(self.tris)
 
-    def run(self, points, samples, depth, shading=0, cull=0, first_sample=0, stride=None):
+    def run(self, points, samples, depth, shading=0, cull=0, first_sample=0, stride=None, margin=0.0):
         """-> dict: "sum" [n, 3] f32 (the samples added in order from +0), "mean" [n, 3] f32 (sum / f32(samples); 0 for a point
-        without a surface, like the sum) and "first_hit" [n, samples] bool (the first scatter ray hit something; False for no point)"""
+        without a surface, like the sum), "first_hit" [n, samples] bool (the first scatter ray hit something; False for no point) and
+        "counters" [n, 5] int64 in the order of radiance_model.COUNTERS.  margin: the culled traversal's cull_margin."""
         lib, n = self.lib, len(points)
         stride = n if stride is None else stride
         args = (self.tris.ctypes.data, self.tris.nbytes // 112, self.nodes.ctypes.data, self.nodes.nbytes // 32, self.mats.ctypes.data,
                 self.mats.nbytes // 80, self.tex_array, len(self.texs))
         total = np.zeros((n, 3), dtype=np.float32)
         first_hit = np.zeros((n, samples), dtype=bool)
+        counters = np.zeros((n, 5), dtype=np.int64)
         out, rs, cnt = _F3(), _F3(), (C.c_uint64 * 5)()
+        entry = lib.orc_trace_ray_m if shading == 0 else lib.orc_trace_ray_wgsl_m
+        nan = float("nan")
         with np.errstate(all="ignore"):
             for i in range(n):
                 if int(points["prim"][i]) == NONE:
+                    o, d, st = _F3(0.0, 0.0, 0.0), _F3(nan, nan, nan), C.c_uint32(1)             # the placeholder ray (class docstring)
+                    entry(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, C.c_float(margin), self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
+                    assert cnt[0] == 1 and cnt[3] == 0 and cnt[4] == 0 and cnt[1] + cnt[2] > 0
+                    counters[i] = samples * np.array(list(cnt), dtype=np.int64)
                     continue
                 P, N = surface(self.caller, points[i])
                 acc = np.zeros(3, dtype=np.float32)
@@ -239,16 +253,14 @@ class Gather:
                     probe = C.c_uint32(st.value)                                                 # the first segment alone: did it hit?
                     lib.orc_trace_ray_wgsl(*args, C.byref(o), C.byref(d), 1, C.byref(probe), 0, self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
                     first_hit[i, s] = cnt[3] > 0
-                    if shading == 0:
-                        lib.orc_trace_ray(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, self.orc.LIBM_GLIBC235, C.byref(out))
-                    else:
-                        lib.orc_trace_ray_wgsl(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
+                    entry(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, C.c_float(margin), self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
+                    counters[i] += np.array(list(cnt), dtype=np.int64)
                     acc = acc + np.array(list(out), dtype=np.float32)                            # f32 + f32, rounded once
                 total[i] = acc
         none = points["prim"] == NONE
         mean = total / F(samples)
         mean[none] = 0
-        return dict(sum=total, mean=mean, first_hit=first_hit)
+        return dict(sum=total, mean=mean, first_hit=first_hit, counters=counters)
 
 
 def conditions(model_out, points):

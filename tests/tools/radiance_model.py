@@ -1,7 +1,7 @@
 """The model of mipt_query_radiance (include/mipt.h "radiance queries") for tests/test_gpu_radiance.py and
-tests/test_cpp_host_radiance.py: a Python loop over the oracle's one-ray entries -- orc_trace_ray (shading 0) and orc_trace_ray_wgsl
-(shading 1) -- with one rng word carried across a ray's samples and the f32 sum and divide done in numpy.  Nothing of the library
-under test is used here."""
+tests/test_cpp_host_radiance.py: a Python loop over the oracle's one-ray entries -- orc_trace_ray_m (shading 0) and
+orc_trace_ray_wgsl_m (shading 1), which take the cull margin and return the counters -- with one rng word carried across a ray's
+samples and the f32 sum and divide done in numpy.  Nothing of the library under test is used here."""
 import ctypes as C
 
 import numpy as np
@@ -51,9 +51,10 @@ class Model:
         self.texs = [np.ascontiguousarray(t) for t in sc.textures]
         self.tex_array = orc._tex_array(self.texs)
 
-    def trace(self, rays, samples, depth, shading=0, cull=0):
+    def trace(self, rays, samples, depth, shading=0, cull=0, margin=0.0):
         """-> dict: "sum" [n, 3] f32 (the samples added in order from +0), "mean" [n, 3] f32 (sum / f32(samples)), "state" [n] u32
-        (the stream after the last sample) and, for shading 1, "counters" [n, 5] int64 in the order of COUNTERS"""
+        (the stream after the last sample) and "counters" [n, 5] int64 in the order of COUNTERS.  margin: the culled traversal's
+        cull_margin (MiptRadianceOptions), ignored by the reference traversal."""
         lib, n = self.lib, len(rays)
         args = (self.tris.ctypes.data, self.tris.nbytes // 112, self.nodes.ctypes.data, self.nodes.nbytes // 32, self.mats.ctypes.data,
                 self.mats.nbytes // 80, self.tex_array, len(self.texs))
@@ -61,22 +62,17 @@ class Model:
         state = np.zeros(n, dtype=np.uint32)
         counters = np.zeros((n, 5), dtype=np.int64)
         out, cnt = _F3(), (C.c_uint64 * 5)()
+        entry = lib.orc_trace_ray_m if shading == 0 else lib.orc_trace_ray_wgsl_m
         for i in range(n):
             o, d = _F3(*[float(x) for x in rays["origin"][i]]), _F3(*[float(x) for x in rays["direction"][i]])
             st = C.c_uint32(int(rays["reserved"][i]))
             acc = np.zeros(3, dtype=np.float32)
             for _ in range(samples):
-                if shading == 0:
-                    lib.orc_trace_ray(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, self.orc.LIBM_GLIBC235, C.byref(out))
-                else:
-                    lib.orc_trace_ray_wgsl(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
-                    counters[i] += np.array(list(cnt), dtype=np.int64)
+                entry(*args, C.byref(o), C.byref(d), depth, C.byref(st), cull, C.c_float(margin), self.orc.LIBM_GLIBC235, C.byref(out), C.byref(cnt))
+                counters[i] += np.array(list(cnt), dtype=np.int64)
                 acc = acc + np.array(list(out), dtype=np.float32)                   # f32 + f32, rounded once
             total[i], state[i] = acc, st.value
-        res = dict(sum=total, mean=total / np.float32(samples), state=state)
-        if shading == 1:
-            res["counters"] = counters
-        return res
+        return dict(sum=total, mean=total / np.float32(samples), state=state, counters=counters)
 
     def first_hits(self, rays):
         """bool [n]: the ray's first segment hits a triangle (un-culled traversal; the wgsl entry counts it, whatever the seed)"""
