@@ -453,6 +453,125 @@ MIPT_API int mipt_bake_gather(MiptScene *scene, const MiptSurfacePoint *points, 
 MIPT_API int mipt_bake_gather_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeOptions *opt,
                                      float *d_radiance /* n*3 */, void *hip_stream, MiptStats *stats);
 
+/* mipt_bake_surface: where a surface point lies and which way its surface faces -- the guides of mipt_lightmap_filter.  For point i
+ * the values are the P and N of mipt_bake_gather above, formed by the same rounded operations:
+ *     position[i] = P = (v0 + e1 * u) + e2 * v
+ *     normal[i]   = N = (n0 * ((1 - u) - v) + n1 * u) + n2 * v, reversed iff bit 31 of prim is clear
+ * With MIPT_BAKE_SURFACE_UNIT_NORMALS, normal[i] = normalized(N) instead: N / sqrt((N.x*N.x + N.y*N.y) + N.z*N.z), one division per
+ * component (vec3.rs:93-109).  A zero N then gives NaNs, and they are left as they are.  A MIPT_HIT_NONE point writes +0 to all six
+ * words.  Either output may be NULL = not wanted (never written), not both.  Every point's values depend on the point alone.
+ * Options: NULL = all zero; flags: MIPT_BAKE_SURFACE_UNIT_NORMALS only; reserved words 0.
+ * Errors, in gather's order: a null scene or points, or both outputs NULL; n >= 2^31; flags; reserved words; for the device entry
+ * d_points not 16-byte aligned, an output not 4-byte aligned; (n == 0 is MIPT_OK here, without a launch); for the device entry an
+ * output that overlaps the points or the other output, a pointer that is not memory of the scene's device; a prim whose triangle is
+ * >= the scene's count: MIPT_ERR_INVALID_ARG naming the first such index, as mipt_bake_gather finds it, with both outputs untouched.
+ * The map from the caller's triangle index to the device record is the gather's, made by whichever call needs it first and dropped
+ * whenever the tree changes.  Both entries block until done, see the geometry of the last successful update and work on a mesh scene
+ * and on a replica handle. */
+#define MIPT_BAKE_SURFACE_UNIT_NORMALS 1u
+typedef struct { uint32_t flags; uint32_t reserved[7]; } MiptBakeSurfaceOptions;   /* 32 B */
+MIPT_API int mipt_bake_surface(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, const MiptBakeSurfaceOptions *opt,
+                               float *position /* n*3 or NULL */, float *normal /* n*3 or NULL */);
+MIPT_API int mipt_bake_surface_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeSurfaceOptions *opt,
+                                      float *d_position /* n*3 or NULL */, float *d_normal /* n*3 or NULL */, void *hip_stream);
+
+/* ---- lightmap finishing: an edge-avoiding filter over the covered texels of an atlas, and dilation into its gutters -------------------
+ * What turns the atlas mipt_bake_texels + mipt_bake_gather leave -- a noisy mean per covered texel, zeros elsewhere -- into one a
+ * renderer can sample (csrc/lightmap.hip).  Scene-free, like the denoiser: planes in, a plane out.  The reference has no baker:
+ * both operators are defined HERE, and the kernels and tests/tools/lightmap_model.py obey them bit for bit.  Every operator is one
+ * rounded f32 operation, nothing is fused, and the operations run in the order written.  Texel (x, y) of a width x height atlas is
+ * index y * width + x of every plane.  A texel is COVERED iff prim of its record in `points` (the records mipt_bake_texels wrote)
+ * is not MIPT_HIT_NONE; nothing else of the record is read.  Limit, as for mipt_bake_texels: width * height < 2^31, and here both
+ * sides greater than 0.
+ *
+ * mipt_lightmap_filter: the a-trous filter of the denoiser section in atlas space.  Planes:
+ *   radiance  3 f32 / texel, required
+ *   points    16 B / texel, required (16-byte aligned for the device entry)
+ *   position  3 f32 / texel, optional: the P of mipt_bake_surface
+ *   normal    3 f32 / texel, optional; used as given, not normalised
+ *   out       3 f32 / texel, required; may be radiance
+ * A NULL guide means its terms are left out: not computed, not fetched.  There is no demodulation: the gather's value carries no
+ * albedo.  c0 = radiance.
+ * Iteration i = 0 ... iterations - 1 (1 <= iterations <= 8) has step s = 1 << i, reads the previous iteration's colours c and writes
+ * new ones.  An UNCOVERED texel keeps its words: its `out` is its `radiance` word for word.  For a covered texel p = (x, y):
+ *   - taps q = (x + s*dx, y + s*dy), dy = -2 ... 2 the outer loop and dx = -2 ... 2 the inner one.  A tap outside [0,W) x [0,H) and
+ *     an UNCOVERED tap are skipped -- neither weighted nor added: what an uncovered texel holds reaches no covered one.
+ *   - h = [1/16, 1/4, 3/8, 1/4, 1/16]; the tap's kernel weight h[dy+2] * h[dx+2] is an exact constant.
+ *   - dc = ((dr*dr) + (dg*dg)) + (db*db) with dr = c_p.r - c_q.r and so on; dn likewise from the normals N_p - N_q.
+ *   - D = P_q - P_p (three subtractions); dd = ((D.x*D.x) + (D.y*D.y)) + (D.z*D.z);
+ *     l = ((N_p.x*D.x) + (N_p.y*D.y)) + (N_p.z*D.z); dl = l * l: the tap's squared distance from the centre's tangent plane (for a
+ *     unit N_p), which lets the filter run along a flat chart and stops it at a chart that lies on another plane.
+ *   - e = (((dc * kc_i) + (dn * kn)) + (dl * kl)) + (dd * kd_i); dn needs `normal`, dd needs `position`, dl needs both; an absent
+ *     term is left out of the sum, the others keep their order.  The constants are formed on the host in f32:
+ *     kn = 1.0f / (sigma_normal * sigma_normal), kl likewise from sigma_plane, kc_i = 1.0f / (sc * sc) with sc = sigma_color * 2^-i,
+ *     kd_i = 1.0f / (sd * sd) with sd = sigma_distance * 2^i: the world distance a tap may lie away grows with the step, as the taps do.
+ *   - e = e < 128.0f ? e : 128.0f (a NaN gives 128).
+ *   - w = (h[dy+2] * h[dx+2]) * expf(-e), expf as in the denoiser section.  The centre tap has weight 9/64 without evaluation.
+ *   - sum_ch = sum_ch + (w * c_q.ch) and wsum = wsum + w, both starting at +0.
+ *   - the new colour is, per channel, wsum > 0 ? sum_ch / wsum : c_p.ch.
+ * The NaN rule of the query section applies.  What the operators cannot do: two charts that are neighbours on the surface but not in
+ * the atlas do not see each other (that takes a world-space neighbour search), and two charts that ARE neighbours in the atlas are
+ * kept apart only by the guides: without position and normal, light leaks across a gutter narrower than the taps reach.
+ * Errors, before any device work and in this order: a null opt, buffers, radiance, points or out; a zero side; width * height >= 2^31;
+ * iterations outside 1 ... 8; non-zero flags or reserved fields; sigma_color, then sigma_normal (with normal), sigma_plane (with
+ * both guides), sigma_distance (with position): each finite and greater than 0 with a finite k > 0, kc_i and kd_i for every i (a
+ * sigma of an absent term is ignored); planes that overlap (out == radiance alone is allowed); for the device entry the
+ * denoiser's list: workspace NULL, too small, misaligned, overlapped; a misaligned plane; memory not of radiance's device. */
+typedef struct {
+    uint32_t width, height;
+    uint32_t iterations;          /* 1 ... 8 */
+    float    sigma_color, sigma_normal, sigma_plane, sigma_distance;
+    uint32_t flags;               /* must be 0 */
+    uint32_t reserved[8];         /* must be 0 */
+} MiptLightmapFilterOptions;      /* 64 B */
+typedef struct {
+    const float *radiance;
+    const MiptSurfacePoint *points;
+    const float *position, *normal;               /* NULL = absent */
+    float       *out;                             /* may be radiance */
+    void        *reserved[3];                     /* must be NULL */
+} MiptLightmapFilterBuffers;      /* 64 B */
+/* Bytes of workspace mipt_lightmap_filter_device needs: four float4 planes, 64 B per texel.  0 = an invalid size. */
+MIPT_API uint64_t mipt_lightmap_filter_workspace_bytes(uint32_t width, uint32_t height);
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_lightmap_filter(const MiptLightmapFilterOptions *opt, const MiptLightmapFilterBuffers *host, int device_id);
+/* DEVICE buffers of one device on `hip_stream`; stream-ordered, allocates nothing, writes `out` and the first
+ * mipt_lightmap_filter_workspace_bytes() bytes of the caller's 16-byte aligned workspace and nothing else (as mipt_denoise_device). */
+MIPT_API int mipt_lightmap_filter_device(const MiptLightmapFilterOptions *opt, const MiptLightmapFilterBuffers *device, void *d_workspace,
+                                         uint64_t workspace_bytes, void *hip_stream);
+
+/* mipt_lightmap_dilate: fill the gutter from the charts' borders outwards.  Planes:
+ *   radiance  3 f32 / texel, required
+ *   points    16 B / texel, required (16-byte aligned for the device entry)
+ *   out       3 f32 / texel, required; may be radiance
+ *   level     1 u32 / texel, optional
+ * Level.  Every texel has a value (its radiance words at first) and a level: 1 if covered, 0 otherwise.
+ * Pass k = 1 ... radius (0 <= radius <= 64) reads only the state after pass k - 1:
+ *   - a texel of level 0 is FILLED if at least one of its eight neighbours has a non-zero level.  The neighbours are visited
+ *     dy = -1 ... 1 the outer loop and dx = -1 ... 1 the inner one, the centre and texels outside the atlas skipped;
+ *   - the filled value is, per channel, the sum of the values of the neighbours of non-zero level in that order, from +0, divided by
+ *     (float)count, count being their number; the filled texel's level becomes k + 1;
+ *   - every other texel keeps its value and level.
+ * After the last pass `out` holds the values and `level` (if given) the levels: 1 + the Chebyshev distance to the nearest covered
+ * texel where that is <= radius, else 0.  A texel still at level 0 keeps its radiance words, covered texels come back word for
+ * word, and radius == 0 is a copy.  Because a pass reads only the previous pass's state the result does not depend on scheduling.
+ * Errors, in this order: a null opt, buffers, radiance, points or out; a zero side; width * height >= 2^31; radius above 64; non-zero
+ * flags or reserved fields; planes that overlap (out == radiance alone is allowed); the device entry's list as above. */
+#define MIPT_LIGHTMAP_MAX_RADIUS 64u
+typedef struct { uint32_t width, height, radius, flags; uint32_t reserved[4]; } MiptLightmapDilateOptions;   /* 32 B */
+typedef struct {
+    const float *radiance;
+    const MiptSurfacePoint *points;
+    float       *out;                             /* may be radiance */
+    uint32_t    *level;                           /* NULL = not wanted */
+    void        *reserved[4];                     /* must be NULL */
+} MiptLightmapDilateBuffers;      /* 64 B */
+/* Bytes of workspace mipt_lightmap_dilate_device needs: two float4 planes, 32 B per texel.  0 = an invalid size. */
+MIPT_API uint64_t mipt_lightmap_dilate_workspace_bytes(uint32_t width, uint32_t height);
+MIPT_API int mipt_lightmap_dilate(const MiptLightmapDilateOptions *opt, const MiptLightmapDilateBuffers *host, int device_id);
+MIPT_API int mipt_lightmap_dilate_device(const MiptLightmapDilateOptions *opt, const MiptLightmapDilateBuffers *device, void *d_workspace,
+                                         uint64_t workspace_bytes, void *hip_stream);
+
 /* ---- first-hit feature buffers: depth, ids, position, uv, normal, albedo, emission per pixel --------------------------------------
  * What the camera ray of every pixel hits and what the surface looks like there: the guide images of a denoiser, the id and depth
  * planes of a compositor, G-buffers for training data (csrc/first_hit.hip).  No path is traced: a sample ends at its first hit.

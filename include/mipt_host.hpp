@@ -111,6 +111,70 @@ inline int bake_gather_on(MiptScene *scene, const std::vector<MiptSurfacePoint> 
     if (rc != MIPT_OK) log_error(mipt_last_error());
     return rc;
 }
+// mipt_bake_surface on any resident scene handle: position[3 i .. 3 i + 3) and normal[3 i .. 3 i + 3) of points[i] -- the P and N of
+// the gather, N normalized with `unit_normals` -- the guides of lightmap_filter.  Both are computed.
+inline int bake_surface_on(MiptScene *scene, const std::vector<MiptSurfacePoint> &points, std::vector<float> &position, std::vector<float> &normal,
+                           bool unit_normals = false) {
+    position.assign(points.size() * 3, 0.0f);
+    normal.assign(points.size() * 3, 0.0f);
+    static const MiptSurfacePoint no_point{};
+    static float no_value[2] = {0.0f, 0.0f};
+    MiptBakeSurfaceOptions opt{};
+    opt.flags = unit_normals ? MIPT_BAKE_SURFACE_UNIT_NORMALS : 0u;
+    const int rc = mipt_bake_surface(scene, points.empty() ? &no_point : points.data(), points.size(), &opt, position.empty() ? &no_value[0] : position.data(),
+                                     normal.empty() ? &no_value[1] : normal.data());
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+
+// lightmap_filter: the filter's settings (MiptLightmapFilterOptions; the defaults of the Python mirror)
+struct LightmapFilterSettings {
+    uint32_t iterations = 5;
+    float sigma_color = 4.0f, sigma_normal = 0.5f, sigma_plane = 0.05f, sigma_distance = 0.5f;
+};
+// mipt_lightmap_filter over host planes of a width x height atlas (include/mipt.h "lightmap finishing"): `radiance` 3 f32 per texel,
+// `points` the records of bake_texels, `position` and `normal` 3 f32 per texel or empty = absent.  `out` is resized; it may be
+// `radiance` itself.  A plane of the wrong size is refused here with MIPT_ERR_INVALID_ARG.
+inline int lightmap_filter(uint32_t width, uint32_t height, const std::vector<float> &radiance, const std::vector<MiptSurfacePoint> &points,
+                           const std::vector<float> &position, const std::vector<float> &normal, std::vector<float> &out,
+                           const LightmapFilterSettings &settings = {}, int device_id = 0) {
+    const size_t n = (size_t)width * height;
+    if (radiance.size() != n * 3 || points.size() != n || (!position.empty() && position.size() != n * 3) || (!normal.empty() && normal.size() != n * 3)) {
+        log_error("lightmap_filter: radiance, position and normal hold 3 values and points one record per texel of the atlas");
+        return MIPT_ERR_INVALID_ARG;
+    }
+    if (&out != &radiance) out.assign(n * 3, 0.0f);
+    MiptLightmapFilterOptions o{};
+    o.width = width; o.height = height; o.iterations = settings.iterations;
+    o.sigma_color = settings.sigma_color; o.sigma_normal = settings.sigma_normal; o.sigma_plane = settings.sigma_plane; o.sigma_distance = settings.sigma_distance;
+    MiptLightmapFilterBuffers b{};
+    b.radiance = radiance.data(); b.points = points.data(); b.out = out.data();
+    b.position = position.empty() ? nullptr : position.data();
+    b.normal = normal.empty() ? nullptr : normal.data();
+    const int rc = mipt_lightmap_filter(&o, &b, device_id);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+// mipt_lightmap_dilate over host planes: `radius` passes into the gutter.  `out` is resized and may be `radiance` itself; `level`, if
+// given, receives 1 for a covered texel, k + 1 for one filled in pass k and 0 for one still empty.
+inline int lightmap_dilate(uint32_t width, uint32_t height, const std::vector<float> &radiance, const std::vector<MiptSurfacePoint> &points, uint32_t radius,
+                           std::vector<float> &out, std::vector<uint32_t> *level = nullptr, int device_id = 0) {
+    const size_t n = (size_t)width * height;
+    if (radiance.size() != n * 3 || points.size() != n) {
+        log_error("lightmap_dilate: radiance holds 3 values and points one record per texel of the atlas");
+        return MIPT_ERR_INVALID_ARG;
+    }
+    if (&out != &radiance) out.assign(n * 3, 0.0f);
+    if (level) level->assign(n, 0u);
+    MiptLightmapDilateOptions o{};
+    o.width = width; o.height = height; o.radius = radius;
+    MiptLightmapDilateBuffers b{};
+    b.radiance = radiance.data(); b.points = points.data(); b.out = out.data();
+    b.level = level ? level->data() : nullptr;
+    const int rc = mipt_lightmap_dilate(&o, &b, device_id);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
 
 // mipt_render_features on any resident scene handle: first-hit feature buffers (include/mipt.h "first-hit feature buffers") for
 // `cameras` with `opt`.  `wanted`: FeatureBit flags; only those images are computed and filled, each view-major [view][row][column][k]
@@ -382,6 +446,11 @@ class Scene {                                              // src/scene.rs:12-19
     int bake_gather(const std::vector<MiptSurfacePoint> &points, std::vector<float> &radiance, const MiptBakeOptions &opt, MiptStats *stats = nullptr) const {
         MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
         return m ? bake_gather_on(mipt_multi_scene(m, 0), points, radiance, opt, stats) : MIPT_ERR_HIP;
+    }
+    // the guides of lightmap_filter (mipt_bake_surface), on the same replica
+    int bake_surface(const std::vector<MiptSurfacePoint> &points, std::vector<float> &position, std::vector<float> &normal, bool unit_normals = false) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? bake_surface_on(mipt_multi_scene(m, 0), points, position, normal, unit_normals) : MIPT_ERR_HIP;
     }
 
   private:

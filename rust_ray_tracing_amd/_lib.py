@@ -132,6 +132,39 @@ class MiptBakeOptions(C.Structure):
 
 assert C.sizeof(MiptBakeOptions) == 64 and C.sizeof(MiptBakeTexelOptions) == 32 and C.sizeof(MiptBakeTexelInfo) == 32
 
+BAKE_SURFACE_UNIT_NORMALS = 1
+
+
+class MiptBakeSurfaceOptions(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+# ---- lightmap finishing (include/mipt.h "lightmap finishing") ----
+LIGHTMAP_MAX_RADIUS = 64
+
+
+class MiptLightmapFilterOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("sigma_distance", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class MiptLightmapFilterBuffers(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("points", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("out", C.c_void_p),
+                ("reserved", C.c_void_p * 3)]
+
+
+class MiptLightmapDilateOptions(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class MiptLightmapDilateBuffers(C.Structure):
+    _fields_ = [("radiance", C.c_void_p), ("points", C.c_void_p), ("out", C.c_void_p), ("level", C.c_void_p), ("reserved", C.c_void_p * 4)]
+
+
+assert C.sizeof(MiptBakeSurfaceOptions) == 32 and C.sizeof(MiptLightmapFilterOptions) == 64 and C.sizeof(MiptLightmapFilterBuffers) == 64
+assert C.sizeof(MiptLightmapDilateOptions) == 32 and C.sizeof(MiptLightmapDilateBuffers) == 64
+
 
 # ---- first-hit feature buffers (include/mipt.h "first-hit feature buffers") ----
 FEATURES = (("depth", 1, np.float32), ("prim", 1, np.uint32), ("material", 1, np.uint32), ("position", 3, np.float32),
@@ -291,6 +324,9 @@ EXPORTS = [
     "mipt_sample_map_fill_workspace_bytes", "mipt_sample_map_fill", "mipt_sample_map_fill_device",
     "mipt_query_radiance", "mipt_query_radiance_device",
     "mipt_bake_texels", "mipt_bake_texels_device", "mipt_bake_gather", "mipt_bake_gather_device",
+    "mipt_bake_surface", "mipt_bake_surface_device",
+    "mipt_lightmap_filter_workspace_bytes", "mipt_lightmap_filter", "mipt_lightmap_filter_device",
+    "mipt_lightmap_dilate_workspace_bytes", "mipt_lightmap_dilate", "mipt_lightmap_dilate_device",
 ]
 
 _lib = None
@@ -428,6 +464,25 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_bake_gather.restype = C.c_int
     lib.mipt_bake_gather_device.argtypes = [vp, vp, u64, bo, vp, vp, C.POINTER(MiptStats)]
     lib.mipt_bake_gather_device.restype = C.c_int
+    bs = C.POINTER(MiptBakeSurfaceOptions)
+    lib.mipt_bake_surface.argtypes = [vp, vp, u64, bs, vp, vp]
+    lib.mipt_bake_surface.restype = C.c_int
+    lib.mipt_bake_surface_device.argtypes = [vp, vp, u64, bs, vp, vp, vp]
+    lib.mipt_bake_surface_device.restype = C.c_int
+    lfo, lfb = C.POINTER(MiptLightmapFilterOptions), C.POINTER(MiptLightmapFilterBuffers)
+    lib.mipt_lightmap_filter_workspace_bytes.argtypes = [u32, u32]
+    lib.mipt_lightmap_filter_workspace_bytes.restype = u64
+    lib.mipt_lightmap_filter.argtypes = [lfo, lfb, C.c_int]
+    lib.mipt_lightmap_filter.restype = C.c_int
+    lib.mipt_lightmap_filter_device.argtypes = [lfo, lfb, vp, u64, vp]
+    lib.mipt_lightmap_filter_device.restype = C.c_int
+    ldo, ldb = C.POINTER(MiptLightmapDilateOptions), C.POINTER(MiptLightmapDilateBuffers)
+    lib.mipt_lightmap_dilate_workspace_bytes.argtypes = [u32, u32]
+    lib.mipt_lightmap_dilate_workspace_bytes.restype = u64
+    lib.mipt_lightmap_dilate.argtypes = [ldo, ldb, C.c_int]
+    lib.mipt_lightmap_dilate.restype = C.c_int
+    lib.mipt_lightmap_dilate_device.argtypes = [ldo, ldb, vp, u64, vp]
+    lib.mipt_lightmap_dilate_device.restype = C.c_int
     fb = C.POINTER(MiptFeatureBuffers)
     lib.mipt_render_features.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, C.POINTER(MiptStats)]
     lib.mipt_render_features.restype = C.c_int

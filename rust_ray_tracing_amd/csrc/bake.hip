@@ -1,6 +1,7 @@
 // bake.hip -- the kernels of include/mipt.h "baking": which triangle owns a lightmap texel and where on it the texel's centre lies
 // (mipt_bake_texels*), and the rays a surface point gathers light along with the ordered sum of what they bring back
-// (mipt_bake_gather*; the paths themselves run in pt_kernel.hip's ray kernel, untouched).  Every operator is one rounded f32 operation
+// (mipt_bake_gather*; the paths themselves run in pt_kernel.hip's ray kernel, untouched), and where a surface point lies and which
+// way its surface faces (mipt_bake_surface*).  Every operator is one rounded f32 operation
 // (-ffp-contract=off, correctly rounded division and square root): tests/tools/bake_model.py restates the arithmetic in numpy.
 #include "pt_kernel.h"
 #include "pt_device_math.h"
@@ -250,6 +251,34 @@ __global__ __launch_bounds__(kT) void bake_reduce_kernel(BakeGather g, const flo
     }
 }
 
+// ---- surface -----------------------------------------------------------------------------------------------------------------------
+// A lane per point: P and N as bake_rays_kernel forms them (the same operations on the same operands: the same bits), N normalized
+// on request.  No point: +0.  Either output may be null.
+__global__ __launch_bounds__(kT) void bake_surface_kernel(DevScene sc, const uint4 *points, const uint32_t *inv_order, unsigned long long n,
+                                                          uint32_t unit, float *position, float *normal) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kT + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * kT) {
+        const uint4 pt = points[i];
+        const uint32_t k = pt.w & 0x01ffffffu;
+        V3 P = mk(0.0f, 0.0f, 0.0f), N = mk(0.0f, 0.0f, 0.0f);
+        if (pt.w != MIPT_HIT_NONE && k < sc.n_tris) {                                     // (the entry has refused any other triangle)
+            const float4 *tp = sc.tri_pos + (size_t)inv_order[k] * 4;
+            const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+            const uint32_t t = __float_as_uint(p2.y);
+            if (t < sc.n_tris) {
+                const float4 a0 = sc.tri_attr[(size_t)t * 4 + 0], a1 = sc.tri_attr[(size_t)t * 4 + 1], a2 = sc.tri_attr[(size_t)t * 4 + 2];
+                const float u = __uint_as_float(pt.y), v = __uint_as_float(pt.z);
+                P = (mk(p0.x, p0.y, p0.z) + mk(p0.w, p1.x, p1.y) * u) + mk(p1.z, p1.w, p2.x) * v;
+                const float w = (1.0f - u) - v;                                           // ray.rs:45
+                N = (mk(a0.x, a0.y, a0.z) * w + mk(a0.w, a1.x, a1.y) * u) + mk(a1.z, a1.w, a2.x) * v;
+                if (!(pt.w & MIPT_HIT_FRONT_FACE)) N = mk(-N.x, -N.y, -N.z);              // ray.rs:46-48
+                if (unit) N = normalized(N);
+            }
+        }
+        if (position) { float *o = position + i * 3; o[0] = P.x; o[1] = P.y; o[2] = P.z; }
+        if (normal) { float *o = normal + i * 3; o[0] = N.x; o[1] = N.y; o[2] = N.z; }
+    }
+}
+
 uint32_t grid_for(unsigned long long work, int n_cu) {
     unsigned long long blocks = (work + kT - 1) / kT, cap = (unsigned long long)(n_cu > 0 ? n_cu : 1) * 8ull;
     if (blocks > cap) blocks = cap;
@@ -292,6 +321,13 @@ hipError_t launch_bake_check_points(const void *points, unsigned long long n, ui
 
 hipError_t launch_bake_rays(const DevScene &sc, const BakeGather &g, float4 *rays, int n_cu, hipStream_t stream) {
     hipLaunchKernelGGL(bake_rays_kernel, dim3(grid_for(g.n_paths, n_cu)), dim3(kT), 0, stream, sc, g, rays);
+    return hipGetLastError();
+}
+
+hipError_t launch_bake_surface(const DevScene &sc, const void *points, const uint32_t *inv_order, unsigned long long n, bool unit,
+                               float *position, float *normal, int n_cu, hipStream_t stream) {
+    hipLaunchKernelGGL(bake_surface_kernel, dim3(grid_for(n, n_cu)), dim3(kT), 0, stream, sc, reinterpret_cast<const uint4 *>(points), inv_order, n,
+                       unit ? 1u : 0u, position, normal);
     return hipGetLastError();
 }
 

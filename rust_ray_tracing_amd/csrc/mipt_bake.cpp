@@ -1,4 +1,4 @@
-// mipt_bake.cpp -- the baking entry points of include/mipt.h (mipt_bake_texels, mipt_bake_gather and their _device forms): argument
+// mipt_bake.cpp -- the baking entry points of include/mipt.h (mipt_bake_texels, mipt_bake_gather, mipt_bake_surface and their _device forms): argument
 // checks, the scene-owned workspace, staging for the host entries and the launches of bake.hip's kernels around the ray kernel of the
 // radiance queries (mipt::radiance_launch, mipt_radiance.cpp).  Host C++ only; every device operation is stream-ordered HIP.
 #include "../../include/mipt.h"
@@ -12,6 +12,7 @@ static_assert(sizeof(MiptBakeTexelOptions) == 32 && sizeof(MiptBakeTexelInfo) ==
 static_assert(offsetof(MiptSurfacePoint, prim) == offsetof(MiptHit, prim) && offsetof(MiptSurfacePoint, u) == offsetof(MiptHit, u),
               "a MiptHit with a seed in its t word is a point");
 static_assert(sizeof(mipt::BakeCtl) == 32, "one memset");
+static_assert(sizeof(MiptBakeSurfaceOptions) == 32, "ABI struct sizes (tests/test_lightmap_abi.py)");
 
 namespace {
 
@@ -97,6 +98,35 @@ void add_stats(MiptStats *sum, const MiptStats &c) {
     for (size_t k = 0; k < sizeof sum->diag / sizeof sum->diag[0]; k++) sum->diag[k] += c.diag[k];
 }
 
+// the caller -> record map of the scene (d_bake_inv), made on first use and kept until the tree changes (release_geometry)
+int inverse_order(MiptScene *scene, hipStream_t stream) {
+    if (scene->d_bake_inv) return MIPT_OK;
+    mipt::DevPtr<uint32_t> inv;
+    MIPT_HIP(inv.alloc(scene->n_tris ? scene->n_tris : 1));
+    MIPT_HIP(hipMemsetAsync(inv.get(), 0, (scene->n_tris ? scene->n_tris : 1) * sizeof(uint32_t), stream));
+    MIPT_HIP(mipt::launch_bake_invert_order(scene->dev, scene->d_tri_order, inv.get(), scene->n_cu, stream));
+    MIPT_HIP(hipStreamSynchronize(stream));
+    scene->d_bake_inv = std::move(inv);
+    return MIPT_OK;
+}
+
+// the first point of d_points whose triangle the scene does not have, refused as bad_prim; blocks
+int check_prims_device(const char *who, MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, hipStream_t stream) {
+    int rc;
+    if ((rc = scene->d_bake_ctl.grow(sizeof(mipt::BakeCtl)))) return rc;
+    mipt::BakeCtl ctl;
+    MIPT_HIP(mipt::launch_bake_check_points(d_points, n, (uint32_t)scene->n_tris, scene->d_bake_ctl, scene->n_cu, stream));
+    MIPT_HIP(hipMemcpyAsync(&ctl, scene->d_bake_ctl, sizeof ctl, hipMemcpyDeviceToHost, stream));
+    MIPT_HIP(hipStreamSynchronize(stream));
+    if (ctl.bad_point != ~0ull) return bad_prim(who, ctl.bad_point, scene);
+    return MIPT_OK;
+}
+int check_prims_host(const char *who, const MiptScene *scene, const MiptSurfacePoint *points, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++)
+        if (points[i].prim != MIPT_HIT_NONE && (points[i].prim & 0x01ffffffu) >= scene->n_tris) return bad_prim(who, i, scene);
+    return MIPT_OK;
+}
+
 // The gather with every argument already checked (the triangle indices too, unless check_prims); d_points / d_radiance in HBM of the
 // scene's device, n > 0
 int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeOptions *opt, float *d_radiance,
@@ -108,21 +138,8 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
     if ((rc = scene->d_bake_ctl.grow(sizeof(mipt::BakeCtl)))) return rc;
     if ((rc = scene->d_bake_rays.grow((size_t)chunk * sizeof(MiptRay)))) return rc;
     if ((rc = scene->d_bake_path.grow((size_t)chunk * 12 + 32))) return rc;   // + the two carry slots
-    if (check_prims) {
-        mipt::BakeCtl ctl;
-        MIPT_HIP(mipt::launch_bake_check_points(d_points, n, (uint32_t)scene->n_tris, scene->d_bake_ctl, scene->n_cu, stream));
-        MIPT_HIP(hipMemcpyAsync(&ctl, scene->d_bake_ctl, sizeof ctl, hipMemcpyDeviceToHost, stream));
-        MIPT_HIP(hipStreamSynchronize(stream));
-        if (ctl.bad_point != ~0ull) return bad_prim(who, ctl.bad_point, scene);
-    }
-    if (!scene->d_bake_inv) {                                             // the caller -> record map, until the tree changes (release_geometry)
-        mipt::DevPtr<uint32_t> inv;
-        MIPT_HIP(inv.alloc(scene->n_tris ? scene->n_tris : 1));
-        MIPT_HIP(hipMemsetAsync(inv.get(), 0, (scene->n_tris ? scene->n_tris : 1) * sizeof(uint32_t), stream));
-        MIPT_HIP(mipt::launch_bake_invert_order(scene->dev, scene->d_tri_order, inv.get(), scene->n_cu, stream));
-        MIPT_HIP(hipStreamSynchronize(stream));
-        scene->d_bake_inv = std::move(inv);
-    }
+    if (check_prims && (rc = check_prims_device(who, scene, d_points, n, stream))) return rc;
+    if ((rc = inverse_order(scene, stream))) return rc;
     mipt::Event ev0, ev1;
     MIPT_HIP(hipEventCreate(ev0.put()));
     MIPT_HIP(hipEventCreate(ev1.put()));
@@ -177,16 +194,90 @@ int gather_host(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, co
     if (rc) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return MIPT_OK;
-    for (uint64_t i = 0; i < n; i++)
-        if (points[i].prim != MIPT_HIT_NONE && (points[i].prim & 0x01ffffffu) >= scene->n_tris) return bad_prim(who, i, scene);
+    if ((rc = check_prims_host(who, scene, points, n))) return rc;
     return mipt::staged_call(scene, points, (size_t)n * sizeof(MiptSurfacePoint), radiance, (size_t)n * 3 * sizeof(float), [&](const void *d_points, void *d_out) {
         return gather_launch(who, scene, (const MiptSurfacePoint *)d_points, n, opt, (float *)d_out, nullptr, false, stats);
+    });
+}
+
+// ---- surface -----------------------------------------------------------------------------------------------------------------------
+int surface_check(const char *who, const MiptScene *scene, const void *points, uint64_t n, const MiptBakeSurfaceOptions *opt, const void *position,
+                  const void *normal) {
+    if (!scene || !points || (!position && !normal)) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene or points, or position and normal both null", who);
+    int rc;
+    if ((rc = mipt::ray_count_check(who, "n", n))) return rc;
+    if (!opt) return MIPT_OK;
+    if (opt->flags & ~MIPT_BAKE_SURFACE_UNIT_NORMALS)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: flags 0x%x: only MIPT_BAKE_SURFACE_UNIT_NORMALS is accepted", who, opt->flags);
+    return mipt::reserved_check(who, opt->reserved);
+}
+
+// every argument checked, the triangle indices too; the pointers in HBM of the scene's device, n > 0; blocks
+int surface_launch(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeSurfaceOptions *opt, float *d_position,
+                   float *d_normal, hipStream_t stream) {
+    int rc;
+    if ((rc = inverse_order(scene, stream))) return rc;
+    const bool unit = opt && (opt->flags & MIPT_BAKE_SURFACE_UNIT_NORMALS);
+    MIPT_HIP(mipt::launch_bake_surface(scene->dev, d_points, scene->d_bake_inv, n, unit, d_position, d_normal, scene->n_cu, stream));
+    MIPT_HIP(hipStreamSynchronize(stream));
+    return MIPT_OK;
+}
+
+int surface_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeSurfaceOptions *opt, float *d_position,
+                   float *d_normal, void *hip_stream) {
+    const char *who = "mipt_bake_surface_device";
+    int rc = surface_check(who, scene, d_points, n, opt, d_position, d_normal);
+    if (rc) return rc;
+    // device_call's order with two result buffers: alignments, the empty call, overlaps, whose memory, the triangles, the launch
+    if ((uintptr_t)d_points & 15u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_points must be 16-byte aligned", who);
+    if ((uintptr_t)d_position & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_position must be 4-byte aligned", who);
+    if ((uintptr_t)d_normal & 3u) return fail(MIPT_ERR_INVALID_ARG, "%s: d_normal must be 4-byte aligned", who);
+    if (n == 0) return MIPT_OK;
+    const uint64_t in_bytes = n * sizeof(MiptSurfacePoint), out_bytes = n * 12;
+    if (d_position && mipt::ranges_overlap(d_points, in_bytes, d_position, out_bytes))
+        return fail(MIPT_ERR_INVALID_ARG, "%s: d_points overlaps d_position", who);
+    if (d_normal && mipt::ranges_overlap(d_points, in_bytes, d_normal, out_bytes)) return fail(MIPT_ERR_INVALID_ARG, "%s: d_points overlaps d_normal", who);
+    if (d_position && d_normal && mipt::ranges_overlap(d_position, out_bytes, d_normal, out_bytes))
+        return fail(MIPT_ERR_INVALID_ARG, "%s: d_position overlaps d_normal", who);
+    if ((rc = mipt::device_buffer_check(who, d_points, scene->device, "d_points"))) return rc;
+    if (d_position && (rc = mipt::device_buffer_check(who, d_position, scene->device, "d_position"))) return rc;
+    if (d_normal && (rc = mipt::device_buffer_check(who, d_normal, scene->device, "d_normal"))) return rc;
+    MIPT_HIP(hipSetDevice(scene->device));
+    if ((rc = check_prims_device(who, scene, d_points, n, (hipStream_t)hip_stream))) return rc;
+    return surface_launch(scene, d_points, n, opt, d_position, d_normal, (hipStream_t)hip_stream);
+}
+
+int surface_host(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, const MiptBakeSurfaceOptions *opt, float *position, float *normal) {
+    const char *who = "mipt_bake_surface";
+    int rc = surface_check(who, scene, points, n, opt, position, normal);
+    if (rc) return rc;
+    if (n == 0) return MIPT_OK;
+    if ((rc = check_prims_host(who, scene, points, n))) return rc;
+    // the scene's staging pair holds the points and the first wanted output; a second output is staged beside it
+    const size_t out_bytes = (size_t)n * 3 * sizeof(float);
+    float *first = position ? position : normal;
+    return mipt::staged_call(scene, points, (size_t)n * sizeof(MiptSurfacePoint), first, out_bytes, [&](const void *d_points, void *d_out) -> int {
+        mipt::DevPtr<float> d_second;
+        if (position && normal) MIPT_HIP(d_second.alloc((size_t)n * 3));
+        float *d_position = position ? (float *)d_out : nullptr, *d_normal = !normal ? nullptr : position ? d_second.get() : (float *)d_out;
+        int rc2 = surface_launch(scene, (const MiptSurfacePoint *)d_points, n, opt, d_position, d_normal, nullptr);
+        if (rc2) return rc2;
+        if (position && normal) MIPT_HIP(hipMemcpy(normal, d_second.get(), out_bytes, hipMemcpyDeviceToHost));
+        return MIPT_OK;
     });
 }
 
 } // namespace
 
 extern "C" {
+
+int mipt_bake_surface(MiptScene *scene, const MiptSurfacePoint *points, uint64_t n, const MiptBakeSurfaceOptions *opt, float *position, float *normal) {
+    MIPT_NO_THROW(surface_host(scene, points, n, opt, position, normal))
+}
+int mipt_bake_surface_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeSurfaceOptions *opt, float *d_position,
+                             float *d_normal, void *hip_stream) {
+    MIPT_NO_THROW(surface_device(scene, d_points, n, opt, d_position, d_normal, hip_stream))
+}
 
 int mipt_bake_texels(MiptScene *scene, uint32_t width, uint32_t height, const MiptBakeTexelOptions *opt, MiptSurfacePoint *points,
                      MiptBakeTexelInfo *info) {

@@ -166,6 +166,35 @@ struct BakeGather {                         // one chunk of a gather: paths [fir
 hipError_t launch_bake_rays(const DevScene &sc, const BakeGather &g, float4 *rays, int n_cu, hipStream_t stream);
 // path: n_paths x 3 f32, the chunk's traced radiance; radiance: the caller's n x 3 f32
 hipError_t launch_bake_reduce(const BakeGather &g, const float *path, float *radiance, int n_cu, hipStream_t stream);
+// position[i], normal[i] (3 f32 each; either may be NULL) of point i < n: P and N of the gather, N normalized if `unit`; +0 for no point
+hipError_t launch_bake_surface(const DevScene &sc, const void *points, const uint32_t *inv_order, unsigned long long n, bool unit,
+                               float *position, float *normal, int n_cu, hipStream_t stream);
+
+// ---- lightmap finishing (lightmap.hip; mipt_lightmap_filter* / mipt_lightmap_dilate*) ----
+struct DevLightmapFilter {
+    // planar inputs; position / normal NULL = absent (their terms are left out).  out may be radiance.
+    const float *radiance, *position, *normal;
+    const uint4 *points;                    // the texel records; only `prim` (w) is read
+    float *out;
+    // the workspace: four float4 planes of width * height each -- two colour planes {r, g, b, covered ? 1 : 0}, position, normal
+    float4 *colour[2], *pos4, *nrm4;
+    uint32_t width, height, iterations;
+    uint32_t tiles_x, tiles_y;              // 64x4-texel tiles per row / per column
+    float kc[8], kd[8], kn, kl;             // 1 / sigma^2; colour and distance per iteration (include/mipt.h)
+};
+// the pack pass and `iterations` filter passes, one launch each (stream-ordered; no allocation, no synchronisation inside)
+hipError_t launch_lightmap_filter(const DevLightmapFilter &d, hipStream_t stream);
+struct DevLightmapDilate {
+    const float *radiance;
+    const uint4 *points;
+    float *out;
+    uint32_t *level;                        // NULL = not wanted
+    float4 *state[2];                       // the workspace: two planes of {r, g, b, level as its bits}
+    uint32_t width, height, radius;
+    uint32_t tiles_x, tiles_y;
+};
+// the pack pass, `radius` passes and the unpack pass, one launch each (stream-ordered; no allocation, no synchronisation inside)
+hipError_t launch_lightmap_dilate(const DevLightmapDilate &d, hipStream_t stream);
 
 // ---- first-hit feature buffers (first_hit.hip; mipt_render_features*) ----
 struct PartRec;                             // pt_mesh_rule.h

@@ -758,11 +758,152 @@ class Scene:  # scene.rs:12-19
             rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
         return self._traced(rc, f, out, st)
 
-    def bake_lightmap(self, width: int, height: int, samples: int, device=None, stream=None, **gather_args):
+    def bake_surface(self, points, unit_normals: bool = False, handle=None, stream=None, want=("position", "normal")):
+        """World position and interpolated normal of every surface point (mipt_bake_surface / _device): the P and N ``bake_gather``
+        leaves from, the guides of ``lightmap_filter``.  ``points`` as for ``bake_gather`` (no seeds needed).  ``unit_normals``:
+        normalized(N) instead of N as formed.  ``want``: which of the two to compute.  Returns (position, normal), [n, 3] float32
+        arrays (host points) or device tensors (device points); None for one not wanted.  A HIT_NONE point yields zeros."""
+        where, r = self._bake_points(points, None if not isinstance(points, dict) else np.zeros(len(points["u"]), dtype=np.uint32))
+        want = tuple(want)
+        if not want or any(w not in ("position", "normal") for w in want):
+            raise ValueError('want: expected "position", "normal" or both')
+        h = self._resident(handle)
+        n = len(r)
+        opt = L.MiptBakeSurfaceOptions()
+        opt.flags = L.BAKE_SURFACE_UNIT_NORMALS if unit_normals else 0
+        lib = L.load()
+        if where == "host":
+            outs = [np.zeros((n, 3), dtype=np.float32) if w in want else None for w in ("position", "normal")]
+            ptrs = [None if o is None else (L.ptr(o) if n else C.c_void_p(16)) for o in outs]
+            L.check(lib.mipt_bake_surface(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), ptrs[0], ptrs[1]), "mipt_bake_surface")
+        else:
+            import torch
+            outs = [torch.empty((n, 3), dtype=torch.float32, device=r.device) if w in want else None for w in ("position", "normal")]
+            ptrs = [None if o is None else (o.data_ptr() if n else 16) for o in outs]
+            L.check(lib.mipt_bake_surface_device(h, r.data_ptr() if n else 16, n, C.byref(opt), ptrs[0], ptrs[1], self._stream_arg(stream, r.device)),
+                    "mipt_bake_surface_device")
+        return outs[0], outs[1]
+
+    @staticmethod
+    def _lightmap_planes(radiance, points, guides):
+        """-> (torch?, (H, W), radiance, points, {name: guide}); ValueError naming the argument for anything else."""
+        torch_in = Scene._is_torch(radiance)
+        if not torch_in:
+            radiance = np.asarray(radiance)
+        if radiance.ndim != 3 or radiance.shape[-1] != 3:
+            raise ValueError(f"radiance: expected shape [H,W,3]; got {tuple(radiance.shape)}")
+        h, w = int(radiance.shape[0]), int(radiance.shape[1])
+        where, pts = Scene._bake_points(points, None)
+        if (where == "device") != torch_in:
+            raise ValueError("points: radiance and points must both be numpy arrays or both device tensors")
+        if len(pts) != h * w:
+            raise ValueError(f"points: expected {h * w} records, one per texel; got {len(pts)}")
+        planes = {}
+        for name, a in [("radiance", radiance)] + list(guides.items()):
+            if a is None:
+                continue
+            if Scene._is_torch(a) != torch_in:
+                raise ValueError(f"{name}: radiance and the guides must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                if a.dtype != torch.float32 or not a.is_cuda or a.device != radiance.device:
+                    raise ValueError(f"{name}: expected a float32 tensor on radiance's device {radiance.device}")
+                if a.numel() != h * w * 3 or a.shape[-1] != 3:
+                    raise ValueError(f"{name}: expected shape {(h, w, 3)}; got {tuple(a.shape)}")
+                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
+                    raise ValueError(f"{name}: expected a contiguous tensor")
+                planes[name] = a
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.float32:
+                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
+                if a.size != h * w * 3 or a.shape[-1] != 3:
+                    raise ValueError(f"{name}: expected shape {(h, w, 3)}; got {a.shape}")
+                planes[name] = np.ascontiguousarray(a)
+        if torch_in and pts.device != radiance.device:
+            raise ValueError(f"points: expected a tensor on radiance's device {radiance.device}")
+        return torch_in, (h, w), planes.pop("radiance"), pts, planes
+
+    @staticmethod
+    def _lightmap_device_call(f, name, opt, bufs, need, tensors, dev, stream):
+        """a stream-ordered device entry with a torch tensor as its workspace, as ``Renderer.denoise`` runs one"""
+        import torch
+        workspace = torch.empty((max(int(need), 16) // 16, 4), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+        s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+        for t in tensors + [workspace]:
+            t.record_stream(s)
+        L.check(f(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), name)
+
+    @staticmethod
+    def lightmap_filter(radiance, points, position=None, normal=None, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.5,
+                        sigma_plane: float = 0.05, sigma_distance: float = 0.5, device_id: int = 0, stream=None):
+        """The edge-avoiding a-trous filter of include/mipt.h "lightmap finishing" over the covered texels of one atlas: ``radiance``
+        [H,W,3] float32, ``points`` the H*W records of ``bake_texels``, the optional guides ``position`` and ``normal`` [H,W,3] (or
+        [H*W,3], as ``bake_surface`` returns them; None = their terms are left out).  Uncovered texels are never taps and come back
+        unchanged.  numpy arrays go through mipt_lightmap_filter on ``device_id``; device tensors through mipt_lightmap_filter_device
+        on ``stream`` without blocking.  Returns a new array / tensor [H,W,3]."""
+        torch_in, (h, w), rad, pts, g = Scene._lightmap_planes(radiance, points, {"position": position, "normal": normal})
+        opt = L.MiptLightmapFilterOptions()
+        opt.width, opt.height, opt.iterations = w, h, iterations
+        opt.sigma_color, opt.sigma_normal, opt.sigma_plane, opt.sigma_distance = sigma_color, sigma_normal, sigma_plane, sigma_distance
+        bufs = L.MiptLightmapFilterBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            out = torch.empty_like(rad)
+            bufs.radiance, bufs.points, bufs.out = rad.data_ptr(), pts.data_ptr(), out.data_ptr()
+            for name, a in g.items():
+                setattr(bufs, name, a.data_ptr())
+            Scene._lightmap_device_call(lib.mipt_lightmap_filter_device, "mipt_lightmap_filter_device", opt, bufs,
+                                        lib.mipt_lightmap_filter_workspace_bytes(w, h), [rad, pts, out] + list(g.values()), rad.device, stream)
+            return out
+        out = np.empty_like(rad)
+        bufs.radiance, bufs.points, bufs.out = rad.ctypes.data, pts.ctypes.data, out.ctypes.data
+        for name, a in g.items():
+            setattr(bufs, name, a.ctypes.data)
+        L.check(lib.mipt_lightmap_filter(C.byref(opt), C.byref(bufs), device_id), "mipt_lightmap_filter")
+        return out
+
+    @staticmethod
+    def lightmap_dilate(radiance, points, radius: int = 2, want_level: bool = False, device_id: int = 0, stream=None):
+        """Dilation of include/mipt.h "lightmap finishing": ``radius`` passes, each filling the uncovered texels that touch a covered
+        or already filled one with the mean of those neighbours.  ``radiance`` [H,W,3] float32 and ``points`` as for
+        ``lightmap_filter``.  Returns the dilated atlas [H,W,3], or (atlas, level [H,W] uint32 -- int32 for a tensor) with
+        ``want_level``: 1 = covered, k + 1 = filled in pass k, 0 = still empty."""
+        torch_in, (h, w), rad, pts, _ = Scene._lightmap_planes(radiance, points, {})
+        opt = L.MiptLightmapDilateOptions()
+        opt.width, opt.height, opt.radius = w, h, radius
+        bufs = L.MiptLightmapDilateBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            out = torch.empty_like(rad)
+            level = torch.empty((h, w), dtype=torch.int32, device=rad.device) if want_level else None
+            bufs.radiance, bufs.points, bufs.out = rad.data_ptr(), pts.data_ptr(), out.data_ptr()
+            bufs.level = level.data_ptr() if want_level else None
+            Scene._lightmap_device_call(lib.mipt_lightmap_dilate_device, "mipt_lightmap_dilate_device", opt, bufs,
+                                        lib.mipt_lightmap_dilate_workspace_bytes(w, h), [rad, pts, out] + ([level] if want_level else []), rad.device, stream)
+        else:
+            out = np.empty_like(rad)
+            level = np.zeros((h, w), dtype=np.uint32) if want_level else None
+            bufs.radiance, bufs.points, bufs.out = rad.ctypes.data, pts.ctypes.data, out.ctypes.data
+            bufs.level = level.ctypes.data if want_level else None
+            L.check(lib.mipt_lightmap_dilate(C.byref(opt), C.byref(bufs), device_id), "mipt_lightmap_dilate")
+        return (out, level) if want_level else out
+
+    def bake_lightmap(self, width: int, height: int, samples: int, device=None, stream=None, filter=None, dilate: int = 0, **gather_args):
         """``bake_texels`` then ``bake_gather`` with the texel indices as seeds: the mean radiance every covered texel of the atlas
         gathers.  With torch and a visible device (``device`` None) or ``device=True`` both steps stay in HBM and tensors come back;
-        otherwise numpy arrays.  Returns (atlas [height, width, 3] float32, covered [height, width] bool, stats); stats carries the
-        texel pass's info under "texels"."""
+        otherwise numpy arrays.  ``filter``: None, or a dict of ``lightmap_filter``'s options -- the atlas is then filtered, guided
+        by ``bake_surface``'s position and unit normal; ``dilate`` > 0: ``lightmap_dilate`` with that radius afterwards.  With
+        neither, the result and the calls are those of the two steps alone.  Returns (atlas [height, width, 3] float32, covered
+        [height, width] bool -- the texel pass's mask, whatever was dilated --, stats); stats carries the texel pass's info under
+        "texels"."""
         if device is None:
             try:
                 import torch
@@ -776,7 +917,15 @@ class Scene:  # scene.rs:12-19
             covered = (points[:, 3] != -1).reshape(height, width)
         else:
             covered = (points["prim"] != L.HIT_NONE).reshape(height, width)
-        return rad.reshape(height, width, 3), covered, stats
+        rad = rad.reshape(height, width, 3)
+        if width and height and (filter is not None or dilate):
+            device_id = self._handle_device if gather_args.get("handle") is None else 0
+            if filter is not None:
+                pos, nrm = self.bake_surface(points, unit_normals=True, handle=gather_args.get("handle"), stream=stream)
+                rad = Scene.lightmap_filter(rad, points, position=pos, normal=nrm, device_id=device_id, stream=stream, **dict(filter))
+            if dilate:
+                rad = Scene.lightmap_dilate(rad, points, radius=dilate, device_id=device_id, stream=stream)
+        return rad, covered, stats
 
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
