@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import math
 import os
 import sys
 from dataclasses import dataclass, field
@@ -101,6 +102,87 @@ class Texture:  # texture.rs:3-10
             return Texture(int(desc.width), int(desc.height), int(h.value), px)
         finally:
             lib.mipt_texture_free(img)
+
+
+# -- what the wrappers of Scene and Renderer share -------------------------------------------------
+def _is_torch(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _stream_arg(stream, device):
+    """the raw hipStream_t of ``stream``: a torch stream, a raw handle or None = torch's current stream on ``device``"""
+    if stream is None:
+        import torch
+        return torch.cuda.current_stream(device).cuda_stream
+    return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+
+def _camera_table(cams, who=None) -> np.ndarray:
+    """the contiguous CAMERA table of a list of Camera (or CAMERA records); ``who``: the caller an empty list is refused for"""
+    if who and not cams:
+        raise ValueError(f"{who}: no cameras")
+    return np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+
+
+def _views(lead):
+    """(V, H, W) of a plane's leading shape [V,H,W] or [H,W]"""
+    return ((1,) + lead) if len(lead) == 2 else lead
+
+
+def _check_planes(anchor_name, anchor, family, table, flat=False, required=(), missing=""):
+    """The planes of one image-space call: all numpy arrays or all tensors like ``anchor``, the plane whose kind and device the
+    others follow.  ``table``: (name, plane or None, expected shape, ids?) rows, the anchor's own among them -- an ids plane is
+    uint32 as an array and int32 as a tensor (the same bits), any other float32.  ``flat``: a plane may have any shape of that many
+    values with that last dimension ([H*W,3] for [H,W,3]).  A None plane is left out, unless its name is in ``required``: then
+    ``missing`` says why not.  -> (torch?, {name: contiguous array, or the tensor}); ValueError naming the plane otherwise."""
+    torch_in = _is_torch(anchor)
+    planes = {}
+    for name, a, want, ids in table:
+        if a is None:
+            if name in required:
+                raise ValueError(f"{name}: {missing}")
+            continue
+        if _is_torch(a) != torch_in:
+            raise ValueError(f"{name}: {family} must all be numpy arrays or all torch tensors")
+        if torch_in:
+            import torch
+            if a.dtype != (torch.int32 if ids else torch.float32) or not a.is_cuda or a.device != anchor.device:
+                raise ValueError(f"{name}: expected a {'int32' if ids else 'float32'} tensor on {anchor_name}'s device {anchor.device}")
+        else:
+            a = np.asarray(a)
+            if a.dtype != (np.uint32 if ids else np.float32):
+                raise ValueError(f"{name}: expected uint32; got {a.dtype}" if ids else f"{name}: expected float32; got {a.dtype}")
+        shape = tuple(a.shape)
+        if (math.prod(shape) != math.prod(want) or shape[-1:] != want[-1:]) if flat else shape != want:
+            raise ValueError(f"{name}: expected shape {want}; got {shape}")
+        if torch_in and not a.is_contiguous():              # a copy here would run on torch's current stream, not on `stream`
+            raise ValueError(f"{name}: expected a contiguous tensor")
+        planes[name] = a if torch_in else np.ascontiguousarray(a)
+    return torch_in, planes
+
+
+def _fill(bufs, **planes) -> list:
+    """the addresses of ``planes`` (arrays or tensors; None = left NULL) into the fields of a ...Buffers struct of those names;
+    -> the planes given, which is what the call then touches"""
+    given = [(name, a) for name, a in planes.items() if a is not None]
+    for name, a in given:
+        setattr(bufs, name, a.data_ptr() if _is_torch(a) else a.ctypes.data)
+    return [a for _, a in given]
+
+
+def _stream_ordered(dev, stream, tensors, need=None):
+    """What a device entry that runs stream-ordered needs from torch: -> (the raw stream, the workspace).  ``tensors``: every tensor
+    the entry reads or writes (None entries are skipped); ``need``: the bytes of its workspace, a torch tensor of 16-byte rows -- an
+    impossible size is the library's to refuse --, None = the entry has none."""
+    import torch
+    workspace = None if need is None else torch.empty((max(int(need), 16) // 16, 4), dtype=torch.float32, device=dev)
+    raw = _stream_arg(stream, dev)
+    # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
+    s = torch.cuda.ExternalStream(raw, device=dev) if raw else torch.cuda.default_stream(dev)
+    for t in list(tensors) + [workspace]:
+        if t is not None:
+            t.record_stream(s)
+    return raw, workspace
 
 
 class Scene:  # scene.rs:12-19
@@ -384,14 +466,10 @@ class Scene:  # scene.rs:12-19
             if str(a.dtype) != "torch.float32" or not a.is_contiguous() or a.numel() != n * width or not a.is_cuda:
                 raise ValueError(f"{name}: expected a contiguous float32 device tensor of {n} x {width} values")
             ptrs[name], tensors[name] = a.data_ptr(), a
-        if stream is None:
-            try:
-                import torch
-                stream = torch.cuda.current_stream(self._handle_device).cuda_stream
-            except Exception:
-                stream = None
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        try:
+            stream = _stream_arg(stream, self._handle_device)
+        except Exception:                                              # None without torch: the null stream
+            stream = None
         info = L.MiptUpdateInfo()
         L.check(L.load().mipt_scene_update_mesh_device(self._handle, ptrs["positions"], ptrs["normals"], ptrs["transforms"], mode, stream, C.byref(info)),
                 "mipt_scene_update_mesh_device")
@@ -465,9 +543,8 @@ class Scene:  # scene.rs:12-19
         self.bvh_nodes = nodes[: count.value].copy()
 
     # -- ray queries (include/mipt.h "ray queries") ---------------------------------------------
-    @staticmethod
-    def _is_torch(a) -> bool:
-        return type(a).__module__.split(".")[0] == "torch"
+    _is_torch = staticmethod(_is_torch)
+    _stream_arg = staticmethod(_stream_arg)
 
     # what the wrappers of the entries that take a list of work items share (queries, radiance queries, baking)
     def _resident(self, handle=None):
@@ -475,13 +552,6 @@ class Scene:  # scene.rs:12-19
         if h is None:
             raise RuntimeError("scene is not resident on a device")
         return h
-
-    @staticmethod
-    def _stream_arg(stream, device):
-        import torch
-        if stream is None:
-            return torch.cuda.current_stream(device).cuda_stream
-        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
 
     @staticmethod
     def _seeds(seeds, n: int) -> np.ndarray:
@@ -787,57 +857,21 @@ class Scene:  # scene.rs:12-19
     @staticmethod
     def _lightmap_planes(radiance, points, guides):
         """-> (torch?, (H, W), radiance, points, {name: guide}); ValueError naming the argument for anything else."""
-        torch_in = Scene._is_torch(radiance)
-        if not torch_in:
+        if not _is_torch(radiance):
             radiance = np.asarray(radiance)
         if radiance.ndim != 3 or radiance.shape[-1] != 3:
             raise ValueError(f"radiance: expected shape [H,W,3]; got {tuple(radiance.shape)}")
         h, w = int(radiance.shape[0]), int(radiance.shape[1])
         where, pts = Scene._bake_points(points, None)
-        if (where == "device") != torch_in:
+        if (where == "device") != _is_torch(radiance):
             raise ValueError("points: radiance and points must both be numpy arrays or both device tensors")
         if len(pts) != h * w:
             raise ValueError(f"points: expected {h * w} records, one per texel; got {len(pts)}")
-        planes = {}
-        for name, a in [("radiance", radiance)] + list(guides.items()):
-            if a is None:
-                continue
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: radiance and the guides must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                if a.dtype != torch.float32 or not a.is_cuda or a.device != radiance.device:
-                    raise ValueError(f"{name}: expected a float32 tensor on radiance's device {radiance.device}")
-                if a.numel() != h * w * 3 or a.shape[-1] != 3:
-                    raise ValueError(f"{name}: expected shape {(h, w, 3)}; got {tuple(a.shape)}")
-                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                planes[name] = a
-            else:
-                a = np.asarray(a)
-                if a.dtype != np.float32:
-                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
-                if a.size != h * w * 3 or a.shape[-1] != 3:
-                    raise ValueError(f"{name}: expected shape {(h, w, 3)}; got {a.shape}")
-                planes[name] = np.ascontiguousarray(a)
+        torch_in, planes = _check_planes("radiance", radiance, "radiance and the guides",
+                                         [(name, a, (h, w, 3), False) for name, a in [("radiance", radiance)] + list(guides.items())], flat=True)
         if torch_in and pts.device != radiance.device:
             raise ValueError(f"points: expected a tensor on radiance's device {radiance.device}")
         return torch_in, (h, w), planes.pop("radiance"), pts, planes
-
-    @staticmethod
-    def _lightmap_device_call(f, name, opt, bufs, need, tensors, dev, stream):
-        """a stream-ordered device entry with a torch tensor as its workspace, as ``Renderer.denoise`` runs one"""
-        import torch
-        workspace = torch.empty((max(int(need), 16) // 16, 4), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-        s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-        for t in tensors + [workspace]:
-            t.record_stream(s)
-        L.check(f(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), name)
 
     @staticmethod
     def lightmap_filter(radiance, points, position=None, normal=None, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.5,
@@ -856,16 +890,12 @@ class Scene:  # scene.rs:12-19
         if torch_in:
             import torch
             out = torch.empty_like(rad)
-            bufs.radiance, bufs.points, bufs.out = rad.data_ptr(), pts.data_ptr(), out.data_ptr()
-            for name, a in g.items():
-                setattr(bufs, name, a.data_ptr())
-            Scene._lightmap_device_call(lib.mipt_lightmap_filter_device, "mipt_lightmap_filter_device", opt, bufs,
-                                        lib.mipt_lightmap_filter_workspace_bytes(w, h), [rad, pts, out] + list(g.values()), rad.device, stream)
+            touched = _fill(bufs, radiance=rad, points=pts, out=out, **g)
+            raw, ws = _stream_ordered(rad.device, stream, touched, lib.mipt_lightmap_filter_workspace_bytes(w, h))
+            L.check(lib.mipt_lightmap_filter_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), ws.numel() * 4, raw), "mipt_lightmap_filter_device")
             return out
         out = np.empty_like(rad)
-        bufs.radiance, bufs.points, bufs.out = rad.ctypes.data, pts.ctypes.data, out.ctypes.data
-        for name, a in g.items():
-            setattr(bufs, name, a.ctypes.data)
+        _fill(bufs, radiance=rad, points=pts, out=out, **g)
         L.check(lib.mipt_lightmap_filter(C.byref(opt), C.byref(bufs), device_id), "mipt_lightmap_filter")
         return out
 
@@ -884,15 +914,13 @@ class Scene:  # scene.rs:12-19
             import torch
             out = torch.empty_like(rad)
             level = torch.empty((h, w), dtype=torch.int32, device=rad.device) if want_level else None
-            bufs.radiance, bufs.points, bufs.out = rad.data_ptr(), pts.data_ptr(), out.data_ptr()
-            bufs.level = level.data_ptr() if want_level else None
-            Scene._lightmap_device_call(lib.mipt_lightmap_dilate_device, "mipt_lightmap_dilate_device", opt, bufs,
-                                        lib.mipt_lightmap_dilate_workspace_bytes(w, h), [rad, pts, out] + ([level] if want_level else []), rad.device, stream)
+            touched = _fill(bufs, radiance=rad, points=pts, out=out, level=level)
+            raw, ws = _stream_ordered(rad.device, stream, touched, lib.mipt_lightmap_dilate_workspace_bytes(w, h))
+            L.check(lib.mipt_lightmap_dilate_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), ws.numel() * 4, raw), "mipt_lightmap_dilate_device")
         else:
             out = np.empty_like(rad)
             level = np.zeros((h, w), dtype=np.uint32) if want_level else None
-            bufs.radiance, bufs.points, bufs.out = rad.ctypes.data, pts.ctypes.data, out.ctypes.data
-            bufs.level = level.ctypes.data if want_level else None
+            _fill(bufs, radiance=rad, points=pts, out=out, level=level)
             L.check(lib.mipt_lightmap_dilate(C.byref(opt), C.byref(bufs), device_id), "mipt_lightmap_dilate")
         return (out, level) if want_level else out
 
@@ -1041,12 +1069,22 @@ class Renderer:  # renderer.rs:8-85
             return None
         return Renderer(options)
 
-    def render_buffers(self, scene: Scene, want_hdr: bool = True, want_rgba8: bool = True, flags: int = 0):
-        """The backend arm: (Renderer, &Scene) -> pixels.  Returns (hdr float32 [h,w,3] | None,
-        rgba8 uint8 [h,w,4] | None, stats dict)."""
+    def _mi355x(self) -> RendererOptions:
+        """the options, for an arm that only this build's backend has"""
         o = self.options
         if o.backend != RendererBackend.MI355X:
             raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        return o
+
+    def _traced(self, rc, f, st) -> dict:
+        """``Scene._traced`` for a render: its stats are ``last_stats`` as well"""
+        _, self.last_stats = Scene._traced(rc, f, None, st)
+        return self.last_stats
+
+    def render_buffers(self, scene: Scene, want_hdr: bool = True, want_rgba8: bool = True, flags: int = 0):
+        """The backend arm: (Renderer, &Scene) -> pixels.  Returns (hdr float32 [h,w,3] | None,
+        rgba8 uint8 [h,w,4] | None, stats dict)."""
+        o = self._mi355x()
         w, h = o.output_image_dimensions
         handle = scene.upload(o.device_id)
         opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, cull_margin=o.cull_margin, shading=o.shading)
@@ -1063,14 +1101,9 @@ class Renderer:  # renderer.rs:8-85
         """Many views of one scene in one launch (mipt_render_batch): `cameras` is a sequence of Camera (or CAMERA records), all
         rendered with this renderer's options.  View i equals render_buffers with cameras[i].  Returns (hdr float32 [n,h,w,3] |
         None, rgba8 uint8 [n,h,w,4] | None, stats dict of the one launch)."""
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
-        cams = [c.uniform if isinstance(c, Camera) else c for c in cameras]
-        if not cams:
-            raise ValueError("render_buffers_batch: no cameras")
-        table = np.ascontiguousarray(np.stack([np.asarray(c, dtype=L.CAMERA).reshape(()) for c in cams]))
-        n = len(cams)
+        o = self._mi355x()
+        table = _camera_table(list(cameras), "render_buffers_batch")
+        n = len(table)
         w, h = o.output_image_dimensions
         handle = scene.upload(o.device_id)
         opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, cull_margin=o.cull_margin, shading=o.shading)
@@ -1093,18 +1126,13 @@ class Renderer:  # renderer.rs:8-85
         ``device=True`` torch tensors of the same shapes on the scene's device (prim / material int32, the same bits), written on
         ``stream`` (a torch stream, a raw hipStream_t or None = torch's current stream).  ``handle``: another resident handle of the
         scene on ``options.device_id``, e.g. a replica of ``upload_multi``.  A stack overflow leaves the buffers written (stats["stack_overflows"] > 0)."""
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        o = self._mi355x()
         known = {name: (k, dt) for name, k, dt in L.FEATURES}
         names = list(features)
         if not names or len(set(names)) != len(names) or any(n not in known for n in names):
             raise ValueError(f"features: expected distinct names out of {', '.join(known)}; got {features!r}")
-        cams = [scene.camera] if cameras is None else list(cameras)
-        if not cams:
-            raise ValueError("render_features: no cameras")
-        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
-        n = len(cams)
+        table = _camera_table([scene.camera] if cameras is None else list(cameras), "render_features")
+        n = len(table)
         w, h = o.output_image_dimensions
         hnd = handle if handle is not None else scene.upload(o.device_id)
         opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, flags, cull_margin=o.cull_margin, shading=o.shading)
@@ -1117,24 +1145,17 @@ class Renderer:  # renderer.rs:8-85
             for name in names:
                 k, dt = known[name]
                 out[name] = torch.empty((n, h, w) + ((k,) if k > 1 else ()), dtype=torch.float32 if dt is np.float32 else torch.int32, device=dev)
-                setattr(bufs, name, out[name].data_ptr())
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            rc = lib.mipt_render_features_device(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), stream, C.byref(st))
-            where = "mipt_render_features_device"
+            _fill(bufs, **out)
+            f = lib.mipt_render_features_device
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), _stream_arg(stream, dev), C.byref(st))
         else:
             for name in names:
                 k, dt = known[name]
                 out[name] = np.zeros((n, h, w) + ((k,) if k > 1 else ()), dtype=dt)
-                setattr(bufs, name, out[name].ctypes.data)
-            rc = lib.mipt_render_features(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
-            where = "mipt_render_features"
-        if rc != L.ERR_STACK:
-            L.check(rc, where)
-        self.last_stats = st.as_dict()
-        return out, self.last_stats
+            _fill(bufs, **out)
+            f = lib.mipt_render_features
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
+        return out, self._traced(rc, f, st)
 
     def render_motion(self, scene: Scene, cameras=None, prev_tris=None, device: bool = False, stream=None, handle=None):
         """Previous positions (mipt_render_motion / _device): per pixel the world position that the first hit's surface point had in
@@ -1143,14 +1164,9 @@ class Renderer:  # renderer.rs:8-85
         a numpy array, which is copied to the device, a contiguous uint8 / float32 tensor of it or a raw device pointer), None = the
         generation the scene tracks (``Scene.track_motion``).  ``cameras``, ``device``, ``stream`` and ``handle`` as in
         ``render_features``.  Returns ([V,H,W,3] float32 array or tensor, stats)."""
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
-        cams = [scene.camera] if cameras is None else list(cameras)
-        if not cams:
-            raise ValueError("render_motion: no cameras")
-        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
-        n = len(cams)
+        o = self._mi355x()
+        table = _camera_table([scene.camera] if cameras is None else list(cameras), "render_motion")
+        n = len(table)
         w, h = o.output_image_dimensions
         keep = None
         if prev_tris is not None and not isinstance(prev_tris, int) and not Scene._is_torch(prev_tris):
@@ -1179,60 +1195,33 @@ class Renderer:  # renderer.rs:8-85
                 bufs.prev_tris, bufs.n_prev_tris = keep.data_ptr(), keep.numel() * keep.element_size() // L.TRIANGLE.itemsize
             out = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
             bufs.prev_position = out.data_ptr()
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
+            stream = _stream_arg(stream, dev)
             if keep is not None and stream != torch.cuda.current_stream(dev).cuda_stream:
                 torch.cuda.current_stream(dev).synchronize()      # the copy above ran on torch's stream
-            rc = lib.mipt_render_motion_device(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), stream, C.byref(st))
-            where = "mipt_render_motion_device"
+            f = lib.mipt_render_motion_device
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), stream, C.byref(st))
         else:
             if keep is not None:
                 bufs.prev_tris, bufs.n_prev_tris = keep.ctypes.data, len(keep)
             out = np.zeros((n, h, w, 3), dtype=np.float32)
             bufs.prev_position = out.ctypes.data
-            rc = lib.mipt_render_motion(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
-            where = "mipt_render_motion"
-        if rc != L.ERR_STACK:
-            L.check(rc, where)
-        self.last_stats = st.as_dict()
-        return out, self.last_stats
+            f = lib.mipt_render_motion
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), C.byref(bufs), C.byref(st))
+        return out, self._traced(rc, f, st)
 
     # -- a-trous denoiser (include/mipt.h "a-trous denoiser") ------------------------------------
     @staticmethod
     def _denoise_planes(hdr, normal, depth, albedo):
         """-> (torch?, (V, H, W), {name: contiguous float32 array or tensor}); ValueError naming the argument for anything else."""
-        torch_in = Scene._is_torch(hdr)
-        if not torch_in:
+        if not _is_torch(hdr):
             hdr = np.asarray(hdr)
         if hdr.ndim not in (3, 4) or hdr.shape[-1] != 3:
             raise ValueError(f"hdr: expected shape [V,H,W,3] or [H,W,3]; got {tuple(hdr.shape)}")
         lead = tuple(hdr.shape[:-1])
-        planes = {}
-        for name, a, want in (("hdr", hdr, lead + (3,)), ("normal", normal, lead + (3,)), ("depth", depth, lead), ("albedo", albedo, lead + (3,))):
-            if a is None:
-                continue
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: hdr and the guides must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                if a.dtype != torch.float32 or not a.is_cuda or a.device != hdr.device:
-                    raise ValueError(f"{name}: expected a float32 tensor on hdr's device {hdr.device}")
-                if tuple(a.shape) != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
-                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                planes[name] = a
-            else:
-                a = np.asarray(a)
-                if a.dtype != np.float32:
-                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
-                if a.shape != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
-                planes[name] = np.ascontiguousarray(a)
-        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
-        return torch_in, (v, h, w), planes
+        torch_in, planes = _check_planes("hdr", hdr, "hdr and the guides", [
+            ("hdr", hdr, lead + (3,), False), ("normal", normal, lead + (3,), False), ("depth", depth, lead, False),
+            ("albedo", albedo, lead + (3,), False)])
+        return torch_in, _views(lead), planes
 
     def denoise(self, hdr, normal=None, depth=None, albedo=None, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.5,
                 sigma_depth: float = 0.5, stream=None):
@@ -1250,27 +1239,13 @@ class Renderer:  # renderer.rs:8-85
         lib = L.load()
         if torch_in:
             import torch
-            dev = p["hdr"].device
             out = torch.empty_like(p["hdr"])
-            for name, a in p.items():
-                setattr(bufs, name, a.data_ptr())
-            bufs.out = out.data_ptr()
-            need = int(lib.mipt_denoise_workspace_bytes(w, h, v))
-            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [out, workspace]:
-                t.record_stream(s)
-            L.check(lib.mipt_denoise_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), "mipt_denoise_device")
+            touched = _fill(bufs, out=out, **p)
+            raw, ws = _stream_ordered(out.device, stream, touched, lib.mipt_denoise_workspace_bytes(w, h, v))
+            L.check(lib.mipt_denoise_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), ws.numel() * 4, raw), "mipt_denoise_device")
             return out
         out = np.empty_like(p["hdr"])
-        for name, a in p.items():
-            setattr(bufs, name, a.ctypes.data)
-        bufs.out = out.ctypes.data
+        _fill(bufs, out=out, **p)
         L.check(lib.mipt_denoise(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise")
         return out
 
@@ -1286,27 +1261,8 @@ class Renderer:  # renderer.rs:8-85
         Returns a new array / tensor of ``hdr``'s kind and shape, or with ``want_variance`` the pair (out, variance_out [..])."""
         torch_in, (v, h, w), p = self._denoise_planes(hdr, normal, depth, albedo)
         lead = tuple(p["hdr"].shape[:-1])
-        for name, a in (("variance", variance), ("length", length)):
-            if a is None:
-                continue
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: hdr, the guides, variance and length must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                if a.dtype != torch.float32 or not a.is_cuda or a.device != p["hdr"].device:
-                    raise ValueError(f"{name}: expected a float32 tensor on hdr's device {p['hdr'].device}")
-                if tuple(a.shape) != lead:
-                    raise ValueError(f"{name}: expected shape {lead}; got {tuple(a.shape)}")
-                if not a.is_contiguous():
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                p[name] = a
-            else:
-                a = np.asarray(a)
-                if a.dtype != np.float32:
-                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
-                if a.shape != lead:
-                    raise ValueError(f"{name}: expected shape {lead}; got {a.shape}")
-                p[name] = np.ascontiguousarray(a)
+        p.update(_check_planes("hdr", p["hdr"], "hdr, the guides, variance and length",
+                               [("variance", variance, lead, False), ("length", length, lead, False)])[1])
         opt = L.MiptVarianceOptions()
         opt.width, opt.height, opt.n_views, opt.iterations = w, h, v, iterations
         opt.sigma_luminance, opt.sigma_normal, opt.sigma_depth, opt.short_history = sigma_luminance, sigma_normal, sigma_depth, short_history
@@ -1314,35 +1270,17 @@ class Renderer:  # renderer.rs:8-85
         lib = L.load()
         if torch_in:
             import torch
-            dev = p["hdr"].device
             out = torch.empty_like(p["hdr"])
-            var_out = torch.empty(lead, dtype=torch.float32, device=dev) if want_variance else None
-            for name, a in p.items():
-                setattr(bufs, name, a.data_ptr())
-            bufs.out = out.data_ptr()
-            if want_variance:
-                bufs.variance_out = var_out.data_ptr()
-            need = int(lib.mipt_denoise_variance_workspace_bytes(w, h, v))
-            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [out, workspace] + ([var_out] if want_variance else []):
-                t.record_stream(s)
-            L.check(lib.mipt_denoise_variance_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream),
+            var_out = torch.empty(lead, dtype=torch.float32, device=out.device) if want_variance else None
+            touched = _fill(bufs, out=out, variance_out=var_out, **p)
+            raw, ws = _stream_ordered(out.device, stream, touched, lib.mipt_denoise_variance_workspace_bytes(w, h, v))
+            L.check(lib.mipt_denoise_variance_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), ws.numel() * 4, raw),
                     "mipt_denoise_variance_device")
-            return (out, var_out) if want_variance else out
-        out = np.empty_like(p["hdr"])
-        var_out = np.zeros(lead, dtype=np.float32) if want_variance else None
-        for name, a in p.items():
-            setattr(bufs, name, a.ctypes.data)
-        bufs.out = out.ctypes.data
-        if want_variance:
-            bufs.variance_out = var_out.ctypes.data
-        L.check(lib.mipt_denoise_variance(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise_variance")
+        else:
+            out = np.empty_like(p["hdr"])
+            var_out = np.zeros(lead, dtype=np.float32) if want_variance else None
+            _fill(bufs, out=out, variance_out=var_out, **p)
+            L.check(lib.mipt_denoise_variance(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_denoise_variance")
         return (out, var_out) if want_variance else out
 
     # -- guided upsampling (include/mipt.h "guided upsampling") ---------------------------------------
@@ -1351,8 +1289,7 @@ class Renderer:  # renderer.rs:8-85
     @staticmethod
     def _upsample_planes(lo_hdr, lo_guides, guides, scale):
         """-> (torch?, (V, H, W), {buffer field: contiguous array or tensor}); ValueError naming the argument for anything else."""
-        torch_in = Scene._is_torch(lo_hdr)
-        if not torch_in:
+        if not _is_torch(lo_hdr):
             lo_hdr = np.asarray(lo_hdr)
         if lo_hdr.ndim not in (3, 4) or lo_hdr.shape[-1] != 3:
             raise ValueError(f"lo_hdr: expected shape [V,h,w,3] or [h,w,3]; got {tuple(lo_hdr.shape)}")
@@ -1364,39 +1301,17 @@ class Renderer:  # renderer.rs:8-85
         lo_guides, guides = lo_guides or {}, guides or {}
         lo_lead = tuple(lo_hdr.shape[:-1])
         lead = lo_lead[:-2] + (lo_lead[-2] * scale, lo_lead[-1] * scale)
-        planes = {}
-        todo = [("lo_hdr", lo_hdr, lo_lead, 3, False)]
+        table = [("lo_hdr", lo_hdr, lo_lead + (3,), False)]
         for name, k in Renderer._UPSAMPLE_GUIDES:
             lo, hi = lo_guides.get(name), guides.get(name)
             if (lo is None) != (hi is None):
                 where = "guides" if lo is None else "lo_guides"
                 raise ValueError(f"{'lo_' + name if lo is None else name}: {name} is given at both resolutions or at neither; only {where} holds it")
             if lo is not None:
-                todo += [("lo_" + name, lo, lo_lead, k, name == "material"), (name, hi, lead, k, name == "material")]
-        for name, a, ld, k, ids in todo:
-            want = ld + ((k,) if k > 1 else ())
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: lo_hdr and the guides must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                dt = torch.int32 if ids else torch.float32
-                if a.dtype != dt or not a.is_cuda or a.device != lo_hdr.device:
-                    raise ValueError(f"{name}: expected a {str(dt).replace('torch.', '')} tensor on lo_hdr's device {lo_hdr.device}")
-                if tuple(a.shape) != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
-                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                planes[name] = a
-            else:
-                a = np.asarray(a)
-                dt = np.uint32 if ids else np.float32
-                if a.dtype != dt:
-                    raise ValueError(f"{name}: expected {np.dtype(dt).name}; got {a.dtype}")
-                if a.shape != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
-                planes[name] = np.ascontiguousarray(a)
-        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
-        return torch_in, (v, h, w), lead, planes
+                last = (k,) if k > 1 else ()
+                table += [("lo_" + name, lo, lo_lead + last, name == "material"), (name, hi, lead + last, name == "material")]
+        torch_in, planes = _check_planes("lo_hdr", lo_hdr, "lo_hdr and the guides", table)
+        return torch_in, _views(lead), lead, planes
 
     def upsample(self, lo_hdr, lo_guides, guides, scale, sigma_normal: float = 0.5, sigma_depth: float = 0.5, want_weight: bool = False,
                  stream=None):
@@ -1420,31 +1335,14 @@ class Renderer:  # renderer.rs:8-85
             dev = p["lo_hdr"].device
             out = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
             weight = torch.empty(lead, dtype=torch.float32, device=dev) if want_weight else None
-            for name, a in p.items():
-                setattr(bufs, name, a.data_ptr())
-            bufs.out = out.data_ptr()
-            if want_weight:
-                bufs.weight = weight.data_ptr()
-            need = int(lib.mipt_upsample_workspace_bytes(w, h, v, int(scale)))
-            workspace = torch.empty((max(need, 16) // 16, 4), dtype=torch.float32, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            # the passes are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [out, workspace] + ([weight] if want_weight else []):
-                t.record_stream(s)
-            L.check(lib.mipt_upsample_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), workspace.numel() * 4, stream), "mipt_upsample_device")
-            return (out, weight) if want_weight else out
-        out = np.empty(lead + (3,), dtype=np.float32)
-        weight = np.zeros(lead, dtype=np.float32) if want_weight else None
-        for name, a in p.items():
-            setattr(bufs, name, a.ctypes.data)
-        bufs.out = out.ctypes.data
-        if want_weight:
-            bufs.weight = weight.ctypes.data
-        L.check(lib.mipt_upsample(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_upsample")
+            touched = _fill(bufs, out=out, weight=weight, **p)
+            raw, ws = _stream_ordered(dev, stream, touched, lib.mipt_upsample_workspace_bytes(w, h, v, int(scale)))
+            L.check(lib.mipt_upsample_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), ws.numel() * 4, raw), "mipt_upsample_device")
+        else:
+            out = np.empty(lead + (3,), dtype=np.float32)
+            weight = np.zeros(lead, dtype=np.float32) if want_weight else None
+            _fill(bufs, out=out, weight=weight, **p)
+            L.check(lib.mipt_upsample(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_upsample")
         return (out, weight) if want_weight else out
 
     _FULL_FEATURES = ("depth", "normal", "albedo", "material")
@@ -1472,18 +1370,13 @@ class Renderer:  # renderer.rs:8-85
         features, features_full, stats): ``full`` [V,H,W,3] and the dict ``features_full`` at ``output_image_dimensions``, the other
         four as above at (W/k, H/k)."""
         import torch
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        o = self._mi355x()
         if upsample is not None:
             low = self._low_resolution(upsample, "render_denoised")
             u_args = {k[len("upsample_"):]: denoise_args.pop(k) for k in ("upsample_sigma_normal", "upsample_sigma_depth") if k in denoise_args}
-            stream = denoise_args.get("stream")
-            if stream is None:
-                stream = denoise_args["stream"] = torch.cuda.current_stream(torch.device("cuda", o.device_id))
+            raw = denoise_args["stream"] = _stream_arg(denoise_args.get("stream"), torch.device("cuda", o.device_id))
             denoised, noisy, features, stats = low._render_denoised_low(scene, cameras, variance, ("depth", "normal", "albedo", "material"), denoise_args)
             cams = [scene.camera] if cameras is None else list(cameras)
-            raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
             one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
             features_full, _ = one.render_features(scene, cams, self._FULL_FEATURES, device=True, stream=raw)
             full = self.upsample(denoised, features, features_full, upsample, stream=raw, **u_args)
@@ -1496,16 +1389,11 @@ class Renderer:  # renderer.rs:8-85
         import torch
         o = self.options
         cams = [scene.camera] if cameras is None else list(cameras)
-        if not cams:
-            raise ValueError("render_denoised: no cameras")
-        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        table = _camera_table(cams, "render_denoised")
         n = len(cams)
         w, h = o.output_image_dimensions
         dev = torch.device("cuda", o.device_id)
-        stream = denoise_args.pop("stream", None)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        raw = _stream_arg(denoise_args.pop("stream", None), dev)
         handle = scene.upload(o.device_id)
         opt = make_options(w, h, o.samples, o.max_ray_depth, o.seed_mode, o.traversal, cull_margin=o.cull_margin, shading=o.shading)
         noisy = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev)
@@ -1533,16 +1421,11 @@ class Renderer:  # renderer.rs:8-85
         records), None = the scene's camera.  ``flags``: FLAG_COUNT, FLAG_SUM and, with tensors and ``out``, FLAG_ACCUM.  ``out``: a
         float32 tensor [V,H,W,3] to write (to add to, under FLAG_ACCUM) instead of a new one.  ``handle`` as in ``render_features``.
         Returns (hdr [V,H,W,3] float32, rgba8 [V,H,W,4] uint8 | None, stats) as numpy arrays or tensors, after ``counts``' kind."""
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
-        cams = [scene.camera] if cameras is None else list(cameras)
-        if not cams:
-            raise ValueError("render_adaptive: no cameras")
-        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
-        n = len(cams)
+        o = self._mi355x()
+        table = _camera_table([scene.camera] if cameras is None else list(cameras), "render_adaptive")
+        n = len(table)
         w, h = o.output_image_dimensions
-        torch_in = Scene._is_torch(counts)
+        torch_in = _is_torch(counts)
         if not torch_in:
             counts = np.asarray(counts)
         if tuple(counts.shape) not in ((n, h, w), (h, w)) or (counts.ndim == 2 and n != 1):
@@ -1562,13 +1445,9 @@ class Renderer:  # renderer.rs:8-85
                       and tuple(out.shape) == (n, h, w, 3)):
                 raise ValueError(f"out: expected a contiguous float32 tensor of shape {(n, h, w, 3)} on {dev}")
             rgba = torch.empty((n, h, w, 4), dtype=torch.uint8, device=dev) if want_rgba8 else None
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            rc = lib.mipt_render_adaptive_device(hnd, L.ptr(table), n, C.byref(opt), counts.data_ptr(), out.data_ptr(),
-                                                 rgba.data_ptr() if want_rgba8 else None, stream, C.byref(st))
-            where, hdr = "mipt_render_adaptive_device", out
+            f, hdr = lib.mipt_render_adaptive_device, out
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), counts.data_ptr(), out.data_ptr(), rgba.data_ptr() if want_rgba8 else None,
+                   _stream_arg(stream, dev), C.byref(st))
         else:
             if out is not None:
                 raise ValueError("out: a tensor to write needs counts as a tensor")
@@ -1577,13 +1456,9 @@ class Renderer:  # renderer.rs:8-85
             counts = np.ascontiguousarray(counts)
             hdr = np.zeros((n, h, w, 3), dtype=np.float32)
             rgba = np.zeros((n, h, w, 4), dtype=np.uint8) if want_rgba8 else None
-            rc = lib.mipt_render_adaptive(hnd, L.ptr(table), n, C.byref(opt), L.ptr(counts), L.ptr(hdr), L.ptr(rgba) if want_rgba8 else None,
-                                          C.byref(st))
-            where = "mipt_render_adaptive"
-        if rc != L.ERR_STACK:
-            L.check(rc, where)
-        self.last_stats = st.as_dict()
-        return hdr, rgba, self.last_stats
+            f = lib.mipt_render_adaptive
+            rc = f(hnd, L.ptr(table), n, C.byref(opt), L.ptr(counts), L.ptr(hdr), L.ptr(rgba) if want_rgba8 else None, C.byref(st))
+        return hdr, rgba, self._traced(rc, f, st)
 
     def sample_map(self, variance, hdr=None, albedo=None, min_samples: int = 1, max_samples=None, budget=None, stream=None, rounds=None):
         """The sample map of include/mipt.h: a variance plane [V,H,W] or [H,W] float32 -- ``variance_out`` of ``denoise_variance``, or
@@ -1595,38 +1470,16 @@ class Renderer:  # renderer.rs:8-85
         stream, a raw hipStream_t or None = torch's current stream) without blocking and give an int32 tensor (the same bits).
         ``rounds`` (1 ... 8; None = the plain map) goes through mipt_sample_map_fill / _device instead: what the clamp at
         ``max_samples`` cuts off is handed on to the pixels below it, ``rounds`` - 1 times; ``rounds=1`` gives the plain map's counts."""
-        torch_in = Scene._is_torch(variance)
-        if not torch_in:
+        if not _is_torch(variance):
             variance = np.asarray(variance)
         if variance.ndim not in (2, 3):
             raise ValueError(f"variance: expected shape [V,H,W] or [H,W]; got {tuple(variance.shape)}")
         if albedo is not None and hdr is None:
             raise ValueError("albedo: given only with hdr")
         lead = tuple(variance.shape)
-        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
-        p = {}
-        for name, a, k in (("variance", variance, 1), ("hdr", hdr, 3), ("albedo", albedo, 3)):
-            if a is None:
-                continue
-            want = lead + ((k,) if k > 1 else ())
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: variance, hdr and albedo must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                if a.dtype != torch.float32 or not a.is_cuda or a.device != variance.device:
-                    raise ValueError(f"{name}: expected a float32 tensor on variance's device {variance.device}")
-                if tuple(a.shape) != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
-                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                p[name] = a
-            else:
-                a = np.asarray(a)
-                if a.dtype != np.float32:
-                    raise ValueError(f"{name}: expected float32; got {a.dtype}")
-                if a.shape != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
-                p[name] = np.ascontiguousarray(a)
+        v, h, w = _views(lead)
+        torch_in, p = _check_planes("variance", variance, "variance, hdr and albedo", [
+            ("variance", variance, lead, False), ("hdr", hdr, lead + (3,), False), ("albedo", albedo, lead + (3,), False)])
         opt = L.MiptSampleMapOptions() if rounds is None else L.MiptSampleMapFillOptions()
         if rounds is not None:
             opt.rounds = rounds
@@ -1637,30 +1490,17 @@ class Renderer:  # renderer.rs:8-85
         bufs, lib = L.MiptSampleMapBuffers(), L.load()
         if torch_in:
             import torch
-            dev = variance.device
-            counts = torch.empty(lead, dtype=torch.int32, device=dev)
-            for name, a in p.items():
-                setattr(bufs, name, a.data_ptr())
-            bufs.counts = counts.data_ptr()
+            counts = torch.empty(lead, dtype=torch.int32, device=variance.device)
+            touched = _fill(bufs, counts=counts, **p)
             need = lib.mipt_sample_map_workspace_bytes(w, h, v) if rounds is None else lib.mipt_sample_map_fill_workspace_bytes(w, h, v, rounds)
-            workspace = torch.empty((max(int(need), 16) // 16, 4), dtype=torch.float32, device=dev)   # an impossible size is the library's to refuse
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            # the launches are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [counts, workspace]:
-                t.record_stream(s)
+            raw, ws = _stream_ordered(variance.device, stream, touched, need)
             if rounds is None:
-                L.check(lib.mipt_sample_map_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_device")
+                L.check(lib.mipt_sample_map_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), raw), "mipt_sample_map_device")
             else:
-                L.check(lib.mipt_sample_map_fill_device(C.byref(opt), C.byref(bufs), workspace.data_ptr(), stream), "mipt_sample_map_fill_device")
+                L.check(lib.mipt_sample_map_fill_device(C.byref(opt), C.byref(bufs), ws.data_ptr(), raw), "mipt_sample_map_fill_device")
             return counts
         counts = np.zeros(lead, dtype=np.uint32)
-        for name, a in p.items():
-            setattr(bufs, name, a.ctypes.data)
-        bufs.counts = counts.ctypes.data
+        _fill(bufs, counts=counts, **p)
         if rounds is None:
             L.check(lib.mipt_sample_map(C.byref(opt), C.byref(bufs), self.options.device_id), "mipt_sample_map")
         else:
@@ -1673,44 +1513,19 @@ class Renderer:  # renderer.rs:8-85
     @staticmethod
     def _temporal_planes(hdr, features):
         """-> (torch?, (V, H, W), {name: contiguous array or tensor}); ValueError naming the argument for anything else."""
-        torch_in = Scene._is_torch(hdr)
-        if not torch_in:
+        if not _is_torch(hdr):
             hdr = np.asarray(hdr)
         if hdr.ndim not in (3, 4) or hdr.shape[-1] != 3:
             raise ValueError(f"hdr: expected shape [V,H,W,3] or [H,W,3]; got {tuple(hdr.shape)}")
         if not isinstance(features, dict):
             raise ValueError("features: expected a dict with position, normal, depth, material and optionally albedo")
         lead = tuple(hdr.shape[:-1])
-        planes = {}
-        for name, k, required in (("hdr", 3, True),) + Renderer._TEMPORAL_PLANES:
-            a = hdr if name == "hdr" else features.get(name)
-            if a is None:
-                if required:
-                    raise ValueError(f"{name}: features must hold it (render_features with position, normal, depth, material)")
-                continue
-            want = lead + ((k,) if k > 1 else ())
-            if Scene._is_torch(a) != torch_in:
-                raise ValueError(f"{name}: hdr and the features must all be numpy arrays or all torch tensors")
-            if torch_in:
-                import torch
-                dt = torch.int32 if name == "material" else torch.float32
-                if a.dtype != dt or not a.is_cuda or a.device != hdr.device:
-                    raise ValueError(f"{name}: expected a {str(dt).replace('torch.', '')} tensor on hdr's device {hdr.device}")
-                if tuple(a.shape) != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {tuple(a.shape)}")
-                if not a.is_contiguous():                   # a copy here would run on torch's current stream, not on `stream`
-                    raise ValueError(f"{name}: expected a contiguous tensor")
-                planes[name] = a
-            else:
-                a = np.asarray(a)
-                dt = np.uint32 if name == "material" else np.float32
-                if a.dtype != dt:
-                    raise ValueError(f"{name}: expected {np.dtype(dt).name}; got {a.dtype}")
-                if a.shape != want:
-                    raise ValueError(f"{name}: expected shape {want}; got {a.shape}")
-                planes[name] = np.ascontiguousarray(a)
-        v, h, w = ((1,) + lead) if len(lead) == 2 else lead
-        return torch_in, (v, h, w), planes
+        table = [("hdr", hdr, lead + (3,), False)]
+        table += [(name, features.get(name), lead + ((k,) if k > 1 else ()), name == "material") for name, k, _ in Renderer._TEMPORAL_PLANES]
+        torch_in, planes = _check_planes("hdr", hdr, "hdr and the features", table,
+                                         required=[name for name, _, must in Renderer._TEMPORAL_PLANES if must],
+                                         missing="features must hold it (render_features with position, normal, depth, material)")
+        return torch_in, _views(lead), planes
 
     def temporal(self, hdr, features, cameras, history=None, alpha_min: float = 0.0, max_history: float = 32.0, normal_tol: float = 0.1,
                  depth_tol: float = 0.1, want_length: bool = False, want_variance: bool = False, stream=None, history_out=None,
@@ -1733,7 +1548,7 @@ class Renderer:  # renderer.rs:8-85
         cams = list(cameras.reshape(-1)) if isinstance(cameras, np.ndarray) else ([cameras] if isinstance(cameras, Camera) else list(cameras))
         if len(cams) != v:
             raise ValueError(f"cameras: expected {v} cameras, one per view; got {len(cams)}")
-        table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+        table = _camera_table(cams)
         opt = L.MiptTemporalOptions()
         opt.width, opt.height, opt.n_views = w, h, v
         opt.alpha_min, opt.max_history, opt.normal_tol, opt.depth_tol = alpha_min, max_history, normal_tol, depth_tol
@@ -1741,13 +1556,13 @@ class Renderer:  # renderer.rs:8-85
         lib = L.load()
         words = max(int(lib.mipt_temporal_history_bytes(w, h, v)), 16) // 4          # an impossible size is left to the library to refuse
         lead = tuple(p["hdr"].shape[:-1])
-        extras = {}
+        want = (("length", want_length), ("variance", want_variance))
         if counts is None:
             if samples_cap is not None:
                 raise ValueError("samples_cap: given only with counts")
         else:
             samples_cap = self.options.samples if samples_cap is None else samples_cap
-            if Scene._is_torch(counts) != torch_in:
+            if _is_torch(counts) != torch_in:
                 raise ValueError("counts: hdr and counts must both be numpy arrays or both torch tensors")
             if not torch_in:
                 counts = np.asarray(counts)
@@ -1767,27 +1582,13 @@ class Renderer:  # renderer.rs:8-85
                     raise ValueError(f"{name}: expected a contiguous int32 tensor of {words} words on hdr's device {dev}")
             out = torch.empty_like(p["hdr"])
             new = history_out if history_out is not None else torch.empty((words,), dtype=torch.int32, device=dev)
-            for name, a in p.items():
-                setattr(bufs, name, a.data_ptr())
-            bufs.out, bufs.history_out = out.data_ptr(), new.data_ptr()
-            bufs.history_in = history.data_ptr() if history is not None else None
-            for name, on in (("length", want_length), ("variance", want_variance)):
-                if on:
-                    extras[name] = torch.empty(lead, dtype=torch.float32, device=dev)
-                    setattr(bufs, name, extras[name].data_ptr())
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            elif hasattr(stream, "cuda_stream"):
-                stream = stream.cuda_stream
-            # the launches are queued, not finished: tell torch's allocator that `stream` still uses these blocks
-            s = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
-            for t in list(p.values()) + [out, new] + list(extras.values()) + ([history] if history is not None else []) + (
-                    [counts] if counts is not None else []):
-                t.record_stream(s)
+            extras = {name: torch.empty(lead, dtype=torch.float32, device=dev) for name, on in want if on}
+            touched = _fill(bufs, out=out, history_in=history, history_out=new, **p, **extras)
+            raw, _ = _stream_ordered(dev, stream, touched + [counts])
             if counts is None:
-                L.check(lib.mipt_temporal_device(C.byref(opt), L.ptr(table), C.byref(bufs), stream), "mipt_temporal_device")
+                L.check(lib.mipt_temporal_device(C.byref(opt), L.ptr(table), C.byref(bufs), raw), "mipt_temporal_device")
             else:
-                L.check(lib.mipt_temporal_counts_device(C.byref(opt), L.ptr(table), C.byref(bufs), counts.data_ptr(), samples_cap, stream),
+                L.check(lib.mipt_temporal_counts_device(C.byref(opt), L.ptr(table), C.byref(bufs), counts.data_ptr(), samples_cap, raw),
                         "mipt_temporal_counts_device")
             return out, new, extras
         if history is not None:
@@ -1796,14 +1597,8 @@ class Renderer:  # renderer.rs:8-85
                 raise ValueError(f"history: expected a uint32 array of {words} words; got {history.dtype} of {history.size}")
         out = np.empty_like(p["hdr"])
         new = np.zeros(words, dtype=np.uint32)
-        for name, a in p.items():
-            setattr(bufs, name, a.ctypes.data)
-        bufs.out, bufs.history_out = out.ctypes.data, new.ctypes.data
-        bufs.history_in = history.ctypes.data if history is not None else None
-        for name, on in (("length", want_length), ("variance", want_variance)):
-            if on:
-                extras[name] = np.zeros(lead, dtype=np.float32)
-                setattr(bufs, name, extras[name].ctypes.data)
+        extras = {name: np.zeros(lead, dtype=np.float32) for name, on in want if on}
+        _fill(bufs, out=out, history_in=history, history_out=new, **p, **extras)
         if counts is None:
             L.check(lib.mipt_temporal(C.byref(opt), L.ptr(table), C.byref(bufs), self.options.device_id), "mipt_temporal")
         else:
@@ -1845,9 +1640,7 @@ class Renderer:  # renderer.rs:8-85
         number of SAMPLES, not of frames; ``rounds=R`` (1 ... 8) makes the map mipt_sample_map_fill_device, which hands on what the
         clamp at ``max_samples`` cuts off.  With neither key the call sequence is the one above, call for call."""
         import torch
-        o = self.options
-        if o.backend != RendererBackend.MI355X:
-            raise NotImplementedError(f"backend {o.backend.name} is not part of this build; use RendererBackend.MI355X")
+        o = self._mi355x()
         if adaptive is not None:
             if denoise != "variance":
                 raise ValueError("render_sequence: adaptive needs denoise=\"variance\": the sample map is made from the filter's variance_out")
@@ -1875,9 +1668,7 @@ class Renderer:  # renderer.rs:8-85
         t_args, d_args = {k: args[k] for k in t_names if k in args}, {k: args[k] for k in d_names if k in args}
         w, h = o.output_image_dimensions
         dev = torch.device("cuda", o.device_id)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        raw = _stream_arg(stream, dev)
         one = Renderer(RendererOptions(**{**o.__dict__, "samples": 1}))
         one_full = Renderer(RendererOptions(**{**self.options.__dict__, "samples": 1})) if upsample is not None else None
         lib = L.load()
@@ -1892,7 +1683,7 @@ class Renderer:  # renderer.rs:8-85
             cams = [cams] if isinstance(cams, (Camera, np.void)) or (isinstance(cams, np.ndarray) and cams.ndim == 0) else list(cams)
             if not cams or (n is not None and len(cams) != n):
                 raise ValueError(f"render_sequence: frame {frame} has {len(cams)} cameras; every frame needs the same number, at least 1")
-            table = np.ascontiguousarray(np.stack([np.asarray(c.uniform if isinstance(c, Camera) else c, dtype=L.CAMERA).reshape(()) for c in cams]))
+            table = _camera_table(cams)
             if n is None:
                 n = len(cams)
                 handle = scene.upload(o.device_id)
