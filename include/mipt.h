@@ -572,6 +572,108 @@ MIPT_API int mipt_lightmap_dilate(const MiptLightmapDilateOptions *opt, const Mi
 MIPT_API int mipt_lightmap_dilate_device(const MiptLightmapDilateOptions *opt, const MiptLightmapDilateBuffers *device, void *d_workspace,
                                          uint64_t workspace_bytes, void *hip_stream);
 
+/* ---- irradiance probes: SH coefficients of the light that arrives at a point, and their lookup ------------------------------------------
+ * What a lightmapped scene uses for everything that moves: a grid of probes, each holding the incoming radiance around its position
+ * projected onto real spherical harmonics up to band 2 (9 coefficients x RGB), and a lookup that blends the grid at a shaded point
+ * and convolves with the clamped cosine (Ramamoorthi-Hanrahan).  Kernels: csrc/probe.hip; the paths of the bake run in the ray
+ * kernel of the radiance queries, staged as mipt_bake_gather stages its own.  Every operator below is one rounded f32 operation,
+ * nothing is fused, and the operations run in the order written; tests/tools/probe_model.py restates them.
+ *
+ * The basis, for a direction (x, y, z), in the order (l, m) = (0,0) (1,-1) (1,0) (1,1) (2,-2) (2,-1) (2,0) (2,1) (2,2):
+ *     Y0 = 0.2820948f
+ *     Y1 = 0.48860252f * y            Y2 = 0.48860252f * z            Y3 = 0.48860252f * x
+ *     Y4 = 1.0925485f * (x * y)       Y5 = 1.0925485f * (y * z)       Y6 = 0.31539157f * ((3.0f * (z * z)) - 1.0f)
+ *     Y7 = 1.0925485f * (x * z)       Y8 = 0.54627424f * ((x * x) - (y * y))
+ * Each literal is the float nearest to its closed form: sqrt(1/4pi), sqrt(3/4pi), sqrt(15/4pi), sqrt(5/16pi), sqrt(15/16pi).
+ *
+ * mipt_probe_bake: probes -> coefficients.  MiptProbe = {x, y, z, seed}.  sh[i * 27 + k * 3 + c] is coefficient k of channel c of
+ * probe i.  Sample g = first_sample + s, s < samples, of probe i at P = (x, y, z) runs on a stream of its own:
+ *     rng = 987612486 * (seed + g * sample_stride + 87636354) mod 2^32, 1 in place of 0       (the gather's formula; all of it wraps)
+ *     d = rand_in_unit_sphere(rng)                           (vec3.rs:66-68: already a unit vector, used as given; uniform on the sphere)
+ *     L = trace(ray = (P, d), max_ray_depth, rng)            the origin is exactly P -- a probe lies on no surface, there is no offset --
+ *                                                            and the stream continues into the trace
+ * trace is Ray::trace (MIPT_SHADING_CPU) or rt_compute.wgsl's trace (MIPT_SHADING_WGPU), as in the radiance queries.
+ *     acc[k][c] = acc[k][c] + (L[c] * Y_k(d))                over the samples IN ORDER, from +0
+ *     sh[i][k][c] = (acc[k][c] / (float)samples) * 12.566371f        unless MIPT_FLAG_SUM is set: then acc[k][c] as it is
+ * 12.566371f is 4 pi: the estimate of the coefficient under the uniform pdf 1 / 4 pi.  MIPT_FLAG_ACCUM (device entry only, with
+ * MIPT_FLAG_SUM) follows the GATHER's rule, not the radiance query's: the ordered sums go on from the 27 words found in d_sh[i]
+ * and go back there, so any split of the samples into consecutive calls (first_sample 0 and 4 for 4 + 4, say) into zeros equals the
+ * single call bit for bit.  Each probe's 27 words depend on that probe and the options only -- never on i, on n or on how the work
+ * was scheduled.  NaN and inf -- a non-finite P, a NaN d from a degenerate draw -- are left as they are.
+ * Limit of precision: an ordered f32 sum stops gaining precision as the running sum approaches 2^24 times the typical term.  Keep
+ * one buffer to about 2^16 samples and average buffers beyond that; the entry accepts any `samples`, as the gather does.
+ * Options (required): MiptBakeOptions field for field.  stats (may be NULL), chunks (at most 2^22 paths; path q is sample q % samples
+ * of probe q / samples; a probe may span chunks, and one of more than 2^22 samples spans whole chunks) and staging (the gather's
+ * buffers of the scene plus two carry slots of 27 words): as mipt_bake_gather.
+ * Errors: the gather's list with `probes` for `points` and `sh` for `radiance` (d_probes 16-byte aligned, d_sh 4-byte aligned; n * 27
+ * floats); there is no prim, so no index check.  n == 0 is MIPT_OK without a launch.  MIPT_ERR_STACK is returned after all chunks
+ * have run and the results are written.  Both entries block until done, see the geometry of the last successful update and work on
+ * a mesh scene and on a replica handle.  After any error the scene renders, queries and bakes as before. */
+typedef struct { float x, y, z; uint32_t seed; } MiptProbe;   /* 16 B */
+typedef struct {
+    uint32_t samples;        /* > 0: paths per probe */
+    uint32_t max_ray_depth;  /* > 0 */
+    uint32_t traversal;      /* MiptTraversal */
+    float    cull_margin;    /* as MiptRadianceOptions */
+    uint32_t shading;        /* MiptShading */
+    uint32_t flags;          /* MIPT_FLAG_COUNT, MIPT_FLAG_SUM, MIPT_FLAG_ACCUM (device entry only, needs SUM) */
+    uint32_t first_sample;   /* g of this call's first sample */
+    uint32_t sample_stride;  /* > 0 */
+    uint32_t reserved[8];    /* must be 0 */
+} MiptProbeBakeOptions;     /* 64 B */
+MIPT_API int mipt_probe_bake(MiptScene *scene, const MiptProbe *probes, uint64_t n, const MiptProbeBakeOptions *opt,
+                             float *sh /* n*27 */, MiptStats *stats);
+MIPT_API int mipt_probe_bake_device(MiptScene *scene, const MiptProbe *d_probes, uint64_t n, const MiptProbeBakeOptions *opt,
+                                    float *d_sh /* n*27 */, void *hip_stream, MiptStats *stats);
+
+/* mipt_probe_irradiance: a grid of probes + points with normals -> irradiance.  Scene-free, like the denoiser and the lightmap
+ * operators: buffers in, a buffer out.  The grid has dims[0] x dims[1] x dims[2] probes; probe (ix, iy, iz) lies at
+ * origin + spacing * (ix, iy, iz) and has index (iz * dims[1] + iy) * dims[0] + ix.  Buffers:
+ *   sh          n_probes * 27 f32, required: what mipt_probe_bake wrote (the mean, not the sum)
+ *   valid       n_probes bytes, optional: 0 = the probe is left out of every blend (one the caller found inside a wall, say)
+ *   position    n * 3 f32, required
+ *   normal      n * 3 f32, required; used as given, not normalised
+ *   irradiance  n * 3 f32, required
+ * For query point p, per axis a:
+ *     g = (p_a - origin_a) / spacing_a;   g = 0 unless g >= 0 (a NaN gives 0);   g = min(g, (float)(dims_a - 1))
+ *     i0 = min((uint32_t)g, dims_a - 2) and f = g - (float)i0;   dims_a == 1: i0 = 0 and f = 0
+ *     w_a[0] = 1.0f - f     w_a[1] = f
+ * The eight corners (i0x + dx, i0y + dy, i0z + dz) are taken in the order dz * 4 + dy * 2 + dx = 0 ... 7, with weight
+ * w = (w_x[dx] * w_y[dy]) * w_z[dz].  A corner whose weight is exactly 0 or whose `valid` byte is 0 is SKIPPED: neither read nor
+ * added (a NaN probe behind a zero weight cannot leak; the corner beyond a one-probe axis is never addressed).  Over the kept
+ * corners, in that order and from +0:
+ *     b[k][c] = b[k][c] + (w * sh[probe][k][c])          wsum = wsum + w
+ * Then, with Y_k the basis above evaluated at the normal and A0 = 3.1415927f, A1 = 2.0943952f, A2 = 0.7853982f (pi, 2 pi / 3, pi / 4):
+ *     E[c] = ((A0 * (Y0 * b0)) + (A1 * (((Y1 * b1) + (Y2 * b2)) + (Y3 * b3))))
+ *            + (A2 * (((((Y4 * b4) + (Y5 * b5)) + (Y6 * b6)) + (Y7 * b7)) + (Y8 * b8)))             b_k = b[k][c]
+ * With a `valid` plane E[c] = E[c] / wsum, one division per channel, and +0 where wsum == 0 (every corner left out); without one
+ * there is no division (the weights of a cell sum to 1 up to rounding).  With MIPT_PROBE_CLAMP (a flag of the grid) E[c] =
+ * E[c] > 0 ? E[c] : +0 last of all (band-2 ringing can go negative; a NaN becomes 0).  Every point writes its three words and nothing
+ * else is touched; irradiance[i] depends on point i and the grid only.
+ * Errors, before any device work and in this order: a null grid or buffers; n >= 2^31; a null sh, position, normal or irradiance; a
+ * zero dimension; a product of dims >= 2^31; a spacing that is zero, negative or not finite; unknown flags; non-zero reserved words
+ * or pointers; irradiance overlapping an input; for the device entry a misaligned buffer (4 bytes; valid: any address) or one that
+ * is not memory of sh's device.  n == 0 is then MIPT_OK without a launch.  No workspace is needed: a lane per point. */
+#define MIPT_PROBE_CLAMP 1u
+typedef struct {
+    float    origin[3];
+    float    spacing[3];     /* finite and > 0 */
+    uint32_t dims[3];        /* > 0; their product < 2^31 */
+    uint32_t flags;          /* MIPT_PROBE_CLAMP */
+    uint32_t reserved[6];    /* must be 0 */
+} MiptProbeGrid;            /* 64 B */
+typedef struct {
+    const float   *sh;
+    const uint8_t *valid;                         /* NULL = every probe is valid */
+    const float   *position, *normal;
+    float         *irradiance;
+    void          *reserved[3];                   /* must be NULL */
+} MiptProbeIrradianceBuffers;   /* 64 B */
+/* HOST buffers, staged through memory of HIP device `device_id`; blocks until done. */
+MIPT_API int mipt_probe_irradiance(const MiptProbeGrid *grid, uint64_t n, const MiptProbeIrradianceBuffers *host, int device_id);
+/* DEVICE buffers of one device on `hip_stream`; stream-ordered, allocates nothing, writes `irradiance` and nothing else. */
+MIPT_API int mipt_probe_irradiance_device(const MiptProbeGrid *grid, uint64_t n, const MiptProbeIrradianceBuffers *device, void *hip_stream);
+
 /* ---- first-hit feature buffers: depth, ids, position, uv, normal, albedo, emission per pixel --------------------------------------
  * What the camera ray of every pixel hits and what the surface looks like there: the guide images of a denoiser, the id and depth
  * planes of a compositor, G-buffers for training data (csrc/first_hit.hip).  No path is traced: a sample ends at its first hit.

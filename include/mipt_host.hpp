@@ -176,6 +176,52 @@ inline int lightmap_dilate(uint32_t width, uint32_t height, const std::vector<fl
     return rc;
 }
 
+// mipt_probe_bake on any resident scene handle (include/mipt.h "irradiance probes"): sh[27 i + 3 k + c] is coefficient k of channel c
+// of the light that arrives at probes[i].  MIPT_ERR_STACK leaves the results written.
+inline int bake_probes_on(MiptScene *scene, const std::vector<MiptProbe> &probes, std::vector<float> &sh, const MiptProbeBakeOptions &opt,
+                          MiptStats *stats = nullptr) {
+    sh.assign(probes.size() * 27, 0.0f);
+    static const MiptProbe no_probe{};
+    static float no_value = 0.0f;
+    const int rc = mipt_probe_bake(scene, probes.empty() ? &no_probe : probes.data(), probes.size(), &opt, sh.empty() ? &no_value : sh.data(), stats);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+// The positions of a grid's probes in index order, (iz * dims[1] + iy) * dims[0] + ix: origin + spacing * index, one f32 product and
+// sum per coordinate; each probe's seed is its index, to go with sample_stride = the count.
+inline std::vector<MiptProbe> probe_grid(const MiptProbeGrid &grid) {
+    std::vector<MiptProbe> probes;
+    probes.reserve((size_t)grid.dims[0] * grid.dims[1] * grid.dims[2]);
+    for (uint32_t iz = 0; iz < grid.dims[2]; iz++)
+        for (uint32_t iy = 0; iy < grid.dims[1]; iy++)
+            for (uint32_t ix = 0; ix < grid.dims[0]; ix++)
+                probes.push_back({grid.origin[0] + grid.spacing[0] * (float)ix, grid.origin[1] + grid.spacing[1] * (float)iy,
+                                  grid.origin[2] + grid.spacing[2] * (float)iz, (uint32_t)probes.size()});
+    return probes;
+}
+// mipt_probe_irradiance over host buffers: `sh` 27 f32 per probe of `grid` (what bake_probes wrote for probe_grid(grid)), `position`
+// and `normal` 3 f32 per point, `valid` one byte per probe or empty = every probe counts.  `irradiance` is resized to 3 f32 per point.
+// A buffer of the wrong size is refused here with MIPT_ERR_INVALID_ARG.
+inline int probe_irradiance(const MiptProbeGrid &grid, const std::vector<float> &sh, const std::vector<float> &position, const std::vector<float> &normal,
+                            std::vector<float> &irradiance, const std::vector<uint8_t> &valid = {}, int device_id = 0) {
+    const uint64_t n_probes = (uint64_t)grid.dims[0] * grid.dims[1] * grid.dims[2];       // a product that wraps is the library's to refuse
+    if (position.size() % 3 != 0 || normal.size() != position.size() || sh.size() != n_probes * 27 || (!valid.empty() && valid.size() != n_probes)) {
+        log_error("probe_irradiance: sh holds 27 values and valid one byte per probe of the grid, position and normal 3 values per point");
+        return MIPT_ERR_INVALID_ARG;
+    }
+    irradiance.assign(position.size(), 0.0f);
+    static float no_value[3] = {0.0f, 0.0f, 0.0f};
+    MiptProbeIrradianceBuffers b{};
+    b.sh = sh.empty() ? &no_value[0] : sh.data();
+    b.valid = valid.empty() ? nullptr : valid.data();
+    b.position = position.empty() ? &no_value[0] : position.data();
+    b.normal = normal.empty() ? &no_value[1] : normal.data();
+    b.irradiance = irradiance.empty() ? &no_value[2] : irradiance.data();
+    const int rc = mipt_probe_irradiance(&grid, position.size() / 3, &b, device_id);
+    if (rc != MIPT_OK) log_error(mipt_last_error());
+    return rc;
+}
+
 // mipt_render_features on any resident scene handle: first-hit feature buffers (include/mipt.h "first-hit feature buffers") for
 // `cameras` with `opt`.  `wanted`: FeatureBit flags; only those images are computed and filled, each view-major [view][row][column][k]
 // with row 0 the top row; the others are left empty.  MIPT_ERR_STACK leaves the images written.
@@ -451,6 +497,11 @@ class Scene {                                              // src/scene.rs:12-19
     int bake_surface(const std::vector<MiptSurfacePoint> &points, std::vector<float> &position, std::vector<float> &normal, bool unit_normals = false) const {
         MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
         return m ? bake_surface_on(mipt_multi_scene(m, 0), points, position, normal, unit_normals) : MIPT_ERR_HIP;
+    }
+    // irradiance probes (mipt_probe_bake), on the same replica: 9 SH coefficients x RGB of the light that arrives at every probe
+    int bake_probes(const std::vector<MiptProbe> &probes, std::vector<float> &sh, const MiptProbeBakeOptions &opt, MiptStats *stats = nullptr) const {
+        MiptMulti *m = node_handle(multi_devices_ > 0 ? multi_devices_ : 1);
+        return m ? bake_probes_on(mipt_multi_scene(m, 0), probes, sh, opt, stats) : MIPT_ERR_HIP;
     }
 
   private:

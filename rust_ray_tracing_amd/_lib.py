@@ -166,6 +166,30 @@ assert C.sizeof(MiptBakeSurfaceOptions) == 32 and C.sizeof(MiptLightmapFilterOpt
 assert C.sizeof(MiptLightmapDilateOptions) == 32 and C.sizeof(MiptLightmapDilateBuffers) == 64
 
 
+# ---- irradiance probes (include/mipt.h "irradiance probes") ----
+PROBE = np.dtype([("position", "<f4", 3), ("seed", "<u4")])                                                   # MiptProbe
+assert PROBE.itemsize == 16
+PROBE_CLAMP = 1
+PROBE_SH_WORDS = 27
+
+
+class MiptProbeBakeOptions(C.Structure):
+    _fields_ = list(MiptBakeOptions._fields_)
+
+
+class MiptProbeGrid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 6)]
+
+
+class MiptProbeIrradianceBuffers(C.Structure):
+    _fields_ = [("sh", C.c_void_p), ("valid", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("irradiance", C.c_void_p),
+                ("reserved", C.c_void_p * 3)]
+
+
+assert C.sizeof(MiptProbeBakeOptions) == 64 and C.sizeof(MiptProbeGrid) == 64 and C.sizeof(MiptProbeIrradianceBuffers) == 64
+
+
 # ---- first-hit feature buffers (include/mipt.h "first-hit feature buffers") ----
 FEATURES = (("depth", 1, np.float32), ("prim", 1, np.uint32), ("material", 1, np.uint32), ("position", 3, np.float32),
             ("uv", 2, np.float32), ("normal", 3, np.float32), ("albedo", 3, np.float32), ("emission", 3, np.float32))   # name, values per pixel, type
@@ -327,6 +351,7 @@ EXPORTS = [
     "mipt_bake_surface", "mipt_bake_surface_device",
     "mipt_lightmap_filter_workspace_bytes", "mipt_lightmap_filter", "mipt_lightmap_filter_device",
     "mipt_lightmap_dilate_workspace_bytes", "mipt_lightmap_dilate", "mipt_lightmap_dilate_device",
+    "mipt_probe_bake", "mipt_probe_bake_device", "mipt_probe_irradiance", "mipt_probe_irradiance_device",
 ]
 
 _lib = None
@@ -483,6 +508,15 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.mipt_lightmap_dilate.restype = C.c_int
     lib.mipt_lightmap_dilate_device.argtypes = [ldo, ldb, vp, u64, vp]
     lib.mipt_lightmap_dilate_device.restype = C.c_int
+    pbo, pg, pib = C.POINTER(MiptProbeBakeOptions), C.POINTER(MiptProbeGrid), C.POINTER(MiptProbeIrradianceBuffers)
+    lib.mipt_probe_bake.argtypes = [vp, vp, u64, pbo, vp, C.POINTER(MiptStats)]
+    lib.mipt_probe_bake.restype = C.c_int
+    lib.mipt_probe_bake_device.argtypes = [vp, vp, u64, pbo, vp, vp, C.POINTER(MiptStats)]
+    lib.mipt_probe_bake_device.restype = C.c_int
+    lib.mipt_probe_irradiance.argtypes = [pg, u64, pib, C.c_int]
+    lib.mipt_probe_irradiance.restype = C.c_int
+    lib.mipt_probe_irradiance_device.argtypes = [pg, u64, pib, vp]
+    lib.mipt_probe_irradiance_device.restype = C.c_int
     fb = C.POINTER(MiptFeatureBuffers)
     lib.mipt_render_features.argtypes = [vp, vp, u32, C.POINTER(MiptOptions), fb, C.POINTER(MiptStats)]
     lib.mipt_render_features.restype = C.c_int

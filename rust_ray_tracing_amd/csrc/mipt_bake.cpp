@@ -18,7 +18,8 @@ namespace {
 
 using mipt::fail;
 
-constexpr uint64_t kChunkPaths = 1ull << 22;                     // paths per trace launch: 32 + 12 B of staging each
+using mipt::add_stats;
+using mipt::kChunkPaths;                                         // paths per trace launch: 32 + 12 B of staging each
 constexpr uint32_t kHugeCap = 8192;                              // triangles the grid-wide coverage kernel takes (bake.hip)
 
 // ---- texels ------------------------------------------------------------------------------------------------------------------------
@@ -88,14 +89,6 @@ int gather_check(const char *who, const MiptScene *scene, const void *points, ui
 int bad_prim(const char *who, uint64_t i, const MiptScene *scene) {
     return fail(MIPT_ERR_INVALID_ARG, "%s: points[%llu].prim names a triangle the scene does not have (%zu triangles)", who, (unsigned long long)i,
                 scene->n_tris);
-}
-
-void add_stats(MiptStats *sum, const MiptStats &c) {
-    sum->rays += c.rays; sum->inner_steps += c.inner_steps; sum->tri_tests += c.tri_tests; sum->hits += c.hits;
-    sum->texel_fetches += c.texel_fetches; sum->stack_overflows += c.stack_overflows; sum->tex_clamped += c.tex_clamped;
-    sum->pixels += c.pixels;
-    if (c.max_stack > sum->max_stack) sum->max_stack = c.max_stack;
-    for (size_t k = 0; k < sizeof sum->diag / sizeof sum->diag[0]; k++) sum->diag[k] += c.diag[k];
 }
 
 // the caller -> record map of the scene (d_bake_inv), made on first use and kept until the tree changes (release_geometry)

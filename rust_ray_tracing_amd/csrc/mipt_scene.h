@@ -75,6 +75,9 @@ struct MiptScene {
     mipt::DevBuf<float4> d_bake_rays;
     mipt::DevBuf<float> d_bake_path;
     mipt::DevPtr<uint32_t> d_bake_inv;
+    // irradiance probes (mipt_probe.cpp, probe.hip): a bake stages its rays and radiance in d_bake_rays / d_bake_path; the two carry
+    // slots of a probe that spans chunks, 27 running sums each
+    mipt::DevBuf<float> d_probe_carry;
     mipt::Event ev0, ev1;
     int n_cu = 0;
     uint32_t max_leaf = 0;
@@ -283,6 +286,17 @@ inline void stats_from_device(const DevStats &hs, float kernel_ms, MiptStats *st
 // chunk.  d_rays / d_radiance in HBM of the scene's device; blocks until done; MIPT_ERR_STACK with results and stats delivered.
 int radiance_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance, hipStream_t stream,
                     MiptStats *stats);
+
+// What the entries that trace in chunks share (mipt_bake.cpp: the gather; mipt_probe.cpp: the probe bake): the paths of one trace
+// launch -- 32 + 12 B of staging each -- and the sum of the chunks' counters (max_stack: their maximum; kernel_ms is the caller's).
+constexpr uint64_t kChunkPaths = 1ull << 22;
+inline void add_stats(MiptStats *sum, const MiptStats &c) {
+    sum->rays += c.rays; sum->inner_steps += c.inner_steps; sum->tri_tests += c.tri_tests; sum->hits += c.hits;
+    sum->texel_fetches += c.texel_fetches; sum->stack_overflows += c.stack_overflows; sum->tex_clamped += c.tex_clamped;
+    sum->pixels += c.pixels;
+    if (c.max_stack > sum->max_stack) sum->max_stack = c.max_stack;
+    for (size_t k = 0; k < sizeof sum->diag / sizeof sum->diag[0]; k++) sum->diag[k] += c.diag[k];
+}
 
 // ---- the first-hit passes (mipt_features.cpp: the feature buffers; mipt_motion.cpp: previous positions) ----
 // the checks that concern neither the buffers nor a device; `buffers` is only tested for null.  count_allowed: MIPT_FLAG_COUNT passes

@@ -196,6 +196,33 @@ struct DevLightmapDilate {
 // the pack pass, `radius` passes and the unpack pass, one launch each (stream-ordered; no allocation, no synchronisation inside)
 hipError_t launch_lightmap_dilate(const DevLightmapDilate &d, hipStream_t stream);
 
+// ---- irradiance probes (probe.hip; mipt_probe_bake* / mipt_probe_irradiance*) ----
+constexpr uint32_t kProbeCarryWords = 32;   // one carry slot: a probe's 27 running sums, padded
+struct ProbeBake {                          // one chunk of a probe bake: paths [first_path, first_path + n_paths) of n * samples
+    const float4 *probes;                   // all n records (MiptProbe): {x, y, z, seed}
+    unsigned long long first_path, n_paths;
+    uint32_t samples, first_sample, sample_stride;
+    uint32_t sum_only, accumulate;
+    float samples_f;
+    const float *carry_in;                  // 27 f32: the sums so far of the probe whose samples began in a chunk before
+    float *carry_out;                       // 27 f32: the sums so far of the probe whose samples go on in the next chunk
+};
+// rays[j] (n_paths x 32 B, MiptRay: origin P, direction d, the stream's state after the draws as its seed) for path first_path + j
+hipError_t launch_probe_rays(const ProbeBake &g, float4 *rays, int n_cu, hipStream_t stream);
+// path: n_paths x 3 f32, the chunk's traced radiance; rays: what launch_probe_rays wrote; sh: the caller's n x 27 f32
+hipError_t launch_probe_project(const ProbeBake &g, const float4 *rays, const float *path, float *sh, int n_cu, hipStream_t stream);
+struct DevProbeLookup {
+    const float *sh;                        // n_probes x 27
+    const uint8_t *valid;                   // n_probes, or NULL
+    const float *position, *normal;         // n x 3 each
+    float *irradiance;                      // n x 3
+    unsigned long long n;
+    float origin[3], spacing[3];
+    uint32_t dims[3];
+    uint32_t clamp;
+};
+hipError_t launch_probe_irradiance(const DevProbeLookup &d, int n_cu, hipStream_t stream);
+
 // ---- first-hit feature buffers (first_hit.hip; mipt_render_features*) ----
 struct PartRec;                             // pt_mesh_rule.h
 struct DevFeatures {

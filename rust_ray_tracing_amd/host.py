@@ -561,14 +561,16 @@ class Scene:  # scene.rs:12-19
         return np.ascontiguousarray(s).view(np.uint32)
 
     @staticmethod
-    def _radiance_out(accumulate_into, n: int, device, what: str):
-        """-> (the [n, 3] float32 result tensor of a device entry on ``device``, whether it is the caller's running sum)"""
+    def _radiance_out(accumulate_into, n: int, device, what: str, tail=(3,)):
+        """-> (the [n, 3] float32 result tensor of a device entry on ``device``, whether it is the caller's running sum); ``tail``:
+        what follows n in its shape ((9, 3) for the probes' coefficients)"""
         import torch
+        shape = (n,) + tuple(tail)
         if accumulate_into is None:
-            return torch.empty((n, 3), dtype=torch.float32, device=device), False
+            return torch.empty(shape, dtype=torch.float32, device=device), False
         out = accumulate_into
-        if not Scene._is_torch(out) or out.dtype != torch.float32 or out.shape != (n, 3) or out.device != device or not out.is_contiguous():
-            raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({n}, 3) on the {what}' device")
+        if not Scene._is_torch(out) or out.dtype != torch.float32 or out.shape != shape or out.device != device or not out.is_contiguous():
+            raise ValueError(f"accumulate_into: expected a contiguous float32 tensor of shape ({', '.join(map(str, shape))}) on the {what}' device")
         return out, True
 
     @staticmethod
@@ -954,6 +956,114 @@ class Scene:  # scene.rs:12-19
             if dilate:
                 rad = Scene.lightmap_dilate(rad, points, radius=dilate, device_id=device_id, stream=stream)
         return rad, covered, stats
+
+    # -- irradiance probes (include/mipt.h "irradiance probes") ----------------------------------------
+    def bake_probes(self, positions, seeds=None, samples: int = 64, max_ray_depth: int = 8, traversal: int = L.TRAVERSAL_REFERENCE,
+                    cull_margin: float = L.CULL_MARGIN_SAFE, shading: int = 0, first_sample: int = 0, sample_stride=None, sum: bool = False,
+                    accumulate_into=None, count: bool = False, stream=None, handle=None):
+        """The light that arrives at every probe from the whole sphere, projected onto real spherical harmonics up to band 2
+        (mipt_probe_bake / _device): ``samples`` paths per probe, each leaving the probe's position along rand_in_unit_sphere on a
+        stream seeded from the probe's seed and the sample's number ``first_sample + s``.  ``positions``: [n, 3] float32, a numpy
+        array (host entry) or a device tensor (device entry on ``stream``).  ``seeds``: n uint32, None = ``radiance_default_seeds``;
+        ``sample_stride``: None = n.  ``sum``: the ordered sums instead of the coefficients; ``accumulate_into``: a float32 device
+        tensor [n, 9, 3] the call's samples are added to (device positions only; implies ``sum``).  Returns (sh [n, 9, 3] float32
+        array or tensor -- coefficient k of channel c at [i, k, c] --, stats)."""
+        torch_in = _is_torch(positions)
+        if torch_in:
+            import torch
+            if positions.dtype != torch.float32 or positions.dim() != 2 or positions.shape[1] != 3 or not positions.is_cuda:
+                raise ValueError("positions: expected a float32 device tensor of shape (n, 3)")
+        else:
+            positions = np.asarray(positions)
+            if positions.dtype != np.float32 or positions.ndim != 2 or positions.shape[1] != 3:
+                raise ValueError("positions: expected a float32 array of shape (n, 3)")
+        h = self._resident(handle)
+        n = int(positions.shape[0])
+        s = self.radiance_default_seeds(n) if seeds is None else self._seeds(seeds, n)
+        opt = L.MiptProbeBakeOptions()
+        opt.samples, opt.max_ray_depth, opt.traversal, opt.cull_margin, opt.shading = samples, max_ray_depth, traversal, cull_margin, shading
+        opt.first_sample, opt.sample_stride = first_sample, (max(n, 1) if sample_stride is None else sample_stride)
+        opt.flags = (L.FLAG_COUNT if count else 0) | (L.FLAG_SUM if sum or accumulate_into is not None else 0)
+        st = L.MiptStats()
+        lib = L.load()
+        if not torch_in:
+            if accumulate_into is not None:
+                raise ValueError("accumulate_into needs device positions: the running sum lives in a device tensor")
+            r = np.zeros(n, dtype=L.PROBE)
+            r["position"], r["seed"] = positions, s
+            out = np.zeros((n, 9, 3), dtype=np.float32)
+            f = lib.mipt_probe_bake
+            rc = f(h, L.ptr(r) if n else C.c_void_p(16), n, C.byref(opt), L.ptr(out) if n else C.c_void_p(16), C.byref(st))
+        else:
+            r = torch.cat([positions, torch.from_numpy(s.view(np.int32)).to(positions.device).view(torch.float32).reshape(n, 1)], dim=1).contiguous()
+            out, accum = self._radiance_out(accumulate_into, n, r.device, "positions", tail=(9, 3))
+            opt.flags |= L.FLAG_ACCUM if accum else 0
+            f = lib.mipt_probe_bake_device
+            rc = f(h, r.data_ptr() if n else 16, n, C.byref(opt), out.data_ptr() if n else 16, self._stream_arg(stream, r.device), C.byref(st))
+        return self._traced(rc, f, out, st)
+
+    @staticmethod
+    def probe_grid(origin, spacing, dims) -> np.ndarray:
+        """The positions of a ``dims[0]`` x ``dims[1]`` x ``dims[2]`` probe grid in index order, (iz * dims[1] + iy) * dims[0] + ix:
+        origin + spacing * (ix, iy, iz), one f32 multiplication and addition per coordinate.  -> [n, 3] float32"""
+        o, sp = np.asarray(origin, dtype=np.float32), np.asarray(spacing, dtype=np.float32)
+        d = [int(x) for x in dims]
+        if o.shape != (3,) or sp.shape != (3,) or len(d) != 3 or min(d) < 1:
+            raise ValueError("probe_grid: expected origin [3], spacing [3] and three dimensions greater than 0")
+        iz, iy, ix = np.meshgrid(*(np.arange(k, dtype=np.float32) for k in (d[2], d[1], d[0])), indexing="ij")
+        return np.ascontiguousarray(o + sp * np.stack([ix, iy, iz], axis=-1).reshape(-1, 3))
+
+    @staticmethod
+    def probe_irradiance(sh, grid, position, normal, valid=None, clamp: bool = False, device_id: int = 0, stream=None):
+        """Irradiance at every point from a grid of baked probes (mipt_probe_irradiance / _device): the trilinear blend of the cell's
+        eight probes, then the clamped-cosine convolution at ``normal`` (used as given).  ``sh``: [n_probes, 9, 3] float32, what
+        ``bake_probes`` returns for ``probe_grid(*grid)``; ``grid``: (origin, spacing, dims); ``position``, ``normal``: [n, 3]
+        float32; ``valid``: n_probes uint8 (a bool array or tensor is taken as such), 0 = leave the probe out; ``clamp``: no negative
+        result.  numpy arrays go through the host entry on ``device_id``; device tensors through the device entry on ``stream``
+        without blocking.  Returns [n, 3] float32."""
+        origin, spacing, dims = grid
+        g = L.MiptProbeGrid()
+        g.origin[:], g.spacing[:], g.dims[:] = [float(x) for x in origin], [float(x) for x in spacing], [int(x) for x in dims]
+        g.flags = L.PROBE_CLAMP if clamp else 0
+        n_probes = int(g.dims[0]) * int(g.dims[1]) * int(g.dims[2])
+        if not _is_torch(position):
+            position = np.asarray(position)
+        if position.ndim != 2 or position.shape[1] != 3:
+            raise ValueError(f"position: expected shape [n,3]; got {tuple(position.shape)}")
+        n = int(position.shape[0])
+        torch_in, planes = _check_planes("position", position, "sh, position and normal",
+                                         [("position", position, (n, 3), False), ("normal", normal, (n, 3), False), ("sh", sh, (n_probes, 9, 3), False)],
+                                         flat=True, required=("normal", "sh"), missing="needed")
+        if valid is not None:
+            if _is_torch(valid) != torch_in:
+                raise ValueError("valid: sh, position and normal must all be numpy arrays or all torch tensors")
+            if torch_in:
+                import torch
+                if valid.dtype not in (torch.uint8, torch.bool) or valid.numel() != n_probes or valid.device != position.device or not valid.is_contiguous():
+                    raise ValueError(f"valid: expected {n_probes} contiguous uint8 or bool values on position's device")
+                valid = valid.view(torch.uint8)
+            else:
+                valid = np.asarray(valid)
+                if valid.dtype not in (np.dtype(np.uint8), np.dtype(bool)) or valid.size != n_probes:
+                    raise ValueError(f"valid: expected {n_probes} uint8 or bool values")
+                valid = np.ascontiguousarray(valid).view(np.uint8)
+        bufs = L.MiptProbeIrradianceBuffers()
+        lib = L.load()
+        if torch_in:
+            import torch
+            out = torch.empty((n, 3), dtype=torch.float32, device=position.device)
+            touched = _fill(bufs, irradiance=out, valid=valid, **planes)
+            raw, _ = _stream_ordered(position.device, stream, touched)
+            if n == 0:
+                bufs.position = bufs.normal = bufs.irradiance = 16
+            L.check(lib.mipt_probe_irradiance_device(C.byref(g), n, C.byref(bufs), raw), "mipt_probe_irradiance_device")
+            return out
+        out = np.zeros((n, 3), dtype=np.float32)
+        _fill(bufs, irradiance=out, valid=valid, **planes)
+        if n == 0:
+            bufs.position = bufs.normal = bufs.irradiance = 16
+        L.check(lib.mipt_probe_irradiance(C.byref(g), n, C.byref(bufs), device_id), "mipt_probe_irradiance")
+        return out
 
     def info(self, handle=None) -> dict:
         """MiptSceneInfo of the resident scene (sizes + what the setup took)."""
