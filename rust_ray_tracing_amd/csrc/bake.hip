@@ -4,6 +4,7 @@
 // way its surface faces (mipt_bake_surface*).  Every operator is one rounded f32 operation
 // (-ffp-contract=off, correctly rounded division and square root): tests/tools/bake_model.py restates the arithmetic in numpy.
 #include "pt_kernel.h"
+#include "chunk_paths.h"
 #include "pt_device_math.h"
 #include "../../include/mipt.h"
 
@@ -182,37 +183,38 @@ __global__ __launch_bounds__(kT) void check_points_kernel(const uint4 *points, u
     }
 }
 
-// Ray generation: a lane per path of the chunk.  Path q is sample q % samples of point q / samples (include/mipt.h "the sample").
-__global__ __launch_bounds__(kT) void bake_rays_kernel(DevScene sc, BakeGather g, float4 *rays) {
+// P and N of a surface point (include/mipt.h "mipt_bake_gather"), N turned round for a back face; false: no point, P and N untouched.
+// The one statement of them: the gather's rays and mipt_bake_surface start from the same bits.
+__device__ __forceinline__ bool surface_point(const DevScene &sc, const uint32_t *inv_order, const uint4 &pt, V3 &P, V3 &N) {
+    const uint32_t k = pt.w & 0x01ffffffu;
+    if (pt.w == MIPT_HIT_NONE || k >= sc.n_tris) return false;                            // (the entry has refused any other triangle)
+    const float4 *tp = sc.tri_pos + (size_t)inv_order[k] * 4;
+    const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
+    const uint32_t t = __float_as_uint(p2.y);                                              // the record's triangle in tree order: tri_attr's index
+    if (t >= sc.n_tris) return false;                                                     // (cannot be: the map was made from these records)
+    const float4 a0 = sc.tri_attr[(size_t)t * 4 + 0], a1 = sc.tri_attr[(size_t)t * 4 + 1], a2 = sc.tri_attr[(size_t)t * 4 + 2];
+    const float u = __uint_as_float(pt.y), v = __uint_as_float(pt.z);
+    P = (mk(p0.x, p0.y, p0.z) + mk(p0.w, p1.x, p1.y) * u) + mk(p1.z, p1.w, p2.x) * v;
+    const float w = (1.0f - u) - v;                                                       // ray.rs:45
+    N = (mk(a0.x, a0.y, a0.z) * w + mk(a0.w, a1.x, a1.y) * u) + mk(a1.z, a1.w, a2.x) * v;
+    if (!(pt.w & MIPT_HIT_FRONT_FACE)) N = mk(-N.x, -N.y, -N.z);                          // ray.rs:46-48
+    return true;
+}
+// no point: a ray whose slab tests all fail (every quotient a NaN), so it costs one step; the reduce kernel never reads it
+__device__ __forceinline__ void no_point_ray(float4 *ray) {
     const float qnan = __uint_as_float(0x7fc00000u);
-    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < g.n_paths; j += (unsigned long long)gridDim.x * kT) {
-        const unsigned long long q = g.first_path + j;
-        const unsigned long long p = q / g.samples;
-        const uint32_t s = (uint32_t)(q - p * g.samples);
-        const uint4 pt = g.points[p];
-        const uint32_t k = pt.w & 0x01ffffffu;
-        if (pt.w == MIPT_HIT_NONE || k >= sc.n_tris) {
-            // no point: a ray whose slab tests all fail (every quotient a NaN), so it costs one step; the reduce kernel never reads it
-            rays[j * 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            rays[j * 2 + 1] = make_float4(qnan, qnan, qnan, __uint_as_float(1u));
-            continue;
-        }
-        const float4 *tp = sc.tri_pos + (size_t)g.inv_order[k] * 4;
-        const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
-        const uint32_t t = __float_as_uint(p2.y);                                          // the record's triangle in tree order: tri_attr's index
-        if (t >= sc.n_tris) {                                                             // (cannot be: the map was made from these records)
-            rays[j * 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            rays[j * 2 + 1] = make_float4(qnan, qnan, qnan, __uint_as_float(1u));
-            continue;
-        }
-        const float4 a0 = sc.tri_attr[(size_t)t * 4 + 0], a1 = sc.tri_attr[(size_t)t * 4 + 1], a2 = sc.tri_attr[(size_t)t * 4 + 2];
-        const float u = __uint_as_float(pt.y), v = __uint_as_float(pt.z);
-        const V3 P = (mk(p0.x, p0.y, p0.z) + mk(p0.w, p1.x, p1.y) * u) + mk(p1.z, p1.w, p2.x) * v;
-        const float w = (1.0f - u) - v;                                                   // ray.rs:45
-        V3 N = (mk(a0.x, a0.y, a0.z) * w + mk(a0.w, a1.x, a1.y) * u) + mk(a1.z, a1.w, a2.x) * v;
-        if (!(pt.w & MIPT_HIT_FRONT_FACE)) N = mk(-N.x, -N.y, -N.z);                      // ray.rs:46-48
-        uint32_t rng = 987612486u * (pt.x + (g.first_sample + s) * g.sample_stride + 87636354u);   // cpu.rs:28-29, wrapping
-        if (rng == 0u) rng = 1u;
+    ray[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    ray[1] = make_float4(qnan, qnan, qnan, __uint_as_float(1u));
+}
+
+// Ray generation: a lane per path of the chunk.
+__global__ __launch_bounds__(kT) void bake_rays_kernel(DevScene sc, const uint4 *points, const uint32_t *inv_order, PathChunk c, float4 *rays) {
+    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < c.n_paths; j += (unsigned long long)gridDim.x * kT) {
+        const PathOf at = path_of(c.first_path, c.samples, j);
+        const uint4 pt = points[at.p];
+        V3 P, N;
+        if (!surface_point(sc, inv_order, pt, P, N)) { no_point_ray(rays + j * 2); continue; }
+        uint32_t rng = path_rng(pt.x, c.first_sample, c.sample_stride, at.s);
         const V3 rs = rand_in_unit_sphere(rng, GlTabGlobal());
         const V3 dir = normalized(N + rs);                                                // ray.rs:179-180
         const V3 o = P + dir * 0.0001f;                                                   // ray.rs:181
@@ -221,68 +223,44 @@ __global__ __launch_bounds__(kT) void bake_rays_kernel(DevScene sc, BakeGather g
     }
 }
 
-// The ordered sum: a lane per point that has a path in the chunk.  A point whose samples began in the chunk before goes on from
-// carry_in; one whose samples go on behind this chunk leaves its sum in carry_out (at most one point of each kind, and two slots).
-__global__ __launch_bounds__(kT) void bake_reduce_kernel(BakeGather g, const float *path, float *radiance) {
-    const unsigned long long last_path = g.first_path + g.n_paths;                        // one past
-    const unsigned long long p_first = g.first_path / g.samples, p_last = (last_path - 1ull) / g.samples;
-    const unsigned long long n = p_last - p_first + 1ull;
-    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < n; j += (unsigned long long)gridDim.x * kT) {
-        const unsigned long long p = p_first + j;
-        const unsigned long long begin = p * g.samples, end = begin + g.samples;
-        const unsigned long long q0 = begin > g.first_path ? begin : g.first_path, q1 = end < last_path ? end : last_path;
-        const bool none = g.points[p].w == MIPT_HIT_NONE;
+// The ordered sum: a lane per point that has a path in the chunk (chunk_paths.h: its span, and when it goes on from carry_in or
+// leaves its sum in carry_out).
+__global__ __launch_bounds__(kT) void bake_reduce_kernel(const uint4 *points, PathChunk c, const float *path, float *radiance) {
+    const ChunkItems items = chunk_items(c.first_path, c.n_paths, c.samples);
+    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < items.count; j += (unsigned long long)gridDim.x * kT) {
+        const unsigned long long p = items.p_first + j;
+        const ItemSpan sp = item_span(c.first_path, c.n_paths, c.samples, p);
+        const bool none = points[p].w == MIPT_HIT_NONE;
         float *dst = radiance + p * 3;
-        if (none && g.accumulate) continue;                                               // left untouched
+        if (none && c.accumulate) continue;                                               // left untouched
         float r = 0.0f, gr = 0.0f, b = 0.0f;
-        if (q0 != begin) { r = g.carry_in[0]; gr = g.carry_in[1]; b = g.carry_in[2]; }
-        else if (g.accumulate) { r = dst[0]; gr = dst[1]; b = dst[2]; }                   // the running sum goes on
+        if (sp.q0 != sp.begin) { r = c.carry_in[0]; gr = c.carry_in[1]; b = c.carry_in[2]; }
+        else if (c.accumulate) { r = dst[0]; gr = dst[1]; b = dst[2]; }                   // the running sum goes on
         if (!none) {
-            for (unsigned long long q = q0; q < q1; q++) {
-                const float *src = path + (q - g.first_path) * 3;
+            for (unsigned long long q = sp.q0; q < sp.q1; q++) {
+                const float *src = path + (q - c.first_path) * 3;
                 r = r + src[0]; gr = gr + src[1]; b = b + src[2];                        // cpu.rs:52
             }
         }
-        if (q1 != end) { g.carry_out[0] = r; g.carry_out[1] = gr; g.carry_out[2] = b; continue; }
-        if (!g.sum_only && !none) {
-            r = r / g.samples_f; gr = gr / g.samples_f; b = b / g.samples_f;             // cpu.rs:60
+        if (sp.q1 != sp.end) { c.carry_out[0] = r; c.carry_out[1] = gr; c.carry_out[2] = b; continue; }
+        if (!c.sum_only && !none) {
+            r = r / c.samples_f; gr = gr / c.samples_f; b = b / c.samples_f;             // cpu.rs:60
         }
         dst[0] = r; dst[1] = gr; dst[2] = b;
     }
 }
 
 // ---- surface -----------------------------------------------------------------------------------------------------------------------
-// A lane per point: P and N as bake_rays_kernel forms them (the same operations on the same operands: the same bits), N normalized
-// on request.  No point: +0.  Either output may be null.
+// A lane per point: P and N of surface_point, N normalized on request.  No point: +0.  Either output may be null.
 __global__ __launch_bounds__(kT) void bake_surface_kernel(DevScene sc, const uint4 *points, const uint32_t *inv_order, unsigned long long n,
                                                           uint32_t unit, float *position, float *normal) {
     for (unsigned long long i = (unsigned long long)blockIdx.x * kT + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * kT) {
         const uint4 pt = points[i];
-        const uint32_t k = pt.w & 0x01ffffffu;
         V3 P = mk(0.0f, 0.0f, 0.0f), N = mk(0.0f, 0.0f, 0.0f);
-        if (pt.w != MIPT_HIT_NONE && k < sc.n_tris) {                                     // (the entry has refused any other triangle)
-            const float4 *tp = sc.tri_pos + (size_t)inv_order[k] * 4;
-            const float4 p0 = tp[0], p1 = tp[1], p2 = tp[2];
-            const uint32_t t = __float_as_uint(p2.y);
-            if (t < sc.n_tris) {
-                const float4 a0 = sc.tri_attr[(size_t)t * 4 + 0], a1 = sc.tri_attr[(size_t)t * 4 + 1], a2 = sc.tri_attr[(size_t)t * 4 + 2];
-                const float u = __uint_as_float(pt.y), v = __uint_as_float(pt.z);
-                P = (mk(p0.x, p0.y, p0.z) + mk(p0.w, p1.x, p1.y) * u) + mk(p1.z, p1.w, p2.x) * v;
-                const float w = (1.0f - u) - v;                                           // ray.rs:45
-                N = (mk(a0.x, a0.y, a0.z) * w + mk(a0.w, a1.x, a1.y) * u) + mk(a1.z, a1.w, a2.x) * v;
-                if (!(pt.w & MIPT_HIT_FRONT_FACE)) N = mk(-N.x, -N.y, -N.z);              // ray.rs:46-48
-                if (unit) N = normalized(N);
-            }
-        }
+        if (surface_point(sc, inv_order, pt, P, N) && unit) N = normalized(N);
         if (position) { float *o = position + i * 3; o[0] = P.x; o[1] = P.y; o[2] = P.z; }
         if (normal) { float *o = normal + i * 3; o[0] = N.x; o[1] = N.y; o[2] = N.z; }
     }
-}
-
-uint32_t grid_for(unsigned long long work, int n_cu) {
-    unsigned long long blocks = (work + kT - 1) / kT, cap = (unsigned long long)(n_cu > 0 ? n_cu : 1) * 8ull;
-    if (blocks > cap) blocks = cap;
-    return (uint32_t)(blocks < 1 ? 1 : blocks);
 }
 
 } // namespace
@@ -299,15 +277,15 @@ hipError_t launch_bake_texels(const DevScene &sc, const uint32_t *tri_order, uin
     a.width_f = (float)width; a.height_f = (float)height;
     a.pad_x = 1.0f + (float)(width >> 19); a.pad_y = 1.0f + (float)(height >> 19);          // span()
     if (sc.n_tris) {
-        hipLaunchKernelGGL(cover_kernel, dim3(grid_for(sc.n_tris, n_cu)), dim3(kT), 0, stream, a);
+        hipLaunchKernelGGL(cover_kernel, dim3(grid_for(sc.n_tris, n_cu, kT)), dim3(kT), 0, stream, a);
         hipLaunchKernelGGL(cover_huge_kernel, dim3((uint32_t)(n_cu > 0 ? n_cu : 1) * 4u), dim3(kT), 0, stream, a);
     }
-    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(n, n_cu)), dim3(kT), 0, stream, a, reinterpret_cast<uint4 *>(points));
+    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(n, n_cu, kT)), dim3(kT), 0, stream, a, reinterpret_cast<uint4 *>(points));
     return hipGetLastError();
 }
 
 hipError_t launch_bake_invert_order(const DevScene &sc, const uint32_t *tri_order, uint32_t *inv, int n_cu, hipStream_t stream) {
-    hipLaunchKernelGGL(invert_order_kernel, dim3(grid_for(sc.n_tris, n_cu)), dim3(kT), 0, stream, sc.tri_pos, tri_order, sc.n_tris, inv);
+    hipLaunchKernelGGL(invert_order_kernel, dim3(grid_for(sc.n_tris, n_cu, kT)), dim3(kT), 0, stream, sc.tri_pos, tri_order, sc.n_tris, inv);
     return hipGetLastError();
 }
 
@@ -315,25 +293,27 @@ hipError_t launch_bake_check_points(const void *points, unsigned long long n, ui
     hipError_t e = hipMemsetAsync(ctl, 0, sizeof(BakeCtl), stream);
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(&ctl->bad_point, 0xff, sizeof(unsigned long long), stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(check_points_kernel, dim3(grid_for(n, n_cu)), dim3(kT), 0, stream, reinterpret_cast<const uint4 *>(points), n, n_tris, ctl);
+    hipLaunchKernelGGL(check_points_kernel, dim3(grid_for(n, n_cu, kT)), dim3(kT), 0, stream, reinterpret_cast<const uint4 *>(points), n, n_tris, ctl);
     return hipGetLastError();
 }
 
-hipError_t launch_bake_rays(const DevScene &sc, const BakeGather &g, float4 *rays, int n_cu, hipStream_t stream) {
-    hipLaunchKernelGGL(bake_rays_kernel, dim3(grid_for(g.n_paths, n_cu)), dim3(kT), 0, stream, sc, g, rays);
+hipError_t launch_bake_rays(const DevScene &sc, const void *points, const uint32_t *inv_order, const PathChunk &c, float4 *rays, int n_cu,
+                            hipStream_t stream) {
+    hipLaunchKernelGGL(bake_rays_kernel, dim3(grid_for(c.n_paths, n_cu, kT)), dim3(kT), 0, stream, sc, reinterpret_cast<const uint4 *>(points), inv_order, c,
+                       rays);
     return hipGetLastError();
 }
 
 hipError_t launch_bake_surface(const DevScene &sc, const void *points, const uint32_t *inv_order, unsigned long long n, bool unit,
                                float *position, float *normal, int n_cu, hipStream_t stream) {
-    hipLaunchKernelGGL(bake_surface_kernel, dim3(grid_for(n, n_cu)), dim3(kT), 0, stream, sc, reinterpret_cast<const uint4 *>(points), inv_order, n,
+    hipLaunchKernelGGL(bake_surface_kernel, dim3(grid_for(n, n_cu, kT)), dim3(kT), 0, stream, sc, reinterpret_cast<const uint4 *>(points), inv_order, n,
                        unit ? 1u : 0u, position, normal);
     return hipGetLastError();
 }
 
-hipError_t launch_bake_reduce(const BakeGather &g, const float *path, float *radiance, int n_cu, hipStream_t stream) {
-    const unsigned long long points = (g.first_path + g.n_paths - 1ull) / g.samples - g.first_path / g.samples + 1ull;
-    hipLaunchKernelGGL(bake_reduce_kernel, dim3(grid_for(points, n_cu)), dim3(kT), 0, stream, g, path, radiance);
+hipError_t launch_bake_reduce(const void *points, const PathChunk &c, const float *path, float *radiance, int n_cu, hipStream_t stream) {
+    hipLaunchKernelGGL(bake_reduce_kernel, dim3(grid_for(chunk_items(c.first_path, c.n_paths, c.samples).count, n_cu, kT)), dim3(kT), 0, stream,
+                       reinterpret_cast<const uint4 *>(points), c, path, radiance);
     return hipGetLastError();
 }
 

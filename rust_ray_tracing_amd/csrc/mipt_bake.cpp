@@ -18,8 +18,6 @@ namespace {
 
 using mipt::fail;
 
-using mipt::add_stats;
-using mipt::kChunkPaths;                                         // paths per trace launch: 32 + 12 B of staging each
 constexpr uint32_t kHugeCap = 8192;                              // triangles the grid-wide coverage kernel takes (bake.hip)
 
 // ---- texels ------------------------------------------------------------------------------------------------------------------------
@@ -75,15 +73,10 @@ int texels_host(MiptScene *scene, uint32_t width, uint32_t height, const MiptBak
 }
 
 // ---- gather ------------------------------------------------------------------------------------------------------------------------
-// everything that needs neither the scene's contents nor a device
 int gather_check(const char *who, const MiptScene *scene, const void *points, uint64_t n, const MiptBakeOptions *opt, const void *radiance,
                  bool device_entry) {
-    if (!scene || !points || !opt || !radiance) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, points, options or radiance", who);
-    int rc;
-    if ((rc = mipt::ray_count_check(who, "n", n)) || (rc = mipt::ray_sampling_check(who, opt->samples, opt->max_ray_depth))) return rc;
-    if (opt->sample_stride == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: sample_stride must be > 0 (every sample of a point would run on one stream)", who);
-    if ((rc = mipt::path_options_check(who, *opt))) return rc;
-    return mipt::accum_check(who, opt->flags, device_entry ? nullptr : "mipt_bake_gather_device");
+    return mipt::chunked_entry_check(who, !scene || !points || !opt || !radiance, "null scene, points, options or radiance", "point", n, opt,
+                                     device_entry ? nullptr : "mipt_bake_gather_device");
 }
 
 int bad_prim(const char *who, uint64_t i, const MiptScene *scene) {
@@ -126,49 +119,15 @@ int gather_launch(const char *who, MiptScene *scene, const MiptSurfacePoint *d_p
                   hipStream_t stream, bool check_prims, MiptStats *stats) {
     MIPT_HIP(hipSetDevice(scene->device));
     int rc;
-    const uint64_t total = n * opt->samples;                              // < 2^63: n < 2^31, samples < 2^32
-    const uint64_t chunk = total < kChunkPaths ? total : kChunkPaths;
-    if ((rc = scene->d_bake_ctl.grow(sizeof(mipt::BakeCtl)))) return rc;
-    if ((rc = scene->d_bake_rays.grow((size_t)chunk * sizeof(MiptRay)))) return rc;
-    if ((rc = scene->d_bake_path.grow((size_t)chunk * 12 + 32))) return rc;   // + the two carry slots
     if (check_prims && (rc = check_prims_device(who, scene, d_points, n, stream))) return rc;
     if ((rc = inverse_order(scene, stream))) return rc;
-    mipt::Event ev0, ev1;
-    MIPT_HIP(hipEventCreate(ev0.put()));
-    MIPT_HIP(hipEventCreate(ev1.put()));
-    MIPT_HIP(hipEventRecord(ev0.get(), stream));
-
-    MiptRadianceOptions ro{};
-    ro.samples = 1; ro.max_ray_depth = opt->max_ray_depth; ro.traversal = opt->traversal; ro.cull_margin = opt->cull_margin;
-    ro.shading = opt->shading; ro.flags = (opt->flags & MIPT_FLAG_COUNT) | MIPT_FLAG_SUM;
-    float *d_path = scene->d_bake_path, *d_carry = d_path + (size_t)chunk * 3;
-    mipt::BakeGather g{};
-    g.points = reinterpret_cast<const uint4 *>(d_points); g.inv_order = scene->d_bake_inv;
-    g.samples = opt->samples; g.first_sample = opt->first_sample; g.sample_stride = opt->sample_stride;
-    g.sum_only = (opt->flags & MIPT_FLAG_SUM) ? 1u : 0u; g.accumulate = (opt->flags & MIPT_FLAG_ACCUM) ? 1u : 0u;
-    g.samples_f = (float)opt->samples;                                    // cpu.rs:60
-    MiptStats sum{};
-    bool stack = false;
-    uint32_t slot = 0;
-    for (uint64_t first = 0; first < total; first += chunk, slot ^= 1u) {
-        g.first_path = first; g.n_paths = total - first < chunk ? total - first : chunk;
-        g.carry_in = d_carry + 4 * (slot ^ 1u); g.carry_out = d_carry + 4 * slot;
-        MIPT_HIP(mipt::launch_bake_rays(scene->dev, g, scene->d_bake_rays, scene->n_cu, stream));
-        MiptStats st;
-        rc = mipt::radiance_launch(scene, (const MiptRay *)scene->d_bake_rays.get(), g.n_paths, &ro, d_path, stream, &st);
-        if (rc && rc != MIPT_ERR_STACK) return rc;
-        stack = stack || rc == MIPT_ERR_STACK;
-        add_stats(&sum, st);
-        MIPT_HIP(mipt::launch_bake_reduce(g, d_path, d_radiance, scene->n_cu, stream));
-    }
-    MIPT_HIP(hipEventRecord(ev1.get(), stream));
-    MIPT_HIP(hipStreamSynchronize(stream));
-    float ms = 0.0f;
-    MIPT_HIP(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-    sum.kernel_ms = ms;
-    if (stats) *stats = sum;
-    if (stack) return mipt::stack_overflow_fail(sum.stack_overflows);
-    return MIPT_OK;
+    auto gen = [&](const mipt::PathChunk &c, float4 *d_rays, hipStream_t s) {
+        return mipt::launch_bake_rays(scene->dev, d_points, scene->d_bake_inv, c, d_rays, scene->n_cu, s);
+    };
+    auto fold = [&](const mipt::PathChunk &c, const float4 *, const float *d_path, hipStream_t s) {
+        return mipt::launch_bake_reduce(d_points, c, d_path, d_radiance, scene->n_cu, s);
+    };
+    return mipt::chunked_trace(scene, n, *opt, stream, stats, gen, fold);
 }
 
 int gather_device(MiptScene *scene, const MiptSurfacePoint *d_points, uint64_t n, const MiptBakeOptions *opt, float *d_radiance, void *hip_stream,

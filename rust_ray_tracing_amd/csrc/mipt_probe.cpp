@@ -1,7 +1,6 @@
 // mipt_probe.cpp -- the irradiance-probe entry points of include/mipt.h (mipt_probe_bake, mipt_probe_irradiance and their _device
-// forms): argument checks, the chunked staging of the bake around the ray kernel of the radiance queries (mipt::radiance_launch,
-// mipt_radiance.cpp) exactly as mipt_bake.cpp stages the gather, and the launches of probe.hip's kernels.  Host C++ only; every device
-// operation is stream-ordered HIP.
+// forms): argument checks and the launches of probe.hip's kernels; the bake traces in chunks through mipt::chunked_trace (mipt_scene.h),
+// as the gather of mipt_bake.cpp does.  Host C++ only; every device operation is stream-ordered HIP.
 #include "../../include/mipt.h"
 #include "pt_kernel.h"
 #include "mipt_scene.h"                                          // and with it mipt_host_util.h, mipt_internal.h
@@ -24,63 +23,20 @@ using mipt::fail;
 constexpr uint64_t kShWords = 27;                                // 9 coefficients x RGB per probe
 
 // ---- bake --------------------------------------------------------------------------------------------------------------------------
-// everything that needs neither the scene's contents nor a device
 int bake_check(const char *who, const MiptScene *scene, const void *probes, uint64_t n, const MiptProbeBakeOptions *opt, const void *sh,
                bool device_entry) {
-    if (!scene || !probes || !opt || !sh) return fail(MIPT_ERR_INVALID_ARG, "%s: null scene, probes, options or sh", who);
-    int rc;
-    if ((rc = mipt::ray_count_check(who, "n", n)) || (rc = mipt::ray_sampling_check(who, opt->samples, opt->max_ray_depth))) return rc;
-    if (opt->sample_stride == 0) return fail(MIPT_ERR_INVALID_ARG, "%s: sample_stride must be > 0 (every sample of a probe would run on one stream)", who);
-    if ((rc = mipt::path_options_check(who, *opt))) return rc;
-    return mipt::accum_check(who, opt->flags, device_entry ? nullptr : "mipt_probe_bake_device");
+    return mipt::chunked_entry_check(who, !scene || !probes || !opt || !sh, "null scene, probes, options or sh", "probe", n, opt,
+                                     device_entry ? nullptr : "mipt_probe_bake_device");
 }
 
 // The bake with every argument already checked; d_probes / d_sh in HBM of the scene's device, n > 0
 int bake_launch(MiptScene *scene, const MiptProbe *d_probes, uint64_t n, const MiptProbeBakeOptions *opt, float *d_sh, hipStream_t stream,
                 MiptStats *stats) {
-    MIPT_HIP(hipSetDevice(scene->device));
-    int rc;
-    const uint64_t total = n * opt->samples;                              // < 2^63: n < 2^31, samples < 2^32
-    const uint64_t chunk = total < mipt::kChunkPaths ? total : mipt::kChunkPaths;
-    if ((rc = scene->d_bake_rays.grow((size_t)chunk * sizeof(MiptRay)))) return rc;
-    if ((rc = scene->d_bake_path.grow((size_t)chunk * 12 + 32))) return rc;   // the gather's size: either entry finds what it needs
-    if ((rc = scene->d_probe_carry.grow(2 * mipt::kProbeCarryWords * sizeof(float)))) return rc;
-    mipt::Event ev0, ev1;
-    MIPT_HIP(hipEventCreate(ev0.put()));
-    MIPT_HIP(hipEventCreate(ev1.put()));
-    MIPT_HIP(hipEventRecord(ev0.get(), stream));
-
-    MiptRadianceOptions ro{};
-    ro.samples = 1; ro.max_ray_depth = opt->max_ray_depth; ro.traversal = opt->traversal; ro.cull_margin = opt->cull_margin;
-    ro.shading = opt->shading; ro.flags = (opt->flags & MIPT_FLAG_COUNT) | MIPT_FLAG_SUM;
-    float *d_path = scene->d_bake_path, *d_carry = scene->d_probe_carry;
-    mipt::ProbeBake g{};
-    g.probes = reinterpret_cast<const float4 *>(d_probes);
-    g.samples = opt->samples; g.first_sample = opt->first_sample; g.sample_stride = opt->sample_stride;
-    g.sum_only = (opt->flags & MIPT_FLAG_SUM) ? 1u : 0u; g.accumulate = (opt->flags & MIPT_FLAG_ACCUM) ? 1u : 0u;
-    g.samples_f = (float)opt->samples;
-    MiptStats sum{};
-    bool stack = false;
-    uint32_t slot = 0;
-    for (uint64_t first = 0; first < total; first += chunk, slot ^= 1u) {
-        g.first_path = first; g.n_paths = total - first < chunk ? total - first : chunk;
-        g.carry_in = d_carry + mipt::kProbeCarryWords * (slot ^ 1u); g.carry_out = d_carry + mipt::kProbeCarryWords * slot;
-        MIPT_HIP(mipt::launch_probe_rays(g, scene->d_bake_rays, scene->n_cu, stream));
-        MiptStats st;
-        rc = mipt::radiance_launch(scene, (const MiptRay *)scene->d_bake_rays.get(), g.n_paths, &ro, d_path, stream, &st);
-        if (rc && rc != MIPT_ERR_STACK) return rc;
-        stack = stack || rc == MIPT_ERR_STACK;
-        mipt::add_stats(&sum, st);
-        MIPT_HIP(mipt::launch_probe_project(g, scene->d_bake_rays, d_path, d_sh, scene->n_cu, stream));
-    }
-    MIPT_HIP(hipEventRecord(ev1.get(), stream));
-    MIPT_HIP(hipStreamSynchronize(stream));
-    float ms = 0.0f;
-    MIPT_HIP(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-    sum.kernel_ms = ms;
-    if (stats) *stats = sum;
-    if (stack) return mipt::stack_overflow_fail(sum.stack_overflows);
-    return MIPT_OK;
+    auto gen = [&](const mipt::PathChunk &c, float4 *d_rays, hipStream_t s) { return mipt::launch_probe_rays(d_probes, c, d_rays, scene->n_cu, s); };
+    auto fold = [&](const mipt::PathChunk &c, const float4 *d_rays, const float *d_path, hipStream_t s) {
+        return mipt::launch_probe_project(c, d_rays, d_path, d_sh, scene->n_cu, s);
+    };
+    return mipt::chunked_trace(scene, n, *opt, stream, stats, gen, fold);
 }
 
 int bake_device(MiptScene *scene, const MiptProbe *d_probes, uint64_t n, const MiptProbeBakeOptions *opt, float *d_sh, void *hip_stream,

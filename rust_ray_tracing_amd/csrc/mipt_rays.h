@@ -58,4 +58,19 @@ inline int accum_check(const char *who, uint32_t flags, const char *device_entry
     return MIPT_OK;
 }
 
+// The entries that trace n items x samples paths in chunks (mipt_bake_gather*: MiptBakeOptions; mipt_probe_bake*: MiptProbeBakeOptions,
+// field for field the same): everything that needs neither the scene's contents nor a device.  any_null / null_text: the entry's own
+// null test, `opt` among its pointers, and its message; noun: what the entry calls an item; device_entry: as accum_check takes it.
+template <class Options>
+int chunked_entry_check(const char *who, bool any_null, const char *null_text, const char *noun, uint64_t n, const Options *opt,
+                        const char *device_entry) {
+    if (any_null) return fail(MIPT_ERR_INVALID_ARG, "%s: %s", who, null_text);
+    int rc;
+    if ((rc = ray_count_check(who, "n", n)) || (rc = ray_sampling_check(who, opt->samples, opt->max_ray_depth))) return rc;
+    if (opt->sample_stride == 0)
+        return fail(MIPT_ERR_INVALID_ARG, "%s: sample_stride must be > 0 (every sample of a %s would run on one stream)", who, noun);
+    if ((rc = path_options_check(who, *opt))) return rc;
+    return accum_check(who, opt->flags, device_entry);
+}
+
 } // namespace mipt

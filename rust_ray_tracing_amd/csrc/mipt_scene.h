@@ -6,6 +6,7 @@
 // works on a scene's workspace.
 #pragma once
 #include "../../include/mipt.h"
+#include "chunk_paths.h"
 #include "mipt_host_util.h"
 #include "pt_kernel.h"
 
@@ -67,17 +68,18 @@ struct MiptScene {
     uint32_t list_used = 0;                 // entries that launch itself took, hot_used of them as "the hot pixels"
     mipt::DevBuf<void> d_qrays, d_qout;     // the host entries of the queries, radiance queries and bake: staging for items and results (mipt::staged_call)
     // baking (mipt_bake.cpp, bake.hip): the owner word per texel and the list of triangles the whole grid covers (mipt_bake_texels);
-    // the counters of a call; the map from the caller's triangle index to its tri_pos record, made on first use and dropped with the tree (release_geometry); the ray
-    // and radiance staging of a chunk of paths and the two carry slots of a point that spans chunks (mipt_bake_gather).  Grown on demand.
+    // the counters of a call; the map from the caller's triangle index to its tri_pos record, made on first use and dropped with the tree
+    // (release_geometry).  Grown on demand.
     mipt::DevBuf<unsigned long long> d_bake_owner;
     mipt::DevBuf<uint32_t> d_bake_huge;
     mipt::DevBuf<mipt::BakeCtl> d_bake_ctl;
+    mipt::DevPtr<uint32_t> d_bake_inv;
+    // the entries that trace in chunks (mipt_bake_gather*, mipt_probe_bake*), sized and handed out by mipt::chunked_trace (below) and
+    // by nothing else: the ray and radiance staging of one chunk, 32 and 12 B per path, and the two carry slots of an item that spans
+    // chunks, kCarrySlotWords each -- a point's 3 running sums or a probe's 27 in the first words of a slot
     mipt::DevBuf<float4> d_bake_rays;
     mipt::DevBuf<float> d_bake_path;
-    mipt::DevPtr<uint32_t> d_bake_inv;
-    // irradiance probes (mipt_probe.cpp, probe.hip): a bake stages its rays and radiance in d_bake_rays / d_bake_path; the two carry
-    // slots of a probe that spans chunks, 27 running sums each
-    mipt::DevBuf<float> d_probe_carry;
+    mipt::DevBuf<float> d_chunk_carry;
     mipt::Event ev0, ev1;
     int n_cu = 0;
     uint32_t max_leaf = 0;
@@ -188,7 +190,7 @@ inline int traversal_grid(MiptScene *scene, int blocks_per_cu, unsigned long lon
     return scene->d_ovf.grow(waves * (size_t)mipt::kStackOvf * 64 * sizeof(uint32_t));
 }
 
-// MIPT_ERR_STACK with the one text every launch that traces reports it in (traversal_launch; mipt_bake.cpp over its chunks)
+// MIPT_ERR_STACK with the one text every launch that traces reports it in (traversal_launch; chunked_trace over its chunks)
 inline int stack_overflow_fail(unsigned long long count) {
     return fail(MIPT_ERR_STACK, "traversal stack overflowed %llu times (capacity %d; the reference panics at 32, ray.rs:85)", count,
                 kStackLds + kStackOvf);
@@ -282,13 +284,14 @@ inline void stats_from_device(const DevStats &hs, float kernel_ms, MiptStats *st
     stats->diag[6] = hs.d_service_lanes; stats->diag[7] = hs.d_cycles_service; stats->diag[8] = hs.d_cycles_total; stats->diag[9] = hs.d_cycles_mem; stats->diag[10] = hs.d_cycles_tail;
 }
 
-// The trace launch of mipt_query_radiance_device with every argument already checked (mipt_radiance.cpp); mipt_bake.cpp runs it per
+// The trace launch of mipt_query_radiance_device with every argument already checked (mipt_radiance.cpp); chunked_trace runs it per
 // chunk.  d_rays / d_radiance in HBM of the scene's device; blocks until done; MIPT_ERR_STACK with results and stats delivered.
 int radiance_launch(MiptScene *scene, const MiptRay *d_rays, uint64_t n_rays, const MiptRadianceOptions *opt, float *d_radiance, hipStream_t stream,
                     MiptStats *stats);
 
-// What the entries that trace in chunks share (mipt_bake.cpp: the gather; mipt_probe.cpp: the probe bake): the paths of one trace
-// launch -- 32 + 12 B of staging each -- and the sum of the chunks' counters (max_stack: their maximum; kernel_ms is the caller's).
+// ---- the entries that trace in chunks (mipt_bake.cpp: the gather; mipt_probe.cpp: the probe bake) ----
+// The paths of one trace launch -- 32 + 12 B of staging each -- and the sum of the chunks' counters (max_stack: their maximum;
+// kernel_ms is chunked_trace's).
 constexpr uint64_t kChunkPaths = 1ull << 22;
 inline void add_stats(MiptStats *sum, const MiptStats &c) {
     sum->rays += c.rays; sum->inner_steps += c.inner_steps; sum->tri_tests += c.tri_tests; sum->hits += c.hits;
@@ -296,6 +299,60 @@ inline void add_stats(MiptStats *sum, const MiptStats &c) {
     sum->pixels += c.pixels;
     if (c.max_stack > sum->max_stack) sum->max_stack = c.max_stack;
     for (size_t k = 0; k < sizeof sum->diag / sizeof sum->diag[0]; k++) sum->diag[k] += c.diag[k];
+}
+
+// n items x opt.samples paths, n > 0 and every option checked (MiptBakeOptions or MiptProbeBakeOptions), in chunks of at most
+// kChunkPaths on `stream`: per chunk gen(chunk, d_rays, stream) writes the chunk's rays, radiance_launch traces them one sample
+// each, and fold(chunk, d_rays, d_path, stream) adds the traced radiance to the caller's result per item in sample order; both
+// return a hipError_t.  An item that straddles a chunk edge passes its running sums on through the scene's two carry slots
+// (chunk_paths.h: carry_slots).  Blocks until done; *stats (may be null) = the chunks' counters and the time from the first kernel
+// to the last; MIPT_ERR_STACK with results and stats delivered.
+template <class Options, class Gen, class Fold>
+int chunked_trace(MiptScene *scene, uint64_t n, const Options &opt, hipStream_t stream, MiptStats *stats, Gen gen, Fold fold) {
+    MIPT_HIP(hipSetDevice(scene->device));
+    int rc;
+    const uint64_t total = n * opt.samples;                               // < 2^63: n < 2^31, samples < 2^32
+    const uint64_t chunk = total < kChunkPaths ? total : kChunkPaths;
+    if ((rc = scene->d_bake_rays.grow((size_t)chunk * sizeof(MiptRay)))) return rc;
+    if ((rc = scene->d_bake_path.grow((size_t)chunk * 12))) return rc;
+    if ((rc = scene->d_chunk_carry.grow(2 * kCarrySlotWords * sizeof(float)))) return rc;
+    Event ev0, ev1;
+    MIPT_HIP(hipEventCreate(ev0.put()));
+    MIPT_HIP(hipEventCreate(ev1.put()));
+    MIPT_HIP(hipEventRecord(ev0.get(), stream));
+
+    MiptRadianceOptions ro{};
+    ro.samples = 1; ro.max_ray_depth = opt.max_ray_depth; ro.traversal = opt.traversal; ro.cull_margin = opt.cull_margin;
+    ro.shading = opt.shading; ro.flags = (opt.flags & MIPT_FLAG_COUNT) | MIPT_FLAG_SUM;
+    float4 *d_rays = scene->d_bake_rays;
+    float *d_path = scene->d_bake_path, *d_carry = scene->d_chunk_carry;
+    PathChunk c{};
+    c.samples = opt.samples; c.first_sample = opt.first_sample; c.sample_stride = opt.sample_stride;
+    c.sum_only = (opt.flags & MIPT_FLAG_SUM) ? 1u : 0u; c.accumulate = (opt.flags & MIPT_FLAG_ACCUM) ? 1u : 0u;
+    c.samples_f = (float)opt.samples;                                     // cpu.rs:60
+    MiptStats sum{};
+    bool stack = false;
+    uint64_t index = 0;
+    for (uint64_t first = 0; first < total; first += chunk, index++) {
+        c.first_path = first; c.n_paths = total - first < chunk ? total - first : chunk;
+        const CarrySlots slots = carry_slots(index);                      // chunk_paths.h
+        c.carry_in = d_carry + kCarrySlotWords * slots.in; c.carry_out = d_carry + kCarrySlotWords * slots.out;
+        MIPT_HIP(gen(c, d_rays, stream));
+        MiptStats st;
+        rc = radiance_launch(scene, (const MiptRay *)d_rays, c.n_paths, &ro, d_path, stream, &st);
+        if (rc && rc != MIPT_ERR_STACK) return rc;
+        stack = stack || rc == MIPT_ERR_STACK;
+        add_stats(&sum, st);
+        MIPT_HIP(fold(c, d_rays, d_path, stream));
+    }
+    MIPT_HIP(hipEventRecord(ev1.get(), stream));
+    MIPT_HIP(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    MIPT_HIP(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+    sum.kernel_ms = ms;
+    if (stats) *stats = sum;
+    if (stack) return stack_overflow_fail(sum.stack_overflows);
+    return MIPT_OK;
 }
 
 // ---- the first-hit passes (mipt_features.cpp: the feature buffers; mipt_motion.cpp: previous positions) ----

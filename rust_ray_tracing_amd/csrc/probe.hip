@@ -4,6 +4,7 @@
 // cosine (mipt_probe_irradiance*).  Every operator is one rounded f32 operation (-ffp-contract=off, correctly rounded division):
 // tests/tools/probe_model.py restates the arithmetic in numpy.
 #include "pt_kernel.h"
+#include "chunk_paths.h"
 #include "pt_device_math.h"
 #include "../../include/mipt.h"
 
@@ -28,15 +29,12 @@ __device__ __forceinline__ float sh_basis(uint32_t k, float x, float y, float z)
     }
 }
 
-// Ray generation: a lane per path of the chunk.  Path q is sample q % samples of probe q / samples (include/mipt.h "mipt_probe_bake").
-__global__ __launch_bounds__(kT) void probe_rays_kernel(ProbeBake g, float4 *rays) {
-    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < g.n_paths; j += (unsigned long long)gridDim.x * kT) {
-        const unsigned long long q = g.first_path + j;
-        const unsigned long long p = q / g.samples;
-        const uint32_t s = (uint32_t)(q - p * g.samples);
-        const float4 pr = g.probes[p];
-        uint32_t rng = 987612486u * (__float_as_uint(pr.w) + (g.first_sample + s) * g.sample_stride + 87636354u);   // cpu.rs:28-29, wrapping
-        if (rng == 0u) rng = 1u;
+// Ray generation: a lane per path of the chunk (include/mipt.h "mipt_probe_bake").
+__global__ __launch_bounds__(kT) void probe_rays_kernel(const float4 *probes, PathChunk c, float4 *rays) {
+    for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < c.n_paths; j += (unsigned long long)gridDim.x * kT) {
+        const PathOf at = path_of(c.first_path, c.samples, j);
+        const float4 pr = probes[at.p];
+        uint32_t rng = path_rng(__float_as_uint(pr.w), c.first_sample, c.sample_stride, at.s);
         const V3 d = rand_in_unit_sphere(rng, GlTabGlobal());                             // vec3.rs:66-68: a unit vector, used as given
         rays[j * 2] = make_float4(pr.x, pr.y, pr.z, 0.0f);                                // the origin is the probe: no offset
         rays[j * 2 + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(rng));
@@ -47,28 +45,25 @@ __global__ __launch_bounds__(kT) void probe_rays_kernel(ProbeBake g, float4 *ray
 // a probe are independent of each other, so nine lanes walk the probe's samples side by side.  Lanes are handed out as
 // [group of 64 probes][k][probe of the group]: k is the same for a whole wave, so the basis function is a scalar branch.  The walk
 // itself is serial -- the sum is ordered -- and bound by the latency of its loads: kBatch samples are fetched before they are added,
-// in order.  A probe whose samples began in a chunk before goes on from carry_in; one whose samples go on behind this chunk leaves
-// its sums in carry_out (at most one probe of each kind -- the same one where a chunk lies inside a probe --, and two slots).
+// in order.  chunk_paths.h: a probe's span, and when it goes on from carry_in or leaves its sums in carry_out.
 constexpr int kBatch = 16;
-__global__ __launch_bounds__(kT) void probe_project_kernel(ProbeBake g, const float4 *rays, const float *path, float *sh) {
-    const unsigned long long last_path = g.first_path + g.n_paths;                        // one past
-    const unsigned long long p_first = g.first_path / g.samples, p_last = (last_path - 1ull) / g.samples;
-    const unsigned long long n_probes = p_last - p_first + 1ull;
-    const unsigned long long n = ((n_probes + 63ull) / 64ull) * (9ull * 64ull);
+__host__ __device__ inline unsigned long long project_lanes(unsigned long long n_probes) { return ((n_probes + 63ull) / 64ull) * (9ull * 64ull); }   // kernel and launcher
+__global__ __launch_bounds__(kT) void probe_project_kernel(PathChunk c, const float4 *rays, const float *path, float *sh) {
+    const ChunkItems items = chunk_items(c.first_path, c.n_paths, c.samples);
+    const unsigned long long n = project_lanes(items.count);
     for (unsigned long long j = (unsigned long long)blockIdx.x * kT + threadIdx.x; j < n; j += (unsigned long long)gridDim.x * kT) {
         const unsigned long long local = (j / (9ull * 64ull)) * 64ull + (j & 63ull);
         const uint32_t k = (uint32_t)((j / 64ull) % 9ull);                                // wave-uniform: kT and the stride are multiples of 64
-        if (local >= n_probes) continue;
-        const unsigned long long p = p_first + local;
-        const unsigned long long begin = p * g.samples, end = begin + g.samples;
-        const unsigned long long q0 = begin > g.first_path ? begin : g.first_path, q1 = end < last_path ? end : last_path;
+        if (local >= items.count) continue;
+        const unsigned long long p = items.p_first + local;
+        const ItemSpan sp = item_span(c.first_path, c.n_paths, c.samples, p);
         float *dst = sh + p * 27ull + k * 3u;
         float r = 0.0f, gr = 0.0f, b = 0.0f;
-        if (q0 != begin) { r = g.carry_in[k * 3u]; gr = g.carry_in[k * 3u + 1u]; b = g.carry_in[k * 3u + 2u]; }
-        else if (g.accumulate) { r = dst[0]; gr = dst[1]; b = dst[2]; }                   // the running sums go on
-        const float4 *ray = rays + (q0 - g.first_path) * 2ull + 1ull;                     // the direction half of the record
-        const float *src = path + (q0 - g.first_path) * 3ull;
-        unsigned long long left = q1 - q0;
+        if (sp.q0 != sp.begin) { r = c.carry_in[k * 3u]; gr = c.carry_in[k * 3u + 1u]; b = c.carry_in[k * 3u + 2u]; }
+        else if (c.accumulate) { r = dst[0]; gr = dst[1]; b = dst[2]; }                   // the running sums go on
+        const float4 *ray = rays + (sp.q0 - c.first_path) * 2ull + 1ull;                  // the direction half of the record
+        const float *src = path + (sp.q0 - c.first_path) * 3ull;
+        unsigned long long left = sp.q1 - sp.q0;
         for (; left >= (unsigned long long)kBatch; left -= kBatch, ray += 2 * kBatch, src += 3 * kBatch) {
             float4 d[kBatch];
             float l[kBatch][3];
@@ -85,9 +80,9 @@ __global__ __launch_bounds__(kT) void probe_project_kernel(ProbeBake g, const fl
             const float y = sh_basis(k, d.x, d.y, d.z);
             r = r + (src[0] * y); gr = gr + (src[1] * y); b = b + (src[2] * y);
         }
-        if (q1 != end) { g.carry_out[k * 3u] = r; g.carry_out[k * 3u + 1u] = gr; g.carry_out[k * 3u + 2u] = b; continue; }
-        if (!g.sum_only) {
-            r = (r / g.samples_f) * 12.566371f; gr = (gr / g.samples_f) * 12.566371f; b = (b / g.samples_f) * 12.566371f;
+        if (sp.q1 != sp.end) { c.carry_out[k * 3u] = r; c.carry_out[k * 3u + 1u] = gr; c.carry_out[k * 3u + 2u] = b; continue; }
+        if (!c.sum_only) {
+            r = (r / c.samples_f) * 12.566371f; gr = (gr / c.samples_f) * 12.566371f; b = (b / c.samples_f) * 12.566371f;
         }
         dst[0] = r; dst[1] = gr; dst[2] = b;
     }
@@ -152,27 +147,21 @@ __global__ __launch_bounds__(kT) void probe_irradiance_kernel(DevProbeLookup a) 
     }
 }
 
-uint32_t grid_for(unsigned long long work, int n_cu) {
-    unsigned long long blocks = (work + kT - 1) / kT, cap = (unsigned long long)(n_cu > 0 ? n_cu : 1) * 8ull;
-    if (blocks > cap) blocks = cap;
-    return (uint32_t)(blocks < 1 ? 1 : blocks);
-}
-
 } // namespace
 
-hipError_t launch_probe_rays(const ProbeBake &g, float4 *rays, int n_cu, hipStream_t stream) {
-    hipLaunchKernelGGL(probe_rays_kernel, dim3(grid_for(g.n_paths, n_cu)), dim3(kT), 0, stream, g, rays);
+hipError_t launch_probe_rays(const void *probes, const PathChunk &c, float4 *rays, int n_cu, hipStream_t stream) {
+    hipLaunchKernelGGL(probe_rays_kernel, dim3(grid_for(c.n_paths, n_cu, kT)), dim3(kT), 0, stream, reinterpret_cast<const float4 *>(probes), c, rays);
     return hipGetLastError();
 }
 
-hipError_t launch_probe_project(const ProbeBake &g, const float4 *rays, const float *path, float *sh, int n_cu, hipStream_t stream) {
-    const unsigned long long probes = (g.first_path + g.n_paths - 1ull) / g.samples - g.first_path / g.samples + 1ull;
-    hipLaunchKernelGGL(probe_project_kernel, dim3(grid_for(((probes + 63ull) / 64ull) * (9ull * 64ull), n_cu)), dim3(kT), 0, stream, g, rays, path, sh);
+hipError_t launch_probe_project(const PathChunk &c, const float4 *rays, const float *path, float *sh, int n_cu, hipStream_t stream) {
+    const unsigned long long lanes = project_lanes(chunk_items(c.first_path, c.n_paths, c.samples).count);
+    hipLaunchKernelGGL(probe_project_kernel, dim3(grid_for(lanes, n_cu, kT)), dim3(kT), 0, stream, c, rays, path, sh);
     return hipGetLastError();
 }
 
 hipError_t launch_probe_irradiance(const DevProbeLookup &d, int n_cu, hipStream_t stream) {
-    hipLaunchKernelGGL(probe_irradiance_kernel, dim3(grid_for(d.n, n_cu)), dim3(kT), 0, stream, d);
+    hipLaunchKernelGGL(probe_irradiance_kernel, dim3(grid_for(d.n, n_cu, kT)), dim3(kT), 0, stream, d);
     return hipGetLastError();
 }
 

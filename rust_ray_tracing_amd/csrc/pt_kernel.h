@@ -152,20 +152,24 @@ hipError_t launch_bake_texels(const DevScene &sc, const uint32_t *tri_order, uin
 hipError_t launch_bake_invert_order(const DevScene &sc, const uint32_t *tri_order, uint32_t *inv, int n_cu, hipStream_t stream);
 // ctl->bad_point = the lowest i < n whose point names a triangle >= n_tris (ctl zeroed first, bad_point all ones)
 hipError_t launch_bake_check_points(const void *points, unsigned long long n, uint32_t n_tris, BakeCtl *ctl, int n_cu, hipStream_t stream);
-struct BakeGather {                         // one chunk of a gather: paths [first_path, first_path + n_paths) of n * samples
-    const uint4 *points;                    // all n records (MiptSurfacePoint)
-    const uint32_t *inv_order;              // the caller's triangle index -> its record in tri_pos
+// One chunk of an entry that traces n * samples paths in chunks (mipt::chunked_trace, mipt_scene.h; the gather: items are surface
+// points, bake.hip; the probe bake: items are probes, probe.hip): paths [first_path, first_path + n_paths), path q being sample
+// q % samples of item q / samples.  The spans of the items in a chunk: chunk_paths.h.
+constexpr uint32_t kCarrySlotWords = 32;    // one carry slot: the gather uses its first 3 words, the probe bake its first 27
+struct PathChunk {
     unsigned long long first_path, n_paths;
     uint32_t samples, first_sample, sample_stride;
     uint32_t sum_only, accumulate;
-    float samples_f;
-    const float *carry_in;                  // 3 f32: the sum so far of the point whose samples began in the chunk before
-    float *carry_out;                       // 3 f32: the sum so far of the point whose samples go on in the next chunk
+    float samples_f;                        // samples as f32 (cpu.rs:60)
+    const float *carry_in;                  // the running sums of the item whose samples began in a chunk before
+    float *carry_out;                       // the running sums of the item whose samples go on in the next chunk
 };
-// rays[j] (n_paths x 32 B, MiptRay with the stream's state after the draws as its seed) for path first_path + j
-hipError_t launch_bake_rays(const DevScene &sc, const BakeGather &g, float4 *rays, int n_cu, hipStream_t stream);
+// rays[j] (n_paths x 32 B, MiptRay with the stream's state after the draws as its seed) for path first_path + j; points: all n
+// records (MiptSurfacePoint); inv_order: the caller's triangle index -> its record in tri_pos
+hipError_t launch_bake_rays(const DevScene &sc, const void *points, const uint32_t *inv_order, const PathChunk &c, float4 *rays, int n_cu,
+                            hipStream_t stream);
 // path: n_paths x 3 f32, the chunk's traced radiance; radiance: the caller's n x 3 f32
-hipError_t launch_bake_reduce(const BakeGather &g, const float *path, float *radiance, int n_cu, hipStream_t stream);
+hipError_t launch_bake_reduce(const void *points, const PathChunk &c, const float *path, float *radiance, int n_cu, hipStream_t stream);
 // position[i], normal[i] (3 f32 each; either may be NULL) of point i < n: P and N of the gather, N normalized if `unit`; +0 for no point
 hipError_t launch_bake_surface(const DevScene &sc, const void *points, const uint32_t *inv_order, unsigned long long n, bool unit,
                                float *position, float *normal, int n_cu, hipStream_t stream);
@@ -197,20 +201,11 @@ struct DevLightmapDilate {
 hipError_t launch_lightmap_dilate(const DevLightmapDilate &d, hipStream_t stream);
 
 // ---- irradiance probes (probe.hip; mipt_probe_bake* / mipt_probe_irradiance*) ----
-constexpr uint32_t kProbeCarryWords = 32;   // one carry slot: a probe's 27 running sums, padded
-struct ProbeBake {                          // one chunk of a probe bake: paths [first_path, first_path + n_paths) of n * samples
-    const float4 *probes;                   // all n records (MiptProbe): {x, y, z, seed}
-    unsigned long long first_path, n_paths;
-    uint32_t samples, first_sample, sample_stride;
-    uint32_t sum_only, accumulate;
-    float samples_f;
-    const float *carry_in;                  // 27 f32: the sums so far of the probe whose samples began in a chunk before
-    float *carry_out;                       // 27 f32: the sums so far of the probe whose samples go on in the next chunk
-};
-// rays[j] (n_paths x 32 B, MiptRay: origin P, direction d, the stream's state after the draws as its seed) for path first_path + j
-hipError_t launch_probe_rays(const ProbeBake &g, float4 *rays, int n_cu, hipStream_t stream);
+// rays[j] (n_paths x 32 B, MiptRay: origin P, direction d, the stream's state after the draws as its seed) for path first_path + j;
+// probes: all n records (MiptProbe): {x, y, z, seed}
+hipError_t launch_probe_rays(const void *probes, const PathChunk &c, float4 *rays, int n_cu, hipStream_t stream);
 // path: n_paths x 3 f32, the chunk's traced radiance; rays: what launch_probe_rays wrote; sh: the caller's n x 27 f32
-hipError_t launch_probe_project(const ProbeBake &g, const float4 *rays, const float *path, float *sh, int n_cu, hipStream_t stream);
+hipError_t launch_probe_project(const PathChunk &c, const float4 *rays, const float *path, float *sh, int n_cu, hipStream_t stream);
 struct DevProbeLookup {
     const float *sh;                        // n_probes x 27
     const uint8_t *valid;                   // n_probes, or NULL

@@ -135,6 +135,18 @@ def test_plane_checks_under_asan_ubsan(tmp_path):
     assert "plane_checks ok" in out.stdout
 
 
+def test_chunk_spans_under_asan_ubsan(tmp_path):
+    """The span arithmetic and the carry-slot rule of the chunked entries (csrc/chunk_paths.h), walked as mipt::chunked_trace walks a
+    call for every chunk size 1 ... 9, samples 1 ... 20 and 1 ... 12 items against a brute force over the paths, and at the largest
+    operands (tests/cpp/chunk_spans.cpp): no HIP, no libmipt.so."""
+    exe = str(tmp_path / "chunk_spans")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "cpp", "chunk_spans.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    assert "chunk_spans ok" in out.stdout
+
+
 def test_oracle_under_asan_ubsan(built, tmp_path):
     """The oracle itself (test infrastructure) under ASan/UBSan: a small render through a standalone driver."""
     drv = tmp_path / "drv.c"

@@ -570,6 +570,35 @@ def test_gather_across_a_chunk_boundary(rrt):
     assert not none[straddler] and straddler * samples < (1 << 22) < (straddler + 1) * samples
 
 
+def test_gather_points_longer_than_a_chunk(rrt, orc):
+    """Four points of 2^22 + 2^21 + 7 samples each at depth 1, the third of them no point: whole chunks inside one point and straddles
+    at different offsets, so both carry slots are written and read more than once.  Against the same entry in SUM | ACCUM calls of at
+    most 2^21 samples: 2^21 divides a chunk, so no point of such a call crosses one, and such calls are on the path the small cases
+    hold to the model.  The three real points see the box's light (chosen on the CPU: their sums are no whole numbers, so the order
+    of the additions shows)."""
+    import torch
+    from rust_ray_tracing_amd import _lib as L
+    sc, _, _, pts = _case(rrt, orc, "cornell")
+    four = pts[[0, 1, 14, 2]].copy()
+    assert four["prim"][2] == B.NONE and np.all(four["prim"][[0, 1, 3]] != B.NONE)
+    per = (1 << 22) + (1 << 21) + 7
+    assert per > (1 << 22) and len({(k * per) % (1 << 22) for k in (1, 2, 3)}) == 3 and (1 << 22) % (1 << 21) == 0
+    rc, whole, st = _gather(rrt, sc, four, per, 1, flags=L.FLAG_SUM, device=True, stride=4)
+    assert rc == 0 and st["pixels"] == 4 * per                                           # a NONE point's placeholder paths count
+    d_acc = torch.zeros((4 * 3 + 4,), dtype=torch.float32, device="cuda").view(torch.int32)
+    d_acc[4 * 3:] = SENTINEL
+    first = 0
+    while first < per:
+        k = min(1 << 21, per - first)
+        rc, parts, _ = _gather(rrt, sc, four, k, 1, flags=L.FLAG_SUM | L.FLAG_ACCUM, device=True, stride=4, first_sample=first, d_out=d_acc)
+        assert rc == 0                                                                    # (_gather asserts the sentinels)
+        first += k
+    real = whole[[0, 1, 3]]
+    assert np.all(np.isfinite(real)) and np.all(real > 0) and not B.same_bits(real[0], real[1]) and not B.same_bits(real[1], real[2])
+    assert not whole[2].view(np.uint32).any() and not parts[2].view(np.uint32).any()      # +0, bit for bit
+    assert B.same_bits(whole, parts), _bad_rows(whole, parts)
+
+
 def test_bake_lightmap_is_texels_then_gather(rrt, orc):
     base = _base_scene(rrt, "wgsl_pbr")
     v = base.tris["vertices"]                                                               # the atrium's UVs tile the atlas: shrink them into a chart
