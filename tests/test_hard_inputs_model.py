@@ -3,7 +3,9 @@ tests/test_gpu_radiance_hard.py and tests/test_gpu_bake_hard.py compare the kern
 hard rays and points; here the models are held to what those comparisons rely on, so that no GPU test passes for lack of cases:
 the one-ray oracle entries with a margin are the old ones at margin 0, every class of input is there and falls on both sides of the
 kernel's guard, few rows are NaN, the rows at margin 2^-7 are the reference traversal's, and the step counts of the three arms all
-differ -- which is what lets a counter comparison see a margin that was dropped."""
+differ -- which is what lets a counter comparison see a margin that was dropped.  The same for tests/tools/probe_model.py on the hard
+probes of tests/test_gpu_probe_hard.py: every class is there, a third of them fail the origin clauses of the guard and a sixth pass,
+a quarter have a path that hits and a quarter one that escapes."""
 import ctypes as C
 import os
 import sys
@@ -14,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import bake_model as B  # noqa: E402
 import hard_inputs as H  # noqa: E402
+import probe_model as PM  # noqa: E402
 import radiance_model as R  # noqa: E402
 import test_gpu_bake as TB  # noqa: E402
 import test_gpu_radiance as TR  # noqa: E402
@@ -153,3 +156,82 @@ def test_gather_model_rows_few_nans_and_the_safe_margin_is_the_reference(rrt, or
             if kind == "helmet":
                 steps = [int(out[arm]["counters"][:, INNER].sum()) for arm in ARMS]
                 assert len(set(steps)) == 3, (shading, first_sample, steps)
+
+
+# ---- the bake model on the hard probes ------------------------------------------------------------------------------------------------------
+_probe_cases = {}
+
+
+def _probe_case(rrt, orc, kind):
+    """(host-built Scene of tests/test_gpu_probe.py's triangles in its order, PM.Bake, the hard probes and their tags)"""
+    if kind not in _probe_cases:
+        tris, mats, texs = PM.case_scene(rrt, kind)
+        sc = rrt.Scene.from_arrays(np.ascontiguousarray(tris[np.random.default_rng(11).permutation(len(tris))]), mats, texs)
+        pr, tags = H.hard_probes(sc.tris, sc.bvh_nodes, H.PROBE_SEED)
+        _probe_cases[kind] = (sc, PM.Bake(orc, sc), pr, tags)
+    return _probe_cases[kind]
+
+
+@pytest.mark.parametrize("kind", ["cornell", "helmet", "wgsl_pbr"])
+def test_every_class_of_hard_probe_is_there_on_both_sides_of_the_guard(rrt, orc, kind):
+    sc, _, pr, tags = _probe_case(rrt, orc, kind)
+    assert tags.tolist() == H.PROBE_CLASSES and len(set(tags.tolist())) == len(pr) == 63
+    safe = H.origin_safe(pr)
+    assert 3 * int((~safe).sum()) >= len(pr) and 6 * int(safe.sum()) >= len(pr), (int(safe.sum()), len(pr))
+    by = dict(zip(tags.tolist(), safe.tolist()))
+    pos = dict(zip(tags.tolist(), pr["position"]))
+    for a, axis in enumerate("xyz"):                                                # each boundary of the origin clauses, from both sides
+        assert by[f"p{axis}=2^40"] and not by[f"p{axis}=next(2^40)"] and by[f"p{axis}=2^-70"] and not by[f"p{axis}=2^-71"]
+        assert by[f"p{axis}=0"] and by[f"p{axis}=-0"] and not by[f"p{axis}=1e-42"] and not by[f"p{axis}=nan"] and not by[f"p{axis}=+inf"]
+        assert np.signbit(pos[f"p{axis}=-0"][a]) and pos[f"p{axis}=-0"][a] == 0 and not np.signbit(pos[f"p{axis}=0"][a])
+        others = [b for b in range(3) if b != a]
+        assert np.all(np.isfinite(pos[f"p{axis}=nan"][others])) and np.isnan(pos[f"p{axis}=nan"][a])
+    assert by["p=0"] and not by["p=2^-71"] and not pr["position"][tags == "p=0"].any()
+    assert not H.origin_safe(pr, tiny_axes=7)[np.char.startswith(tags, "p") & (np.char.endswith(tags, "=0") | np.char.endswith(tags, "=-0"))].any()
+    for s in H.HARD_SEEDS + H.ZERO_SEEDS + (H.LATE_ZERO_SEED,):
+        assert s in pr["seed"][np.char.startswith(tags, "on_")]
+    # on geometry: bit for bit on a vertex, on a plane of an inner node, on a corner of the bounds
+    P = sc.tris["vertices"]["position"].reshape(-1, 3)
+    for t in tags[np.char.startswith(tags, "on_vertex")]:
+        assert np.any(np.all(P == pos[t], axis=1)), t
+    inner = sc.bvh_nodes[sc.bvh_nodes["num_tris"] == 0]
+    planes = np.concatenate([inner["bounds_min"], inner["bounds_max"]])
+    for t in tags[np.char.startswith(tags, "on_node_plane")]:
+        assert any(np.any(planes[:, a] == pos[t][a]) for a in range(3)), t
+    lo, hi = P.min(0), P.max(0)
+    for t in tags[np.char.startswith(tags, "on_corner")]:
+        assert np.all((pos[t] == lo) | (pos[t] == hi)), t
+
+
+@pytest.mark.parametrize("kind,shadings", [("cornell", (0,)), ("helmet", (0, 1)), ("wgsl_pbr", (1,))])
+def test_probe_model_on_the_hard_probes_few_nans_hits_and_escapes(rrt, orc, kind, shadings):
+    _, m, pr, _ = _probe_case(rrt, orc, kind)
+    for shading in shadings:
+        for first_sample in (0, H.HARD_FIRST_SAMPLE):
+            out = {arm: m.run(pr, 3, 8, shading=shading, cull=arm[0], margin=arm[1], first_sample=first_sample, stride=H.HARD_STRIDE) for arm in ARMS}
+            for arm in ARMS:
+                H.few_nan_rows(out[arm])
+                assert 4 * int(out[arm]["hit"].any(axis=1).sum()) >= len(pr)                  # a quarter of the probes have a path that hits
+                assert 4 * int((~out[arm]["hit"]).any(axis=1).sum()) >= len(pr)               # a quarter have one that escapes
+                assert np.abs(np.linalg.norm(out[arm]["dirs"].astype(np.float64), axis=2) - 1).max() < 1e-6
+                rays = H.probe_rays(pr, out[arm]["dirs"])                                       # unit directions pass their clauses: the origin decides
+                assert np.array_equal(H.ray_safe(rays), np.repeat(H.origin_safe(pr), 3))
+            assert H.same_bits_or_both_nan(out[ARMS[2]]["sum"], out[ARMS[0]]["sum"]), (kind, shading, first_sample)
+    # the streams: both zero seeds run on stream 1 at first_sample 0, the late one at the second sample of HARD_FIRST_SAMPLE
+    assert all(B.sample_seed(s, 0, H.HARD_STRIDE) == 1 for s in H.ZERO_SEEDS)
+    assert B.sample_seed(H.LATE_ZERO_SEED, H.HARD_FIRST_SAMPLE + 1, H.HARD_STRIDE) == 1
+
+
+def test_tiny_plane_probes_leave_the_fast_path_for_the_planes_alone(rrt, orc):
+    from test_gpu_radiance_hard import _tiny_plane_scene
+    sc = _tiny_plane_scene(rrt)
+    pr = H.tiny_plane_probes()
+    assert len(pr) == 45 and len(set(pr["seed"].tolist())) == 45
+    out = PM.Bake(orc, sc).run(pr, 3, 8)
+    rays = H.probe_rays(pr, out["dirs"])
+    only = (H.ray_safe(rays, 0) & ~H.ray_safe(rays, 5)).reshape(len(pr), 3).all(axis=1)
+    assert int(only.sum()) >= 12, int(only.sum())
+    safe = H.ray_safe(rays, 5)
+    assert 4 * int(safe.sum()) >= len(rays) and 4 * int((~safe).sum()) >= len(rays)
+    H.few_nan_rows(out)
+    assert 4 * int(out["hit"].sum()) >= out["hit"].size

@@ -1,7 +1,8 @@
 """CPU: the models of tests/tools/probe_model.py, held to what include/mipt.h "irradiance probes" says independently of the library:
 the literals against their closed forms, the basis against orthonormality, the vectorised lookup against its scalar restatement and
 against closed forms of the cosine convolution in float64, the f32 bake model against a float64 projection written from the textbook
-formulas, and the conditions every scene of tests/test_gpu_probe.py must meet on the model alone."""
+formulas, the conditions every scene of tests/test_gpu_probe.py must meet on the model alone, and those of the hard lookup cases of
+tests/test_gpu_probe_hard.py (PM.lookup_hard_case)."""
 import os
 import sys
 
@@ -94,6 +95,111 @@ def test_lookup_closed_forms():
     E = PM.lookup(sh, grid, P, N.astype(np.float32)).astype(np.float64)
     want = np.pi / 3 + np.pi * (3 * N[:, 2] ** 2 - 1) / 12
     assert np.abs(E[:, 1] / want - 1).max() < 1e-5
+
+
+# ---- the hard lookup cases of tests/test_gpu_probe_hard.py ------------------------------------------------------------------------------
+LOOKUP_HARD_SEED = 7
+_hard_lookup = []
+
+
+def _hard_cases():
+    if not _hard_lookup:
+        _hard_lookup.extend(PM.lookup_hard_case(LOOKUP_HARD_SEED))
+    return list(zip(PM.LOOKUP_HARD_NAMES, _hard_lookup))
+
+
+def _nan_rows(x):
+    return int(np.isnan(x).any(axis=1).sum())
+
+
+def _same_or_both_nan(a, b):
+    wa, wb = np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)
+    return not np.any((wa != wb) & ~(np.isnan(a) & np.isnan(b)))
+
+
+def test_hard_lookup_cases_vectorised_equals_scalar_and_the_models_conditions():
+    seen = set()
+    for name, (grid, sh, valid, P, N) in _hard_cases():
+        assert len(P) % 64 != 0 and P.dtype == N.dtype == sh.dtype == np.float32 and valid.dtype == np.uint8, name
+        seen |= set(valid.tolist())
+        planes = (valid,) if name.startswith("non-finite") else (None, valid)         # without its plane that grid is all NaN, by design
+        for v in planes:
+            for clamp in (False, True):
+                a = PM.lookup(sh, grid, P, N, v, clamp)
+                if clamp:
+                    assert not np.any(np.isnan(a)) and not np.any(a < 0), (name, v is not None)
+                else:
+                    assert 10 * _nan_rows(a) <= len(a) and np.any(a < 0), (name, v is not None, _nan_rows(a), len(a))
+                assert np.any(a > 0) and np.any(np.isfinite(a) & (a != 0))
+                if (v is None) == (not clamp):                                       # (no plane, no clamp) and (plane, clamp): the scalar loop is slow
+                    b = PM.lookup_scalar(sh, grid, P, N, v, clamp)
+                    assert _same_or_both_nan(a, b), (name, np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)).any(axis=1))[:8])
+        normal_kinds = [np.any(np.all(N == 0, axis=1)), np.any(np.signbit(N) & (N == 0)), np.any(np.isnan(N)), np.any(np.isinf(N)),
+                        np.any(N == F(1e30)), np.any(N == F(1e-30)), np.any(N == F(1e-42))]
+        odd = ~np.isclose(np.linalg.norm(N.astype(np.float64), axis=1), 1.0, atol=1e-5)
+        assert (all(normal_kinds) or len(P) < 100) and 10 * int(odd.sum()) <= len(P), (name, normal_kinds, int(odd.sum()))
+    assert seen == set(range(256))                                                    # every byte value of `valid`, 0 among them
+
+
+def test_hard_lookup_grids_do_not_divide_back_and_cover_their_points():
+    for name, (grid, sh, valid, P, N) in _hard_cases()[:3]:
+        origin, spacing, dims = grid
+        pts = PM.grid_positions(*grid)
+        assert PM.same_bits(P[: len(pts)], pts)
+        inexact = 0
+        for a in range(3):
+            g = (pts[:, a] - F(origin[a])) / F(spacing[a])
+            inexact += int((g != np.round(g)).sum())
+            i0, f = PM._axis(P[:, a], origin[a], spacing[a], dims[a])
+            if dims[a] > 1:
+                assert set(i0.tolist()) == set(range(dims[a] - 1)), (name, a)        # every cell of the axis is visited
+                assert np.any(f == 0) and np.any(f == 1) and np.any((f > 0) & (f < 2.0 ** -10)) and np.any((f < 1) & (f > 1 - 2.0 ** -10))
+        assert inexact > 0, name                                                      # a probe's own position does not give an integer quotient
+        assert np.isnan(P).any() and np.isinf(P).any() and np.any(np.abs(P) == F(3e38)) and np.any(P == F(1e-42))
+        assert np.any((P == 0) & np.signbit(P)) and np.any((P == 0) & ~np.signbit(P))
+    # a multiplication by the reciprocal of the spacing is another function on these grids
+    grid, sh, valid, P, N = _hard_cases()[0][1]
+    with np.errstate(all="ignore"):
+        g = (P[:, 0] - F(grid[0][0])) / F(grid[1][0])
+        r = (P[:, 0] - F(grid[0][0])) * (F(1.0) / F(grid[1][0]))
+    assert np.any((g != r) & np.isfinite(g))
+
+
+def test_hard_lookup_extreme_spacings_overflow_go_denormal_and_underflow():
+    for name, (grid, sh, valid, P, N) in _hard_cases()[3:5]:
+        origin, spacing, dims = grid
+        with np.errstate(all="ignore"):
+            g = [(P[:, a] - F(origin[a])) / F(spacing[a]) for a in range(3)]
+        assert np.any(np.isinf(g[0])) and np.any((g[2] != 0) & (np.abs(g[2]) < 2.0 ** -126)), name    # a quotient overflows, one is denormal
+        w = [(F(1.0) - f, f) for _, f in (PM._axis(P[:, a], origin[a], spacing[a], dims[a]) for a in range(3))]
+        under = np.zeros(len(P), dtype=bool)
+        with np.errstate(all="ignore"):
+            for c in range(8):
+                parts = (w[0][c & 1], w[1][(c >> 1) & 1], w[2][c >> 2])
+                under |= ((parts[0] * parts[1]) * parts[2] == 0) & (parts[0] != 0) & (parts[1] != 0) & (parts[2] != 0)
+        assert int(under.sum()) >= 4, (name, int(under.sum()))                       # three non-zero weights whose product is exactly 0: skipped
+
+
+def test_hard_lookup_never_reads_an_invalid_probe_and_divides_by_a_tiny_sum():
+    cases = dict(_hard_cases())
+    grid, sh, valid, P, N = cases["non-finite words behind invalid probes"]
+    bad = sh[valid == 0]
+    assert len(bad) and not np.isfinite(bad).any() and np.any(bad.view(np.uint32) == PM.SENTINEL_BITS) and np.isfinite(sh[valid != 0]).all()
+    noise = sh.copy()
+    noise[valid == 0] = np.random.default_rng(3).normal(0, 1, bad.shape).astype(np.float32)
+    for clamp in (False, True):
+        a, b = PM.lookup(sh, grid, P, N, valid, clamp), PM.lookup(noise, grid, P, N, valid, clamp)
+        assert PM.same_bits(a[~np.isnan(a).any(axis=1)], b[~np.isnan(a).any(axis=1)]) and _same_or_both_nan(a, b)
+    with np.errstate(all="ignore"):                                                   # a multiply by 0 in place of the skip shows on most points
+        leaky = PM.lookup(np.where(np.isfinite(sh), sh, np.nan), grid, P, N, None)
+    assert 2 * _nan_rows(leaky) >= len(P)
+    grid, sh, valid, P, N = cases["inf on a valid probe"]
+    assert int(np.isinf(sh).sum()) == 1 and valid[np.flatnonzero(np.isinf(sh).reshape(len(sh), -1).any(axis=1))[0]] != 0
+    assert np.isinf(PM.lookup(sh, grid, P, N, valid)).any()
+    grid, sh, valid, P, N = cases["one valid corner of tiny weight"]
+    E, wsum = PM.lookup(sh, grid, P, N, valid, with_wsum=True)
+    tiny = (wsum > 0) & (wsum < 2.0 ** -60)
+    assert int(tiny.sum()) >= 4 and np.all(np.isfinite(E[tiny])) and np.all(E[tiny] != 0), (int(tiny.sum()), E[tiny])
 
 
 def test_grid_positions_are_in_index_order(rrt):

@@ -1,12 +1,14 @@
-"""Hard inputs for the two entries whose caller hands over a path's first segment: rays for mipt_query_radiance, surface points for
-mipt_bake_gather.  Pure numpy, shared by tests/test_hard_inputs_model.py (CPU: the models alone), tests/test_gpu_radiance_hard.py and
-tests/test_gpu_bake_hard.py.  Every input is legal per include/mipt.h; the oracle decides what each is worth.
+"""Hard inputs for the three entries whose caller hands over a path's first segment: rays for mipt_query_radiance, surface points for
+mipt_bake_gather, probes for mipt_probe_bake.  Pure numpy, shared by tests/test_hard_inputs_model.py (CPU: the models alone),
+tests/test_gpu_radiance_hard.py, tests/test_gpu_bake_hard.py and tests/test_gpu_probe_hard.py.  Every input is legal per
+include/mipt.h; the oracle decides what each is worth.
 
 hard_rays():  both sides of every boundary of ray_safe (csrc/pt_traverse.h: |d| in [2^-60, 2], |o| <= 2^40, |o| >= 2^-70 or 0), zero,
 denormal, huge and non-finite components, rays in a triangle's plane and rays through vertices and edges, with the seeds 0 (the
 stuck stream), 1, 0x80000000 and 0xffffffff among the default ones.  hard_points(): barycentrics that are no barycentrics, normals
 that cannot be normalised, a zero-area triangle, the seeds at which the sample seed formula gives 0, prim words with the ignored
-bits set, the first and the last triangle, and no point in between."""
+bits set, the first and the last triangle, and no point in between.  hard_probes(): an origin on both sides of every origin
+clause of the guard, shared by all of a probe's samples, and origins on vertices, edges, triangles, node planes and corners."""
 import numpy as np
 
 from bake_model import FRONT, NONE, POINT, TRI_MASK, M32
@@ -117,7 +119,7 @@ def spread(hard, pool):
     indices of the hard rays, the indices of the pool rays); needs 4 len(hard) pool rays"""
     n = len(hard)
     assert len(pool) >= 4 * n
-    out = np.zeros(5 * n, dtype=RAY)
+    out = np.zeros(5 * n, dtype=hard.dtype)                                       # rays, or the probes of hard_probes
     at = 5 * np.arange(n)
     rest = np.setdiff1d(np.arange(5 * n), at)
     out[at], out[rest] = hard, pool[: 4 * n]
@@ -220,6 +222,96 @@ def interleave(a, b):
     out = np.zeros(n, dtype=a.dtype)
     out[ia], out[ib] = a, b
     return out, ia, ib
+
+
+# ---- probes ---------------------------------------------------------------------------------------------------------------------------
+# A probe is the origin of all its samples' first segments: with s samples it puts s consecutive lanes of the ray kernel on the same
+# side of ray_safe's origin clauses (the directions are unit vectors as drawn, and pass theirs).
+PROBE = np.dtype([("position", "<f4", 3), ("seed", "<u4")])       # MiptProbe (probe_model.PROBE)
+PROBE_AXIS_VALUES = ORIGIN_SMALL + ORIGIN_BIG + ORIGIN_BAD + [("0", 0.0), ("-0", -0.0)]
+N_PROBE_TRIS, N_PROBE_PLANES, N_PROBE_CORNERS = 6, 6, 4
+PROBE_CLASSES = ([f"p{'xyz'[a]}={n}" for n, _ in PROBE_AXIS_VALUES for a in range(3)] + ["p=0", "p=2^-71"] +
+                 [f"{w}{k}" for k in range(N_PROBE_TRIS) for w in ("on_vertex", "on_edge", "on_centroid")] +
+                 [f"on_node_plane{k}" for k in range(N_PROBE_PLANES)] + [f"on_corner{k}" for k in range(N_PROBE_CORNERS)])
+PROBE_SEED = 41                                 # hard_probes' seed in every test, so that the CPU test sees the GPU tests' probes
+
+
+def hard_probes(tris, nodes, seed):
+    """-> (probes [63] PROBE, tags [63] of str, PROBE_CLASSES in order).  tris, nodes: the scene's triangles and its mirrored tree;
+    seed: picks the triangles, the inner nodes and the corners.  Per axis every value of PROBE_AXIS_VALUES with the other two
+    coordinates inside the scene; all three coordinates 0 and 2^-71; on a vertex, on an edge's midpoint and at the f32 centroid of
+    some triangles; on a bounding plane of an inner node; on a corner of the scene's bounds.  Seeds 13 i + 7 but for HARD_SEEDS, both
+    ZERO_SEEDS and LATE_ZERO_SEED (whose second sample under HARD_FIRST_SAMPLE / HARD_STRIDE runs on stream 1), which go to probes
+    on geometry."""
+    P = np.asarray(tris["vertices"]["position"], dtype=np.float32)
+    flat = P.reshape(-1, 3)
+    lo, hi = flat.min(0), flat.max(0)
+    centre = ((lo + hi) * F(0.5)).astype(np.float32)
+    inside = (centre + np.clip((hi - lo) * np.float32([0.11, 0.17, -0.13]), F(-0.5), F(0.5))).astype(np.float32)
+    assert np.all(inside > lo) and np.all(inside < hi) and np.all(np.abs(inside) >= 2.0 ** -20)
+    rng = np.random.default_rng(seed)
+    pick = rng.choice(len(P), N_PROBE_TRIS, replace=False)
+    inner = np.flatnonzero(np.asarray(nodes["num_tris"]) == 0)
+    assert len(inner) >= N_PROBE_PLANES
+    pick_nodes = rng.choice(inner, N_PROBE_PLANES, replace=False)
+    pick_corners = rng.choice(8, N_PROBE_CORNERS, replace=False)
+    pos, tags = [], []
+
+    def add(tag, p):
+        tags.append(tag); pos.append(np.asarray(p, dtype=np.float32))
+    for name, value in PROBE_AXIS_VALUES:
+        for axis in range(3):
+            p = inside.copy(); p[axis] = F(value)
+            add(f"p{'xyz'[axis]}={name}", p)
+    add("p=0", (0.0, 0.0, 0.0)); add("p=2^-71", (2.0 ** -71,) * 3)
+    for k, t in enumerate(pick):
+        v0, v1, v2 = P[t]
+        add(f"on_vertex{k}", (v0, v1, v2)[k % 3]); add(f"on_edge{k}", F(0.5) * ((v0, v1, v2)[k % 3] + (v0, v1, v2)[(k + 1) % 3]))
+        add(f"on_centroid{k}", ((v0 + v1) + v2) / F(3.0))
+    for k, j in enumerate(pick_nodes):                                              # the middle of the node's box, moved onto one of its six planes
+        b0, b1 = np.asarray(nodes["bounds_min"][j], dtype=np.float32), np.asarray(nodes["bounds_max"][j], dtype=np.float32)
+        p = ((b0 + b1) * F(0.5)).astype(np.float32)
+        p[k % 3] = (b0, b1)[(k // 3) % 2][k % 3]
+        add(f"on_node_plane{k}", p)
+    for k, c in enumerate(pick_corners):
+        add(f"on_corner{k}", [(lo, hi)[(c >> a) & 1][a] for a in range(3)])
+    n = len(tags)
+    assert tags == PROBE_CLASSES
+    probes = np.zeros(n, dtype=PROBE)
+    probes["position"] = np.stack(pos)
+    probes["seed"] = 13 * np.arange(n, dtype=np.uint32) + 7
+    first = tags.index("on_vertex0")
+    for k, s in enumerate(HARD_SEEDS + ZERO_SEEDS + (LATE_ZERO_SEED,)):             # on_vertex0, on_edge0, on_centroid0, on_vertex1, ...
+        probes["seed"][first + k] = s
+    return probes, np.array(tags)
+
+
+def tiny_plane_probes(copies=3):
+    """the origins of tests/test_gpu_radiance_hard.py::test_hard_rays_on_a_scene_with_tiny_planes as probes: a coordinate of 0, 2^-71
+    or 2^-70 on each axis and on two pairs of axes, the rest of (0.5, -2, -7); `copies` probes of each with seeds of their own"""
+    o = []
+    for value in (0.0, 2.0 ** -71, 2.0 ** -70):
+        for axis in range(3):
+            oo = np.float32([0.5, -2.0, -7.0]); oo[axis] = value; o.append(oo)
+        o.append(np.float32([value, -2.0, value])); o.append(np.float32([value, value, -7.0]))
+    probes = np.zeros(len(o) * copies, dtype=PROBE)
+    probes["position"] = np.tile(np.stack(o), (copies, 1))
+    probes["seed"] = 29 * np.arange(len(probes), dtype=np.uint32) + 300
+    return probes
+
+
+def probe_rays(probes, dirs):
+    """the first segments of a bake as RAY records, for ray_safe: probes [n], dirs [n, samples, 3] -> [n * samples]"""
+    dirs = np.asarray(dirs, dtype=np.float32)
+    rays = np.zeros(dirs.shape[0] * dirs.shape[1], dtype=RAY)
+    rays["origin"] = np.repeat(np.asarray(probes["position"], dtype=np.float32), dirs.shape[1], axis=0)
+    rays["direction"] = dirs.reshape(-1, 3)
+    return rays
+
+
+def origin_safe(probes, tiny_axes=0):
+    """bool [n]: the probes whose position passes ray_safe's origin clauses"""
+    return ray_safe(probe_rays(probes, np.ones((len(probes), 1, 3), dtype=np.float32)), tiny_axes)
 
 
 # ---- comparisons and what the model must show before anything is compared with it -----------------------------------------------------

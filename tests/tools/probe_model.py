@@ -1,5 +1,5 @@
-"""The models of include/mipt.h "irradiance probes" for tests/test_probe_model.py, tests/test_probe_abi.py, tests/test_gpu_probe.py and
-tests/test_cpp_host_probe.py.
+"""The models of include/mipt.h "irradiance probes" for tests/test_probe_model.py, tests/test_probe_abi.py, tests/test_gpu_probe.py,
+tests/test_gpu_probe_hard.py and tests/test_cpp_host_probe.py.
 
 Bake: mipt_probe_bake as a Python loop over the oracle's orc_rand_in_unit_sphere and orc_trace_ray_m / orc_trace_ray_wgsl_m (the
 one-ray entries with a cull margin and counters), with bake_model's seed arithmetic and argument packing; the basis and the 27
@@ -126,9 +126,9 @@ def _axis(p, origin, spacing, dim):
     return i0, f
 
 
-def lookup(sh, grid, position, normal, valid=None, clamp=False):
+def lookup(sh, grid, position, normal, valid=None, clamp=False, with_wsum=False):
     """mipt_probe_irradiance: sh [n_probes, 9, 3] f32, grid = (origin, spacing, dims), position / normal [n, 3] f32, valid n_probes
-    uint8 or None -> [n, 3] f32"""
+    uint8 or None -> [n, 3] f32; with_wsum: -> (that, the sum of the weights of the corners that were added [n] f32)"""
     origin, spacing, dims = grid
     sh = np.ascontiguousarray(sh, dtype=np.float32).reshape(-1, 9, 3)
     P, N = np.asarray(position, dtype=np.float32), np.asarray(normal, dtype=np.float32)
@@ -160,7 +160,7 @@ def lookup(sh, grid, position, normal, valid=None, clamp=False):
         if clamp:
             E = np.where(E > 0, E, F(0.0))
     assert E.dtype == np.float32 and b.dtype == np.float32
-    return np.ascontiguousarray(E)
+    return (np.ascontiguousarray(E), wsum) if with_wsum else np.ascontiguousarray(E)
 
 
 def lookup_scalar(sh, grid, position, normal, valid=None, clamp=False):
@@ -243,6 +243,141 @@ def lookup_case(dims, n, seed):
     N = (N / np.linalg.norm(N, axis=1, keepdims=True)).astype(np.float32)
     N[-3:] *= F(2.5)
     return (origin, spacing, dims), sh, P, N
+
+
+# ---- the hard lookup cases of tests/test_gpu_probe_hard.py; tests/test_probe_model.py (CPU) holds the model alone to its conditions on them
+HARD_DIMS = ((67, 1, 2), (1, 129, 1), (5, 4, 3))
+HARD_ORIGIN, HARD_SPACING = (0.1, -0.3, 7.7), (0.3, 1.7, 0.013)          # nothing dyadic: a probe's position does not divide back to its index
+EXTREME_DIMS, EXTREME_SPACINGS = (4, 3, 2), ((2.0 ** -100, 1.0, 2.0 ** 100), (1e-42, 1.0, 3e38))     # origin 0: tiny coordinates stay what they are
+SENTINEL_BITS = 0x7FA5A5A5
+TINY_CELL = (0, 0, 0)                                                    # of (5, 4, 3): the cell whose one valid corner is its far one
+LOOKUP_HARD_NAMES = ("67x1x2", "1x129x1", "5x4x3", "spacing 2^-100, 1, 2^100", "spacing 1e-42, 1, 3e38", "non-finite words behind invalid probes",
+                     "inf on a valid probe", "one valid corner of tiny weight")
+_NORMAL_SPECIALS = (0.0, -0.0, np.nan, np.inf, 1e30, 1e-30, 1e-42)
+
+
+def _ulps(x, k):
+    """x moved by k ulps (k of either sign), f32"""
+    x = F(x)
+    for _ in range(abs(k)):
+        x = np.nextafter(x, F(np.inf if k > 0 else -np.inf))
+    return x
+
+
+def _hard_points(grid, rng, n_random):
+    """every probe position, nextafter to both sides of it on each axis, one ulp beyond the first and the last probe on each axis,
+    +-0, a denormal, +-3e38, NaN and +-inf on each axis and on all three, random points in and around the grid"""
+    origin, spacing, dims = grid
+    pts = grid_positions(origin, spacing, dims)
+    out = [pts]
+    for a in range(3):
+        for to in (-np.inf, np.inf):
+            q = pts.copy(); q[:, a] = np.nextafter(q[:, a], F(to)); out.append(q)
+        first, last = pts[0].copy(), pts[-1].copy()
+        first[a], last[a] = np.nextafter(first[a], F(-np.inf)), np.nextafter(last[a], F(np.inf))
+        out += [first[None], last[None]]
+    mid = (pts[0] + pts[-1]) * F(0.5)
+    for value in (0.0, -0.0, 1e-42, -1e-42, 3e38, -3e38, np.nan, np.inf, -np.inf):
+        for a in range(3):
+            q = mid.copy(); q[a] = F(value); out.append(q[None])
+        out.append(np.full((1, 3), value, dtype=np.float32))
+    ext = np.array([(d - 1) * s for d, s in zip(dims, spacing)])
+    out.append((np.array(origin) + rng.uniform(-0.3, 1.3, (n_random, 3)) * np.maximum(ext, 1.0)).astype(np.float32))
+    P = np.ascontiguousarray(np.concatenate(out), dtype=np.float32)
+    return P if len(P) % 64 else P[:-1]                                   # a ragged last wave
+
+
+def _hard_normals(n, rng):
+    """unit normals; every 11th point has one of _NORMAL_SPECIALS in one component or, every fourth of those, in all three"""
+    N = rng.normal(0, 1, (n, 3))
+    N = (N / np.linalg.norm(N, axis=1, keepdims=True)).astype(np.float32)
+    for j, i in enumerate(range(5, n, 11)):
+        value = F(_NORMAL_SPECIALS[j % len(_NORMAL_SPECIALS)])
+        if j % 4 == 3:
+            N[i] = value
+        else:
+            N[i, (j // len(_NORMAL_SPECIALS)) % 3] = value
+    return N
+
+
+def _tiny_weight_points(grid):
+    """points of cell TINY_CELL one to three ulps above its lowest probe on every axis: the cell's far corner weighs less than 2^-60
+    there and more than 0 (near the origin of HARD_ORIGIN an ulp is 2^-25 of a cell on x and y and 2^-15 on z)"""
+    origin, spacing, dims = grid
+    ix, iy, iz = TINY_CELL
+    base = grid_positions(origin, spacing, dims)[(iz * dims[1] + iy) * dims[0] + ix]
+    found = []
+    for k in range(1, 4):
+        for j in range(1, 4):
+            for m in range(1, 3):
+                p = np.float32([_ulps(base[0], k), _ulps(base[1], j), _ulps(base[2], m)])
+                ax = [_axis(p[a: a + 1], origin[a], spacing[a], dims[a]) for a in range(3)]
+                wt = (ax[0][1][0] * ax[1][1][0]) * ax[2][1][0]
+                if all(int(ax[a][0][0]) == TINY_CELL[a] for a in range(3)) and 0 < wt < 2.0 ** -60:
+                    found.append(p)
+    assert len(found) >= 4, len(found)
+    return np.stack(found)
+
+
+def lookup_hard_case(seed):
+    """-> a list of (grid, sh, valid, P, N), named by LOOKUP_HARD_NAMES, from `seed` alone.  The three HARD_DIMS grids with
+    _hard_points and _hard_normals and a `valid` plane in which every seventh probe is 0 and the others count 1 ... 255 through
+    the three grids; (4, 3, 2) with the two EXTREME_SPACINGS, whose quotients overflow, go denormal and give weight products that
+    underflow to 0; (5, 4, 3) with NaN, +-inf and SENTINEL_BITS in the coefficients of its invalid probes; the same grid with +inf
+    in one coefficient of a valid probe; the same grid with TINY_CELL's corners invalid but the far one, and points in that corner's
+    far end of the cell."""
+    rng = np.random.default_rng(seed)
+    cases, count = [], 0
+    for dims in HARD_DIMS:
+        grid = (HARD_ORIGIN, HARD_SPACING, dims)
+        n_probes = int(np.prod(dims))
+        sh = rng.normal(0, 1, (n_probes, 9, 3)).astype(np.float32)
+        valid = np.zeros(n_probes, dtype=np.uint8)
+        for i in range(n_probes):
+            if i % 7 != 3:
+                valid[i] = 1 + count % 255
+                count += 1
+        P = _hard_points(grid, rng, 200)
+        cases.append((grid, sh, valid, P, _hard_normals(len(P), rng)))
+    assert count >= 255
+    for spacing in EXTREME_SPACINGS:
+        grid = ((0.0, 0.0, 0.0), spacing, EXTREME_DIMS)
+        sx, sz = F(spacing[0]), F(spacing[2])
+        with np.errstate(all="ignore"):
+            xs = np.float32([0.0, sx * F(2.0 ** -20), sx * F(0.5), sx, sx * F(1.5), sx * F(3.0), sx * F(4.0), 1e-45, 1.0, 3e38])
+            ys = np.float32([0.0, 2.0 ** -20, 0.5, 1.0, 1.999, 2.5])
+            zs = np.float32([0.0, 1e-45, 2.0 ** -30, 0.25, 1.0, 3.0, sz * F(2.0 ** -30), sz * F(0.5), sz * F(0.999), sz, 3e38])
+        P = np.ascontiguousarray(np.stack(np.meshgrid(xs, ys, zs, indexing="ij"), axis=-1).reshape(-1, 3))
+        P = np.concatenate([P, rng.uniform(-1, 3, (31, 3)).astype(np.float32)])
+        assert len(P) % 64
+        sh = rng.normal(0, 1, (int(np.prod(EXTREME_DIMS)), 9, 3)).astype(np.float32)
+        valid = (np.arange(len(sh)) % 5 != 2).astype(np.uint8) * np.uint8(255)
+        cases.append((grid, sh, valid, P, _hard_normals(len(P), rng)))
+    grid = (HARD_ORIGIN, HARD_SPACING, HARD_DIMS[2])
+    _, sh0, _, P0, N0 = cases[2]
+    n_probes = len(sh0)
+    valid = (np.arange(n_probes) % 3 != 1).astype(np.uint8)               # a third invalid: most cells have such a corner
+    sh = sh0.copy()
+    words = sh.view(np.uint32)
+    for j, i in enumerate(np.flatnonzero(valid == 0)):
+        words[i] = (0x7FC00000, 0x7F800000, 0xFF800000, SENTINEL_BITS)[j % 4]
+    words[np.flatnonzero(valid == 0)[0], 4, 1] = SENTINEL_BITS               # and a lone one among numbers
+    cases.append((grid, sh, valid, P0, N0))
+    sh = sh0.copy()
+    sh[(1 * 4 + 2) * 5 + 2, 0, 0] = np.inf                                  # probe (2, 2, 1), band 0, red
+    cases.append((grid, sh, (np.arange(n_probes) % 7 != 3).astype(np.uint8), P0, N0))
+    valid = np.ones(n_probes, dtype=np.uint8)
+    ix, iy, iz = TINY_CELL
+    for c in range(7):                                                      # every corner of the cell but (1, 1, 1)
+        valid[((iz + (c >> 2)) * 4 + iy + ((c >> 1) & 1)) * 5 + ix + (c & 1)] = 0
+    P = np.concatenate([_tiny_weight_points(grid), P0[:60]])
+    N = _hard_normals(len(P), rng)
+    plain = rng.normal(0, 1, (len(P) - 60, 3))
+    N[: len(P) - 60] = (plain / np.linalg.norm(plain, axis=1, keepdims=True)).astype(np.float32)    # unit normals on the tiny-weight points
+    assert len(P) % 64
+    cases.append((grid, sh0, valid, P, N))
+    assert len(cases) == len(LOOKUP_HARD_NAMES)
+    return cases
 
 
 # ---- the scenes and probes of tests/test_gpu_probe.py, made here so that tests/test_probe_model.py (CPU) can hold the model alone to
