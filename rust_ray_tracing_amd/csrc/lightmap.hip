@@ -1,35 +1,20 @@
 // lightmap.hip -- the kernels of include/mipt.h "lightmap finishing": the edge-avoiding a-trous filter over the covered texels of an
 // atlas (mipt_lightmap_filter*) and the dilation into its gutters (mipt_lightmap_dilate*).
 //
-// Both are a pack pass, then one launch per iteration or pass, in the shape of denoise.hip: one texel per lane, a 256-thread block
-// covers 64x4 texels, so a tap load at any step is one contiguous run of a row, and the reuse between neighbouring texels' taps is
-// left to the vector L1 and L2.  The filter's pack pass writes one float4 of colour per texel with the covered flag in w, and one
-// float4 each of position and normal where those guides exist: a tap is then 16-byte loads, and a tap whose colour word says
-// "uncovered" fetches no guide.  An iteration reads one colour plane and writes the other; the last one writes the planar output, so
-// `out` may be `radiance`.  Which guides exist and whether a pass is the last are template arguments.  The dilation keeps {r, g, b,
-// level} per texel in two planes; a pass reads one and writes the other, so it sees only the state of the pass before it.
+// Both are a pack pass, then one launch per iteration or pass (image_kernels.h: the tile walk over the atlas's one view, the taps, the
+// ladder).  The filter's pack pass writes one float4 of colour per texel with the covered flag in w, and one float4 each of position
+// and normal where those guides exist: a tap is then 16-byte loads, and a tap whose colour word says "uncovered" fetches no guide.
+// An iteration reads one colour plane and writes the other; the last one writes the planar output, so `out` may be `radiance`.
+// Which guides exist and whether a pass is the last are template arguments.  The dilation keeps {r, g, b, level} per texel in two
+// planes; a pass reads one and writes the other, so it sees only the state of the pass before it.
 //
-// Every operator below is one rounded f32 operation in the order the header gives (the translation unit is built with
-// -ffp-contract=off); expf is gl_expf of pt_device_math.h, glibc 2.35's, on the domain [-128, -0] the clamp leaves.  An uncovered
-// texel's words travel through the planes as loaded: no arithmetic touches them.
-#include "pt_kernel.h"
-#include "pt_device_math.h"
+// An uncovered texel's words travel through the planes as loaded: no arithmetic touches them.
+#include "image_kernels.h"
 #include "../../include/mipt.h"
 
 namespace mipt {
 
 namespace {
-
-constexpr uint32_t kTileW = 64, kTileH = 4;                  // texels a block covers: one wave per row
-constexpr uint32_t kMaxGrid = 1u << 16;                      // blocks per launch; a block walks the tiles with this stride
-static_assert(kTileW * kTileH == (uint32_t)kBlockThreads, "one texel per lane");
-
-// The texel of this lane in tile `t`; false = outside the atlas (a ragged edge tile).  The index stays below 2^31.
-__device__ __forceinline__ bool lane_texel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t t, uint32_t &x, uint32_t &y) {
-    x = (t % tiles_x) * kTileW + (threadIdx.x & (kTileW - 1u));
-    y = (t / tiles_x) * kTileH + (threadIdx.x / kTileW);
-    return x < width && y < height;
-}
 
 // ---- filter ------------------------------------------------------------------------------------------------------------------------
 template <bool POS, bool NRM>
@@ -49,7 +34,6 @@ __global__ __launch_bounds__(kBlockThreads) void lightmap_pack_kernel(DevLightma
 template <bool POS, bool NRM, bool LAST>
 __global__ __launch_bounds__(kBlockThreads) void lightmap_pass_kernel(DevLightmapFilter d, uint32_t n_tiles, const float4 *__restrict__ src,
                                                                       float4 *__restrict__ dst, uint32_t step, float kc, float kd) {
-    constexpr float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         uint32_t x, y;
         if (!lane_texel(d.width, d.height, d.tiles_x, t, x, y)) continue;
@@ -61,47 +45,41 @@ __global__ __launch_bounds__(kBlockThreads) void lightmap_pass_kernel(DevLightma
             if (POS) pp = d.pos4[i];
             if (NRM) np = d.nrm4[i];
             float sr = 0.0f, sg = 0.0f, sb = 0.0f, wsum = 0.0f;
+            const auto tap = [&](float hk, bool centre, size_t q) {
+                const float4 cq = centre ? cp : src[q];                  // one whole load, then the test of its w
+                float w = hk;                                             // the centre: 9/64 without evaluation
+                if (!centre) {
+                    if (cq.w == 0.0f) return;                             // an uncovered tap: skipped like one outside, no guide fetched
+                    const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
+                    float e = (((dr * dr) + (dg * dg)) + (db * db)) * kc;
+                    float4 nq = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pq = nq;
+                    if (NRM) nq = d.nrm4[q];
+                    if (POS) pq = d.pos4[q];
+                    if (NRM) e = e + normal_term(np, nq, d.kn);
+                    if (POS) {
+                        const float Dx = pq.x - pp.x, Dy = pq.y - pp.y, Dz = pq.z - pp.z;   // tap minus centre: l below has a sign
+                        if (NRM) {
+                            const float l = ((np.x * Dx) + (np.y * Dy)) + (np.z * Dz);
+                            e = e + ((l * l) * d.kl);
+                        }
+                        e = e + ((((Dx * Dx) + (Dy * Dy)) + (Dz * Dz)) * kd);
+                    }
+                    w = tap_weight(hk, e);
+                }
+                sr = sr + (w * cq.x); sg = sg + (w * cq.y); sb = sb + (w * cq.z);
+                wsum = wsum + w;
+            };
+            // atrous_taps of image_kernels.h spelled out: the same taps, bounds rule and kernel.  Written in the kernel, the compiler keeps
+            // gl_expf's rare branch out of a tap's straight path; through the shared loop a pass was 4 % slower.
 #pragma unroll
             for (int dy = -2; dy <= 2; dy++) {
-                // a tap outside the atlas is skipped: neither weighted nor added (signed 64-bit: step * 2 may pass the atlas's size)
                 const long long qy = (long long)y + (long long)dy * (long long)step;
                 if (qy < 0 || qy >= (long long)d.height) continue;
 #pragma unroll
                 for (int dx = -2; dx <= 2; dx++) {
                     const long long qx = (long long)x + (long long)dx * (long long)step;
                     if (qx < 0 || qx >= (long long)d.width) continue;
-                    const float hk = h[dy + 2] * h[dx + 2];              // exact: a constant after unrolling
-                    float w;
-                    float4 cq;
-                    if (dy == 0 && dx == 0) {
-                        cq = cp;
-                        w = hk;                                           // the centre: 9/64 without evaluation
-                    } else {
-                        const size_t q = (size_t)qy * d.width + (size_t)qx;
-                        cq = src[q];
-                        if (cq.w == 0.0f) continue;                       // an uncovered tap: skipped like one outside, no guide fetched
-                        const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
-                        float e = (((dr * dr) + (dg * dg)) + (db * db)) * kc;
-                        float4 nq = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pq = nq;
-                        if (NRM) nq = d.nrm4[q];
-                        if (POS) pq = d.pos4[q];
-                        if (NRM) {
-                            const float nx = np.x - nq.x, ny = np.y - nq.y, nz = np.z - nq.z;
-                            e = e + ((((nx * nx) + (ny * ny)) + (nz * nz)) * d.kn);
-                        }
-                        if (POS) {
-                            const float Dx = pq.x - pp.x, Dy = pq.y - pp.y, Dz = pq.z - pp.z;
-                            if (NRM) {
-                                const float l = ((np.x * Dx) + (np.y * Dy)) + (np.z * Dz);
-                                e = e + ((l * l) * d.kl);
-                            }
-                            e = e + ((((Dx * Dx) + (Dy * Dy)) + (Dz * Dz)) * kd);
-                        }
-                        e = e < 128.0f ? e : 128.0f;                      // a NaN gives 128
-                        w = hk * gl_expf(-e);
-                    }
-                    sr = sr + (w * cq.x); sg = sg + (w * cq.y); sb = sb + (w * cq.z);
-                    wsum = wsum + w;
+                    tap(tap_kernel(2, dy + 2) * tap_kernel(2, dx + 2), dy == 0 && dx == 0, ((size_t)qy * d.width + (size_t)qx));
                 }
             }
             if (wsum > 0.0f) { r = sr / wsum; g = sg / wsum; b = sb / wsum; }
@@ -116,21 +94,20 @@ __global__ __launch_bounds__(kBlockThreads) void lightmap_pass_kernel(DevLightma
 }
 
 template <bool POS, bool NRM>
-hipError_t launch_filter_passes(const DevLightmapFilter &d, uint32_t n_tiles, uint32_t grid, hipStream_t stream) {
-    hipError_t e;
-    hipLaunchKernelGGL((lightmap_pack_kernel<POS, NRM>), dim3(grid), dim3(kBlockThreads), 0, stream, d, n_tiles);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (uint32_t i = 0; i < d.iterations; i++) {
-        const float4 *src = d.colour[i & 1u];
-        float4 *dst = d.colour[(i + 1u) & 1u];
-        const uint32_t step = 1u << i;
-        if (i + 1u < d.iterations)
-            hipLaunchKernelGGL((lightmap_pass_kernel<POS, NRM, false>), dim3(grid), dim3(kBlockThreads), 0, stream, d, n_tiles, src, dst, step, d.kc[i], d.kd[i]);
-        else
-            hipLaunchKernelGGL((lightmap_pass_kernel<POS, NRM, true>), dim3(grid), dim3(kBlockThreads), 0, stream, d, n_tiles, src, dst, step, d.kc[i], d.kd[i]);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+hipError_t launch_filter_passes(const DevLightmapFilter &d, hipStream_t stream) {
+    const uint32_t n_tiles = (uint32_t)tile_count(d.tiles_x, d.tiles_y, 1u);   // at most 2^30 (tile_shape.h)
+    const dim3 grid(tile_grid(n_tiles, kAtlasMaxGrid)), block(kBlockThreads);
+    return launch_ladder(
+        d.colour, 0u, d.iterations, false,
+        [&] {
+            hipLaunchKernelGGL((lightmap_pack_kernel<POS, NRM>), grid, block, 0, stream, d, n_tiles);
+            return hipGetLastError();
+        },
+        [&](uint32_t i, const float4 *src, float4 *dst, int mode) {
+            const auto pass = mode == 0 ? lightmap_pass_kernel<POS, NRM, false> : lightmap_pass_kernel<POS, NRM, true>;
+            hipLaunchKernelGGL(pass, grid, block, 0, stream, d, n_tiles, src, dst, 1u << i, d.kc[i], d.kd[i]);
+            return hipGetLastError();
+        });
 }
 
 // ---- dilation ----------------------------------------------------------------------------------------------------------------------
@@ -155,20 +132,13 @@ __global__ __launch_bounds__(kBlockThreads) void dilate_pass_kernel(DevLightmapD
         if (__float_as_uint(s.w) == 0u) {
             float sr = 0.0f, sg = 0.0f, sb = 0.0f;
             uint32_t count = 0;
-#pragma unroll
-            for (int dy = -1; dy <= 1; dy++) {
-                const long long qy = (long long)y + dy;
-                if (qy < 0 || qy >= (long long)d.height) continue;
-#pragma unroll
-                for (int dx = -1; dx <= 1; dx++) {
-                    const long long qx = (long long)x + dx;
-                    if ((dy == 0 && dx == 0) || qx < 0 || qx >= (long long)d.width) continue;
-                    const float4 q = src[(size_t)qy * d.width + (size_t)qx];
-                    if (__float_as_uint(q.w) == 0u) continue;
-                    sr = sr + q.x; sg = sg + q.y; sb = sb + q.z;
-                    count++;
-                }
-            }
+            taps_3x3(x, y, d.width, d.height, 0, [&](float, bool centre, size_t qi) {   // the eight neighbours, unweighted
+                if (centre) return;
+                const float4 q = src[qi];
+                if (__float_as_uint(q.w) == 0u) return;
+                sr = sr + q.x; sg = sg + q.y; sb = sb + q.z;
+                count++;
+            });
             if (count != 0u) {
                 const float cf = (float)count;
                 s = make_float4(sr / cf, sg / cf, sb / cf, __uint_as_float(k + 1u));
@@ -194,15 +164,13 @@ __global__ __launch_bounds__(kBlockThreads) void dilate_unpack_kernel(DevLightma
 
 // instantiations: {position} x {normal} x ({pack} + {middle, last})
 hipError_t launch_lightmap_filter(const DevLightmapFilter &d, hipStream_t stream) {
-    const uint32_t n_tiles = d.tiles_x * d.tiles_y;                      // < 2^31: one tile holds at least one texel
-    const uint32_t grid = n_tiles < kMaxGrid ? n_tiles : kMaxGrid;
-    if (d.position) return d.normal ? launch_filter_passes<true, true>(d, n_tiles, grid, stream) : launch_filter_passes<true, false>(d, n_tiles, grid, stream);
-    return d.normal ? launch_filter_passes<false, true>(d, n_tiles, grid, stream) : launch_filter_passes<false, false>(d, n_tiles, grid, stream);
+    if (d.position) return d.normal ? launch_filter_passes<true, true>(d, stream) : launch_filter_passes<true, false>(d, stream);
+    return d.normal ? launch_filter_passes<false, true>(d, stream) : launch_filter_passes<false, false>(d, stream);
 }
 
 hipError_t launch_lightmap_dilate(const DevLightmapDilate &d, hipStream_t stream) {
-    const uint32_t n_tiles = d.tiles_x * d.tiles_y;
-    const uint32_t grid = n_tiles < kMaxGrid ? n_tiles : kMaxGrid;
+    const uint32_t n_tiles = (uint32_t)tile_count(d.tiles_x, d.tiles_y, 1u);
+    const uint32_t grid = tile_grid(n_tiles, kAtlasMaxGrid);
     hipError_t e;
     hipLaunchKernelGGL(dilate_pack_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, d, n_tiles);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -5,6 +5,7 @@
 // What needs HIP -- the device-entry checks and the staging of the host entries -- is at the end of mipt_host_util.h.
 #pragma once
 #include "mipt_internal.h"
+#include "tile_shape.h"                                      // tiles_across, tiles_down: the kernels' tiles over a frame
 
 #include <cmath>
 #include <cstdint>
@@ -34,10 +35,6 @@ inline bool inverse_square(float sigma, float *k) {
     *k = 1.0f / (sigma * sigma);
     return std::isfinite(*k) && *k > 0.0f;
 }
-
-// the 64 x 4 pixel tiles of the image-space kernels over a frame
-inline uint32_t tiles_across(uint32_t width) { return (width + 63u) / 64u; }
-inline uint32_t tiles_down(uint32_t height) { return (height + 3u) / 4u; }
 
 // One plane of an entry's buffers struct.  pixel_bytes: its size per pixel of the full frame (planes_bind sizes it; an entry sizes
 // what is otherwise -- a low-resolution plane, a history -- itself).  over: for an output, the input plane it may be given as

@@ -13,7 +13,7 @@
 //
 // mipt_sample_map_fill: the same reduction, then one launch per round (sample_map_fill_kernel below): rounds + 1 launches, since each
 // round's pass also forms the two sums of the round after it.
-#include "pt_kernel.h"
+#include "image_kernels.h"                                  // floored, luminance
 
 #include <cstddef>
 
@@ -23,9 +23,6 @@ namespace {
 
 constexpr uint32_t kMapThreads = 256, kMapWaves = kMapThreads / 64;
 constexpr uint32_t kMapMaxGrid = 2048;                       // blocks per launch; a block walks the pixels with this stride
-constexpr float kAlbedoFloor = 1.0f / 256.0f;
-
-__device__ __forceinline__ float floored(float albedo) { return albedo > kAlbedoFloor ? albedo : kAlbedoFloor; }   // a NaN gives the floor
 
 // qi of pixel i.  MODE 0: variance alone; 1: relative to hdr's luminance; 2: to the luminance of hdr / albedo.
 template <int MODE>
@@ -41,7 +38,7 @@ __device__ __forceinline__ uint32_t pixel_weight(const DevSampleMap &d, unsigned
             const float *a = d.albedo + i * 3;
             r = r / floored(a[0]); g = g / floored(a[1]); b = b / floored(a[2]);
         }
-        float l = ((0.2126f * r) + (0.7152f * g)) + (0.0722f * b);
+        float l = luminance(r, g, b);
         l = l > 0.0f ? l : 0.0f;
         w = s / (l + 0.00390625f);
     }

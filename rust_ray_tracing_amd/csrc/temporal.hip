@@ -5,29 +5,21 @@
 // and writes the new history, the output frame and the optional length / variance planes.  A history keeps three float4 per pixel
 // ({colour, length}, {normal, depth}, {moments, material}), so a tap costs three 16-byte loads.
 //
-// One pixel per lane.  A 256-thread block covers 64x4 pixels, as in denoise.hip; the blocks walk (view, tile row, tile column) with a
-// grid stride.  Whether there is an albedo plane and whether this is the first frame are template arguments: the absent branches do
-// not exist in the code; neither does anything of the count plane (mipt_temporal_counts*, COUNTS) in the plain kernels, whose
-// argument stays DevTemporal.  The camera records of this frame travel as kernel arguments, eight views to a launch, and the first
-// tile of each view writes its record into history_out's header, so the entry neither allocates nor copies.
+// The tile walk and the colour helpers are image_kernels.h's; the four bilinear taps are this file's own.  Whether there is an albedo
+// plane and whether this is the first frame are template arguments: the absent branches do not exist in the code; neither does
+// anything of the count plane (mipt_temporal_counts*, COUNTS) in the plain kernels, whose argument stays DevTemporal.  The camera
+// records of this frame travel as kernel arguments, eight views to a launch, and the first tile of each view writes its record into
+// history_out's header, so the entry neither allocates nor copies.
 //
-// Every operator below is one rounded f32 operation in the order the header gives (the translation unit is built with
-// -ffp-contract=off); every comparison is written so that a NaN takes the reject / reset side.
-#include "pt_kernel.h"
+// Every comparison is written so that a NaN takes the reject / reset side.
+#include "image_kernels.h"
 
 namespace mipt {
 
 namespace {
 
-constexpr uint32_t kTileW = 64, kTileH = 4;                  // pixels a block covers: one wave per row
-constexpr uint32_t kMaxGrid = 1u << 20;                      // blocks per launch; a block walks the tiles with this stride
-static_assert(kTileW * kTileH == (uint32_t)kBlockThreads, "one pixel per lane");
-
-constexpr float kAlbedoFloor = 1.0f / 256.0f;
 constexpr float kMinWeight = 1.0f / 64.0f;
 constexpr float kMiss = 1e30f;
-
-__device__ __forceinline__ float floored(float albedo) { return albedo > kAlbedoFloor ? albedo : kAlbedoFloor; }   // a NaN gives the floor
 
 struct Sums { float w, r, g, b, len, m1, m2; };
 
@@ -63,7 +55,6 @@ __device__ __forceinline__ uint32_t samples_of(const DevTemporalCounts &a, size_
 template <bool ALBEDO, bool FIRST, bool COUNTS>
 __global__ __launch_bounds__(kBlockThreads) void temporal_kernel(typename KernelArgs<COUNTS>::type args, unsigned long long n_tiles) {
     const DevTemporal &d = plain(args);
-    const uint32_t per_view = d.tiles_x * d.tiles_y;
     const size_t header = (size_t)d.n_views * 16;            // f32 in front of the planes
     const float4 *in0 = nullptr, *in1 = nullptr, *in2 = nullptr;
     if (!FIRST) {
@@ -75,12 +66,14 @@ __global__ __launch_bounds__(kBlockThreads) void temporal_kernel(typename Kernel
     const float wf = (float)d.width, hf = (float)d.height;
     const float aspect = wf / hf;
     for (unsigned long long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const uint32_t local = (uint32_t)(t / per_view), r = (uint32_t)(t % per_view);   // local < view_count <= kTemporalGroupViews
+        uint32_t x, y, local;                                 // local < view_count <= kTemporalGroupViews
+        const bool inside = lane_pixel(d.width, d.height, d.tiles_x, d.tiles_y, t, x, y, local);
         const uint32_t view = d.view_begin + local;
-        if (r == 0 && threadIdx.x < 16) d.history_out[(size_t)view * 16 + threadIdx.x] = d.camera[local][threadIdx.x];
-        const uint32_t x = (r % d.tiles_x) * kTileW + (threadIdx.x & (kTileW - 1u));
-        const uint32_t y = (r / d.tiles_x) * kTileH + (threadIdx.x / kTileW);
-        if (x >= d.width || y >= d.height) continue;         // a ragged edge tile
+        // the camera record: lanes 0 ... 15 of the view's first tile -- row 0, x == lane -- and before the test, since a frame narrower
+        // than 16 pixels has them outside
+        static_assert(kTileW >= 16u, "the 16 words of a record lie in one tile row");
+        if (y == 0u && x < 16u) d.history_out[(size_t)view * 16 + x] = d.camera[local][x];
+        if (!inside) continue;                                // a ragged edge tile
         const size_t base = (size_t)view * d.width * d.height;
         const size_t i = base + ((size_t)y * d.width + x);   // < 2^32 (MIPT_BATCH_MAX_PIXELS)
 
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(kBlockThreads) void temporal_kernel(typename Kernel
             ar = floored(a[0]); ag = floored(a[1]); ab = floored(a[2]);
             ccr = ccr / ar; ccg = ccg / ag; ccb = ccb / ab;
         }
-        const float l = ((0.2126f * ccr) + (0.7152f * ccg)) + (0.0722f * ccb);
+        const float l = luminance(ccr, ccg, ccb);
         const float *n = d.normal + i * 3;
         const float nx = n[0], ny = n[1], nz = n[2];
         const float depth = d.depth[i];
@@ -167,8 +160,8 @@ __global__ __launch_bounds__(kBlockThreads) void temporal_kernel(typename Kernel
 
 template <bool ALBEDO, bool FIRST>
 hipError_t launch_group(const DevTemporal &d, const uint32_t *counts, uint32_t samples_cap, hipStream_t stream) {
-    const unsigned long long n_tiles = (unsigned long long)d.tiles_x * d.tiles_y * d.view_count;
-    const uint32_t grid = n_tiles < kMaxGrid ? (uint32_t)n_tiles : kMaxGrid;
+    const unsigned long long n_tiles = tile_count(d.tiles_x, d.tiles_y, d.view_count);
+    const uint32_t grid = tile_grid(n_tiles, kFrameMaxGrid);
     if (counts) {
         const DevTemporalCounts c = {d, counts, samples_cap};
         hipLaunchKernelGGL((temporal_kernel<ALBEDO, FIRST, true>), dim3(grid), dim3(kBlockThreads), 0, stream, c, n_tiles);

@@ -2,43 +2,19 @@
 // pipeline of first_hit.hip, temporal.hip and denoise_variance.hip: a frame traced and filtered at W/k x H/k comes back at W x H, its
 // edges and textures taken from the full-resolution guides.
 //
-// A pack pass over the low frame, then one pass over the full frame.  The shape is denoise.hip's, for the reasons given there: one
-// pixel per lane, a 256-thread block covers 64x4 pixels, a block-stride loop over (view, tile row, tile column), and the low frame's
-// planar inputs packed into one float4 of colour {c.r, c.g, c.b, bits(material)} and one of guides {n.x, n.y, n.z, z} per low pixel,
-// so that a tap costs at most two 16-byte loads.  Which guides exist is a template argument; the scale is a kernel argument, uniform
-// over the launch.  The 64 lanes of a tile row share 64/k + 1 low texels per low row; that reuse is left to the vector L1 and L2.
+// A pack pass over the low frame, then one pass over the full frame (image_kernels.h: the tile walk, the pack, the guide terms).  The
+// low frame's planar inputs are packed into one float4 of colour {c.r, c.g, c.b, bits(material)} and one of guides {n.x, n.y, n.z, z}
+// per low pixel, so that a tap costs at most two 16-byte loads.  Which guides exist is a template argument; the scale is a kernel
+// argument, uniform over the launch.  The 64 lanes of a tile row share 64/k + 1 low texels per low row; that reuse is left to the
+// vector L1 and L2.
 //
 // A tap that does not take part (outside the low frame, or with a bilinear weight of 0) is predicated off: it is not loaded.  A tap
 // whose material differs has loaded its colour -- the plain bilinear sums need it -- but not its guides.
-//
-// Every operator below is one rounded f32 operation in the order the header gives (the translation unit is built with
-// -ffp-contract=off); expf is gl_expf of pt_device_math.h on [-128, -0].
-#include "pt_kernel.h"
-#include "pt_device_math.h"
+#include "image_kernels.h"
 
 namespace mipt {
 
 namespace {
-
-constexpr uint32_t kTileW = 64, kTileH = 4;                  // pixels a block covers: one wave per row
-constexpr uint32_t kMaxGrid = 1u << 20;                      // blocks per launch; a block walks the tiles with this stride
-static_assert(kTileW * kTileH == (uint32_t)kBlockThreads, "one pixel per lane");
-
-constexpr float kAlbedoFloor = 1.0f / 256.0f;
-
-// The pixel of this lane in tile `t` of a launch over views of width x height: tiles run over (view, tile row, tile column).
-// false = outside the frame (a ragged edge tile).  view_base < 2^32 (MIPT_BATCH_MAX_PIXELS).
-__device__ __forceinline__ bool lane_pixel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t tiles_y, unsigned long long t,
-                                           uint32_t &x, uint32_t &y, uint32_t &view) {
-    const uint32_t per_view = tiles_x * tiles_y;
-    const uint32_t r = (uint32_t)(t % per_view);
-    view = (uint32_t)(t / per_view);
-    x = (r % tiles_x) * kTileW + (threadIdx.x & (kTileW - 1u));
-    y = (r / tiles_x) * kTileH + (threadIdx.x / kTileW);
-    return x < width && y < height;
-}
-
-__device__ __forceinline__ float floored(float albedo) { return albedo > kAlbedoFloor ? albedo : kAlbedoFloor; }   // a NaN gives the floor
 
 template <bool NORMAL, bool DEPTH, bool ALBEDO, bool MATERIAL>
 __global__ __launch_bounds__(kBlockThreads) void upsample_pack_kernel(DevUpsample d, unsigned long long n_tiles) {
@@ -46,19 +22,8 @@ __global__ __launch_bounds__(kBlockThreads) void upsample_pack_kernel(DevUpsampl
         uint32_t x, y, view;
         if (!lane_pixel(d.lo_width, d.lo_height, d.lo_tiles_x, d.lo_tiles_y, t, x, y, view)) continue;
         const size_t i = (size_t)view * d.lo_width * d.lo_height + ((size_t)y * d.lo_width + x);
-        const float *h = d.lo_hdr + i * 3;
-        float r = h[0], g = h[1], b = h[2];
-        if (ALBEDO) {
-            const float *a = d.lo_albedo + i * 3;
-            r = r / floored(a[0]); g = g / floored(a[1]); b = b / floored(a[2]);
-        }
-        d.colour[i] = make_float4(r, g, b, MATERIAL ? __uint_as_float(d.lo_material[i]) : 0.0f);
-        if (NORMAL || DEPTH) {
-            float4 gd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (NORMAL) { const float *n = d.lo_normal + i * 3; gd.x = n[0]; gd.y = n[1]; gd.z = n[2]; }
-            if (DEPTH) gd.w = d.lo_depth[i];
-            d.guides[i] = gd;
-        }
+        pack_pixel<NORMAL, DEPTH, ALBEDO>(d.lo_hdr, d.lo_albedo, d.lo_normal, d.lo_depth, i, MATERIAL ? __uint_as_float(d.lo_material[i]) : 0.0f,
+                                          d.colour, d.guides);
     }
 }
 
@@ -77,10 +42,10 @@ __global__ __launch_bounds__(kBlockThreads) void upsample_kernel(DevUpsample d, 
         const uint32_t rx = X - x0 * k, ry = Y - y0 * k;
         const float wx = (float)rx / fk, ux = 1.0f - wx;
         const float wy = (float)ry / fk, uy = 1.0f - wy;
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f, zp = 0.0f;
+        float4 gp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);     // the pixel's own guides, as the pack pass lays out a low pixel's
         uint32_t mp = 0;
-        if (NORMAL) { const float *n = d.normal + i * 3; nx = n[0]; ny = n[1]; nz = n[2]; }
-        if (DEPTH) zp = d.depth[i];
+        if (NORMAL) { const float *n = d.normal + i * 3; gp.x = n[0]; gp.y = n[1]; gp.z = n[2]; }
+        if (DEPTH) gp.w = d.depth[i];
         if (MATERIAL) mp = d.material[i];
         float br = 0.0f, bg = 0.0f, bb = 0.0f, bsum = 0.0f;  // the plain bilinear sums
         float sr = 0.0f, sg = 0.0f, sb = 0.0f, wsum = 0.0f;  // the guided sums
@@ -98,20 +63,7 @@ __global__ __launch_bounds__(kBlockThreads) void upsample_kernel(DevUpsample d, 
                 bsum = bsum + b;
                 if (MATERIAL && __float_as_uint(cq.w) != mp) continue;
                 float w = b;                                  // neither normal nor depth: b without evaluation
-                if (NORMAL || DEPTH) {
-                    const float4 gq = guides[q];
-                    float e = 0.0f;
-                    if (NORMAL) {
-                        const float dx = nx - gq.x, dy = ny - gq.y, dz = nz - gq.z;
-                        e = (((dx * dx) + (dy * dy)) + (dz * dz)) * d.kn;
-                    }
-                    if (DEPTH) {
-                        const float dz = (zp - gq.w) * (zp - gq.w);
-                        e = NORMAL ? e + (dz * d.kz) : dz * d.kz;
-                    }
-                    e = e < 128.0f ? e : 128.0f;              // a NaN gives 128
-                    w = b * gl_expf(-e);
-                }
+                if (NORMAL || DEPTH) w = tap_weight(b, guide_energy<NORMAL, DEPTH>(gp, guides[q], d.kn, d.kz));
                 sr = sr + (w * cq.x); sg = sg + (w * cq.y); sb = sb + (w * cq.z);
                 wsum = wsum + w;
             }
@@ -132,10 +84,8 @@ __global__ __launch_bounds__(kBlockThreads) void upsample_kernel(DevUpsample d, 
 
 template <bool NORMAL, bool DEPTH, bool ALBEDO, bool MATERIAL>
 hipError_t launch_both(const DevUpsample &d, hipStream_t stream) {
-    const unsigned long long lo_tiles = (unsigned long long)d.lo_tiles_x * d.lo_tiles_y * d.n_views;
-    const unsigned long long n_tiles = (unsigned long long)d.tiles_x * d.tiles_y * d.n_views;
-    const uint32_t lo_grid = lo_tiles < kMaxGrid ? (uint32_t)lo_tiles : kMaxGrid;
-    const uint32_t grid = n_tiles < kMaxGrid ? (uint32_t)n_tiles : kMaxGrid;
+    const unsigned long long lo_tiles = tile_count(d.lo_tiles_x, d.lo_tiles_y, d.n_views), n_tiles = tile_count(d.tiles_x, d.tiles_y, d.n_views);
+    const uint32_t lo_grid = tile_grid(lo_tiles, kFrameMaxGrid), grid = tile_grid(n_tiles, kFrameMaxGrid);
     hipError_t e;
     hipLaunchKernelGGL((upsample_pack_kernel<NORMAL, DEPTH, ALBEDO, MATERIAL>), dim3(lo_grid), dim3(kBlockThreads), 0, stream, d, lo_tiles);
     if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -147,6 +147,19 @@ def test_chunk_spans_under_asan_ubsan(tmp_path):
     assert "chunk_spans ok" in out.stdout
 
 
+def test_tile_walk_under_asan_ubsan(tmp_path):
+    """The tile arithmetic of the image-space kernels (csrc/tile_shape.h): frames ragged against the 64x4 tile both ways, with 1 and 3
+    views, walked as a launch walks them on full and capped grids -- every in-frame pixel met exactly once, no index past the
+    planes --, the largest operands against 128-bit arithmetic, and tile_grid around both caps (tests/cpp/tile_walk.cpp): no HIP, no
+    libmipt.so."""
+    exe = str(tmp_path / "tile_walk")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(ROOT, "tests", "cpp", "tile_walk.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    assert "tile_walk ok" in out.stdout
+
+
 def test_oracle_under_asan_ubsan(built, tmp_path):
     """The oracle itself (test infrastructure) under ASan/UBSan: a small render through a standalone driver."""
     drv = tmp_path / "drv.c"

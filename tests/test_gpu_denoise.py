@@ -169,6 +169,22 @@ def test_special_values(rrt, orc):
     assert np.isfinite(want).all() and D.same_bits(_device(rrt, clean, ("albedo",), 5), want)
 
 
+def test_albedo_around_the_floor(rrt, orc):
+    """albedos on both sides of the floor 1/256, half of them below it, none far from it: below it the floor divides and multiplies,
+    not the albedo, and a floored pixel mixes with its neighbours, so a floor of another value moves bits (the floored pixels of
+    test_special_values are too bright once demodulated to mix with anything)"""
+    size, views = (61, 37), 1
+    planes = _fields(size, views, seed=3)
+    planes["albedo"] = planes["albedo"] * np.float32(1.0 / 128.0)              # (1 / 6400, 1 / 128]
+    below = planes["albedo"] < np.float32(1.0 / 256.0)
+    assert planes["albedo"].dtype == np.float32 and 0.3 < below.mean() < 0.7
+    for combo in (("albedo",), GUIDES):
+        want = _model(orc, planes, combo, 2)
+        assert np.isfinite(want).all()
+        for entry in (_host, _device):
+            assert D.same_bits(entry(rrt, planes, combo, 2), want), (combo, entry.__name__)
+
+
 def test_sigmas_reach_the_kernel(rrt, orc):
     planes = _fields((61, 37), 1, seed=3)
     base = _model(orc, planes, GUIDES, 5)
@@ -188,7 +204,7 @@ def test_many_tiny_views(rrt, orc):
     assert D.same_bits(want[5], _model(orc, {k: a[5:6] for k, a in planes.items()}, GUIDES, 2)[0])     # views never see each other
 
 
-CAP = 1 << 20                                                   # kMaxGrid: workgroups per launch, one 64x4 tile per trip
+CAP = 1 << 20                                                   # kFrameMaxGrid (csrc/tile_shape.h): workgroups per launch, one 64x4 tile per trip
 
 
 def _past_cap_subset(views):

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 SENTINEL = TB.SENTINEL
 POISON = 0x7FB1B2B3                             # a NaN pattern no output has
 EXTRA = 4
-K_MAX_GRID = 1 << 16                            # restated from csrc/lightmap.hip (kMaxGrid): edit together with it
+K_MAX_GRID = 1 << 16                            # restated from csrc/tile_shape.h (kAtlasMaxGrid): edit together with it
 
 
 def _poisoned(n_words, device):
@@ -340,7 +340,7 @@ def test_filter_keeps_charts_apart_that_are_far_apart_in_the_world(rrt, orc):
 
 
 def test_more_tiles_than_the_grid_holds(rrt, orc):
-    """an atlas of 1 x (4 * kMaxGrid + 5): one tile more than a launch has workgroups, a ragged one behind it, and the vertical taps
+    """an atlas of 1 x (4 * kAtlasMaxGrid + 5): one tile more than a launch has workgroups, a ragged one behind it, and the vertical taps
     of the filter and the neighbours of the dilation cross between a workgroup's first trip and another's second"""
     import torch
     w, h = 1, 4 * K_MAX_GRID + 5

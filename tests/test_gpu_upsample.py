@@ -260,7 +260,7 @@ def test_many_tiny_views(rrt, orc):
     assert UM.same_bits(want[0][5], alone[0][0]) and UM.same_bits(want[1][5], alone[1][0])     # views never see each other
 
 
-CAP = 1 << 20                                                   # kMaxGrid: workgroups per launch, one 64x4 tile per trip
+CAP = 1 << 20                                                   # kFrameMaxGrid (csrc/tile_shape.h): workgroups per launch, one 64x4 tile per trip
 
 
 def test_more_tiles_than_the_grid_holds(rrt, orc):
