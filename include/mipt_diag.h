@@ -74,7 +74,8 @@ MIPT_DIAG_API int mipt_debug_popcount(const uint32_t *d_bitmap, uint64_t n_words
  *   mipt_diag_scene_tile_order  what a scene handle of libmipt.so keeps after its last plain single-view launch: info_out[0] = local
  *                               tiles (0 = no valid state), [1] = the state is valid, [2] = that launch itself ran in the order made
  *                               before it; with non-NULL buffers of `cap` words, that launch's rays per local tile and the order
- *                               sorted from them.
+ *                               sorted from them -- by the launch where a later one can read it, else (a list of every slot leaves
+ *                               the tiles no walk, so the launch queued no sort) here, by the same kernel.
  * Return as mipt_debug_eval. */
 MIPT_DIAG_API int mipt_debug_tile_order(const uint32_t *cost, uint32_t n_tiles, uint32_t samples, uint32_t *order_out);
 MIPT_DIAG_API int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *order_out, uint32_t cap, uint32_t info_out[3]);
@@ -91,10 +92,16 @@ MIPT_DIAG_API int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_o
  *   mipt_diag_scene_list        the whole list, of which the H hot pixels are the head: info_out[0] = its entries (0 = no valid state;
  *                               the local slots where the list is complete, slots of cost 0 last), [1] = the entries that launch
  *                               itself took from the list made before it; with a non-NULL buffer of `cap` words, the list.
+ *   mipt_diag_scene_hot_bits    the bitmap of the listed slots that goes with that list, 2 words per local tile, into `cap_words` words
+ *                               (-1 without a valid state or a list).
+ *   mipt_diag_scene_cost_atomics  on != 0: the handle's launches measure their pixels' costs with one atomic per path, as a launch
+ *                               does whose sample count or ray depth is too large for the packed counter; 0: the product's choice again.
  * Return as mipt_debug_eval. */
 MIPT_DIAG_API int mipt_debug_hot_select(const uint32_t *cost, uint32_t n_slots, uint32_t samples, uint32_t n_hot, uint32_t *hot_out, uint32_t *bits_out);
 MIPT_DIAG_API int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint32_t cap_slots, uint32_t *hot_out, uint32_t cap_hot, uint32_t info_out[3]);
 MIPT_DIAG_API int mipt_diag_scene_list(const void *scene, uint32_t *list_out, uint32_t cap, uint32_t info_out[2]);
+MIPT_DIAG_API int mipt_diag_scene_hot_bits(const void *scene, uint32_t *bits_out, uint32_t cap_words);
+MIPT_DIAG_API int mipt_diag_scene_cost_atomics(void *scene, int on);
 
 MIPT_DIAG_API const char *mipt_diag_last_error(void);
 

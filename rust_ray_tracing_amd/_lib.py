@@ -604,7 +604,7 @@ def load_multitest() -> C.CDLL:
 
 
 DIAG_LIB_PATH = os.path.join(_HERE, "libmipt_diag.so")
-DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_texel", "mipt_debug_divide", "mipt_debug_popcount", "mipt_debug_tile_order", "mipt_diag_scene_tile_order", "mipt_debug_hot_select", "mipt_diag_scene_hot_pixels", "mipt_diag_scene_list", "mipt_diag_last_error",
+DIAG_EXPORTS = ["mipt_debug_eval", "mipt_debug_eval_range", "mipt_debug_wgsl", "mipt_debug_texel", "mipt_debug_divide", "mipt_debug_popcount", "mipt_debug_tile_order", "mipt_diag_scene_tile_order", "mipt_debug_hot_select", "mipt_diag_scene_hot_pixels", "mipt_diag_scene_list", "mipt_diag_scene_hot_bits", "mipt_diag_scene_cost_atomics", "mipt_diag_last_error",
                 "mipt_internal_pair_order", "mipt_internal_pair_order_top", "mipt_internal_tri_slots",
                 "mipt_diag_scene_sizes", "mipt_diag_scene_tables", "mipt_diag_scene_read", "mipt_diag_scene_hash", "mipt_diag_write_obj", "mipt_diag_host_layout", "mipt_diag_hash_words"]
 _diag = None
@@ -643,6 +643,10 @@ def load_diag() -> C.CDLL:
     lib.mipt_diag_scene_hot_pixels.restype = C.c_int
     lib.mipt_diag_scene_list.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32 * 2)]
     lib.mipt_diag_scene_list.restype = C.c_int
+    lib.mipt_diag_scene_hot_bits.argtypes = [vp, vp, C.c_uint32]
+    lib.mipt_diag_scene_hot_bits.restype = C.c_int
+    lib.mipt_diag_scene_cost_atomics.argtypes = [vp, C.c_int]
+    lib.mipt_diag_scene_cost_atomics.restype = C.c_int
     lib.mipt_diag_last_error.argtypes = []
     lib.mipt_diag_last_error.restype = C.c_char_p
     u32p = C.POINTER(C.c_uint32)

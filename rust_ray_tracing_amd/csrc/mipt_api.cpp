@@ -597,13 +597,16 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
     // dry.  A plain single-view launch adds up the rays of every local tile, one small kernel behind the trace sorts the tiles by
     // decreasing cost, and the next launch with the same key AND THE SAME CAMERA on this handle hands them out in that order: the
     // same pixels bit for bit, ending with the cheapest tiles (a view rendered again: further samples of a still view, a re-render).
+    // The sort is queued only where a launch can read it -- behind a list that holds every slot (below) none walks the tiles -- and
+    // tile_order_sorted says whether it was; the tile costs are written by every launch, and the test hook sorts them itself.
     // A camera that has moved is a change of key: measured, the costs of a view turned by 2 degrees or more order the tiles no
     // better than chance while the order gives up the plain one's locality (neighbouring tiles in flight together), +1 % of kernel
     // time; at 0.5 degrees it is a wash.  A launch with another key or camera runs in the plain order and only
     // measures; counting, batch, wgpu-shading and accumulating launches and a rank without tiles neither use nor touch the state.
     // Hot pixels.  Single heavy pixels make that tail (measured on config M: the heaviest is 4.4 x the mean, a sequential chain of
-    // ~70 % of the frame, yet adds 5 % to its tile's sum): so the cost is measured per pixel -- the tile costs are the sums, taken
-    // behind the launch -- and the H most expensive pixels -- two per resident lane of the launch that measured them, at most a
+    // ~70 % of the frame, yet adds 5 % to its tile's sum): so the cost is measured per pixel -- a lane keeps its pixel's rays in the
+    // spare bits of its sample counter and stores them once, where the frame is written (mipt::cost_packs; else one atomic per
+    // path, as every launch did once) -- the tile costs are the sums, taken behind the launch -- and the H most expensive pixels -- two per resident lane of the launch that measured them, at most a
     // quarter of the local pixels -- are handed out before everything else, so that every long chain starts with the frame; the
     // pass over the ordered tiles skips them.  Same key, same valid flag; the frame's tail share 7.5 -> 5.6 % of its wave-cycles.
     // H is NOT a function of the key: the grid depends on the traversal mode (5 blocks per CU culled, 4 un-culled), which the key
@@ -636,6 +639,9 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
             scene->d_hot_bits.bytes() < bytes * 2 || scene->d_hot_work.bytes() < work_bytes || memcmp(key, scene->tile_key, sizeof key) != 0 ||
             memcmp(pr.cam, scene->tile_cam, sizeof pr.cam) != 0)
             scene->tile_order_valid = false;
+        // which slots are pixels is a matter of {width, height, world, rank, local tiles}: with another of these, or in a new buffer,
+        // the slots that are none no longer read 0
+        if (scene->d_pixel_cost.bytes() < bytes * 64 || memcmp(key, scene->tile_key, 5 * sizeof key[0]) != 0) scene->pixel_cost_clean = false;
         if ((rc = scene->d_tile_cost.grow(bytes))) return rc;
         if ((rc = scene->d_tile_order.grow(bytes))) return rc;
         if ((rc = scene->d_pixel_cost.grow(bytes * 64))) return rc;
@@ -644,9 +650,16 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         if ((rc = scene->d_hot_work.grow(work_bytes))) return rc;
         memcpy(scene->tile_key, key, sizeof key);
         memcpy(scene->tile_cam, pr.cam, sizeof pr.cam);
-        MIPT_HIP(hipMemsetAsync(scene->d_pixel_cost, 0, bytes * 64, stream));   // the kernels behind the last launch have read them
+        // The cost of a pixel: one store per pixel where its rays fit the lane's sample counter, which overwrites every slot that is a
+        // pixel -- the others are zeroed once -- else one atomic per path into a buffer zeroed for every launch (the kernels behind the
+        // last launch have read it).
+        pr.cost_packed = (mipt::cost_packs(opt->samples, opt->max_ray_depth) && !scene->cost_atomics) ? 1u : 0u;
+        if (!pr.cost_packed || !scene->pixel_cost_clean) {
+            MIPT_HIP(hipMemsetAsync(scene->d_pixel_cost, 0, bytes * 64, stream));
+            scene->pixel_cost_clean = true;
+        }
         pr.pixel_cost = scene->d_pixel_cost;
-        pr.tile_order = scene->tile_order_valid ? scene->d_tile_order : nullptr;
+        pr.tile_order = (scene->tile_order_valid && scene->tile_order_sorted) ? scene->d_tile_order.get() : nullptr;
         scene->tile_order_used = scene->tile_order_valid;
         scene->hot_used = 0u; scene->list_used = 0u;
         if (scene->tile_order_valid && scene->hot_n != 0u) {
@@ -676,7 +689,10 @@ static int render_launch(MiptScene *scene, const MiptCamera *cameras, uint32_t n
         [&]() -> int {
             if (order_on) {                                       // behind ev1: kernel_ms stays the trace alone
                 MIPT_HIP(mipt::launch_pixel_reduce(scene->d_pixel_cost, n_slots, opt->samples, scene->d_tile_cost, scene->d_hot_work, stream));
-                MIPT_HIP(mipt::launch_tile_order(scene->d_tile_cost, pr.n_local_tiles, opt->samples, scene->d_tile_order, stream));
+                // the tile order: read by the walk over the tiles behind the list, which a list of every slot does not leave
+                scene->tile_order_sorted = list_next != n_slots;
+                if (scene->tile_order_sorted)
+                    MIPT_HIP(mipt::launch_tile_order(scene->d_tile_cost, pr.n_local_tiles, opt->samples, scene->d_tile_order, stream));
                 if (list_next != 0u)
                     MIPT_HIP(mipt::launch_hot_select(scene->d_pixel_cost, n_slots, opt->samples, list_next, scene->d_hot_work, scene->d_hot, scene->d_hot_bits, stream));
                 scene->hot_n = hot_next; scene->list_n = list_next;

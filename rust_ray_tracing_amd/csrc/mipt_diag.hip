@@ -261,7 +261,16 @@ int mipt_diag_scene_tile_order(const void *scene, uint32_t *cost_out, uint32_t *
     hipError_t e;
     if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
     if ((e = hipMemcpy(cost_out, s->d_tile_cost, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
-    if ((e = hipMemcpy(order_out, s->d_tile_order, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    // a launch whose list holds every slot queues no sort (mipt_api.cpp): the order of its tile costs is made here, by the same
+    // kernel, into a buffer of this call's own -- the handle is only read
+    mipt::DevPtr<uint32_t> dorder;
+    const uint32_t *order = s->d_tile_order;
+    if (!s->tile_order_sorted) {
+        if ((e = dorder.alloc(n)) != hipSuccess) return fail(e, "hipMalloc");
+        if ((e = mipt::launch_tile_order(s->d_tile_cost, n, s->tile_key[6], dorder, nullptr)) != hipSuccess) return fail(e, "launch_tile_order");
+        order = dorder;
+    }
+    if ((e = hipMemcpy(order_out, order, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     return 0;
 }
 
@@ -299,6 +308,23 @@ int mipt_diag_scene_hot_pixels(const void *scene, uint32_t *pixel_cost_out, uint
     if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
     if ((e = hipMemcpy(pixel_cost_out, s->d_pixel_cost, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
     if (h != 0u && (e = hipMemcpy(hot_out, s->d_hot, (size_t)h * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+int mipt_diag_scene_hot_bits(const void *scene, uint32_t *bits_out, uint32_t cap_words) {
+    const MiptScene *s = (const MiptScene *)scene;
+    const uint32_t n = (s && s->tile_order_valid && s->list_n != 0u) ? s->tile_key[4] * 2u : 0u;
+    if (!s || !bits_out || n == 0u || cap_words < n) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_hot_bits: bad argument, no list, or cap < %u words", n); return -1; }
+    hipError_t e;
+    if ((e = hipSetDevice(s->device)) != hipSuccess) return fail(e, "hipSetDevice");
+    if ((e = hipMemcpy(bits_out, s->d_hot_bits, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "hipMemcpy");
+    return 0;
+}
+
+int mipt_diag_scene_cost_atomics(void *scene, int on) {
+    MiptScene *s = (MiptScene *)scene;
+    if (!s) { snprintf(g_err, sizeof g_err, "mipt_diag_scene_cost_atomics: bad argument"); return -1; }
+    s->cost_atomics = on != 0;
     return 0;
 }
 

@@ -56,10 +56,15 @@ struct MiptScene {
     float tile_cam[12] = {0};               // DevParams::cam of that launch, compared bit for bit
     bool tile_order_valid = false;          // d_tile_order is the order of d_tile_cost, both of the launch tile_key describes
     bool tile_order_used = false;           // that launch itself handed its tiles out by the order before it (read by the test hook)
+    bool tile_order_sorted = false;         // d_tile_order really holds that order: the sort is queued only where a launch can read it
+                                            // (a list of every slot leaves the tiles no walk), else the test hook sorts d_tile_cost itself
     // hot pixels, part of the same state (one key, one valid flag): rays per slot (local tile * 64 + pixel of the tile) of that launch,
     // the tile costs being their sums; the hot_n slots of highest cost, which the next launch with the key and camera hands out first,
     // their bitmap (2 words per tile) and the scratch of the selection kernels (mipt::hot_work_words)
     mipt::DevBuf<uint32_t> d_pixel_cost, d_hot, d_hot_bits, d_hot_work;
+    bool pixel_cost_clean = false;          // the slots of d_pixel_cost that are no pixels of tile_key's image read 0 (a launch that packs
+                                            // its costs writes the pixels' slots alone and zeroes the buffer only where this is false)
+    bool cost_atomics = false;              // test hook (mipt_diag_scene_cost_atomics): never pack, one atomic per path as before
     uint32_t hot_n = 0;                     // entries of d_hot (0 = the launch was too large for 32-bit slots: no hot list)
     uint32_t hot_used = 0;                  // entries that launch itself took from the list made before it (0 = it ran without)
     // the list goes on behind its first hot_n entries, in the same cost order: list_n >= hot_n entries of d_hot, all local slots where

@@ -62,7 +62,9 @@ struct DevStats {                 // zeroed before every launch
 struct DevParams {
     uint32_t width, height, samples, max_depth;
     uint32_t seed_mode, sample_begin, sum_only, packed;
-    uint32_t accumulate, pad1;              // accumulate: hdr += this call's result (progressive rendering)
+    uint32_t accumulate;                    // hdr += this call's result (progressive rendering)
+    uint32_t cost_packed;                   // pixel_cost != NULL: 1 = a pixel's rays ride in its lane's sample counter and are stored once
+                                            // (cost_packs()), 0 = one atomic per path into pixel_cost, which the host has zeroed
     uint32_t tile_rank, tile_world, tiles_x, tiles_y;
     uint32_t n_local_tiles;
     uint32_t n_list;                        // work indices [0, n_list) take slot hot[wi] (0 = no list); pt_kernel.hip "hot pixels"
@@ -93,6 +95,12 @@ struct DevBatch {
     uint32_t tiles_recip;                   // floor((2^32 - 1) / n_local_tiles): umulhi(lt, it) is lt / n_local_tiles or up to 2 below
 };
 
+// A pixel's cost in its lane's sample counter: the samples done in the low kCostShift bits, the rays of its paths above them.  A
+// path traces at most max(max_depth, 1) rays, so neither field overflows where this holds.
+constexpr uint32_t kCostShift = 12, kCostSampleMask = (1u << kCostShift) - 1u;
+inline bool cost_packs(uint32_t samples, uint32_t max_depth) {
+    return samples <= kCostSampleMask && (unsigned long long)samples * ((unsigned long long)max_depth + 1ull) <= (0xffffffffu >> kCostShift);
+}
 constexpr int kStackLds = 16;               // per-lane traversal-stack entries held in LDS
 constexpr int kStackOvf = 48;               // further entries spilled to HBM (rarely touched)
 constexpr int kWavesPerBlock = 4;

@@ -178,6 +178,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                                            const float4 *__restrict__ rays = nullptr) {
     static_assert(BATCH || !ADAPT, "the count plane is addressed by (view, pixel): batch launches only");
     static_assert(!RAYS || (!BATCH && !ADAPT), "a ray launch has no views and no count plane");
+    constexpr bool COST = !BATCH && !RAYS;                 // the launches that can measure their pixels' costs (pr.pixel_cost)
     __shared__ uint32_t s_stack[kWavesPerBlock][kStackLds + 1][64];   // row kStackLds: scratch target of the branch-free push
     __shared__ double s_logtab[32];                                    // __logf_data.tab (16 x {invc, logc}) for gl_log10f
     __shared__ __attribute__((aligned(16))) float s_draw[kWavesPerBlock][64 * 6];                   // scatter draws of a service pass: 3 x {u_theta, u_rho} per hit lane, compacted
@@ -308,8 +309,14 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
             if (state == ST_S) {
                 if (path_done) {
                     // tile order, hot pixels: this path's rays, added to its pixel's cost (slot = local tile * 64 + pixel of the tile);
-                    // the sums per tile are taken behind the launch (pixel_reduce_kernel)
-                    if (!BATCH && !RAYS && pr.pixel_cost) atomicAdd(&pr.pixel_cost[slot], bounces + ((best_tri == kNoTri) ? 1u : 0u));
+                    // the sums per tile are taken behind the launch (pixel_reduce_kernel).  A lane has its pixel from the fetch to the
+                    // frame's store, so the sum rides in `sample` above the sample count (kCostShift; the host passes cost_packed
+                    // where neither field can overflow) and is stored once, beside the frame; else one atomic per path.
+                    if (COST) {
+                        const uint32_t path_rays = bounces + ((best_tri == kNoTri) ? 1u : 0u);
+                        if (pr.cost_packed) sample += path_rays << kCostShift;
+                        else if (pr.pixel_cost) atomicAdd(&pr.pixel_cost[slot], path_rays);
+                    }
                     const V3 res = (bounces == 0u) ? incoming : incoming / (float)bounces; // ray.rs:197-201
                     final_color = final_color + res;                                 // cpu.rs:52
                     sample += 1;
@@ -318,9 +325,10 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                         const uint32_t c = counts[view * bt.view_pixels + pix];
                         n_samples = c < pr.samples ? c : pr.samples;
                     }
-                    if (sample < n_samples) {
+                    if (((COST && pr.cost_packed) ? (sample & kCostSampleMask) : sample) < n_samples) {
                         state = ST_G;
                     } else {
+                        if (COST && pr.cost_packed) pr.pixel_cost[slot] = sample >> kCostShift;
                         if (!pr.sum_only) final_color = final_color / (ADAPT ? (float)n_samples : pr.samples_f);  // cpu.rs:60
                         float *dst = pr.hdr + (BATCH ? (size_t)view * bt.view_pixels + pix : (size_t)((!RAYS && pr.packed) ? slot : pix)) * 3;
                         if (pr.accumulate) {      // progressive rendering: add this call's samples to the running sum
@@ -414,7 +422,7 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
                 } else {
                     if (SHADING == 1 || pr.seed_mode != 0u) {                             // rt_compute.wgsl:102
                         const uint32_t px = pix % pr.width, py = pix / pr.width;
-                        rng = (pr.sample_begin + sample) * 6023u + (757283u * px + 872653746u * py);
+                        rng = (pr.sample_begin + ((COST && pr.cost_packed) ? (sample & kCostSampleMask) : sample)) * 6023u + (757283u * px + 872653746u * py);
                     }
                     const float jx = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
                     const float jy = (rand_f32(rng) * 2.0f - 1.0f) * 0.0005f;
@@ -469,6 +477,8 @@ __device__ __forceinline__ void trace_body(DevScene sc, DevParams pr, DevBatch b
         // 2 - 8 %: the host passes period 1 (mipt_api.cpp).
         bool leaf_hold;
         {
+            // (m_t and-ed with one ballot of the bare compare drops the two select / compare pairs this lowers to and measured
+            //  0.15 - 0.24 ms SLOWER per frame: tools/experiments/leaf_ballot_masks_result.txt)
             const unsigned long long m_lf = __ballot(state == ST_T && tri_cur < tri_end);
             const unsigned long long m_in = __ballot(state == ST_T && !(tri_cur < tri_end));
             const bool phase = leaf_wait == 0u || m_in == 0ull || (uint32_t)__popcll(m_lf) * pr.leaf_den >= n_t;
