@@ -29,9 +29,13 @@ def _f32_mul(a, b):
         return float(np.float32(a) * np.float32(b))
 
 
-def traverse(orc_lib, tris, nodes, ray, cull=False, margin=0.0, anyhit=False, counters=None):
+def traverse(orc_lib, tris, nodes, ray, cull=False, margin=0.0, anyhit=False, counters=None, events=None):
     """One ray.  Closest hit: -> (t bits, u bits, v bits, tree triangle index or NONE, front_face).  Occlusion (anyhit): the same
-    tuple for the FIRST triangle in visit order with has_hit && t < t_max (the bound never shrinks).  `counters` (dict) is updated."""
+    tuple for the FIRST triangle in visit order with has_hit && t < t_max (the bound never shrinks).  `counters` (dict) is updated.
+    `events` (list) records what happens to LEAVES on the way, as the kernels' stack entries see them: ("push", node, triangle
+    count, swapped, stack size after the push) when a leaf is stacked as the far child (swapped: it is the pair's first child, stacked
+    after the d1 > d2 swap), ("pop", node, triangle count, stack size before the pop) when one comes off the stack, and ("enter",
+    node, triangle count) when one is entered without the stack: the near child, or the root."""
     tris8 = tris.view(np.uint8).reshape(-1, 112)
     nodes8 = nodes.view(np.uint8).reshape(-1, 32)
     tri_base, node_base = tris8.ctypes.data, nodes8.ctypes.data
@@ -50,6 +54,15 @@ def traverse(orc_lib, tris, nodes, ray, cull=False, margin=0.0, anyhit=False, co
     c["rays"] = c.get("rays", 0) + 1
     inner = tests = 0
     max_stack = c.get("max_stack", 0)
+
+    def pop():
+        depth, top = len(stack), stack.pop()
+        if events is not None and count[top] > 0:
+            events.append(("pop", top, int(count[top]), depth))
+        return top
+
+    if events is not None and count[0] > 0:
+        events.append(("enter", 0, int(count[0])))
 
     def slab(i, max_d):
         t = orc_lib.orc_intersect_node(C.byref(o), C.byref(d), C.c_void_p(node_base + 32 * i))     # ray.rs:69-81
@@ -73,25 +86,30 @@ def traverse(orc_lib, tris, nodes, ray, cull=False, margin=0.0, anyhit=False, co
                     best = float(out[1])
             if done or not stack:
                 break
-            node = stack.pop()
+            node = pop()
             continue
         c1 = int(first[node])
         c2 = c1 + 1
         inner += 1
         max_d = _f32_mul(best, scale)
         d1, d2 = slab(c1, max_d), slab(c2, max_d)
-        if d1 > d2:                                                                                  # ray.rs:120-123
+        swapped = d1 > d2
+        if swapped:                                                                                  # ray.rs:120-123
             d1, d2, c1, c2 = d2, d1, c2, c1
         if d1 == MISS:                                                                               # ray.rs:124-130
             if not stack:
                 break
-            node = stack.pop()
+            node = pop()
         else:
             node = c1
+            if events is not None and count[c1] > 0:
+                events.append(("enter", c1, int(count[c1])))
             if d2 < MISS:                                                                            # ray.rs:133-136
                 if len(stack) < STACK_CAP:
                     stack.append(c2)
                     max_stack = max(max_stack, len(stack))
+                    if events is not None and count[c2] > 0:
+                        events.append(("push", c2, int(count[c2]), swapped, len(stack)))
                 else:
                     c["stack_overflows"] = c.get("stack_overflows", 0) + 1                           # the reference panics here
     c["inner_steps"] = c.get("inner_steps", 0) + inner
